@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: forward FFT convolution throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgA]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfgA] [--dump-outputs DIR] [--full]
 
 A "step" is one forward pass of the hot path (FFTConv1d.forward, kernel spectrum
 cached per weight version as the module does) over one synthetic batch that is
@@ -16,7 +16,11 @@ convolves its own batch shard of the same size (weak scaling); the only
 collective is the one-off broadcast of the weights from rank 0.  The timed
 region is bracketed by barrier + synchronize and the max over ranks is taken.
 
-Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline
+figure (`value`, `ms_per_step`).  `--dump-outputs DIR` writes what the last timed step computed to DIR
+(inputs are seeded, so two builds can be compared output for output).  `--full` adds everything else the
+benchmark reports: the check of the timed result against an eager forward, the HBM roofline, the eager
+end-to-end timings and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -50,6 +54,8 @@ CONFIGS = {
 # whole-node batch of the problems BASELINE.json states for 8 GPUs (--scaling strong splits THIS batch over the ranks)
 STRONG_BATCH = {"cfgA": 32, "cfgB": 16, "cfgC": 8, "cfgD": 64}
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_FULL_BYTES = 48 * 10**6    # --dump-outputs: outputs up to this size are written whole ...
+DUMP_SAMPLES = 1 << 21          # ... larger ones as this many elements at fixed, seeded positions
 
 
 def algorithmic_bytes(batch, cin, cout, groups, spatial, kernel, out_spatial):
@@ -180,6 +186,22 @@ def eager_us(fn, iters=60, warm=10):
     return e0.elapsed_time(e1) * 1e3 / iters, wall
 
 
+def dump_outputs(out_dir, y):
+    """Write the output of the timed path's last step as ``out_dir/y.npy`` (float32, its own shape).  An output
+    larger than DUMP_FULL_BYTES is written as DUMP_SAMPLES elements at fixed positions of the flattened tensor
+    (seed 0, ascending), ``y.npy``, with those positions as ``y_index.npy`` (float64): about 25 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = y.detach().reshape(-1)
+    if flat.numel() * flat.element_size() <= DUMP_FULL_BYTES:
+        np.save(os.path.join(out_dir, "y.npy"), y.detach().cpu().numpy().astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=DUMP_SAMPLES, replace=False))
+    sample = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "y.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "y_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -191,14 +213,23 @@ def main():
                          "BASELINE.json problem (cfgA 32, cfgB 16, cfgC 8, cfgD 64) is split over the ranks with shard_range "
                          "and `value` is the whole problem's outputs per second")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the eager module / uncached fft_conv timings (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: check the timed result against an eager forward, report the HBM "
+                         "roofline, the eager end-to-end timings and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output of the last one to DIR/y.npy (rank 0; a seeded sample "
+                         "with DIR/y_index.npy when the output is larger than 48 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true",
+                    help="with --full: skip the eager module / uncached fft_conv timings (profiling runs)")
     ap.add_argument("--tile", type=int, default=0, help="force the FFT tile length (0 = planner's choice)")
     ap.add_argument("--spinup-ms", type=float, default=80.0,
                     help="untimed device spin-up before the warm-up steps: the same launches, replayed for this long, so "
                          "that the timed steps see the clock the device holds in steady state, not its ramp from idle "
                          "(measured: 37.0 us per launch after 40 warm-up steps, 34.1 after 400, 33.4 after 2,000)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -330,13 +361,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, dev_ms = float(t[0]), float(t[1])
 
-    # light sanity check of the timed path's result (not a parity test: tests/ does that)
-    assert torch.isfinite(ys[0]).all() and torch.allclose(ys[0], y0, rtol=0, atol=0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ys[(steps - 1) % nbuf])     # step i wrote ys[i % nbuf] (per_graph is a multiple of nbuf)
+
+    if args.full:
+        # light sanity check of the timed path's result (not a parity test: tests/ does that)
+        assert torch.isfinite(ys[0]).all() and torch.allclose(ys[0], y0, rtol=0, atol=0)
 
     if rank == 0:
-        kernel_us = dev_ms * 1e3 / steps          # HIP-event time per launch on the launch stream
-        achieved = alg_bytes / (kernel_us * 1e-6) / 1e9
-        step_us = elapsed * 1e6 / steps           # host clock around the same steps (what `value` is made of)
         out = {
             "metric": "GSamples/s (output elems/s), forward fft_conv",
             "value": (n_out // batch) * total_batch * steps / elapsed / 1e9,
@@ -351,13 +383,17 @@ def main():
                        "tile": plan.tile, "buffer_sets": nbuf, "hip_graph": graph is not None, "launches_per_graph": per_graph if graph is not None else 0,
                        "spinup_ms": args.spinup_ms,
                        "kernel_spectrum": "cached per weight version (FFTConv module)"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc_traffic(args.config, dominant_kernel_name(plan)),
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_us": kernel_us,
-                         "kernel": dominant_kernel_name(plan),
-                         "frac_from_ms_per_step": alg_bytes / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBPS},
         }
-        if world == 1 and not args.no_end_to_end:
+        if args.full:
+            kernel_us = dev_ms * 1e3 / steps          # HIP-event time per launch on the launch stream
+            achieved = alg_bytes / (kernel_us * 1e-6) / 1e9
+            step_us = elapsed * 1e6 / steps           # host clock around the same steps (what `value` is made of)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc_traffic(args.config, dominant_kernel_name(plan)),
+                               "algorithmic_bytes_per_launch": alg_bytes, "kernel_us": kernel_us,
+                               "kernel": dominant_kernel_name(plan),
+                               "frac_from_ms_per_step": alg_bytes / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBPS}
+        if args.full and world == 1 and not args.no_end_to_end:
             # What a user's call costs end to end, launched eagerly from the host (no graph): the module with its
             # cached spectrum, and the functional fft_conv() that transforms the kernel on EVERY call like the
             # reference does (functional.py:71) and allocates its output -- the "uncached" figure of SURVEY 8d.
@@ -374,7 +410,7 @@ def main():
                 "kernel_transform_us": tr_dev,
                 "uncached_value": n_out / (max(unc_dev, unc_wall) * 1e-6) / 1e9, "unit": "us / GSamples/s",
                 "note": "eager launches, input re-read from cache (one buffer); uncached = kernel transform + forward + output allocation per call"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out))
     if world > 1:

@@ -69,7 +69,7 @@ for cfg, summ in (("cfgA", "r3f_summary.txt"), ("cfg0", "r3f_cfg0_summary.txt"),
     if cfg != "cfgA":
         bench = os.path.join(OUT, f"r3f_bench_{cfg}.json")
         others.append(f"######## {cfg}: scripts/gpu_prof_traffic.sh r3f_{cfg} --config {cfg}  (kernel trace + FETCH_SIZE + WRITE_SIZE passes, "
-                      f"KiB per launch; the JSON line is bench.py --config {cfg} --steps 100 --warmup 20 on the same box without the profiler)")
+                      f"KiB per launch; the JSON line is bench.py --full --config {cfg} --steps 100 --warmup 20 on the same box without the profiler)")
         if os.path.exists(bench):
             others.append(open(bench).read().strip())
         others.append(open(os.path.join(OUT, summ)).read().strip())

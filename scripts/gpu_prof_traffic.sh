@@ -16,7 +16,7 @@ run() {  # name, timeout, cmd...
   echo "rc=$rc"; tail -n 2 "$OUT/$name.log" | cut -c1-300
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT in $name: stopping"; exit 1; fi
 }
-BENCH="python3 $ROOTDIR/bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-end-to-end $*"
+BENCH="python3 $ROOTDIR/bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-end-to-end $*"
 run ${TAG}_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_trace" -- $BENCH
 i=0
 for PMC in "FETCH_SIZE" "WRITE_SIZE"; do

@@ -6,13 +6,13 @@ mkdir -p $OUT
 case "$1" in
   a)  # headline: rocprofv3 trace + every PMC pass, then the bench lines (default steps, and the driver's 20 / 5)
     bash scripts/gpu_prof.sh r3f || exit 1
-    timeout -k 10 400 python3 bench.py > $OUT/r3f_bench_cfgA.json 2> $OUT/r3f_bench_cfgA.err || exit 1
-    timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/r3f_bench_cfgA_driver.json 2>> $OUT/r3f_bench_cfgA.err || exit 1
+    timeout -k 10 400 python3 bench.py --full > $OUT/r3f_bench_cfgA.json 2> $OUT/r3f_bench_cfgA.err || exit 1
+    timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/r3f_bench_cfgA_driver.json 2>> $OUT/r3f_bench_cfgA.err || exit 1
     ;;
   b)  # other BASELINE configurations and the per-GPU shards: kernel stats + FETCH / WRITE passes, then the plain bench line
     for cfg in cfg0 cfgB cfgC cfgD cfgA_shard cfgB_shard cfgC_shard; do
       bash scripts/gpu_prof_traffic.sh r3f_$cfg --config $cfg > $OUT/r3f_${cfg}_traffic.log 2>&1 || exit 1
-      timeout -k 10 300 python3 bench.py --config $cfg --steps 100 --warmup 20 --no-cpu-baseline --no-end-to-end > $OUT/r3f_bench_$cfg.json 2> $OUT/r3f_bench_$cfg.err || exit 1
+      timeout -k 10 300 python3 bench.py --full --config $cfg --steps 100 --warmup 20 --no-cpu-baseline --no-end-to-end > $OUT/r3f_bench_$cfg.json 2> $OUT/r3f_bench_$cfg.err || exit 1
     done
     ;;
   c)  # rows next to the headline path, README shapes, same-GPU yardsticks, float64
@@ -21,7 +21,7 @@ case "$1" in
     timeout -k 10 300 python3 scripts/sweep_vs_rocfft.py > $OUT/r3f_sweep.jsonl 2> $OUT/r3f_sweep.err || exit 1
     timeout -k 10 200 python3 scripts/f64_check.py > $OUT/r3f_f64.txt 2>&1 || exit 1
     for cfg in readme1d readme2d readme3d; do
-      timeout -k 10 200 python3 bench.py --config $cfg --steps 100 --warmup 20 --no-cpu-baseline > $OUT/r3f_bench_$cfg.json 2> $OUT/r3f_bench_$cfg.err || exit 1
+      timeout -k 10 200 python3 bench.py --full --config $cfg --steps 100 --warmup 20 --no-cpu-baseline > $OUT/r3f_bench_$cfg.json 2> $OUT/r3f_bench_$cfg.err || exit 1
     done
     ;;
   d)  # the whole GPU suite + the driver's smoke

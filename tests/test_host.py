@@ -84,14 +84,17 @@ def test_product_package_never_imports_the_oracle():
 
 
 def test_wgrad_descriptor_query_is_safe_without_a_device():
-    """fc_wgrad1d_slices is a pure query: it must answer (0 = not covered / no device) and never raise."""
+    """fc_wgrad1d_slices is a pure query: it must answer (0 = not covered / no device) and never raise.  Strides up to 64
+    are covered on a device (fc_wgrad1d, ABI 6); beyond that, and for 2-D, the answer is 0 everywhere."""
     from fft_conv_pytorch_amd import _native
     ok = _native.conv_desc(1, 4, 8, 8, 1, (4096,), (33,), (1,), (0,), (1,), 0)
     strided = _native.conv_desc(1, 4, 8, 8, 1, (4096,), (33,), (2,), (0,), (1,), 0)
+    too_strided = _native.conv_desc(1, 4, 8, 8, 1, (4096,), (33,), (65,), (0,), (1,), 0)
     two_d = _native.conv_desc(2, 4, 8, 8, 1, (64, 64), (3, 3), (1, 1), (0, 0), (1, 1), 0)
     has_gpu = torch.cuda.is_available()
     assert (_native.wgrad1d_slices(ok) > 0) == has_gpu
-    assert _native.wgrad1d_slices(strided) == 0
+    assert (_native.wgrad1d_slices(strided) > 0) == has_gpu
+    assert _native.wgrad1d_slices(too_strided) == 0
     assert _native.wgrad1d_slices(two_d) == 0
 
 

@@ -19,10 +19,9 @@
 // first accumulate into a second LDS region.
 #pragma once
 #include "fft_engine.hpp"
+#include "axis_map.hpp"
 
 namespace fc {
-
-enum PadMode : int { PAD_CONSTANT = 0, PAD_REFLECT = 1, PAD_REPLICATE = 2, PAD_CIRCULAR = 3 };
 
 struct Conv1dArgs {
   const float* x;        // (B, Cin, L)

@@ -18,6 +18,7 @@
 
 #include "direct_f64.h"
 #include "fft_f64.h"
+#include "nd_f64.h"
 #include "fc_internal.h"
 #include "fftconv_amd.h"
 
@@ -171,6 +172,9 @@ struct fc_plan {
   int nyt, Vy;                // the same for the middle axis of a 3-D problem (one c2c launch per tile)
   int nd_cob, nd_Cog_pad;
   int f64_T, f64_V, f64_ntiles, f64_cob;   // float64 1-D FFT path (fft_f64.hip): tile, valid samples, tiles per row, out-chunk; 0 = direct kernel
+                                           // (2-D / 3-D: f64_T = the last axis' transform length)
+  int f64_t[3], f64_v[3], f64_nt[3];       // float64 N-d FFT path (nd_f64.hip): transform length, valid samples, tiles per axis
+  int f64_nb;                              // batch items per workgroup of its fused pass (f64_cob output channels each)
   int planes;                 // 1: 3-D plane-major three-launch pipeline (planes3d.hpp) instead of the five separable passes;
                               // 2: 2-D with the same thread-per-sequence column pass between row passes that keep the rows as they are
   size_t ws_a, ws_b;          // fc::f2 counts of the two workspace regions
@@ -853,6 +857,105 @@ static int plan_nd(fc_plan* p) {
   return rc;
 }
 
+// float64 2-D / 3-D plans (forward and transposed) leave the direct kernel from this many of its multiply-adds per
+// output of the FFT path: Cin/g x prod(k), divided by prod(stride) for a forward plan (its FFT computes every
+// stride-1 output and decimates).  MI355X sweep (profiles/r04_float64_nd.txt): the FFT path runs 0.36-1.0x as fast
+// as the direct kernel at 4-72, 1.6-15x at 125-2744 (2-D B4 128^2 and 3-D B2 32^3, 1 and 8 input channels, k 2-7);
+// stride-2 forward rows 0.52-0.95x at 18-50 and 1.65-2.6x at 98-196 (per stride-1 output); stride-2 transposed rows,
+// whose direct kernel still walks every tap, 1.4-4.9x at 128-1024 undivided.
+static const int64_t kF64MinMacs = 100;
+
+// One axis of a float64 N-d plan: one transform of nextpow2(Sp) points while that is <= 2048, else overlap-save tiles
+// of T >= 2 kd points (V = T - kd + 1 valid samples each) or of 2048 points (V >= 1024 for any kd <= 1025); the fewest
+// transformed points n*T, the shorter tile on a tie (an axis just past a power of two takes several short tiles rather
+// than one transform of twice its length).  Returns false if no tile fits (kd > 2048).
+static bool f64_axis_plan(int64_t Sp, int64_t Lf, int64_t kd, int* T_out, int* V_out, int* nt_out) {
+  int64_t best_cost = -1;
+  int best_T = 0;
+  auto consider = [&](int T) {
+    const int64_t V = T - kd + 1;
+    if (V < 1) return;
+    const int64_t cost = (Lf + V - 1) / V * T;
+    if (best_cost < 0 || cost < best_cost || (cost == best_cost && T < best_T)) { best_cost = cost; best_T = T; }
+  };
+  int Ts = 8;
+  while (Ts < Sp) Ts *= 2;
+  if (Ts <= 2048) consider(Ts);
+  for (int T = 8; T <= 2048; T *= 2)
+    if (T >= 2 * kd || T == 2048) consider(T);
+  if (best_T == 0) return false;
+  *T_out = best_T;
+  *V_out = (int)(best_T - kd + 1);
+  *nt_out = (int)((Lf + *V_out - 1) / *V_out);
+  return true;
+}
+
+// float64 2-D / 3-D plan on the FFT path (nd_f64.hip): per-axis transforms, channel blocking of the fused pass,
+// kernel-spectrum and workspace sizes.  Axis 0 = outermost (fused pass), nd-1 = rows, 1 = middle (3-D).  Returns false,
+// with the plan untouched (the direct kernel's state), when an axis gets no transform or a launch would exceed what one
+// dispatch can address (2^31 workgroups, 2^32 work-items).
+static bool plan_nd_f64(fc_plan* p) {
+  const fc_desc& d = p->d;
+  const int nd = p->nd;
+  int T[3] = {0, 0, 0}, V[3] = {0, 0, 0}, nt[3] = {0, 0, 0};
+  for (int i = 0; i < nd; ++i)
+    if (!f64_axis_plan(p->Sp[i], p->Lf[i], p->kd[i], &T[i], &V[i], &nt[i])) return false;
+  const int Tx = T[nd - 1], Fx = Tx / 2 + 1;
+  const size_t B = (size_t)d.batch, Ci = (size_t)d.in_channels, Co = (size_t)d.out_channels, NA = Co * p->Cig;
+  const size_t Ncol = (size_t)nt[nd - 1] * Fx;
+  const size_t t_outer = (size_t)T[0] * (nd == 3 ? (size_t)T[1] : 1);
+  const size_t spectrum_bytes = (size_t)d.groups * p->Cog * p->Cig * t_outer * Fx * sizeof(double2);
+  // fused pass: 8 accumulator slots per thread and bin, shared by nb batch items x cob output channels; spare slots
+  // (few output channels) and a large kernel spectrum both make batch items share each read of it
+  int cob = std::min(8, p->Cog), nb = 1;
+  if (cob <= 2 && d.batch >= 3) nb = 4;
+  else if (cob <= 4 && d.batch >= 2) nb = 2;
+  else if (spectrum_bytes >= ((size_t)32 << 20) && d.batch >= 2) { nb = 2; cob = 4; }
+  // every launch of the forward and of the kernel transform within one dispatch (grid and work-items as nd_f64.hip)
+  bool fits = true;
+  auto launch = [&](int t, size_t seqs) {        // seqs: sequences (column groups count NS sequences each)
+    const size_t ns = (size_t)fc::nd_f64_nseq(t), grid = (seqs + ns - 1) / ns;
+    fits = fits && grid < ((size_t)1 << 31) && grid * ns * (size_t)(t / 2) < ((size_t)1 << 32);
+  };
+  auto cols = [&](int t, size_t lines, size_t ncol) {
+    const size_t ns = (size_t)fc::nd_f64_nseq(t);
+    launch(t, lines * ((ncol + ns - 1) / ns) * ns);
+  };
+  size_t rows_in = B * Ci, rows_out = B * Co, krows = NA;
+  for (int i = 0; i < nd - 1; ++i) { rows_in *= d.spatial[i]; rows_out *= p->out_sp[i]; krows *= d.kernel[i]; }
+  launch(Tx, (rows_in + 1) / 2 * nt[nd - 1]);
+  launch(Tx, (krows + 1) / 2);
+  launch(Tx, (rows_out + 1) / 2 * nt[nd - 1]);
+  size_t ncol_outer = Ncol, a, b;
+  if (nd == 3) {
+    const size_t Mcol = (size_t)nt[1] * T[1] * Ncol;
+    cols(T[1], B * Ci * d.spatial[0] * nt[1], Ncol);                 // middle axis forward
+    cols(T[1], B * Co * p->out_sp[0] * nt[1], Ncol);                 // and back
+    cols(T[1], NA * d.kernel[0], Fx);                                // kernel: middle axis
+    cols(T[0], NA, (size_t)T[1] * Fx);                               // kernel: outer axis
+    ncol_outer = Mcol;
+    a = std::max({B * Ci * d.spatial[0] * d.spatial[1] * Ncol, NA * d.kernel[0] * d.kernel[1] * Fx,   // rows
+                  B * Co * p->out_sp[0] * Mcol});                                                     // fused pass out
+    b = std::max({B * Ci * d.spatial[0] * Mcol, NA * d.kernel[0] * T[1] * Fx,                        // middle axis
+                  B * Co * p->out_sp[0] * p->out_sp[1] * Ncol});                                      // middle axis back
+  } else {
+    cols(T[0], NA, Fx);                                              // kernel: outer axis
+    a = std::max(B * Ci * d.spatial[0] * Ncol, NA * d.kernel[0] * Fx);          // rows of the signal / of the taps
+    b = B * Co * p->out_sp[0] * Ncol;                                              // after the fused pass
+  }
+  cols(T[0], (B + nb - 1) / nb * d.groups * ((p->Cog + cob - 1) / cob) * nt[0], ncol_outer);   // fused pass
+  if (!fits) return false;
+  for (int i = 0; i < nd; ++i) { p->f64_t[i] = T[i]; p->f64_v[i] = V[i]; p->f64_nt[i] = nt[i]; }
+  p->f64_T = Tx;
+  p->spectrum_bytes = spectrum_bytes;
+  p->ws_a = a;
+  p->ws_b = b;
+  p->workspace_bytes = (a + b) * sizeof(double2);
+  p->f64_cob = cob;
+  p->f64_nb = nb;
+  return true;
+}
+
 static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** out_plan);
 
 int fc_plan_create(const fc_desc* desc, fc_plan** out_plan) { return plan_create_impl(desc, nullptr, out_plan); }
@@ -961,10 +1064,23 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
     p->workspace_bytes = 0;
     p->tile = nullptr;
     rc = FC_OK;
-    // 1-D, not transposed, at least 16 taps, dilated extent within half of a 2048-point tile: the FFT path in double
-    // precision (fft_f64.hip).  FFTCONV_F64_FFT=0 keeps the direct kernel (A/B runs, tests).
+    // The FFT paths in double precision: 1-D plans, forward and transposed, with at least 16 taps (fft_f64.hip);
+    // 2-D / 3-D plans, forward and transposed, from kF64MinMacs multiply-adds of the direct kernel per output of the FFT
+    // path (nd_f64.hip).
+    // A dilated extent past 1025 on any axis keeps the direct kernel.  FFTCONV_F64_FFT=0 keeps it for everything (A/B
+    // runs, tests).  Chosen from the descriptor alone, with no device query: float64 plans can be made anywhere.
+    // FFTCONV_F64_FFT=2 (crossover sweeps) takes the 2-D / 3-D FFT path at any size.
     const char* env = getenv("FFTCONV_F64_FFT");
-    if ((!env || atoi(env) != 0) && d.ndim == 1 && !d.transposed && d.kernel[0] >= 16 && p->kd[0] <= 1025 &&
+    const bool fft_on = !env || atoi(env) != 0;
+    const bool force_nd = env && atoi(env) == 2;
+    int64_t macs = p->Cig, strides = 1;      // multiply-adds of the direct kernel per output (x strides: per FFT output)
+    bool kd_ok = true;
+    for (int i = 0; i < d.ndim; ++i) {
+      macs *= d.kernel[i];
+      if (!d.transposed) strides *= d.stride[i];
+      kd_ok = kd_ok && p->kd[i] <= 1025;
+    }
+    if (fft_on && kd_ok && d.ndim == 1 && d.kernel[0] >= 16 &&
         (int64_t)d.batch * d.groups * ((p->out_sp[0] + 255) / 256) < 0x40000000) {
       int T = 256;
       while (T < 2 * p->kd[0] && T < 2048) T *= 2;
@@ -984,6 +1100,8 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
       p->f64_cob = std::min(cob, std::max(p->Cog, 1));
       p->Lfull = p->Lf[0];
       p->spectrum_bytes = (size_t)d.out_channels * p->Cig * T * 2 * sizeof(double);
+    } else if (fft_on && kd_ok && d.ndim > 1 && (force_nd || macs >= kF64MinMacs * strides)) {
+      (void)plan_nd_f64(p);              // false: the direct kernel, as set up above
     }
   } else if (d.ndim == 1) rc = plan_1d(p);
   else rc = plan_nd(p);
@@ -1130,6 +1248,11 @@ int fc_plan_layout(const fc_plan* plan, int32_t layout[8]) {
   layout[0] = p.tile ? p.tile->T : 0;
   layout[1] = p.ph; layout[2] = p.nseg; layout[3] = p.seg_taps;
   layout[4] = p.diag; layout[5] = p.bd_gs; layout[6] = p.dense ? 2 : p.wide; layout[7] = p.pers_nb;
+  if (p.d.dtype == FC_F64 && p.nd != 1 && p.f64_T) {   // float64 N-d: [outermost T, Tx, middle T (3-D)]
+    for (int i = 0; i < 8; ++i) layout[i] = 0;
+    layout[0] = p.f64_t[0]; layout[1] = p.f64_t[p.nd - 1]; layout[2] = p.nd == 3 ? p.f64_t[1] : 0;
+    return FC_OK;
+  }
   if (p.nd != 1) {   // N-d: the spectrum is laid out over the row / middle-axis transform lengths too
     layout[1] = p.tx ? p.tx->T : 0; layout[2] = p.tm ? p.tm->T : 0; layout[3] = p.nd_cob;   // (x tiles share one kernel spectrum)
     layout[4] = layout[5] = layout[6] = 0;
@@ -1155,10 +1278,134 @@ long long fc_debug_grid(const fc_plan* plan) {
 static void fill_f64_args(const fc_plan& p, fc::FftF64Args* a) {
   a->B = (int)p.d.batch; a->Cin = (int)p.d.in_channels; a->Cout = (int)p.d.out_channels; a->G = (int)p.d.groups;
   a->Cig = p.Cig; a->Cog = p.Cog;
-  a->L = (int)p.d.spatial[0]; a->pad = (int)p.d.padding[0]; a->pad_mode = p.d.padding_mode;
-  a->K = (int)p.d.kernel[0]; a->dil = (int)p.d.dilation[0]; a->stride = (int)p.d.stride[0];
+  a->L = (int)p.d.spatial[0]; a->pad = p.padl[0]; a->pad_mode = p.d.padding_mode;
+  a->K = (int)p.d.kernel[0]; a->dil = (int)p.d.dilation[0]; a->stride = p.ostride[0];
+  a->up = p.up[0]; a->transposed = p.d.transposed;
   a->T = p.f64_T; a->V = p.f64_V; a->ntiles = p.f64_ntiles; a->Lfull = p.Lf[0]; a->Lout = (int)p.out_sp[0];
   a->cob = p.f64_cob; a->n_ochunks = (p.Cog + p.f64_cob - 1) / p.f64_cob;
+}
+
+// ---- float64 2-D / 3-D (nd_f64.hip).  Axis 0 = outermost, nd-1 = rows (x), 1 = middle (3-D); see nd_f64.h for layouts.
+static fc::AxisMap f64_map(const fc_plan& p, int i) {
+  fc::AxisMap m;
+  m.size = (int)p.d.spatial[i]; m.pad = p.padl[i]; m.mode = p.d.padding_mode; m.up = p.up[i];
+  return m;
+}
+
+// kernel spectrum: the forward passes on the dilated taps (flipped, channels exchanged for a transposed plan), the
+// last one conjugating and scaling by 1/prod(T); ndim launches
+static int transform_kernel_nd_f64(const fc_plan& p, const double* w, double2* H, double2* ws, hipStream_t st) {
+  const int nd = p.nd, X = nd - 1;
+  const int Tx = p.f64_t[X], Fx = Tx / 2 + 1;
+  const long long NA = p.d.out_channels * (long long)p.Cig;
+  const int flip = p.d.transposed;
+  double2* wsA = ws;
+  double2* wsB = ws + p.ws_a;
+  fc::RowsF64Args r{};
+  r.src = w; r.dst = wsA;
+  r.NR = nd == 3 ? (int)(p.d.kernel[0] * p.d.kernel[1]) : (int)p.d.kernel[0];
+  r.R = NA * r.NR; r.Sx = (int)p.d.kernel[X];
+  r.T = Tx; r.V = Tx; r.nt = 1; r.Fx = Fx;
+  r.from_kernel = 1; r.K = (int)p.d.kernel[X]; r.dil = (int)p.d.dilation[X]; r.kd = (int)p.kd[X]; r.flip = flip;
+  if (flip) { r.tw_Cig = p.Cig; r.tw_Cog = p.Cog; }
+  FC_HIP(fc::launch_rows_r2c_f64(r, st));
+  double scale = 1.0;
+  for (int i = 0; i < nd; ++i) scale /= (double)p.f64_t[i];
+  fc::ColF64Args c{};
+  c.mode = 1; c.nt = 1; c.flip = flip;
+  if (nd == 3) {
+    // rows [img][kz][ky][Fx] -> [img][kz][Ty][Fx]
+    const int Ty = p.f64_t[1];
+    c.src = wsA; c.dst = wsB; c.nlines = NA * p.d.kernel[0]; c.ncol = Fx; c.T = Ty; c.V = Ty;
+    c.src_line = p.d.kernel[1] * (long long)Fx; c.src_pt = Fx;
+    c.dst_line = (long long)Ty * Fx; c.dst_pt = Fx; c.dst_tile = 0;
+    c.K = (int)p.d.kernel[1]; c.dil = (int)p.d.dilation[1]; c.kd = (int)p.kd[1];
+    FC_HIP(fc::launch_col_f64(c, st));
+    // [img][kz][Ty*Fx] -> H[img][Tz][Ty*Fx]
+    const int Tz = p.f64_t[0];
+    c.src = wsB; c.dst = H; c.nlines = NA; c.ncol = Ty * Fx; c.T = Tz; c.V = Tz;
+    c.src_line = p.d.kernel[0] * (long long)Ty * Fx; c.src_pt = (long long)Ty * Fx;
+    c.dst_line = (long long)Tz * Ty * Fx; c.dst_pt = (long long)Ty * Fx;
+    c.K = (int)p.d.kernel[0]; c.dil = (int)p.d.dilation[0]; c.kd = (int)p.kd[0];
+  } else {
+    // rows [img][ky][Fx] -> H[img][Ty][Fx]
+    const int Ty = p.f64_t[0];
+    c.src = wsA; c.dst = H; c.nlines = NA; c.ncol = Fx; c.T = Ty; c.V = Ty;
+    c.src_line = p.d.kernel[0] * (long long)Fx; c.src_pt = Fx;
+    c.dst_line = (long long)Ty * Fx; c.dst_pt = Fx;
+    c.K = (int)p.d.kernel[0]; c.dil = (int)p.d.dilation[0]; c.kd = (int)p.kd[0];
+  }
+  c.conj_scale = 1; c.scale = scale;
+  FC_HIP(fc::launch_col_f64(c, st));
+  return FC_OK;
+}
+
+// forward: rows, (middle,) fused outer pass, (middle back,) rows back -- three launches in 2-D, five in 3-D
+static int forward_nd_f64(const fc_plan& p, const double* x, const double2* H, const double* bias, double* y,
+                          double2* ws, hipStream_t st) {
+  const int nd = p.nd, X = nd - 1;
+  const int Tx = p.f64_t[X], Fx = Tx / 2 + 1;
+  const long long B = p.d.batch, Ci = p.d.in_channels, Co = p.d.out_channels;
+  const long long Ncol = (long long)p.f64_nt[X] * Fx;
+  double2* wsA = ws;
+  double2* wsB = ws + p.ws_a;
+  // rows of the signal: (b, ci, [z,] y) rows that exist in the input
+  fc::RowsF64Args r{};
+  r.src = x; r.dst = wsA;
+  r.NR = 1;
+  for (int i = 0; i < X; ++i) r.NR *= (int)p.d.spatial[i];
+  r.R = B * Ci * r.NR; r.Sx = (int)p.d.spatial[X];
+  r.T = Tx; r.V = p.f64_v[X]; r.nt = p.f64_nt[X]; r.Fx = Fx; r.mx = f64_map(p, X);
+  FC_HIP(fc::launch_rows_r2c_f64(r, st));
+  const double2* fsrc = wsA;
+  long long ncol = Ncol, Tmid = 1;
+  if (nd == 3) {
+    // middle axis: [img*Sz][Sy][Ncol] -> [img*Sz][nty*Ty][Ncol]
+    const int Ty = p.f64_t[1];
+    fc::ColF64Args c{};
+    c.mode = 0; c.src = wsA; c.dst = wsB; c.nlines = B * Ci * p.d.spatial[0]; c.ncol = (int)Ncol;
+    c.T = Ty; c.V = p.f64_v[1]; c.nt = p.f64_nt[1]; c.m = f64_map(p, 1);
+    c.src_line = p.d.spatial[1] * Ncol; c.src_pt = Ncol;
+    c.dst_line = (long long)p.f64_nt[1] * Ty * Ncol; c.dst_tile = (long long)Ty * Ncol; c.dst_pt = Ncol;
+    FC_HIP(fc::launch_col_f64(c, st));
+    fsrc = wsB;
+    ncol = c.dst_line;
+    Tmid = Ty;
+  }
+  // outermost axis: [b*Cin + ci][S0][ncol] -> [b*Cout + co][O0][ncol]
+  fc::FusedF64Args f{};
+  f.src = fsrc; f.H = H; f.dst = nd == 3 ? wsA : wsB;
+  f.ncol = (int)ncol; f.src_img = p.d.spatial[0] * ncol; f.src_pt = ncol;
+  f.dst_img = p.out_sp[0] * ncol; f.dst_pt = ncol;
+  f.T = p.f64_t[0]; f.V = p.f64_v[0]; f.nt = p.f64_nt[0]; f.m = f64_map(p, 0);
+  f.B = (int)B; f.Cin = (int)Ci; f.Cout = (int)Co; f.G = (int)p.d.groups; f.Cig = p.Cig; f.Cog = p.Cog;
+  f.cob = p.f64_cob; f.n_ochunks = (p.Cog + p.f64_cob - 1) / p.f64_cob; f.nb = p.f64_nb;
+  f.Lf = p.Lf[0]; f.ostride = p.ostride[0];
+  f.Ncol = (int)Ncol; f.Tmid = (int)Tmid; f.Fx = Fx; f.Hcols = (int)(Tmid * Fx);
+  FC_HIP(fc::launch_fused_f64(f, st));
+  const double2* rsrc = f.dst;
+  if (nd == 3) {
+    // middle axis back: [(b,co,zo)][nty*Ty][Ncol] -> [(b,co,zo)][Oy][Ncol]
+    const int Ty = p.f64_t[1];
+    fc::ColF64Args c{};
+    c.mode = 2; c.src = wsA; c.dst = wsB; c.nlines = B * Co * p.out_sp[0]; c.ncol = (int)Ncol;
+    c.T = Ty; c.V = p.f64_v[1]; c.nt = p.f64_nt[1];
+    c.src_line = ncol; c.src_tile = (long long)Ty * Ncol; c.src_pt = Ncol;
+    c.dst_line = p.out_sp[1] * Ncol; c.dst_pt = Ncol;
+    c.Lf = p.Lf[1]; c.ostride = p.ostride[1];
+    FC_HIP(fc::launch_col_f64(c, st));
+    rsrc = wsB;
+  }
+  // rows back: [(b, co, [zo,] yo)][ntx][Fx] -> y
+  fc::RowsC2RF64Args o{};
+  o.src = rsrc; o.y = y; o.bias = bias;
+  o.rows_per_co = 1;
+  for (int i = 0; i < X; ++i) o.rows_per_co *= p.out_sp[i];
+  o.R = B * Co * o.rows_per_co; o.Cout = (int)Co;
+  o.T = Tx; o.V = p.f64_v[X]; o.nt = p.f64_nt[X]; o.Fx = Fx; o.Lf = p.Lf[X]; o.ostride = p.ostride[X];
+  o.Ox = (int)p.out_sp[X];
+  FC_HIP(fc::launch_rows_c2r_f64(o, st));
+  return FC_OK;
 }
 
 int fc_transform_kernel(const fc_plan* plan, const float* weight, void* w_hat, void* workspace, void* hip_stream) {
@@ -1167,6 +1414,10 @@ int fc_transform_kernel(const fc_plan* plan, const float* weight, void* w_hat, v
   (void)workspace;
   hipStream_t st = (hipStream_t)hip_stream;
   const fc_plan& p = *plan;
+  if (p.d.dtype == FC_F64 && p.f64_T && p.nd > 1) {
+    if (!workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
+    return transform_kernel_nd_f64(p, (const double*)weight, (double2*)w_hat, (double2*)workspace, st);
+  }
   if (p.d.dtype == FC_F64 && p.f64_T) {
     fc::FftF64Args a{};
     fill_f64_args(p, &a);
@@ -1287,6 +1538,12 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
   hipStream_t st = (hipStream_t)hip_stream;
   const fc_plan& p = *plan;
   if (p.d.has_bias && !bias) return fail(FC_ERR_INVALID, "plan was created with has_bias=1 but bias is NULL");
+  if (p.d.dtype == FC_F64 && p.f64_T && p.nd > 1) {
+    if (stamps) return fail(FC_ERR_UNSUPPORTED, "no timestamp hook in the float64 kernels");
+    if (!workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
+    return forward_nd_f64(p, (const double*)x, (const double2*)w_hat, p.d.has_bias ? (const double*)bias : nullptr,
+                          (double*)y, (double2*)workspace, st);
+  }
   if (p.d.dtype == FC_F64 && p.f64_T) {
     if (stamps) return fail(FC_ERR_UNSUPPORTED, "no timestamp hook in the float64 kernels");
     fc::FftF64Args a{};

@@ -6,12 +6,14 @@ namespace fc {
 
 struct FftF64Args {
   const double* x;       // (B, Cin, L)
-  const double* w;       // (Cout, Cin/G, K)            (kernel transform only)
+  const double* w;       // (Cout, Cin/G, K) or, transposed, (Cin, Cout/G, K)   (kernel transform only)
   double2* wspec;        // [G][Cog][Cig][T]  H = conj(FFT_T(dilated taps)) / T
   const double* bias;    // (Cout) or null
   double* y;             // (B, Cout, Lout)
   int B, Cin, Cout, G, Cig, Cog;
   int L, pad, pad_mode, K, dil, stride;
+  int up, transposed;    // transposed plan: input spread over a grid of `up` (= its stride), taps flipped, weight
+                         // (Cin, Cout/G, K); `pad` is then the left offset kd - 1 - padding and `stride` 1
   int T, V, ntiles, Lfull, Lout;
   int cob, n_ochunks;    // output channels per workgroup (<= 8)
 };

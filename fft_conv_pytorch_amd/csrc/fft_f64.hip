@@ -8,12 +8,15 @@
 // twiddles from a table the workgroup builds with sincospi), two real channels per complex sequence, the output
 // channels' spectra accumulated in registers over the input channels (a thread owns bins t and t + T/2).  It is not
 // tuned like the packed-fp32 engine (fft_engine.hpp is written on v_pk_*_f32 pairs and 8-byte LDS slots); it exists so
-// that float64 results come from the same transform-domain arithmetic as the reference's at FFT cost.  2-D / 3-D and
-// transposed float64 plans keep the direct kernel.
+// that float64 results come from the same transform-domain arithmetic as the reference's at FFT cost.  A transposed
+// plan (functional.py:126-162 of the reference) runs the same kernels: its input spread over the stride's grid behind
+// a left offset of kd - 1 - padding (which may be negative), its taps flipped and read with the channels exchanged.
+// 2-D / 3-D float64 plans run nd_f64.hip.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 
+#include "axis_map.hpp"
 #include "fft_f64.h"
 
 namespace fc {
@@ -21,14 +24,6 @@ namespace {
 
 __device__ __forceinline__ double2 cmul_d(double2 a, double2 b) {
   return make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
-}
-
-__device__ __forceinline__ int src_index_d(int pos, int size, int pad, int mode) {   // unpadded coordinate or -1 (zero)
-  if ((unsigned)pos < (unsigned)size) return pos;
-  if (pos < -pad || pos >= size + pad || mode == 0) return -1;
-  if (mode == 1) return pos < 0 ? -pos : 2 * (size - 1) - pos;      // reflect
-  if (mode == 2) return pos < 0 ? 0 : size - 1;                     // replicate
-  return pos < 0 ? pos + size : pos - size;                          // circular
 }
 
 // Stockham radix-2, T points, T/2 threads, natural order in (buffer `a`) and out (returned pointer: a or b).
@@ -66,13 +61,17 @@ __global__ __launch_bounds__(1024) void spectrum_f64_kernel(const FftF64Args a) 
   double2* bufB = lds64 + T;
   double2* tw = lds64 + 2 * T;
   const int oi = blockIdx.x;                       // o_all * Cig + i
-  const double* wrow = a.w + (size_t)oi * a.K;
+  // transposed: the weight is (Cin, Cout/g, K) and H[g][o][i] holds the taps of w[g*Cig + i][o] back to front
+  const int i_ = oi % a.Cig, go = oi / a.Cig;
+  const double* wrow = a.w + (size_t)(a.transposed ? ((go / a.Cog) * a.Cig + i_) * a.Cog + go % a.Cog : oi) * a.K;
+  const int kd = (a.K - 1) * a.dil + 1;
   build_table(tw, T, t);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int n = t + h * (T >> 1);
-    const int tap = n / a.dil;
-    bufA[n] = make_double2((tap * a.dil == n && tap < a.K) ? wrow[tap] : 0.0, 0.0);
+    const int pp = a.transposed ? kd - 1 - n : n;
+    const int tap = pp >= 0 ? tap_src(pp, a.dil, a.K) : -1;
+    bufA[n] = make_double2(tap >= 0 ? wrow[tap] : 0.0, 0.0);
   }
   __syncthreads();
   double2* r = fft_stockham<-1>(bufA, bufB, tw, T, t);
@@ -98,7 +97,8 @@ __global__ __launch_bounds__(1024) void conv1d_f64_kernel(const FftF64Args a) {
   const int g = id % a.G;
   const int b = id / a.G;
   build_table(tw, T, t);
-  const int pos0 = tile * a.V - a.pad;                 // source position of the tile's first sample
+  const AxisMap map{a.L, a.pad, a.pad_mode, a.up};    // a.pad: left offset (padding; kd - 1 - padding transposed)
+  const int p0 = tile * a.V;                           // padded position of the tile's first sample
   const int nout = min(a.cob, a.Cog - oc * a.cob);
   double2 acc[8][2];
 #pragma unroll
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(1024) void conv1d_f64_kernel(const FftF64Args a) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int n = t + h * half;
-      const int q = src_index_d(pos0 + n, a.L, a.pad, a.pad_mode);
+      const int q = axis_src(map, p0 + n);
       bufA[n] = make_double2(q >= 0 ? xa[q] : 0.0, (q >= 0 && two) ? xb[q] : 0.0);
     }
     __syncthreads();

@@ -20,25 +20,6 @@
 
 namespace fc {
 
-// Index map of one padded axis: position p in [0, n_padded) -> source index or -1 (zero).
-struct AxisMap {
-  int size;       // unpadded extent
-  int pad;        // left padding (may be negative for a transposed plan)
-  int mode;       // PadMode
-  int up;         // transposed plan: source spread over a grid of this step
-};
-__device__ __forceinline__ int axis_src(const AxisMap& m, int p) {   // p: padded coordinate
-  const int pos = p - m.pad;
-  if (m.up > 1) {
-    const int q = pos / m.up;
-    return (pos >= 0 && q * m.up == pos && q < m.size) ? q : -1;
-  }
-  if ((unsigned)pos < (unsigned)m.size) return pos;
-  if (pos < -m.pad || pos >= m.size + m.pad || m.mode == PAD_CONSTANT) return -1;
-  if (m.mode == PAD_REFLECT) return pos < 0 ? -pos : 2 * (m.size - 1) - pos;
-  if (m.mode == PAD_REPLICATE) return pos < 0 ? 0 : m.size - 1;
-  return pos < 0 ? pos + m.size : pos - m.size;
-}
 // Image index as the pass counts it -> image index in the caller's tensor.  Off (identity) for a convolution; the
 // weight-gradient plans (fc_wgrad_nd) read the signal and the output gradient with batch and channels exchanged
 // and write dW in the weight layout, without a transposed copy:  img = (q0*n1 + q1)*n2 + q2  ->  q0*s0 + q1*s1 + q2*s2.
@@ -50,11 +31,6 @@ __device__ __forceinline__ size_t map_img(const ImgMap& m, int img) {
   if (!m.on) return (size_t)img;
   const int q2 = img % m.n2, t = img / m.n2;
   return (size_t)((long long)(t / m.n1) * m.s0 + (long long)(t % m.n1) * m.s1 + (long long)q2 * m.s2);
-}
-// Kernel taps: position p -> tap index p/dil if p is a multiple of dil and in range.
-__device__ __forceinline__ int tap_src(int p, int dil, int k) {
-  const int t = p / dil;
-  return (t * dil == p && t < k) ? t : -1;
 }
 
 // ------------------------------------------------------------------------------------------

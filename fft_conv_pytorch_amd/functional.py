@@ -31,7 +31,8 @@ def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
             f"(no CPU fallback). Move the tensor to 'cuda'.")
     if t.dtype != dtype or dtype not in _DTYPE_CODES:
         raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; signal, kernel and bias must share one of "
-                        f"float32 (the FFT kernels), float64 (direct float64 kernel) or float16 / bfloat16 (computed in "
+                        f"float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
+                        f"their crossover) or float16 / bfloat16 (computed in "
                         f"float32)")
 
 

@@ -33,8 +33,10 @@ enum fc_pad_mode { FC_PAD_CONSTANT = 0, FC_PAD_REFLECT = 1, FC_PAD_REPLICATE = 2
 enum fc_dtype {
   FC_F32 = 0,  /* the FFT kernels; every float* below is float */
   FC_F64 = 1   /* float64 tensors: x, weight, w_hat, bias and y are double (pass them through the float* / void*
-                  parameters); a direct time-domain kernel computes the same function in float64 (the reference is
-                  dtype-agnostic); fc_wgrad1d and the profiling hook are float32-only */
+                  parameters); double-precision FFT kernels compute the same function (the reference is dtype-agnostic):
+                  1-D plans with >= 16 taps, 2-D / 3-D plans from 100 multiply-adds per output (Cin/groups x
+                  prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  N-d plans need
+                  fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook are float32-only */
 };
 
 /* Problem descriptor: the arguments of functional.py:19-28 after to_ntuple

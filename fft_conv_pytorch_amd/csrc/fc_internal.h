@@ -1,4 +1,4 @@
-// fc_internal.h -- glue between the C ABI (fc_api.cpp) and the per-tile kernel TUs.
+// fc_internal.h -- glue between the host planner (fc_plan.h) and the per-tile kernel TUs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "conv1d_fused.hpp"

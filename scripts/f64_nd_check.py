@@ -1,6 +1,6 @@
 """float64 2-D / 3-D and transposed convolutions: the FFT path (csrc/nd_f64.hip) against the direct kernel
 (FFTCONV_F64_FFT=0) and the reference's torch.fft formulation (rfftn / einsum / irfftn) on the same GPU, plus the
-crossover sweep that sets the planner's threshold (kF64MinMacs in csrc/fc_api.cpp).
+crossover sweep that sets the planner's threshold (kF64MinMacs in csrc/host_f64.cpp).
 Usage: python scripts/f64_nd_check.py [--sweep-only | --no-sweep | --cfgc-only]
 (the sweep times the FFT path below the crossover too: FFTCONV_F64_FFT=2 plans every shape the path can run)"""
 import os

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Forward time of a few 8->8 1-D shapes under the flavour forced by FFTCONV_TILE / FFTCONV_PERS (or the
-planner's own choice when unset): used to check the planner's table (fc_api.cpp: choose_fast_path)."""
+planner's own choice when unset): used to check the planner's table (host_1d.cpp: choose_fast_path)."""
 import os
 import sys
 

@@ -468,7 +468,7 @@ AUTOTILE_CASES = [
 
 @pytest.mark.parametrize("case", AUTOTILE_CASES, ids=[f"{c[0]}d-{'x'.join(map(str, c[5]))}-{c[9]}" for c in AUTOTILE_CASES])
 def test_rows_just_past_a_power_of_two_run_in_tiles_and_match_torch(case, monkeypatch):
-    """The planner cuts rows / the middle axis into overlap-save tiles where that saves >= 15 % of the points (fc_api.cpp
+    """The planner cuts rows / the middle axis into overlap-save tiles where that saves >= 15 % of the points (host_nd.cpp
     plan_nd): forward, dX, dW and db against torch float64, and the forward against the single-transform plan (knobs = 0)."""
     from fft_conv_pytorch_amd import _native
     from fft_conv_pytorch_amd.functional import fft_conv, _plan_for

@@ -23,8 +23,19 @@ EXPORTS = (
     "fc_version", "fc_last_error", "fc_plan_create", "fc_plan_destroy", "fc_output_shape",
     "fc_kernel_spectrum_bytes", "fc_workspace_bytes", "fc_plan_tile", "fc_plan_layout", "fc_transform_kernel",
     "fc_forward", "fc_forward_stamped", "fc_wgrad1d_slices", "fc_wgrad1d", "fc_wgrad1d_db", "fc_wgrad1d_db_supported",
-    "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd",
+    "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd", "fc_debug_route",
 )
+
+# words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
+ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd")
+ROUTE_WORDS = {
+    "f32_1d": ("T", "ntiles", "pers_nb", "ph", "ph2", "slot_tiles", "nseg", "diag", "bd_gs", "wide", "dense",
+               "chunk_launches", "accumulate", "n_ochunks", "pers_items"),
+    "f32_nd": ("T", "ntiles", "Tx", "nxt", "Tm", "nyt", "planes", "cob", "accumulate"),
+    "f64_direct": (),
+    "f64_fft_1d": ("T", "ntiles", "cob"),
+    "f64_fft_nd": ("t0", "t1", "t2", "nt0", "nt1", "nt2", "nb", "cob"),
+}
 
 
 class FcDesc(ctypes.Structure):
@@ -99,6 +110,8 @@ def load_library() -> ctypes.CDLL:
         lib.fc_plan_layout.restype = i32
         lib.fc_debug_grid.argtypes = [vp]
         lib.fc_debug_grid.restype = ctypes.c_longlong
+        lib.fc_debug_route.argtypes = [vp, ctypes.POINTER(ctypes.c_int32 * 16)]
+        lib.fc_debug_route.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -175,6 +188,18 @@ class WgradPlan:
             pass
 
 
+def read_route(lib, handle) -> dict:
+    """``fc_debug_route`` as a dict: ``kind`` (a ROUTE_KINDS name) and that kind's ROUTE_WORDS (tests)."""
+    words = (ctypes.c_int32 * 16)()
+    st = lib.fc_debug_route(handle, ctypes.byref(words))
+    if st != FC_OK:
+        _raise(lib, st)
+    kind = ROUTE_KINDS[words[0]]
+    route = {"kind": kind}
+    route.update({name: int(words[1 + i]) for i, name in enumerate(ROUTE_WORDS[kind])})
+    return route
+
+
 def _raise(lib, status: int):
     msg = lib.fc_last_error().decode("utf-8", "replace")
     if status == FC_ERR_INVALID:
@@ -224,6 +249,7 @@ class Plan:
         # what the byte layout of the kernel spectrum depends on besides the descriptor: two plans with
         # equal signatures accept each other's spectra (used by the multi-GPU broadcast)
         self.layout = tuple(int(v) for v in lay)
+        self.route = read_route(lib, handle)
         self._stamps = None
 
     def signature(self) -> Tuple:

@@ -319,6 +319,38 @@ long long fc_debug_grid(const fc_plan* plan) {
   }
 }
 
+int fc_debug_route(const fc_plan* plan, int32_t route[16]) {
+  if (!plan || !route) return fail(FC_ERR_INVALID, "null argument");
+  const fc_plan& p = *plan;
+  for (int i = 0; i < 16; ++i) route[i] = 0;
+  route[0] = (int32_t)p.kind;
+  switch (p.kind) {
+    case PlanKind::F32_1D: {
+      const int32_t w[] = {p.tile->T, p.ntiles, p.f1d.pers_nb, p.f1d.ph, p.f1d.ph2, p.f1d.slot_tiles, p.f1d.nseg,
+                           p.f1d.diag, p.f1d.bd_gs, p.f1d.wide, p.f1d.dense, p.f1d.chunk_launches, p.accumulate,
+                           p.n_ochunks, p.f1d.pers_items};
+      for (int i = 0; i < 15; ++i) route[1 + i] = w[i];
+      break;
+    }
+    case PlanKind::F32_ND: {
+      const int32_t w[] = {p.tile->T, p.ntiles, p.fnd.tx->T, p.fnd.nxt, p.fnd.tm ? p.fnd.tm->T : 0, p.fnd.nyt,
+                           p.fnd.planes, p.fnd.cob, p.accumulate};
+      for (int i = 0; i < 9; ++i) route[1 + i] = w[i];
+      break;
+    }
+    case PlanKind::F64_DIRECT:
+      break;
+    case PlanKind::F64_FFT_1D:
+      route[1] = p.f64.T; route[2] = p.f64.ntiles; route[3] = p.f64.cob;
+      break;
+    case PlanKind::F64_FFT_ND:
+      for (int i = 0; i < 3; ++i) { route[1 + i] = p.f64.t[i]; route[4 + i] = p.f64.nt[i]; }
+      route[7] = p.f64.nb; route[8] = p.f64.cob;
+      break;
+  }
+  return FC_OK;
+}
+
 int fc_transform_kernel(const fc_plan* plan, const float* weight, void* w_hat, void* workspace, void* hip_stream) {
   if (!plan || !weight || !w_hat) return fail(FC_ERR_INVALID, "null argument");
   (void)hipGetLastError();   // a stale sticky error of an earlier, unrelated call (e.g. an invalidated capture) is not this call's

@@ -157,6 +157,18 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
                        void* workspace, void* hip_stream, void* stamps);
 long long fc_debug_grid(const fc_plan* plan);
 
+/* Which kernel build a plan runs, for tests (read-only: no device call, nothing a launch reads changes).
+ * route[0] = plan kind (0 float32 1-D, 1 float32 N-d, 2 float64 direct, 3 float64 1-D FFT, 4 float64 N-d FFT); then
+ *   float32 1-D:  tile, tiles, batch items per workgroup (0 = general kernel), phases, phase pairs (1) / quads (2),
+ *                 slots are tiles, segments, depthwise blocks, block-diagonal group size, wide, dense, launches per
+ *                 input chunk, running sums, out-chunks, work items
+ *   float32 N-d:  outer tile, outer tiles, x tile, x tiles, middle tile (0 in 2-D), middle tiles, planes, channel
+ *                 block, running sums
+ *   float64 1-D:  tile, tiles, channel block
+ *   float64 N-d:  tile per axis (3), tiles per axis (3), batch items per workgroup, channel block
+ * Unused words are 0.  NULL plan or array: FC_ERR_INVALID. */
+int fc_debug_route(const fc_plan* plan, int32_t route[16]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,34 @@ def _hip(x, w, b, **kw):
     return y.cpu().numpy()
 
 
+def _maxrel(a, b):
+    """Element-wise error relative to the reference's max magnitude (the bound of BASELINE.json's north_star)."""
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
+
+
+@pytest.fixture
+def knob_plans(monkeypatch):
+    """monkeypatch for knobs read at plan creation, with the plan cache emptied on the way out, failed or not: the cache
+    key does not hold the knobs, so a plan built under one must not serve a later test."""
+    from fft_conv_pytorch_amd import _native
+    yield monkeypatch
+    _native.clear_plan_cache()
+
+
+def _route(x, w, b, **kw):
+    """Plan.route of the forward plan fft_conv runs for these arguments (fc_debug_route)."""
+    from fft_conv_pytorch_amd.functional import _plan_for
+    to = lambda t: None if t is None else t.detach().float().to(DEV)
+    return _plan_for(to(x), to(w), to(b), kw.get("stride", 1), kw.get("padding", 0), kw.get("dilation", 1),
+                     kw.get("groups", 1), kw.get("padding_mode", "constant")).route
+
+
+def _assert_route(r, want, what):
+    bad = sorted(k for k, v in want.items() if r[k] != v)
+    assert r["kind"] == "f32_1d" and not bad, f"{what}: plan left its route ({bad}): {r}"
+
+
 def test_native_library_is_loaded():
     from fft_conv_pytorch_amd import _native
     lib = _native.load_library()
@@ -331,7 +359,7 @@ def test_weight_gradient_kernel(case):
 
 
 WIDE_CASES = [  # B, Cin, Cout, groups, L, K, padding, mode  (more than 8 input channels per group, k >= 97)
-    (8, 64, 64, 1, 16384, 129, 0, "constant"),
+    (8, 64, 64, 1, 16384, 129, 0, "constant"),        # (the many-channel pipeline's shape: FFTCONV_DENSE=0 below)
     (3, 16, 8, 1, 5000, 100, 16, "reflect"),
     (5, 24, 16, 1, 3000, 200, 7, "circular"),
     (2, 20, 8, 1, 2500, 700, 0, "constant"),          # 20 channels: the last chunk is half empty
@@ -341,10 +369,14 @@ WIDE_CASES = [  # B, Cin, Cout, groups, L, K, padding, mode  (more than 8 input 
 
 
 @pytest.mark.parametrize("case", WIDE_CASES)
-def test_wide_input_kernel(case):
+def test_wide_input_kernel(case, knob_plans):
     """conv1d_wide_kernel (running sums of the out-chunk in registers over the input chunks) against torch's
-    direct convolution in float64, and against the general kernel it replaces (FFTCONV_WIDE=0 plans)."""
+    direct convolution in float64.  Every case asserts that its plan runs that kernel (tile 1024, or 2048 past 768
+    dilated taps); the many-channel pipeline, which the first shape would take, is switched off."""
+    from fft_conv_pytorch_amd import _native
     from fft_conv_pytorch_amd.functional import fft_conv
+    knob_plans.setenv("FFTCONV_DENSE", "0")
+    _native.clear_plan_cache()
     B, cin, cout, groups, L, K, pad, mode = case
     gen = torch.Generator().manual_seed(4321 + L)
     x = torch.randn(B, cin, L, generator=gen)
@@ -352,11 +384,14 @@ def test_wide_input_kernel(case):
     b = torch.randn(cout, generator=gen)
     xp = F.pad(x.double(), [pad, pad], mode=mode) if (mode != "constant" and pad) else x.double()
     want = F.conv1d(xp, w.double(), b.double(), padding=pad if mode == "constant" else 0, groups=groups)
-    got = fft_conv(x.to(DEV), w.to(DEV), b.to(DEV), padding=pad, padding_mode=mode, groups=groups)
+    kw = dict(padding=pad, padding_mode=mode, groups=groups)
+    _assert_route(_route(x, w, b, **kw), dict(wide=1, dense=0, T=1024 if K <= 768 else 2048), case)
+    got = fft_conv(x.to(DEV), w.to(DEV), b.to(DEV), **kw)
     assert got.shape == want.shape
     err = (got.double().cpu() - want).norm().item() / want.norm().item()
     print(f"wide {case}: rel err {err:.2e}")
     assert err < REL_TOL
+    assert _maxrel(got, want) < REL_TOL
 
 
 def test_large_grouped_dilated_rows_sampled():
@@ -424,20 +459,23 @@ def test_small_batch_long_rows_use_tile_slots(batch, mode):
     b = torch.randn(8, generator=gen)
     xp = F.pad(x.double(), [pad, pad], mode=mode) if mode != "constant" else x.double()
     want = F.conv1d(xp, w.double(), b.double(), padding=pad if mode == "constant" else 0)
+    r = _route(x, w, b, padding=pad, padding_mode=mode)
+    assert r["slot_tiles"] == 1 and r["pers_nb"] > batch, r
     got = fft_conv(x.to(DEV), w.to(DEV), b.to(DEV), padding=pad, padding_mode=mode)
     assert got.shape == want.shape
     assert (got.double().cpu() - want).norm().item() / want.norm().item() < REL_TOL
+    assert _maxrel(got, want) < REL_TOL
 
 
-DEPTHWISE_CASES = [  # B, C, L, K, padding, dilation, mode
-    (8, 64, 20000, 1025, 0, 1, "constant"),
-    (3, 24, 5000, 33, 5, 1, "reflect"),
-    (1, 8, 100000, 257, 0, 1, "constant"),       # batch 1: tile slots
-    (5, 16, 9000, 129, 64, 3, "circular"),       # dilation as phases on depthwise blocks
-    (2, 40, 3000, 700, 10, 1, "replicate"),
-    (4, 12, 2000, 65, 0, 1, "constant"),         # 12 channels: the second block is half empty
-    (3, 5, 3000, 129, 7, 1, "reflect"),          # one block, 5 of 8 channels (odd count: a lone channel in a pair)
-    (2, 21, 2500, 300, 0, 2, "constant"),        # 21 channels, dilation phases
+DEPTHWISE_CASES = [  # B, C, L, K, padding, dilation, mode, route words beyond diag = 1
+    (8, 64, 20000, 1025, 0, 1, "constant", dict(T=2048, ph=1)),
+    (3, 24, 5000, 33, 5, 1, "reflect", dict(ph=1, slot_tiles=0)),
+    (1, 8, 100000, 257, 0, 1, "constant", dict(slot_tiles=1)),        # batch 1: tile slots
+    (5, 16, 9000, 300, 64, 3, "circular", dict(ph=3)),                # dilation as phases on depthwise blocks
+    (2, 40, 3000, 700, 10, 1, "replicate", dict(ph=1)),
+    (4, 12, 2000, 65, 0, 1, "constant", dict(ph=1)),                  # 12 channels: the second block is half empty
+    (3, 5, 3000, 129, 7, 1, "reflect", dict(ph=1)),      # one block, 5 of 8 channels (odd count: a lone channel in a pair)
+    (2, 21, 2500, 300, 0, 2, "constant", dict(ph=1)),    # 21 channels, dilation 2 on the dilated kernel (the planner's pick)
 ]
 
 
@@ -446,7 +484,7 @@ def test_depthwise_blocks(case):
     """groups == channels: 8-channel blocks on the batch-sharing kernel with a per-channel mix; forward,
     transposed (dX) and weight gradient against torch's direct convolution in float64."""
     from fft_conv_pytorch_amd.functional import fft_conv
-    B, C, L, K, pad, dil, mode = case
+    B, C, L, K, pad, dil, mode, want_route = case
     gen = torch.Generator().manual_seed(900 + C + K)
     x = torch.randn(B, C, L, generator=gen, dtype=torch.float64)
     w = torch.randn(C, 1, K, generator=gen, dtype=torch.float64) / K ** 0.5
@@ -455,21 +493,24 @@ def test_depthwise_blocks(case):
     xp = F.pad(xr, [pad, pad], mode=mode) if (mode != "constant" and pad) else xr
     want = F.conv1d(xp, wr, br, padding=pad if mode == "constant" else 0, dilation=dil, groups=C)
     xd, wd, bd = (t.float().to(DEV).requires_grad_() for t in (x, w, b))
-    got = fft_conv(xd, wd, bias=bd, padding=pad, dilation=dil, groups=C, padding_mode=mode)
+    kw = dict(padding=pad, dilation=dil, groups=C, padding_mode=mode)
+    _assert_route(_route(x, w, b, **kw), dict(diag=1, nseg=1, **want_route), case[:7])
+    got = fft_conv(xd, wd, bias=bd, **kw)
     gy = torch.randn(want.shape, generator=gen, dtype=torch.float64)
     want.backward(gy)
     got.backward(gy.float().to(DEV))
-    for a_, b_ in ((got, want), (xd.grad, xr.grad), (wd.grad, wr.grad), (bd.grad, br.grad)):
+    for name, a_, b_ in (("y", got, want), ("dX", xd.grad, xr.grad), ("dW", wd.grad, wr.grad), ("db", bd.grad, br.grad)):
         err = (a_.detach().double().cpu() - b_.detach()).norm().item() / b_.detach().norm().item()
-        assert err < REL_TOL, (case, err)
+        assert err < REL_TOL, (case, name, err)
+        assert _maxrel(a_, b_) < REL_TOL, (case, name, "element-wise", _maxrel(a_, b_))
 
 
-LONG_KERNEL_CASES = [  # B, Cin, Cout, groups, L, K, padding, dilation, mode
-    (2, 8, 8, 1, 20000, 5000, 0, 1, "constant"),          # batch-sharing kernel, 5 segments
-    (3, 4, 6, 1, 12000, 3000, 50, 2, "reflect"),          # general kernel, dilated extent 5999
-    (2, 16, 16, 16, 9000, 2048, 0, 1, "constant"),        # depthwise blocks, 2 segments
-    (2, 12, 8, 1, 15000, 4500, 100, 1, "circular"),       # two input chunks + segments
-    (1, 8, 8, 1, 8192, 8192, 4096, 1, "constant"),        # kernel as long as the row
+LONG_KERNEL_CASES = [  # B, Cin, Cout, groups, L, K, padding, dilation, mode, route words
+    (2, 8, 8, 1, 20000, 5000, 0, 1, "constant", dict(nseg=5, pers_nb=1, diag=0)),       # batch-sharing kernel, 5 segments
+    (3, 4, 6, 1, 12000, 3000, 50, 2, "reflect", dict(nseg=6, pers_nb=0)),               # general kernel, dilated extent 5999
+    (2, 16, 16, 16, 9000, 2048, 0, 1, "constant", dict(nseg=2, diag=1)),                # depthwise blocks, 2 segments
+    (2, 12, 8, 1, 15000, 4500, 100, 1, "circular", dict(nseg=5, pers_nb=0, accumulate=1)),   # two input chunks + segments
+    (1, 8, 8, 1, 8192, 8192, 4096, 1, "constant", dict(nseg=8, pers_nb=1)),             # kernel as long as the row
 ]
 
 
@@ -478,7 +519,7 @@ def test_long_kernels_run_in_segments(case):
     """Kernels longer than the largest FFT tile (and 8-channel shapes beyond 1537 taps) run as segments of taps
     that accumulate into y; forward and all three gradients against torch's direct convolution in float64."""
     from fft_conv_pytorch_amd.functional import fft_conv
-    B, cin, cout, groups, L, K, pad, dil, mode = case
+    B, cin, cout, groups, L, K, pad, dil, mode, want_route = case
     gen = torch.Generator().manual_seed(333 + K)
     x = torch.randn(B, cin, L, generator=gen, dtype=torch.float64)
     w = torch.randn(cout, cin // groups, K, generator=gen, dtype=torch.float64) / (K * cin // groups) ** 0.5
@@ -487,7 +528,9 @@ def test_long_kernels_run_in_segments(case):
     xp = F.pad(xr, [pad, pad], mode=mode) if (mode != "constant" and pad) else xr
     want = F.conv1d(xp, wr, br, padding=pad if mode == "constant" else 0, dilation=dil, groups=groups)
     xd, wd, bd = (t.float().to(DEV).requires_grad_() for t in (x, w, b))
-    got = fft_conv(xd, wd, bias=bd, padding=pad, dilation=dil, groups=groups, padding_mode=mode)
+    kw = dict(padding=pad, dilation=dil, groups=groups, padding_mode=mode)
+    _assert_route(_route(x, w, b, **kw), want_route, case[:9])
+    got = fft_conv(xd, wd, bias=bd, **kw)
     assert got.shape == want.shape
     gy = torch.randn(want.shape, generator=gen, dtype=torch.float64)
     want.backward(gy)
@@ -495,13 +538,14 @@ def test_long_kernels_run_in_segments(case):
     for name, a_, b_ in (("y", got, want), ("dX", xd.grad, xr.grad), ("dW", wd.grad, wr.grad), ("db", bd.grad, br.grad)):
         err = (a_.detach().double().cpu() - b_.detach()).norm().item() / b_.detach().norm().item()
         assert err < REL_TOL, (case, name, err)
+        assert _maxrel(a_, b_) < REL_TOL, (case, name, "element-wise", _maxrel(a_, b_))
 
 
 SMALL_GROUP_CASES = [  # B, C, group size, L, K, padding, dilation, mode
     (4, 16, 2, 20000, 257, 0, 1, "constant"),
-    (3, 32, 4, 9000, 129, 30, 1, "reflect"),
-    (5, 8, 4, 5000, 513, 0, 2, "constant"),
-    (2, 24, 2, 3000, 65, 10, 1, "circular"),
+    (3, 32, 4, 9000, 257, 30, 1, "reflect"),       # (k 257: at k 129 the general kernel's 256-point tiles are cheaper)
+    (5, 8, 4, 5000, 513, 0, 2, "constant"),        # dilation as phases (pairs) on the blocks
+    (2, 24, 2, 3000, 257, 10, 1, "circular"),
     (2, 12, 4, 3000, 65, 0, 1, "constant"),        # 3 groups of 4: not a whole number of 8-channel blocks -> generic plan
 ]
 
@@ -521,10 +565,14 @@ def test_small_groups_as_block_diagonal_blocks(case):
     xp = F.pad(xr, [pad, pad], mode=mode) if (mode != "constant" and pad) else xr
     want = F.conv1d(xp, wr, br, padding=pad if mode == "constant" else 0, dilation=dil, groups=groups)
     xd, wd, bd = (t.float().to(DEV).requires_grad_() for t in (x, w, b))
-    got = fft_conv(xd, wd, bias=bd, padding=pad, dilation=dil, groups=groups, padding_mode=mode)
+    kw = dict(padding=pad, dilation=dil, groups=groups, padding_mode=mode)
+    blocks = groups % (8 // gs) == 0
+    _assert_route(_route(x, w, b, **kw), dict(bd_gs=gs if blocks else 0, pers_nb=2 if blocks else 0), case)
+    got = fft_conv(xd, wd, bias=bd, **kw)
     gy = torch.randn(want.shape, generator=gen, dtype=torch.float64)
     want.backward(gy)
     got.backward(gy.float().to(DEV))
     for name, a_, b_ in (("y", got, want), ("dX", xd.grad, xr.grad), ("dW", wd.grad, wr.grad), ("db", bd.grad, br.grad)):
         err = (a_.detach().double().cpu() - b_.detach()).norm().item() / b_.detach().norm().item()
         assert err < REL_TOL, (case, name, err)
+        assert _maxrel(a_, b_) < REL_TOL, (case, name, "element-wise", _maxrel(a_, b_))

@@ -24,6 +24,15 @@ def _rel(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
 
 
+@pytest.fixture
+def knob_plans(monkeypatch):
+    """monkeypatch for knobs read at plan creation, with the plan cache emptied on the way out, failed or not: the cache
+    key does not hold the knobs, so a plan built under one must not serve a later test."""
+    from fft_conv_pytorch_amd import _native
+    yield monkeypatch
+    _native.clear_plan_cache()
+
+
 def _gcd3(a, b, c):
     return math.gcd(a, math.gcd(b, c))
 
@@ -508,23 +517,27 @@ def test_float64_tensors_direct_kernel():
 
 
 # ----------------------------------------------------------------------------- dilation phases in pairs (8-byte accesses)
+@pytest.mark.usefixtures("knob_plans")
 def test_paired_dilation_phases_match_single_phases(monkeypatch):
-    """An even dilation runs its phases in pairs on the batch-sharing kernel: a lane loads / stores both phases of a
-    position as 8 bytes and trades halves with its partner lane (v_permlane32_swap).  Against the one-phase-per-slot
-    build (FFTCONV_PH2=0) and torch, for row ends where the odd phase is one sample shorter, odd paddings (unaligned
-    8-byte accesses), every padding mode (border tiles take the per-sample path), groups and both work-item sizes."""
+    """An even dilation can run its phases in pairs on the batch-sharing kernel: a lane loads / stores both phases of a
+    position as 8 bytes and trades halves with its partner lane (v_permlane32_swap).  Each case asserts the phases its
+    plan takes.  The first takes four, in pairs (FFTCONV_PH2=1) and singly (=0), with a row end where the phases differ
+    in length; the others run the dilated kernel (the cost model's pick at their size) across odd paddings, every padding
+    mode and groups.  All against torch in float64; tests/test_gpu_routes.py runs pairs on more shapes."""
     from fft_conv_pytorch_amd import _native
-    from fft_conv_pytorch_amd.functional import fft_conv
+    from fft_conv_pytorch_amd.functional import _plan_for, fft_conv
     gen = torch.Generator().manual_seed(2024)
-    cases = [  # batch, channels, groups, L, k, dilation, padding, mode
-        (8, 8, 1, 40001, 129, 4, 0, "constant"),        # Lfull odd: phase lengths differ
-        (4, 16, 2, 30000, 257, 2, 255, "constant"),     # odd padding
-        (3, 8, 1, 20011, 65, 6, 33, "reflect"),
-        (5, 8, 1, 9000, 33, 4, 64, "circular"),
-        (2, 24, 3, 70000, 200, 2, 7, "replicate"),
-        (16, 8, 1, 5000, 17, 4, 3, "constant"),          # short rows: mostly border tiles
+    # (the last column: the phases the planner takes -- 1 = the dilated kernel, which the cost model prefers for these
+    #  shapes; the pairs build then does not run, tests/test_gpu_routes.py runs it on more shapes)
+    cases = [  # batch, channels, groups, L, k, dilation, padding, mode, phases
+        (8, 8, 1, 40001, 129, 4, 0, "constant", 4),        # Lfull odd: phase lengths differ
+        (4, 16, 2, 30000, 257, 2, 255, "constant", 1),     # odd padding
+        (3, 8, 1, 20011, 65, 6, 33, "reflect", 1),
+        (5, 8, 1, 9000, 33, 4, 64, "circular", 1),
+        (2, 24, 3, 70000, 200, 2, 7, "replicate", 1),
+        (16, 8, 1, 5000, 17, 4, 3, "constant", 1),          # short rows: mostly border tiles
     ]
-    for B, C, g, L, k, dil, pad, mode in cases:
+    for B, C, g, L, k, dil, pad, mode, ph in cases:
         x = torch.randn(B, C, L, generator=gen).to(DEV)
         w = (torch.randn(C, C // g, k, generator=gen) / math.sqrt(C // g * k)).to(DEV)
         b = torch.randn(C, generator=gen).to(DEV)
@@ -532,6 +545,8 @@ def test_paired_dilation_phases_match_single_phases(monkeypatch):
         for ph2 in ("1", "0"):
             monkeypatch.setenv("FFTCONV_PH2", ph2)       # (read at plan creation; "1" = pairs even where quads would run)
             _native.clear_plan_cache()
+            r = _plan_for(x, w, b, (1,), (pad,), (dil,), g, mode).route
+            assert (r["ph"], r["ph2"]) == (ph, 1 if ph2 == "1" and ph > 1 else 0), (B, C, g, L, k, dil, pad, mode, r)
             outs[ph2] = fft_conv(x, w, b, padding=pad, padding_mode=mode, dilation=dil, groups=g)
         xd = x.double()
         if mode != "constant" and pad:
@@ -546,26 +561,30 @@ def test_paired_dilation_phases_match_single_phases(monkeypatch):
 
 
 # ----------------------------------------------------------------------------- dilation phases in quads (16-byte accesses)
+@pytest.mark.usefixtures("knob_plans")
 def test_dilation_phase_quads_match_pairs_and_torch(monkeypatch):
-    """A dilation that is a multiple of 4 on a full 8 -> 8 channel block runs its phases in QUADS (round 3, conv1d_pers.hpp
-    PH4): a complex sequence carries two phases of one channel, a lane loads / stores all four phases of a position as 16
-    bytes.  Against the pairs build (FFTCONV_PH2=1), the single-phase build (=0) and torch in float64: rows whose length
-    is not a multiple of 4 (the 16-byte path must fall back), odd paddings (unaligned tile positions), phases of unequal
-    length at the row end, every padding mode (border tiles), dilation 8 (two quads per batch item), groups of 8 and
-    batch sizes that leave tail items."""
+    """A dilation that is a multiple of 4 on a full 8 -> 8 channel block can run its phases in QUADS (round 3,
+    conv1d_pers.hpp PH4): a complex sequence carries two phases of one channel, a lane loads / stores all four phases of
+    a position as 16 bytes.  Each case asserts what each build (FFTCONV_PH2 = 2 / 1 / 0) runs: quads on the cfgD-like
+    grouping (groups of 8, a tail of batch items); pairs on the three dilation-4 rows whose work items hold two batch
+    items (one with L % 4 != 0, one with two groups); the dilated kernel on the rest (odd padding, dilation 8, short
+    rows).  All against torch in float64; tests/test_gpu_routes.py runs quads on more shapes."""
     from fft_conv_pytorch_amd import _native
-    from fft_conv_pytorch_amd.functional import fft_conv
+    from fft_conv_pytorch_amd.functional import _plan_for, fft_conv
     gen = torch.Generator().manual_seed(404)
-    cases = [  # batch, channels, groups, L, k, dilation, padding, mode
-        (8, 8, 1, 40000, 129, 4, 0, "constant"),         # aligned: the 16-byte path everywhere
-        (8, 8, 1, 40001, 129, 4, 0, "constant"),         # L % 4 != 0: 4-byte fallback on loads and stores
-        (3, 16, 2, 36864, 257, 4, 256, "constant"),      # aligned padding, two groups, odd batch
-        (4, 8, 1, 30002, 65, 4, 31, "reflect"),          # odd padding, border tiles by index map
-        (2, 8, 1, 50000, 33, 8, 64, "circular"),         # dilation 8: two quads per batch item
-        (5, 64, 8, 20480, 100, 4, 6, "replicate"),       # cfgD-like grouping
-        (16, 8, 1, 4099, 17, 4, 4, "constant"),          # short rows, unequal phase lengths
+    # (the last column: what the default build takes -- 2 quads, 1 pairs (two batch items per work item: quads need
+    #  four), 0 the dilated kernel, which the cost model prefers for those shapes; tests/test_gpu_routes.py runs quads
+    #  on more shapes)
+    cases = [  # batch, channels, groups, L, k, dilation, padding, mode, default ph2
+        (8, 8, 1, 40000, 129, 4, 0, "constant", 1),         # aligned: the 16-byte path everywhere
+        (8, 8, 1, 40001, 129, 4, 0, "constant", 1),         # L % 4 != 0: 4-byte fallback on loads and stores
+        (3, 16, 2, 36864, 257, 4, 256, "constant", 1),      # aligned padding, two groups, odd batch
+        (4, 8, 1, 30002, 65, 4, 31, "reflect", 0),          # odd padding, border tiles by index map
+        (2, 8, 1, 50000, 33, 8, 64, "circular", 0),         # dilation 8: two quads per batch item
+        (5, 64, 8, 20480, 100, 4, 6, "replicate", 2),       # cfgD-like grouping
+        (16, 8, 1, 4099, 17, 4, 4, "constant", 0),          # short rows, unequal phase lengths
     ]
-    for B, C, g, L, k, dil, pad, mode in cases:
+    for B, C, g, L, k, dil, pad, mode, ph2_default in cases:
         x = torch.randn(B, C, L, generator=gen).to(DEV)
         w = (torch.randn(C, C // g, k, generator=gen) / math.sqrt(C // g * k)).to(DEV)
         b = torch.randn(C, generator=gen).to(DEV)
@@ -573,6 +592,9 @@ def test_dilation_phase_quads_match_pairs_and_torch(monkeypatch):
         for knob in ("2", "1", "0"):
             monkeypatch.setenv("FFTCONV_PH2", knob)
             _native.clear_plan_cache()
+            r = _plan_for(x, w, b, (1,), (pad,), (dil,), g, mode).route
+            assert r["ph2"] == min(ph2_default, int(knob)), (knob, B, C, g, L, k, dil, pad, mode, r)
+            assert (r["ph"] > 1) == (ph2_default > 0), (knob, B, C, g, L, k, dil, pad, mode, r)
             outs[knob] = fft_conv(x, w, b, padding=pad, padding_mode=mode, dilation=dil, groups=g)
         xd = x.double()
         if mode != "constant" and pad:

@@ -18,6 +18,15 @@ def _rel(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
 
 
+@pytest.fixture
+def knob_plans(monkeypatch):
+    """monkeypatch for knobs read at plan creation, with the plan cache emptied on the way out, failed or not: the cache
+    key does not hold the knobs, so a plan built under one must not serve a later test."""
+    from fft_conv_pytorch_amd import _native
+    yield monkeypatch
+    _native.clear_plan_cache()
+
+
 # ----------------------------------------------------------------------------- plane-major 3-D pipeline (row N3)
 PLANE_CASES = [
     # B, Cin, Cout, groups, size, k, stride, padding, dilation, mode
@@ -38,20 +47,26 @@ PLANE_CASES = [
 
 
 @pytest.mark.parametrize("case", PLANE_CASES, ids=[f"{c[4]}k{c[5]}{c[9]}" for c in PLANE_CASES])
+@pytest.mark.usefixtures("knob_plans")
 def test_planes3d_matches_separable_passes_and_torch(case, monkeypatch):
     """planes_fwd / colz / planes_inv (csrc/planes3d.hpp) against the five separable passes (FFTCONV_PLANES=0) and
     torch's direct convolution in float64: same function, three launches, plane-major intermediates."""
     from fft_conv_pytorch_amd import _native
-    from fft_conv_pytorch_amd.functional import fft_conv
+    from fft_conv_pytorch_amd.functional import _plan_for, fft_conv
     B, Ci, Co, g, size, k, s, p, d, mode = case
     gen = torch.Generator().manual_seed(1000 + sum(case[4]) + case[0])
     x = torch.randn(B, Ci, *size, generator=gen).to(DEV)
     w = (torch.randn(Co, Ci // g, *k, generator=gen) / math.sqrt(Ci // g * math.prod(k))).to(DEV)
     b = torch.randn(Co, generator=gen).to(DEV)
     outs = {}
+    tup = lambda v: (v,) * 3 if isinstance(v, int) else tuple(v)
     for knob in ("1", "0"):
         monkeypatch.setenv("FFTCONV_PLANES", knob)          # (read at plan creation)
         _native.clear_plan_cache()
+        r = _plan_for(x, w, b, tup(s), tup(p), tup(d), g, mode).route
+        assert r["planes"] == int(knob), (knob, case, r)
+        if knob == "1":
+            assert r["Tx"] == r["Tm"] == 64 and r["nxt"] * r["nyt"] <= 36, (case, r)
         outs[knob] = fft_conv(x, w, b, stride=s, padding=p, dilation=d, groups=g, padding_mode=mode)
     xd, wd, bd = x.double().cpu(), w.double().cpu(), b.double().cpu()
     if mode == "constant":

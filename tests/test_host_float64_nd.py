@@ -175,3 +175,81 @@ def test_float64_knob_keeps_the_direct_kernel(monkeypatch):
                 _key(2, 8, 8, 1, (700,), (33,), (2,), (5,), transposed=True, out_pad=(1,))):
         plan = _native.Plan(key)
         assert plan.tile == 0 and plan.workspace_bytes == 0
+
+
+# ----------------------------------------------------------------------------- Plan.route (fc_debug_route)
+def _nb_cob(B, cog, spectrum):
+    """plan_nd_f64's channel blocking of the fused pass: 8 output channels a workgroup, spare slots (few output
+    channels) or a kernel spectrum of 32 MiB or more make batch items share each read of it."""
+    cob, nb = min(8, cog), 1
+    if cob <= 2 and B >= 3:
+        nb = 4
+    elif cob <= 4 and B >= 2:
+        nb = 2
+    elif spectrum >= 32 << 20 and B >= 2:
+        nb, cob = 2, 4
+    return nb, cob
+
+
+ROUTE_CASES = ND_CASES + [
+    # B, Cin, Cout, groups, size, k, stride, padding, dilation
+    (3, 4, 2, 1, (30, 40), (7, 7), (1, 1), (3, 3), (1, 1)),                 # cob 2, B 3: nb 4
+    (7, 6, 2, 1, (8, 10, 12), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1)),  # nb 4, a remainder of 3
+    (2, 4, 2, 1, (30, 40), (7, 7), (1, 1), (3, 3), (1, 1)),                 # cob 2, B 2: nb 2
+    (2, 9, 4, 1, (21, 33), (7, 7), (2, 2), (3, 3), (1, 1)),                 # cob 4: nb 2
+    (1, 4, 3, 1, (30, 40), (7, 7), (1, 1), (3, 3), (1, 1)),                 # B 1: nb 1
+    (2, 4, 9, 1, (30, 40), (7, 7), (1, 1), (3, 3), (1, 1)),                 # cob 8, a partial chunk
+    # 256 x 256 transforms (248^2 'same', k 9): 528,384 spectrum bytes per channel pair, 63.5 pairs make 32 MiB
+    (2, 9, 7, 1, (248, 248), (9, 9), (1, 1), (4, 4), (1, 1)),               # 63 pairs: just below, nb 1
+    (2, 8, 8, 1, (248, 248), (9, 9), (1, 1), (4, 4), (1, 1)),               # 64 pairs: just above, nb 2 cob 4
+    (1, 8, 8, 1, (248, 248), (9, 9), (1, 1), (4, 4), (1, 1)),               # above, but one batch item: nb 1
+    (3, 12, 6, 1, (248, 248), (9, 9), (1, 1), (4, 4), (1, 1)),              # Cout 6 in chunks of 4: the last one partial
+    (2, 13, 5, 1, (248, 248), (9, 9), (1, 1), (4, 4), (1, 1)),
+]
+
+
+@pytest.mark.parametrize("case", ROUTE_CASES, ids=[f"B{c[0]}c{c[1]}-{c[2]}-{'x'.join(map(str, c[4]))}-k{'x'.join(map(str, c[5]))}"
+                                                   for c in ROUTE_CASES])
+def test_float64_nd_route_words(case, monkeypatch):
+    """Plan.route of a float64 N-d plan: per-axis transform lengths and tile counts as the axis rule gives them, and the
+    fused pass's batch sharing and channel block as plan_nd_f64's rule gives them."""
+    monkeypatch.delenv("FFTCONV_F64_FFT", raising=False)
+    B, ci, co, g, S, k, s, p, d = case
+    plan = _native.Plan(_key(B, ci, co, g, S, k, s, p, d))
+    _, _, spectrum, _, geo = _expect(B, ci, co, g, S, k, s, p, d)
+    r = plan.route
+    assert r["kind"] == "f64_fft_nd", r
+    n = len(S)
+    assert [r[f"t{i}"] for i in range(3)] == [geo[i][0] for i in range(n)] + [0] * (3 - n), r
+    assert [r[f"nt{i}"] for i in range(3)] == [geo[i][2] for i in range(n)] + [0] * (3 - n), r
+    assert plan.spectrum_bytes == spectrum
+    assert (r["nb"], r["cob"]) == _nb_cob(B, co // g, spectrum), (r, spectrum)
+
+
+def test_float64_32_mib_boundary_both_sides(monkeypatch):
+    monkeypatch.delenv("FFTCONV_F64_FFT", raising=False)
+    geo = (1, 1), (4, 4), (1, 1)
+    below = _native.Plan(_key(2, 9, 7, 1, (248, 248), (9, 9), *geo))
+    above = _native.Plan(_key(2, 8, 8, 1, (248, 248), (9, 9), *geo))
+    assert below.spectrum_bytes < 32 << 20 <= above.spectrum_bytes
+    assert (below.route["nb"], below.route["cob"]) == (1, 7)
+    assert (above.route["nb"], above.route["cob"]) == (2, 4)
+
+
+def test_float64_other_kinds_route_words(monkeypatch):
+    monkeypatch.delenv("FFTCONV_F64_FFT", raising=False)
+    assert _native.Plan(_key(2, 3, 3, 1, (10, 10), (1, 1))).route == {"kind": "f64_direct"}
+    plan = _native.Plan(_key(2, 2, 3, 1, (5000,), (600,), pad=(10,)))
+    T, V = 2048, 2048 - 600 + 1
+    assert plan.route == {"kind": "f64_fft_1d", "T": T, "ntiles": -(-(5000 + 20 - 599) // V), "cob": 2}
+    assert plan.tile == T
+
+
+def test_debug_route_rejects_null_arguments(monkeypatch):
+    import ctypes
+    monkeypatch.delenv("FFTCONV_F64_FFT", raising=False)
+    lib = _native.load_library()
+    words = (ctypes.c_int32 * 16)()
+    assert lib.fc_debug_route(None, ctypes.byref(words)) == _native.FC_ERR_INVALID
+    plan = _native.Plan(_key(2, 3, 3, 1, (10, 10), (1, 1)))
+    assert lib.fc_debug_route(plan._h, None) == _native.FC_ERR_INVALID

@@ -31,7 +31,8 @@ ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd")
 ROUTE_WORDS = {
     "f32_1d": ("T", "ntiles", "pers_nb", "ph", "ph2", "slot_tiles", "nseg", "diag", "bd_gs", "wide", "dense",
                "chunk_launches", "accumulate", "n_ochunks", "pers_items"),
-    "f32_nd": ("T", "ntiles", "Tx", "nxt", "Tm", "nyt", "planes", "cob", "accumulate"),
+    "f32_nd": ("T", "ntiles", "Tx", "nxt", "Tm", "nyt", "planes", "cob", "accumulate",
+               "nseg0", "nseg1", "nseg2", "seg_taps0", "seg_taps1", "seg_taps2"),
     "f64_direct": (),
     "f64_fft_1d": ("T", "ntiles", "cob"),
     "f64_fft_nd": ("t0", "t1", "t2", "nt0", "nt1", "nt2", "nb", "cob"),

@@ -284,9 +284,10 @@ int fc_plan_layout(const fc_plan* plan, int32_t layout[8]) {
       layout[1] = p.f1d.ph; layout[2] = p.f1d.nseg; layout[3] = p.f1d.seg_taps;
       layout[4] = p.f1d.diag; layout[5] = p.f1d.bd_gs; layout[6] = p.f1d.dense ? 2 : p.f1d.wide; layout[7] = p.f1d.pers_nb;
       break;
-    case PlanKind::F32_ND:   // the spectrum is laid out over the row / middle-axis transform lengths too
+    case PlanKind::F32_ND:   // the spectrum is laid out over the row / middle-axis transform lengths and the segments too
       layout[0] = p.tile->T;
       layout[1] = p.fnd.tx->T; layout[2] = p.fnd.tm ? p.fnd.tm->T : 0; layout[3] = p.fnd.cob;   // (x tiles share one kernel spectrum)
+      for (int a = 0; a < p.nd; ++a) layout[4 + a] = p.fnd.nseg[a] > 1 ? p.fnd.seg_taps[a] : 0;   // taps per segment (0: whole axis)
       layout[7] = p.fnd.planes;      // 1 / 2: the thread-per-sequence column pass (3-D plane-major / 2-D); same spectrum bytes either way
       break;
     case PlanKind::F64_FFT_ND:   // [outermost T, Tx, middle T (3-D)]
@@ -336,6 +337,7 @@ int fc_debug_route(const fc_plan* plan, int32_t route[16]) {
       const int32_t w[] = {p.tile->T, p.ntiles, p.fnd.tx->T, p.fnd.nxt, p.fnd.tm ? p.fnd.tm->T : 0, p.fnd.nyt,
                            p.fnd.planes, p.fnd.cob, p.accumulate};
       for (int i = 0; i < 9; ++i) route[1 + i] = w[i];
+      for (int a = 0; a < p.nd; ++a) { route[10 + a] = p.fnd.nseg[a]; route[13 + a] = p.fnd.seg_taps[a]; }   // (tensor order)
       break;
     }
     case PlanKind::F64_DIRECT:
@@ -380,6 +382,8 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
   const fc_plan& p = *plan;
   if (p.d.has_bias && !bias) return fail(FC_ERR_INVALID, "plan was created with has_bias=1 but bias is NULL");
   if (p.workspace_bytes && !workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
+  if (stamps && p.kind == PlanKind::F32_ND && p.fnd.nseg_total > 1)
+    return fail(FC_ERR_UNSUPPORTED, "a plan that runs its kernel in %d segments of taps has no stamped forward", p.fnd.nseg_total);
   switch (p.kind) {
     case PlanKind::F32_1D: return forward_1d(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F32_ND: return forward_nd(p, x, w_hat, bias, y, workspace, st, stamps);

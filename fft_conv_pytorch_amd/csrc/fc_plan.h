@@ -54,7 +54,7 @@ int64_t round_up(int64_t v, int64_t m);
 
 enum class PlanKind {
   F32_1D,       // host_1d.cpp: fused / batch-sharing / wide / dense kernels, segments, phases
-  F32_ND,       // host_nd.cpp: separable passes, plane-major pipeline, 2-D column pass
+  F32_ND,       // host_nd.cpp: separable passes, plane-major pipeline, 2-D column pass, segments of taps
   F64_DIRECT,   // host_f64.cpp: direct time-domain kernel (any ndim)
   F64_FFT_1D,   // host_f64.cpp: fft_f64.hip
   F64_FFT_ND,   // host_f64.cpp: nd_f64.hip
@@ -119,6 +119,11 @@ struct fc_plan {
     // the tensors keep the caller's layout (ImgMap in the row passes)
     int swap;
     int64_t sw_B, sw_Cig, sw_Cog, sw_g;      // of the ORIGINAL convolution
+    // segments of taps (host_nd.cpp plan_nd_segments): axis a runs as nseg[a] convolutions of seg_taps[a] taps each
+    // (kd, Sp and need of the plan are those of one segment); nseg_total = their product, one kernel spectrum of
+    // seg_spectrum_bytes each, in tensor order.  nseg[a] = 1, seg_taps[a] = kernel[a] on an axis that is not cut.
+    int nseg[3], seg_taps[3], nseg_total;
+    size_t seg_spectrum_bytes;
   } fnd;
 
   struct {                    // ---- F64_FFT_1D / F64_FFT_ND

@@ -1,7 +1,7 @@
 // host_nd.cpp -- float32 2-D / 3-D plans (PlanKind::F32_ND): transforms of the rows and middle axes (full length or
 // overlap-save tiles), the fused outermost-axis tile, the plane-major pipeline and the 2-D column pass (`planes`),
-// workspace and spectrum sizes; the kernel transform and the forward of such a plan, the N-d weight gradient's image
-// maps included (`swap`, fc_wgrad_nd).
+// workspace and spectrum sizes, kernels longer than a tile in segments of taps; the kernel transform and the forward of
+// such a plan, the N-d weight gradient's image maps included (`swap`, fc_wgrad_nd).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,12 +67,117 @@ static int plan_axis_tiles(const fc_plan* p, int ax, const char* knob, int64_t m
   return FC_OK;
 }
 
+// Whether the fused (outermost-axis) pass can run tile t with this plan's channel chunk: the CB sequences (twice that with
+// running sums over several input chunks) must fit 160 KiB of LDS.
+static bool outer_tile_fits(const fc_plan* p, const fc::TileImpl* t, size_t* lds_out) {
+  const size_t lds = (size_t)(p->accumulate ? 2 : 1) * p->CB * t->lseqp * sizeof(fc::f2);
+  if (lds_out) *lds_out = lds;
+  return p->CB <= t->fusedc_max_cib && lds <= 160 * 1024;
+}
+
+// Points-based cost of one pass over an axis of Lf stride-1 outputs against a dilated extent kd, with the padded axis
+// (Lf + kd - 1) held whole: the row / middle-axis transforms (plan_axis_tiles without its sub-tile search) and the fused
+// outer-axis tiles (the tile loop of plan_nd).  < 0 when no tile holds kd.
+static double axis_cost(const fc_plan* p, int ax, int64_t kd, int64_t Lf) {
+  const int64_t Sp = Lf + kd - 1;
+  if (ax != 0) {
+    const fc::TileImpl* t = smallest_tile_at_least(Sp);
+    int64_t n = 1;
+    if (!t) {
+      t = find_tile(kd <= 1025 ? 2048 : 4096);
+      if (!t || t->T < kd) return -1;
+      n = (Lf + t->T - kd) / (t->T - kd + 1);
+    }
+    return (double)n * t->T * (2.0 * std::log2((double)t->T) + 4.0);
+  }
+  double best = -1;
+  int ntl;
+  auto tiles = all_tiles(&ntl);
+  for (int i = 0; i < ntl; ++i) {
+    const fc::TileImpl* t = tiles[i];
+    size_t lds;
+    if (t->T < kd || !outer_tile_fits(p, t, &lds)) continue;
+    const int64_t nt = t->T >= Sp ? 1 : (Lf + t->T - kd) / (t->T - kd + 1);
+    double cost = (double)nt * t->T * (2.0 * std::log2((double)t->T) + 4.0 + 2.0 * p->CB);
+    if (lds > 80 * 1024) cost *= 1.25;
+    if (best < 0 || cost < best) best = cost;
+  }
+  return best;
+}
+
+// Segments of taps.  An axis whose dilated extent no tile holds -- past 4096 along the rows / middle
+// axes, past the largest tile the fused pass can run with this channel chunk along the outermost axis -- is cut into
+// segments of C taps: segment j holds taps [j*C, min(k, (j+1)*C)), a convolution of dilated extent (C-1)*d + 1 with the
+// same Lf stride-1 outputs that reads the padded axis from position j*C*d on (forward_nd adds the segments into y).  C
+// minimises segments x (the axis' points-based cost over all rows of the problem + a fixed cost per segment): every
+// segment runs the whole pipeline (4-6 launches of at least ~4 us each), and a small problem spent most of its time in
+// them when only points counted (training step B2 3->4 16x8192 k3, dW: 33 segments of 256-point rows, 965 us per step;
+// profiles/r05_nd_segments.txt).  The two constants are rough fits to those rows: ~2e6 cost units per us, 20 us per
+// segment.  FFTCONV_NDSEG=<taps> (testing) forces segments of that many taps on every axis with more taps.  The plan's
+// kd, Sp and need become those of one segment (no zero-wrap shortening).
+static int plan_nd_segments(fc_plan* p) {
+  const fc_desc& d = p->d;
+  const char* env = getenv("FFTCONV_NDSEG");
+  const int64_t forced = env ? atoll(env) : 0;
+  long long total = 1;
+  constexpr double kUnitsPerUs = 2e6, kSegmentUs = 20.0;
+  for (int ax = 0; ax < p->nd; ++ax) {
+    p->fnd.nseg[ax] = 1;
+    p->fnd.seg_taps[ax] = (int)d.kernel[ax];
+    int64_t limit = 4096;
+    if (ax == 0) {
+      limit = 0;
+      int ntl;
+      auto tiles = all_tiles(&ntl);
+      for (int i = 0; i < ntl; ++i)
+        if (outer_tile_fits(p, tiles[i], nullptr)) limit = std::max<int64_t>(limit, tiles[i]->T);
+      if (!limit) continue;     // (refused by the tile loop)
+    }
+    const int64_t k = d.kernel[ax], dil = d.dilation[ax], Lf = p->Lf[ax];
+    const int64_t cmax = (limit - 1) / dil + 1;       // most taps whose dilated extent fits
+    int64_t C = 0;
+    if (forced > 0 && k > forced && forced <= cmax) {
+      C = forced;
+    } else if (p->kd[ax] > limit) {
+      // rows of the problem along this axis: images on both sides, padded extents of the other axes
+      double rows = (double)d.batch * (double)(d.in_channels + d.out_channels);
+      for (int b = 0; b < p->nd; ++b)
+        if (b != ax) rows *= p->Sp[b];
+      double best = 0;
+      for (int64_t ns = (k + cmax - 1) / cmax; ns <= std::min<int64_t>(k, 64); ++ns) {
+        const int64_t c = (k + ns - 1) / ns;
+        if ((k + c - 1) / c != ns) continue;            // (the taps of a smaller count)
+        const double cost = axis_cost(p, ax, (c - 1) * dil + 1, Lf);
+        if (cost < 0) continue;
+        const double us = (double)ns * (cost * rows / kUnitsPerUs + kSegmentUs);
+        if (!C || us < best) { C = c; best = us; }
+      }
+      if (!C) C = cmax;                                 // (more than 64 segments: refused below)
+    }
+    if (!C) continue;
+    p->fnd.nseg[ax] = (int)((k + C - 1) / C);
+    p->fnd.seg_taps[ax] = (int)C;
+    p->kd[ax] = (C - 1) * dil + 1;
+    p->Sp[ax] = (int)(Lf + p->kd[ax] - 1);
+    p->need[ax] = p->Sp[ax];
+    total = std::min<long long>(total * p->fnd.nseg[ax], 1LL << 40);
+  }
+  if (total > 64)
+    return fail(FC_ERR_UNSUPPORTED, "the kernel would run as %lld segments of taps (at most 64): kernel extents or "
+                "dilations too large", total);
+  p->fnd.nseg_total = (int)total;
+  return FC_OK;
+}
+
 int plan_nd(fc_plan* p) {
   const fc_desc& d = p->d;
   const int nd = p->nd;
+  int rc = plan_nd_segments(p);
+  if (rc != FC_OK) return rc;
+  const bool segmented = p->fnd.nseg_total > 1;
   // rows axis: one full-length transform when the padded row fits the largest FFT, overlap-save tiles otherwise
   // (the reference has no size limit: functional.py:66-70); middle axis (3-D): the same
-  int rc = plan_axis_tiles(p, nd - 1, "FFTCONV_XTILE", INT64_MAX, "the last axis", &p->fnd.tx, &p->fnd.Vx, &p->fnd.nxt);
+  rc = plan_axis_tiles(p, nd - 1, "FFTCONV_XTILE", INT64_MAX, "the last axis", &p->fnd.tx, &p->fnd.Vx, &p->fnd.nxt);
   if (rc != FC_OK) return rc;
   p->fnd.Fx = p->fnd.tx->T / 2;        // odd-frequency bins along the rows axis (nd_passes.hpp, rows_r2c)
   p->fnd.Fxt = p->fnd.nxt * p->fnd.Fx;
@@ -99,7 +204,7 @@ int plan_nd(fc_plan* p) {
   // 3-D planes larger than 64 x 64 after padding: cut into overlap-save tiles of 64 x 64 so that the plane-major pipeline
   // (below) still applies -- each tile is one workgroup of planes_fwd / planes_inv and one block of 2048 columns of colz.
   // Measured against the separable passes with the planner's own x / y tiles (profiles/r03_experiments.md block 12).
-  if (nd == 3 && !getenv("FFTCONV_XTILE") && !getenv("FFTCONV_YTILE") && !p->fnd.swap && !d.tile_hint) {
+  if (nd == 3 && !getenv("FFTCONV_XTILE") && !getenv("FFTCONV_YTILE") && !p->fnd.swap && !d.tile_hint && !segmented) {
     const char* pl = getenv("FFTCONV_PLANES");
     const fc::TileImpl* t64 = find_tile(64);
     const bool wide = p->fnd.tx->T > 64 || p->fnd.tm->T > 64 || p->fnd.nxt > 1 || p->fnd.nyt > 1;
@@ -150,9 +255,9 @@ int plan_nd(fc_plan* p) {
                   (int64_t)4 * std::max(d.in_channels, d.out_channels) * std::max<int64_t>(p->Sp[0], p->out_sp[0]) * p->fnd.Fxt * 8 < ((int64_t)1 << 31);
     }
   }
+  if (segmented) planes_ok = false;   // (segments run the separable passes only)
   // overlap-save tiles along the outermost axis
   const int64_t Kd = p->kd[0], Lfull = p->Lf[0];
-  const size_t lds_cap = 160 * 1024;
   const fc::TileImpl* best = nullptr;
   double best_cost = 0;
   int ntl;
@@ -161,9 +266,8 @@ int plan_nd(fc_plan* p) {
     const fc::TileImpl* t = tiles[i];
     if (d.tile_hint && t->T != d.tile_hint) continue;
     if (planes_ok && t->T != 64) continue;
-    if (t->T < Kd || p->CB > t->fusedc_max_cib) continue;
-    const size_t lds = (size_t)(p->accumulate ? 2 : 1) * p->CB * t->lseqp * sizeof(fc::f2);
-    if (lds > lds_cap) continue;
+    size_t lds;
+    if (t->T < Kd || !outer_tile_fits(p, t, &lds)) continue;
     const int64_t V = t->T - Kd + 1;
     const int64_t nt = t->T >= p->need[0] ? 1 : (Lfull + V - 1) / V;     // (one tile when the zero padding absorbs the wrap)
     double cost = (double)nt * t->T * (2.0 * std::log2((double)t->T) + 4.0 + 2.0 * p->CB);
@@ -216,22 +320,43 @@ int plan_nd(fc_plan* p) {
   p->ws_a = std::max(a_sig, a_w);
   p->ws_b = std::max(b_sig, b_w);
   p->workspace_bytes = (p->ws_a + p->ws_b) * sizeof(fc::f2);
-  p->spectrum_bytes = (size_t)d.groups * p->fnd.Cog_pad * (p->Cig_pad / 2) * ncol * best->T * sizeof(fc::f4);
+  p->fnd.seg_spectrum_bytes = (size_t)d.groups * p->fnd.Cog_pad * (p->Cig_pad / 2) * ncol * best->T * sizeof(fc::f4);
+  p->spectrum_bytes = p->fnd.seg_spectrum_bytes * (size_t)p->fnd.nseg_total;   // (one spectrum per segment, in tensor order)
   rc = get_twiddles(best, &p->tw);
   if (rc == FC_OK) rc = get_twiddles(p->fnd.tx, &p->fnd.twx);
   if (rc == FC_OK && p->fnd.tm) rc = get_twiddles(p->fnd.tm, &p->fnd.twm);
   return rc;
 }
 
-// kernel spectrum: the separable passes, fed from the dilated taps
+// segment s of a segmented plan (tensor order) -> its index along every axis
+static void segment_of(const fc_plan& p, int s, int j[3]) {
+  j[0] = j[1] = j[2] = 0;
+  for (int ax = p.nd - 1; ax >= 0; --ax) { j[ax] = s % p.fnd.nseg[ax]; s /= p.fnd.nseg[ax]; }
+}
+
+static int transform_kernel_nd_segment(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st,
+                                       const int j[3]);
+
+// kernel spectrum: the separable passes, fed from the dilated taps -- one spectrum per segment of taps
 int transform_kernel_nd(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st) {
+  // phantom channels (padding of the channel counts up to the chunk size) must read as zero; without any, every
+  // entry of the spectrum is written by the passes below and the fill (6 us per call on a 2-D training step) is skipped
+  if (p.Cig_pad != p.Cig || p.fnd.Cog_pad != p.Cog) FC_HIP(hipMemsetAsync(w_hat, 0, p.spectrum_bytes, st));
+  for (int s = 0; s < p.fnd.nseg_total; ++s) {
+    int j[3];
+    segment_of(p, s, j);
+    const int rc = transform_kernel_nd_segment(p, weight, (char*)w_hat + (size_t)s * p.fnd.seg_spectrum_bytes, workspace, st, j);
+    if (rc != FC_OK) return rc;
+  }
+  return FC_OK;
+}
+
+static int transform_kernel_nd_segment(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st,
+                                       const int j[3]) {
   fc::f2* wsA = (fc::f2*)workspace;
   fc::f2* wsB = wsA + p.ws_a;
   const int nd = p.nd;
   const int Co = (int)p.d.out_channels;
-  // phantom channels (padding of the channel counts up to the chunk size) must read as zero; without any, every
-  // entry of the spectrum is written by the passes below and the fill (6 us per call on a 2-D training step) is skipped
-  if (p.Cig_pad != p.Cig || p.fnd.Cog_pad != p.Cog) FC_HIP(hipMemsetAsync(w_hat, 0, p.spectrum_bytes, st));
   fc::RowsR2CArgs r{};
   r.src = weight; r.dst = wsA; r.twA = p.fnd.twx.twA; r.twB = p.fnd.twx.twB; r.from_kernel = 1;
   r.kx = (int)p.d.kernel[nd - 1]; r.dx = (int)p.d.dilation[nd - 1];
@@ -239,6 +364,14 @@ int transform_kernel_nd(const fc_plan& p, const float* weight, void* w_hat, void
   r.kz = nd == 3 ? (int)p.d.kernel[0] : 1; r.dz = nd == 3 ? (int)p.d.dilation[0] : 1;
   r.NA = Co * p.Cig; r.NC = nd == 3 ? (int)p.kd[0] : 1; r.NY = (int)p.kd[nd - 2]; r.NYa = r.NY;
   r.SZ = r.kz; r.SY = r.ky; r.SX = r.kx; r.Fx = p.fnd.Fx;
+  // segment j of an axis: taps [j*C, min(k, (j+1)*C)) (the source keeps its full extent SX / SY / SZ)
+  const int zx = nd - 1, zy = nd - 2;
+  auto seg_taps = [&](int ax) { return std::min(p.fnd.seg_taps[ax], (int)p.d.kernel[ax] - j[ax] * p.fnd.seg_taps[ax]); };
+  if (!p.fnd.swap) {
+    r.kx = seg_taps(zx); r.tox = j[zx] * p.fnd.seg_taps[zx];
+    r.ky = seg_taps(zy); r.toy = j[zy] * p.fnd.seg_taps[zy];
+    if (nd == 3) { r.kz = seg_taps(0); r.toz = j[0] * p.fnd.seg_taps[0]; }
+  }
   r.nxt = 1; r.Vx = 0;                       // the kernel sits in the first x tile
   r.transposed = p.d.transposed; r.Cig = p.Cig; r.Cog = p.Cog;
   if (p.fnd.swap) {   // "kernel" = the output gradient (B, g*Cog, *Lout), read as ((g, o), b): image o_all*B + b sits at b*(g*Cog) + o_all
@@ -246,8 +379,13 @@ int transform_kernel_nd(const fc_plan& p, const float* weight, void* w_hat, void
     // a tensor as large as the signal: read it through the signal's index maps (taps spread by the dilation = a source
     // spread over a grid of that step, nothing in front), which have the unrolled zero-padding path the tap loop lacks
     r.from_kernel = 0;
-    auto tmap = [&](int64_t taps, int64_t dil) { fc::AxisMap m; m.size = (int)taps; m.pad = 0; m.mode = FC_PAD_CONSTANT; m.up = (int)dil; return m; };
-    r.mx = tmap(r.kx, r.dx); r.my = tmap(r.ky, r.dy); r.mz = tmap(r.kz, r.dz);
+    // (segment j of an axis: the taps [j*C, min(k, (j+1)*C)) moved to the front)
+    auto tmap = [&](int ax, int64_t taps, int64_t dil) {
+      const int C = ax >= 0 ? p.fnd.seg_taps[ax] : (int)taps, jj = ax >= 0 ? j[ax] : 0;
+      fc::AxisMap m; m.size = (int)std::min<int64_t>(taps, (int64_t)(jj + 1) * C); m.pad = -(int)(jj * C * dil);
+      m.mode = FC_PAD_CONSTANT; m.up = (int)dil; return m;
+    };
+    r.mx = tmap(zx, r.kx, r.dx); r.my = tmap(zy, r.ky, r.dy); r.mz = tmap(nd == 3 ? 0 : -1, r.kz, r.dz);
     const unsigned long long bytes = 4ull * (unsigned long long)r.NA * r.SZ * r.SY * r.SX;
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
@@ -336,11 +474,10 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
   r.rowmajor = p.fnd.planes == 2;
+  const int64_t dil[3] = {p.d.dilation[0], p.d.dilation[1], p.d.dilation[2]};
   if (p.fnd.swap) {   // signal = x (B, g*Cig, *S) read as (i, (g, b)): image (i*g + gi)*B + b sits at b*(g*Cig) + gi*Cig + i
     r.im.on = 1; r.im.n1 = (int)p.fnd.sw_g; r.im.n2 = (int)p.fnd.sw_B; r.im.s0 = 1; r.im.s1 = p.fnd.sw_Cig; r.im.s2 = p.fnd.sw_g * p.fnd.sw_Cig;
   }
-  FC_HIP(p.fnd.tx->rows_r2c(r, st));
-
   fc::FusedCArgs f{};
   f.wspec = (const fc::f4*)w_hat; f.twA = p.tw.twA; f.twB = p.tw.twB;
   f.B = B; f.Cin = Ci; f.Cout = Co; f.G = (int)p.d.groups; f.Cig = p.Cig; f.Cog = p.Cog;
@@ -359,47 +496,60 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     o.im.on = 1; o.im.n1 = 1; o.im.n2 = (int)(p.fnd.sw_g * p.fnd.sw_Cog); o.im.s0 = 1; o.im.s1 = 0; o.im.s2 = p.fnd.sw_Cig;
   }
 
-  if (nd == 2 && p.fnd.planes == 2) {
-    // x (B,Ci,Y,X) -> S[(b,ci)][yp][fx] (rows_r2c above, rows as they are) -> O[(b,co)][y_out][fx] -> y
-    // (all x tiles of the signal; they share the Tx/2 spectrum columns)
-    FC_HIP(p.tile->colz(colz_args(p, wsA, w_hat, wsB, Fs, p.fnd.Fx, stamps), st));
-    o.src = wsB; o.NC = 1; o.rowmajor = 1;
-    FC_HIP(p.fnd.tx->rows_c2r(o, st));
-  } else if (nd == 2) {
-    f.src = wsA; f.dst = wsB; f.ncol = Fs;
-    FC_HIP(p.tile->fusedc(p.CB, f, st));
-    o.src = wsB; o.NC = 1;
-    FC_HIP(p.fnd.tx->rows_c2r(o, st));
-  } else {
-    const int Ty = p.fnd.tm->T, Szp = p.Sp[0], Syp = p.Sp[1], Lzo = (int)p.out_sp[0], Lyo = (int)p.out_sp[1];
-    fc::C2CArgs c{};
-    c.scale = 1.f; c.store_mode = 0; c.twA = p.fnd.twm.twA; c.twB = p.fnd.twm.twB;
-    // S1[(b,ci)][zp][fx][yp] -> S2[(b,ci)][fx][yt,fy][zp]   (one launch per middle-axis tile yt)
-    const int nyt = p.fnd.nyt, Vy = p.fnd.Vy;
-    const long long Tys = (long long)nyt * Ty;
-    c.NA = B * Ci; c.NC = Fs; c.NB = Szp;
-    c.sa = (long long)Szp * Fs * Syp; c.sb = (long long)Fs * Syp; c.sc = Syp;
-    c.ta = (long long)Fs * Tys * Szp; c.tc = Tys * Szp; c.tf = Szp;
-    c.NV = 0; c.stride = 1; c.noff = 0;
-    for (int yt = 0; yt < nyt; ++yt) {
-      c.src = wsA + (size_t)yt * Vy; c.dst = wsB + (size_t)yt * Ty * Szp;
-      c.NLEN = std::min(Ty, Syp - yt * Vy);
-      FC_HIP(p.fnd.tm->c2c_fwd(c, st));
+  // segments of taps: segment j of an axis reads the padded signal from j*C*dilation on, against its own spectrum; the
+  // first stores y with the bias, the later ones add into it (an unsegmented plan runs this once, as segment 0)
+  for (int s = 0; s < p.fnd.nseg_total; ++s) {
+    int j[3];
+    segment_of(p, s, j);
+    auto shift = [&](int ax) { return (int)(j[ax] * p.fnd.seg_taps[ax] * dil[ax]); };
+    r.shx = shift(nd - 1); r.shy = shift(nd - 2); r.shz = nd == 3 ? shift(0) : 0;
+    f.wspec = (const fc::f4*)((const char*)w_hat + (size_t)s * p.fnd.seg_spectrum_bytes);
+    o.accum = s > 0;
+    if (s > 0) o.bias = nullptr;
+    FC_HIP(p.fnd.tx->rows_r2c(r, st));
+
+    if (nd == 2 && p.fnd.planes == 2) {
+      // x (B,Ci,Y,X) -> S[(b,ci)][yp][fx] (rows_r2c above, rows as they are) -> O[(b,co)][y_out][fx] -> y
+      // (all x tiles of the signal; they share the Tx/2 spectrum columns)
+      FC_HIP(p.tile->colz(colz_args(p, wsA, w_hat, wsB, Fs, p.fnd.Fx, stamps), st));
+      o.src = wsB; o.NC = 1; o.rowmajor = 1;
+      FC_HIP(p.fnd.tx->rows_c2r(o, st));
+    } else if (nd == 2) {
+      f.src = wsA; f.dst = wsB; f.ncol = Fs;
+      FC_HIP(p.tile->fusedc(p.CB, f, st));
+      o.src = wsB; o.NC = 1;
+      FC_HIP(p.fnd.tx->rows_c2r(o, st));
+    } else {
+      const int Ty = p.fnd.tm->T, Szp = p.Sp[0], Syp = p.Sp[1], Lzo = (int)p.out_sp[0], Lyo = (int)p.out_sp[1];
+      fc::C2CArgs c{};
+      c.scale = 1.f; c.store_mode = 0; c.twA = p.fnd.twm.twA; c.twB = p.fnd.twm.twB;
+      // S1[(b,ci)][zp][fx][yp] -> S2[(b,ci)][fx][yt,fy][zp]   (one launch per middle-axis tile yt)
+      const int nyt = p.fnd.nyt, Vy = p.fnd.Vy;
+      const long long Tys = (long long)nyt * Ty;
+      c.NA = B * Ci; c.NC = Fs; c.NB = Szp;
+      c.sa = (long long)Szp * Fs * Syp; c.sb = (long long)Fs * Syp; c.sc = Syp;
+      c.ta = (long long)Fs * Tys * Szp; c.tc = Tys * Szp; c.tf = Szp;
+      c.NV = 0; c.stride = 1; c.noff = 0;
+      for (int yt = 0; yt < nyt; ++yt) {
+        c.src = wsA + (size_t)yt * Vy; c.dst = wsB + (size_t)yt * Ty * Szp;
+        c.NLEN = std::min(Ty, Syp - yt * Vy);
+        FC_HIP(p.fnd.tm->c2c_fwd(c, st));
+      }
+      f.src = wsB; f.dst = wsA; f.ncol = (int)(Fs * Tys);
+      FC_HIP(p.tile->fusedc(p.CB, f, st));
+      // O2[(b,co)][fx][yt,fy][z_out] -> O1[(b,co)][z_out][fx][y_out]
+      c.NA = B * Co; c.NC = Fs; c.NB = Lzo;
+      c.sa = (long long)Fs * Tys * Lzo; c.sc = Tys * Lzo; c.sb = Lzo;
+      c.ta = (long long)Lzo * Fs * Lyo; c.tb = (long long)Fs * Lyo; c.tc = Lyo;
+      c.stride = p.ostride[1];
+      for (int yt = 0; yt < nyt; ++yt) {
+        c.src = wsA + (size_t)yt * Ty * Lzo; c.dst = wsB;
+        c.noff = yt * Vy; c.NV = std::min(Vy, p.Lf[1] - yt * Vy);
+        FC_HIP(p.fnd.tm->c2c_inv(c, st));
+      }
+      o.src = wsB; o.NC = Lzo;
+      FC_HIP(p.fnd.tx->rows_c2r(o, st));
     }
-    f.src = wsB; f.dst = wsA; f.ncol = (int)(Fs * Tys);
-    FC_HIP(p.tile->fusedc(p.CB, f, st));
-    // O2[(b,co)][fx][yt,fy][z_out] -> O1[(b,co)][z_out][fx][y_out]
-    c.NA = B * Co; c.NC = Fs; c.NB = Lzo;
-    c.sa = (long long)Fs * Tys * Lzo; c.sc = Tys * Lzo; c.sb = Lzo;
-    c.ta = (long long)Lzo * Fs * Lyo; c.tb = (long long)Fs * Lyo; c.tc = Lyo;
-    c.stride = p.ostride[1];
-    for (int yt = 0; yt < nyt; ++yt) {
-      c.src = wsA + (size_t)yt * Ty * Lzo; c.dst = wsB;
-      c.noff = yt * Vy; c.NV = std::min(Vy, p.Lf[1] - yt * Vy);
-      FC_HIP(p.fnd.tm->c2c_inv(c, st));
-    }
-    o.src = wsB; o.NC = Lzo;
-    FC_HIP(p.fnd.tx->rows_c2r(o, st));
   }
   return FC_OK;
 }

@@ -119,6 +119,12 @@ struct RowsR2CArgs {
   FastDiv d_nyb, d_nxt, d_nc;   // unit map of the launch (filled by the dispatcher)
   int rowmajor;          // dst [(a*NC + c)][NY][nxt*Fx] instead of the transposed [..][Fx][NYa]: the 2-D pipeline whose column
                          // pass runs one THREAD per sequence with its lanes over neighbouring bin columns (planes3d.hpp colz)
+  // segments of taps (host_nd.cpp): segment j of an axis reads the padded signal from position j*C*dilation on (shift, in
+  // padded coordinates, added before the axis map -- the map's own pad stays the reflect / replicate / circular bound)
+  // and holds taps j*C .. j*C + k - 1 of the kernel (k = kx / ky / kz above, the tap offset added before a transposed
+  // plan flips the taps against SX / SY / SZ); all 0 for an unsegmented plan
+  int shx, shy, shz;
+  int tox, toy, toz;
 };
 
 template <int P, int S, int NSEQ, int NT>
@@ -152,9 +158,11 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
       if (a.from_kernel) {
         ys = yp < a.NY ? tap_src(yp, a.dy, a.ky) : -1;
         zs = tap_src(c, a.dz, a.kz);
+        if (ys >= 0) ys += a.toy;
+        if (zs >= 0) zs += a.toz;
       } else {
-        ys = yp < a.NY ? axis_src(a.my, yp) : -1;
-        zs = axis_src(a.mz, c);       // (2-D plans carry an identity map here)
+        ys = yp < a.NY ? axis_src(a.my, yp + a.shy) : -1;
+        zs = axis_src(a.mz, c + a.shz);       // (2-D plans carry an identity map here)
       }
       ok[h] = ys >= 0 && zs >= 0;
       size_t simg = map_img(a.im, img);
@@ -173,8 +181,8 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
       const unsigned ro1 = ok[1] ? (unsigned)((rows[1] - a.src) * 4) : 0xFFFFFFFFu;
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
-        const int xs = x0 + G::N2 * n1 + tseq - a.mx.pad;
-        const bool in = (unsigned)xs < (unsigned)a.SX;
+        const int xs = x0 + G::N2 * n1 + tseq + a.shx - a.mx.pad;
+        const bool in = (unsigned)xs < (unsigned)a.mx.size;     // (== SX, but for a segment of a weight-gradient plan's dY)
         v[n1].x = buf_load_f32(sg, (in && ok[0]) ? ro0 + (unsigned)xs * 4u : 0xFFFFFFFFu, 0);
         v[n1].y = buf_load_f32(sg, (in && ok[1]) ? ro1 + (unsigned)xs * 4u : 0xFFFFFFFFu, 0);
       }
@@ -183,7 +191,8 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
 #pragma unroll 1
       for (int n1 = 0; n1 < P; ++n1) {
         const int xp = x0 + G::N2 * n1 + tseq;
-        int xs = a.from_kernel ? tap_src(xp, a.dx, a.kx) : axis_src(a.mx, xp);
+        int xs = a.from_kernel ? tap_src(xp, a.dx, a.kx) : axis_src(a.mx, xp + a.shx);
+        if (a.from_kernel && xs >= 0) xs += a.tox;
         if (a.from_kernel && a.transposed && xs >= 0) xs = a.SX - 1 - xs;
         const float v0 = (ok[0] && xs >= 0) ? rows[0][xs] : 0.f;
         const float v1 = (ok[1] && xs >= 0) ? rows[1][xs] : 0.f;
@@ -427,6 +436,7 @@ struct RowsC2RArgs {
   ImgMap im;             // where image `img` of this pass goes in dst (identity unless a weight-gradient plan)
   FastDiv d_nyb, d_nxt, d_nc;   // unit map of the launch (filled by the dispatcher)
   int rowmajor;          // src [(a*NC + c)][NY][nxt*Fx] (see RowsR2CArgs)
+  int accum;             // add into dst instead of storing, no bias (later segments of taps, host_nd.cpp)
 };
 
 template <int P, int S, int NSEQ, int NT>
@@ -542,7 +552,7 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
   const int ya_row = y0 + 2 * sq;
   // (declared arrived before the guarded stores: met first inside them, hipcc puts a full s_waitcnt vmcnt(0) in front of
   // every store, and vmcnt counts stores too -- each store would wait for the one before it)
-  float b = a.bias ? a.bias[img % a.Cout] : 0.f;
+  float b = (a.bias && !a.accum) ? a.bias[img % a.Cout] : 0.f;
   asm volatile("" : "+v"(b));
   // buffer stores relative to this workgroup's RB output rows (32-bit offsets; samples past the valid window, decimated
   // away or in rows past NY get an out-of-range offset instead of a branch)
@@ -553,6 +563,39 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
   const unsigned r0 = (unsigned)(2 * sq * a.Xo) * 4u, r1 = r0 + (unsigned)a.Xo * 4u;
   const unsigned bad0 = has0 ? 0u : 0x80000000u, bad1 = has1 ? 0u : 0x80000000u;
   const int nbase = (tseq >> G::LGS) + P * P * j;
+  if (a.accum) {
+    // a later segment of taps: y += this segment's samples, eight samples per row at a time (their y values requested
+    // before the first store; offsets that must not be stored read as zero).  (Offsets are recomputed rather than kept:
+    // arrays over all P samples would cost this kernel an occupancy step on its unsegmented launches too.)
+    auto offs = [&](int k, unsigned* f0, unsigned* f1) {
+      const int n = nbase + P * k;
+      const int t = x0 + n;
+      const int idx = t / a.stride;
+      const unsigned xo = (unsigned)idx * 4u, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
+      *f0 = (r0 + xo) | bad0 | badx;
+      *f1 = (r1 + xo) | bad1 | badx;
+    };
+    constexpr int KC = P < 8 ? P : 8;
+#pragma unroll
+    for (int k0 = 0; k0 < P; k0 += KC) {
+      float y0v[KC], y1v[KC];
+#pragma unroll
+      for (int u = 0; u < KC; ++u) {
+        unsigned f0, f1;
+        offs(k0 + u, &f0, &f1);
+        y0v[u] = buf_load_f32(orr, f0, 0);
+        y1v[u] = buf_load_f32(orr, f1, 0);
+      }
+#pragma unroll
+      for (int u = 0; u < KC; ++u) {
+        unsigned f0, f1;
+        offs(k0 + u, &f0, &f1);
+        buf_store_f32(v[k0 + u].x + y0v[u], orr, f0, 0);
+        buf_store_f32(v[k0 + u].y + y1v[u], orr, f1, 0);
+      }
+    }
+    return;
+  }
   if (a.stride == 1) {
 #pragma unroll
     for (int k = 0; k < P; ++k) {

@@ -90,9 +90,11 @@ size_t fc_workspace_bytes(const fc_plan* plan);
 int fc_plan_tile(const fc_plan* plan);
 
 /* Everything the byte layout of the kernel spectrum depends on besides the descriptor itself:
- * {tile, dilation phases, kernel segments, taps per segment, depthwise blocks, regrouped small groups,
+ * float32 1-D {tile, dilation phases, kernel segments, taps per segment, depthwise blocks, regrouped small groups,
  * wide-input kernel (2 = the many-channel pipeline: bin-major complex matrices for its per-bin GEMM), batch items
- * per workgroup}.  Two plans of equal descriptor (up to the batch size),
+ * per workgroup}; float32 2-D / 3-D {outer tile, x tile, middle tile (0 in 2-D), channel block, taps per segment of
+ * kernel axis 0, 1, 2 in tensor order (0 on an axis not cut into segments; the segments' spectra follow one another),
+ * column-pass variant}.  Two plans of equal descriptor (up to the batch size),
  * equal fc_kernel_spectrum_bytes() and equal layout words accept each other's fc_transform_kernel()
  * output -- what a multi-GPU caller checks before broadcasting one rank's spectrum (the planner looks at
  * the local batch size).  No counterpart in the reference (it re-transforms the kernel on every call,
@@ -148,7 +150,8 @@ int fc_wgrad_nd_plan_create(const fc_desc* conv_desc, fc_plan** out_plan);
 int fc_wgrad_nd(const fc_plan* plan, const float* x, const float* dy, float* dw, void* spectrum, void* workspace,
                 void* hip_stream);
 
-/* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable):
+/* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
+ * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the
  * fused kernels stores the 100 MHz wall clock at its phase boundaries (batch-sharing 1-D kernel: one
  * record of 16 stamps per wave, 16 wave slots per work item).  The stamped launch drains its loads at
@@ -163,7 +166,9 @@ long long fc_debug_grid(const fc_plan* plan);
  *                 slots are tiles, segments, depthwise blocks, block-diagonal group size, wide, dense, launches per
  *                 input chunk, running sums, out-chunks, work items
  *   float32 N-d:  outer tile, outer tiles, x tile, x tiles, middle tile (0 in 2-D), middle tiles, planes, channel
- *                 block, running sums
+ *                 block, running sums, segments of taps per kernel axis (3, tensor order: 1 on an axis not cut),
+ *                 taps per segment per kernel axis (3, tensor order: the kernel extent on an axis not cut); words of
+ *                 the third axis are 0 in 2-D
  *   float64 1-D:  tile, tiles, channel block
  *   float64 N-d:  tile per axis (3), tiles per axis (3), batch items per workgroup, channel block
  * Unused words are 0.  NULL plan or array: FC_ERR_INVALID. */

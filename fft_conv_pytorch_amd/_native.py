@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("FFTCONV_LIB") or os.path.join(_HERE, LIB_NAME)   # en
 
 FC_OK, FC_ERR_INVALID, FC_ERR_UNSUPPORTED, FC_ERR_HIP = 0, 1, 2, 3
 PAD_MODES = {"constant": 0, "zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 EXPORTS = (
     "fc_version", "fc_last_error", "fc_plan_create", "fc_plan_destroy", "fc_output_shape",
@@ -238,7 +238,10 @@ class Plan:
         self._lib, self._h, self.key = lib, handle, key
         self.device_index = int(device_index)
         import torch
-        self.dtype = torch.float64 if dtype_code == 1 else torch.float32
+        # dtype: of the signal and the output; weight_dtype: of the weight and bias the library reads (a float16 /
+        # bfloat16 plan reads and writes 16-bit x / y and takes a float32 weight and bias)
+        self.dtype = {1: torch.float64, 2: torch.float16, 3: torch.bfloat16}.get(dtype_code, torch.float32)
+        self.weight_dtype = torch.float64 if dtype_code == 1 else torch.float32
         out = (ctypes.c_int64 * 3)()
         lib.fc_output_shape(handle, ctypes.byref(out))
         self.out_spatial = tuple(int(out[i]) for i in range(ndim))

@@ -48,6 +48,7 @@ struct Conv1dArgs {
   int pos_shift;         // kernel segment: its first tap sits this many samples into the (dilated) kernel
   int add_out;           // 1: y += result (later chunk launches of such a plan; bias went with the first)
   unsigned long long* stamps;  // optional profiling hook: 16 timestamps per workgroup (null = off)
+  int io = 0;            // element type of x and y (fc_dtype: 0 float32, 2 float16, 3 bfloat16; Io<IO> in fft_engine.hpp)
 };
 
 // Branch-free padded load.  Outside [0, L) the index is remapped as a*pos + b with
@@ -87,20 +88,23 @@ __device__ __forceinline__ float load_padded(const float* __restrict__ row, int 
 
 // Byte offset of padded position pos inside a row starting at row_off, or an out-of-range offset
 // (buffer loads then return zero) -- the mask is consumed before the load, nothing stays live.
+// ES: bytes per sample.
+template <unsigned ES = 4>
 __device__ __forceinline__ unsigned padded_offset(unsigned row_off, int pos, int L, int pad, const PadMap& m, bool chan_ok) {
   const bool inside = (unsigned)pos < (unsigned)L;
   const int qm = (pos < 0) ? m.lo_a * pos + m.lo_b : m.hi_a * pos + m.hi_b;
   int q = inside ? pos : qm;
   q = min(max(q, 0), L - 1);
   const bool ok = chan_ok && (inside || (m.live && pos >= -pad && pos < L + pad));
-  return ok ? row_off + (unsigned)q * 4u : 0xFFFFFFFFu;
+  return ok ? row_off + (unsigned)q * ES : 0xFFFFFFFFu;
 }
 
 // The same for the zero-spread source of a transposed plan (see load_spread).
+template <unsigned ES = 4>
 __device__ __forceinline__ unsigned spread_offset(unsigned row_off, int pos, int L, int up, bool chan_ok) {
   const int q = pos / up;
   const bool ok = chan_ok && pos >= 0 && q * up == pos && q < L;
-  return ok ? row_off + (unsigned)q * 4u : 0xFFFFFFFFu;
+  return ok ? row_off + (unsigned)q * ES : 0xFFFFFFFFu;
 }
 
 // Profiling hook: lane 0 of each workgroup records the 100 MHz wall clock at phase boundaries.
@@ -108,9 +112,11 @@ __device__ __forceinline__ void stamp(unsigned long long* buf, int slot) {
   if (buf != nullptr && threadIdx.x == 0) buf[(size_t)blockIdx.x * 16 + slot] = __builtin_amdgcn_s_memrealtime();
 }
 
-template <int P, int S, int CIB, int NT>
+template <int P, int S, int CIB, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   constexpr int T = G::T;
   constexpr int NPI = CIB / 2;
   constexpr int SEQ_PER_IT = NT / G::TS;  // sequences processed concurrently
@@ -138,7 +144,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
   // buffer descriptors from uniform values only (no waterfall loops)
   const BufRsrc twA = make_rsrc(a.twA, (unsigned)(P * G::N2 * 8));
   const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
-  const BufRsrc xg = make_rsrc(a.x + ((size_t)b * a.Cin + (size_t)g * a.Cig) * a.L, (unsigned)a.Cig * (unsigned)a.L * 4u);
+  const BufRsrc xg = make_rsrc(io_ptr<IO>(a.x) + ((size_t)b * a.Cin + (size_t)g * a.Cig) * a.L, (unsigned)a.Cig * (unsigned)a.L * ES);
   const size_t wgroup = (size_t)a.Cog_pad * (a.Cig_pad / 2) * (T / 2);   // float4 per group
   const BufRsrc wg = make_rsrc(a.wspec + (size_t)g * wgroup, (unsigned)(wgroup * 16));
 
@@ -153,12 +159,12 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
       // (rows of phantom channels -- ci >= Cig in the last chunk, past the tensor for the last group -- are never
       // dereferenced: every load below goes through the group's buffer resource with an out-of-range offset for them)
       if (interior && has1) {
-        const unsigned v0 = ((unsigned)ci0 * (unsigned)a.L + (unsigned)(tile_pos + tseq)) * 4u;
-        const unsigned v1 = v0 + (unsigned)a.L * 4u;
+        const unsigned v0 = ((unsigned)ci0 * (unsigned)a.L + (unsigned)(tile_pos + tseq)) * ES;
+        const unsigned v1 = v0 + (unsigned)a.L * ES;
 #pragma unroll
         for (int n1 = 0; n1 < P; ++n1) {
-          v[n1].x = buf_load_f32(xg, v0, G::N2 * n1 * 4);
-          v[n1].y = buf_load_f32(xg, v1, G::N2 * n1 * 4);
+          v[n1].x = io.load(xg, v0, G::N2 * n1 * ES);
+          v[n1].y = io.load(xg, v1, G::N2 * n1 * ES);
         }
       } else {
         // border tile / odd channel count / zero-spread source of a transposed plan: a rolled loop
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
         // `ok ? row[q] : 0` cost one memory latency per sample -- 32 in a row on every tile of a plan with an odd
         // channel count or a spread source.
         f2* col = zin + sq * G::LSEQ + tseq;
-        const unsigned ro0 = (unsigned)ci0 * (unsigned)a.L * 4u, ro1 = ro0 + (unsigned)a.L * 4u;
+        const unsigned ro0 = (unsigned)ci0 * (unsigned)a.L * ES, ro1 = ro0 + (unsigned)a.L * ES;
         constexpr int CH = P < 8 ? P : 8;
 #pragma unroll 1
         for (int c0 = 0; c0 < P; c0 += CH) {
@@ -178,10 +184,10 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
 #pragma unroll
           for (int u = 0; u < CH; ++u) {
             const int pos = tile_pos + G::N2 * (c0 + u) + tseq;
-            const unsigned o0 = (a.up == 1) ? padded_offset(ro0, pos, a.L, a.pad, pm, has0) : spread_offset(ro0, pos, a.L, a.up, has0);
-            const unsigned o1 = (a.up == 1) ? padded_offset(ro1, pos, a.L, a.pad, pm, has1) : spread_offset(ro1, pos, a.L, a.up, has1);
-            t[u].x = buf_load_f32(xg, o0, 0);
-            t[u].y = buf_load_f32(xg, o1, 0);
+            const unsigned o0 = (a.up == 1) ? padded_offset<ES>(ro0, pos, a.L, a.pad, pm, has0) : spread_offset<ES>(ro0, pos, a.L, a.up, has0);
+            const unsigned o1 = (a.up == 1) ? padded_offset<ES>(ro1, pos, a.L, a.pad, pm, has1) : spread_offset<ES>(ro1, pos, a.L, a.up, has1);
+            t[u].x = io.load(xg, o0, 0);
+            t[u].y = io.load(xg, o1, 0);
           }
 #pragma unroll
           for (int u = 0; u < CH; ++u) col[(c0 + u) * G::RS] = t[u];
@@ -345,8 +351,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
     const int t0 = tile * a.V;
     const int limit = min(a.V, a.Lfull - t0);      // valid samples of this tile
     const int nbase = o1 + P * P * j;
-    if (a.add_out) {
-      // chunk-by-chunk plan, chunks after the first: accumulate into the output already in HBM
+    if (IO == IO_F32 && a.add_out) {
+      // chunk-by-chunk plan, chunks after the first: accumulate into the output already in HBM (float32 plans only)
       float* y0 = a.y + ((size_t)b * a.Cout + cg0) * a.Lout;
       float* y1 = y0 + a.Lout;
 #pragma unroll
@@ -360,28 +366,28 @@ __global__ __launch_bounds__(NT, 2) void conv1d_fused_kernel(const Conv1dArgs a)
         }
       }
     } else if (a.stride == 1) {
-      float* y0 = a.y + ((size_t)b * a.Cout + cg0) * a.Lout + t0 + nbase;
-      float* y1 = y0 + a.Lout;
+      auto* y0 = io_ptr<IO>(a.y) + ((size_t)b * a.Cout + cg0) * a.Lout + t0 + nbase;
+      auto* y1 = y0 + a.Lout;
       if (has1) {
 #pragma unroll
         for (int k = 0; k < P; ++k)
-          if (nbase + P * k < limit) { y0[P * k] = v[k].x + bias0; y1[P * k] = v[k].y + bias1; }
+          if (nbase + P * k < limit) { y0[P * k] = io.out(v[k].x + bias0); y1[P * k] = io.out(v[k].y + bias1); }
       } else if (has0) {
 #pragma unroll
         for (int k = 0; k < P; ++k)
-          if (nbase + P * k < limit) y0[P * k] = v[k].x + bias0;
+          if (nbase + P * k < limit) y0[P * k] = io.out(v[k].x + bias0);
       }
     } else {
-      float* y0 = a.y + ((size_t)b * a.Cout + cg0) * a.Lout;
-      float* y1 = y0 + a.Lout;
+      auto* y0 = io_ptr<IO>(a.y) + ((size_t)b * a.Cout + cg0) * a.Lout;
+      auto* y1 = y0 + a.Lout;
 #pragma unroll
       for (int k = 0; k < P; ++k) {
         const int n = nbase + P * k;
         const int t = t0 + n;
         const int idx = t / a.stride;
         if (n < limit && idx * a.stride == t) {
-          if (has0) y0[idx] = v[k].x + bias0;
-          if (has1) y1[idx] = v[k].y + bias1;
+          if (has0) y0[idx] = io.out(v[k].x + bias0);
+          if (has1) y1[idx] = io.out(v[k].y + bias1);
         }
       }
     }

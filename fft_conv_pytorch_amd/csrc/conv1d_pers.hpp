@@ -55,7 +55,7 @@ __device__ __forceinline__ void stamp_clock(unsigned long long* buf, int item, i
 // PH2's 8 bytes at a 16-byte pitch cost partial-line write-backs and re-fetches: 1.6x the output bytes written at cfgD).
 // The mix contracts the same 8 x 8 matrix per bin; its slots are phases and its steps single output channels.
 template <int P, int S, int CIB, int NB, int NT, bool PHASES = false, int RING = 2, bool DIAG = false, bool SEG = false, bool PH2 = false,
-          bool STAMPS = false, bool PH4 = false>
+          bool STAMPS = false, bool PH4 = false, int IO = IO_F32>
 __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs pa) {
   static_assert(!PH2 || (PHASES && !DIAG && !SEG && S == 1 && CIB == 8), "paired phases: plain phase build on a P*P tile");
   static_assert(!PH4 || (PHASES && !DIAG && !SEG && !PH2 && S == 1 && CIB == 8 && NB == 4), "phase quads: 8 channels x 2 phase pairs");
@@ -71,6 +71,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   constexpr int TWN = P * G::N2;            // pass-A twiddle table entries
   extern __shared__ __attribute__((aligned(16))) f2 lds[];
   const Conv1dArgs& a = pa.c;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;         // bytes per sample of x and y
   auto stampi = [&](int item, int slot) { if constexpr (STAMPS) stamp_item(a.stamps, item, slot); };
   auto stampc = [&](int item, int slot) { if constexpr (STAMPS) stamp_clock(a.stamps, item, slot); };
   const int nph = PHASES ? a.ph : 1;          // dilation phases (compile-time 1 in the plain build)
@@ -107,40 +109,40 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
     const int pos0 = tile * a.V * nph + phase - a.pad + (SEG ? a.pos_shift : 0);   // source position of the tile's first sample
     const bool interior = (pos0 >= 0) && (pos0 + (T - 1) * nph < a.L);
     const bool act_in = nb < wi.nbc;
-    const float* xbase = a.x + ((size_t)bfirst * a.Cin + (size_t)g * a.Cig) * a.L;
-    const BufRsrc xg = make_rsrc(xbase, (unsigned)(((size_t)(blast - bfirst) * a.Cin + a.Cig) * a.L * 4));
+    const auto* xbase = io_ptr<IO>(a.x) + ((size_t)bfirst * a.Cin + (size_t)g * a.Cig) * a.L;
+    const BufRsrc xg = make_rsrc(xbase, (unsigned)(((size_t)(blast - bfirst) * a.Cin + a.Cig) * a.L * ES));
     const int ci0 = 2 * pr;
     // (a depthwise plan's last block may reach past the last channel)
     const bool has0 = act_in && ci0 < a.Cig && (!DIAG || g * CIB + ci0 < a.Cin);
     const bool has1 = act_in && ci0 + 1 < a.Cig && (!DIAG || g * CIB + ci0 + 1 < a.Cin);
-    const unsigned ro0 = ((unsigned)(b - bfirst) * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * 4u;
-    const unsigned ro1 = ro0 + (unsigned)a.L * 4u;
+    const unsigned ro0 = ((unsigned)(b - bfirst) * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * ES;
+    const unsigned ro1 = ro0 + (unsigned)a.L * ES;
     if constexpr (PH4) {
       // wave = channel pr of batch item bA, phases phA .. phA + 3 (phA a multiple of 4: items hold four slots)
       const int bA = wi.b0 / nph, phA = wi.b0 - bA * nph;
       const int posA = wi.tile * a.V * nph + phA - a.pad;
       const bool all_in = (posA >= 0) && (posA + 3 + (T - 1) * nph < a.L);
       const bool chan = pr < a.Cig;
-      const unsigned rA = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * 4u;
-      // 16-byte accesses need the row base and the tile position on 16-byte boundaries (uniform test; else 4-byte loads)
-      const bool al16 = (((size_t)xbase | ((size_t)a.L * 4) | ((size_t)(unsigned)posA * 4)) & 15) == 0;
+      const unsigned rA = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * ES;
+      // 4-sample accesses need the row base and the tile position on 4-sample boundaries (uniform test; else 1-sample loads)
+      const bool al16 = (((size_t)xbase | ((size_t)a.L * ES) | ((size_t)(unsigned)posA * ES)) & (4 * ES - 1)) == 0;
       if (all_in && al16) {
-        const unsigned q0 = chan ? rA + (unsigned)(posA + (tid & 63) * nph) * 4u : 0x80000000u;
-        const unsigned step4 = 256u * (unsigned)nph;
+        const unsigned q0 = chan ? rA + (unsigned)(posA + (tid & 63) * nph) * ES : 0x80000000u;
+        const unsigned step4 = 64u * ES * (unsigned)nph;
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) {
-          const f4 q = buf_load_f32x4(xg, q0, step4 * m);
+          const f4 q = io.load4(xg, q0, step4 * m);
           v[2 * m] = q.xy; v[2 * m + 1] = q.zw;
         }
         return;        // (the halves are traded in fetch_finish)
       }
       // border tiles / unaligned rows: per-sample padded loads of this half-wave's two phases
-      const unsigned ro = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * 4u;
+      const unsigned ro = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * ES;
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
         const int pos = posA + 2 * nb + (G::N2 * n1 + tseq) * nph;
-        v[n1].x = buf_load_f32(xg, padded_offset(ro, pos, a.L, a.pad, pm, chan), 0);
-        v[n1].y = buf_load_f32(xg, padded_offset(ro, pos + 1, a.L, a.pad, pm, chan), 0);
+        v[n1].x = io.load(xg, padded_offset<ES>(ro, pos, a.L, a.pad, pm, chan), 0);
+        v[n1].y = io.load(xg, padded_offset<ES>(ro, pos + 1, a.L, a.pad, pm, chan), 0);
       }
       return;
     }
@@ -153,19 +155,19 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         // lane L of the wave asks for (phase, phase + 1) at the positions 64 m + L, m = 0 .. P/2 - 1; the swap hands
         // lanes 0-31 (even phase) the even-phase halves of both lane groups and lanes 32-63 the odd-phase halves:
         // rows n1 = 2m and 2m + 1 of this thread's sequence
-        const unsigned rA = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * 4u;
-        const unsigned q0 = rA + (unsigned)(posA + (tid & 63) * nph) * 4u, q1 = q0 + (unsigned)a.L * 4u;
-        const unsigned step2 = 256u * (unsigned)nph;
+        const unsigned rA = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * ES;
+        const unsigned q0 = rA + (unsigned)(posA + (tid & 63) * nph) * ES, q1 = q0 + (unsigned)a.L * ES;
+        const unsigned step2 = 64u * ES * (unsigned)nph;
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) {
-          f2 cx = buf_load_f32x2(xg, q0, step2 * m), cy = buf_load_f32x2(xg, q1, step2 * m);
+          f2 cx = io.load2(xg, q0, step2 * m), cy = io.load2(xg, q1, step2 * m);
           v[2 * m].x = cx.x; v[2 * m + 1].x = cx.y; v[2 * m].y = cy.x; v[2 * m + 1].y = cy.y;
         }
         return;        // (the halves are traded in fetch_finish, when the item starts: here nothing may wait for the loads)
       }
     }
     if (interior && has1 && !PHASES) {
-      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq) * 4u, v1 = ro1 + (unsigned)(pos0 + tseq) * 4u;
+      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq) * ES, v1 = ro1 + (unsigned)(pos0 + tseq) * ES;
 #if FC_DIAG == 7
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) { v[n1] = mk2(1e-3f * n1, (float)tseq); asm volatile("" : "+v"(v[n1])); }
@@ -174,23 +176,23 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
 #endif
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
-        v[n1].x = buf_load_f32(xg, v0, G::N2 * n1 * 4);
-        v[n1].y = buf_load_f32(xg, v1, G::N2 * n1 * 4);
+        v[n1].x = io.load(xg, v0, G::N2 * n1 * ES);
+        v[n1].y = io.load(xg, v1, G::N2 * n1 * ES);
       }
     } else if (interior && has1) {
-      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq * nph) * 4u, v1 = ro1 + (unsigned)(pos0 + tseq * nph) * 4u;
-      const unsigned step = (unsigned)(G::N2 * 4) * (unsigned)nph;
+      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq * nph) * ES, v1 = ro1 + (unsigned)(pos0 + tseq * nph) * ES;
+      const unsigned step = (unsigned)(G::N2 * ES) * (unsigned)nph;
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
-        v[n1].x = buf_load_f32(xg, v0, step * n1);
-        v[n1].y = buf_load_f32(xg, v1, step * n1);
+        v[n1].x = io.load(xg, v0, step * n1);
+        v[n1].y = io.load(xg, v1, step * n1);
       }
     } else {
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
         const int pos = pos0 + (G::N2 * n1 + tseq) * nph;
-        v[n1].x = buf_load_f32(xg, padded_offset(ro0, pos, a.L, a.pad, pm, has0), 0);
-        v[n1].y = buf_load_f32(xg, padded_offset(ro1, pos, a.L, a.pad, pm, has1), 0);
+        v[n1].x = io.load(xg, padded_offset<ES>(ro0, pos, a.L, a.pad, pm, has0), 0);
+        v[n1].y = io.load(xg, padded_offset<ES>(ro1, pos, a.L, a.pad, pm, has1), 0);
       }
     }
   };
@@ -203,9 +205,9 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
       const int bA = wi.b0 / nph, phA = wi.b0 - bA * nph;
       const int posA = wi.tile * a.V * nph + phA - a.pad;
       const int bfirst = wi.b0 / nph;
-      const float* xbase = a.x + ((size_t)bfirst * a.Cin + (size_t)(wi.goc / a.n_ochunks) * a.Cig) * a.L;
+      const auto* xbase = io_ptr<IO>(a.x) + ((size_t)bfirst * a.Cin + (size_t)(wi.goc / a.n_ochunks) * a.Cig) * a.L;
       const bool all_in = (posA >= 0) && (posA + 3 + (T - 1) * nph < a.L);
-      const bool al16 = (((size_t)xbase | ((size_t)a.L * 4) | ((size_t)(unsigned)posA * 4)) & 15) == 0;
+      const bool al16 = (((size_t)xbase | ((size_t)a.L * ES) | ((size_t)(unsigned)posA * ES)) & (4 * ES - 1)) == 0;
       if (all_in && al16) {
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) { swap_halves_c<0>(v[2 * m], v[2 * m + 1]); swap_halves_c<1>(v[2 * m], v[2 * m + 1]); }
@@ -561,8 +563,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
       const int t0 = tile * a.V;                                      // in samples of this phase
       const int limit = min(a.V, (a.Lfull - phase + nph - 1) / nph - t0);
       const int nbase = o1 + P * P * j;
-      float* y0 = a.y + ((size_t)b * a.Cout + cg0) * a.Lout + (size_t)(t0 + nbase) * nph + phase;
-      float* y1 = y0 + a.Lout;
+      auto* y0 = io_ptr<IO>(a.y) + ((size_t)b * a.Cout + cg0) * a.Lout + (size_t)(t0 + nbase) * nph + phase;
+      auto* y1 = y0 + a.Lout;
       if constexpr (DIAG) {
         // depthwise: the last block may hold fewer than 8 channels, so every row is guarded
         const int ystep = P * nph;
@@ -570,8 +572,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
 #pragma unroll
         for (int k = 0; k < P; ++k)
           if (nbase + P * k < limit) {
-            if (ok0) y0[ystep * k] = v[k].x + (addo ? y0[ystep * k] : bias0);
-            if (ok1) y1[ystep * k] = v[k].y + (addo ? y1[ystep * k] : bias1);
+            if (ok0) y0[ystep * k] = io.out(v[k].x + (addo ? io.in(y0[ystep * k]) : bias0));
+            if (ok1) y1[ystep * k] = io.out(v[k].y + (addo ? io.in(y1[ystep * k]) : bias1));
           }
       } else if (SEG && a.add_out) {
         // later segments of a long kernel accumulate into the output of the first
@@ -584,8 +586,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         // valid row of stores, later k are outside for every lane (ka is wave-uniform).  Buffer stores: one 32-bit
         // offset register per output row, the step P k as the instruction's immediate.
         const int ka = limit >= P ? (limit - P) / P + 1 : 0;
-        const BufRsrc yr = make_rsrc(a.y + ((size_t)b * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * 4));
-        const unsigned vo0 = (unsigned)((size_t)(2 * pr) * a.Lout + (size_t)(t0 + nbase)) * 4u, vo1 = vo0 + (unsigned)a.Lout * 4u;
+        const BufRsrc yr = make_rsrc(io_ptr<IO>(a.y) + ((size_t)b * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * ES));
+        const unsigned vo0 = (unsigned)((size_t)(2 * pr) * a.Lout + (size_t)(t0 + nbase)) * ES, vo1 = vo0 + (unsigned)a.Lout * ES;
         // Blocks of 8 rows: a block below ka is straight-line code behind ONE scalar branch (per-row tests, even
         // wave-uniform ones, cost more instructions than the stores they guard); only the block that holds row ka
         // tests its rows, and there the lanes past the window get an offset outside the resource (store dropped).
@@ -599,8 +601,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
 #else
             static_for<k0, k0 + 8>([&](auto kc) {
               constexpr int k = decltype(kc)::value;
-              buf_store_f32(v[k].x + bias0, yr, vo0, P * k * 4);
-              buf_store_f32(v[k].y + bias1, yr, vo1, P * k * 4);
+              io.store(v[k].x + bias0, yr, vo0, P * k * ES);
+              io.store(v[k].y + bias1, yr, vo1, P * k * ES);
             });
 #endif
           } else if (ka >= k0) {
@@ -608,8 +610,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
               constexpr int k = decltype(kc)::value;
               if (k <= ka) {
                 const unsigned dead = (nbase + P * k < limit) ? 0u : 0x80000000u;
-                buf_store_f32(v[k].x + bias0, yr, vo0 | dead, P * k * 4);
-                buf_store_f32(v[k].y + bias1, yr, vo1 | dead, P * k * 4);
+                io.store(v[k].x + bias0, yr, vo0 | dead, P * k * ES);
+                io.store(v[k].y + bias1, yr, vo1 | dead, P * k * ES);
               }
             });
           }
@@ -617,7 +619,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
       } else if (!PHASES) {
 #pragma unroll
         for (int k = 0; k < P; ++k)
-          if (nbase + P * k < limit) { y0[P * k] = v[k].x + bias0; y1[P * k] = v[k].y + bias1; }
+          if (nbase + P * k < limit) { y0[P * k] = io.out(v[k].x + bias0); y1[P * k] = io.out(v[k].y + bias1); }
       } else if constexpr (PH4) {
         // all four phases of a position leave as 16 bytes: after the trade lane L of the wave holds (phases 0, 1) in
         // row 2m and (phases 2, 3) in row 2m + 1 of sample 64 m + L.  Phases past the end of the row are shorter by one.
@@ -625,11 +627,11 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         int lim[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) lim[j] = min(a.V, (a.Lfull - (phA + j) + nph - 1) / nph - t0);
-        const BufRsrc yr = make_rsrc(a.y + ((size_t)bA * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * 4));
+        const BufRsrc yr = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bA * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * ES));
         const int L64 = tid & 63;
-        const unsigned w0 = (unsigned)(((size_t)pr * a.Lout + (size_t)(t0 + L64) * nph + phA) * 4);
-        const unsigned step4 = 256u * (unsigned)nph;
-        const bool al16 = (((size_t)a.y | ((size_t)a.Lout * 4)) & 15) == 0;
+        const unsigned w0 = (unsigned)(((size_t)pr * a.Lout + (size_t)(t0 + L64) * nph + phA) * ES);
+        const unsigned step4 = 64u * ES * (unsigned)nph;
+        const bool al16 = (((size_t)a.y | ((size_t)a.Lout * ES)) & (4 * ES - 1)) == 0;
         const int mfull = (al16 && lim[3] >= 64) ? (lim[3] - 64) / 64 + 1 : 0;       // rows m below it: every lane, every phase valid
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) { swap_halves_c<0>(v[2 * m], v[2 * m + 1]); swap_halves_c<1>(v[2 * m], v[2 * m + 1]); }
@@ -638,20 +640,19 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
           if (mfull >= m0 + 4) {
             static_for<m0, m0 + 4>([&](auto mc) {
               constexpr int m = decltype(mc)::value;
-              u32x4 d;
-              d.x = __float_as_uint(v[2 * m].x + bias0); d.y = __float_as_uint(v[2 * m].y + bias0);
-              d.z = __float_as_uint(v[2 * m + 1].x + bias0); d.w = __float_as_uint(v[2 * m + 1].y + bias0);
-              __builtin_amdgcn_raw_buffer_store_b128(d, yr, w0, step4 * m, 0);
+              f4 d;
+              d.x = v[2 * m].x + bias0; d.y = v[2 * m].y + bias0; d.z = v[2 * m + 1].x + bias0; d.w = v[2 * m + 1].y + bias0;
+              io.store4(d, yr, w0, step4 * m);
             });
           } else if (64 * m0 < lim[0]) {
             static_for<m0, m0 + 4>([&](auto mc) {
               constexpr int m = decltype(mc)::value;
               if (64 * m < lim[0]) {
                 const int n = 64 * m + L64;
-                buf_store_f32(v[2 * m].x + bias0, yr, w0 | (n < lim[0] ? 0u : 0x80000000u), step4 * m);
-                buf_store_f32(v[2 * m].y + bias0, yr, (w0 + 4u) | (n < lim[1] ? 0u : 0x80000000u), step4 * m);
-                buf_store_f32(v[2 * m + 1].x + bias0, yr, (w0 + 8u) | (n < lim[2] ? 0u : 0x80000000u), step4 * m);
-                buf_store_f32(v[2 * m + 1].y + bias0, yr, (w0 + 12u) | (n < lim[3] ? 0u : 0x80000000u), step4 * m);
+                io.store(v[2 * m].x + bias0, yr, w0 | (n < lim[0] ? 0u : 0x80000000u), step4 * m);
+                io.store(v[2 * m].y + bias0, yr, (w0 + ES) | (n < lim[1] ? 0u : 0x80000000u), step4 * m);
+                io.store(v[2 * m + 1].x + bias0, yr, (w0 + 2 * ES) | (n < lim[2] ? 0u : 0x80000000u), step4 * m);
+                io.store(v[2 * m + 1].y + bias0, yr, (w0 + 3 * ES) | (n < lim[3] ? 0u : 0x80000000u), step4 * m);
               }
             });
           }
@@ -661,10 +662,10 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         // phase, odd phase) of sample 64 m + L.  The odd phase may be one sample shorter at the very end of a row.
         const int vbA = wi.b0 + 2 * (wv / NPI), bA = vbA / nph, phA = vbA - bA * nph;
         const int limA = min(a.V, (a.Lfull - phA + nph - 1) / nph - t0), limB = min(a.V, (a.Lfull - phA - 1 + nph - 1) / nph - t0);
-        const BufRsrc yr = make_rsrc(a.y + ((size_t)bA * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * 4));
+        const BufRsrc yr = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bA * a.Cout + (size_t)(g * a.Cog + oc * a.cob)) * a.Lout, (unsigned)((size_t)a.cob * a.Lout * ES));
         const int L64 = tid & 63;
-        const unsigned w0 = (unsigned)(((size_t)(2 * pr) * a.Lout + (size_t)(t0 + L64) * nph + phA) * 4), w1 = w0 + (unsigned)a.Lout * 4u;
-        const unsigned step2 = 256u * (unsigned)nph;
+        const unsigned w0 = (unsigned)(((size_t)(2 * pr) * a.Lout + (size_t)(t0 + L64) * nph + phA) * ES), w1 = w0 + (unsigned)a.Lout * ES;
+        const unsigned step2 = 64u * ES * (unsigned)nph;
         const int mfull = limB >= 64 ? (limB - 64) / 64 + 1 : 0;        // rows m below it: every lane valid in both phases
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) { swap_halves_c<0>(v[2 * m], v[2 * m + 1]); swap_halves_c<1>(v[2 * m], v[2 * m + 1]); }
@@ -673,8 +674,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
           if (mfull >= m0 + 4) {
             static_for<m0, m0 + 4>([&](auto mc) {
               constexpr int m = decltype(mc)::value;
-              buf_store_f32x2(mk2(v[2 * m].x + bias0, v[2 * m + 1].x + bias0), yr, w0, step2 * m);
-              buf_store_f32x2(mk2(v[2 * m].y + bias1, v[2 * m + 1].y + bias1), yr, w1, step2 * m);
+              io.store2(mk2(v[2 * m].x + bias0, v[2 * m + 1].x + bias0), yr, w0, step2 * m);
+              io.store2(mk2(v[2 * m].y + bias1, v[2 * m + 1].y + bias1), yr, w1, step2 * m);
             });
           } else if (64 * m0 < limA) {
             static_for<m0, m0 + 4>([&](auto mc) {
@@ -682,10 +683,10 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
               if (64 * m < limA) {
                 const int n = 64 * m + L64;
                 const unsigned dA = n < limA ? 0u : 0x80000000u, dB = n < limB ? 0u : 0x80000000u;
-                buf_store_f32(v[2 * m].x + bias0, yr, w0 | dA, step2 * m);
-                buf_store_f32(v[2 * m + 1].x + bias0, yr, (w0 + 4u) | dB, step2 * m);
-                buf_store_f32(v[2 * m].y + bias1, yr, w1 | dA, step2 * m);
-                buf_store_f32(v[2 * m + 1].y + bias1, yr, (w1 + 4u) | dB, step2 * m);
+                io.store(v[2 * m].x + bias0, yr, w0 | dA, step2 * m);
+                io.store(v[2 * m + 1].x + bias0, yr, (w0 + ES) | dB, step2 * m);
+                io.store(v[2 * m].y + bias1, yr, w1 | dA, step2 * m);
+                io.store(v[2 * m + 1].y + bias1, yr, (w1 + ES) | dB, step2 * m);
               }
             });
           }
@@ -694,7 +695,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         const int ystep = P * nph;
 #pragma unroll
         for (int k = 0; k < P; ++k)
-          if (nbase + P * k < limit) { y0[ystep * k] = v[k].x + bias0; y1[ystep * k] = v[k].y + bias1; }
+          if (nbase + P * k < limit) { y0[ystep * k] = io.out(v[k].x + bias0); y1[ystep * k] = io.out(v[k].y + bias1); }
       }
     }
     stampi(it, 10);

@@ -13,7 +13,7 @@
 
 namespace fc {
 
-template <int P, int S, int NB, int NT>
+template <int P, int S, int NB, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs pa) {
   using G = Geo<P, S>;
   constexpr int T = G::T;
@@ -28,6 +28,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs
   constexpr int TWN = P * G::N2;
   extern __shared__ __attribute__((aligned(16))) f2 lds[];
   const Conv1dArgs& a = pa.c;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;         // bytes per sample of x and y
 
   const int tid = threadIdx.x;
   const int sq = tid / G::TS, tseq = tid % G::TS;
@@ -43,8 +45,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs
   const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
   const size_t wgroup = (size_t)a.Cog_pad * (a.Cig_pad / 2) * (T / 2);   // float4 per group
   const BufRsrc wg = make_rsrc(a.wspec + (size_t)g * wgroup, (unsigned)(wgroup * 16));
-  const float* xbase = a.x + ((size_t)wi.b0 * a.Cin + (size_t)g * a.Cig) * a.L;
-  const BufRsrc xg = make_rsrc(xbase, (unsigned)(((size_t)(wi.nbc - 1) * a.Cin + a.Cig) * a.L * 4));
+  const auto* xbase = io_ptr<IO>(a.x) + ((size_t)wi.b0 * a.Cin + (size_t)g * a.Cig) * a.L;
+  const BufRsrc xg = make_rsrc(xbase, (unsigned)(((size_t)(wi.nbc - 1) * a.Cin + a.Cig) * a.L * ES));
   const int tile_pos = wi.tile * a.V - a.pad;
   const bool interior = (tile_pos >= 0) && (tile_pos + T <= a.L);
   const int n_ichunks = a.Cig_pad / CIB;
@@ -77,14 +79,14 @@ __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs
       f2 v[P];
       const int ci0 = ic * CIB + 2 * pr;
       const bool has0 = ci0 < a.Cig, has1 = ci0 + 1 < a.Cig;
-      const unsigned ro0 = ((unsigned)nb * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * 4u;
-      const unsigned ro1 = ro0 + (unsigned)a.L * 4u;
+      const unsigned ro0 = ((unsigned)nb * (unsigned)a.Cin + (unsigned)ci0) * (unsigned)a.L * ES;
+      const unsigned ro1 = ro0 + (unsigned)a.L * ES;
       if (interior && has1) {
-        const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * 4u, v1 = ro1 + (unsigned)(tile_pos + tseq) * 4u;
+        const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * ES, v1 = ro1 + (unsigned)(tile_pos + tseq) * ES;
 #pragma unroll
         for (int n1 = 0; n1 < P; ++n1) {
-          v[n1].x = buf_load_f32(xg, v0, G::N2 * n1 * 4);
-          v[n1].y = buf_load_f32(xg, v1, G::N2 * n1 * 4);
+          v[n1].x = io.load(xg, v0, G::N2 * n1 * ES);
+          v[n1].y = io.load(xg, v1, G::N2 * n1 * ES);
         }
       } else {
         // The per-sample padded offsets do not depend on the chunk: left alone, hipcc hoists all 2 * P of them
@@ -95,8 +97,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs
 #pragma unroll
         for (int n1 = 0; n1 < P; ++n1) {
           const int pos = tpos + G::N2 * n1 + tseq;
-          v[n1].x = buf_load_f32(xg, padded_offset(ro0, pos, a.L, a.pad, pm, has0), 0);
-          v[n1].y = buf_load_f32(xg, padded_offset(ro1, pos, a.L, a.pad, pm, has1), 0);
+          v[n1].x = io.load(xg, padded_offset<ES>(ro0, pos, a.L, a.pad, pm, has0), 0);
+          v[n1].y = io.load(xg, padded_offset<ES>(ro1, pos, a.L, a.pad, pm, has1), 0);
         }
       }
       passA_fft_twiddle_store_lds_lowreg<G, -1>(v, zseq, tseq, twl);
@@ -222,11 +224,11 @@ __global__ __launch_bounds__(NT, 2) void conv1d_wide_kernel(const Conv1dPersArgs
     const int t0 = wi.tile * a.V;
     const int limit = min(a.V, a.Lfull - t0);
     const int nbase = o1 + P * P * j;
-    float* y0 = a.y + ((size_t)(wi.b0 + nb) * a.Cout + cg0) * a.Lout + t0 + nbase;
-    float* y1 = y0 + a.Lout;
+    auto* y0 = io_ptr<IO>(a.y) + ((size_t)(wi.b0 + nb) * a.Cout + cg0) * a.Lout + t0 + nbase;
+    auto* y1 = y0 + a.Lout;
 #pragma unroll
     for (int k = 0; k < P; ++k)
-      if (nbase + P * k < limit) { y0[P * k] = v[k].x + bias0; y1[P * k] = v[k].y + bias1; }
+      if (nbase + P * k < limit) { y0[P * k] = io.out(v[k].x + bias0); y1[P * k] = io.out(v[k].y + bias1); }
   }
 }
 

@@ -33,12 +33,15 @@ struct DenseArgs {
   int L, pad, pad_mode, V, ntiles, Lfull, Lout;
   int m0, mcount;        // this slab: rows m0 .. m0 + mcount - 1 of M = B * ntiles (row m = batch m / ntiles, tile m % ntiles)
   int cus;               // CUs of the device (grid of the persistent GEMM)
+  int io = 0;            // element type of x and y (fc_dtype: 0 float32, 2 float16, 3 bfloat16; Io<IO> in fft_engine.hpp)
 };
 
 // ------------------------------------------------------------------------------------------ dense_fwd
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void dense_fwd_kernel(const DenseArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   constexpr int T = G::T, NF = T / 2 + 1;
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS, "one thread slot per point group of every sequence");
@@ -60,24 +63,24 @@ __global__ __launch_bounds__(NT) void dense_fwd_kernel(const DenseArgs a) {
   f2 v[P];
   {
     const PadMap pm = make_padmap(a.pad_mode, a.L);
-    const float* xbase = a.x + ((size_t)b * a.Cin + (size_t)g * a.Cig) * a.L;
-    const BufRsrc xg = make_rsrc(xbase, (unsigned)((size_t)a.Cig * a.L * 4));
+    const auto* xbase = io_ptr<IO>(a.x) + ((size_t)b * a.Cin + (size_t)g * a.Cig) * a.L;
+    const BufRsrc xg = make_rsrc(xbase, (unsigned)((size_t)a.Cig * a.L * ES));
     const int pos0 = tile * a.V - a.pad;
     const bool interior = (pos0 >= 0) && (pos0 + T <= a.L);
-    const unsigned ro0 = (unsigned)ci0 * (unsigned)a.L * 4u, ro1 = ro0 + (unsigned)a.L * 4u;
+    const unsigned ro0 = (unsigned)ci0 * (unsigned)a.L * ES, ro1 = ro0 + (unsigned)a.L * ES;
     if (interior && has1) {
-      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq) * 4u, v1 = ro1 + (unsigned)(pos0 + tseq) * 4u;
+      const unsigned v0 = ro0 + (unsigned)(pos0 + tseq) * ES, v1 = ro1 + (unsigned)(pos0 + tseq) * ES;
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
-        v[n1].x = buf_load_f32(xg, v0, G::N2 * n1 * 4);
-        v[n1].y = buf_load_f32(xg, v1, G::N2 * n1 * 4);
+        v[n1].x = io.load(xg, v0, G::N2 * n1 * ES);
+        v[n1].y = io.load(xg, v1, G::N2 * n1 * ES);
       }
     } else {
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
         const int pos = pos0 + G::N2 * n1 + tseq;
-        v[n1].x = buf_load_f32(xg, padded_offset(ro0, pos, a.L, a.pad, pm, has0), 0);
-        v[n1].y = buf_load_f32(xg, padded_offset(ro1, pos, a.L, a.pad, pm, has1), 0);
+        v[n1].x = io.load(xg, padded_offset<ES>(ro0, pos, a.L, a.pad, pm, has0), 0);
+        v[n1].y = io.load(xg, padded_offset<ES>(ro1, pos, a.L, a.pad, pm, has1), 0);
       }
     }
   }
@@ -112,9 +115,11 @@ __global__ __launch_bounds__(NT) void dense_fwd_kernel(const DenseArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ dense_inv
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void dense_inv_kernel(const DenseArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   constexpr int T = G::T, NF = T / 2 + 1;
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS, "one thread slot per point group of every sequence");
@@ -177,36 +182,36 @@ __global__ __launch_bounds__(NT) void dense_inv_kernel(const DenseArgs a) {
       // that holds row ka with per-row tests and an out-of-range offset for lanes past the window; channels that do
       // not exist (padding of the pair) start from an offset outside the resource
       const int ka = limit >= P ? (limit - P) / P + 1 : 0;
-      const BufRsrc yr = make_rsrc(a.y + ((size_t)b * a.Cout + (size_t)g * a.Cog) * a.Lout, (unsigned)((size_t)a.Cog * a.Lout * 4));
-      const unsigned vo = (unsigned)(((size_t)co0 * a.Lout + (size_t)(t0 + nbase)) * 4);
-      const unsigned vo0 = ok0 ? vo : 0x80000000u, vo1 = ok1 ? vo + (unsigned)a.Lout * 4u : 0x80000000u;
+      const BufRsrc yr = make_rsrc(io_ptr<IO>(a.y) + ((size_t)b * a.Cout + (size_t)g * a.Cog) * a.Lout, (unsigned)((size_t)a.Cog * a.Lout * ES));
+      const unsigned vo = (unsigned)(((size_t)co0 * a.Lout + (size_t)(t0 + nbase)) * ES);
+      const unsigned vo0 = ok0 ? vo : 0x80000000u, vo1 = ok1 ? vo + (unsigned)a.Lout * ES : 0x80000000u;
       static_for<0, P / 8>([&](auto bc) {
         constexpr int k0 = 8 * decltype(bc)::value;
         if (ka >= k0 + 8) {
           static_for<k0, k0 + 8>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            buf_store_f32(v[k].x + bias0, yr, vo0, P * k * 4);
-            buf_store_f32(v[k].y + bias1, yr, vo1, P * k * 4);
+            io.store(v[k].x + bias0, yr, vo0, P * k * ES);
+            io.store(v[k].y + bias1, yr, vo1, P * k * ES);
           });
         } else if (ka >= k0) {
           static_for<k0, k0 + 8>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             if (k <= ka) {
               const unsigned dead = (nbase + P * k < limit) ? 0u : 0x80000000u;
-              buf_store_f32(v[k].x + bias0, yr, vo0 | dead, P * k * 4);
-              buf_store_f32(v[k].y + bias1, yr, vo1 | dead, P * k * 4);
+              io.store(v[k].x + bias0, yr, vo0 | dead, P * k * ES);
+              io.store(v[k].y + bias1, yr, vo1 | dead, P * k * ES);
             }
           });
         }
       });
     } else {
-      float* y0 = a.y + ((size_t)b * a.Cout + cg0) * a.Lout + (size_t)(t0 + nbase);
-      float* y1 = y0 + a.Lout;
+      auto* y0 = io_ptr<IO>(a.y) + ((size_t)b * a.Cout + cg0) * a.Lout + (size_t)(t0 + nbase);
+      auto* y1 = y0 + a.Lout;
 #pragma unroll
       for (int k = 0; k < P; ++k)
         if (nbase + P * k < limit) {
-          if (ok0) y0[P * k] = v[k].x + bias0;
-          if (ok1) y1[P * k] = v[k].y + bias1;
+          if (ok0) y0[P * k] = io.out(v[k].x + bias0);
+          if (ok1) y1[P * k] = io.out(v[k].y + bias1);
         }
     }
   }

@@ -156,7 +156,9 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   *out_plan = nullptr;
   const fc_desc& d = *desc;
   if (d.ndim < 1 || d.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", d.ndim);
-  if (d.dtype != FC_F32 && d.dtype != FC_F64) return fail(FC_ERR_UNSUPPORTED, "dtype must be FC_F32 or FC_F64");
+  if (d.dtype != FC_F32 && d.dtype != FC_F64 && d.dtype != FC_F16 && d.dtype != FC_BF16)
+    return fail(FC_ERR_UNSUPPORTED, "dtype must be FC_F32, FC_F64, FC_F16 or FC_BF16");
+  if (sw && d.dtype != FC_F32) return fail(FC_ERR_UNSUPPORTED, "weight-gradient plans are float32 only");
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
     return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
   if (d.in_channels % d.groups || d.out_channels % d.groups)
@@ -168,6 +170,10 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   std::memset(p.get(), 0, sizeof *p);
   p->d = d;
   p->nd = d.ndim;
+  // 16-bit x / y: planned exactly as the float32 plan of the descriptor (same route, spectrum layout and sizes, so a
+  // float32 plan's kernel spectrum serves it); only the launches' loads of x and stores of y take the element type
+  p->io = d.dtype == FC_F64 ? FC_F32 : d.dtype;
+  if (p->io != FC_F32) p->d.dtype = FC_F32;
   if (sw) { p->fnd.swap = 1; p->fnd.sw_B = sw->B; p->fnd.sw_Cig = sw->Cig; p->fnd.sw_Cog = sw->Cog; p->fnd.sw_g = sw->g; }
   if (d.transposed && d.padding_mode != FC_PAD_CONSTANT) {
     return fail(FC_ERR_INVALID, "a transposed plan supports zero padding only");
@@ -244,6 +250,19 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   else if (d.ndim == 1) { p->kind = PlanKind::F32_1D; rc = plan_1d(p.get()); }
   else { p->kind = PlanKind::F32_ND; rc = plan_nd(p.get()); }
   if (rc != FC_OK) return rc;
+  if (p->io != FC_F32) {
+    // routes that read y back between launches would round a 16-bit output between them: not offered (the caller computes
+    // such shapes in float32 and rounds once)
+    const char* route = nullptr;
+    if (p->kind == PlanKind::F32_1D && p->f1d.chunk_launches) route = "1-D chunk launches (chunk_launches)";
+    else if (p->kind == PlanKind::F32_1D && p->f1d.nseg > 1) route = "1-D segments of taps (nseg > 1)";
+    else if (p->kind == PlanKind::F32_ND && p->fnd.nseg_total > 1) route = "2-D / 3-D segments of taps (nseg0*nseg1*nseg2 > 1)";
+    if (route) {
+      fc_plan_destroy(p.release());
+      return fail(FC_ERR_UNSUPPORTED, "float16 / bfloat16 I/O: the route %s accumulates into y across launches; "
+                  "run this shape in float32", route);
+    }
+  }
   *out_plan = p.release();
   return FC_OK;
 }
@@ -382,6 +401,7 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
   const fc_plan& p = *plan;
   if (p.d.has_bias && !bias) return fail(FC_ERR_INVALID, "plan was created with has_bias=1 but bias is NULL");
   if (p.workspace_bytes && !workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
+  if (stamps && p.io != FC_F32) return fail(FC_ERR_UNSUPPORTED, "a float16 / bfloat16 plan has no stamped forward");
   if (stamps && p.kind == PlanKind::F32_ND && p.fnd.nseg_total > 1)
     return fail(FC_ERR_UNSUPPORTED, "a plan that runs its kernel in %d segments of taps has no stamped forward", p.fnd.nseg_total);
   switch (p.kind) {

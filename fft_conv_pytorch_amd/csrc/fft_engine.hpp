@@ -269,6 +269,84 @@ __device__ __forceinline__ void buf_store_f32(float v, BufRsrc r, unsigned voff,
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
 }
 
+// ---- element type of the signal x and the output y of a forward launch (the arithmetic is float32 either way) ----
+// Io<IO_F32> is float and its members are the buf_*_f32 calls above.  Io<IO_H16> is 16-bit storage: float16 or bfloat16,
+// chosen by a wave-uniform flag of the launch (one build serves both), widened exactly on load (bfloat16: a shift,
+// float16: v_cvt_f32_f16) and rounded once on store to nearest even as Tensor.to() rounds (v_cvt_pk_f16_f32: overflow to
+// inf; v_cvt_pk_bf16_f32: a NaN stays a NaN), two samples per conversion where two are stored together.  n consecutive
+// samples travel as one access of n * B bytes.  Byte offsets are in units of B; an offset outside the resource still
+// drops the access.
+constexpr int IO_F32 = 0, IO_H16 = 1;
+constexpr int IO_CODE_F16 = 2, IO_CODE_BF16 = 3;   // fc_dtype codes of a launch's `io` field (0: float32)
+template <int IO>
+struct Io;
+template <>
+struct Io<IO_F32> {
+  using T = float;
+  static constexpr unsigned B = 4;
+  __device__ __forceinline__ explicit Io(int) {}
+  __device__ __forceinline__ float in(float v) const { return v; }
+  __device__ __forceinline__ float out(float v) const { return v; }
+  __device__ __forceinline__ float load(BufRsrc r, unsigned voff, unsigned soff) const { return buf_load_f32(r, voff, soff); }
+  __device__ __forceinline__ f2 load2(BufRsrc r, unsigned voff, unsigned soff) const { return buf_load_f32x2(r, voff, soff); }
+  __device__ __forceinline__ f4 load4(BufRsrc r, unsigned voff, unsigned soff) const { return buf_load_f32x4(r, voff, soff); }
+  __device__ __forceinline__ void store(float v, BufRsrc r, unsigned voff, unsigned soff) const { buf_store_f32(v, r, voff, soff); }
+  __device__ __forceinline__ void store2(f2 v, BufRsrc r, unsigned voff, unsigned soff) const { buf_store_f32x2(v, r, voff, soff); }
+  __device__ __forceinline__ void store4(f4 v, BufRsrc r, unsigned voff, unsigned soff) const {
+    u32x4 d;
+    d.x = __float_as_uint(v.x); d.y = __float_as_uint(v.y); d.z = __float_as_uint(v.z); d.w = __float_as_uint(v.w);
+    __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 0);
+  }
+};
+template <>
+struct Io<IO_H16> {
+  using T = unsigned short;
+  static constexpr unsigned B = 2;
+  bool bf;   // bfloat16 (else float16); wave-uniform
+  __device__ __forceinline__ explicit Io(int code) : bf(code == IO_CODE_BF16) {}
+  __device__ __forceinline__ float in(unsigned h) const {
+    h &= 0xFFFFu;
+    return bf ? __uint_as_float(h << 16) : (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+  }
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+  __device__ __forceinline__ unsigned short out(float v) const {
+    return bf ? __builtin_bit_cast(unsigned short, (__bf16)v) : __builtin_bit_cast(unsigned short, (_Float16)v);
+  }
+  __device__ __forceinline__ unsigned pack(float lo, float hi) const {
+    const bf16x2 b = {(__bf16)lo, (__bf16)hi};
+    const f16x2 h = {(_Float16)lo, (_Float16)hi};
+    return bf ? __builtin_bit_cast(unsigned, b) : __builtin_bit_cast(unsigned, h);
+  }
+  __device__ __forceinline__ float load(BufRsrc r, unsigned voff, unsigned soff) const {
+    return in(__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0));
+  }
+  __device__ __forceinline__ f2 load2(BufRsrc r, unsigned voff, unsigned soff) const {
+    const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
+    return mk2(in(w), in(w >> 16));
+  }
+  __device__ __forceinline__ f4 load4(BufRsrc r, unsigned voff, unsigned soff) const {
+    const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
+    f4 o; o.x = in(w.x); o.y = in(w.x >> 16); o.z = in(w.y); o.w = in(w.y >> 16);
+    return o;
+  }
+  __device__ __forceinline__ void store(float v, BufRsrc r, unsigned voff, unsigned soff) const {
+    __builtin_amdgcn_raw_buffer_store_b16(out(v), r, voff, soff, 0);
+  }
+  __device__ __forceinline__ void store2(f2 v, BufRsrc r, unsigned voff, unsigned soff) const {
+    __builtin_amdgcn_raw_buffer_store_b32(pack(v.x, v.y), r, voff, soff, 0);
+  }
+  __device__ __forceinline__ void store4(f4 v, BufRsrc r, unsigned voff, unsigned soff) const {
+    u32x2 d; d.x = pack(v.x, v.y); d.y = pack(v.z, v.w);
+    __builtin_amdgcn_raw_buffer_store_b64(d, r, voff, soff, 0);
+  }
+};
+// element pointer of a float32-typed tensor argument that holds Io<IO>::T samples
+template <int IO>
+__device__ __forceinline__ typename Io<IO>::T* io_ptr(float* p) { return reinterpret_cast<typename Io<IO>::T*>(p); }
+template <int IO>
+__device__ __forceinline__ const typename Io<IO>::T* io_ptr(const float* p) { return reinterpret_cast<const typename Io<IO>::T*>(p); }
+
 // ---- cross-lane helpers (DPP quad permutes: VALU rate, no LDS) --------------
 __device__ __forceinline__ float dpp_xor1(float v) {   // quad_perm [1,0,3,2]
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));

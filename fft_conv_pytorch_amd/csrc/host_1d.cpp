@@ -444,7 +444,7 @@ int forward_1d(const fc_plan& p, const float* x, const void* w_hat, const float*
   if (p.f1d.dense) {
     fc::DenseArgs a{};
     const size_t NF = (size_t)p.tile->T / 2 + 1;
-    a.x = x; a.y = y; a.bias = p.d.has_bias ? bias : nullptr; a.Hd = (const fc::f2*)w_hat;
+    a.x = x; a.y = y; a.bias = p.d.has_bias ? bias : nullptr; a.Hd = (const fc::f2*)w_hat; a.io = p.io;
     a.twA = p.tw.twA; a.twB = p.tw.twB;
     a.B = (int)p.d.batch; a.Cin = (int)p.d.in_channels; a.Cout = (int)p.d.out_channels; a.G = p.G;
     a.Cig = p.Cig; a.Cog = p.Cog; a.Kc = p.Cig_pad; a.Nc = p.Cog_pad;
@@ -474,6 +474,7 @@ int forward_1d(const fc_plan& p, const float* x, const void* w_hat, const float*
   a.ic_begin = 0; a.ic_end = p.Cig_pad / p.CB; a.add_out = 0;
   a.stamps = (unsigned long long*)stamps;
   a.segmented = p.f1d.nseg > 1; a.pos_shift = 0;
+  a.io = p.io;
   if (p.f1d.pers_nb) {
     for (int j = 0; j < p.f1d.nseg; ++j) {
       fc::Conv1dPersArgs pa;

@@ -442,7 +442,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   if (p.fnd.planes == 1) {
     // x (B,Ci,Z,Y,X) -> S[(b,ci)][zp][col] -> O[(b,co)][z_out][col] -> y; col = fx*64 + fy
     fc::PlaneFwdArgs f1{};
-    f1.src = x; f1.dst = wsA; f1.twA = p.fnd.twx.twA; f1.twB = p.fnd.twx.twB;
+    f1.src = x; f1.dst = wsA; f1.twA = p.fnd.twx.twA; f1.twB = p.fnd.twx.twB; f1.io = p.io;
     f1.mx = axis_map(p, 2); f1.my = axis_map(p, 1); f1.mz = axis_map(p, 0);
     f1.SZ = (int)p.d.spatial[0]; f1.SY = (int)p.d.spatial[1]; f1.SX = (int)p.d.spatial[2]; f1.NZ = p.Sp[0];
     f1.nxt = p.fnd.nxt; f1.nyt = p.fnd.nyt; f1.Vx = p.fnd.Vx; f1.Vy = p.fnd.Vy;
@@ -450,7 +450,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     // (the tiles of a plane share the spectrum's 2048 columns)
     FC_HIP(p.tile->colz(colz_args(p, wsA, w_hat, wsB, fc::kPlCols * p.fnd.nxt * p.fnd.nyt, fc::kPlCols, stamps), st));
     fc::PlaneInvArgs f3{};
-    f3.src = wsB; f3.dst = y; f3.bias = p.d.has_bias ? bias : nullptr; f3.twA = p.fnd.twx.twA; f3.twB = p.fnd.twx.twB;
+    f3.src = wsB; f3.dst = y; f3.bias = p.d.has_bias ? bias : nullptr; f3.twA = p.fnd.twx.twA; f3.twB = p.fnd.twx.twB; f3.io = p.io;
     f3.NZo = (int)p.out_sp[0]; f3.Cout = Co;
     f3.NVy = p.Lf[1]; f3.sy = p.ostride[1]; f3.Yo = (int)p.out_sp[1];
     f3.NVx = p.Lf[2]; f3.sx = p.ostride[2]; f3.Xo = (int)p.out_sp[2];
@@ -459,7 +459,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     return FC_OK;
   }
   fc::RowsR2CArgs r{};
-  r.src = x; r.dst = wsA; r.twA = p.fnd.twx.twA; r.twB = p.fnd.twx.twB; r.from_kernel = 0;
+  r.src = x; r.dst = wsA; r.twA = p.fnd.twx.twA; r.twB = p.fnd.twx.twB; r.from_kernel = 0; r.io = p.io;
   r.mx = axis_map(p, nd - 1); r.my = axis_map(p, nd - 2);
   // a one-plane padded z axis still goes through its map: a transposed plan can crop its only source plane away
   if (nd == 3) r.mz = axis_map(p, 0);
@@ -470,7 +470,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   r.nxt = p.fnd.nxt; r.Vx = p.fnd.Vx;
   const int Fs = p.fnd.Fxt;                       // signal-side bin columns per plane (all x tiles)
   {
-    const unsigned long long bytes = 4ull * (unsigned long long)B * Ci * r.SZ * r.SY * r.SX;
+    const unsigned long long bytes = (p.io == FC_F32 ? 4ull : 2ull) * (unsigned long long)B * Ci * r.SZ * r.SY * r.SX;
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
   r.rowmajor = p.fnd.planes == 2;
@@ -487,7 +487,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   f.stamps = (unsigned long long*)stamps;
 
   fc::RowsC2RArgs o{};
-  o.dst = y; o.bias = p.d.has_bias ? bias : nullptr; o.twA = p.fnd.twx.twA; o.twB = p.fnd.twx.twB;
+  o.dst = y; o.bias = p.d.has_bias ? bias : nullptr; o.twA = p.fnd.twx.twA; o.twB = p.fnd.twx.twB; o.io = p.io;
   o.NA = B * Co; o.Fx = p.fnd.Fx; o.Cout = Co; o.nxt = p.fnd.nxt; o.Vx = p.fnd.Vx;
   f.wfx = p.fnd.Fx; f.wty = nd == 3 ? p.fnd.tm->T : 1; f.wrep = nd == 3 ? p.fnd.nyt : 1; f.wncol = f.wfx * f.wty;
   o.NV = p.Lf[nd - 1]; o.stride = p.ostride[nd - 1]; o.Xo = (int)p.out_sp[nd - 1];

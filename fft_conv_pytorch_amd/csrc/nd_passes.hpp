@@ -125,11 +125,16 @@ struct RowsR2CArgs {
   // plan flips the taps against SX / SY / SZ); all 0 for an unsegmented plan
   int shx, shy, shz;
   int tox, toy, toz;
+  int io = 0;            // element type of a signal source (fc_dtype: 0 float32, 2 float16, 3 bfloat16; src_bytes counts
+                         // its bytes); kernel taps are float32
 };
 
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
+  const auto* src = io_ptr<IO>(a.src);
   constexpr int T = G::T;
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   constexpr int RB = 2 * NSEQ;
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
   f2 v[P];
   {
     // two rows per sequence
-    const float* rows[2];
+    const typename Io<IO>::T* rows[2];
     bool ok[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -171,20 +176,20 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
         simg = (size_t)((o_all / a.Cog) * a.Cig + i) * a.Cog + (o_all % a.Cog);
         ys = a.SY - 1 - ys; zs = a.SZ - 1 - zs;
       }
-      rows[h] = a.src + ((simg * a.SZ + (ok[h] ? zs : 0)) * a.SY + (ok[h] ? ys : 0)) * a.SX;
+      rows[h] = src + ((simg * a.SZ + (ok[h] ? zs : 0)) * a.SY + (ok[h] ? ys : 0)) * a.SX;
     }
     if (!a.from_kernel && a.mx.up == 1 && a.mx.mode == PAD_CONSTANT && a.src_bytes != 0) {
       // fast path (zero padding): unrolled buffer loads over the whole source tensor; a sample outside
       // its row gets an out-of-range offset and reads as zero -- no masks live across the loads
       const BufRsrc sg = make_rsrc(a.src, a.src_bytes);
-      const unsigned ro0 = ok[0] ? (unsigned)((rows[0] - a.src) * 4) : 0xFFFFFFFFu;
-      const unsigned ro1 = ok[1] ? (unsigned)((rows[1] - a.src) * 4) : 0xFFFFFFFFu;
+      const unsigned ro0 = ok[0] ? (unsigned)((rows[0] - src) * ES) : 0xFFFFFFFFu;
+      const unsigned ro1 = ok[1] ? (unsigned)((rows[1] - src) * ES) : 0xFFFFFFFFu;
 #pragma unroll
       for (int n1 = 0; n1 < P; ++n1) {
         const int xs = x0 + G::N2 * n1 + tseq + a.shx - a.mx.pad;
         const bool in = (unsigned)xs < (unsigned)a.mx.size;     // (== SX, but for a segment of a weight-gradient plan's dY)
-        v[n1].x = buf_load_f32(sg, (in && ok[0]) ? ro0 + (unsigned)xs * 4u : 0xFFFFFFFFu, 0);
-        v[n1].y = buf_load_f32(sg, (in && ok[1]) ? ro1 + (unsigned)xs * 4u : 0xFFFFFFFFu, 0);
+        v[n1].x = io.load(sg, (in && ok[0]) ? ro0 + (unsigned)xs * ES : 0xFFFFFFFFu, 0);
+        v[n1].y = io.load(sg, (in && ok[1]) ? ro1 + (unsigned)xs * ES : 0xFFFFFFFFu, 0);
       }
     } else {
       f2* col = lds + sq * LSEQP + tseq;
@@ -194,8 +199,8 @@ __global__ __launch_bounds__(NT) void rows_r2c_kernel(const RowsR2CArgs a) {
         int xs = a.from_kernel ? tap_src(xp, a.dx, a.kx) : axis_src(a.mx, xp + a.shx);
         if (a.from_kernel && xs >= 0) xs += a.tox;
         if (a.from_kernel && a.transposed && xs >= 0) xs = a.SX - 1 - xs;
-        const float v0 = (ok[0] && xs >= 0) ? rows[0][xs] : 0.f;
-        const float v1 = (ok[1] && xs >= 0) ? rows[1][xs] : 0.f;
+        const float v0 = (ok[0] && xs >= 0) ? io.in(rows[0][xs]) : 0.f;
+        const float v1 = (ok[1] && xs >= 0) ? io.in(rows[1][xs]) : 0.f;
         col[n1 * G::RS] = mk2(v0, v1);
       }
 #pragma unroll
@@ -437,11 +442,14 @@ struct RowsC2RArgs {
   FastDiv d_nyb, d_nxt, d_nc;   // unit map of the launch (filled by the dispatcher)
   int rowmajor;          // src [(a*NC + c)][NY][nxt*Fx] (see RowsR2CArgs)
   int accum;             // add into dst instead of storing, no bias (later segments of taps, host_nd.cpp)
+  int io = 0;            // element type of dst (fc_dtype: 0 float32, 2 float16, 3 bfloat16; float32 with accum)
 };
 
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   constexpr int T = G::T;
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   constexpr int RB = 2 * NSEQ;
@@ -556,14 +564,14 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
   asm volatile("" : "+v"(b));
   // buffer stores relative to this workgroup's RB output rows (32-bit offsets; samples past the valid window, decimated
   // away or in rows past NY get an out-of-range offset instead of a branch)
-  float* orow = a.dst + ((map_img(a.im, img) * a.NC + c) * a.NY + y0) * a.Xo;
-  const BufRsrc orr = make_rsrc(orow, (unsigned)((size_t)min(RB, a.NY - y0) * a.Xo * 4));
+  auto* orow = io_ptr<IO>(a.dst) + ((map_img(a.im, img) * a.NC + c) * a.NY + y0) * a.Xo;
+  const BufRsrc orr = make_rsrc(orow, (unsigned)((size_t)min(RB, a.NY - y0) * a.Xo * ES));
   const bool has0 = ya_row < a.NY, has1 = ya_row + 1 < a.NY;
   // (offsets are sums of small row and column parts; bit 31 marks a store that must not happen)
-  const unsigned r0 = (unsigned)(2 * sq * a.Xo) * 4u, r1 = r0 + (unsigned)a.Xo * 4u;
+  const unsigned r0 = (unsigned)(2 * sq * a.Xo) * ES, r1 = r0 + (unsigned)a.Xo * ES;
   const unsigned bad0 = has0 ? 0u : 0x80000000u, bad1 = has1 ? 0u : 0x80000000u;
   const int nbase = (tseq >> G::LGS) + P * P * j;
-  if (a.accum) {
+  if (IO == IO_F32 && a.accum) {
     // a later segment of taps: y += this segment's samples, eight samples per row at a time (their y values requested
     // before the first store; offsets that must not be stored read as zero).  (Offsets are recomputed rather than kept:
     // arrays over all P samples would cost this kernel an occupancy step on its unsegmented launches too.)
@@ -600,9 +608,9 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
 #pragma unroll
     for (int k = 0; k < P; ++k) {
       const int n = nbase + P * k;
-      const unsigned xo = (unsigned)(x0 + n) * 4u, badx = n < xlim ? 0u : 0x80000000u;
-      buf_store_f32(v[k].x + b, orr, (r0 + xo) | bad0 | badx, 0);
-      buf_store_f32(v[k].y + b, orr, (r1 + xo) | bad1 | badx, 0);
+      const unsigned xo = (unsigned)(x0 + n) * ES, badx = n < xlim ? 0u : 0x80000000u;
+      io.store(v[k].x + b, orr, (r0 + xo) | bad0 | badx, 0);
+      io.store(v[k].y + b, orr, (r1 + xo) | bad1 | badx, 0);
     }
     return;
   }
@@ -611,9 +619,9 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
     const int n = nbase + P * k;
     const int t = x0 + n;
     const int idx = t / a.stride;
-    const unsigned xo = (unsigned)idx * 4u, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
-    buf_store_f32(v[k].x + b, orr, (r0 + xo) | bad0 | badx, 0);
-    buf_store_f32(v[k].y + b, orr, (r1 + xo) | bad1 | badx, 0);
+    const unsigned xo = (unsigned)idx * ES, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
+    io.store(v[k].x + b, orr, (r0 + xo) | bad0 | badx, 0);
+    io.store(v[k].y + b, orr, (r1 + xo) | bad1 | badx, 0);
   }
 }
 

@@ -47,11 +47,14 @@ struct PlaneFwdArgs {
   int nxt, nyt, Vx, Vy;  // overlap-save tiles of the plane (padded plane larger than 64 x 64): tile (yt, xt) is the window of padded
                          // positions [yt*Vy, yt*Vy + 64) x [xt*Vx, xt*Vx + 64); dst then holds nyt*nxt blocks of 2048 columns per plane
   FastDiv d_nz, d_nt, d_nx;   // unit map of the launch (filled by the dispatcher): blockIdx = (img*NZ + zp)*ntile + tile, tile = yt*nxt + xt
+  int io = 0;            // element type of src (fc_dtype: 0 float32, 2 float16, 3 bfloat16)
 };
 
-template <int NT_>
+template <int NT_, int IO = IO_F32>
 __global__ __launch_bounds__(kPlNT) void planes_fwd_kernel(const PlaneFwdArgs a) {
   using G = Geo<8, 1>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   // ONE 18 KB region serves, one after the other, as row buffer, x-pass exchange, [fx][y] transpose, y-pass exchange and
   // output staging (a workgroup barrier at every change of hands): eight workgroups per CU instead of four
   __shared__ __attribute__((aligned(16))) f2 reg[32 * kPlPitch];
@@ -79,8 +82,8 @@ __global__ __launch_bounds__(kPlNT) void planes_fwd_kernel(const PlaneFwdArgs a)
   // ---- 1. the padded plane -> LDS (dword per lane, 256 contiguous bytes per wave-instruction; padding of both axes
   // through the index maps, positions past the padded extent read as zero)
   {
-    const float* plane = a.src + ((size_t)img * a.SZ + zs) * a.SY * a.SX;
-    const BufRsrc pr = make_rsrc(plane, (unsigned)(a.SY * a.SX * 4));
+    const auto* plane = io_ptr<IO>(a.src) + ((size_t)img * a.SZ + zs) * a.SY * a.SX;
+    const BufRsrc pr = make_rsrc(plane, (unsigned)(a.SY * a.SX * ES));
     const int xp = tid & 63;
     float val[16];
     if (a.mx.up == 1 && a.my.up == 1 && a.mx.mode == PAD_CONSTANT) {
@@ -88,11 +91,11 @@ __global__ __launch_bounds__(kPlNT) void planes_fwd_kernel(const PlaneFwdArgs a)
       // a division and three mode branches per element, 17 times per thread: most of this kernel's instructions
       const int xs = x0 + xp - a.mx.pad;
       const bool xok = (unsigned)xs < (unsigned)a.SX;
-      const unsigned base = (unsigned)((y0 + (tid >> 6) - a.my.pad) * a.SX + xs) * 4u, step = (unsigned)(4 * a.SX) * 4u;
+      const unsigned base = (unsigned)((y0 + (tid >> 6) - a.my.pad) * a.SX + xs) * ES, step = (unsigned)(4 * a.SX) * ES;
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int ys = y0 + (tid >> 6) + 4 * u - a.my.pad;
-        val[u] = buf_load_f32(pr, (xok && (unsigned)ys < (unsigned)a.SY) ? base + step * u : 0xFFFFFFFFu, 0);
+        val[u] = io.load(pr, (xok && (unsigned)ys < (unsigned)a.SY) ? base + step * u : 0xFFFFFFFFu, 0);
       }
     } else {
       const int xs = axis_src(a.mx, x0 + xp);
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(kPlNT) void planes_fwd_kernel(const PlaneFwdArgs a)
       for (int u = 0; u < 16; ++u) {
         const int yp = y0 + (tid >> 6) + 4 * u;
         const int ys = axis_src(a.my, yp);
-        val[u] = buf_load_f32(pr, (ys >= 0 && xs >= 0) ? (unsigned)(ys * a.SX + xs) * 4u : 0xFFFFFFFFu, 0);
+        val[u] = io.load(pr, (ys >= 0 && xs >= 0) ? (unsigned)(ys * a.SX + xs) * ES : 0xFFFFFFFFu, 0);
       }
     }
 #pragma unroll
@@ -181,11 +184,13 @@ struct PlaneInvArgs {
   int nxt, nyt, Vx, Vy;  // overlap-save tiles of the plane (see PlaneFwdArgs): tile (yt, xt) yields the stride-1 samples
                          // [yt*Vy, yt*Vy + Vy) x [xt*Vx, xt*Vx + Vx) of the plane; src holds nyt*nxt blocks of 2048 columns per plane
   FastDiv d_nz, d_nt, d_nx;   // unit map of the launch (filled by the dispatcher): blockIdx = (img*NZo + zi)*ntile + tile, tile = yt*nxt + xt
+  int io = 0;            // element type of dst (fc_dtype: 0 float32, 2 float16, 3 bfloat16)
 };
 
-template <int NT_>
+template <int NT_, int IO = IO_F32>
 __global__ __launch_bounds__(kPlNT) void planes_inv_kernel(const PlaneInvArgs a) {
   using G = Geo<8, 1>;
+  const Io<IO> io(a.io);
   __shared__ __attribute__((aligned(16))) f2 reg[32 * kPlPitch];     // one region, six changes of hands (see planes_fwd)
   constexpr int YP = 36;                                   // Yt[yo][fx] pitch (complex): row pairs land 64 bytes apart mod 256
   static_assert(64 * YP <= 32 * kPlPitch, "transposed rows fit the region");
@@ -293,14 +298,14 @@ __global__ __launch_bounds__(kPlNT) void planes_inv_kernel(const PlaneInvArgs a)
     }
   }
   __syncthreads();
-  float* op = a.dst + (size_t)qq * a.Yo * a.Xo;             // the (b, co, z_out) plane
+  auto* op = io_ptr<IO>(a.dst) + (size_t)qq * a.Yo * a.Xo;   // the (b, co, z_out) plane
   const int total = Yo * Xo;
   if (a.nxt * a.nyt == 1) {                                 // (the whole plane: one contiguous run)
-    for (int idx = tid; idx < total; idx += kPlNT) op[idx] = ob[idx];
+    for (int idx = tid; idx < total; idx += kPlNT) op[idx] = io.out(ob[idx]);
   } else {
     for (int idx = tid; idx < total; idx += kPlNT) {
       const int r = idx / Xo, c = idx - r * Xo;
-      op[(size_t)(oy0 + r) * a.Xo + ox0 + c] = ob[idx];
+      op[(size_t)(oy0 + r) * a.Xo + ox0 + c] = io.out(ob[idx]);
     }
   }
 }

@@ -45,9 +45,11 @@ hipError_t ensure_lds(K kernel, size_t lds, LdsOptIn* done) {
   return e;
 }
 
-template <int CIB>
+// IO: element type of x and y (Io in fft_engine.hpp); the 16-bit builds serve float16 and bfloat16 plans (a.io), which
+// never run the chunk-by-chunk, segment or profiling launches
+template <int CIB, int IO = IO_F32>
 hipError_t launch_conv1d(const Conv1dArgs& a, int grid, size_t lds, hipStream_t st) {
-  auto k = conv1d_fused_kernel<FC_P, FC_S, CIB, FC_NT>;
+  auto k = conv1d_fused_kernel<FC_P, FC_S, CIB, FC_NT, IO>;
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
   if (e != hipSuccess) return e;
@@ -56,6 +58,14 @@ hipError_t launch_conv1d(const Conv1dArgs& a, int grid, size_t lds, hipStream_t 
 }
 
 hipError_t conv1d_dispatch(int cib, const Conv1dArgs& a, int grid, size_t lds, hipStream_t st) {
+  if (a.io != 0) {
+    switch (cib) {
+      case 2: return launch_conv1d<2, IO_H16>(a, grid, lds, st);
+      case 4: return launch_conv1d<4, IO_H16>(a, grid, lds, st);
+      case 8: return launch_conv1d<8, IO_H16>(a, grid, lds, st);
+      default: return hipErrorInvalidValue;
+    }
+  }
   switch (cib) {
     case 2: return launch_conv1d<2>(a, grid, lds, st);
     case 4: return launch_conv1d<4>(a, grid, lds, st);
@@ -73,9 +83,10 @@ hipError_t spec1d_dispatch(const Spec1dArgs& a, int grid, size_t lds, hipStream_
   return hipGetLastError();
 }
 
-hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
+template <int IO>
+hipError_t launch_rows_r2c(const RowsR2CArgs& a, hipStream_t st) {
   constexpr int NT = kNSEQ_R * GG::TS;
-  auto k = rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, NT>;
+  auto k = rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, NT, IO>;
   const size_t lds = (size_t)kNSEQ_R * kLSEQP * sizeof(float2);
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
@@ -87,6 +98,9 @@ hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
   b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
   return hipGetLastError();
+}
+hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
+  return a.io != 0 ? launch_rows_r2c<IO_H16>(a, st) : launch_rows_r2c<IO_F32>(a, st);
 }
 
 template <bool INV>
@@ -113,9 +127,10 @@ hipError_t c2c_dispatch(const C2CArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
+template <int IO>
+hipError_t launch_rows_c2r(const RowsC2RArgs& a, hipStream_t st) {
   constexpr int NT = kNSEQ_R * GG::TS;
-  auto k = rows_c2r_kernel<FC_P, FC_S, kNSEQ_R, NT>;
+  auto k = rows_c2r_kernel<FC_P, FC_S, kNSEQ_R, NT, IO>;
   const size_t lds = (size_t)kNSEQ_R * kLSEQP * sizeof(float2);
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
@@ -127,6 +142,9 @@ hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
   b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
   return hipGetLastError();
+}
+hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
+  return a.io != 0 ? launch_rows_c2r<IO_H16>(a, st) : launch_rows_c2r<IO_F32>(a, st);
 }
 
 // fused column pass: NB batch items per workgroup share the spectrum loads.  NB is the largest of
@@ -192,11 +210,12 @@ constexpr size_t pers_lds_bytes(int nb) { return ((size_t)FC_P * GG::N2 + (size_
 
 // batch-sharing kernel builds: PHASES (dilation as phases) x DIAG (depthwise blocks); the plain one keeps its
 // immediate offsets and is the only one the headline configuration runs
-template <int NB, bool PHASES, bool DIAG, bool SEG = false, bool PH2 = false, bool STAMPS = false, bool PH4 = false>
+template <int NB, bool PHASES, bool DIAG, bool SEG = false, bool PH2 = false, bool STAMPS = false, bool PH4 = false,
+          int IO = IO_F32>
 hipError_t launch_pers_variant(const Conv1dPersArgs& a, int grid, hipStream_t st) {
   constexpr int NT = NB * 4 * GG::TS;
   const size_t lds = pers_lds_bytes(NB);
-  auto k = conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, PHASES, 2, DIAG, SEG, PH2, STAMPS, PH4>;
+  auto k = conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, PHASES, 2, DIAG, SEG, PH2, STAMPS, PH4, IO>;
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
   if (e != hipSuccess) return e;
@@ -210,6 +229,19 @@ hipError_t launch_pers(const Conv1dPersArgs& a, int grid, hipStream_t st) {
     return hipErrorInvalidValue;
   } else {
     const bool ph = a.c.ph > 1, dg = a.c.diag != 0;
+    if (a.c.io != 0) {     // 16-bit x / y: the builds without segments and profiling hook
+      if (a.c.segmented || a.c.stamps) return hipErrorInvalidValue;
+      if (ph && dg) return launch_pers_variant<NB, true, true, false, false, false, false, IO_H16>(a, grid, st);
+#if FC_S == 1
+      if constexpr (NB == 4) {
+        if (ph && a.c.ph2 == 2) return launch_pers_variant<NB, true, false, false, false, false, true, IO_H16>(a, grid, st);
+      }
+      if (ph && a.c.ph2) return launch_pers_variant<NB, true, false, false, true, false, false, IO_H16>(a, grid, st);
+#endif
+      if (ph) return launch_pers_variant<NB, true, false, false, false, false, false, IO_H16>(a, grid, st);
+      if (dg) return launch_pers_variant<NB, false, true, false, false, false, false, IO_H16>(a, grid, st);
+      return launch_pers_variant<NB, false, false, false, false, false, false, IO_H16>(a, grid, st);
+    }
     if (a.c.segmented) return dg ? launch_pers_variant<NB, false, true, true>(a, grid, st)
                                  : launch_pers_variant<NB, false, false, true>(a, grid, st);
     if (ph && dg) return launch_pers_variant<NB, true, true>(a, grid, st);
@@ -237,15 +269,19 @@ hipError_t pers_dispatch(int nb, const Conv1dPersArgs& a, int grid, hipStream_t 
 
 #if FC_P == 32 && (FC_S == 1 || FC_S == 2)
 constexpr int kWideNb = 2;
-hipError_t wide_dispatch(const Conv1dPersArgs& a, int grid, hipStream_t st) {
+template <int IO>
+hipError_t launch_wide(const Conv1dPersArgs& a, int grid, hipStream_t st) {
   constexpr int NT = kWideNb * 4 * GG::TS;
-  auto k = conv1d_wide_kernel<FC_P, FC_S, kWideNb, NT>;
+  auto k = conv1d_wide_kernel<FC_P, FC_S, kWideNb, NT, IO>;
   const size_t lds = pers_lds_bytes(kWideNb);
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
   return hipGetLastError();
+}
+hipError_t wide_dispatch(const Conv1dPersArgs& a, int grid, hipStream_t st) {
+  return a.c.io != 0 ? launch_wide<IO_H16>(a, grid, st) : launch_wide<IO_F32>(a, grid, st);
 }
 #else
 constexpr int kWideNb = 0;
@@ -292,19 +328,18 @@ hipError_t dense_dispatch(int which, const DenseArgs& a, hipStream_t st) {
     const long long ncb = (nch / 2 + kDenseNseq - 1) / kDenseNseq;
     const long long grid = (long long)a.mcount * ncb * a.G;
     if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    static LdsOptIn done_f, done_i;
-    if (which == 0) {
-      auto k = dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT>;
-      hipError_t e = ensure_lds(k, lds_fft, &done_f);
+    static LdsOptIn done_f, done_i, done_fh, done_ih;
+    auto launch = [&](auto k, LdsOptIn* done) {
+      hipError_t e = ensure_lds(k, lds_fft, done);
       if (e != hipSuccess) return e;
       hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds_fft, st, a);
-    } else {
-      auto k = dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT>;
-      hipError_t e = ensure_lds(k, lds_fft, &done_i);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds_fft, st, a);
-    }
-    return hipGetLastError();
+      return hipGetLastError();
+    };
+    if (which == 0)
+      return a.io != 0 ? launch(dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT, IO_H16>, &done_fh)
+                       : launch(dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT>, &done_f);
+    return a.io != 0 ? launch(dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT, IO_H16>, &done_ih)
+                     : launch(dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT>, &done_i);
   }
   // GEMM: the widest column block that the output channels fill (8 channels per wave), the smallest K chunk that
   // covers the input channels (or 64 and several chunks)
@@ -353,7 +388,8 @@ hipError_t planes_fwd_dispatch(const PlaneFwdArgs& a, int n_images, hipStream_t 
   const long long grid = (long long)n_images * a.NZ * ntile;
   if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
   b.d_nz = make_fastdiv((unsigned)a.NZ); b.d_nt = make_fastdiv((unsigned)ntile); b.d_nx = make_fastdiv((unsigned)b.nxt);
-  hipLaunchKernelGGL(planes_fwd_kernel<kPlNT>, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
+  auto k = a.io != 0 ? planes_fwd_kernel<kPlNT, IO_H16> : planes_fwd_kernel<kPlNT>;
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
   return hipGetLastError();
 }
 hipError_t planes_inv_dispatch(const PlaneInvArgs& a, int n_images, hipStream_t st) {
@@ -365,7 +401,8 @@ hipError_t planes_inv_dispatch(const PlaneInvArgs& a, int n_images, hipStream_t 
   const long long grid = (long long)n_images * a.NZo * ntile;
   if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
   b.d_nz = make_fastdiv((unsigned)a.NZo); b.d_nt = make_fastdiv((unsigned)ntile); b.d_nx = make_fastdiv((unsigned)b.nxt);
-  hipLaunchKernelGGL(planes_inv_kernel<kPlNT>, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
+  auto k = a.io != 0 ? planes_inv_kernel<kPlNT, IO_H16> : planes_inv_kernel<kPlNT>;
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
   return hipGetLastError();
 }
 template <int NB, bool STAMPS, int NCOLC>

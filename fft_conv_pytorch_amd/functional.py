@@ -8,6 +8,7 @@ and no torch.fft / rocFFT / hipFFT call anywhere in this package.
 """
 from __future__ import annotations
 
+import collections
 import os
 from typing import Iterable, Optional, Union
 
@@ -20,7 +21,7 @@ from .utils import to_ntuple
 __all__ = ["fft_conv", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
 
 
-_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}      # enum fc_dtype
+_DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}      # enum fc_dtype
 
 
 def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
@@ -32,8 +33,8 @@ def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
     if t.dtype != dtype or dtype not in _DTYPE_CODES:
         raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; signal, kernel and bias must share one of "
                         f"float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
-                        f"their crossover) or float16 / bfloat16 (computed in "
-                        f"float32)")
+                        f"their crossover) or float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
+                        f"kernels, which widen the signal as they load it and round the output once as they store it)")
 
 
 class KernelSpectrum:
@@ -123,17 +124,27 @@ def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, g
     index = _device_index(dev)
     plan = _native.lookup_plan(index, key)
     if plan is None:
+        if (index,) + key in _REFUSED_HALF:
+            raise NotImplementedError(_REFUSED_HALF[(index,) + key])
         # the library allocates twiddle tables and work lists on the CURRENT HIP device and sizes the work
         # list for its CU count: create the plan with the tensors' device current
-        with torch.cuda.device(index):
-            plan = _native.get_plan(index, key)
+        try:
+            with torch.cuda.device(index):
+                plan = _native.get_plan(index, key)
+        except NotImplementedError as e:
+            if dtype in _LOW_PRECISION:      # a route that reads y back: remembered, the caller takes the cast path
+                _REFUSED_HALF[(index,) + key] = str(e)
+                while len(_REFUSED_HALF) > 256:
+                    _REFUSED_HALF.popitem(last=False)
+            raise
     return plan
 
 
 def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
-    """Kernel transform (dilate, zero-pad, FFT, conjugate) on the device; rows a2 + a6."""
-    _require_gpu_f32("kernel", kernel, plan.dtype)
-    kernel = kernel.detach().contiguous()
+    """Kernel transform (dilate, zero-pad, FFT, conjugate) on the device; rows a2 + a6.  A float16 / bfloat16 plan takes
+    a weight of its own dtype (widened to a float32 copy that lives for this call only) or a float32 one."""
+    _require_gpu_f32("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype)
+    kernel = kernel.detach().to(plan.weight_dtype).contiguous()
     if _device_index(kernel.device) != plan.device_index:
         raise ValueError(f"kernel is on {kernel.device} but the plan was made for cuda:{plan.device_index}")
     with torch.cuda.device(kernel.device):
@@ -156,7 +167,8 @@ def _launch_forward(signal: Tensor, spectrum: KernelSpectrum, bias_c: Optional[T
 
 def _forward_native(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Tensor]) -> Tensor:
     signal = signal.detach().contiguous()
-    bias_c = bias.detach().contiguous() if bias is not None else None
+    # (a float16 / bfloat16 plan reads a float32 bias: Cout values)
+    bias_c = bias.detach().to(spectrum.plan.weight_dtype).contiguous() if bias is not None else None
     index = _device_index(signal.device)
     if signal.dtype != spectrum.plan.dtype:
         raise TypeError(f"signal is {signal.dtype} but the plan was made for {spectrum.plan.dtype}")
@@ -194,6 +206,17 @@ def fft_conv(
 
 
 _LOW_PRECISION = (torch.float16, torch.bfloat16)
+# (device, plan key) of float16 / bfloat16 descriptors whose route the library refuses (it would round y between
+# launches) -> its message: such calls take the cast path without asking the library again
+_REFUSED_HALF: "collections.OrderedDict[tuple, str]" = collections.OrderedDict()
+
+
+def _half_native(signal: Tensor, kernel: Tensor, bias) -> bool:
+    """A float16 / bfloat16 call the kernels read and write in its own dtype: the three tensors agree, no gradient is
+    required (autograd keeps the float32 cast path) and FFTCONV_HALF_IO is not 0."""
+    return (signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype
+            and (bias is None or bias.dtype == signal.dtype) and not _needs_grad(signal, kernel, bias)
+            and os.environ.get("FFTCONV_HALF_IO", "1") != "0")
 
 
 def _string_padding(padding: str, kernel: Tensor, stride, dilation, n: int):
@@ -227,6 +250,17 @@ def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padd
             # larger buffer and break downstream .view() calls)
             out = out[(slice(None), slice(None)) + tuple(slice(d, None) for d in drop)].contiguous()
         return out
+    if _half_native(signal, kernel, bias):
+        # the kernels read x and write y in the tensors' dtype (float32 arithmetic, the bits of the cast path below)
+        try:
+            if plan is None:
+                plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
+        except NotImplementedError:
+            plan = None       # a refused route (reads y back between launches): the cast path
+        if plan is not None:
+            if spectrum is None or spectrum.plan is not plan:
+                spectrum = transform_kernel(plan, kernel)
+            return _forward_native(signal, spectrum, bias)
     if signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype and (bias is None or bias.dtype == signal.dtype):
         # half-precision tensors in, half-precision tensor out; the arithmetic is the fp32 path (one cast pass each way)
         out = _fft_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride, padding,
@@ -268,6 +302,17 @@ def fft_conv_transpose(
 def _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum,
                              plan=None):
     """Shared by the functional and the transposed modules (``spectrum`` / ``plan``: see ``_fft_conv_impl``)."""
+    if _half_native(signal, kernel, bias):
+        try:
+            if plan is None:
+                plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, "constant",
+                                 transposed=True, output_padding=output_padding)
+        except NotImplementedError:
+            plan = None
+        if plan is not None:
+            if spectrum is None or spectrum.plan is not plan:
+                spectrum = transform_kernel(plan, kernel)
+            return _forward_native(signal, spectrum, bias)
     if signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype and (bias is None or bias.dtype == signal.dtype):
         # half-precision tensors: fp32 arithmetic, one cast pass each way (as the forward op)
         out = _fft_conv_transpose_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride,

@@ -35,6 +35,7 @@ class _SpectrumCache:
 
     def invalidate_kernel_spectrum(self):
         self.__dict__.pop("_spectrum_cache", None)
+        self.__dict__.pop("_bias_cache", None)
 
     def _cached_spectrum(self, plan):
         weight = self.weight
@@ -50,11 +51,23 @@ class _SpectrumCache:
             self.__dict__["_spectrum_cache"] = cached
         return cached[1]
 
+    def _cached_bias(self, plan):
+        """The float32 bias (Cout values) a float16 / bfloat16 plan reads, widened once per bias version."""
+        bias = self.bias
+        if bias is None or bias.dtype == plan.weight_dtype:
+            return bias
+        tag = (bias.data_ptr(), bias._version)
+        cached = self.__dict__.get("_bias_cache")
+        if cached is None or cached[0] != tag:
+            cached = (tag, bias.detach().to(plan.weight_dtype))
+            self.__dict__["_bias_cache"] = cached
+        return cached[1]
+
     # The cached spectrum and the remembered plan hold native handles (ctypes pointers, a loaded library): they are
     # per-process acceleration state, not part of the module.  copy.deepcopy (EMA / AveragedModel, quantization flows),
     # pickle and torch.save(module) therefore see the module WITHOUT them -- exactly what a reference FFTConv module,
     # a plain nn.Conv subclass, carries -- and the copy rebuilds its own on first use.
-    _TRANSIENT = ("_spectrum_cache", "_last_plan")
+    _TRANSIENT = ("_spectrum_cache", "_last_plan", "_bias_cache")
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -84,13 +97,25 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
     def forward(self, signal: Tensor):
         assert signal.ndim == self.weight.ndim
         padding_mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
-        if isinstance(self.padding, str) or signal.dtype not in (torch.float32, torch.float64):
-            # padding='same' / 'valid' (torch stores the string) and half-precision inputs: the functional resolves them
+        if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64)
+                                             and not F_._half_native(signal, self.weight, self.bias)):
+            # padding='same' / 'valid' (torch stores the string) and half-precision calls the kernels do not read and write
+            # in their own dtype (gradients, FFTCONV_HALF_IO=0, mixed dtypes): the functional resolves them
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                      self.groups, padding_mode, None)
-        plan = self._plan(signal, padding_mode)
+        try:
+            plan = self._plan(signal, padding_mode)
+        except NotImplementedError:
+            if signal.dtype not in F_._LOW_PRECISION:
+                raise
+            # a float16 / bfloat16 shape whose route the library refuses: the functional's cast path
+            return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                     self.groups, padding_mode, None)
+        spectrum = self._cached_spectrum(plan)
+        if spectrum is not None and signal.dtype in F_._LOW_PRECISION:     # (no widening kernel per call)
+            return F_._forward_native(signal, spectrum, self._cached_bias(plan))
         return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                                 self.groups, padding_mode, self._cached_spectrum(plan), plan)
+                                 self.groups, padding_mode, spectrum, plan)
 
     def _plan(self, signal: Tensor, padding_mode: str):
         """Plan for this call; the argument validation and descriptor lookup are skipped while the call looks
@@ -112,14 +137,22 @@ class _FFTConvTransposeForward(_SpectrumCache, nn.Module):
 
     def forward(self, signal: Tensor):
         assert signal.ndim == self.weight.ndim
-        if signal.dtype in F_._LOW_PRECISION:      # half-precision tensors: the functional casts (fp32 arithmetic)
-            return F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,
-                                               self.output_padding, self.dilation, self.groups, None, None)
-        plan = F_._plan_for(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                            self.groups, "constant", transposed=True, output_padding=self.output_padding)
+        cast = lambda: F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,  # noqa: E731
+                                                   self.output_padding, self.dilation, self.groups, None, None)
+        if signal.dtype in F_._LOW_PRECISION and not F_._half_native(signal, self.weight, self.bias):
+            return cast()      # half-precision call the kernels do not read and write natively: the functional casts
+        try:
+            plan = F_._plan_for(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                self.groups, "constant", transposed=True, output_padding=self.output_padding)
+        except NotImplementedError:
+            if signal.dtype not in F_._LOW_PRECISION:
+                raise
+            return cast()      # a float16 / bfloat16 shape whose route the library refuses
+        spectrum = self._cached_spectrum(plan)
+        if spectrum is not None and signal.dtype in F_._LOW_PRECISION:
+            return F_._forward_native(signal, spectrum, self._cached_bias(plan))
         return F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,
-                                           self.output_padding, self.dilation, self.groups,
-                                           self._cached_spectrum(plan), plan)
+                                           self.output_padding, self.dilation, self.groups, spectrum, plan)
 
 
 class FFTConv1d(_FFTConvForward, nn.Conv1d):

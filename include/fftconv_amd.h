@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define FC_ABI_VERSION 6
+#define FC_ABI_VERSION 7
 
 enum fc_status {
   FC_OK = 0,
@@ -32,11 +32,20 @@ enum fc_status {
 enum fc_pad_mode { FC_PAD_CONSTANT = 0, FC_PAD_REFLECT = 1, FC_PAD_REPLICATE = 2, FC_PAD_CIRCULAR = 3 };
 enum fc_dtype {
   FC_F32 = 0,  /* the FFT kernels; every float* below is float */
-  FC_F64 = 1   /* float64 tensors: x, weight, w_hat, bias and y are double (pass them through the float* / void*
+  FC_F64 = 1,  /* float64 tensors: x, weight, w_hat, bias and y are double (pass them through the float* / void*
                   parameters); double-precision FFT kernels compute the same function (the reference is dtype-agnostic):
                   1-D plans with >= 16 taps, 2-D / 3-D plans from 100 multiply-adds per output (Cin/groups x
                   prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  N-d plans need
                   fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook are float32-only */
+  FC_F16 = 2,
+  FC_BF16 = 3  /* float16 / bfloat16 signal and output (ABI 7): x and y are 16-bit (pass them through the float* parameters);
+                  weight, w_hat and bias stay float32 (the caller widens the weight and the bias).  The kernels widen x exactly as
+                  they load it, compute in float32 and round y once as they store it (to nearest even; bfloat16 NaN -> 0x7FC0), so
+                  the result has the bits of: widen to float32, run the float32 plan, round.  The plan is the float32 plan of the
+                  descriptor under the same knobs: equal fc_debug_route, fc_plan_layout, fc_kernel_spectrum_bytes and
+                  fc_workspace_bytes, so a float32 plan's spectrum serves it.  Routes that add into y across launches are refused
+                  with FC_ERR_UNSUPPORTED, the text naming the route: 1-D chunk launches, 1-D segments of taps, 2-D / 3-D
+                  segments of taps.  fc_forward_stamped, fc_wgrad1d* and fc_wgrad_nd* take no 16-bit plan or descriptor */
 };
 
 /* Problem descriptor: the arguments of functional.py:19-28 after to_ntuple

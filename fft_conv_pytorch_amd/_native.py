@@ -119,10 +119,11 @@ def load_library() -> ctypes.CDLL:
     return _lib
 
 
-def conv_desc(ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode) -> FcDesc:
-    """``struct fc_desc`` of a forward convolution (used by the calls that take a descriptor, not a plan)."""
+def conv_desc(ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode, dtype=0) -> FcDesc:
+    """``struct fc_desc`` of a forward convolution (used by the calls that take a descriptor, not a plan).  ``dtype``: the
+    fc_dtype code of x and dY for the weight-gradient calls (0 float32, 2 float16, 3 bfloat16; dW stays float32)."""
     d = FcDesc()
-    d.ndim, d.dtype = ndim, 0
+    d.ndim, d.dtype = ndim, dtype
     d.batch, d.in_channels, d.out_channels, d.groups = batch, cin, cout, groups
     for i in range(3):
         d.spatial[i] = spatial[i] if i < ndim else 1
@@ -161,8 +162,9 @@ def wgrad1d_db(desc: FcDesc, x_ptr: int, dy_ptr: int, partial_ptr: int, db_ptr: 
 
 
 class WgradPlan:
-    """Owns the plan of ``fc_wgrad_nd`` for one convolution descriptor (2-D / 3-D, float32): created on the CURRENT HIP
-    device.  ``run`` reads x (B, Cin, *S) and dY (B, Cout, *Lout) and writes dW (Cout, Cin/g, *k) -- no copies around it."""
+    """Owns the plan of ``fc_wgrad_nd`` for one convolution descriptor (2-D / 3-D; x and dY float32, float16 or bfloat16
+    as the descriptor's dtype says): created on the CURRENT HIP device.  ``run`` reads x (B, Cin, *S) and dY (B, Cout, *Lout)
+    and writes a float32 dW (Cout, Cin/g, *k) -- no copies around it."""
 
     def __init__(self, desc: FcDesc):
         lib = load_library()

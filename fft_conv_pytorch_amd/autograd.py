@@ -16,6 +16,12 @@ autograd, so the three gradients are expressed as convolutions the native librar
     db = sum of dY over batch and space    -> a plain reduction
 
 torch is used for data movement only (transposes, unfold views, the final chunk sum and db).
+
+float16 / bfloat16 calls save their 16-bit signal and weight.  Backward gives each gradient the bits of the float32 cast
+path (widen, run the float32 function, round): the kernels read 16-bit dY and x and compute what the float32 plan of the
+same route computes; dX is written in 16 bits by its transposed plan, dW and db are summed in float32 and rounded once.
+Where no 16-bit route exists (a refused dX plan, non-constant padding, the forward-plan dW, a library that predates 16-bit
+weight gradients) dY and x are widened for that gradient only.
 """
 from __future__ import annotations
 
@@ -30,6 +36,9 @@ from . import functional as F_
 _DW_TILE = 2048      # FFT tile the dW correlation is sized for: the largest one that also fits the
                      # accumulating (> 8 channels', i.e. batch > 8) mode of the fused kernel in LDS
 
+
+# fc_dtype code of the x / dY a weight-gradient launch reads (dW is float32 for all of them)
+_WGRAD_IO = {torch.float32: 0, torch.float16: 2, torch.bfloat16: 3}
 
 _BWD_PLANS: dict = {}      # (shapes, hyper-parameters, device) -> (transposed plan of dX, ...): skips the argument
                            # normalisation and descriptor lookup of the functional on every backward call
@@ -63,6 +72,19 @@ def _pad_adjoint(dxp: Tensor, in_spatial, padding, mode: str) -> Tensor:
 
 
 def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode) -> Tensor:
+    if grad.dtype in F_._LOW_PRECISION:
+        if padding_mode == "constant":
+            try:
+                return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode)
+            except NotImplementedError:
+                pass      # a route the 16-bit transposed plan refuses (it would round dX between launches)
+        # float32 dX (and the padding adjoint in float32), rounded once; the widened dY lives for this call only
+        return _grad_input_plan(grad.float(), weight.float(), in_spatial, stride, padding, dilation, groups,
+                                padding_mode).to(grad.dtype)
+    return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode)
+
+
+def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode) -> Tensor:
     n = grad.ndim - 2
     key = ("dx", tuple(grad.shape), tuple(weight.shape), tuple(in_spatial), stride, padding, dilation, groups, padding_mode,
            grad.device, grad.dtype)
@@ -88,7 +110,10 @@ def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilat
 
 def _grad_weight_plans(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Tensor:
     """dW through forward plans with the roles of batch and channels swapped, ALL channel groups in one call
-    (they ride the group axis of the swapped convolution).  x: (B, Cin, *S), grad: (B, Cout, *Lout) -> (Cout, Cin/g, *k)."""
+    (they ride the group axis of the swapped convolution).  x: (B, Cin, *S), grad: (B, Cout, *Lout) -> (Cout, Cin/g, *k).
+    16-bit x and dY are widened here (the float32 plans; dW comes back float32)."""
+    if x.dtype in F_._LOW_PRECISION:
+        x, grad = x.float(), grad.float()
     n = x.ndim - 2
     b, g = x.shape[0], groups
     cog, cig, ksize = wshape[0] // groups, wshape[1], tuple(wshape[2:])
@@ -145,17 +170,20 @@ def _grad_weight_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilati
                         want_db: bool = False):
     """dW by ``fc_wgrad1d`` (cross-spectra accumulated on chip over batch and row); None when not covered.  With
     ``want_db`` the bias gradient rides the same launch where the kernel offers it (bin 0 of the gradient spectra):
-    the slices come as rows [dW | db] and ONE reduction sums both.  Returns (dW, db or None)."""
-    if x.ndim != 3 or x.dtype != torch.float32:      # (float64 runs the direct kernel: dW through forward plans)
+    the slices come as rows [dW | db] and ONE reduction sums both.  Returns (dW, db or None), float32 also for 16-bit
+    x and dY (read as they are: a descriptor of their dtype)."""
+    if x.ndim != 3 or x.dtype not in _WGRAD_IO:      # (float64 runs the direct kernel: dW through forward plans)
         return None
     from . import _native
     if grad.device != x.device:
         raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
-    key = ("dw", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device)
+    if grad.dtype != x.dtype:
+        raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
+    key = ("dw", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device, x.dtype)
     hit = _BWD_PLANS.get(key)
     if hit is None:
         desc = _native.conv_desc(1, x.shape[0], x.shape[1], wshape[0], groups, (x.shape[2],), (wshape[2],), stride, padding,
-                                 dilation, _native.PAD_MODES[padding_mode])
+                                 dilation, _native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
         # the library sizes the launch for, and keeps its twiddle tables on, the CURRENT device
         with torch.cuda.device(x.device):
             slices = _native.wgrad1d_slices(desc)
@@ -184,18 +212,21 @@ def _grad_weight_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilati
 def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
     """2-D / 3-D dW by ``fc_wgrad_nd``: the role-swapped convolution run by the library on the tensors as they are
     (x (B, Cin, *S) and dY (B, Cout, *Lout) are read, dW (Cout, Cin/g, *k) is written, in these layouts) -- no transposed
-    copies, no crop, no reduction on the torch side.  None when not covered (1-D, float64, a shape the plan refuses)."""
+    copies, no crop, no reduction on the torch side.  None when not covered (1-D, float64, a shape the plan refuses).
+    16-bit x and dY are read as they are; dW is float32."""
     n = x.ndim - 2
-    if n < 2 or x.dtype != torch.float32:
+    if n < 2 or x.dtype not in _WGRAD_IO:
         return None
     from . import _native
     if grad.device != x.device:
         raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
-    key = ("dwn", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device)
+    if grad.dtype != x.dtype:
+        raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
+    key = ("dwn", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device, x.dtype)
     plan = _BWD_PLANS.get(key)
     if plan is None:
         desc = _native.conv_desc(n, x.shape[0], x.shape[1], wshape[0], groups, tuple(x.shape[2:]), tuple(wshape[2:]), stride,
-                                 padding, dilation, _native.PAD_MODES[padding_mode])
+                                 padding, dilation, _native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
         try:
             with torch.cuda.device(x.device):
                 plan = _native.WgradPlan(desc)
@@ -217,14 +248,31 @@ def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dil
     return dw
 
 
-def _grad_weight(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Tensor:
-    native = _grad_weight_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode)
+def _grad_weight_db(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode,
+                    want_db: bool = False):
+    """(dW, db or None) in float32 by the first route that covers the shape: fc_wgrad1d (db riding it where offered),
+    fc_wgrad_nd, forward plans.  16-bit x and dY that no 16-bit launch takes (a library without 16-bit weight gradients)
+    are widened for this gradient, and the float32 routes decide -- the bits of the cast path either way."""
+    native = _grad_weight_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode, want_db)
     if native is not None:
-        return native[0]
+        return native
     nd = _grad_weight_nd_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode)
     if nd is not None:
-        return nd
-    return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode)
+        return nd, None
+    if x.dtype in F_._LOW_PRECISION:
+        return _grad_weight_db(x.float(), grad.float(), wshape, stride, padding, dilation, groups, padding_mode, want_db)
+    return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode), None
+
+
+def _grad_weight(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Tensor:
+    return _grad_weight_db(x, grad, wshape, stride, padding, dilation, groups, padding_mode)[0]
+
+
+def _grad_bias(grad: Tensor) -> Tensor:
+    """Sum of dY over batch and space; a 16-bit dY is summed as the float32 cast path sums it (widened first)."""
+    if grad.dtype in F_._LOW_PRECISION:
+        grad = grad.float()
+    return grad.sum(dim=[0] + list(range(2, grad.ndim)))
 
 
 class FFTConvFunction(torch.autograd.Function):
@@ -246,23 +294,20 @@ class FFTConvFunction(torch.autograd.Function):
         stride, padding, dilation, groups, padding_mode, has_bias = ctx.conf
         grad = grad.contiguous()
         d_signal = d_kernel = d_bias = None
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            # (db rides the weight-gradient launch where the kernel offers it; dW goes first: widened 16-bit operands of a
+            # weight-gradient route are freed before dX is allocated)
+            d_kernel, d_bias = _grad_weight_db(signal.detach(), grad, tuple(kernel.shape), stride, padding, dilation,
+                                               groups, padding_mode, want_db)
+            d_kernel = d_kernel.to(kernel.dtype)     # (16-bit: the float32 sum rounded once)
         if ctx.needs_input_grad[0]:
             d_signal = _grad_input(grad, kernel.detach(), tuple(signal.shape[2:]), stride, padding, dilation, groups,
                                    padding_mode)
-        want_db = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
-            native = _grad_weight_native(signal.detach(), grad, tuple(kernel.shape), stride, padding, dilation, groups,
-                                         padding_mode, want_db)
-            if native is not None:
-                d_kernel, d_bias = native          # (db rode the weight-gradient launch where the kernel offers it)
-            else:
-                d_kernel = _grad_weight_nd_native(signal.detach(), grad, tuple(kernel.shape), stride, padding, dilation,
-                                                  groups, padding_mode)
-                if d_kernel is None:
-                    d_kernel = _grad_weight_plans(signal.detach(), grad, tuple(kernel.shape), stride, padding, dilation,
-                                                  groups, padding_mode)
         if want_db and d_bias is None:
-            d_bias = grad.sum(dim=[0] + list(range(2, grad.ndim)))
+            d_bias = _grad_bias(grad)
+        if d_bias is not None:
+            d_bias = d_bias.to(kernel.dtype)
         return d_signal, d_kernel, d_bias, None, None, None, None, None, None
 
 
@@ -315,6 +360,7 @@ class FFTConvTransposeFunction(torch.autograd.Function):
                     flat += [0, conv_sp[i] - in_spatial[i]]
                 xg = F.pad(xg, flat)
             d_kernel = _grad_weight(grad, xg, tuple(kernel.shape), stride, padding, dilation, groups, "constant")
+            d_kernel = d_kernel.to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            d_bias = grad.sum(dim=[0] + list(range(2, grad.ndim)))
+            d_bias = _grad_bias(grad).to(kernel.dtype)
         return d_signal, d_kernel, d_bias, None, None, None, None, None, None

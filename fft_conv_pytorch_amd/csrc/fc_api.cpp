@@ -158,7 +158,7 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   if (d.ndim < 1 || d.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", d.ndim);
   if (d.dtype != FC_F32 && d.dtype != FC_F64 && d.dtype != FC_F16 && d.dtype != FC_BF16)
     return fail(FC_ERR_UNSUPPORTED, "dtype must be FC_F32, FC_F64, FC_F16 or FC_BF16");
-  if (sw && d.dtype != FC_F32) return fail(FC_ERR_UNSUPPORTED, "weight-gradient plans are float32 only");
+  if (sw && d.dtype == FC_F64) return fail(FC_ERR_UNSUPPORTED, "weight-gradient plans take float32, float16 or bfloat16 x and dY");
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
     return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
   if (d.in_channels % d.groups || d.out_channels % d.groups)
@@ -174,6 +174,8 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   // float32 plan's kernel spectrum serves it); only the launches' loads of x and stores of y take the element type
   p->io = d.dtype == FC_F64 ? FC_F32 : d.dtype;
   if (p->io != FC_F32) p->d.dtype = FC_F32;
+  // a weight-gradient plan reads 16-bit x and dY but writes a float32 dW (which segments of taps may add into)
+  p->io_y = sw ? FC_F32 : p->io;
   if (sw) { p->fnd.swap = 1; p->fnd.sw_B = sw->B; p->fnd.sw_Cig = sw->Cig; p->fnd.sw_Cog = sw->Cog; p->fnd.sw_g = sw->g; }
   if (d.transposed && d.padding_mode != FC_PAD_CONSTANT) {
     return fail(FC_ERR_INVALID, "a transposed plan supports zero padding only");
@@ -250,7 +252,7 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   else if (d.ndim == 1) { p->kind = PlanKind::F32_1D; rc = plan_1d(p.get()); }
   else { p->kind = PlanKind::F32_ND; rc = plan_nd(p.get()); }
   if (rc != FC_OK) return rc;
-  if (p->io != FC_F32) {
+  if (p->io_y != FC_F32) {
     // routes that read y back between launches would round a 16-bit output between them: not offered (the caller computes
     // such shapes in float32 and rounds once)
     const char* route = nullptr;
@@ -424,7 +426,8 @@ int fc_wgrad_nd_plan_create(const fc_desc* conv, fc_plan** out_plan) {
   *out_plan = nullptr;
   const fc_desc& c = *conv;
   if (c.ndim < 2 || c.ndim > 3) return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd covers 2-D and 3-D convolutions (1-D: fc_wgrad1d)");
-  if (c.dtype != FC_F32 || c.transposed) return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd: float32, not transposed");
+  if ((c.dtype != FC_F32 && c.dtype != FC_F16 && c.dtype != FC_BF16) || c.transposed)
+    return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd: float32, float16 or bfloat16 x and dY, not transposed");
   if (c.batch < 1 || c.in_channels < 1 || c.out_channels < 1 || c.groups < 1 || c.in_channels % c.groups || c.out_channels % c.groups)
     return fail(FC_ERR_INVALID, "batch, channels and groups must be positive and the channels divisible by groups");
   WgradSwap sw;

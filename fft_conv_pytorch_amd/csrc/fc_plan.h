@@ -66,7 +66,9 @@ struct fc_plan {
   fc_desc d;                  // (a float16 / bfloat16 plan holds its descriptor with dtype FC_F32: it is planned as float32)
   fc::PlanKind kind;
   int nd;
-  int io;                     // fc_dtype of x and y: FC_F32, FC_F16 or FC_BF16 on the float32 kinds (Io<> in fft_engine.hpp)
+  int io;                     // fc_dtype of x (and of the kernel' dY of a weight-gradient plan): FC_F32, FC_F16 or FC_BF16 on
+                              // the float32 kinds (Io<> in fft_engine.hpp)
+  int io_y;                   // fc_dtype of y: io, but FC_F32 for a weight-gradient plan (dW is float32 whatever x and dY are)
   // ---- axis geometry (axis 0 = fused (outermost), axis nd-1 = rows (x), middle axis only in 3-D)
   int64_t out_sp[3];
   int64_t kd[3];              // dilated kernel extent per axis

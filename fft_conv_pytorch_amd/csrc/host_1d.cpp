@@ -520,7 +520,9 @@ struct WgradGeom {
   int kd_seg, seg_taps, nseg, V, ntiles, nob, nib, Cig, Cog, n_items, ipw, slices, pad, diag;
 };
 int wgrad_geometry(const fc_desc& d, WgradGeom* g) {
-  if (d.ndim != 1 || d.dtype != FC_F32 || d.transposed || d.stride[0] < 1 || d.stride[0] > 64 || d.groups < 1) return 0;
+  // (float16 / bfloat16 x and dY: the float32 geometry -- same slices, segments and kernel -- with 16-bit loads)
+  if (d.dtype != FC_F32 && d.dtype != FC_F16 && d.dtype != FC_BF16) return 0;
+  if (d.ndim != 1 || d.transposed || d.stride[0] < 1 || d.stride[0] > 64 || d.groups < 1) return 0;
   if (d.batch < 1 || d.in_channels % d.groups || d.out_channels % d.groups) return 0;
   const int64_t Cig = d.in_channels / d.groups, Cog = d.out_channels / d.groups;
   if (Cig > 64 || Cog > 64) return 0;      // every 4 x 4 channel block repeats the transforms of its rows: beyond this the plan path wins
@@ -618,6 +620,7 @@ int fc_wgrad1d_db(const fc_desc* desc, const float* x, const float* dy, float* p
   a.scale = 1.0f / (4.0f * (float)g.t->T);
   a.Krow = (int)d.kernel[0];
   a.part_stride = slice_stride;
+  a.io = d.dtype;                                  // FC_F32 (0), FC_F16 or FC_BF16 (fft_engine.hpp IO_CODE_*)
   const int64_t grid = g.diag ? (int64_t)g.slices * (d.groups / 8) : (int64_t)g.slices * d.groups * g.nob * g.nib;
   if (grid > 0x7fffffff) return fail(FC_ERR_UNSUPPORTED, "grid too large");
   for (int j = 0; j < g.nseg; ++j) {

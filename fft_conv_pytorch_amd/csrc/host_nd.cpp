@@ -386,7 +386,8 @@ static int transform_kernel_nd_segment(const fc_plan& p, const float* weight, vo
       m.mode = FC_PAD_CONSTANT; m.up = (int)dil; return m;
     };
     r.mx = tmap(zx, r.kx, r.dx); r.my = tmap(zy, r.ky, r.dy); r.mz = tmap(nd == 3 ? 0 : -1, r.kz, r.dz);
-    const unsigned long long bytes = 4ull * (unsigned long long)r.NA * r.SZ * r.SY * r.SX;
+    r.io = p.io;                             // dY has the element type of x
+    const unsigned long long bytes = (p.io == FC_F32 ? 4ull : 2ull) * (unsigned long long)r.NA * r.SZ * r.SY * r.SX;
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
   FC_HIP(p.fnd.tx->rows_r2c(r, st));
@@ -450,7 +451,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     // (the tiles of a plane share the spectrum's 2048 columns)
     FC_HIP(p.tile->colz(colz_args(p, wsA, w_hat, wsB, fc::kPlCols * p.fnd.nxt * p.fnd.nyt, fc::kPlCols, stamps), st));
     fc::PlaneInvArgs f3{};
-    f3.src = wsB; f3.dst = y; f3.bias = p.d.has_bias ? bias : nullptr; f3.twA = p.fnd.twx.twA; f3.twB = p.fnd.twx.twB; f3.io = p.io;
+    f3.src = wsB; f3.dst = y; f3.bias = p.d.has_bias ? bias : nullptr; f3.twA = p.fnd.twx.twA; f3.twB = p.fnd.twx.twB; f3.io = p.io_y;
     f3.NZo = (int)p.out_sp[0]; f3.Cout = Co;
     f3.NVy = p.Lf[1]; f3.sy = p.ostride[1]; f3.Yo = (int)p.out_sp[1];
     f3.NVx = p.Lf[2]; f3.sx = p.ostride[2]; f3.Xo = (int)p.out_sp[2];
@@ -487,7 +488,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   f.stamps = (unsigned long long*)stamps;
 
   fc::RowsC2RArgs o{};
-  o.dst = y; o.bias = p.d.has_bias ? bias : nullptr; o.twA = p.fnd.twx.twA; o.twB = p.fnd.twx.twB; o.io = p.io;
+  o.dst = y; o.bias = p.d.has_bias ? bias : nullptr; o.twA = p.fnd.twx.twA; o.twB = p.fnd.twx.twB; o.io = p.io_y;
   o.NA = B * Co; o.Fx = p.fnd.Fx; o.Cout = Co; o.nxt = p.fnd.nxt; o.Vx = p.fnd.Vx;
   f.wfx = p.fnd.Fx; f.wty = nd == 3 ? p.fnd.tm->T : 1; f.wrep = nd == 3 ? p.fnd.nyt : 1; f.wncol = f.wfx * f.wty;
   o.NV = p.Lf[nd - 1]; o.stride = p.ostride[nd - 1]; o.Xo = (int)p.out_sp[nd - 1];

@@ -290,9 +290,11 @@ hipError_t wide_dispatch(const Conv1dPersArgs&, int, hipStream_t) { return hipEr
 
 #if FC_P == 32 && FC_S == 1
 constexpr int kWgradNb = 2;
-hipError_t wgrad_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
+// IO: element type of x and dY (the 16-bit builds serve float16 and bfloat16 through a.io)
+template <int IO>
+hipError_t launch_wgrad(const WGradArgs& a, int grid, hipStream_t st) {
   constexpr int NT = kWgradNb * 4 * GG::TS;
-  auto k = wgrad1d_kernel<FC_P, FC_S, kWgradNb, NT>;
+  auto k = wgrad1d_kernel<FC_P, FC_S, kWgradNb, NT, IO>;
   const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)kWgradNb * 4 * GG::LSEQ) * sizeof(float2);
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
@@ -300,15 +302,22 @@ hipError_t wgrad_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
   hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
   return hipGetLastError();
 }
-hipError_t wgrad_diag_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
+hipError_t wgrad_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
+  return a.io != 0 ? launch_wgrad<IO_H16>(a, grid, st) : launch_wgrad<IO_F32>(a, grid, st);
+}
+template <int IO>
+hipError_t launch_wgrad_diag(const WGradArgs& a, int grid, hipStream_t st) {
   constexpr int NT = 8 * GG::TS;
-  auto k = wgrad1d_diag_kernel<FC_P, FC_S, NT>;
+  auto k = wgrad1d_diag_kernel<FC_P, FC_S, NT, IO>;
   const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)8 * GG::LSEQ) * sizeof(float2);
   static LdsOptIn done;
   hipError_t e = ensure_lds(k, lds, &done);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
   return hipGetLastError();
+}
+hipError_t wgrad_diag_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
+  return a.io != 0 ? launch_wgrad_diag<IO_H16>(a, grid, st) : launch_wgrad_diag<IO_F32>(a, grid, st);
 }
 #else
 constexpr int kWgradNb = 0;

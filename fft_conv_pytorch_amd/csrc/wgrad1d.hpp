@@ -16,14 +16,18 @@
 // kernel), NB items at a time.  In the accumulation step a thread owns BP bin pairs (f, T-f) and the 16
 // cross-spectra of the block at those bins.  The self-paired bins 0 and T/2 (real) share one complex
 // accumulator per (o, i): .x = bin 0, .y = bin T/2.  Partial results (one per slice) are summed by the caller.
+//
+// x and dY are float32 or 16-bit (IO = IO_H16: float16 or bfloat16 by the wave-uniform `io` flag, Io<> in fft_engine.hpp),
+// widened exactly as they are loaded; everything after the loads, the partials and the bias-gradient partials included,
+// is the float32 kernel's arithmetic.
 #pragma once
 #include "conv1d_fused.hpp"
 
 namespace fc {
 
 struct WGradArgs {
-  const float* x;      // (B, Cin, L)
-  const float* dy;     // (B, Cout, Lout)
+  const float* x;      // (B, Cin, L)       elements of type `io`
+  const float* dy;     // (B, Cout, Lout)   elements of type `io`
   float* part;         // [slices][Cout][Cig][K]
   const f2* twA;       // pass-A table of the tile
   const f2* twB;
@@ -40,7 +44,26 @@ struct WGradArgs {
   float* dbpart;                   // optional: bias gradient partials, dbpart[slice*part_stride + channel] (dense kernel,
                                    // first tap segment only): db[o] = sum of dY = bin 0 of the gradient spectra this
                                    // kernel forms anyway -- the separate reduction over dY (a 33 MB read at cfgA) goes away
+  int io = 0;                      // element type of x and dY (fc_dtype: 0 float32, 2 float16, 3 bfloat16; Io<IO> in
+                                   // fft_engine.hpp); part and dbpart are float32 either way
 };
+
+// 16-bit loads of P sample pairs (row 0 -> .x, row 1 -> .y), off(n1, h) giving the byte offset of sample n1 of row h
+// (out of range: reads as zero).  Every load is issued before the first sample is widened: widened right behind its load,
+// each sample made the compiler wait for that load before issuing the next (64 loads in turn per sequence; the 16-bit
+// wgrad1d_kernel took 2.1x the float32 one at cfgA).  The float32 builds load straight into v as before.
+template <int P, class Off>
+__device__ __forceinline__ void load_pairs_h16(const Io<IO_H16>& io, BufRsrc r, f2 (&v)[P], Off off) {
+  unsigned w0[P], w1[P];
+#pragma unroll
+  for (int n1 = 0; n1 < P; ++n1) {
+    w0[n1] = __builtin_amdgcn_raw_buffer_load_b16(r, off(n1, 0), 0, 0);
+    w1[n1] = __builtin_amdgcn_raw_buffer_load_b16(r, off(n1, 1), 0, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int n1 = 0; n1 < P; ++n1) v[n1] = mk2(io.in(w0[n1]), io.in(w1[n1]));
+}
 
 // acc += conj(y) * x
 __device__ __forceinline__ void cmacc(f2& acc, f2 y, f2 x) {
@@ -48,9 +71,11 @@ __device__ __forceinline__ void cmacc(f2& acc, f2 y, f2 x) {
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_hi:[0,1,0]" : "+v"(acc) : "v"(y), "v"(x));
 }
 
-template <int P, int S, int NB, int NT>
+template <int P, int S, int NB, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT, 2) void wgrad1d_kernel(const WGradArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;        // bytes per sample of x and dY
   constexpr int T = G::T;
   constexpr int NSEQ = NB * 4;              // per item: 2 input pairs + 2 output-gradient pairs
   static_assert(NT == NSEQ * G::TS, "one thread slot per point group of every sequence");
@@ -79,8 +104,8 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_kernel(const WGradArgs a) {
 
   const PadMap pm = make_padmap(a.pad_mode, a.L);
   const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
-  const BufRsrc xr = make_rsrc(a.x, (unsigned)((size_t)a.B * a.Cin * a.L * 4));
-  const BufRsrc yr = make_rsrc(a.dy, (unsigned)((size_t)a.B * a.Cout * a.Lout * 4));
+  const BufRsrc xr = make_rsrc(a.x, (unsigned)((size_t)a.B * a.Cin * a.L * ES));
+  const BufRsrc yr = make_rsrc(a.dy, (unsigned)((size_t)a.B * a.Cout * a.Lout * ES));
   copy_table_to_lds<TWN, NT>(twl, a.twA, tid);
 
   f2 acc[BP][4][4];                          // [bin pair][o][i]
@@ -104,38 +129,57 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_kernel(const WGradArgs a) {
       if (role == 0) {
         const int ci0 = ib * 4 + 2 * pr;
         const bool has0 = ci0 < a.Cig, has1 = ci0 + 1 < a.Cig;
-        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cin + (unsigned)(g * a.Cig + ci0)) * (unsigned)a.L * 4u;
-        const unsigned ro1 = ro0 + (unsigned)a.L * 4u;
+        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cin + (unsigned)(g * a.Cig + ci0)) * (unsigned)a.L * ES;
+        const unsigned ro1 = ro0 + (unsigned)a.L * ES;
         const int tile_pos = tile * a.V - a.pad + a.pos_shift;
         if (tile_pos >= 0 && tile_pos + T <= a.L && has1) {
-          const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * 4u, v1 = ro1 + (unsigned)(tile_pos + tseq) * 4u;
+          const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * ES, v1 = ro1 + (unsigned)(tile_pos + tseq) * ES;
+          if constexpr (IO == IO_F32) {
 #pragma unroll
-          for (int n1 = 0; n1 < P; ++n1) {
-            v[n1].x = buf_load_f32(xr, v0, G::N2 * n1 * 4);
-            v[n1].y = buf_load_f32(xr, v1, G::N2 * n1 * 4);
+            for (int n1 = 0; n1 < P; ++n1) {
+              v[n1].x = io.load(xr, v0, G::N2 * n1 * ES);
+              v[n1].y = io.load(xr, v1, G::N2 * n1 * ES);
+            }
+          } else {
+            load_pairs_h16<P>(io, xr, v, [&](int n1, int h) { return (h ? v1 : v0) + G::N2 * n1 * ES; });
           }
         } else {
 #pragma unroll
           for (int n1 = 0; n1 < P; ++n1) {
             const int pos = tile_pos + G::N2 * n1 + tseq;
-            v[n1].x = buf_load_f32(xr, padded_offset(ro0, pos, a.L, a.pad, pm, has0), 0);
-            v[n1].y = buf_load_f32(xr, padded_offset(ro1, pos, a.L, a.pad, pm, has1), 0);
+            v[n1].x = io.load(xr, padded_offset<ES>(ro0, pos, a.L, a.pad, pm, has0), 0);
+            v[n1].y = io.load(xr, padded_offset<ES>(ro1, pos, a.L, a.pad, pm, has1), 0);
           }
         }
       } else {
         const int co0 = ob * 4 + 2 * pr;
         const bool has0 = co0 < a.Cog, has1 = co0 + 1 < a.Cog;
-        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cout + (unsigned)(g * a.Cog + co0)) * (unsigned)a.Lout * 4u;
-        const unsigned ro1 = ro0 + (unsigned)a.Lout * 4u;
+        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cout + (unsigned)(g * a.Cog + co0)) * (unsigned)a.Lout * ES;
+        const unsigned ro1 = ro0 + (unsigned)a.Lout * ES;
         const int t0 = tile * a.V;
         const int limit = min(a.V, a.Lext - t0);        // gradient positions of this tile (zero beyond)
-        if (a.stride == 1) {
+        if constexpr (IO != IO_F32) {
+          if (a.stride == 1) {
+            load_pairs_h16<P>(io, yr, v, [&](int n1, int h) {
+              const int n = G::N2 * n1 + tseq;
+              return (n < limit && (h ? has1 : has0)) ? (h ? ro1 : ro0) + (unsigned)(t0 + n) * ES : 0xFFFFFFFFu;
+            });
+          } else {
+            const int q0 = t0 / a.stride;                  // (t0 is a multiple of the stride)
+            load_pairs_h16<P>(io, yr, v, [&](int n1, int h) {
+              const int n = G::N2 * n1 + tseq;
+              const int nq = n / a.stride;
+              return (n < limit && nq * a.stride == n && (h ? has1 : has0)) ? (h ? ro1 : ro0) + (unsigned)(q0 + nq) * ES
+                                                                            : 0xFFFFFFFFu;
+            });
+          }
+        } else if (a.stride == 1) {
 #pragma unroll
           for (int n1 = 0; n1 < P; ++n1) {
             const int n = G::N2 * n1 + tseq;
             const bool in = n < limit;
-            v[n1].x = buf_load_f32(yr, (in && has0) ? ro0 + (unsigned)(t0 + n) * 4u : 0xFFFFFFFFu, 0);
-            v[n1].y = buf_load_f32(yr, (in && has1) ? ro1 + (unsigned)(t0 + n) * 4u : 0xFFFFFFFFu, 0);
+            v[n1].x = io.load(yr, (in && has0) ? ro0 + (unsigned)(t0 + n) * ES : 0xFFFFFFFFu, 0);
+            v[n1].y = io.load(yr, (in && has1) ? ro1 + (unsigned)(t0 + n) * ES : 0xFFFFFFFFu, 0);
           }
         } else {
           const int q0 = t0 / a.stride;                  // (t0 is a multiple of the stride)
@@ -144,8 +188,8 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_kernel(const WGradArgs a) {
             const int n = G::N2 * n1 + tseq;
             const int nq = n / a.stride;
             const bool in = n < limit && nq * a.stride == n;
-            v[n1].x = buf_load_f32(yr, (in && has0) ? ro0 + (unsigned)(q0 + nq) * 4u : 0xFFFFFFFFu, 0);
-            v[n1].y = buf_load_f32(yr, (in && has1) ? ro1 + (unsigned)(q0 + nq) * 4u : 0xFFFFFFFFu, 0);
+            v[n1].x = io.load(yr, (in && has0) ? ro0 + (unsigned)(q0 + nq) * ES : 0xFFFFFFFFu, 0);
+            v[n1].y = io.load(yr, (in && has1) ? ro1 + (unsigned)(q0 + nq) * ES : 0xFFFFFFFFu, 0);
           }
         }
       }
@@ -283,9 +327,11 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_kernel(const WGradArgs a) {
 // Depthwise variant (groups == Cin == Cout, a multiple of 8): a workgroup owns the 8 channels of block g
 // and a slice of the items; per item it transforms 4 input pairs + 4 gradient pairs and accumulates ONE
 // cross-spectrum per channel (8 per bin pair).  part is [slices][C][1][Krow].
-template <int P, int S, int NT>
+template <int P, int S, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT, 2) void wgrad1d_diag_kernel(const WGradArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
   constexpr int T = G::T;
   constexpr int NSEQ = 8;
   static_assert(NT == NSEQ * G::TS, "one thread slot per point group of every sequence");
@@ -310,8 +356,8 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_diag_kernel(const WGradArgs a) 
 
   const PadMap pm = make_padmap(a.pad_mode, a.L);
   const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
-  const BufRsrc xr = make_rsrc(a.x, (unsigned)((size_t)a.B * a.Cin * a.L * 4));
-  const BufRsrc yr = make_rsrc(a.dy, (unsigned)((size_t)a.B * a.Cout * a.Lout * 4));
+  const BufRsrc xr = make_rsrc(a.x, (unsigned)((size_t)a.B * a.Cin * a.L * ES));
+  const BufRsrc yr = make_rsrc(a.dy, (unsigned)((size_t)a.B * a.Cout * a.Lout * ES));
   copy_table_to_lds<TWN, NT>(twl, a.twA, tid);
 
   f2 acc[BP][4][2];                          // [bin pair][channel pair][even / odd channel]
@@ -327,37 +373,49 @@ __global__ __launch_bounds__(NT, 2) void wgrad1d_diag_kernel(const WGradArgs a) 
     {
       f2 v[P];
       if (role == 0) {
-        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cin + (unsigned)c0) * (unsigned)a.L * 4u;
-        const unsigned ro1 = ro0 + (unsigned)a.L * 4u;
+        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cin + (unsigned)c0) * (unsigned)a.L * ES;
+        const unsigned ro1 = ro0 + (unsigned)a.L * ES;
         const int tile_pos = tile * a.V - a.pad + a.pos_shift;
         if (tile_pos >= 0 && tile_pos + T <= a.L) {
-          const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * 4u, v1 = ro1 + (unsigned)(tile_pos + tseq) * 4u;
+          const unsigned v0 = ro0 + (unsigned)(tile_pos + tseq) * ES, v1 = ro1 + (unsigned)(tile_pos + tseq) * ES;
+          if constexpr (IO == IO_F32) {
 #pragma unroll
-          for (int n1 = 0; n1 < P; ++n1) {
-            v[n1].x = buf_load_f32(xr, v0, G::N2 * n1 * 4);
-            v[n1].y = buf_load_f32(xr, v1, G::N2 * n1 * 4);
+            for (int n1 = 0; n1 < P; ++n1) {
+              v[n1].x = io.load(xr, v0, G::N2 * n1 * ES);
+              v[n1].y = io.load(xr, v1, G::N2 * n1 * ES);
+            }
+          } else {
+            load_pairs_h16<P>(io, xr, v, [&](int n1, int h) { return (h ? v1 : v0) + G::N2 * n1 * ES; });
           }
         } else {
 #pragma unroll
           for (int n1 = 0; n1 < P; ++n1) {
             const int pos = tile_pos + G::N2 * n1 + tseq;
-            v[n1].x = buf_load_f32(xr, padded_offset(ro0, pos, a.L, a.pad, pm, true), 0);
-            v[n1].y = buf_load_f32(xr, padded_offset(ro1, pos, a.L, a.pad, pm, true), 0);
+            v[n1].x = io.load(xr, padded_offset<ES>(ro0, pos, a.L, a.pad, pm, true), 0);
+            v[n1].y = io.load(xr, padded_offset<ES>(ro1, pos, a.L, a.pad, pm, true), 0);
           }
         }
       } else {
-        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cout + (unsigned)c0) * (unsigned)a.Lout * 4u;
-        const unsigned ro1 = ro0 + (unsigned)a.Lout * 4u;
+        const unsigned ro0 = ((unsigned)b * (unsigned)a.Cout + (unsigned)c0) * (unsigned)a.Lout * ES;
+        const unsigned ro1 = ro0 + (unsigned)a.Lout * ES;
         const int t0 = tile * a.V;
         const int limit = min(a.V, a.Lext - t0);
         const int q0 = t0 / a.stride;
+        if constexpr (IO == IO_F32) {
 #pragma unroll
-        for (int n1 = 0; n1 < P; ++n1) {
-          const int n = G::N2 * n1 + tseq;
-          const int nq = a.stride == 1 ? n : n / a.stride;
-          const bool in = n < limit && nq * a.stride == n;
-          v[n1].x = buf_load_f32(yr, in ? ro0 + (unsigned)(q0 + nq) * 4u : 0xFFFFFFFFu, 0);
-          v[n1].y = buf_load_f32(yr, in ? ro1 + (unsigned)(q0 + nq) * 4u : 0xFFFFFFFFu, 0);
+          for (int n1 = 0; n1 < P; ++n1) {
+            const int n = G::N2 * n1 + tseq;
+            const int nq = a.stride == 1 ? n : n / a.stride;
+            const bool in = n < limit && nq * a.stride == n;
+            v[n1].x = io.load(yr, in ? ro0 + (unsigned)(q0 + nq) * ES : 0xFFFFFFFFu, 0);
+            v[n1].y = io.load(yr, in ? ro1 + (unsigned)(q0 + nq) * ES : 0xFFFFFFFFu, 0);
+          }
+        } else {
+          load_pairs_h16<P>(io, yr, v, [&](int n1, int h) {
+            const int n = G::N2 * n1 + tseq;
+            const int nq = a.stride == 1 ? n : n / a.stride;
+            return (n < limit && nq * a.stride == n) ? (h ? ro1 : ro0) + (unsigned)(q0 + nq) * ES : 0xFFFFFFFFu;
+          });
         }
       }
       passA_fft_twiddle_store_lds<G, -1>(v, zseq, tseq, twl);

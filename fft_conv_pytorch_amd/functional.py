@@ -212,10 +212,10 @@ _REFUSED_HALF: "collections.OrderedDict[tuple, str]" = collections.OrderedDict()
 
 
 def _half_native(signal: Tensor, kernel: Tensor, bias) -> bool:
-    """A float16 / bfloat16 call the kernels read and write in its own dtype: the three tensors agree, no gradient is
-    required (autograd keeps the float32 cast path) and FFTCONV_HALF_IO is not 0."""
+    """A float16 / bfloat16 call the kernels read and write in its own dtype: the three tensors agree and FFTCONV_HALF_IO
+    is not 0.  A call that needs gradients then runs the autograd function on the 16-bit tensors (autograd.py)."""
     return (signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype
-            and (bias is None or bias.dtype == signal.dtype) and not _needs_grad(signal, kernel, bias)
+            and (bias is None or bias.dtype == signal.dtype)
             and os.environ.get("FFTCONV_HALF_IO", "1") != "0")
 
 
@@ -258,6 +258,12 @@ def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padd
         except NotImplementedError:
             plan = None       # a refused route (reads y back between launches): the cast path
         if plan is not None:
+            if _needs_grad(signal, kernel, bias):
+                # 16-bit tensors saved for backward, whose kernels read 16-bit dY and x (autograd.py)
+                from .autograd import FFTConvFunction
+                n = signal.ndim - 2
+                return FFTConvFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
+                                             to_ntuple(dilation, n), groups, padding_mode, spectrum)
             if spectrum is None or spectrum.plan is not plan:
                 spectrum = transform_kernel(plan, kernel)
             return _forward_native(signal, spectrum, bias)
@@ -310,6 +316,12 @@ def _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_paddi
         except NotImplementedError:
             plan = None
         if plan is not None:
+            if _needs_grad(signal, kernel, bias):
+                from .autograd import FFTConvTransposeFunction
+                n = signal.ndim - 2
+                return FFTConvTransposeFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
+                                                      to_ntuple(output_padding, n), to_ntuple(dilation, n), groups,
+                                                      spectrum)
             if spectrum is None or spectrum.plan is not plan:
                 spectrum = transform_kernel(plan, kernel)
             return _forward_native(signal, spectrum, bias)

@@ -100,7 +100,7 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
         if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64)
                                              and not F_._half_native(signal, self.weight, self.bias)):
             # padding='same' / 'valid' (torch stores the string) and half-precision calls the kernels do not read and write
-            # in their own dtype (gradients, FFTCONV_HALF_IO=0, mixed dtypes): the functional resolves them
+            # in their own dtype (FFTCONV_HALF_IO=0, mixed dtypes): the functional resolves them
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                      self.groups, padding_mode, None)
         try:
@@ -112,7 +112,8 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                      self.groups, padding_mode, None)
         spectrum = self._cached_spectrum(plan)
-        if spectrum is not None and signal.dtype in F_._LOW_PRECISION:     # (no widening kernel per call)
+        if (spectrum is not None and signal.dtype in F_._LOW_PRECISION      # (no widening kernel per call)
+                and not F_._needs_grad(signal, self.weight, self.bias)):
             return F_._forward_native(signal, spectrum, self._cached_bias(plan))
         return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                  self.groups, padding_mode, spectrum, plan)
@@ -149,7 +150,7 @@ class _FFTConvTransposeForward(_SpectrumCache, nn.Module):
                 raise
             return cast()      # a float16 / bfloat16 shape whose route the library refuses
         spectrum = self._cached_spectrum(plan)
-        if spectrum is not None and signal.dtype in F_._LOW_PRECISION:
+        if spectrum is not None and signal.dtype in F_._LOW_PRECISION and not F_._needs_grad(signal, self.weight, self.bias):
             return F_._forward_native(signal, spectrum, self._cached_bias(plan))
         return F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,
                                            self.output_padding, self.dilation, self.groups, spectrum, plan)

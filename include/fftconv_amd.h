@@ -36,7 +36,7 @@ enum fc_dtype {
                   parameters); double-precision FFT kernels compute the same function (the reference is dtype-agnostic):
                   1-D plans with >= 16 taps, 2-D / 3-D plans from 100 multiply-adds per output (Cin/groups x
                   prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  N-d plans need
-                  fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook are float32-only */
+                  fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook take no float64 */
   FC_F16 = 2,
   FC_BF16 = 3  /* float16 / bfloat16 signal and output (ABI 7): x and y are 16-bit (pass them through the float* parameters);
                   weight, w_hat and bias stay float32 (the caller widens the weight and the bias).  The kernels widen x exactly as
@@ -45,7 +45,13 @@ enum fc_dtype {
                   descriptor under the same knobs: equal fc_debug_route, fc_plan_layout, fc_kernel_spectrum_bytes and
                   fc_workspace_bytes, so a float32 plan's spectrum serves it.  Routes that add into y across launches are refused
                   with FC_ERR_UNSUPPORTED, the text naming the route: 1-D chunk launches, 1-D segments of taps, 2-D / 3-D
-                  segments of taps.  fc_forward_stamped, fc_wgrad1d* and fc_wgrad_nd* take no 16-bit plan or descriptor */
+                  segments of taps.  fc_forward_stamped takes no 16-bit plan.
+                  Weight gradients (ABI 7 extension): fc_wgrad1d_slices, fc_wgrad1d, fc_wgrad1d_db, fc_wgrad1d_db_supported
+                  and fc_wgrad_nd_plan_create accept a 16-bit descriptor.  x and dy are then 16-bit; partial, db_partial,
+                  dw, the spectrum and the workspace stay float32.  Sizes, slices and the route equal those of the float32
+                  descriptor, and the loads widen exactly, so every partial and dW has the float32 call's bits on the widened
+                  tensors; segments of taps add into the float32 dW as they do there.  A library that predates this answers
+                  such a descriptor with 0 slices or FC_ERR_UNSUPPORTED: a caller widens x and dy for that gradient. */
 };
 
 /* Problem descriptor: the arguments of functional.py:19-28 after to_ntuple
@@ -135,6 +141,7 @@ int fc_forward(const fc_plan* plan, const float* x, const void* w_hat, const flo
  * (the caller then differentiates through fc_forward plans instead); it also builds the device tables
  * the launch needs, so fc_wgrad1d itself never allocates or copies (call fc_wgrad1d_slices first, on the
  * same device -- the caller needs its answer to size `partial` anyway). */
+/* desc->dtype may be FC_F16 / FC_BF16: x and dy are then 16-bit, partial and db_partial float32 (see fc_dtype). */
 int fc_wgrad1d_slices(const fc_desc* desc);
 int fc_wgrad1d(const fc_desc* desc, const float* x, const float* dy, float* partial, int slices, void* hip_stream);
 /* The same launch with the bias gradient folded in (ABI 5): db[o] = sum over batch and row of dY[b][o][t] is bin 0 of the
@@ -155,6 +162,7 @@ int fc_wgrad1d_db(const fc_desc* desc, const float* x, const float* dy, float* p
  * two scratch buffers).  fc_wgrad_nd transforms dY (B, Cout, *Lout), runs x (B, Cin, *S) against it and writes
  * dw (Cout, Cin/groups, *k) completely -- both tensors are read and dW is written in these layouts, no transposed
  * copies, no partial results.  Asynchronous on hip_stream; allocates nothing. */
+/* conv_desc->dtype may be FC_F16 / FC_BF16: x and dy are then 16-bit, dw, spectrum and workspace float32 (see fc_dtype). */
 int fc_wgrad_nd_plan_create(const fc_desc* conv_desc, fc_plan** out_plan);
 int fc_wgrad_nd(const fc_plan* plan, const float* x, const float* dy, float* dw, void* spectrum, void* workspace,
                 void* hip_stream);

@@ -24,6 +24,8 @@ EXPORTS = (
     "fc_kernel_spectrum_bytes", "fc_workspace_bytes", "fc_plan_tile", "fc_plan_layout", "fc_transform_kernel",
     "fc_forward", "fc_forward_stamped", "fc_wgrad1d_slices", "fc_wgrad1d", "fc_wgrad1d_db", "fc_wgrad1d_db_supported",
     "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd", "fc_debug_route",
+    "fc_long_geometry", "fc_long_plan_create", "fc_long_plan_destroy", "fc_long_plan_info", "fc_long_transform_kernel",
+    "fc_long_forward",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -51,6 +53,19 @@ class FcDesc(ctypes.Structure):
         ("transposed", ctypes.c_int32),
         ("output_padding", ctypes.c_int64 * 3),
     ]
+
+
+class FcLongDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_desc`` (the long-filter plans)."""
+    _fields_ = [
+        ("batch", ctypes.c_int64), ("in_channels", ctypes.c_int64), ("out_channels", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("length", ctypes.c_int64), ("kernel", ctypes.c_int64),
+        ("pad_left", ctypes.c_int64), ("pad_right", ctypes.c_int64), ("out_keep", ctypes.c_int64),
+        ("flip", ctypes.c_int32), ("has_bias", ctypes.c_int32),
+    ]
+
+
+LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
 class NativeLibraryMissing(ImportError):
@@ -113,6 +128,19 @@ def load_library() -> ctypes.CDLL:
         lib.fc_debug_grid.restype = ctypes.c_longlong
         lib.fc_debug_route.argtypes = [vp, ctypes.POINTER(ctypes.c_int32 * 16)]
         lib.fc_debug_route.restype = i32
+        i64x8 = ctypes.POINTER(ctypes.c_int64 * 8)
+        lib.fc_long_geometry.argtypes = [ctypes.POINTER(FcLongDesc), i64x8]
+        lib.fc_long_geometry.restype = i32
+        lib.fc_long_plan_create.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(vp)]
+        lib.fc_long_plan_create.restype = i32
+        lib.fc_long_plan_destroy.argtypes = [vp]
+        lib.fc_long_plan_destroy.restype = None
+        lib.fc_long_plan_info.argtypes = [vp, i64x8]
+        lib.fc_long_plan_info.restype = i32
+        lib.fc_long_transform_kernel.argtypes = [vp, vp, vp, vp, vp]
+        lib.fc_long_transform_kernel.restype = i32
+        lib.fc_long_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.fc_long_forward.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -294,6 +322,65 @@ class Plan:
             pass
 
 
+def long_desc(key: Tuple) -> FcLongDesc:
+    """``struct fc_long_desc`` of a long-plan key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_keep, flip,
+    has_bias)."""
+    d = FcLongDesc()
+    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_keep,
+     d.flip, d.has_bias) = (int(v) for v in key)
+    return d
+
+
+def long_geometry(key: Tuple) -> dict:
+    """``fc_long_geometry``: the info words of the plan this key would get, from the descriptor alone (no device)."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    st = lib.fc_long_geometry(ctypes.byref(long_desc(key)), ctypes.byref(info))
+    if st != FC_OK:
+        _raise(lib, st)
+    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+
+
+class LongPlan:
+    """Owns one ``fc_long_plan`` (long-filter path; immutable after creation): created on the CURRENT HIP device, which the
+    caller sets to ``device_index``.  Quacks like ``Plan`` where ``KernelSpectrum`` and ``new_workspace`` look."""
+
+    def __init__(self, key: Tuple, device_index: int = 0):
+        lib = load_library()
+        handle = ctypes.c_void_p()
+        st = lib.fc_long_plan_create(ctypes.byref(long_desc(key)), ctypes.byref(handle))
+        if st != FC_OK:
+            _raise(lib, st)
+        self._lib, self._h, self.key = lib, handle, key
+        self.device_index = int(device_index)
+        info = (ctypes.c_int64 * 8)()
+        lib.fc_long_plan_info(handle, ctypes.byref(info))
+        self.info = {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+        self.out_len = self.info["out_len"]
+        self.spectrum_bytes = self.info["spectrum_bytes"]
+        self.workspace_bytes = self.info["workspace_bytes"]
+        import torch
+        self.dtype = self.weight_dtype = torch.float32
+
+    def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int):
+        st = self._lib.fc_long_transform_kernel(self._h, weight_ptr, spectrum_ptr, workspace_ptr, stream)
+        if st != FC_OK:
+            _raise(self._lib, st)
+
+    def forward(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int, stream: int):
+        st = self._lib.fc_long_forward(self._h, x_ptr, spectrum_ptr, bias_ptr, y_ptr, workspace_ptr, stream)
+        if st != FC_OK:
+            _raise(self._lib, st)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.fc_long_plan_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
 # otherwise keep one plan (and its device work list) alive per shape ever seen.  An evicted plan is
 # destroyed when the last KernelSpectrum / module that still refers to it lets go.
@@ -318,7 +405,8 @@ def get_plan(device_index: int, key: Tuple) -> Plan:
     with _plans_lock:
         plan = _plans.get(full)
         if plan is None:
-            plan = Plan(key, device_index)
+            # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
+            plan = LongPlan(key[1:], device_index) if key and key[0] == "long" else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):
                 _plans.popitem(last=False)

@@ -364,3 +364,49 @@ class FFTConvTransposeFunction(torch.autograd.Function):
         if has_bias and ctx.needs_input_grad[2]:
             d_bias = _grad_bias(grad).to(kernel.dtype)
         return d_signal, d_kernel, d_bias, None, None, None, None, None, None
+
+
+class FFTLongConvFunction(torch.autograd.Function):
+    """``fft_long_conv`` with its three gradients, each through the same three kernels (``F_._long_run``, the primitive
+    y[t] = sum_k u[k] * xpad[t + k] with separate left / right zero padding, a tap order and a count of kept samples):
+
+        dX = the primitive on dY with the opposite tap order, the complementary padding (K - 1 - pad) and in / out
+             channels exchanged;
+        dW = the primitive with batch and channels exchanged, signal' = x as (Cin/g, g*B, L), kernel' = dY as
+             (Cout, B, Lout), the first K lags kept -- flipped afterwards when the forward read the taps flipped (causal);
+        db = dY summed over batch and row.
+
+    torch builds the transposed copies of the operands."""
+
+    @staticmethod
+    def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum):
+        ctx.save_for_backward(signal, kernel)
+        ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None)
+        keep = signal.shape[2] if causal else 0
+        return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal, keep, groups, spectrum)
+
+    @staticmethod
+    def backward(ctx, grad):
+        signal, kernel = ctx.saved_tensors
+        pad_left, pad_right, flip, g, has_bias = ctx.cfg
+        grad = grad.detach().contiguous()
+        B, cin, L = signal.shape
+        cout, cig, K = kernel.shape
+        cog = cout // g
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
+            pl, pr, dy = K - 1 - pad_left, K - 1 - pad_right, grad
+            if pl < 0:          # padding wider than the filter: those leading output samples never met the data
+                dy, pl = dy[..., -pl:], 0
+            if pr < 0:
+                dy, pr = dy[..., :dy.shape[2] + pr], 0
+            dx = F_._long_run(dy, wt, None, pl, pr, not flip, L, g)
+        if ctx.needs_input_grad[1]:
+            xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
+            dyt = grad.permute(1, 0, 2).contiguous()
+            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g).permute(1, 0, 2)
+            dw = (du.flip(-1) if flip else du).contiguous()
+        if has_bias and ctx.needs_input_grad[2]:
+            db = grad.sum(dim=(0, 2))
+        return dx, dw, db, None, None, None, None, None

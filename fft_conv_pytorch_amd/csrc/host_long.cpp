@@ -1,0 +1,285 @@
+// host_long.cpp -- plans and launches the long-filter path (include/fftconv_amd.h "Long filters", kernels in
+// long1d.hpp): descriptor checks, the factorisation N = N1 * N2, sizes, slabs, the two-table twiddles, the launches.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "fc_plan.h"
+#include "long1d.hpp"
+
+namespace {
+
+using namespace fc;
+
+constexpr int64_t kMaxN = (int64_t)1 << 24;        // 4096 x 4096
+constexpr int64_t kDefaultBudgetMB = 8192;         // W1 + W2 of one slab
+
+const LongImpl* find_long(int T) {
+  static const LongImpl* impls[] = {get_long_P8_S1(),  get_long_P8_S2(),  get_long_P16_S1(), get_long_P16_S2(),
+                                    get_long_P32_S1(), get_long_P32_S2(), get_long_P32_S4()};
+  for (const LongImpl* l : impls)
+    if (l->T == T) return l;
+  return nullptr;
+}
+
+struct LongGeom {
+  int64_t B, Cin, Cout, G, Cig, Cog, L, K;
+  int64_t nout;                 // kept output samples
+  int64_t padl;                 // row position p holds x[p - padl]
+  int64_t tap0, tstep, keff;    // row position p < keff of a filter row holds taps[tap0 + tstep*p]
+  int64_t need;                 // shortest cyclic length: nout + keff - 1
+  int N1, N2;
+  int64_t N;
+  int64_t npairs, slab_pairs, slabs;
+  int ob;
+  size_t spectrum_bytes, workspace_bytes;
+};
+
+bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 0; }
+
+int long_geometry(const fc_long_desc* desc, LongGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_desc& d = *desc;
+  if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
+    return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
+  if (d.in_channels % d.groups || d.out_channels % d.groups)
+    return fail(FC_ERR_INVALID, "in_channels (%lld) and out_channels (%lld) must be divisible by groups (%lld)",
+                (long long)d.in_channels, (long long)d.out_channels, (long long)d.groups);
+  if (d.length < 1 || d.kernel < 1) return fail(FC_ERR_INVALID, "length and kernel must be positive");
+  if (d.pad_left < 0 || d.pad_right < 0 || d.out_keep < 0) return fail(FC_ERR_INVALID, "padding and out_keep must not be negative");
+  if (d.flip != 0 && d.flip != 1) return fail(FC_ERR_INVALID, "flip must be 0 or 1");
+  const int64_t lim = (int64_t)1 << 30;
+  if (d.length > lim || d.kernel > lim || d.pad_left > lim || d.pad_right > lim)
+    return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of more than 2^30 samples are not addressed by the long-filter kernels");
+  const int64_t Lp = d.length + d.pad_left + d.pad_right;
+  if (d.kernel > Lp)
+    return fail(FC_ERR_INVALID, "kernel (%lld taps) is longer than the padded row (%lld samples)", (long long)d.kernel, (long long)Lp);
+  const int64_t full = Lp - d.kernel + 1;
+  if (d.out_keep > full)
+    return fail(FC_ERR_INVALID, "out_keep (%lld) exceeds the output length %lld", (long long)d.out_keep, (long long)full);
+  LongGeom g{};
+  g.B = d.batch; g.Cin = d.in_channels; g.Cout = d.out_channels; g.G = d.groups;
+  g.Cig = g.Cin / g.G; g.Cog = g.Cout / g.G; g.L = d.length; g.K = d.kernel;
+  g.nout = d.out_keep ? d.out_keep : full;
+  // tap k (of u) meets the data for some kept output iff  pad_left - nout + 1 <= k <= pad_left + L - 1
+  const int64_t klo = std::max<int64_t>(0, d.pad_left - g.nout + 1);
+  const int64_t khi = std::min<int64_t>(d.kernel - 1, d.pad_left + d.length - 1);
+  if (khi < klo) {               // every kept output sees padding only: one tap against a row that reads as zero, y = bias
+    g.keff = 1; g.tap0 = 0; g.tstep = 1;
+    g.padl = kMaxN + 1;          // the data lies past every position of the transform
+  } else {
+    g.keff = khi - klo + 1;
+    g.padl = d.pad_left - klo;
+    g.tap0 = d.flip ? d.kernel - 1 - klo : klo;
+    g.tstep = d.flip ? -1 : 1;
+  }
+  g.need = g.nout + g.keff - 1;
+  if (g.need > kMaxN)
+    return fail(FC_ERR_UNSUPPORTED, "the row needs a transform of %lld points; the long-filter path stops at 2^24 = %lld "
+                "(4096 x 4096)", (long long)g.need, (long long)kMaxN);
+  // smallest N = N1 * N2 >= need with both factors tile lengths; the most balanced split, N2 >= N1
+  int lg = 12;
+  while (((int64_t)1 << lg) < g.need) ++lg;
+  int l1 = lg / 2, l2 = lg - l1;
+  g.N1 = 1 << l1; g.N2 = 1 << l2;
+  if (const char* env = getenv("FFTCONV_LONG_N")) {
+    if (*env) {
+      long long n1 = 0, n2 = 0;
+      if (sscanf(env, "%lldx%lld", &n1, &n2) != 2 || !is_tile_len(n1) || !is_tile_len(n2))
+        return fail(FC_ERR_INVALID, "FFTCONV_LONG_N=%s: expected <N1>x<N2>, both powers of two from 64 to 4096", env);
+      if (n1 * n2 < g.need)
+        return fail(FC_ERR_INVALID, "FFTCONV_LONG_N=%s holds %lld points but the row needs %lld", env, n1 * n2, (long long)g.need);
+      g.N1 = (int)n1; g.N2 = (int)n2;
+    }
+  }
+  g.N = (int64_t)g.N1 * g.N2;
+  const LongImpl* rows = find_long(g.N2);
+  g.ob = rows ? rows->ob : 1;
+  g.npairs = (g.B + 1) / 2;
+  int64_t budget_mb = kDefaultBudgetMB;
+  if (const char* env = getenv("FFTCONV_LONG_WS_MB"))
+    if (*env && atoll(env) > 0) budget_mb = atoll(env);
+  const int64_t pair_bytes = (g.Cin + g.Cout) * g.N * 8;
+  g.slab_pairs = std::max<int64_t>(1, std::min<int64_t>(g.npairs, (budget_mb << 20) / pair_bytes));
+  g.slabs = (g.npairs + g.slab_pairs - 1) / g.slab_pairs;
+  g.workspace_bytes = (size_t)(g.slab_pairs * pair_bytes);
+  g.spectrum_bytes = (size_t)(g.Cout * g.Cig * g.N * 8);
+  // grids are 32-bit: (blocks per row) x rows
+  const int64_t worst = std::max<int64_t>(g.N2 / 2, g.N1 / 2) * std::max<int64_t>(g.slab_pairs * std::max(g.Cin, g.Cout), 1);
+  if (worst > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch pairs x %lld channels x %lld points exceeds the 2^31 workgroups of one "
+                "launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, (long long)std::max(g.Cin, g.Cout), (long long)g.N);
+  *out = g;
+  return FC_OK;
+}
+
+void fill_info(const LongGeom& g, int64_t info[8]) {
+  info[0] = g.N1; info[1] = g.N2; info[2] = g.nout; info[3] = (int64_t)g.spectrum_bytes;
+  info[4] = (int64_t)g.workspace_bytes; info[5] = g.slabs; info[6] = g.ob; info[7] = g.slab_pairs;
+}
+
+// w_N^m = thi[m >> 12] * tlo[m & 4095], both tables rounded once from float64; shared per (device, N)
+struct LongTables {
+  f2* thi = nullptr;
+  f2* tlo = nullptr;
+};
+std::mutex g_lt_mutex;
+std::map<std::pair<int, int64_t>, LongTables> g_lt;
+
+int get_long_tables(int64_t N, LongTables* out) {
+  int dev = 0;
+  FC_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(g_lt_mutex);
+  const auto key = std::make_pair(dev, N);
+  auto it = g_lt.find(key);
+  if (it != g_lt.end()) { *out = it->second; return FC_OK; }
+  const int64_t nhi = N >> kLongLoBits, nlo = (int64_t)1 << kLongLoBits;
+  std::vector<f2> hi((size_t)nhi), lo((size_t)nlo);
+  const double tau = 6.283185307179586476925286766559;
+  for (int64_t a = 0; a < nhi; ++a) {
+    const double ang = -tau * (double)(a << kLongLoBits) / (double)N;
+    hi[(size_t)a] = f2{(float)std::cos(ang), (float)std::sin(ang)};
+  }
+  for (int64_t b = 0; b < nlo; ++b) {
+    const double ang = -tau * (double)b / (double)N;
+    lo[(size_t)b] = f2{(float)std::cos(ang), (float)std::sin(ang)};
+  }
+  LongTables t;
+  FC_HIP_SETUP(hipMalloc(&t.thi, hi.size() * sizeof(f2)));
+  FC_HIP_SETUP(hipMalloc(&t.tlo, lo.size() * sizeof(f2)));
+  FC_HIP_SETUP(hipMemcpy(t.thi, hi.data(), hi.size() * sizeof(f2), hipMemcpyHostToDevice));
+  FC_HIP_SETUP(hipMemcpy(t.tlo, lo.data(), lo.size() * sizeof(f2), hipMemcpyHostToDevice));
+  g_lt[key] = t;
+  *out = t;
+  return FC_OK;
+}
+
+}  // namespace
+
+struct fc_long_plan {
+  fc_long_desc d;
+  LongGeom g;
+  const fc::LongImpl* cols;    // N1-point geometry
+  const fc::LongImpl* rows;    // N2-point geometry
+  fc::Twiddles tw1, tw2;
+  LongTables lt;
+};
+
+namespace {
+
+LongArgs base_args(const fc_long_plan& p) {
+  const LongGeom& g = p.g;
+  LongArgs a{};
+  a.thi = p.lt.thi; a.tlo = p.lt.tlo;
+  a.twA1 = p.tw1.twA; a.twB1 = p.tw1.twB; a.twA2 = p.tw2.twA; a.twB2 = p.tw2.twB;
+  a.N1 = g.N1; a.N2 = g.N2;
+  a.lgN2 = 0;
+  while ((1 << a.lgN2) < g.N2) ++a.lgN2;
+  a.B = (int)g.B; a.G = (int)g.G; a.Cig = (int)g.Cig; a.Cog = (int)g.Cog;
+  a.ob = g.ob; a.nob = (int)((g.Cog + g.ob - 1) / g.ob);
+  a.C = 1;
+  a.L = (int)g.L; a.padl = (int)g.padl;
+  a.tap0 = (int)g.tap0; a.tstep = (int)g.tstep; a.keff = (int)g.keff; a.K = (int)g.K;
+  a.nout = (int)g.nout;
+  a.scale = (float)(1.0 / (double)g.N);
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_long_geometry(const fc_long_desc* desc, int64_t info[8]) {
+  if (!info) return fail(FC_ERR_INVALID, "null argument");
+  LongGeom g;
+  const int st = long_geometry(desc, &g);
+  if (st != FC_OK) return st;
+  fill_info(g, info);
+  return FC_OK;
+}
+
+int fc_long_plan_create(const fc_long_desc* desc, fc_long_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
+  p->d = *desc;
+  int st = long_geometry(desc, &p->g);
+  if (st != FC_OK) return st;
+  p->cols = find_long(p->g.N1);
+  p->rows = find_long(p->g.N2);
+  const fc::TileImpl* t1 = find_tile(p->g.N1);
+  const fc::TileImpl* t2 = find_tile(p->g.N2);
+  if (!p->cols || !p->rows || !t1 || !t2)
+    return fail(FC_ERR_UNSUPPORTED, "no kernels built for %d x %d points", p->g.N1, p->g.N2);
+  if ((st = get_twiddles(t1, &p->tw1)) != FC_OK) return st;
+  if ((st = get_twiddles(t2, &p->tw2)) != FC_OK) return st;
+  if ((st = get_long_tables(p->g.N, &p->lt)) != FC_OK) return st;
+  *out_plan = p.release();
+  return FC_OK;
+}
+
+void fc_long_plan_destroy(fc_long_plan* plan) { delete plan; }
+
+int fc_long_plan_info(const fc_long_plan* plan, int64_t info[8]) {
+  if (!plan || !info) return fail(FC_ERR_INVALID, "null argument");
+  fill_info(plan->g, info);
+  return FC_OK;
+}
+
+int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void* spectrum, void* workspace,
+                             void* hip_stream) {
+  if (!plan || !weight || !spectrum || !workspace) return fail(FC_ERR_INVALID, "null argument");
+  const LongGeom& g = plan->g;
+  hipStream_t st = (hipStream_t)hip_stream;
+  // the filter rows go through the workspace a chunk at a time (it holds at least Cin + Cout >= 2 rows of N points)
+  const int64_t rows_total = g.Cout * g.Cig;
+  const int64_t fit = std::max<int64_t>(1, (int64_t)(g.workspace_bytes / (size_t)(g.N * 8)));
+  const int64_t grid_cap = 0x7fffffffLL / std::max<int64_t>(g.N1, g.N2);
+  const int64_t chunk = std::min(fit, grid_cap);
+  for (int64_t r0 = 0; r0 < rows_total; r0 += chunk) {
+    const int64_t n = std::min(chunk, rows_total - r0);
+    LongArgs a = base_args(*plan);
+    a.from_kernel = 1;
+    a.src = weight + (size_t)r0 * g.K;
+    a.w1 = (f2*)workspace;
+    FC_HIP(plan->cols->cols_fwd(a, n, st));
+    a.spec_mode = 1;
+    a.spec_out = (f2*)spectrum + (size_t)r0 * g.N;
+    FC_HIP(plan->rows->rows(a, n, st));
+  }
+  return FC_OK;
+}
+
+int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectrum, const float* bias, float* y,
+                    void* workspace, void* hip_stream) {
+  if (!plan || !x || !spectrum || !y || !workspace) return fail(FC_ERR_INVALID, "null argument");
+  if (plan->d.has_bias && !bias) return fail(FC_ERR_INVALID, "the plan was made with a bias");
+  const LongGeom& g = plan->g;
+  hipStream_t st = (hipStream_t)hip_stream;
+  for (int64_t s = 0; s < g.slabs; ++s) {
+    const int64_t pair0 = s * g.slab_pairs;
+    const int64_t np = std::min(g.slab_pairs, g.npairs - pair0);
+    LongArgs a = base_args(*plan);
+    a.pair0 = (int)pair0;
+    a.src = x; a.bias = bias; a.y = y;
+    a.spec = (const f2*)spectrum;
+    a.w1 = (f2*)workspace;
+    a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
+    a.C = (int)g.Cin;
+    FC_HIP(plan->cols->cols_fwd(a, np * g.Cin, st));
+    FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
+    a.C = (int)g.Cout;
+    FC_HIP(plan->cols->cols_inv(a, np * g.Cout, st));
+  }
+  return FC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,308 @@
+// long1d.hpp -- 1-D convolution with a filter as long as the row: one N-point cyclic transform per row, N = N1 * N2,
+// run as two workgroup transforms with a trip through HBM between them (host_long.cpp plans it).
+//
+// The zero-padded row is indexed n = n1*N2 + n2 and its bins k = k1 + N1*k2:
+//
+//   X[k1 + N1*k2] = sum_n2 w_N2^(n2*k2) * ( w_N^(n2*k1) * sum_n1 w_N1^(n1*k1) * x[n1*N2 + n2] )
+//
+//   long_cols_fwd   N1-point transforms along n1 (stride N2 in memory) of a block of neighbouring n2 columns, the twiddle
+//                   w_N^(n2*k1), W1[row][k1][n2].  Two real rows (batch items 2p and 2p+1 of one channel) ride one complex
+//                   row, z = x[2p] + i*x[2p+1]; the same kernel reads the filter taps (imaginary part zero).
+//   long_rows       one k1 row of N2 contiguous points: forward transform, product with the filter spectrum summed over the
+//                   input channels of the group, inverse transform, conjugate twiddle, W2[row][k1][n2].  In its other mode it
+//                   finishes the filter spectrum instead: H[o][i][k1][k2] = conj(transform) / N.
+//   long_cols_inv   inverse N1-point transforms along k1, bias, real part -> y[2p], imaginary part -> y[2p+1], the
+//                   kept window only.
+//
+// The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
+// hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
+#pragma once
+#include "nd_passes.hpp"
+
+namespace fc {
+
+constexpr int kLongLoBits = 12;      // w_N^m = thi[m >> 12] * tlo[m & 4095]
+
+struct LongArgs {
+  const float* src;      // signal (B, C, L) or filter taps (rows of K floats)
+  const float* bias;
+  float* y;              // (B, Cout, nout)
+  f2* w1;                // [row][k1][n2]   rows: (pair, input channel) or filter rows of this launch
+  f2* w2;                // [row][k1][n2]   rows: (pair, output channel)
+  const f2* spec;        // [(g*Cog + o)*Cig + i][k1][k2]
+  f2* spec_out;          // rows mode 1: first filter row of this launch
+  const f2* thi;         // [N >> 12]  w_N^(a * 4096)
+  const f2* tlo;         // [4096]     w_N^b
+  const f2* twA1; const f2* twB1;    // engine tables of the N1-point tile
+  const f2* twA2; const f2* twB2;    // ... of the N2-point tile
+  int N1, N2, lgN2;
+  int from_kernel;       // cols_fwd: 0 signal rows, 1 filter rows
+  int spec_mode;         // rows: 1 = finish the filter spectrum
+  int B, pair0;          // batch size, first pair of this slab
+  int C;                 // channels of the source tensor (signal) / of y
+  int G, Cig, Cog, ob, nob;
+  int L, padl;           // signal: row position p holds x[p - padl]
+  int tap0, tstep, keff; // filter: row position p < keff holds taps[tap0 + tstep*p]
+  int K;                 // filter row length in memory
+  int nout;              // kept output samples
+  float scale;           // 1 / N (rows mode 1)
+  FastDiv d_nblk, d_c, d_nob, d_g;   // unit maps (filled by the dispatcher)
+};
+
+__device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m) {
+  const f2 hi = buf_load_f32x2(thi, (m >> kLongLoBits) * 8u, 0);
+  const f2 lo = buf_load_f32x2(tlo, (m & ((1u << kLongLoBits) - 1u)) * 8u, 0);
+  return cmul(hi, lo);
+}
+
+// ------------------------------------------------------------------------------------------ long_cols_fwd
+template <int P, int S, int NSEQ, int NT>
+__global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;                       // == a.N1
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+
+  // the two real rows of the pair (filter rows: one, the imaginary part stays zero)
+  const float* r0;
+  bool has1 = false;
+  unsigned len;
+  if (a.from_kernel) {
+    r0 = a.src + (size_t)row * a.K;
+    len = (unsigned)a.K;
+  } else {
+    unsigned pr;
+    const unsigned c = fdivmod(row, a.d_c, &pr);
+    const int b0 = 2 * (a.pair0 + (int)pr);
+    r0 = a.src + ((size_t)b0 * a.C + c) * a.L;
+    has1 = b0 + 1 < a.B;
+    len = (unsigned)a.L;
+  }
+  const BufRsrc s0 = make_rsrc(r0, len * 4u);
+  const BufRsrc s1 = make_rsrc(has1 ? r0 + (size_t)a.C * a.L : r0, len * 4u);
+  {
+    // lanes run over the NSEQ neighbouring columns first; every sample of the thread is requested before the first is
+    // stored; positions outside the data get an offset outside the resource and read as zero
+    f2 val[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      const int p = (n1 << a.lgN2) + n20 + r;
+      const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
+      const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
+      const unsigned off = ok ? (unsigned)s * 4u : 0x80000000u;
+      val[u].x = buf_load_f32(s0, off, 0);
+      val[u].y = buf_load_f32(s1, has1 ? off : 0x80000000u, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(n1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  nat_load<G>(v, lseq, tseq);
+  seq_sync<G>();
+  fwd_from_regs<G>(v, lseq, tseq, true, twA, twB);
+  __syncthreads();
+  // twiddle w_N^(n2*k1) and store: NSEQ neighbouring n2 per k1
+  const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
+  const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
+  const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8));
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+    const unsigned n2 = (unsigned)(n20 + r);
+    const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
+    const f2 z = lds[r * LSEQP + G::nat(k1)];
+    buf_store_f32x2(cmul(z, w), orr, (((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------ long_rows
+// NSEQ neighbouring k1 rows per workgroup, one sequence each; OB output channels of one group per workgroup, their
+// running sums in registers in the order the inverse transform starts from (bins N2e*i1 + tseq of the thread).
+template <int P, int S, int NSEQ, int NT, int OB>
+__global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;                       // == a.N2
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS, "one thread slot per point group");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA2, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB2, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  f2* lseq = lds + sq * LSEQP;
+  unsigned q;
+  const int k1 = (int)fdivmod(blockIdx.x, a.d_nblk, &q) * NSEQ + sq;
+  const size_t N = (size_t)a.N1 * T;
+  const unsigned rowoff = (unsigned)k1 * (unsigned)(T * 8);      // byte offset of this k1 row inside a row of N points
+  const unsigned toff = rowoff + (unsigned)tseq * 8u;
+
+  if (a.spec_mode) {
+    // filter row q of this launch: transform, conjugate, 1/N
+    const BufRsrc sr = make_rsrc(a.w1 + (size_t)q * N, (unsigned)(N * 8));
+    f2 v[P];
+#pragma unroll
+    for (int n1 = 0; n1 < P; ++n1) v[n1] = buf_load_f32x2(sr, toff, G::N2 * n1 * 8);
+    fwd_from_regs<G>(v, lseq, tseq, true, twA, twB);
+    seq_sync<G>();
+    nat_load<G>(v, lseq, tseq);
+    const BufRsrc orr = make_rsrc(a.spec_out + (size_t)q * N, (unsigned)(N * 8));
+#pragma unroll
+    for (int i1 = 0; i1 < P; ++i1) buf_store_f32x2(mk2(v[i1].x * a.scale, -v[i1].y * a.scale), orr, toff, G::N2 * i1 * 8);
+    return;
+  }
+
+  const int ob0 = (int)fdivmod(q, a.d_nob, &q) * OB;
+  const int g = (int)fdivmod(q, a.d_g, &q);
+  const int pr = (int)q;
+  const int Cin = a.G * a.Cig, Cout = a.G * a.Cog;
+  f2 acc[OB][P];
+#pragma unroll
+  for (int o = 0; o < OB; ++o)
+#pragma unroll
+    for (int i1 = 0; i1 < P; ++i1) acc[o][i1] = mk2(0.f, 0.f);
+
+#pragma unroll 1
+  for (int i = 0; i < a.Cig; ++i) {
+    const BufRsrc sr = make_rsrc(a.w1 + ((size_t)pr * Cin + (size_t)g * a.Cig + i) * N, (unsigned)(N * 8));
+    f2 v[P], h[P];
+#pragma unroll
+    for (int n1 = 0; n1 < P; ++n1) v[n1] = buf_load_f32x2(sr, toff, G::N2 * n1 * 8);
+    {
+      // spectrum of the first output channel: requested before the transform, used after it
+      const BufRsrc hr = make_rsrc(a.spec + (((size_t)g * a.Cog + ob0) * a.Cig + i) * N, (unsigned)(N * 8));
+#pragma unroll
+      for (int i1 = 0; i1 < P; ++i1) h[i1] = buf_load_f32x2(hr, toff, G::N2 * i1 * 8);
+    }
+    fwd_from_regs<G>(v, lseq, tseq, true, twA, twB);
+    seq_sync<G>();
+    nat_load<G>(v, lseq, tseq);
+    seq_sync<G>();                       // the next transform writes this sequence's slots
+    static_for<0, OB>([&](auto oc) {
+      constexpr int o = decltype(oc)::value;
+      if (ob0 + o < a.Cog) {             // (workgroup-uniform)
+        if constexpr (o > 0) {
+          const BufRsrc hr = make_rsrc(a.spec + (((size_t)g * a.Cog + ob0 + o) * a.Cig + i) * N, (unsigned)(N * 8));
+#pragma unroll
+          for (int i1 = 0; i1 < P; ++i1) h[i1] = buf_load_f32x2(hr, toff, G::N2 * i1 * 8);
+        }
+#pragma unroll
+        for (int i1 = 0; i1 < P; ++i1) cmac(acc[o][i1], v[i1], h[i1]);
+      }
+    });
+  }
+
+  const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
+  const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
+  static_for<0, OB>([&](auto oc) {
+    constexpr int o = decltype(oc)::value;
+    if (ob0 + o < a.Cog) {               // (workgroup-uniform, so the barriers inside are met by all)
+      passA_fft_twiddle_store<G, +1>(acc[o], lseq, tseq, twA);
+      seq_sync<G>();
+      f2 v[P];
+      passB_load<G>(v, lseq, tseq);
+      const int j = passB_compute<G, +1>(v, tseq, twB);
+      seq_sync<G>();
+      const int nbase = (tseq >> G::LGS) + P * P * j;
+      const BufRsrc orr = make_rsrc(a.w2 + ((size_t)pr * Cout + (size_t)g * a.Cog + ob0 + o) * N, (unsigned)(N * 8));
+#pragma unroll
+      for (int k = 0; k < P; ++k) {
+        const unsigned n2 = (unsigned)(nbase + P * k);
+        const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
+        buf_store_f32x2(cmulc(v[k], w), orr, rowoff + n2 * 8u, 0);
+      }
+    }
+  });
+}
+
+// ------------------------------------------------------------------------------------------ long_cols_inv
+template <int P, int S, int NSEQ, int NT>
+__global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;                       // == a.N1
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+  unsigned pr;
+  const unsigned o = fdivmod(row, a.d_c, &pr);
+  const int b0 = 2 * (a.pair0 + (int)pr);
+  const bool has1 = b0 + 1 < a.B;
+  f2 wtw[P];
+  passA_twiddle_fetch<G>(wtw, tseq, twA);
+  {
+    const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, (unsigned)(N * 8));
+    f2 val[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      val[u] = buf_load_f32x2(sr, (((unsigned)k1 << a.lgN2) + (unsigned)(n20 + r)) * 8u, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(k1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  const int j = inv_to_regs_pre<G>(v, wtw, lseq, tseq, true, twB);
+  seq_sync<G>();
+  {
+    // back through LDS so that the stores run along n2 (the samples of one thread are N2 apart in y)
+    const int nbase = (tseq >> G::LGS) + P * P * j;
+#pragma unroll
+    for (int k = 0; k < P; ++k) lseq[G::nat(nbase + P * k)] = v[k];
+  }
+  __syncthreads();
+  float b = a.bias ? a.bias[o] : 0.f;
+  asm volatile("" : "+v"(b));
+  float* y0 = a.y + ((size_t)b0 * a.C + o) * a.nout;
+  const BufRsrc o0 = make_rsrc(y0, (unsigned)a.nout * 4u);
+  const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, (unsigned)a.nout * 4u);
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+    const f2 z = lds[r * LSEQP + G::nat(n1)];
+    const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
+    const unsigned off = t < (unsigned)a.nout ? t * 4u : 0x80000000u;     // (samples past the kept window: dropped)
+    buf_store_f32(z.x + b, o0, off, 0);
+    buf_store_f32(z.y + b, o1, has1 ? off : 0x80000000u, 0);
+  }
+}
+
+// what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan
+struct LongImpl {
+  int T, nseq, ob;
+  hipError_t (*cols_fwd)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*rows)(const LongArgs& a, long long units, hipStream_t st);     // units: filter rows, or pairs * G * nob
+  hipError_t (*cols_inv)(const LongArgs& a, long long rows, hipStream_t st);
+};
+
+#define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();
+FC_DECLARE_LONG(8, 1)
+FC_DECLARE_LONG(8, 2)
+FC_DECLARE_LONG(16, 1)
+FC_DECLARE_LONG(16, 2)
+FC_DECLARE_LONG(32, 1)
+FC_DECLARE_LONG(32, 2)
+FC_DECLARE_LONG(32, 4)
+
+}  // namespace fc

@@ -18,7 +18,7 @@ from torch import Tensor
 from . import _native
 from .utils import to_ntuple
 
-__all__ = ["fft_conv", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
+__all__ = ["fft_conv", "fft_long_conv", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
 
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}      # enum fc_dtype
@@ -353,3 +353,127 @@ def complex_matmul(a: Tensor, b: Tensor, groups: int = 1) -> Tensor:
     a_g = a.unflatten(1, [groups, a.size(1) // groups])
     b_g = b.unflatten(0, [groups, b.size(0) // groups])
     return torch.einsum("bgi...,goi...->bgo...", a_g, b_g).flatten(1, 2)
+
+
+# ---------------------------------------------------------------------------------------------- long filters
+LONG_HANDOFF_POINTS = 4096        # a padded row this short is one tile of the fft_conv path
+LONG_MAX_POINTS = 1 << 24         # longest transform of the long-filter path (4096 x 4096)
+
+
+def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int, pad_right: int, flip: bool,
+               out_keep: int, has_bias: bool):
+    """Cached long-filter plan (``fc_long_plan``) for a signal (B, Cin, L) against ``taps`` taps per filter row."""
+    key = ("long", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
+           int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)))
+    index = _device_index(signal.device)
+    plan = _native.lookup_plan(index, key)
+    if plan is None:
+        with torch.cuda.device(index):      # the twiddle tables are allocated on the current device
+            plan = _native.get_plan(index, key)
+    return plan
+
+
+def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: int, pad_right: int, flip: bool,
+              out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None) -> Tensor:
+    """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
+    y[b, o, t] = bias[o] + sum_i sum_k u[o, i, k] * xpad[b, (g, i), t + k] for t < out_keep (0: all), u = the taps in
+    tensor order or flipped."""
+    signal = signal.detach().contiguous()
+    plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
+                      bias is not None)
+    if spectrum is None or spectrum.plan is not plan:
+        spectrum = transform_kernel(plan, kernel)
+    bias_c = bias.detach().contiguous() if bias is not None else None
+    with torch.cuda.device(signal.device):
+        out = torch.empty((signal.shape[0], kernel.shape[0], plan.out_len), dtype=torch.float32, device=signal.device)
+        ws = new_workspace(plan, signal.device)
+        stream = torch.cuda.current_stream(signal.device).cuda_stream
+        plan.forward(signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
+                     out.data_ptr(), ws.data_ptr(), stream)
+    return out
+
+
+def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal):
+    """Argument checks of ``fft_long_conv`` (ValueError, before any device call) -> (pad_left, pad_right, points the row
+    needs)."""
+    if signal.ndim != 3 or kernel.ndim != 3:
+        raise ValueError(f"fft_long_conv expects a (batch, channels, length) signal and an (out, in/groups, taps) kernel, "
+                         f"got shapes {tuple(signal.shape)} and {tuple(kernel.shape)}")
+    if not isinstance(groups, int) or groups < 1:
+        raise ValueError(f"groups must be a positive int, got {groups!r}")
+    cin, cout, taps, length = int(signal.shape[1]), int(kernel.shape[0]), int(kernel.shape[2]), int(signal.shape[2])
+    if cin % groups or cout % groups or int(kernel.shape[1]) * groups != cin:
+        raise ValueError(f"channel mismatch: signal has {cin} channels, kernel is {tuple(kernel.shape)} with groups={groups} "
+                         f"(need kernel.shape[1] * groups == in_channels and out_channels % groups == 0)")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
+    if length < 1 or taps < 1 or signal.shape[0] < 1:
+        raise ValueError("batch, length and taps must be positive")
+    if causal:
+        if not (isinstance(padding, int) and padding == 0):
+            raise ValueError(f"causal=True pads the row itself (taps - 1 zeros in front): padding must be 0, got {padding!r}")
+        return taps - 1, 0, length + min(taps, length) - 1
+    if isinstance(padding, str):
+        if padding == "valid":
+            pad_left = pad_right = 0
+        elif padding == "same":
+            pad_left = (taps - 1) // 2
+            pad_right = taps - 1 - pad_left
+        else:
+            raise ValueError(f"invalid padding string {padding!r}; expected 'same' or 'valid'")
+    else:
+        if isinstance(padding, (tuple, list)) and len(padding) == 1:
+            padding = padding[0]
+        if not isinstance(padding, int) or padding < 0:
+            raise ValueError(f"padding must be a non-negative int, 'same' or 'valid', got {padding!r}")
+        pad_left = pad_right = int(padding)
+    if taps > length + pad_left + pad_right:
+        raise ValueError(f"kernel ({taps} taps) is longer than the padded row ({length + pad_left + pad_right} samples)")
+    return pad_left, pad_right, length + pad_left + pad_right
+
+
+def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
+                  causal: bool = False) -> Tensor:
+    """1-D convolution with a filter as long as the row: ONE transform over the whole padded row (as the reference does,
+    functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
+
+    ``signal`` (B, Cin, L), ``kernel`` (Cout, Cin/groups, K), ``bias`` (Cout,) or None; float32 on a ROCm device; stride 1,
+    dilation 1, zero padding.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, padding=padding, groups=groups)``
+    (cross-correlation; ``padding`` an int, 'same' or 'valid'), output length L + 2*padding - K + 1.  ``causal=True``
+    (``padding`` must be 0): y[b, o, t] = bias[o] + sum_i sum_{s <= min(t, K-1)} kernel[o, i, s] * signal[b, (g, i), t - s],
+    output length L; K may exceed L.  Differentiable in signal, kernel and bias.
+
+    Rows whose padded length is at most 4096 run the ``fft_conv`` kernels; a row that needs more than 2**24 points raises
+    ``NotImplementedError``.  float16 / bfloat16 / float64 tensors are not taken by this path (``TypeError``)."""
+    return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None)
+
+
+def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum):
+    pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal)
+    if need > LONG_MAX_POINTS:
+        raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
+                                  f"2**24 = {LONG_MAX_POINTS}")
+    for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
+        if t is not None:
+            _require_long_f32(name, t)
+    _same_device(signal=signal, kernel=kernel, bias=bias)
+    if need <= LONG_HANDOFF_POINTS:
+        if not causal:
+            return _fft_conv_impl(signal, kernel, bias, 1, padding, 1, groups, "constant", None)
+        taps = min(int(kernel.shape[2]), int(signal.shape[2]))     # taps past L - 1 never reach the output
+        padded = torch.nn.functional.pad(signal, (taps - 1, 0))
+        return _fft_conv_impl(padded, kernel[..., :taps].flip(-1), bias, 1, 0, 1, groups, "constant", None)
+    if _needs_grad(signal, kernel, bias):
+        from .autograd import FFTLongConvFunction
+        return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum)
+    return _long_run(signal, kernel, bias, pad_left, pad_right, causal, signal.shape[2] if causal else 0, groups, spectrum)
+
+
+def _require_long_f32(name: str, t: Tensor):
+    if not t.is_cuda:
+        raise RuntimeError(
+            f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
+            f"(no CPU fallback). Move the tensor to 'cuda'.")
+    if t.dtype != torch.float32:
+        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; fft_long_conv takes float32 signal, kernel and "
+                        f"bias (float16 / bfloat16 / float64 run through fft_conv only)")

@@ -178,3 +178,33 @@ class FFTConvTranspose2d(_FFTConvTransposeForward, nn.ConvTranspose2d):
 
 class FFTConvTranspose3d(_FFTConvTransposeForward, nn.ConvTranspose3d):
     ...
+
+
+class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
+    """``nn.Conv1d`` (stride 1, dilation 1, zero padding; state_dict = weight, bias) whose forward is
+    ``fft_long_conv``: one transform over the whole padded row, for filters as long as the row.  ``causal=True``
+    computes y[t] = sum_s weight[s] * x[t - s] (output length L, ``padding`` must be 0).  The kernel spectrum is cached
+    under the rules of ``_SpectrumCache``."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
+                 dtype=None):
+        if causal and not (isinstance(padding, int) and padding == 0):
+            raise ValueError("causal=True pads the row itself: padding must be 0")
+        super().__init__(in_channels, out_channels, kernel_size, stride=1, padding=padding, dilation=1, groups=groups,
+                         bias=bias, padding_mode="zeros", device=device, dtype=dtype)
+        self.causal = bool(causal)
+
+    def extra_repr(self):
+        return super().extra_repr() + (", causal=True" if self.causal else "")
+
+    def forward(self, signal: Tensor):
+        padding = self.padding if isinstance(self.padding, str) else int(self.padding[0])
+        weight, bias = self.weight, self.bias
+        pad_left, pad_right, need = F_._long_geometry(signal, weight, bias, padding, self.groups, self.causal)
+        spectrum = None
+        if (F_.LONG_HANDOFF_POINTS < need <= F_.LONG_MAX_POINTS and signal.is_cuda and signal.dtype == torch.float32
+                and weight.is_cuda and weight.dtype == torch.float32 and signal.device == weight.device):
+            plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
+                                 signal.shape[2] if self.causal else 0, bias is not None)
+            spectrum = self._cached_spectrum(plan)
+        return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum)

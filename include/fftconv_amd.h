@@ -191,6 +191,49 @@ long long fc_debug_grid(const fc_plan* plan);
  * Unused words are 0.  NULL plan or array: FC_ERR_INVALID. */
 int fc_debug_route(const fc_plan* plan, int32_t route[16]);
 
+/* ---- Long filters (ABI 7 extension: new entry points only, nothing that existed changes): a 1-D filter as long as the row, functional.py:66-75 with one transform over the whole
+ * padded row instead of overlap-save tiles.  float32, stride 1, dilation 1, zero padding.  The plan computes
+ *   y[b][(g,o)][t] = bias[(g,o)] + sum_i sum_k u[(g,o)][i][k] * xpad[b][(g,i)][t + k],   0 <= t < out_keep,
+ * xpad = x with pad_left zeros in front and pad_right behind, u[k] = w[k] (flip 0, cross-correlation) or w[K-1-k]
+ * (flip 1).  The causal long convolution y[t] = sum_s h[s] x[t-s] is pad_left = K-1, pad_right = 0, flip = 1,
+ * out_keep = L; its gradients are the same call with other paddings.  Taps that meet only padding for every
+ * kept output are not read.  One cyclic transform of N = N1 * N2 >= out_keep + (taps that are read) - 1 points per row, N1
+ * and N2 tile lengths (64 .. 4096), as two on-chip transforms with a trip through the workspace between them. */
+typedef struct fc_long_desc {
+  int64_t batch, in_channels, out_channels, groups;
+  int64_t length;        /* L: samples per signal row */
+  int64_t kernel;        /* K: taps per filter row; weight is (Cout, Cin/groups, K) */
+  int64_t pad_left, pad_right;
+  int64_t out_keep;      /* leading output samples kept; 0 = all of them, L + pad_left + pad_right - K + 1 */
+  int32_t flip;          /* tap order, see above */
+  int32_t has_bias;
+} fc_long_desc;
+
+typedef struct fc_long_plan fc_long_plan;
+
+/* info words of a long plan: N1, N2, output length, kernel-spectrum bytes, workspace bytes, slabs (the batch pairs
+ * run in this many rounds of three launches so that the workspace stays inside the budget), output channels per
+ * workgroup of the row pass, batch pairs per slab. */
+enum { FC_LONG_INFO_WORDS = 8 };
+
+/* The info words from the descriptor alone: validates it, touches no device.  FFTCONV_LONG_N=<N1>x<N2> forces the
+ * factorisation (tests), FFTCONV_LONG_WS_MB the workspace budget.  A row that needs more than 2^24 points:
+ * FC_ERR_UNSUPPORTED, the text naming the length. */
+int fc_long_geometry(const fc_long_desc* desc, int64_t info[8]);
+
+/* Plan of the CURRENT device (allocates the twiddle tables: not capturable; everything after it is). */
+int fc_long_plan_create(const fc_long_desc* desc, fc_long_plan** out_plan);
+void fc_long_plan_destroy(fc_long_plan* plan);
+int fc_long_plan_info(const fc_long_plan* plan, int64_t info[8]);
+
+/* weight (Cout, Cin/groups, K) float32 -> spectrum (info[3] bytes); workspace: info[4] bytes. */
+int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void* spectrum, void* workspace,
+                              void* hip_stream);
+/* x (B, Cin, L) -> y (B, Cout, info[2]) float32, every sample written; bias may be NULL.  Three launches per slab on
+ * hip_stream, nothing allocated or synchronised. */
+int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectrum, const float* bias, float* y,
+                     void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ EXPORTS = (
     "fc_forward", "fc_forward_stamped", "fc_wgrad1d_slices", "fc_wgrad1d", "fc_wgrad1d_db", "fc_wgrad1d_db_supported",
     "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd", "fc_debug_route",
     "fc_long_geometry", "fc_long_plan_create", "fc_long_plan_destroy", "fc_long_plan_info", "fc_long_transform_kernel",
-    "fc_long_forward",
+    "fc_long_forward", "fc_long_transform_kernel_io", "fc_long_forward_io",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -141,6 +141,10 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_transform_kernel.restype = i32
         lib.fc_long_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.fc_long_forward.restype = i32
+        lib.fc_long_transform_kernel_io.argtypes = [vp, vp, i32, vp, vp, vp]
+        lib.fc_long_transform_kernel_io.restype = i32
+        lib.fc_long_forward_io.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
+        lib.fc_long_forward_io.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -343,7 +347,10 @@ def long_geometry(key: Tuple) -> dict:
 
 class LongPlan:
     """Owns one ``fc_long_plan`` (long-filter path; immutable after creation): created on the CURRENT HIP device, which the
-    caller sets to ``device_index``.  Quacks like ``Plan`` where ``KernelSpectrum`` and ``new_workspace`` look."""
+    caller sets to ``device_index``.  Quacks like ``Plan`` where ``KernelSpectrum`` and ``new_workspace`` look.
+
+    The plan does not depend on the element types of the tensors: ``transform_kernel`` and ``forward`` name them per call
+    as fc_dtype codes (0 float32, 2 float16, 3 bfloat16; default float32).  Spectrum, workspace and bias are float32."""
 
     def __init__(self, key: Tuple, device_index: int = 0):
         lib = load_library()
@@ -362,13 +369,16 @@ class LongPlan:
         import torch
         self.dtype = self.weight_dtype = torch.float32
 
-    def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int):
-        st = self._lib.fc_long_transform_kernel(self._h, weight_ptr, spectrum_ptr, workspace_ptr, stream)
+    def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int,
+                         weight_dtype: int = 0):
+        st = self._lib.fc_long_transform_kernel_io(self._h, weight_ptr, weight_dtype, spectrum_ptr, workspace_ptr, stream)
         if st != FC_OK:
             _raise(self._lib, st)
 
-    def forward(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int, stream: int):
-        st = self._lib.fc_long_forward(self._h, x_ptr, spectrum_ptr, bias_ptr, y_ptr, workspace_ptr, stream)
+    def forward(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int, stream: int,
+                x_dtype: int = 0, y_dtype: int = 0):
+        st = self._lib.fc_long_forward_io(self._h, x_ptr, x_dtype, spectrum_ptr, bias_ptr, y_ptr, y_dtype, workspace_ptr,
+                                          stream)
         if st != FC_OK:
             _raise(self._lib, st)
 

@@ -376,7 +376,11 @@ class FFTLongConvFunction(torch.autograd.Function):
              (Cout, B, Lout), the first K lags kept -- flipped afterwards when the forward read the taps flipped (causal);
         db = dY summed over batch and row.
 
-    torch builds the transposed copies of the operands."""
+    torch builds the transposed copies of the operands.
+
+    float16 / bfloat16 calls run on their 16-bit tensors (autograd saves 16-bit signal and weight): dX reads 16-bit dY
+    and the 16-bit transposed weight and is written in 16 bits; dW reads the 16-bit transposed copies of x and dY, comes
+    back float32 and is rounded once; db is summed in float32.  Each gradient has the bits of the float32 cast path."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum):
@@ -405,8 +409,8 @@ class FFTLongConvFunction(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
             dyt = grad.permute(1, 0, 2).contiguous()
-            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g).permute(1, 0, 2)
-            dw = (du.flip(-1) if flip else du).contiguous()
+            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32).permute(1, 0, 2)
+            dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = grad.sum(dim=(0, 2))
+            db = _grad_bias(grad).to(kernel.dtype)
         return dx, dw, db, None, None, None, None, None

@@ -192,6 +192,19 @@ LongArgs base_args(const fc_long_plan& p) {
   return a;
 }
 
+// fc_dtype of a tensor argument -> the element code of a launch (LongArgs src_io / y_io)
+int io_code(int dtype, const char* what, int* code) {
+  switch (dtype) {
+    case FC_F32: *code = 0; return FC_OK;
+    case FC_F16: *code = IO_CODE_F16; return FC_OK;
+    case FC_BF16: *code = IO_CODE_BF16; return FC_OK;
+    case FC_F64:
+      return fail(FC_ERR_UNSUPPORTED, "%s is float64: the long-filter path takes float32, float16 and bfloat16 tensors", what);
+    default:
+      return fail(FC_ERR_INVALID, "%s has dtype code %d; expected FC_F32 (0), FC_F16 (2) or FC_BF16 (3)", what, dtype);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,7 +249,16 @@ int fc_long_plan_info(const fc_long_plan* plan, int64_t info[8]) {
 
 int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void* spectrum, void* workspace,
                              void* hip_stream) {
+  return fc_long_transform_kernel_io(plan, weight, FC_F32, spectrum, workspace, hip_stream);
+}
+
+int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, int weight_dtype, void* spectrum,
+                                void* workspace, void* hip_stream) {
   if (!plan || !weight || !spectrum || !workspace) return fail(FC_ERR_INVALID, "null argument");
+  int wio = 0;
+  if (int e = io_code(weight_dtype, "weight", &wio)) return e;
+  const size_t wes = wio ? 2 : 4;
+  const auto cols_fwd = wio ? plan->cols->cols_fwd_h16 : plan->cols->cols_fwd;
   const LongGeom& g = plan->g;
   hipStream_t st = (hipStream_t)hip_stream;
   // the filter rows go through the workspace a chunk at a time (it holds at least Cin + Cout >= 2 rows of N points)
@@ -248,9 +270,10 @@ int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void
     const int64_t n = std::min(chunk, rows_total - r0);
     LongArgs a = base_args(*plan);
     a.from_kernel = 1;
-    a.src = weight + (size_t)r0 * g.K;
+    a.src_io = wio;
+    a.src = (const float*)((const char*)weight + (size_t)r0 * g.K * wes);
     a.w1 = (f2*)workspace;
-    FC_HIP(plan->cols->cols_fwd(a, n, st));
+    FC_HIP(cols_fwd(a, n, st));
     a.spec_mode = 1;
     a.spec_out = (f2*)spectrum + (size_t)r0 * g.N;
     FC_HIP(plan->rows->rows(a, n, st));
@@ -260,8 +283,18 @@ int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void
 
 int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectrum, const float* bias, float* y,
                     void* workspace, void* hip_stream) {
+  return fc_long_forward_io(plan, x, FC_F32, spectrum, bias, y, FC_F32, workspace, hip_stream);
+}
+
+int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, const void* spectrum, const float* bias,
+                       void* y, int y_dtype, void* workspace, void* hip_stream) {
   if (!plan || !x || !spectrum || !y || !workspace) return fail(FC_ERR_INVALID, "null argument");
   if (plan->d.has_bias && !bias) return fail(FC_ERR_INVALID, "the plan was made with a bias");
+  int xio = 0, yio = 0;
+  if (int e = io_code(x_dtype, "x", &xio)) return e;
+  if (int e = io_code(y_dtype, "y", &yio)) return e;
+  const auto cols_fwd = xio ? plan->cols->cols_fwd_h16 : plan->cols->cols_fwd;
+  const auto cols_inv = yio ? plan->cols->cols_inv_h16 : plan->cols->cols_inv;
   const LongGeom& g = plan->g;
   hipStream_t st = (hipStream_t)hip_stream;
   for (int64_t s = 0; s < g.slabs; ++s) {
@@ -269,15 +302,16 @@ int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectr
     const int64_t np = std::min(g.slab_pairs, g.npairs - pair0);
     LongArgs a = base_args(*plan);
     a.pair0 = (int)pair0;
-    a.src = x; a.bias = bias; a.y = y;
+    a.src = (const float*)x; a.bias = bias; a.y = (float*)y;
+    a.src_io = xio; a.y_io = yio;
     a.spec = (const f2*)spectrum;
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
     a.C = (int)g.Cin;
-    FC_HIP(plan->cols->cols_fwd(a, np * g.Cin, st));
+    FC_HIP(cols_fwd(a, np * g.Cin, st));
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;
-    FC_HIP(plan->cols->cols_inv(a, np * g.Cout, st));
+    FC_HIP(cols_inv(a, np * g.Cout, st));
   }
   return FC_OK;
 }

@@ -14,6 +14,12 @@
 //   long_cols_inv   inverse N1-point transforms along k1, bias, real part -> y[2p], imaginary part -> y[2p+1], the
 //                   kept window only.
 //
+// The two column kernels are the only ones that touch tensors, and they take them as float32, float16 or bfloat16
+// (Io<IO>, fft_engine.hpp): the source rows of long_cols_fwd -- signal and filter taps alike -- are widened exactly as they
+// are loaded, and long_cols_inv adds the bias in float32 and rounds each sample once, to nearest even, at its store.  The
+// two element types of a launch are independent (src_io, y_io); W1, W2 and the spectrum are float32 always, so the result
+// has the bits of: widen, run the float32 kernels, round.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -24,9 +30,9 @@ namespace fc {
 constexpr int kLongLoBits = 12;      // w_N^m = thi[m >> 12] * tlo[m & 4095]
 
 struct LongArgs {
-  const float* src;      // signal (B, C, L) or filter taps (rows of K floats)
-  const float* bias;
-  float* y;              // (B, Cout, nout)
+  const float* src;      // signal (B, C, L) or filter taps (rows of K samples); element type src_io
+  const float* bias;     // float32
+  float* y;              // (B, Cout, nout); element type y_io
   f2* w1;                // [row][k1][n2]   rows: (pair, input channel) or filter rows of this launch
   f2* w2;                // [row][k1][n2]   rows: (pair, output channel)
   const f2* spec;        // [(g*Cog + o)*Cig + i][k1][k2]
@@ -47,6 +53,7 @@ struct LongArgs {
   int nout;              // kept output samples
   float scale;           // 1 / N (rows mode 1)
   FastDiv d_nblk, d_c, d_nob, d_g;   // unit maps (filled by the dispatcher)
+  int src_io, y_io;      // element types of src and of y (fc_dtype: 0 float32, 2 float16, 3 bfloat16; wave-uniform, Io<IO>)
 };
 
 __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m) {
@@ -56,9 +63,11 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.src_io);
+  constexpr unsigned ES = Io<IO>::B;            // bytes per sample of the source rows
   constexpr int T = G::T;                       // == a.N1
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
@@ -71,35 +80,53 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const size_t N = (size_t)a.N1 << a.lgN2;
 
   // the two real rows of the pair (filter rows: one, the imaginary part stays zero)
-  const float* r0;
+  const typename Io<IO>::T* r0;
   bool has1 = false;
   unsigned len;
   if (a.from_kernel) {
-    r0 = a.src + (size_t)row * a.K;
+    r0 = io_ptr<IO>(a.src) + (size_t)row * a.K;
     len = (unsigned)a.K;
   } else {
     unsigned pr;
     const unsigned c = fdivmod(row, a.d_c, &pr);
     const int b0 = 2 * (a.pair0 + (int)pr);
-    r0 = a.src + ((size_t)b0 * a.C + c) * a.L;
+    r0 = io_ptr<IO>(a.src) + ((size_t)b0 * a.C + c) * a.L;
     has1 = b0 + 1 < a.B;
     len = (unsigned)a.L;
   }
-  const BufRsrc s0 = make_rsrc(r0, len * 4u);
-  const BufRsrc s1 = make_rsrc(has1 ? r0 + (size_t)a.C * a.L : r0, len * 4u);
+  const BufRsrc s0 = make_rsrc(r0, len * ES);
+  const BufRsrc s1 = make_rsrc(has1 ? r0 + (size_t)a.C * a.L : r0, len * ES);
   {
     // lanes run over the NSEQ neighbouring columns first; every sample of the thread is requested before the first is
     // stored; positions outside the data get an offset outside the resource and read as zero
     f2 val[P];
-#pragma unroll
-    for (int u = 0; u < P; ++u) {
+    const auto offset = [&](int u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
       const int p = (n1 << a.lgN2) + n20 + r;
       const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
       const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
-      const unsigned off = ok ? (unsigned)s * 4u : 0x80000000u;
-      val[u].x = buf_load_f32(s0, off, 0);
-      val[u].y = buf_load_f32(s1, has1 ? off : 0x80000000u, 0);
+      return ok ? (unsigned)s * ES : 0x80000000u;
+    };
+    if constexpr (IO == IO_F32) {
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const unsigned off = offset(u);
+        val[u].x = buf_load_f32(s0, off, 0);
+        val[u].y = buf_load_f32(s1, has1 ? off : 0x80000000u, 0);
+      }
+    } else {
+      // 16-bit rows: all 2 P loads are issued before the first sample is widened (a conversion right behind its load
+      // makes the compiler wait for that load before it issues the next, wgrad1d.hpp load_pairs_h16)
+      unsigned h0[P], h1[P];
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const unsigned off = offset(u);
+        h0[u] = __builtin_amdgcn_raw_buffer_load_b16(s0, off, 0, 0);
+        h1[u] = __builtin_amdgcn_raw_buffer_load_b16(s1, has1 ? off : 0x80000000u, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u] = mk2(io.in(h0[u]), io.in(h1[u]));
     }
 #pragma unroll
     for (int u = 0; u < P; ++u) {
@@ -227,9 +254,11 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
+  const Io<IO> io(a.y_io);
+  constexpr unsigned ES = Io<IO>::B;            // bytes per sample of y
   constexpr int T = G::T;                       // == a.N1
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
@@ -274,17 +303,18 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   __syncthreads();
   float b = a.bias ? a.bias[o] : 0.f;
   asm volatile("" : "+v"(b));
-  float* y0 = a.y + ((size_t)b0 * a.C + o) * a.nout;
-  const BufRsrc o0 = make_rsrc(y0, (unsigned)a.nout * 4u);
-  const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, (unsigned)a.nout * 4u);
+  // (the bias is added in float32; a 16-bit y is rounded once, at the store)
+  typename Io<IO>::T* y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout;
+  const BufRsrc o0 = make_rsrc(y0, (unsigned)a.nout * ES);
+  const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, (unsigned)a.nout * ES);
 #pragma unroll
   for (int u = 0; u < P; ++u) {
     const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
     const f2 z = lds[r * LSEQP + G::nat(n1)];
     const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
-    const unsigned off = t < (unsigned)a.nout ? t * 4u : 0x80000000u;     // (samples past the kept window: dropped)
-    buf_store_f32(z.x + b, o0, off, 0);
-    buf_store_f32(z.y + b, o1, has1 ? off : 0x80000000u, 0);
+    const unsigned off = t < (unsigned)a.nout ? t * ES : 0x80000000u;     // (samples past the kept window: dropped)
+    io.store(z.x + b, o0, off, 0);
+    io.store(z.y + b, o1, has1 ? off : 0x80000000u, 0);
   }
 }
 
@@ -294,6 +324,9 @@ struct LongImpl {
   hipError_t (*cols_fwd)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*rows)(const LongArgs& a, long long units, hipStream_t st);     // units: filter rows, or pairs * G * nob
   hipError_t (*cols_inv)(const LongArgs& a, long long rows, hipStream_t st);
+  // the 16-bit builds of the column passes: float16 and bfloat16 sources (a.src_io) / outputs (a.y_io)
+  hipError_t (*cols_fwd_h16)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_h16)(const LongArgs& a, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

@@ -1,4 +1,5 @@
-// long_inst.hip -- instantiates the three kernels of long1d.hpp for ONE tile geometry (P, S): built once per geometry
+// long_inst.hip -- instantiates the three kernels of long1d.hpp (and the 16-bit builds of the two column kernels, one
+// build for float16 and bfloat16) for ONE tile geometry (P, S): built once per geometry
 // with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "long1d.hpp"
 
@@ -53,10 +54,17 @@ hipError_t launch(K k, LdsOptIn* done, const LongArgs& a, int blocks_per_unit, l
   return hipGetLastError();
 }
 
+bool is_h16(int code) { return code == IO_CODE_F16 || code == IO_CODE_BF16; }
+
 hipError_t cols_fwd(const LongArgs& a, long long rows, hipStream_t st) {
   static LdsOptIn done;
-  if (a.N1 != kT) return hipErrorInvalidValue;
+  if (a.N1 != kT || a.src_io != 0) return hipErrorInvalidValue;
   return launch(long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT>, &done, a, a.N2 / kNSEQ, rows, st);
+}
+hipError_t cols_fwd_h16(const LongArgs& a, long long rows, hipStream_t st) {
+  static LdsOptIn done;
+  if (a.N1 != kT || !is_h16(a.src_io)) return hipErrorInvalidValue;
+  return launch(long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>, &done, a, a.N2 / kNSEQ, rows, st);
 }
 hipError_t rows(const LongArgs& a, long long units, hipStream_t st) {
   static LdsOptIn done;
@@ -65,8 +73,13 @@ hipError_t rows(const LongArgs& a, long long units, hipStream_t st) {
 }
 hipError_t cols_inv(const LongArgs& a, long long rows, hipStream_t st) {
   static LdsOptIn done;
-  if (a.N1 != kT) return hipErrorInvalidValue;
+  if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
   return launch(long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT>, &done, a, a.N2 / kNSEQ, rows, st);
+}
+hipError_t cols_inv_h16(const LongArgs& a, long long rows, hipStream_t st) {
+  static LdsOptIn done;
+  if (a.N1 != kT || !is_h16(a.y_io)) return hipErrorInvalidValue;
+  return launch(long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>, &done, a, a.N2 / kNSEQ, rows, st);
 }
 
 }  // namespace
@@ -74,7 +87,7 @@ hipError_t cols_inv(const LongArgs& a, long long rows, hipStream_t st) {
 #define FC_CAT_(a, b, c, d) a##b##c##d
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
-  static const LongImpl impl = {kT, kNSEQ, kOB, cols_fwd, rows, cols_inv};
+  static const LongImpl impl = {kT, kNSEQ, kOB, cols_fwd, rows, cols_inv, cols_fwd_h16, cols_inv_h16};
   return &impl;
 }
 

@@ -142,16 +142,24 @@ def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, g
 
 def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
     """Kernel transform (dilate, zero-pad, FFT, conjugate) on the device; rows a2 + a6.  A float16 / bfloat16 plan takes
-    a weight of its own dtype (widened to a float32 copy that lives for this call only) or a float32 one."""
-    _require_gpu_f32("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype)
-    kernel = kernel.detach().to(plan.weight_dtype).contiguous()
+    a weight of its own dtype (widened to a float32 copy that lives for this call only) or a float32 one.  A long-filter
+    plan reads a float16 / bfloat16 weight where it lies (no copy); its spectrum is float32, the bytes of the widened
+    weight's."""
+    io = ()
+    if isinstance(plan, _native.LongPlan) and kernel.dtype in _LOW_PRECISION:
+        _require_gpu_f32("kernel", kernel, kernel.dtype)
+        kernel = kernel.detach().contiguous()
+        io = (_DTYPE_CODES[kernel.dtype],)
+    else:
+        _require_gpu_f32("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype)
+        kernel = kernel.detach().to(plan.weight_dtype).contiguous()
     if _device_index(kernel.device) != plan.device_index:
         raise ValueError(f"kernel is on {kernel.device} but the plan was made for cuda:{plan.device_index}")
     with torch.cuda.device(kernel.device):
         buf = torch.empty(max(plan.spectrum_bytes, 16) // 4, dtype=torch.float32, device=kernel.device)
         ws = new_workspace(plan, kernel.device)      # scratch of this call only
         stream = torch.cuda.current_stream(kernel.device).cuda_stream
-        plan.transform_kernel(kernel.data_ptr(), buf.data_ptr(), ws.data_ptr() if ws is not None else None, stream)
+        plan.transform_kernel(kernel.data_ptr(), buf.data_ptr(), ws.data_ptr() if ws is not None else None, stream, *io)
     return KernelSpectrum(plan, buf)
 
 
@@ -374,22 +382,29 @@ def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int,
 
 
 def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: int, pad_right: int, flip: bool,
-              out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None) -> Tensor:
+              out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
+              out_dtype: Optional[torch.dtype] = None) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, t] = bias[o] + sum_i sum_k u[o, i, k] * xpad[b, (g, i), t + k] for t < out_keep (0: all), u = the taps in
-    tensor order or flipped."""
+    tensor order or flipped.
+
+    ``signal`` and ``kernel`` are float32, float16 or bfloat16, each on its own: the kernels read them where they lie and
+    widen as they load.  The result has ``out_dtype`` (default: the signal's; the weight gradient asks for float32 from
+    16-bit operands) and is rounded once, at the store.  The plan, its cache key, the spectrum and the workspace are the
+    float32 ones whatever the dtypes; the bias (Cout values) is widened to float32."""
     signal = signal.detach().contiguous()
+    out_dtype = signal.dtype if out_dtype is None else out_dtype
     plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
                       bias is not None)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)
-    bias_c = bias.detach().contiguous() if bias is not None else None
+    bias_c = bias.detach().float().contiguous() if bias is not None else None
     with torch.cuda.device(signal.device):
-        out = torch.empty((signal.shape[0], kernel.shape[0], plan.out_len), dtype=torch.float32, device=signal.device)
+        out = torch.empty((signal.shape[0], kernel.shape[0], plan.out_len), dtype=out_dtype, device=signal.device)
         ws = new_workspace(plan, signal.device)
         stream = torch.cuda.current_stream(signal.device).cuda_stream
         plan.forward(signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                     out.data_ptr(), ws.data_ptr(), stream)
+                     out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out_dtype])
     return out
 
 
@@ -437,14 +452,20 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     """1-D convolution with a filter as long as the row: ONE transform over the whole padded row (as the reference does,
     functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
 
-    ``signal`` (B, Cin, L), ``kernel`` (Cout, Cin/groups, K), ``bias`` (Cout,) or None; float32 on a ROCm device; stride 1,
-    dilation 1, zero padding.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, padding=padding, groups=groups)``
+    ``signal`` (B, Cin, L), ``kernel`` (Cout, Cin/groups, K), ``bias`` (Cout,) or None, on a ROCm device, all three float32,
+    float16 or bfloat16; stride 1, dilation 1, zero padding.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, padding=padding, groups=groups)``
     (cross-correlation; ``padding`` an int, 'same' or 'valid'), output length L + 2*padding - K + 1.  ``causal=True``
     (``padding`` must be 0): y[b, o, t] = bias[o] + sum_i sum_{s <= min(t, K-1)} kernel[o, i, s] * signal[b, (g, i), t - s],
     output length L; K may exceed L.  Differentiable in signal, kernel and bias.
 
+    float16 / bfloat16 tensors are read and written by the kernels themselves: float32 arithmetic, the signal and the
+    taps widened as they are loaded, the output rounded once as it is stored, so the result (and, in training, each
+    gradient) has the bits of widening the tensors, running the float32 function and rounding with ``.to(dtype)``.
+    Autograd saves the 16-bit tensors.  ``FFTCONV_HALF_IO=0`` takes that cast path instead.
+
     Rows whose padded length is at most 4096 run the ``fft_conv`` kernels; a row that needs more than 2**24 points raises
-    ``NotImplementedError``.  float16 / bfloat16 / float64 tensors are not taken by this path (``TypeError``)."""
+    ``NotImplementedError``.  float64 tensors and tensors of different dtypes are not taken by this path
+    (``TypeError``)."""
     return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None)
 
 
@@ -455,8 +476,13 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum)
                                   f"2**24 = {LONG_MAX_POINTS}")
     for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
         if t is not None:
-            _require_long_f32(name, t)
+            _require_long_dtype(name, t, signal.dtype)
     _same_device(signal=signal, kernel=kernel, bias=bias)
+    if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
+        # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out (what a caller would write by hand)
+        out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
+                                  causal, None)
+        return out.to(signal.dtype)
     if need <= LONG_HANDOFF_POINTS:
         if not causal:
             return _fft_conv_impl(signal, kernel, bias, 1, padding, 1, groups, "constant", None)
@@ -469,11 +495,15 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum)
     return _long_run(signal, kernel, bias, pad_left, pad_right, causal, signal.shape[2] if causal else 0, groups, spectrum)
 
 
-def _require_long_f32(name: str, t: Tensor):
+_LONG_DTYPES = (torch.float32,) + _LOW_PRECISION
+
+
+def _require_long_dtype(name: str, t: Tensor, dtype: torch.dtype):
+    """Device + dtype gate of ``fft_long_conv`` (``dtype``: the signal's)."""
     if not t.is_cuda:
         raise RuntimeError(
             f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
             f"(no CPU fallback). Move the tensor to 'cuda'.")
-    if t.dtype != torch.float32:
-        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; fft_long_conv takes float32 signal, kernel and "
-                        f"bias (float16 / bfloat16 / float64 run through fft_conv only)")
+    if t.dtype != dtype or dtype not in _LONG_DTYPES:
+        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; fft_long_conv takes signal, kernel and bias "
+                        f"that share one of float32, float16 or bfloat16 (float64 runs through fft_conv only)")

@@ -184,7 +184,8 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
     """``nn.Conv1d`` (stride 1, dilation 1, zero padding; state_dict = weight, bias) whose forward is
     ``fft_long_conv``: one transform over the whole padded row, for filters as long as the row.  ``causal=True``
     computes y[t] = sum_s weight[s] * x[t - s] (output length L, ``padding`` must be 0).  The kernel spectrum is cached
-    under the rules of ``_SpectrumCache``."""
+    under the rules of ``_SpectrumCache``, for a float32 module and for one in float16 / bfloat16 (``module.bfloat16()``:
+    the kernels read the 16-bit weight and signal and write a 16-bit output; the cached spectrum stays float32)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
                  dtype=None):
@@ -202,8 +203,9 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         weight, bias = self.weight, self.bias
         pad_left, pad_right, need = F_._long_geometry(signal, weight, bias, padding, self.groups, self.causal)
         spectrum = None
-        if (F_.LONG_HANDOFF_POINTS < need <= F_.LONG_MAX_POINTS and signal.is_cuda and signal.dtype == torch.float32
-                and weight.is_cuda and weight.dtype == torch.float32 and signal.device == weight.device):
+        if (F_.LONG_HANDOFF_POINTS < need <= F_.LONG_MAX_POINTS and signal.is_cuda and weight.is_cuda
+                and signal.device == weight.device and signal.dtype == weight.dtype
+                and (signal.dtype == torch.float32 or F_._half_native(signal, weight, bias))):
             plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
                                  signal.shape[2] if self.causal else 0, bias is not None)
             spectrum = self._cached_spectrum(plan)

@@ -192,7 +192,7 @@ long long fc_debug_grid(const fc_plan* plan);
 int fc_debug_route(const fc_plan* plan, int32_t route[16]);
 
 /* ---- Long filters (ABI 7 extension: new entry points only, nothing that existed changes): a 1-D filter as long as the row, functional.py:66-75 with one transform over the whole
- * padded row instead of overlap-save tiles.  float32, stride 1, dilation 1, zero padding.  The plan computes
+ * padded row instead of overlap-save tiles.  float32 (float16 / bfloat16 tensors: the _io calls below), stride 1, dilation 1, zero padding.  The plan computes
  *   y[b][(g,o)][t] = bias[(g,o)] + sum_i sum_k u[(g,o)][i][k] * xpad[b][(g,i)][t + k],   0 <= t < out_keep,
  * xpad = x with pad_left zeros in front and pad_right behind, u[k] = w[k] (flip 0, cross-correlation) or w[K-1-k]
  * (flip 1).  The causal long convolution y[t] = sum_s h[s] x[t-s] is pad_left = K-1, pad_right = 0, flip = 1,
@@ -233,6 +233,22 @@ int fc_long_transform_kernel(const fc_long_plan* plan, const float* weight, void
  * hip_stream, nothing allocated or synchronised. */
 int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectrum, const float* bias, float* y,
                      void* workspace, void* hip_stream);
+
+/* The two calls above with the element types of their tensors named (ABI 7 extension: new entry points only; the calls
+ * above are these with FC_F32).  A long plan is independent of the element types -- the same N1 x N2, tables, spectrum,
+ * workspace and slabs serve every combination -- so the types are arguments of the call, not fields of fc_long_desc.
+ * weight_dtype, x_dtype and y_dtype are fc_dtype codes: FC_F32, FC_F16 or FC_BF16, each on its own (16-bit x and dy with
+ * a float32 y is how a weight gradient is taken); FC_F64 answers FC_ERR_UNSUPPORTED and any other value FC_ERR_INVALID,
+ * both with text.  A 16-bit weight (Cout, Cin/groups, K) and a 16-bit x (B, Cin, L) are read where they lie and widened
+ * exactly as they are loaded; no float32 copy is made.  spectrum, workspace and bias are float32 whatever the types, and
+ * the spectrum of a 16-bit weight has the bytes of the spectrum of the widened weight.  The arithmetic is float32; a
+ * 16-bit y receives the float32 result with the float32 bias added, rounded once as it is stored (to nearest even;
+ * float16 overflows to inf, a bfloat16 NaN stays a NaN), every sample of the kept window written.  The result therefore
+ * has the bits of: widen the tensors to float32, run fc_long_transform_kernel / fc_long_forward, round y. */
+int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, int weight_dtype, void* spectrum,
+                                 void* workspace, void* hip_stream);
+int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, const void* spectrum, const float* bias,
+                        void* y, int y_dtype, void* workspace, void* hip_stream);
 
 #ifdef __cplusplus
 }

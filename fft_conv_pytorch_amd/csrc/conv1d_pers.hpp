@@ -12,7 +12,7 @@
 //   * the mix streams the spectrum through two register sets that are both in flight (set A holds step
 //     s, set B step s+1; each is refilled with step s+2 right after use); the first two sets of an item
 //     are requested before the barrier in front of the mix;
-//   * with PHASES a dilation d runs as d interleaved phases on the batch-sharing axis (virtual batch
+//   * in the phase builds (pers::phases) a dilation d runs as d interleaved phases on the batch-sharing axis (virtual batch
 //     B*d against the undilated kernel spectrum).
 // Fast-path restrictions (everything else runs conv1d_wide_kernel or conv1d_fused_kernel): a single
 // input-channel chunk (Cin/groups <= CIB), full output chunks (Cout/groups a multiple of CIB), stride 1.
@@ -42,23 +42,46 @@ __device__ __forceinline__ void stamp_clock(unsigned long long* buf, int item, i
     buf[((size_t)item * 16 + (threadIdx.x >> 6)) * 16 + slot] = __builtin_amdgcn_s_memtime();
 }
 
-// PH2 (with PHASES, an even number of phases): the two sequences of a wave are the phases 2j and 2j+1 of ONE channel
+// The build of the kernel is a mask of the features below (template parameter BUILD; a launch names the features it
+// switches on, `pers::phases | pers::pairs`).  The plain build (0) keeps its immediate offsets and is the only one the
+// headline configuration runs.
+namespace pers {
+constexpr unsigned phases = 1;       // a dilation d runs as d interleaved phases on the batch-sharing axis (see above)
+// pairs (with phases, an even number of phases): the two sequences of a wave are the phases 2j and 2j+1 of ONE channel
 // pair instead of two channel pairs of one phase, so that a lane can load / store both phases' samples of a position
 // as 8 bytes and trade halves with its partner lane (v_permlane32_swap): half the memory instructions, each
 // touching half the cache lines of the 4-byte accesses at a 4*d-byte pitch.
-// STAMPS: the profiling hook (fc_forward_stamped) is a build of its own -- compiled into the product kernel, even
-// switched off, its guarded stores made hipcc put a full s_waitcnt vmcnt(0) between the two items of a workgroup
-// (a pending store's registers are reused), i.e. a wait for every output store of the first item.
-// PH4 (with PHASES, a multiple of four phases, 8 -> 8 channel blocks, four slots): the packing is turned round -- a complex
+constexpr unsigned pairs = 2;
+// quads (with phases, a multiple of four phases, 8 -> 8 channel blocks, four slots): the packing is turned round -- a complex
 // sequence carries two PHASES of ONE channel, a wave owns one channel and its two halves the phase pairs (0,1) and (2,3) --
 // so a lane loads / stores all four phases of a position as 16 contiguous bytes (full cache lines per wave-instruction, where
-// PH2's 8 bytes at a 16-byte pitch cost partial-line write-backs and re-fetches: 1.6x the output bytes written at cfgD).
+// the pairs' 8 bytes at a 16-byte pitch cost partial-line write-backs and re-fetches: 1.6x the output bytes written at cfgD).
 // The mix contracts the same 8 x 8 matrix per bin; its slots are phases and its steps single output channels.
-template <int P, int S, int CIB, int NB, int NT, bool PHASES = false, int RING = 2, bool DIAG = false, bool SEG = false, bool PH2 = false,
-          bool STAMPS = false, bool PH4 = false, int IO = IO_F32>
+constexpr unsigned quads = 4;
+constexpr unsigned depthwise = 8;    // every channel meets only its own kernel (blocks of 8 channels)
+constexpr unsigned segments = 16;    // a segment of the taps of a long kernel: shifted source, later segments add to y
+// stamps: the profiling hook (fc_forward_stamped) is a build of its own -- compiled into the product kernel, even
+// switched off, its guarded stores made hipcc put a full s_waitcnt vmcnt(0) between the two items of a workgroup
+// (a pending store's registers are reused), i.e. a wait for every output store of the first item.
+constexpr unsigned stamps = 32;
+constexpr unsigned half_io = 64;     // x and y are 16-bit (Io<IO_H16>: float16 or bfloat16 by the launch's `io` code)
+// the combinations that exist: pairs and quads are phase builds on a P*P tile with 8-channel blocks, quads fill
+// a workgroup of four slots and exclude pairs
+constexpr bool valid(unsigned build, int S, int CIB, int NB) {
+  const bool packable = (build & phases) && !(build & (depthwise | segments)) && S == 1 && CIB == 8;
+  if ((build & pairs) && !packable) return false;
+  if ((build & quads) && !(packable && !(build & pairs) && NB == 4)) return false;
+  return build < 2 * half_io;
+}
+}  // namespace pers
+
+template <int P, int S, int CIB, int NB, int NT, unsigned BUILD>
 __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs pa) {
-  static_assert(!PH2 || (PHASES && !DIAG && !SEG && S == 1 && CIB == 8), "paired phases: plain phase build on a P*P tile");
-  static_assert(!PH4 || (PHASES && !DIAG && !SEG && !PH2 && S == 1 && CIB == 8 && NB == 4), "phase quads: 8 channels x 2 phase pairs");
+  static_assert(pers::valid(BUILD, S, CIB, NB), "no such build: see pers::valid");
+  constexpr bool PHASES = (BUILD & pers::phases) != 0, PH2 = (BUILD & pers::pairs) != 0, PH4 = (BUILD & pers::quads) != 0;
+  constexpr bool DIAG = (BUILD & pers::depthwise) != 0, SEG = (BUILD & pers::segments) != 0, STAMPS = (BUILD & pers::stamps) != 0;
+  constexpr int IO = (BUILD & pers::half_io) ? IO_H16 : IO_F32;
+  constexpr int RING = 2;                   // spectrum register sets of the mix
   using G = Geo<P, S>;
   constexpr int T = G::T;
   constexpr int NPI = CIB / 2;

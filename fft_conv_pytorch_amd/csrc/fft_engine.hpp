@@ -278,6 +278,7 @@ __device__ __forceinline__ void buf_store_f32(float v, BufRsrc r, unsigned voff,
 // drops the access.
 constexpr int IO_F32 = 0, IO_H16 = 1;
 constexpr int IO_CODE_F16 = 2, IO_CODE_BF16 = 3;   // fc_dtype codes of a launch's `io` field (0: float32)
+constexpr bool io_is_h16(int code) { return code == IO_CODE_F16 || code == IO_CODE_BF16; }   // a launch of an IO_H16 build
 template <int IO>
 struct Io;
 template <>

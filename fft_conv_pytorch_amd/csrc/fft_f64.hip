@@ -14,10 +14,9 @@
 // 2-D / 3-D float64 plans run nd_f64.hip.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "axis_map.hpp"
 #include "fft_f64.h"
+#include "launch.hpp"
 
 namespace fc {
 namespace {
@@ -175,24 +174,9 @@ hipError_t launch_fft_f64(int which, const FftF64Args& a, hipStream_t st) {
   const size_t lds = fft_f64_lds_bytes(a.T);
   const int nt = a.T / 2;
   if (nt < 64 || nt > 1024 || lds > 160 * 1024) return hipErrorInvalidValue;
-  // > 64 KiB of dynamic LDS (the 2048-point tile: 80 KiB) needs the opt-in, once per kernel AND device
-  static std::atomic<unsigned long long> opted[2];
-  auto kernel = which == 0 ? spectrum_f64_kernel : conv1d_f64_kernel;
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !(opted[which].load(std::memory_order_acquire) >> dev & 1ull)) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      if (tracked) opted[which].fetch_or(1ull << dev, std::memory_order_release);
-    }
-  }
-  long long grid = which == 0 ? (long long)a.Cout * a.Cig : (long long)a.B * a.G * a.n_ochunks * a.ntiles;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nt), lds, st, a);
-  return hipGetLastError();
+  // (the 2048-point tile takes 80 KiB of LDS)
+  if (which == 0) return launch_kernel<spectrum_f64_kernel>((long long)a.Cout * a.Cig, nt, lds, st, a);
+  return launch_kernel<conv1d_f64_kernel>((long long)a.B * a.G * a.n_ochunks * a.ntiles, nt, lds, st, a);
 }
 
 }  // namespace fc

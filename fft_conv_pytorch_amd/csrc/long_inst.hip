@@ -1,9 +1,8 @@
 // long_inst.hip -- instantiates the three kernels of long1d.hpp (and the 16-bit builds of the two column kernels, one
 // build for float16 and bfloat16) for ONE tile geometry (P, S): built once per geometry
 // with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
+#include "launch.hpp"
 #include "long1d.hpp"
-
-#include <atomic>
 
 #ifndef FC_P
 #error "compile with -DFC_P=<points per thread> -DFC_S=<lane split>"
@@ -22,64 +21,36 @@ constexpr size_t kLds = (size_t)kNSEQ * kLSEQP * sizeof(float2);
 // output channels per workgroup of the row pass: 32 running sums (64 registers) per thread
 constexpr int kOB = 32 / FC_P;
 
-// > 64 KiB of dynamic LDS needs an opt-in per kernel and device (see tile_inst.hip)
-struct LdsOptIn {
-  std::atomic<unsigned long long> mask{0};
-};
-template <class K>
-hipError_t ensure_lds(K kernel, LdsOptIn* done) {
-  if (kLds <= 64 * 1024) return hipSuccess;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const bool tracked = dev >= 0 && dev < 64;
-  if (tracked && (done->mask.load(std::memory_order_acquire) >> dev & 1ull)) return hipSuccess;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess && tracked) done->mask.fetch_or(1ull << dev, std::memory_order_release);
-  return e;
-}
-
-template <class K>
-hipError_t launch(K k, LdsOptIn* done, const LongArgs& a, int blocks_per_unit, long long units, hipStream_t st) {
-  hipError_t e = ensure_lds(k, done);
-  if (e != hipSuccess) return e;
-  const long long grid = units * blocks_per_unit;
-  if (blocks_per_unit <= 0 || units <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+template <auto Kernel>
+hipError_t launch(const LongArgs& a, int blocks_per_unit, long long units, hipStream_t st) {
+  if (blocks_per_unit <= 0 || units <= 0) return hipErrorInvalidValue;
   LongArgs b = a;
   b.d_nblk = make_fastdiv((unsigned)blocks_per_unit);
   b.d_c = make_fastdiv((unsigned)a.C);
   b.d_nob = make_fastdiv((unsigned)a.nob);
   b.d_g = make_fastdiv((unsigned)a.G);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kNT), kLds, st, b);
-  return hipGetLastError();
+  return launch_kernel<Kernel>(units * blocks_per_unit, kNT, kLds, st, b);
 }
-
-bool is_h16(int code) { return code == IO_CODE_F16 || code == IO_CODE_BF16; }
 
 hipError_t cols_fwd(const LongArgs& a, long long rows, hipStream_t st) {
-  static LdsOptIn done;
   if (a.N1 != kT || a.src_io != 0) return hipErrorInvalidValue;
-  return launch(long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT>, &done, a, a.N2 / kNSEQ, rows, st);
+  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT>>(a, a.N2 / kNSEQ, rows, st);
 }
 hipError_t cols_fwd_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  static LdsOptIn done;
-  if (a.N1 != kT || !is_h16(a.src_io)) return hipErrorInvalidValue;
-  return launch(long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>, &done, a, a.N2 / kNSEQ, rows, st);
+  if (a.N1 != kT || !io_is_h16(a.src_io)) return hipErrorInvalidValue;
+  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(a, a.N2 / kNSEQ, rows, st);
 }
 hipError_t rows(const LongArgs& a, long long units, hipStream_t st) {
-  static LdsOptIn done;
   if (a.N2 != kT || a.ob != kOB) return hipErrorInvalidValue;
-  return launch(long_rows_kernel<FC_P, FC_S, kNSEQ, kNT, kOB>, &done, a, a.N1 / kNSEQ, units, st);
+  return launch<long_rows_kernel<FC_P, FC_S, kNSEQ, kNT, kOB>>(a, a.N1 / kNSEQ, units, st);
 }
 hipError_t cols_inv(const LongArgs& a, long long rows, hipStream_t st) {
-  static LdsOptIn done;
   if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
-  return launch(long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT>, &done, a, a.N2 / kNSEQ, rows, st);
+  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT>>(a, a.N2 / kNSEQ, rows, st);
 }
 hipError_t cols_inv_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  static LdsOptIn done;
-  if (a.N1 != kT || !is_h16(a.y_io)) return hipErrorInvalidValue;
-  return launch(long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>, &done, a, a.N2 / kNSEQ, rows, st);
+  if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
+  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(a, a.N2 / kNSEQ, rows, st);
 }
 
 }  // namespace

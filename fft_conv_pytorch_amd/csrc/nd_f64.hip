@@ -19,8 +19,7 @@
 // (256 threads), interleaved in LDS (point n of sequence c at n * NS + c) so that butterflies are bank-conflict free.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
+#include "launch.hpp"
 #include "nd_f64.h"
 
 namespace fc {
@@ -306,61 +305,38 @@ __global__ __launch_bounds__(1024) void rows_c2r_f64_kernel(const RowsC2RF64Args
   }
 }
 
-// > 64 KiB of dynamic LDS (the 2048-point transform: 80 KiB) needs the opt-in, once per kernel AND device
-hipError_t launch_nd(const void* kernel, std::atomic<unsigned long long>& opted, int T, long long grid, const void* args,
-                     hipStream_t st) {
+// T-point transforms, nd_f64_nseq(T) sequences per workgroup (the 2048-point transform takes 80 KiB of LDS)
+template <auto Kernel, class Args>
+hipError_t launch_nd(int T, long long grid, const Args& a, hipStream_t st) {
   const size_t lds = nd_f64_lds_bytes(T);
   if (T < 8 || T > 2048 || (T & (T - 1)) || lds > 160 * 1024) return hipErrorInvalidValue;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !(opted.load(std::memory_order_acquire) >> dev & 1ull)) {
-      e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      if (tracked) opted.fetch_or(1ull << dev, std::memory_order_release);
-    }
-  }
-  void* kargs[] = {const_cast<void*>(args)};     // the kernels take their argument struct by value
-  const unsigned nthr = (unsigned)(nd_f64_nseq(T) * (T / 2));
-  hipError_t e = hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(nthr), kargs, lds, st);
-  if (e != hipSuccess) return e;
-  return hipGetLastError();
+  return launch_kernel<Kernel>(grid, (unsigned)(nd_f64_nseq(T) * (T / 2)), lds, st, a);
 }
 
 }  // namespace
 
 hipError_t launch_rows_r2c_f64(const RowsF64Args& a, hipStream_t st) {
-  static std::atomic<unsigned long long> opted{0};
   const long long seqs = ((a.R + 1) / 2) * a.nt, NS = nd_f64_nseq(a.T);
-  return launch_nd(reinterpret_cast<const void*>(rows_r2c_f64_kernel), opted, a.T, (seqs + NS - 1) / NS, &a, st);
+  return launch_nd<rows_r2c_f64_kernel>(a.T, (seqs + NS - 1) / NS, a, st);
 }
 
 hipError_t launch_col_f64(const ColF64Args& a, hipStream_t st) {
-  static std::atomic<unsigned long long> opted{0};
   const int NS = nd_f64_nseq(a.T);
-  return launch_nd(reinterpret_cast<const void*>(col_f64_kernel), opted, a.T,
-                   a.nlines * a.nt * ((a.ncol + NS - 1) / NS), &a, st);
+  return launch_nd<col_f64_kernel>(a.T, a.nlines * a.nt * ((a.ncol + NS - 1) / NS), a, st);
 }
 
 hipError_t launch_fused_f64(const FusedF64Args& a, hipStream_t st) {
-  static std::atomic<unsigned long long> opted[3];
   const int NS = nd_f64_nseq(a.T);
-  const int which = a.nb == 4 ? 2 : (a.nb == 2 ? 1 : 0);
-  if ((1 << which) != a.nb || a.cob < 1 || a.cob > 8 / a.nb) return hipErrorInvalidValue;
-  const void* k = which == 0 ? reinterpret_cast<const void*>(fused_f64_kernel<1>)
-                : which == 1 ? reinterpret_cast<const void*>(fused_f64_kernel<2>)
-                             : reinterpret_cast<const void*>(fused_f64_kernel<4>);
+  if ((a.nb != 1 && a.nb != 2 && a.nb != 4) || a.cob < 1 || a.cob > 8 / a.nb) return hipErrorInvalidValue;
   const long long grid = (long long)((a.B + a.nb - 1) / a.nb) * a.G * a.n_ochunks * a.nt * ((a.ncol + NS - 1) / NS);
-  return launch_nd(k, opted[which], a.T, grid, &a, st);
+  if (a.nb == 1) return launch_nd<fused_f64_kernel<1>>(a.T, grid, a, st);
+  if (a.nb == 2) return launch_nd<fused_f64_kernel<2>>(a.T, grid, a, st);
+  return launch_nd<fused_f64_kernel<4>>(a.T, grid, a, st);
 }
 
 hipError_t launch_rows_c2r_f64(const RowsC2RF64Args& a, hipStream_t st) {
-  static std::atomic<unsigned long long> opted{0};
   const long long seqs = ((a.R + 1) / 2) * a.nt, NS = nd_f64_nseq(a.T);
-  return launch_nd(reinterpret_cast<const void*>(rows_c2r_f64_kernel), opted, a.T, (seqs + NS - 1) / NS, &a, st);
+  return launch_nd<rows_c2r_f64_kernel>(a.T, (seqs + NS - 1) / NS, a, st);
 }
 
 }  // namespace fc

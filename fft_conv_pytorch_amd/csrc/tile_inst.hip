@@ -2,10 +2,11 @@
 // Built once per geometry with -DFC_P=.. -DFC_S=.. -DFC_NT=.. (see Makefile) so the
 // geometries compile in parallel.
 #include "fc_internal.h"
+#include "launch.hpp"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef FC_P
 #error "compile with -DFC_P=<points per thread> -DFC_S=<lane split> -DFC_NT=<threads of the fused 1-D kernel>"
@@ -24,83 +25,47 @@ constexpr int kNSEQ_R = (kNSEQ_C / FC_ROWS_DIV) < 1 ? 1 : (kNSEQ_C / FC_ROWS_DIV
 constexpr int kLSEQP = SeqLayout<GG>::LSEQP;
 constexpr int kFusedMaxCib = (8 * kLSEQP * 8 <= 160 * 1024 && 8 * GG::TS <= 1024) ? 8 : 4;
 
-// Opt in to > 64 KiB of dynamic LDS (gfx950: 160 KiB per workgroup).  Done once per kernel AND device with
-// the full 160 KiB so nothing but the launch happens on later calls (launches may be under HIP-graph
-// capture).  The attribute belongs to the function on the current device, so the "done" state is a bit per
-// device ordinal; the flag is atomic because plans are shared between threads (a duplicate
-// hipFuncSetAttribute from two racing first calls is harmless).
-struct LdsOptIn {
-  std::atomic<unsigned long long> mask{0};
-};
-template <class K>
-hipError_t ensure_lds(K kernel, size_t lds, LdsOptIn* done) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const bool tracked = dev >= 0 && dev < 64;
-  if (tracked && (done->mask.load(std::memory_order_acquire) >> dev & 1ull)) return hipSuccess;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess && tracked) done->mask.fetch_or(1ull << dev, std::memory_order_release);
-  return e;
+// The float32 or the 16-bit build of a kernel by a launch's `io` code: calls f with IO_F32 or IO_H16 (Io in
+// fft_engine.hpp; one 16-bit build serves float16 and bfloat16) as an integral constant.  The host passes no other
+// code (fc_dtype of the plan).
+template <class F>
+hipError_t with_io(int code, F f) {
+  if (code == 0) return f(std::integral_constant<int, IO_F32>{});
+  if (io_is_h16(code)) return f(std::integral_constant<int, IO_H16>{});
+  return hipErrorInvalidValue;
 }
+#define FC_IO(io) decltype(io)::value
 
-// IO: element type of x and y (Io in fft_engine.hpp); the 16-bit builds serve float16 and bfloat16 plans (a.io), which
-// never run the chunk-by-chunk, segment or profiling launches
-template <int CIB, int IO = IO_F32>
-hipError_t launch_conv1d(const Conv1dArgs& a, int grid, size_t lds, hipStream_t st) {
-  auto k = conv1d_fused_kernel<FC_P, FC_S, CIB, FC_NT, IO>;
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(FC_NT), lds, st, a);
-  return hipGetLastError();
-}
-
+// (the 16-bit builds never run the chunk-by-chunk, segment or profiling launches)
 hipError_t conv1d_dispatch(int cib, const Conv1dArgs& a, int grid, size_t lds, hipStream_t st) {
-  if (a.io != 0) {
+  return with_io(a.io, [&](auto io) {
     switch (cib) {
-      case 2: return launch_conv1d<2, IO_H16>(a, grid, lds, st);
-      case 4: return launch_conv1d<4, IO_H16>(a, grid, lds, st);
-      case 8: return launch_conv1d<8, IO_H16>(a, grid, lds, st);
+      case 2: return launch_kernel<conv1d_fused_kernel<FC_P, FC_S, 2, FC_NT, FC_IO(io)>>(grid, FC_NT, lds, st, a);
+      case 4: return launch_kernel<conv1d_fused_kernel<FC_P, FC_S, 4, FC_NT, FC_IO(io)>>(grid, FC_NT, lds, st, a);
+      case 8: return launch_kernel<conv1d_fused_kernel<FC_P, FC_S, 8, FC_NT, FC_IO(io)>>(grid, FC_NT, lds, st, a);
       default: return hipErrorInvalidValue;
     }
-  }
-  switch (cib) {
-    case 2: return launch_conv1d<2>(a, grid, lds, st);
-    case 4: return launch_conv1d<4>(a, grid, lds, st);
-    case 8: return launch_conv1d<8>(a, grid, lds, st);
-    default: return hipErrorInvalidValue;
-  }
+  });
 }
 
 hipError_t spec1d_dispatch(const Spec1dArgs& a, int grid, size_t lds, hipStream_t st) {
-  auto k = spectrum1d_kernel<FC_P, FC_S, FC_NT>;
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(FC_NT), lds, st, a);
-  return hipGetLastError();
+  return launch_kernel<spectrum1d_kernel<FC_P, FC_S, FC_NT>>(grid, FC_NT, lds, st, a);
 }
 
-template <int IO>
-hipError_t launch_rows_r2c(const RowsR2CArgs& a, hipStream_t st) {
-  constexpr int NT = kNSEQ_R * GG::TS;
-  auto k = rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, NT, IO>;
-  const size_t lds = (size_t)kNSEQ_R * kLSEQP * sizeof(float2);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
+// first and last pass of the N-d plans: Kernel is a build of rows_r2c_kernel (Args = RowsR2CArgs) or rows_c2r_kernel
+constexpr int kNT_R = kNSEQ_R * GG::TS;
+template <auto Kernel, class Args>
+hipError_t launch_rows(const Args& a, hipStream_t st) {
   const long long nyb = (a.NY + 2 * kNSEQ_R - 1) / (2 * kNSEQ_R);
-  const long long grid = (long long)a.NA * a.NC * a.nxt * nyb;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  auto b = a;
+  Args b = a;
   b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
-  return hipGetLastError();
+  return launch_kernel<Kernel>((long long)a.NA * a.NC * a.nxt * nyb, kNT_R, (size_t)kNSEQ_R * kLSEQP * sizeof(float2), st, b);
 }
 hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
-  return a.io != 0 ? launch_rows_r2c<IO_H16>(a, st) : launch_rows_r2c<IO_F32>(a, st);
+  return with_io(a.io, [&](auto io) { return launch_rows<rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, FC_IO(io)>>(a, st); });
+}
+hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
+  return with_io(a.io, [&](auto io) { return launch_rows<rows_c2r_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, FC_IO(io)>>(a, st); });
 }
 
 template <bool INV>
@@ -109,42 +74,10 @@ hipError_t c2c_dispatch(const C2CArgs& a, hipStream_t st) {
   const size_t lds = (size_t)kNSEQ_C * kLSEQP * sizeof(float2);
   const long long nbb = (a.NB + kNSEQ_C - 1) / kNSEQ_C;
   const long long grid = (long long)a.NA * a.NC * nbb;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  static LdsOptIn done;
   C2CArgs b = a;
   b.d_nbb = make_fastdiv((unsigned)nbb); b.d_nc = make_fastdiv((unsigned)a.NC);
-  if (INV) {
-    auto k = c2c_inv_kernel<FC_P, FC_S, kNSEQ_C, NT>;
-    hipError_t e = ensure_lds(k, lds, &done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
-  } else {
-    auto k = c2c_fwd_kernel<FC_P, FC_S, kNSEQ_C, NT>;
-    hipError_t e = ensure_lds(k, lds, &done);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
-  }
-  return hipGetLastError();
-}
-
-template <int IO>
-hipError_t launch_rows_c2r(const RowsC2RArgs& a, hipStream_t st) {
-  constexpr int NT = kNSEQ_R * GG::TS;
-  auto k = rows_c2r_kernel<FC_P, FC_S, kNSEQ_R, NT, IO>;
-  const size_t lds = (size_t)kNSEQ_R * kLSEQP * sizeof(float2);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  const long long nyb = (a.NY + 2 * kNSEQ_R - 1) / (2 * kNSEQ_R);
-  const long long grid = (long long)a.NA * a.NC * a.nxt * nyb;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  auto b = a;
-  b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
-  return hipGetLastError();
-}
-hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
-  return a.io != 0 ? launch_rows_c2r<IO_H16>(a, st) : launch_rows_c2r<IO_F32>(a, st);
+  if constexpr (INV) return launch_kernel<c2c_inv_kernel<FC_P, FC_S, kNSEQ_C, NT>>(grid, NT, lds, st, b);
+  else return launch_kernel<c2c_fwd_kernel<FC_P, FC_S, kNSEQ_C, NT>>(grid, NT, lds, st, b);
 }
 
 // fused column pass: NB batch items per workgroup share the spectrum loads.  NB is the largest of
@@ -161,19 +94,13 @@ hipError_t launch_fusedc_nb(const FusedCArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
   } else {
     constexpr int NT = NB * CIB * GG::TS;
-    auto k = fusedc_kernel<FC_P, FC_S, CIB, NB, NT>;
     const size_t lds = (size_t)(a.accumulate ? 2 : 1) * NB * CIB * kLSEQP * sizeof(float2);
-    static LdsOptIn done;
-    hipError_t e = ensure_lds(k, lds, &done);
-    if (e != hipSuccess) return e;
     const long long nbb = (a.B + NB - 1) / NB;
     const long long grid = nbb * a.ntiles * a.n_ochunks * a.G * ((a.ncol + 7) / 8) * 8;
-    if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
     FusedCArgs b = a;
     b.d_nbb = make_fastdiv((unsigned)nbb); b.d_ncb = make_fastdiv((unsigned)((a.ncol + 7) / 8));
     b.d_g = make_fastdiv((unsigned)a.G); b.d_noc = make_fastdiv((unsigned)a.n_ochunks);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, st, b);
-    return hipGetLastError();
+    return launch_kernel<fusedc_kernel<FC_P, FC_S, CIB, NB, NT>>(grid, NT, lds, st, b);
   }
 }
 template <int CIB>
@@ -208,56 +135,56 @@ constexpr int kPersNb0 = 0, kPersNb1 = 0;
 #endif
 constexpr size_t pers_lds_bytes(int nb) { return ((size_t)FC_P * GG::N2 + (size_t)nb * 4 * GG::LSEQ) * sizeof(float2); }
 
-// batch-sharing kernel builds: PHASES (dilation as phases) x DIAG (depthwise blocks); the plain one keeps its
-// immediate offsets and is the only one the headline configuration runs
-template <int NB, bool PHASES, bool DIAG, bool SEG = false, bool PH2 = false, bool STAMPS = false, bool PH4 = false,
-          int IO = IO_F32>
-hipError_t launch_pers_variant(const Conv1dPersArgs& a, int grid, hipStream_t st) {
-  constexpr int NT = NB * 4 * GG::TS;
-  const size_t lds = pers_lds_bytes(NB);
-  auto k = conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, PHASES, 2, DIAG, SEG, PH2, STAMPS, PH4, IO>;
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
-  return hipGetLastError();
+// The build of the batch-sharing kernel (a mask of the pers:: features, conv1d_pers.hpp) that a launch of NB slots
+// runs, float32 and 16-bit alike; kNoBuild if there is none.  In the order of precedence:
+//   * 16-bit x / y have no segment and no profiling build;
+//   * a segment of a long kernel is not profiled;
+//   * depthwise phases are neither packed nor profiled;
+//   * phases are packed in quads (ph2 == 2; four slots, not profiled: a profiled quad plan runs the pairs) or in pairs
+//     (ph2 != 0), both on the P*P tiles only;
+//   * the profiling build exists for the plain, the phase and the paired-phase kernel.
+constexpr unsigned kNoBuild = ~0u;
+unsigned pers_build(const Conv1dArgs& c, int nb) {
+  const bool h16 = io_is_h16(c.io), ph = c.ph > 1, dg = c.diag != 0;
+  if (c.io != 0 && (!h16 || c.segmented || c.stamps)) return kNoBuild;
+  const unsigned io = h16 ? pers::half_io : 0u;
+  if (c.segmented) return pers::segments | (dg ? pers::depthwise : 0u);
+  if (ph && dg) return io | pers::phases | pers::depthwise;
+  const unsigned st = c.stamps ? pers::stamps : 0u;
+  if (ph && FC_S == 1 && c.ph2 == 2 && nb == 4 && !st) return io | pers::phases | pers::quads;
+  if (ph && FC_S == 1 && c.ph2) return io | pers::phases | pers::pairs | st;
+  if (ph) return io | pers::phases | st;
+  if (dg) return io | pers::depthwise;
+  return io | st;
 }
 
+// launches the one of BUILDS that is `build`
+template <int NB, unsigned... BUILDS>
+hipError_t launch_pers_among(unsigned build, const Conv1dPersArgs& a, int grid, hipStream_t st) {
+  constexpr int NT = NB * 4 * GG::TS;
+  hipError_t e = hipErrorInvalidValue;
+  auto launch = [&](auto b) {
+    constexpr unsigned B = decltype(b)::value;
+    if constexpr (pers::valid(B, FC_S, 8, NB))      // (pairs: only on the P*P tiles; quads: only with four slots)
+      if (build == B) e = launch_kernel<conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, B>>(grid, NT, pers_lds_bytes(NB), st, a);
+  };
+  (launch(std::integral_constant<unsigned, BUILDS>{}), ...);
+  return e;
+}
+
+// every build of the batch-sharing kernel the library holds
 template <int NB>
 hipError_t launch_pers(const Conv1dPersArgs& a, int grid, hipStream_t st) {
   if constexpr (NB == 0) {
     return hipErrorInvalidValue;
   } else {
-    const bool ph = a.c.ph > 1, dg = a.c.diag != 0;
-    if (a.c.io != 0) {     // 16-bit x / y: the builds without segments and profiling hook
-      if (a.c.segmented || a.c.stamps) return hipErrorInvalidValue;
-      if (ph && dg) return launch_pers_variant<NB, true, true, false, false, false, false, IO_H16>(a, grid, st);
-#if FC_S == 1
-      if constexpr (NB == 4) {
-        if (ph && a.c.ph2 == 2) return launch_pers_variant<NB, true, false, false, false, false, true, IO_H16>(a, grid, st);
-      }
-      if (ph && a.c.ph2) return launch_pers_variant<NB, true, false, false, true, false, false, IO_H16>(a, grid, st);
-#endif
-      if (ph) return launch_pers_variant<NB, true, false, false, false, false, false, IO_H16>(a, grid, st);
-      if (dg) return launch_pers_variant<NB, false, true, false, false, false, false, IO_H16>(a, grid, st);
-      return launch_pers_variant<NB, false, false, false, false, false, false, IO_H16>(a, grid, st);
-    }
-    if (a.c.segmented) return dg ? launch_pers_variant<NB, false, true, true>(a, grid, st)
-                                 : launch_pers_variant<NB, false, false, true>(a, grid, st);
-    if (ph && dg) return launch_pers_variant<NB, true, true>(a, grid, st);
-    const bool stamped = a.c.stamps != nullptr;       // profiling builds exist for the plain and the phase kernels only
-#if FC_S == 1
-    if constexpr (NB == 4) {
-      if (ph && a.c.ph2 == 2 && !stamped) return launch_pers_variant<NB, true, false, false, false, false, true>(a, grid, st);
-    }
-    if (ph && a.c.ph2) return stamped ? launch_pers_variant<NB, true, false, false, true, true>(a, grid, st)
-                                      : launch_pers_variant<NB, true, false, false, true>(a, grid, st);
-#endif
-    if (ph) return stamped ? launch_pers_variant<NB, true, false, false, false, true>(a, grid, st)
-                           : launch_pers_variant<NB, true, false>(a, grid, st);
-    if (dg) return launch_pers_variant<NB, false, true>(a, grid, st);
-    return stamped ? launch_pers_variant<NB, false, false, false, false, true>(a, grid, st)
-                   : launch_pers_variant<NB, false, false>(a, grid, st);
+    using namespace pers;
+    return launch_pers_among<NB, 0u, stamps, depthwise, segments, segments | depthwise,
+                             phases, phases | stamps, phases | depthwise,
+                             phases | pairs, phases | pairs | stamps, phases | quads,
+                             half_io, half_io | depthwise,
+                             half_io | phases, half_io | phases | depthwise,
+                             half_io | phases | pairs, half_io | phases | quads>(pers_build(a.c, NB), a, grid, st);
   }
 }
 
@@ -269,19 +196,11 @@ hipError_t pers_dispatch(int nb, const Conv1dPersArgs& a, int grid, hipStream_t 
 
 #if FC_P == 32 && (FC_S == 1 || FC_S == 2)
 constexpr int kWideNb = 2;
-template <int IO>
-hipError_t launch_wide(const Conv1dPersArgs& a, int grid, hipStream_t st) {
-  constexpr int NT = kWideNb * 4 * GG::TS;
-  auto k = conv1d_wide_kernel<FC_P, FC_S, kWideNb, NT, IO>;
-  const size_t lds = pers_lds_bytes(kWideNb);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
-  return hipGetLastError();
-}
 hipError_t wide_dispatch(const Conv1dPersArgs& a, int grid, hipStream_t st) {
-  return a.c.io != 0 ? launch_wide<IO_H16>(a, grid, st) : launch_wide<IO_F32>(a, grid, st);
+  constexpr int NT = kWideNb * 4 * GG::TS;
+  return with_io(a.c.io, [&](auto io) {
+    return launch_kernel<conv1d_wide_kernel<FC_P, FC_S, kWideNb, NT, FC_IO(io)>>(grid, NT, pers_lds_bytes(kWideNb), st, a);
+  });
 }
 #else
 constexpr int kWideNb = 0;
@@ -290,34 +209,18 @@ hipError_t wide_dispatch(const Conv1dPersArgs&, int, hipStream_t) { return hipEr
 
 #if FC_P == 32 && FC_S == 1
 constexpr int kWgradNb = 2;
-// IO: element type of x and dY (the 16-bit builds serve float16 and bfloat16 through a.io)
-template <int IO>
-hipError_t launch_wgrad(const WGradArgs& a, int grid, hipStream_t st) {
-  constexpr int NT = kWgradNb * 4 * GG::TS;
-  auto k = wgrad1d_kernel<FC_P, FC_S, kWgradNb, NT, IO>;
-  const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)kWgradNb * 4 * GG::LSEQ) * sizeof(float2);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
-  return hipGetLastError();
-}
+// (the io code names the element type of x and dY)
 hipError_t wgrad_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
-  return a.io != 0 ? launch_wgrad<IO_H16>(a, grid, st) : launch_wgrad<IO_F32>(a, grid, st);
-}
-template <int IO>
-hipError_t launch_wgrad_diag(const WGradArgs& a, int grid, hipStream_t st) {
-  constexpr int NT = 8 * GG::TS;
-  auto k = wgrad1d_diag_kernel<FC_P, FC_S, NT, IO>;
-  const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)8 * GG::LSEQ) * sizeof(float2);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, a);
-  return hipGetLastError();
+  constexpr int NT = kWgradNb * 4 * GG::TS;
+  const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)kWgradNb * 4 * GG::LSEQ) * sizeof(float2);
+  return with_io(a.io, [&](auto io) {
+    return launch_kernel<wgrad1d_kernel<FC_P, FC_S, kWgradNb, NT, FC_IO(io)>>(grid, NT, lds, st, a);
+  });
 }
 hipError_t wgrad_diag_dispatch(const WGradArgs& a, int grid, hipStream_t st) {
-  return a.io != 0 ? launch_wgrad_diag<IO_H16>(a, grid, st) : launch_wgrad_diag<IO_F32>(a, grid, st);
+  constexpr int NT = 8 * GG::TS;
+  const size_t lds = ((size_t)FC_P * GG::N2 + (size_t)8 * GG::LSEQ) * sizeof(float2);
+  return with_io(a.io, [&](auto io) { return launch_kernel<wgrad1d_diag_kernel<FC_P, FC_S, NT, FC_IO(io)>>(grid, NT, lds, st, a); });
 }
 #else
 constexpr int kWgradNb = 0;
@@ -336,19 +239,10 @@ hipError_t dense_dispatch(int which, const DenseArgs& a, hipStream_t st) {
     const int nch = which == 0 ? a.Kc : a.Nc;
     const long long ncb = (nch / 2 + kDenseNseq - 1) / kDenseNseq;
     const long long grid = (long long)a.mcount * ncb * a.G;
-    if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    static LdsOptIn done_f, done_i, done_fh, done_ih;
-    auto launch = [&](auto k, LdsOptIn* done) {
-      hipError_t e = ensure_lds(k, lds_fft, done);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds_fft, st, a);
-      return hipGetLastError();
-    };
-    if (which == 0)
-      return a.io != 0 ? launch(dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT, IO_H16>, &done_fh)
-                       : launch(dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT>, &done_f);
-    return a.io != 0 ? launch(dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT, IO_H16>, &done_ih)
-                     : launch(dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT>, &done_i);
+    return with_io(a.io, [&](auto io) {
+      if (which == 0) return launch_kernel<dense_fwd_kernel<FC_P, FC_S, kDenseNseq, NT, FC_IO(io)>>(grid, NT, lds_fft, st, a);
+      return launch_kernel<dense_inv_kernel<FC_P, FC_S, kDenseNseq, NT, FC_IO(io)>>(grid, NT, lds_fft, st, a);
+    });
   }
   // GEMM: the widest column block that the output channels fill (8 channels per wave), the smallest K chunk that
   // covers the input channels (or 64 and several chunks)
@@ -361,16 +255,9 @@ hipError_t dense_dispatch(int which, const DenseArgs& a, hipStream_t st) {
   const long long units = nmb * nnb * nf * a.G;
   // persistent: one workgroup per CU (two with the small unit)
   const long long grid = std::min<long long>(units, (long long)std::max(1, a.cus) * (mbr == 32 ? 2 : 1));
-  if (grid <= 0 || units > 0x7fffffffffffLL) return hipErrorInvalidValue;
-#define FC_DENSE_GEMM(N, K, MBR)                                                 \
-  if (nct == N && k2n == K && mbr == MBR) {                                      \
-    static LdsOptIn done;                                                        \
-    auto k = dense_gemm_kernel<N, K, MBR>;                                       \
-    hipError_t e = ensure_lds(k, lds, &done);                                    \
-    if (e != hipSuccess) return e;                                               \
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), lds, st, a, nf);      \
-    return hipGetLastError();                                                    \
-  }
+  if (units > 0x7fffffffffffLL) return hipErrorInvalidValue;
+#define FC_DENSE_GEMM(N, K, MBR) \
+  if (nct == N && k2n == K && mbr == MBR) return launch_kernel<dense_gemm_kernel<N, K, MBR>>(grid, 512, lds, st, a, nf);
   FC_DENSE_GEMM(8, 16, 128) FC_DENSE_GEMM(8, 8, 128) FC_DENSE_GEMM(8, 4, 128)
   FC_DENSE_GEMM(4, 16, 128) FC_DENSE_GEMM(4, 8, 128) FC_DENSE_GEMM(4, 4, 128)
   FC_DENSE_GEMM(2, 16, 128) FC_DENSE_GEMM(2, 8, 128) FC_DENSE_GEMM(2, 4, 128)
@@ -395,11 +282,8 @@ hipError_t planes_fwd_dispatch(const PlaneFwdArgs& a, int n_images, hipStream_t 
   if (b.nyt < 1) b.nyt = 1;
   const long long ntile = (long long)b.nxt * b.nyt;
   const long long grid = (long long)n_images * a.NZ * ntile;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
   b.d_nz = make_fastdiv((unsigned)a.NZ); b.d_nt = make_fastdiv((unsigned)ntile); b.d_nx = make_fastdiv((unsigned)b.nxt);
-  auto k = a.io != 0 ? planes_fwd_kernel<kPlNT, IO_H16> : planes_fwd_kernel<kPlNT>;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
-  return hipGetLastError();
+  return with_io(a.io, [&](auto io) { return launch_kernel<planes_fwd_kernel<kPlNT, FC_IO(io)>>(grid, kPlNT, 0, st, b); });
 }
 hipError_t planes_inv_dispatch(const PlaneInvArgs& a, int n_images, hipStream_t st) {
   PlaneInvArgs b = a;
@@ -408,33 +292,23 @@ hipError_t planes_inv_dispatch(const PlaneInvArgs& a, int n_images, hipStream_t 
   if (b.nxt * b.nyt == 1) { b.Vx = a.NVx > 0 ? a.NVx : 1; b.Vy = a.NVy > 0 ? a.NVy : 1; }    // (one tile: the whole window)
   const long long ntile = (long long)b.nxt * b.nyt;
   const long long grid = (long long)n_images * a.NZo * ntile;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
   b.d_nz = make_fastdiv((unsigned)a.NZo); b.d_nt = make_fastdiv((unsigned)ntile); b.d_nx = make_fastdiv((unsigned)b.nxt);
-  auto k = a.io != 0 ? planes_inv_kernel<kPlNT, IO_H16> : planes_inv_kernel<kPlNT>;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kPlNT), 0, st, b);
-  return hipGetLastError();
+  return with_io(a.io, [&](auto io) { return launch_kernel<planes_inv_kernel<kPlNT, FC_IO(io)>>(grid, kPlNT, 0, st, b); });
 }
 template <int NB, bool STAMPS, int NCOLC>
 hipError_t launch_colz_n(const ColZArgs& a, hipStream_t st) {
   constexpr int RING = 2;
-  auto k = colz_kernel<NB, RING, STAMPS, NCOLC>;
-  const size_t lds = colz_lds_bytes(NB);
-  static LdsOptIn done;
-  hipError_t e = ensure_lds(k, lds, &done);
-  if (e != hipSuccess) return e;
   if (a.ncol < 16 || a.ncol % 16 || (NCOLC > 0 && a.ncol != NCOLC)) return hipErrorInvalidValue;
   const long long nbp = (a.B + NB - 1) / NB;
   const long long per = (a.ncol / 16 + 7) / 8;                  // column blocks per XCD
   const long long grid = nbp * a.ntiles * a.n_ochunks * a.G * per * 8;
-  if (grid <= 0 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
   ColZArgs b = a;
   b.d_nbp = make_fastdiv((unsigned)nbp); b.d_ntiles = make_fastdiv((unsigned)a.ntiles);
   b.d_per = make_fastdiv((unsigned)per); b.d_g = make_fastdiv((unsigned)a.G);
   if (b.hcol <= 0) b.hcol = a.ncol;
   if (b.hcol % 16 || a.ncol % b.hcol) return hipErrorInvalidValue;
   b.d_hcol = make_fastdiv((unsigned)b.hcol);
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NB * 128), lds, st, b);
-  return hipGetLastError();
+  return launch_kernel<colz_kernel<NB, RING, STAMPS, NCOLC>>(grid, NB * 128, colz_lds_bytes(NB), st, b);
 }
 // 3-D pipeline: the column count is the compile-time kPlCols; 2-D pipeline (ncol = Tx/2): the run-time build
 template <int NB, bool STAMPS = false>

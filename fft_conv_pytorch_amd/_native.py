@@ -26,6 +26,7 @@ EXPORTS = (
     "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd", "fc_debug_route",
     "fc_long_geometry", "fc_long_plan_create", "fc_long_plan_destroy", "fc_long_plan_info", "fc_long_transform_kernel",
     "fc_long_forward", "fc_long_transform_kernel_io", "fc_long_forward_io",
+    "fc_long_geometry_ext", "fc_long_plan_create_ext",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -65,6 +66,13 @@ class FcLongDesc(ctypes.Structure):
     ]
 
 
+class FcLongExt(ctypes.Structure):
+    """Mirror of ``struct fc_long_ext`` (padding mode, source spread, tap dilation and output step of a long plan)."""
+    _fields_ = [("pad_mode", ctypes.c_int32), ("src_up", ctypes.c_int32), ("tap_dil", ctypes.c_int32),
+                ("out_step", ctypes.c_int32)]
+
+
+LONG_EXT_DEFAULT = (0, 1, 1, 1)
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
@@ -145,6 +153,10 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_transform_kernel_io.restype = i32
         lib.fc_long_forward_io.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
         lib.fc_long_forward_io.restype = i32
+        lib.fc_long_geometry_ext.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i64x8]
+        lib.fc_long_geometry_ext.restype = i32
+        lib.fc_long_plan_create_ext.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), ctypes.POINTER(vp)]
+        lib.fc_long_plan_create_ext.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -328,18 +340,29 @@ class Plan:
 
 def long_desc(key: Tuple) -> FcLongDesc:
     """``struct fc_long_desc`` of a long-plan key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_keep, flip,
-    has_bias)."""
+    has_bias), or those eleven words of an extended key."""
+    if len(key) not in (11, 15):
+        raise ValueError(f"a long-plan key has 11 words, or 15 with (pad_mode, src_up, tap_dil, out_step); got {len(key)}")
     d = FcLongDesc()
     (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_keep,
-     d.flip, d.has_bias) = (int(v) for v in key)
+     d.flip, d.has_bias) = (int(v) for v in key[:11])
     return d
+
+
+def long_ext(key: Tuple) -> FcLongExt:
+    """``struct fc_long_ext`` of a long-plan key: its last four words (pad_mode, src_up, tap_dil, out_step) when it has 15,
+    the defaults (constant, 1, 1, 1) when it has 11."""
+    e = FcLongExt()
+    e.pad_mode, e.src_up, e.tap_dil, e.out_step = (int(v) for v in (key[11:] if len(key) == 15 else LONG_EXT_DEFAULT))
+    return e
 
 
 def long_geometry(key: Tuple) -> dict:
     """``fc_long_geometry``: the info words of the plan this key would get, from the descriptor alone (no device)."""
     lib = load_library()
     info = (ctypes.c_int64 * 8)()
-    st = lib.fc_long_geometry(ctypes.byref(long_desc(key)), ctypes.byref(info))
+    desc = long_desc(key)
+    st = lib.fc_long_geometry_ext(ctypes.byref(desc), ctypes.byref(long_ext(key)), ctypes.byref(info))
     if st != FC_OK:
         _raise(lib, st)
     return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
@@ -355,7 +378,8 @@ class LongPlan:
     def __init__(self, key: Tuple, device_index: int = 0):
         lib = load_library()
         handle = ctypes.c_void_p()
-        st = lib.fc_long_plan_create(ctypes.byref(long_desc(key)), ctypes.byref(handle))
+        desc = long_desc(key)
+        st = lib.fc_long_plan_create_ext(ctypes.byref(desc), ctypes.byref(long_ext(key)), ctypes.byref(handle))
         if st != FC_OK:
             _raise(lib, st)
         self._lib, self._h, self.key = lib, handle, key

@@ -183,7 +183,7 @@ def _grad_weight_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilati
     hit = _BWD_PLANS.get(key)
     if hit is None:
         desc = _native.conv_desc(1, x.shape[0], x.shape[1], wshape[0], groups, (x.shape[2],), (wshape[2],), stride, padding,
-                                 dilation, _native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
+                                 dilation, F_._native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
         # the library sizes the launch for, and keeps its twiddle tables on, the CURRENT device
         with torch.cuda.device(x.device):
             slices = _native.wgrad1d_slices(desc)
@@ -226,7 +226,7 @@ def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dil
     plan = _BWD_PLANS.get(key)
     if plan is None:
         desc = _native.conv_desc(n, x.shape[0], x.shape[1], wshape[0], groups, tuple(x.shape[2:]), tuple(wshape[2:]), stride,
-                                 padding, dilation, _native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
+                                 padding, dilation, F_._native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
         try:
             with torch.cuda.device(x.device):
                 plan = _native.WgradPlan(desc)
@@ -368,31 +368,40 @@ class FFTConvTransposeFunction(torch.autograd.Function):
 
 class FFTLongConvFunction(torch.autograd.Function):
     """``fft_long_conv`` with its three gradients, each through the same three kernels (``F_._long_run``, the primitive
-    y[t] = sum_k u[k] * xpad[t + k] with separate left / right zero padding, a tap order and a count of kept samples):
+    y[j] = sum_k u[k] * xrow[out_step*j + tap_dil*k] with separate left / right padding in a padding mode, a tap order, a
+    count of kept samples and a row that may be spread over a grid of src_up).  With stride s, dilation d, Lp the padded
+    length and nout the output length:
 
-        dX = the primitive on dY with the opposite tap order, the complementary padding (K - 1 - pad) and in / out
-             channels exchanged;
-        dW = the primitive with batch and channels exchanged, signal' = x as (Cin/g, g*B, L), kernel' = dY as
-             (Cout, B, Lout), the first K lags kept -- flipped afterwards when the forward read the taps flipped (causal);
+        dX = the primitive on dY spread by s (src_up), the opposite tap order at tap_dil = d, left padding
+             d*(K - 1) - pad_left, out_step 1 and in / out channels exchanged; L samples kept with zero padding, else the
+             Lp samples of the gradient of the padded row, folded onto their sources by ``_pad_adjoint``;
+        dW = the primitive with batch and channels exchanged, signal' = x as (Cin/g, g*B, L) read with the forward's
+             padding and mode, kernel' = dY as (Cout, B, nout) at tap_dil = s, out_step = d, the first K lags kept --
+             flipped afterwards when the forward read the taps flipped (causal);
         db = dY summed over batch and row.
 
     torch builds the transposed copies of the operands.
 
     float16 / bfloat16 calls run on their 16-bit tensors (autograd saves 16-bit signal and weight): dX reads 16-bit dY
-    and the 16-bit transposed weight and is written in 16 bits; dW reads the 16-bit transposed copies of x and dY, comes
-    back float32 and is rounded once; db is summed in float32.  Each gradient has the bits of the float32 cast path."""
+    and the 16-bit transposed weight and is written in 16 bits (with a padding mode to fold: in float32, folded, rounded
+    once); dW reads the 16-bit transposed copies of x and dY, comes back float32 and is rounded once; db is summed in
+    float32.  Each gradient has the bits of the float32 cast path."""
 
     @staticmethod
-    def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum):
+    def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
+                padding_mode="constant"):
         ctx.save_for_backward(signal, kernel)
-        ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None)
-        keep = signal.shape[2] if causal else 0
-        return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal, keep, groups, spectrum)
+        ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None, int(stride), int(dilation),
+                   padding_mode)
+        return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
+                            F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
+                            pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
 
     @staticmethod
     def backward(ctx, grad):
         signal, kernel = ctx.saved_tensors
-        pad_left, pad_right, flip, g, has_bias = ctx.cfg
+        pad_left, pad_right, flip, g, has_bias, s, d, padding_mode = ctx.cfg
+        mode = F_._native.PAD_MODES[padding_mode]
         grad = grad.detach().contiguous()
         B, cin, L = signal.shape
         cout, cig, K = kernel.shape
@@ -400,17 +409,32 @@ class FFTLongConvFunction(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
-            pl, pr, dy = K - 1 - pad_left, K - 1 - pad_right, grad
-            if pl < 0:          # padding wider than the filter: those leading output samples never met the data
-                dy, pl = dy[..., -pl:], 0
-            if pr < 0:
-                dy, pr = dy[..., :dy.shape[2] + pr], 0
-            dx = F_._long_run(dy, wt, None, pl, pr, not flip, L, g)
+            # zero padding: the gradient of the row itself; another mode: of the padded row, folded below
+            keep, lead, dy = (L, d * (K - 1) - pad_left, grad) if mode == 0 else (L + pad_left + pad_right, d * (K - 1), grad)
+            if lead < 0:        # padding wider than the filter: those leading output samples never met the data
+                drop = -(lead // s)
+                dy, lead = dy[..., drop:], lead + drop * s
+            tail = keep + d * (K - 1) - lead - (s * (dy.shape[2] - 1) + 1)
+            if tail < 0 and dy.shape[2]:
+                dy, tail = dy[..., :max(0, dy.shape[2] - (-tail) // s)], 0
+            if dy.shape[2] == 0:
+                dx = torch.zeros_like(signal)
+            else:
+                fold32 = mode != 0 and grad.dtype in F_._LOW_PRECISION
+                dx = F_._long_run(dy, wt, None, lead, max(tail, 0), not flip, keep, g,
+                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d)
+                if mode != 0:
+                    # (_pad_adjoint folds equal paddings: a row padded by the larger one has zero gradient at the rest)
+                    p = max(pad_left, pad_right)
+                    if p:
+                        dx = _pad_adjoint(F.pad(dx, (p - pad_left, p - pad_right)), (L,), (p,), padding_mode)
+                    dx = dx.to(grad.dtype)
         if ctx.needs_input_grad[1]:
             xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
             dyt = grad.permute(1, 0, 2).contiguous()
-            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32).permute(1, 0, 2)
+            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32, pad_mode=mode,
+                              tap_dil=s, out_step=d).permute(1, 0, 2)
             dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             db = _grad_bias(grad).to(kernel.dtype)
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None

@@ -34,7 +34,10 @@ struct LongGeom {
   int64_t nout;                 // kept output samples
   int64_t padl;                 // row position p holds x[p - padl]
   int64_t tap0, tstep, keff;    // row position p < keff of a filter row holds taps[tap0 + tstep*p]
-  int64_t need;                 // shortest cyclic length: nout + keff - 1
+  int64_t need;                 // shortest cyclic length: out_step * (nout - 1) + tap_dil * (keff - 1) + 1
+  int pad_mode;                 // PadMode of the signal row, and the positions it fills before / behind the data
+  int64_t mpadl, mpadr;
+  int64_t up, dil, step;        // src_up, tap_dil, out_step
   int N1, N2;
   int64_t N;
   int64_t npairs, slab_pairs, slabs;
@@ -44,9 +47,12 @@ struct LongGeom {
 
 bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 0; }
 
-int long_geometry(const fc_long_desc* desc, LongGeom* out) {
+const fc_long_ext kDefaultExt = {0, 1, 1, 1};
+
+int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, LongGeom* out) {
   if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
   const fc_long_desc& d = *desc;
+  const fc_long_ext& e = ext ? *ext : kDefaultExt;
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
     return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
   if (d.in_channels % d.groups || d.out_channels % d.groups)
@@ -55,32 +61,60 @@ int long_geometry(const fc_long_desc* desc, LongGeom* out) {
   if (d.length < 1 || d.kernel < 1) return fail(FC_ERR_INVALID, "length and kernel must be positive");
   if (d.pad_left < 0 || d.pad_right < 0 || d.out_keep < 0) return fail(FC_ERR_INVALID, "padding and out_keep must not be negative");
   if (d.flip != 0 && d.flip != 1) return fail(FC_ERR_INVALID, "flip must be 0 or 1");
+  if (e.pad_mode < PAD_CONSTANT || e.pad_mode > PAD_CIRCULAR) return fail(FC_ERR_INVALID, "unknown pad_mode %d", e.pad_mode);
+  if (e.src_up < 1 || e.tap_dil < 1 || e.out_step < 1)
+    return fail(FC_ERR_INVALID, "src_up (%d), tap_dil (%d) and out_step (%d) must be >= 1", e.src_up, e.tap_dil, e.out_step);
+  if (e.src_up > 1 && e.pad_mode != PAD_CONSTANT)
+    return fail(FC_ERR_INVALID, "src_up (%d) spreads the row over zeros: it goes with pad_mode constant only", e.src_up);
   const int64_t lim = (int64_t)1 << 30;
-  if (d.length > lim || d.kernel > lim || d.pad_left > lim || d.pad_right > lim)
+  if (d.length > lim || d.kernel > lim || d.pad_left > lim || d.pad_right > lim || e.src_up > lim || e.tap_dil > lim ||
+      e.out_step > lim)
     return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of more than 2^30 samples are not addressed by the long-filter kernels");
-  const int64_t Lp = d.length + d.pad_left + d.pad_right;
-  if (d.kernel > Lp)
-    return fail(FC_ERR_INVALID, "kernel (%lld taps) is longer than the padded row (%lld samples)", (long long)d.kernel, (long long)Lp);
-  const int64_t full = Lp - d.kernel + 1;
+  if (e.pad_mode == PAD_REFLECT && (d.pad_left >= d.length || d.pad_right >= d.length))
+    return fail(FC_ERR_INVALID, "reflect padding (%lld, %lld) must be smaller than the input size (%lld)", (long long)d.pad_left,
+                (long long)d.pad_right, (long long)d.length);
+  if (e.pad_mode == PAD_CIRCULAR && (d.pad_left > d.length || d.pad_right > d.length))
+    return fail(FC_ERR_INVALID, "circular padding (%lld, %lld) must not exceed the input size (%lld)", (long long)d.pad_left,
+                (long long)d.pad_right, (long long)d.length);
+  const int64_t up = e.src_up, dil = e.tap_dil, step = e.out_step;
+  const int64_t span = up * (d.length - 1) + 1;          // positions from the first sample of the data to the last
+  const int64_t Lp = span + d.pad_left + d.pad_right;
+  const int64_t kext = dil * (d.kernel - 1) + 1;
+  if (kext > Lp) {
+    if (dil == 1)
+      return fail(FC_ERR_INVALID, "kernel (%lld taps) is longer than the padded row (%lld samples)", (long long)d.kernel, (long long)Lp);
+    return fail(FC_ERR_INVALID, "kernel (%lld taps, %lld samples at dilation %lld) is longer than the padded row (%lld samples)",
+                (long long)d.kernel, (long long)kext, (long long)dil, (long long)Lp);
+  }
+  const int64_t full = (Lp - kext) / step + 1;
   if (d.out_keep > full)
     return fail(FC_ERR_INVALID, "out_keep (%lld) exceeds the output length %lld", (long long)d.out_keep, (long long)full);
   LongGeom g{};
   g.B = d.batch; g.Cin = d.in_channels; g.Cout = d.out_channels; g.G = d.groups;
   g.Cig = g.Cin / g.G; g.Cog = g.Cout / g.G; g.L = d.length; g.K = d.kernel;
   g.nout = d.out_keep ? d.out_keep : full;
-  // tap k (of u) meets the data for some kept output iff  pad_left - nout + 1 <= k <= pad_left + L - 1
-  const int64_t klo = std::max<int64_t>(0, d.pad_left - g.nout + 1);
-  const int64_t khi = std::min<int64_t>(d.kernel - 1, d.pad_left + d.length - 1);
+  g.pad_mode = e.pad_mode; g.up = up; g.dil = dil; g.step = step;
+  int64_t klo = 0, khi = d.kernel - 1;
+  if (e.pad_mode == PAD_CONSTANT) {
+    // tap k (of u) can meet the data for some kept output only if
+    //   pad_left - step*(nout - 1) <= dil*k <= pad_left + span - 1
+    // (with step = dil = up = 1 exactly the taps that do; otherwise a superset of them)
+    const int64_t lo = d.pad_left - step * (g.nout - 1);
+    klo = lo > 0 ? (lo + dil - 1) / dil : 0;
+    khi = std::min<int64_t>(d.kernel - 1, (d.pad_left + span - 1) / dil);
+  } else {
+    g.mpadl = d.pad_left; g.mpadr = d.pad_right;     // every position of the padded row holds a sample: no tap is dropped
+  }
   if (khi < klo) {               // every kept output sees padding only: one tap against a row that reads as zero, y = bias
     g.keff = 1; g.tap0 = 0; g.tstep = 1;
     g.padl = kMaxN + 1;          // the data lies past every position of the transform
   } else {
     g.keff = khi - klo + 1;
-    g.padl = d.pad_left - klo;
+    g.padl = d.pad_left - dil * klo;
     g.tap0 = d.flip ? d.kernel - 1 - klo : klo;
     g.tstep = d.flip ? -1 : 1;
   }
-  g.need = g.nout + g.keff - 1;
+  g.need = step * (g.nout - 1) + dil * (g.keff - 1) + 1;
   if (g.need > kMaxN)
     return fail(FC_ERR_UNSUPPORTED, "the row needs a transform of %lld points; the long-filter path stops at 2^24 = %lld "
                 "(4096 x 4096)", (long long)g.need, (long long)kMaxN);
@@ -189,6 +223,10 @@ LongArgs base_args(const fc_long_plan& p) {
   a.tap0 = (int)g.tap0; a.tstep = (int)g.tstep; a.keff = (int)g.keff; a.K = (int)g.K;
   a.nout = (int)g.nout;
   a.scale = (float)(1.0 / (double)g.N);
+  a.pad_mode = g.pad_mode; a.mpadl = (int)g.mpadl; a.mpadr = (int)g.mpadr;
+  a.src_up = (int)g.up;
+  a.kpos = (int)(g.dil * (g.keff - 1) + 1);
+  a.d_up = make_fastdiv((unsigned)g.up); a.d_tdil = make_fastdiv((unsigned)g.dil); a.d_ostep = make_fastdiv((unsigned)g.step);
   return a;
 }
 
@@ -209,22 +247,28 @@ int io_code(int dtype, const char* what, int* code) {
 
 extern "C" {
 
-int fc_long_geometry(const fc_long_desc* desc, int64_t info[8]) {
+int fc_long_geometry(const fc_long_desc* desc, int64_t info[8]) { return fc_long_geometry_ext(desc, nullptr, info); }
+
+int fc_long_geometry_ext(const fc_long_desc* desc, const fc_long_ext* ext, int64_t info[8]) {
   if (!info) return fail(FC_ERR_INVALID, "null argument");
   LongGeom g;
-  const int st = long_geometry(desc, &g);
+  const int st = long_geometry(desc, ext, &g);
   if (st != FC_OK) return st;
   fill_info(g, info);
   return FC_OK;
 }
 
 int fc_long_plan_create(const fc_long_desc* desc, fc_long_plan** out_plan) {
+  return fc_long_plan_create_ext(desc, nullptr, out_plan);
+}
+
+int fc_long_plan_create_ext(const fc_long_desc* desc, const fc_long_ext* ext, fc_long_plan** out_plan) {
   if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
   (void)hipGetLastError();
   *out_plan = nullptr;
   std::unique_ptr<fc_long_plan> p(new fc_long_plan());
   p->d = *desc;
-  int st = long_geometry(desc, &p->g);
+  int st = long_geometry(desc, ext, &p->g);
   if (st != FC_OK) return st;
   p->cols = find_long(p->g.N1);
   p->rows = find_long(p->g.N2);
@@ -258,8 +302,10 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
   int wio = 0;
   if (int e = io_code(weight_dtype, "weight", &wio)) return e;
   const size_t wes = wio ? 2 : 4;
-  const auto cols_fwd = wio ? plan->cols->cols_fwd_h16 : plan->cols->cols_fwd;
   const LongGeom& g = plan->g;
+  const LongImpl& c = *plan->cols;
+  // (the mapped build only where the taps are spread)
+  const auto cols_fwd = g.dil > 1 ? (wio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (wio ? c.cols_fwd_h16 : c.cols_fwd);
   hipStream_t st = (hipStream_t)hip_stream;
   // the filter rows go through the workspace a chunk at a time (it holds at least Cin + Cout >= 2 rows of N points)
   const int64_t rows_total = g.Cout * g.Cig;
@@ -293,9 +339,12 @@ int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, con
   int xio = 0, yio = 0;
   if (int e = io_code(x_dtype, "x", &xio)) return e;
   if (int e = io_code(y_dtype, "y", &yio)) return e;
-  const auto cols_fwd = xio ? plan->cols->cols_fwd_h16 : plan->cols->cols_fwd;
-  const auto cols_inv = yio ? plan->cols->cols_inv_h16 : plan->cols->cols_inv;
   const LongGeom& g = plan->g;
+  const LongImpl& c = *plan->cols;
+  // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped)
+  const bool map_in = g.pad_mode != PAD_CONSTANT || g.up > 1, map_out = g.step > 1;
+  const auto cols_fwd = map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
+  const auto cols_inv = map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
   hipStream_t st = (hipStream_t)hip_stream;
   for (int64_t s = 0; s < g.slabs; ++s) {
     const int64_t pair0 = s * g.slab_pairs;

@@ -20,9 +20,15 @@
 // two element types of a launch are independent (src_io, y_io); W1, W2 and the spectrum are float32 always, so the result
 // has the bits of: widen, run the float32 kernels, round.
 //
+// The two column kernels come in a plain and a mapped build (MAP).  The plain build is the zero-padded, stride-1,
+// dilation-1 primitive; the mapped build of long_cols_fwd reads the signal through a padding mode (reflect / replicate /
+// circular, the maps of axis_map.hpp) or spread over a grid of src_up, and the taps spread over a grid of tap_dil; the
+// mapped build of long_cols_inv keeps every out_step-th sample of the stride-1 result.  The host picks per launch.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
+#include "axis_map.hpp"
 #include "nd_passes.hpp"
 
 namespace fc {
@@ -54,6 +60,13 @@ struct LongArgs {
   float scale;           // 1 / N (rows mode 1)
   FastDiv d_nblk, d_c, d_nob, d_g;   // unit maps (filled by the dispatcher)
   int src_io, y_io;      // element types of src and of y (fc_dtype: 0 float32, 2 float16, 3 bfloat16; wave-uniform, Io<IO>)
+  // the mapped builds only (wave-uniform):
+  int pad_mode;          // PadMode of the signal row
+  int mpadl, mpadr;      // positions before / behind the data that the mode fills (0 with PAD_CONSTANT)
+  int src_up;            // signal: row position p holds x[(p - padl) / src_up] where that divides
+  int kpos;              // filter: positions of the row that hold taps, tap_dil * (keff - 1) + 1
+  FastDiv d_up, d_tdil;  // src_up and tap_dil: position p of a filter row holds taps[tap0 + tstep * (p / tap_dil)]
+  FastDiv d_ostep;       // out_step: sample t of the stride-1 result is y[t / out_step] where that divides
 };
 
 __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m) {
@@ -63,7 +76,7 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   const Io<IO> io(a.src_io);
@@ -103,9 +116,33 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
     const auto offset = [&](int u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
       const int p = (n1 << a.lgN2) + n20 + r;
-      const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
-      const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
-      return ok ? (unsigned)s * ES : 0x80000000u;
+      if constexpr (!MAP) {
+        const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
+        const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
+        return ok ? (unsigned)s * ES : 0x80000000u;
+      } else {
+        // (every branch below is wave-uniform: it tests launch arguments)
+        int s;
+        bool ok;
+        if (a.from_kernel) {
+          const unsigned q = fdiv((unsigned)p, a.d_tdil);
+          ok = p < a.kpos && q * a.d_tdil.d == (unsigned)p;
+          s = a.tap0 + a.tstep * (int)q;
+        } else if (a.src_up > 1) {
+          const int pos = p - a.padl;
+          const unsigned q = fdiv((unsigned)pos, a.d_up);
+          ok = pos >= 0 && q * a.d_up.d == (unsigned)pos && q < len;
+          s = (int)q;
+        } else {
+          const int pos = p - a.padl, n = (int)len;
+          ok = pos >= -a.mpadl && pos < n + a.mpadr;
+          s = pos;
+          if (a.pad_mode == PAD_REFLECT) s = pos < 0 ? -pos : (pos >= n ? 2 * (n - 1) - pos : pos);
+          else if (a.pad_mode == PAD_REPLICATE) s = pos < 0 ? 0 : (pos >= n ? n - 1 : pos);
+          else if (a.pad_mode == PAD_CIRCULAR) s = pos < 0 ? pos + n : (pos >= n ? pos - n : pos);
+        }
+        return ok ? (unsigned)s * ES : 0x80000000u;
+      }
     };
     if constexpr (IO == IO_F32) {
 #pragma unroll
@@ -254,7 +291,7 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   const Io<IO> io(a.y_io);
@@ -312,7 +349,13 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
     const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
     const f2 z = lds[r * LSEQP + G::nat(n1)];
     const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
-    const unsigned off = t < (unsigned)a.nout ? t * ES : 0x80000000u;     // (samples past the kept window: dropped)
+    unsigned off;
+    if constexpr (!MAP) {
+      off = t < (unsigned)a.nout ? t * ES : 0x80000000u;     // (samples past the kept window: dropped)
+    } else {
+      const unsigned q = fdiv(t, a.d_ostep);                 // (and those between the kept ones)
+      off = (q * a.d_ostep.d == t && q < (unsigned)a.nout) ? q * ES : 0x80000000u;
+    }
     io.store(z.x + b, o0, off, 0);
     io.store(z.y + b, o1, has1 ? off : 0x80000000u, 0);
   }
@@ -327,6 +370,11 @@ struct LongImpl {
   // the 16-bit builds of the column passes: float16 and bfloat16 sources (a.src_io) / outputs (a.y_io)
   hipError_t (*cols_fwd_h16)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*cols_inv_h16)(const LongArgs& a, long long rows, hipStream_t st);
+  // the mapped builds of the four (padding mode, src_up, tap_dil / out_step)
+  hipError_t (*cols_fwd_map)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_map)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_fwd_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

@@ -369,10 +369,14 @@ LONG_MAX_POINTS = 1 << 24         # longest transform of the long-filter path (4
 
 
 def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int, pad_right: int, flip: bool,
-               out_keep: int, has_bias: bool):
-    """Cached long-filter plan (``fc_long_plan``) for a signal (B, Cin, L) against ``taps`` taps per filter row."""
+               out_keep: int, has_bias: bool, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1, out_step: int = 1):
+    """Cached long-filter plan (``fc_long_plan``) for a signal (B, Cin, L) against ``taps`` taps per filter row.  The four
+    keywords are the words of ``fc_long_ext``; a plan that leaves them at their defaults keeps the 12-field key."""
     key = ("long", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
            int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)))
+    ext = (int(pad_mode), int(src_up), int(tap_dil), int(out_step))
+    if ext != _native.LONG_EXT_DEFAULT:
+        key += ext
     index = _device_index(signal.device)
     plan = _native.lookup_plan(index, key)
     if plan is None:
@@ -383,10 +387,12 @@ def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int,
 
 def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: int, pad_right: int, flip: bool,
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
-              out_dtype: Optional[torch.dtype] = None) -> Tensor:
+              out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
+              out_step: int = 1) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
-    y[b, o, t] = bias[o] + sum_i sum_k u[o, i, k] * xpad[b, (g, i), t + k] for t < out_keep (0: all), u = the taps in
-    tensor order or flipped.
+    y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
+    u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
+    grid of ``src_up`` between zero paddings.
 
     ``signal`` and ``kernel`` are float32, float16 or bfloat16, each on its own: the kernels read them where they lie and
     widen as they load.  The result has ``out_dtype`` (default: the signal's; the weight gradient asks for float32 from
@@ -395,7 +401,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
     signal = signal.detach().contiguous()
     out_dtype = signal.dtype if out_dtype is None else out_dtype
     plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
-                      bias is not None)
+                      bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)
     bias_c = bias.detach().float().contiguous() if bias is not None else None
@@ -408,7 +414,17 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
     return out
 
 
-def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal):
+def _long_int(name: str, value) -> int:
+    """``stride`` / ``dilation`` of the 1-D long path: an int or a 1-tuple, at least 1."""
+    if isinstance(value, (tuple, list)) and len(value) == 1:
+        value = value[0]
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"{name} must be an int >= 1, got {value!r}")
+    return int(value)
+
+
+def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal, stride=1, dilation=1,
+                   padding_mode: str = "constant"):
     """Argument checks of ``fft_long_conv`` (ValueError, before any device call) -> (pad_left, pad_right, points the row
     needs)."""
     if signal.ndim != 3 or kernel.ndim != 3:
@@ -416,6 +432,10 @@ def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal
                          f"got shapes {tuple(signal.shape)} and {tuple(kernel.shape)}")
     if not isinstance(groups, int) or groups < 1:
         raise ValueError(f"groups must be a positive int, got {groups!r}")
+    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
+    if padding_mode not in _native.PAD_MODES:
+        raise ValueError(f"unknown padding_mode {padding_mode!r}; expected one of constant/zeros/reflect/replicate/circular")
+    mode = _native.PAD_MODES[padding_mode]
     cin, cout, taps, length = int(signal.shape[1]), int(kernel.shape[0]), int(kernel.shape[2]), int(signal.shape[2])
     if cin % groups or cout % groups or int(kernel.shape[1]) * groups != cin:
         raise ValueError(f"channel mismatch: signal has {cin} channels, kernel is {tuple(kernel.shape)} with groups={groups} "
@@ -424,16 +444,22 @@ def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal
         raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
     if length < 1 or taps < 1 or signal.shape[0] < 1:
         raise ValueError("batch, length and taps must be positive")
+    extent = dilation * (taps - 1) + 1
     if causal:
         if not (isinstance(padding, int) and padding == 0):
             raise ValueError(f"causal=True pads the row itself (taps - 1 zeros in front): padding must be 0, got {padding!r}")
-        return taps - 1, 0, length + min(taps, length) - 1
+        if mode != 0:
+            raise ValueError(f"causal=True pads the row itself with zeros: padding_mode must be 'constant', got {padding_mode!r}")
+        met = min(taps, (length - 1) // dilation + 1)      # taps at a lag of L or more never reach the output
+        return extent - 1, 0, length + dilation * (met - 1)
     if isinstance(padding, str):
         if padding == "valid":
             pad_left = pad_right = 0
         elif padding == "same":
-            pad_left = (taps - 1) // 2
-            pad_right = taps - 1 - pad_left
+            if stride != 1:
+                raise ValueError("padding='same' is not supported for strided convolutions")
+            pad_left = (extent - 1) // 2
+            pad_right = extent - 1 - pad_left
         else:
             raise ValueError(f"invalid padding string {padding!r}; expected 'same' or 'valid'")
     else:
@@ -442,21 +468,30 @@ def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal
         if not isinstance(padding, int) or padding < 0:
             raise ValueError(f"padding must be a non-negative int, 'same' or 'valid', got {padding!r}")
         pad_left = pad_right = int(padding)
-    if taps > length + pad_left + pad_right:
-        raise ValueError(f"kernel ({taps} taps) is longer than the padded row ({length + pad_left + pad_right} samples)")
+    if extent > length + pad_left + pad_right:
+        at = "" if dilation == 1 else f", {extent} samples at dilation {dilation}"
+        raise ValueError(f"kernel ({taps} taps{at}) is longer than the padded row ({length + pad_left + pad_right} samples)")
+    if mode == 1 and max(pad_left, pad_right) >= length:
+        raise ValueError(f"reflect padding ({max(pad_left, pad_right)}) must be smaller than the input size ({length})")
+    if mode == 3 and max(pad_left, pad_right) > length:
+        raise ValueError(f"circular padding ({max(pad_left, pad_right)}) must not exceed the input size ({length})")
     return pad_left, pad_right, length + pad_left + pad_right
 
 
 def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
-                  causal: bool = False) -> Tensor:
+                  causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant") -> Tensor:
     """1-D convolution with a filter as long as the row: ONE transform over the whole padded row (as the reference does,
     functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
 
     ``signal`` (B, Cin, L), ``kernel`` (Cout, Cin/groups, K), ``bias`` (Cout,) or None, on a ROCm device, all three float32,
-    float16 or bfloat16; stride 1, dilation 1, zero padding.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, padding=padding, groups=groups)``
-    (cross-correlation; ``padding`` an int, 'same' or 'valid'), output length L + 2*padding - K + 1.  ``causal=True``
-    (``padding`` must be 0): y[b, o, t] = bias[o] + sum_i sum_{s <= min(t, K-1)} kernel[o, i, s] * signal[b, (g, i), t - s],
-    output length L; K may exceed L.  Differentiable in signal, kernel and bias.
+    float16 or bfloat16.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, stride, padding, dilation, groups,
+    padding_mode)`` (cross-correlation; ``padding`` an int, 'same' or 'valid'; ``padding_mode`` constant | reflect |
+    replicate | circular), output length (L + 2*padding - dilation*(K-1) - 1) // stride + 1.  ``causal=True`` (``padding``
+    must be 0 and ``padding_mode`` constant):
+    y[b, o, j] = bias[o] + sum_i sum_k kernel[o, i, k] * signal[b, (g, i), stride*j - dilation*k] over the taps with
+    dilation*k <= stride*j, output length ceil(L / stride); K may exceed L.  The stride only skips outputs, the dilation
+    only spreads the taps inside the one transform: neither a zero-stuffed kernel nor a padded copy of the row exists.
+    Differentiable in signal, kernel and bias.
 
     float16 / bfloat16 tensors are read and written by the kernels themselves: float32 arithmetic, the signal and the
     taps widened as they are loaded, the output rounded once as it is stored, so the result (and, in training, each
@@ -466,11 +501,13 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     Rows whose padded length is at most 4096 run the ``fft_conv`` kernels; a row that needs more than 2**24 points raises
     ``NotImplementedError``.  float64 tensors and tensors of different dtypes are not taken by this path
     (``TypeError``)."""
-    return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None)
+    return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode)
 
 
-def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum):
-    pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal)
+def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum, stride=1, dilation=1,
+                        padding_mode="constant"):
+    pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal, stride, dilation, padding_mode)
+    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
     if need > LONG_MAX_POINTS:
         raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
                                   f"2**24 = {LONG_MAX_POINTS}")
@@ -481,18 +518,26 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum)
     if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
         # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out (what a caller would write by hand)
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
-                                  causal, None)
+                                  causal, None, stride, dilation, padding_mode)
         return out.to(signal.dtype)
     if need <= LONG_HANDOFF_POINTS:
         if not causal:
-            return _fft_conv_impl(signal, kernel, bias, 1, padding, 1, groups, "constant", None)
-        taps = min(int(kernel.shape[2]), int(signal.shape[2]))     # taps past L - 1 never reach the output
-        padded = torch.nn.functional.pad(signal, (taps - 1, 0))
-        return _fft_conv_impl(padded, kernel[..., :taps].flip(-1), bias, 1, 0, 1, groups, "constant", None)
+            return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
+        # taps at a lag of L or more never reach the output
+        taps = min(int(kernel.shape[2]), (int(signal.shape[2]) - 1) // dilation + 1)
+        padded = torch.nn.functional.pad(signal, (dilation * (taps - 1), 0))
+        return _fft_conv_impl(padded, kernel[..., :taps].flip(-1), bias, stride, 0, dilation, groups, "constant", None)
     if _needs_grad(signal, kernel, bias):
         from .autograd import FFTLongConvFunction
-        return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum)
-    return _long_run(signal, kernel, bias, pad_left, pad_right, causal, signal.shape[2] if causal else 0, groups, spectrum)
+        return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum,
+                                         stride, dilation, padding_mode)
+    return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
+                     spectrum, pad_mode=_native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
+
+
+def _long_keep(length: int, causal: bool, stride: int) -> int:
+    """``out_keep`` of the forward plan: ceil(L / stride) outputs of the causal form, all of them (0) otherwise."""
+    return -(-int(length) // stride) if causal else 0
 
 
 _LONG_DTYPES = (torch.float32,) + _LOW_PRECISION

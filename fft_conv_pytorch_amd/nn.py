@@ -181,18 +181,23 @@ class FFTConvTranspose3d(_FFTConvTransposeForward, nn.ConvTranspose3d):
 
 
 class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
-    """``nn.Conv1d`` (stride 1, dilation 1, zero padding; state_dict = weight, bias) whose forward is
+    """``nn.Conv1d`` (same parameters and attributes, so state_dict, deepcopy and pickle interchange with ``nn.Conv1d`` and
+    ``FFTConv1d``) whose forward is
     ``fft_long_conv``: one transform over the whole padded row, for filters as long as the row.  ``causal=True``
-    computes y[t] = sum_s weight[s] * x[t - s] (output length L, ``padding`` must be 0).  The kernel spectrum is cached
+    computes y[j] = sum_k weight[k] * x[stride*j - dilation*k] (output length ceil(L / stride); ``padding`` must be 0 and
+    ``padding_mode`` 'zeros').  ``stride``, ``dilation`` and ``padding_mode`` are trailing keyword arguments, stored as
+    ``nn.Conv1d`` stores them.  The kernel spectrum is cached
     under the rules of ``_SpectrumCache``, for a float32 module and for one in float16 / bfloat16 (``module.bfloat16()``:
     the kernels read the 16-bit weight and signal and write a 16-bit output; the cached spectrum stays float32)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
-                 dtype=None):
+                 dtype=None, *, stride=1, dilation=1, padding_mode="zeros"):
         if causal and not (isinstance(padding, int) and padding == 0):
             raise ValueError("causal=True pads the row itself: padding must be 0")
-        super().__init__(in_channels, out_channels, kernel_size, stride=1, padding=padding, dilation=1, groups=groups,
-                         bias=bias, padding_mode="zeros", device=device, dtype=dtype)
+        if causal and padding_mode != "zeros":
+            raise ValueError("causal=True pads the row itself with zeros: padding_mode must be 'zeros'")
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+                         groups=groups, bias=bias, padding_mode=padding_mode, device=device, dtype=dtype)
         self.causal = bool(causal)
 
     def extra_repr(self):
@@ -200,13 +205,18 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
 
     def forward(self, signal: Tensor):
         padding = self.padding if isinstance(self.padding, str) else int(self.padding[0])
+        stride, dilation = int(self.stride[0]), int(self.dilation[0])
+        padding_mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
         weight, bias = self.weight, self.bias
-        pad_left, pad_right, need = F_._long_geometry(signal, weight, bias, padding, self.groups, self.causal)
+        pad_left, pad_right, need = F_._long_geometry(signal, weight, bias, padding, self.groups, self.causal, stride,
+                                                      dilation, padding_mode)
         spectrum = None
         if (F_.LONG_HANDOFF_POINTS < need <= F_.LONG_MAX_POINTS and signal.is_cuda and weight.is_cuda
                 and signal.device == weight.device and signal.dtype == weight.dtype
                 and (signal.dtype == torch.float32 or F_._half_native(signal, weight, bias))):
             plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
-                                 signal.shape[2] if self.causal else 0, bias is not None)
+                                 F_._long_keep(signal.shape[2], self.causal, stride), bias is not None,
+                                 pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
             spectrum = self._cached_spectrum(plan)
-        return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum)
+        return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
+                                      padding_mode)

@@ -192,7 +192,7 @@ long long fc_debug_grid(const fc_plan* plan);
 int fc_debug_route(const fc_plan* plan, int32_t route[16]);
 
 /* ---- Long filters (ABI 7 extension: new entry points only, nothing that existed changes): a 1-D filter as long as the row, functional.py:66-75 with one transform over the whole
- * padded row instead of overlap-save tiles.  float32 (float16 / bfloat16 tensors: the _io calls below), stride 1, dilation 1, zero padding.  The plan computes
+ * padded row instead of overlap-save tiles.  float32 (float16 / bfloat16 tensors: the _io calls below); stride, dilation and the padding modes: the _ext calls below.  The plan computes
  *   y[b][(g,o)][t] = bias[(g,o)] + sum_i sum_k u[(g,o)][i][k] * xpad[b][(g,i)][t + k],   0 <= t < out_keep,
  * xpad = x with pad_left zeros in front and pad_right behind, u[k] = w[k] (flip 0, cross-correlation) or w[K-1-k]
  * (flip 1).  The causal long convolution y[t] = sum_s h[s] x[t-s] is pad_left = K-1, pad_right = 0, flip = 1,
@@ -249,6 +249,31 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
                                  void* workspace, void* hip_stream);
 int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, const void* spectrum, const float* bias,
                         void* y, int y_dtype, void* workspace, void* hip_stream);
+
+/* Stride, dilation and padding modes (ABI 7 extension: new entry points only; fc_long_desc keeps its 80 bytes and the two
+ * calls above that take it are these with ext = NULL, which is {0, 1, 1, 1}).  With the extension the plan computes
+ *   y[b][(g,o)][j] = bias[(g,o)] + sum_i sum_k u[(g,o)][i][k] * xrow[b][(g,i)][out_step*j + tap_dil*k],   0 <= j < nout,
+ * nout = out_keep, or floor((Lp - tap_dil*(K-1) - 1) / out_step) + 1 when out_keep is 0, Lp the length of xrow:
+ *   pad_mode   fc PadMode code (0 constant, 1 reflect, 2 replicate, 3 circular): position p of xrow inside
+ *              [0, pad_left + L + pad_right) holds x[map(p - pad_left)], map the reflect / replicate / circular map of the
+ *              mode, and zero where the mode is constant and the difference lies outside [0, L).  reflect: both paddings
+ *              < L; circular: both <= L.
+ *   src_up     u >= 1: position p holds x[(p - pad_left) / u] where the difference is a non-negative multiple of u with a
+ *              quotient < L, zero elsewhere; Lp = pad_left + u*(L-1) + 1 + pad_right.  With pad_mode constant only
+ *              (FC_ERR_INVALID otherwise).  This is the row the gradient of a strided convolution reads.
+ *   tap_dil    d >= 1: the taps lie d positions apart, the filter covers d*(K-1) + 1 positions.
+ *   out_step   s >= 1: kept output j is sample s*j of the stride-1 result; y is compact, (B, Cout, nout), every sample
+ *              written.
+ * The cyclic length is out_step*(nout-1) + tap_dil*(taps that are read - 1) + 1; with pad_mode constant, taps that cannot
+ * meet the data for any kept output are not read (exactly those when u = d = s = 1, as before), with another mode all are.
+ * fc_long_plan_info, the transform and forward calls, the slabs and the workspace rules are those of any long plan. */
+typedef struct fc_long_ext {
+  int32_t pad_mode;
+  int32_t src_up, tap_dil, out_step;
+} fc_long_ext;
+
+int fc_long_geometry_ext(const fc_long_desc* desc, const fc_long_ext* ext, int64_t info[8]);
+int fc_long_plan_create_ext(const fc_long_desc* desc, const fc_long_ext* ext, fc_long_plan** out_plan);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ EXPORTS = (
     "fc_long_geometry", "fc_long_plan_create", "fc_long_plan_destroy", "fc_long_plan_info", "fc_long_transform_kernel",
     "fc_long_forward", "fc_long_transform_kernel_io", "fc_long_forward_io",
     "fc_long_geometry_ext", "fc_long_plan_create_ext",
+    "fc_long_geometry_kind", "fc_long_plan_create_kind", "fc_long_plan_kind",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -73,6 +74,9 @@ class FcLongExt(ctypes.Structure):
 
 
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
+FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans only)
+# enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
+LONG_REAL, LONG_COMPLEX, LONG_CONJ_SIGNAL, LONG_CONJ_TAPS = 0, 1, 2, 4
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
@@ -157,6 +161,13 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_geometry_ext.restype = i32
         lib.fc_long_plan_create_ext.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), ctypes.POINTER(vp)]
         lib.fc_long_plan_create_ext.restype = i32
+        lib.fc_long_geometry_kind.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i32, i64x8]
+        lib.fc_long_geometry_kind.restype = i32
+        lib.fc_long_plan_create_kind.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i32,
+                                                 ctypes.POINTER(vp)]
+        lib.fc_long_plan_create_kind.restype = i32
+        lib.fc_long_plan_kind.argtypes = [vp]
+        lib.fc_long_plan_kind.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -341,8 +352,9 @@ class Plan:
 def long_desc(key: Tuple) -> FcLongDesc:
     """``struct fc_long_desc`` of a long-plan key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_keep, flip,
     has_bias), or those eleven words of an extended key."""
-    if len(key) not in (11, 15):
-        raise ValueError(f"a long-plan key has 11 words, or 15 with (pad_mode, src_up, tap_dil, out_step); got {len(key)}")
+    if len(key) not in (11, 15, 16):
+        raise ValueError(f"a long-plan key has 11 words, 15 with (pad_mode, src_up, tap_dil, out_step), or 16 with those and "
+                         f"the kind of a complex plan; got {len(key)}")
     d = FcLongDesc()
     (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_keep,
      d.flip, d.has_bias) = (int(v) for v in key[:11])
@@ -350,11 +362,16 @@ def long_desc(key: Tuple) -> FcLongDesc:
 
 
 def long_ext(key: Tuple) -> FcLongExt:
-    """``struct fc_long_ext`` of a long-plan key: its last four words (pad_mode, src_up, tap_dil, out_step) when it has 15,
-    the defaults (constant, 1, 1, 1) when it has 11."""
+    """``struct fc_long_ext`` of a long-plan key: words 11 to 14 (pad_mode, src_up, tap_dil, out_step) when it has 15 or
+    16, the defaults (constant, 1, 1, 1) when it has 11."""
     e = FcLongExt()
-    e.pad_mode, e.src_up, e.tap_dil, e.out_step = (int(v) for v in (key[11:] if len(key) == 15 else LONG_EXT_DEFAULT))
+    e.pad_mode, e.src_up, e.tap_dil, e.out_step = (int(v) for v in (key[11:15] if len(key) >= 15 else LONG_EXT_DEFAULT))
     return e
+
+
+def long_kind(key: Tuple) -> int:
+    """``fc_long_kind`` bits of a long-plan key: its sixteenth word (a complex plan always has sixteen), else real."""
+    return int(key[15]) if len(key) == 16 else LONG_REAL
 
 
 def long_geometry(key: Tuple) -> dict:
@@ -362,7 +379,7 @@ def long_geometry(key: Tuple) -> dict:
     lib = load_library()
     info = (ctypes.c_int64 * 8)()
     desc = long_desc(key)
-    st = lib.fc_long_geometry_ext(ctypes.byref(desc), ctypes.byref(long_ext(key)), ctypes.byref(info))
+    st = lib.fc_long_geometry_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key), ctypes.byref(info))
     if st != FC_OK:
         _raise(lib, st)
     return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
@@ -372,14 +389,16 @@ class LongPlan:
     """Owns one ``fc_long_plan`` (long-filter path; immutable after creation): created on the CURRENT HIP device, which the
     caller sets to ``device_index``.  Quacks like ``Plan`` where ``KernelSpectrum`` and ``new_workspace`` look.
 
-    The plan does not depend on the element types of the tensors: ``transform_kernel`` and ``forward`` name them per call
-    as fc_dtype codes (0 float32, 2 float16, 3 bfloat16; default float32).  Spectrum, workspace and bias are float32."""
+    The plan does not depend on the element types of real tensors: ``transform_kernel`` and ``forward`` name them per call
+    as fc_dtype codes (0 float32, 2 float16, 3 bfloat16; default float32).  Spectrum, workspace and bias are float32.
+    A complex plan (a key of 16 words, ``complex`` True) takes code 4, complex64, for every tensor and a complex64 bias."""
 
     def __init__(self, key: Tuple, device_index: int = 0):
         lib = load_library()
         handle = ctypes.c_void_p()
         desc = long_desc(key)
-        st = lib.fc_long_plan_create_ext(ctypes.byref(desc), ctypes.byref(long_ext(key)), ctypes.byref(handle))
+        st = lib.fc_long_plan_create_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key),
+                                          ctypes.byref(handle))
         if st != FC_OK:
             _raise(lib, st)
         self._lib, self._h, self.key = lib, handle, key
@@ -390,8 +409,10 @@ class LongPlan:
         self.out_len = self.info["out_len"]
         self.spectrum_bytes = self.info["spectrum_bytes"]
         self.workspace_bytes = self.info["workspace_bytes"]
+        self.kind = int(lib.fc_long_plan_kind(handle))
+        self.complex = bool(self.kind & LONG_COMPLEX)
         import torch
-        self.dtype = self.weight_dtype = torch.float32
+        self.dtype = self.weight_dtype = torch.complex64 if self.complex else torch.float32
 
     def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int,
                          weight_dtype: int = 0):

@@ -385,7 +385,13 @@ class FFTLongConvFunction(torch.autograd.Function):
     float16 / bfloat16 calls run on their 16-bit tensors (autograd saves 16-bit signal and weight): dX reads 16-bit dY
     and the 16-bit transposed weight and is written in 16 bits (with a padding mode to fold: in float32, folded, rounded
     once); dW reads the 16-bit transposed copies of x and dY, comes back float32 and is rounded once; db is summed in
-    float32.  Each gradient has the bits of the float32 cast path."""
+    float32.  Each gradient has the bits of the float32 cast path.
+
+    complex64 calls follow PyTorch's convention for complex gradients with the same three constructions, each one run of
+    the primitive on a complex plan: dX runs dY against conj(weight), dW runs conj(x) as the signal against dY as the
+    filter (K complex lags kept), db is dY summed.  The conjugates are not copies: the plan carries a flag
+    (``conj_kernel`` / ``conj_signal`` of ``F_._long_run``) and ``long_cols_fwd`` flips the sign of the imaginary part as it
+    loads.  A lazily conjugated dY is resolved first."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
@@ -402,7 +408,8 @@ class FFTLongConvFunction(torch.autograd.Function):
         signal, kernel = ctx.saved_tensors
         pad_left, pad_right, flip, g, has_bias, s, d, padding_mode = ctx.cfg
         mode = F_._native.PAD_MODES[padding_mode]
-        grad = grad.detach().contiguous()
+        grad = F_._resolved(grad.detach()).contiguous()
+        cx = signal.dtype == torch.complex64
         B, cin, L = signal.shape
         cout, cig, K = kernel.shape
         cog = cout // g
@@ -422,7 +429,7 @@ class FFTLongConvFunction(torch.autograd.Function):
             else:
                 fold32 = mode != 0 and grad.dtype in F_._LOW_PRECISION
                 dx = F_._long_run(dy, wt, None, lead, max(tail, 0), not flip, keep, g,
-                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d)
+                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d, conj_kernel=cx)
                 if mode != 0:
                     # (_pad_adjoint folds equal paddings: a row padded by the larger one has zero gradient at the rest)
                     p = max(pad_left, pad_right)
@@ -433,7 +440,7 @@ class FFTLongConvFunction(torch.autograd.Function):
             xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
             dyt = grad.permute(1, 0, 2).contiguous()
             du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32, pad_mode=mode,
-                              tap_dil=s, out_step=d).permute(1, 0, 2)
+                              tap_dil=s, out_step=d, conj_signal=cx).permute(1, 0, 2)
             dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             db = _grad_bias(grad).to(kernel.dtype)

@@ -40,7 +40,8 @@ struct LongGeom {
   int64_t up, dil, step;        // src_up, tap_dil, out_step
   int N1, N2;
   int64_t N;
-  int64_t npairs, slab_pairs, slabs;
+  int kind;                     // fc_long_kind bits: complex rows, conjugated reads
+  int64_t npairs, slab_pairs, slabs;      // rows of the transform per channel: batch pairs, or batch items of a complex plan
   int ob;
   size_t spectrum_bytes, workspace_bytes;
 };
@@ -49,8 +50,11 @@ bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 
 
 const fc_long_ext kDefaultExt = {0, 1, 1, 1};
 
-int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, LongGeom* out) {
+int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, LongGeom* out) {
   if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  if (kind & ~(FC_LONG_COMPLEX | FC_LONG_CONJ_SIGNAL | FC_LONG_CONJ_TAPS)) return fail(FC_ERR_INVALID, "unknown long-plan kind %d", kind);
+  const bool cx = (kind & FC_LONG_COMPLEX) != 0;
+  if (!cx && kind) return fail(FC_ERR_INVALID, "long-plan kind %d: conjugated reads go with complex rows (FC_LONG_COMPLEX) only", kind);
   const fc_long_desc& d = *desc;
   const fc_long_ext& e = ext ? *ext : kDefaultExt;
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
@@ -70,6 +74,10 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, LongGeom* ou
   if (d.length > lim || d.kernel > lim || d.pad_left > lim || d.pad_right > lim || e.src_up > lim || e.tap_dil > lim ||
       e.out_step > lim)
     return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of more than 2^30 samples are not addressed by the long-filter kernels");
+  // (8-byte samples: the byte size of a row and every offset in use stay below the 2^31 that reads as zero)
+  const int64_t clim = (int64_t)1 << 28;
+  if (cx && (d.length >= clim || d.kernel >= clim || d.pad_left >= clim || d.pad_right >= clim))
+    return fail(FC_ERR_UNSUPPORTED, "complex rows, filters and paddings of 2^28 samples or more are not addressed by the long-filter kernels");
   if (e.pad_mode == PAD_REFLECT && (d.pad_left >= d.length || d.pad_right >= d.length))
     return fail(FC_ERR_INVALID, "reflect padding (%lld, %lld) must be smaller than the input size (%lld)", (long long)d.pad_left,
                 (long long)d.pad_right, (long long)d.length);
@@ -136,7 +144,8 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, LongGeom* ou
   g.N = (int64_t)g.N1 * g.N2;
   const LongImpl* rows = find_long(g.N2);
   g.ob = rows ? rows->ob : 1;
-  g.npairs = (g.B + 1) / 2;
+  g.kind = kind;
+  g.npairs = cx ? g.B : (g.B + 1) / 2;
   int64_t budget_mb = kDefaultBudgetMB;
   if (const char* env = getenv("FFTCONV_LONG_WS_MB"))
     if (*env && atoll(env) > 0) budget_mb = atoll(env);
@@ -148,8 +157,8 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, LongGeom* ou
   // grids are 32-bit: (blocks per row) x rows
   const int64_t worst = std::max<int64_t>(g.N2 / 2, g.N1 / 2) * std::max<int64_t>(g.slab_pairs * std::max(g.Cin, g.Cout), 1);
   if (worst > 0x7fffffffLL)
-    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch pairs x %lld channels x %lld points exceeds the 2^31 workgroups of one "
-                "launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, (long long)std::max(g.Cin, g.Cout), (long long)g.N);
+    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch %s x %lld channels x %lld points exceeds the 2^31 workgroups of one "
+                "launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, cx ? "items" : "pairs", (long long)std::max(g.Cin, g.Cout), (long long)g.N);
   *out = g;
   return FC_OK;
 }
@@ -227,6 +236,7 @@ LongArgs base_args(const fc_long_plan& p) {
   a.src_up = (int)g.up;
   a.kpos = (int)(g.dil * (g.keff - 1) + 1);
   a.d_up = make_fastdiv((unsigned)g.up); a.d_tdil = make_fastdiv((unsigned)g.dil); a.d_ostep = make_fastdiv((unsigned)g.step);
+  a.conj_src = 0;
   return a;
 }
 
@@ -239,8 +249,26 @@ int io_code(int dtype, const char* what, int* code) {
     case FC_F64:
       return fail(FC_ERR_UNSUPPORTED, "%s is float64: the long-filter path takes float32, float16 and bfloat16 tensors", what);
     default:
-      return fail(FC_ERR_INVALID, "%s has dtype code %d; expected FC_F32 (0), FC_F16 (2) or FC_BF16 (3)", what, dtype);
+      return fail(FC_ERR_INVALID, "%s has dtype code %d; expected FC_F32 (0), FC_F16 (2) or FC_BF16 (3), or FC_C64 (4) on a "
+                  "complex plan", what, dtype);
   }
+}
+
+// the same for a tensor argument of `plan`: a complex plan takes FC_C64 and nothing else, a real plan no FC_C64
+int plan_io_code(const fc_long_plan* plan, int dtype, const char* what, int* code) {
+  const bool cx = (plan->g.kind & FC_LONG_COMPLEX) != 0;
+  if (dtype == FC_C64) {
+    if (!cx)
+      return fail(FC_ERR_INVALID, "%s is complex64 (FC_C64) but the plan is a real plan: a complex plan comes from "
+                  "fc_long_plan_create_kind with FC_LONG_COMPLEX", what);
+    *code = IO_CODE_C64;
+    return FC_OK;
+  }
+  if (int e = io_code(dtype, what, code)) return e;
+  if (cx)
+    return fail(FC_ERR_INVALID, "%s has the real dtype code %d but the plan is a complex plan: it takes FC_C64 (4) tensors only",
+                what, dtype);
+  return FC_OK;
 }
 
 }  // namespace
@@ -250,9 +278,13 @@ extern "C" {
 int fc_long_geometry(const fc_long_desc* desc, int64_t info[8]) { return fc_long_geometry_ext(desc, nullptr, info); }
 
 int fc_long_geometry_ext(const fc_long_desc* desc, const fc_long_ext* ext, int64_t info[8]) {
+  return fc_long_geometry_kind(desc, ext, FC_LONG_REAL, info);
+}
+
+int fc_long_geometry_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, int64_t info[8]) {
   if (!info) return fail(FC_ERR_INVALID, "null argument");
   LongGeom g;
-  const int st = long_geometry(desc, ext, &g);
+  const int st = long_geometry(desc, ext, kind, &g);
   if (st != FC_OK) return st;
   fill_info(g, info);
   return FC_OK;
@@ -263,12 +295,18 @@ int fc_long_plan_create(const fc_long_desc* desc, fc_long_plan** out_plan) {
 }
 
 int fc_long_plan_create_ext(const fc_long_desc* desc, const fc_long_ext* ext, fc_long_plan** out_plan) {
+  return fc_long_plan_create_kind(desc, ext, FC_LONG_REAL, out_plan);
+}
+
+int fc_long_plan_kind(const fc_long_plan* plan) { return plan ? plan->g.kind : -1; }
+
+int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, fc_long_plan** out_plan) {
   if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
   (void)hipGetLastError();
   *out_plan = nullptr;
   std::unique_ptr<fc_long_plan> p(new fc_long_plan());
   p->d = *desc;
-  int st = long_geometry(desc, ext, &p->g);
+  int st = long_geometry(desc, ext, kind, &p->g);
   if (st != FC_OK) return st;
   p->cols = find_long(p->g.N1);
   p->rows = find_long(p->g.N2);
@@ -300,12 +338,14 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
                                 void* workspace, void* hip_stream) {
   if (!plan || !weight || !spectrum || !workspace) return fail(FC_ERR_INVALID, "null argument");
   int wio = 0;
-  if (int e = io_code(weight_dtype, "weight", &wio)) return e;
-  const size_t wes = wio ? 2 : 4;
+  if (int e = plan_io_code(plan, weight_dtype, "weight", &wio)) return e;
+  const bool cx = wio == IO_CODE_C64;
+  const size_t wes = cx ? 8 : (wio ? 2 : 4);
   const LongGeom& g = plan->g;
   const LongImpl& c = *plan->cols;
   // (the mapped build only where the taps are spread)
-  const auto cols_fwd = g.dil > 1 ? (wio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (wio ? c.cols_fwd_h16 : c.cols_fwd);
+  const auto cols_fwd = cx ? (g.dil > 1 ? c.cols_fwd_map_cx : c.cols_fwd_cx)
+                           : g.dil > 1 ? (wio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (wio ? c.cols_fwd_h16 : c.cols_fwd);
   hipStream_t st = (hipStream_t)hip_stream;
   // the filter rows go through the workspace a chunk at a time (it holds at least Cin + Cout >= 2 rows of N points)
   const int64_t rows_total = g.Cout * g.Cig;
@@ -317,6 +357,7 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
     LongArgs a = base_args(*plan);
     a.from_kernel = 1;
     a.src_io = wio;
+    a.conj_src = (g.kind & FC_LONG_CONJ_TAPS) != 0;
     a.src = (const float*)((const char*)weight + (size_t)r0 * g.K * wes);
     a.w1 = (f2*)workspace;
     FC_HIP(cols_fwd(a, n, st));
@@ -337,14 +378,17 @@ int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, con
   if (!plan || !x || !spectrum || !y || !workspace) return fail(FC_ERR_INVALID, "null argument");
   if (plan->d.has_bias && !bias) return fail(FC_ERR_INVALID, "the plan was made with a bias");
   int xio = 0, yio = 0;
-  if (int e = io_code(x_dtype, "x", &xio)) return e;
-  if (int e = io_code(y_dtype, "y", &yio)) return e;
+  if (int e = plan_io_code(plan, x_dtype, "x", &xio)) return e;
+  if (int e = plan_io_code(plan, y_dtype, "y", &yio)) return e;
+  const bool cx = xio == IO_CODE_C64;
   const LongGeom& g = plan->g;
   const LongImpl& c = *plan->cols;
   // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped)
   const bool map_in = g.pad_mode != PAD_CONSTANT || g.up > 1, map_out = g.step > 1;
-  const auto cols_fwd = map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
-  const auto cols_inv = map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
+  const auto cols_fwd = cx ? (map_in ? c.cols_fwd_map_cx : c.cols_fwd_cx)
+                           : map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
+  const auto cols_inv = cx ? (map_out ? c.cols_inv_map_cx : c.cols_inv_cx)
+                           : map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
   hipStream_t st = (hipStream_t)hip_stream;
   for (int64_t s = 0; s < g.slabs; ++s) {
     const int64_t pair0 = s * g.slab_pairs;
@@ -353,6 +397,7 @@ int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, con
     a.pair0 = (int)pair0;
     a.src = (const float*)x; a.bias = bias; a.y = (float*)y;
     a.src_io = xio; a.y_io = yio;
+    a.conj_src = (g.kind & FC_LONG_CONJ_SIGNAL) != 0;
     a.spec = (const f2*)spectrum;
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);

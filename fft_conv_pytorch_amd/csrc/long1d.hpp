@@ -25,6 +25,12 @@
 // circular, the maps of axis_map.hpp) or spread over a grid of src_up, and the taps spread over a grid of tap_dil; the
 // mapped build of long_cols_inv keeps every out_step-th sample of the stride-1 result.  The host picks per launch.
 //
+// Both column kernels also have a complex build (CX, plain and mapped) for complex64 tensors: a row is ONE batch item, a
+// sample one 8-byte (re, im) pair, the bias Cout pairs.  The taps are conjugated as they are loaded, because long_rows
+// stores conj(transform) / N and conj(FFT(conj u))[f] = U[-f] is what the unconjugated product y[t] = sum_k u[k] * z[t + k]
+// needs (for real taps this is what the real builds do).  conj_src conjugates the rows of a launch once more: backward
+// reads conj(x) and conj(w) that way, without a conjugated copy.  long_rows sees rows and units only and is the same.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -67,7 +73,11 @@ struct LongArgs {
   int kpos;              // filter: positions of the row that hold taps, tap_dil * (keff - 1) + 1
   FastDiv d_up, d_tdil;  // src_up and tap_dil: position p of a filter row holds taps[tap0 + tstep * (p / tap_dil)]
   FastDiv d_ostep;       // out_step: sample t of the stride-1 result is y[t / out_step] where that divides
+  // the complex builds only (wave-uniform):
+  int conj_src;          // cols_fwd: the rows of this launch are read conjugated (signal: conj(x); taps: u = conj(w))
 };
+
+constexpr int IO_CODE_C64 = 4;       // fc_dtype code of a launch of a complex build (src_io / y_io)
 
 __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m) {
   const f2 hi = buf_load_f32x2(thi, (m >> kLongLoBits) * 8u, 0);
@@ -76,11 +86,13 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
+  static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
   const Io<IO> io(a.src_io);
-  constexpr unsigned ES = Io<IO>::B;            // bytes per sample of the source rows
+  constexpr unsigned ES = CX ? 8u : Io<IO>::B;  // bytes per sample of the source rows
+  constexpr int EW = CX ? 2 : 1;                // elements of Io<IO>::T per sample
   constexpr int T = G::T;                       // == a.N1
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
@@ -92,19 +104,20 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
   const size_t N = (size_t)a.N1 << a.lgN2;
 
-  // the two real rows of the pair (filter rows: one, the imaginary part stays zero)
+  // the two real rows of the pair (filter rows: one, the imaginary part stays zero); complex build: the one row of item
+  // pair0 + pr
   const typename Io<IO>::T* r0;
   bool has1 = false;
   unsigned len;
   if (a.from_kernel) {
-    r0 = io_ptr<IO>(a.src) + (size_t)row * a.K;
+    r0 = io_ptr<IO>(a.src) + (size_t)row * a.K * EW;
     len = (unsigned)a.K;
   } else {
     unsigned pr;
     const unsigned c = fdivmod(row, a.d_c, &pr);
-    const int b0 = 2 * (a.pair0 + (int)pr);
-    r0 = io_ptr<IO>(a.src) + ((size_t)b0 * a.C + c) * a.L;
-    has1 = b0 + 1 < a.B;
+    const int b0 = CX ? a.pair0 + (int)pr : 2 * (a.pair0 + (int)pr);
+    r0 = io_ptr<IO>(a.src) + ((size_t)b0 * a.C + c) * a.L * EW;
+    has1 = !CX && b0 + 1 < a.B;
     len = (unsigned)a.L;
   }
   const BufRsrc s0 = make_rsrc(r0, len * ES);
@@ -144,7 +157,14 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
         return ok ? (unsigned)s * ES : 0x80000000u;
       }
     };
-    if constexpr (IO == IO_F32) {
+    if constexpr (CX) {
+      // taps are conjugated on load (header), conj_src conjugates the rows of the launch once more: a sign-bit flip
+      const unsigned sign = ((a.from_kernel != 0) != (a.conj_src != 0)) ? 0x80000000u : 0u;
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u] = buf_load_f32x2(s0, offset(u), 0);
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u].y = __uint_as_float(__float_as_uint(val[u].y) ^ sign);
+    } else if constexpr (IO == IO_F32) {
 #pragma unroll
       for (int u = 0; u < P; ++u) {
         const unsigned off = offset(u);
@@ -291,11 +311,13 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
+  static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
   const Io<IO> io(a.y_io);
-  constexpr unsigned ES = Io<IO>::B;            // bytes per sample of y
+  constexpr unsigned ES = CX ? 8u : Io<IO>::B;  // bytes per sample of y
+  constexpr int EW = CX ? 2 : 1;                // elements of Io<IO>::T per sample
   constexpr int T = G::T;                       // == a.N1
   constexpr int LSEQP = SeqLayout<G>::LSEQP;
   static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
@@ -308,8 +330,8 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   const size_t N = (size_t)a.N1 << a.lgN2;
   unsigned pr;
   const unsigned o = fdivmod(row, a.d_c, &pr);
-  const int b0 = 2 * (a.pair0 + (int)pr);
-  const bool has1 = b0 + 1 < a.B;
+  const int b0 = CX ? a.pair0 + (int)pr : 2 * (a.pair0 + (int)pr);      // (complex build: one batch item per row)
+  const bool has1 = !CX && b0 + 1 < a.B;
   f2 wtw[P];
   passA_twiddle_fetch<G>(wtw, tseq, twA);
   {
@@ -338,10 +360,15 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
     for (int k = 0; k < P; ++k) lseq[G::nat(nbase + P * k)] = v[k];
   }
   __syncthreads();
-  float b = a.bias ? a.bias[o] : 0.f;
+  float b = a.bias ? a.bias[o * EW] : 0.f;
   asm volatile("" : "+v"(b));
+  [[maybe_unused]] float bi = 0.f;              // complex build: the bias is Cout (re, im) pairs
+  if constexpr (CX) {
+    bi = a.bias ? a.bias[o * 2 + 1] : 0.f;
+    asm volatile("" : "+v"(bi));
+  }
   // (the bias is added in float32; a 16-bit y is rounded once, at the store)
-  typename Io<IO>::T* y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout;
+  typename Io<IO>::T* y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout * EW;
   const BufRsrc o0 = make_rsrc(y0, (unsigned)a.nout * ES);
   const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, (unsigned)a.nout * ES);
 #pragma unroll
@@ -356,8 +383,12 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
       const unsigned q = fdiv(t, a.d_ostep);                 // (and those between the kept ones)
       off = (q * a.d_ostep.d == t && q < (unsigned)a.nout) ? q * ES : 0x80000000u;
     }
-    io.store(z.x + b, o0, off, 0);
-    io.store(z.y + b, o1, has1 ? off : 0x80000000u, 0);
+    if constexpr (CX) {
+      buf_store_f32x2(mk2(z.x + b, z.y + bi), o0, off, 0);
+    } else {
+      io.store(z.x + b, o0, off, 0);
+      io.store(z.y + b, o1, has1 ? off : 0x80000000u, 0);
+    }
   }
 }
 
@@ -375,6 +406,11 @@ struct LongImpl {
   hipError_t (*cols_inv_map)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*cols_fwd_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*cols_inv_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
+  // the complex builds of the column passes, plain and mapped: complex64 rows, one batch item each (a.src_io / a.y_io 4)
+  hipError_t (*cols_fwd_cx)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_cx)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_fwd_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

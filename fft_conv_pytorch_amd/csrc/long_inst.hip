@@ -1,5 +1,5 @@
-// long_inst.hip -- instantiates the three kernels of long1d.hpp (the two column kernels in four builds each: float32 and
-// 16-bit, one build for float16 and bfloat16, plain and mapped) for ONE tile geometry (P, S): built once per geometry
+// long_inst.hip -- instantiates the three kernels of long1d.hpp (the two column kernels in six builds each: float32,
+// 16-bit, one build for float16 and bfloat16, and complex64, each plain and mapped) for ONE tile geometry (P, S): built once per geometry
 // with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
@@ -68,6 +68,22 @@ hipError_t cols_inv_map_h16(const LongArgs& a, long long rows, hipStream_t st) {
   if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
   return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true>>(a, a.N2 / kNSEQ, rows, st);
 }
+hipError_t cols_fwd_cx(const LongArgs& a, long long rows, hipStream_t st) {
+  if (a.N1 != kT || a.src_io != IO_CODE_C64) return hipErrorInvalidValue;
+  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, false, true>>(a, a.N2 / kNSEQ, rows, st);
+}
+hipError_t cols_inv_cx(const LongArgs& a, long long rows, hipStream_t st) {
+  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
+  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, false, true>>(a, a.N2 / kNSEQ, rows, st);
+}
+hipError_t cols_fwd_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
+  if (a.N1 != kT || a.src_io != IO_CODE_C64) return hipErrorInvalidValue;
+  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true>>(a, a.N2 / kNSEQ, rows, st);
+}
+hipError_t cols_inv_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
+  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
+  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true>>(a, a.N2 / kNSEQ, rows, st);
+}
 
 }  // namespace
 
@@ -75,7 +91,8 @@ hipError_t cols_inv_map_h16(const LongArgs& a, long long rows, hipStream_t st) {
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
   static const LongImpl impl = {kT, kNSEQ, kOB, cols_fwd, rows, cols_inv, cols_fwd_h16, cols_inv_h16,
-                                cols_fwd_map, cols_inv_map, cols_fwd_map_h16, cols_inv_map_h16};
+                                cols_fwd_map, cols_inv_map, cols_fwd_map_h16, cols_inv_map_h16,
+                                cols_fwd_cx, cols_inv_cx, cols_fwd_map_cx, cols_inv_map_cx};
   return &impl;
 }
 

@@ -21,7 +21,8 @@ from .utils import to_ntuple
 __all__ = ["fft_conv", "fft_long_conv", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
 
 
-_DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}      # enum fc_dtype
+_DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
+_CONV_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)      # of fft_conv / fft_conv_transpose plans
 
 
 def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
@@ -30,7 +31,7 @@ def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
         raise RuntimeError(
             f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
             f"(no CPU fallback). Move the tensor to 'cuda'.")
-    if t.dtype != dtype or dtype not in _DTYPE_CODES:
+    if t.dtype != dtype or dtype not in _CONV_DTYPES:
         raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; signal, kernel and bias must share one of "
                         f"float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
                         f"their crossover) or float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
@@ -109,7 +110,7 @@ def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, g
                 f"(need kernel.shape[1] * groups == in_channels and out_channels % groups == 0)")
     if bias is not None and tuple(bias.shape) != (cout,):
         raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
-    dtype = signal.dtype if signal.dtype in _DTYPE_CODES else torch.float32
+    dtype = signal.dtype if signal.dtype in _CONV_DTYPES else torch.float32
     key = (n, int(signal.shape[0]), cin, cout, groups,
            tuple(int(s) for s in signal.shape[2:]), tuple(int(k) for k in kernel.shape[2:]),
            tuple(int(s) for s in stride_), tuple(int(p) for p in padding_), tuple(int(d) for d in dilation_),
@@ -144,9 +145,15 @@ def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
     """Kernel transform (dilate, zero-pad, FFT, conjugate) on the device; rows a2 + a6.  A float16 / bfloat16 plan takes
     a weight of its own dtype (widened to a float32 copy that lives for this call only) or a float32 one.  A long-filter
     plan reads a float16 / bfloat16 weight where it lies (no copy); its spectrum is float32, the bytes of the widened
-    weight's."""
+    weight's.  A complex long plan takes a complex64 weight (a lazy conjugate is resolved first)."""
     io = ()
-    if isinstance(plan, _native.LongPlan) and kernel.dtype in _LOW_PRECISION:
+    if isinstance(plan, _native.LongPlan) and plan.complex:
+        if kernel.dtype != torch.complex64:
+            raise TypeError(f"kernel is {kernel.dtype} but the plan is a complex64 long plan")
+        _require_long_dtype("kernel", kernel, kernel.dtype)
+        kernel = _resolved(kernel.detach()).contiguous()
+        io = (_DTYPE_CODES[kernel.dtype],)
+    elif isinstance(plan, _native.LongPlan) and kernel.dtype in _LOW_PRECISION:
         _require_gpu_f32("kernel", kernel, kernel.dtype)
         kernel = kernel.detach().contiguous()
         io = (_DTYPE_CODES[kernel.dtype],)
@@ -369,13 +376,21 @@ LONG_MAX_POINTS = 1 << 24         # longest transform of the long-filter path (4
 
 
 def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int, pad_right: int, flip: bool,
-               out_keep: int, has_bias: bool, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1, out_step: int = 1):
+               out_keep: int, has_bias: bool, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1, out_step: int = 1,
+               conj_signal: bool = False, conj_kernel: bool = False):
     """Cached long-filter plan (``fc_long_plan``) for a signal (B, Cin, L) against ``taps`` taps per filter row.  The four
-    keywords are the words of ``fc_long_ext``; a plan that leaves them at their defaults keeps the 12-field key."""
+    keywords are the words of ``fc_long_ext``; a plan that leaves them at their defaults keeps the 12-field key.  A
+    complex64 signal gets a complex plan (one batch item per row of the transform), whose key always has 17 fields: the
+    extension and the ``fc_long_kind`` bits, with ``conj_signal`` / ``conj_kernel`` (the plan reads that operand conjugated)."""
     key = ("long", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
            int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)))
     ext = (int(pad_mode), int(src_up), int(tap_dil), int(out_step))
-    if ext != _native.LONG_EXT_DEFAULT:
+    if signal.dtype == torch.complex64:
+        key += ext + (_native.LONG_COMPLEX | (_native.LONG_CONJ_SIGNAL if conj_signal else 0)
+                      | (_native.LONG_CONJ_TAPS if conj_kernel else 0),)
+    elif conj_signal or conj_kernel:
+        raise ValueError("conjugated reads go with complex64 tensors only")
+    elif ext != _native.LONG_EXT_DEFAULT:
         key += ext
     index = _device_index(signal.device)
     plan = _native.lookup_plan(index, key)
@@ -385,10 +400,16 @@ def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int,
     return plan
 
 
+def _resolved(t: Tensor) -> Tensor:
+    """A complex tensor with its lazy conjugate / negation materialised: the library reads ``data_ptr()``, which knows of
+    neither bit.  Real tensors pass through."""
+    return t.resolve_conj().resolve_neg() if t.is_complex() else t
+
+
 def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: int, pad_right: int, flip: bool,
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
               out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
-              out_step: int = 1) -> Tensor:
+              out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
     u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
@@ -397,14 +418,25 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
     ``signal`` and ``kernel`` are float32, float16 or bfloat16, each on its own: the kernels read them where they lie and
     widen as they load.  The result has ``out_dtype`` (default: the signal's; the weight gradient asks for float32 from
     16-bit operands) and is rounded once, at the store.  The plan, its cache key, the spectrum and the workspace are the
-    float32 ones whatever the dtypes; the bias (Cout values) is widened to float32."""
-    signal = signal.detach().contiguous()
-    out_dtype = signal.dtype if out_dtype is None else out_dtype
+    float32 ones whatever the dtypes; the bias (Cout values) is widened to float32.
+
+    complex64 ``signal``, ``kernel`` and ``bias`` (all three) run a complex plan: plain bilinear product, complex64 result,
+    the bias read as Cout (re, im) pairs.  ``conj_signal`` / ``conj_kernel`` make that plan read conj(signal) / conj(kernel)
+    (a sign flip as the kernels load; the gradients use it).  Lazy conjugates are resolved here."""
+    signal = _resolved(signal.detach()).contiguous()
+    cx = signal.dtype == torch.complex64
+    out_dtype = signal.dtype if out_dtype is None or cx else out_dtype
     plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
-                      bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step)
+                      bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step,
+                      conj_signal=conj_signal, conj_kernel=conj_kernel)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)
-    bias_c = bias.detach().float().contiguous() if bias is not None else None
+    if bias is None:
+        bias_c = None
+    elif cx:
+        bias_c = _resolved(bias.detach()).contiguous()
+    else:
+        bias_c = bias.detach().float().contiguous()
     with torch.cuda.device(signal.device):
         out = torch.empty((signal.shape[0], kernel.shape[0], plan.out_len), dtype=out_dtype, device=signal.device)
         ws = new_workspace(plan, signal.device)
@@ -484,7 +516,7 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
 
     ``signal`` (B, Cin, L), ``kernel`` (Cout, Cin/groups, K), ``bias`` (Cout,) or None, on a ROCm device, all three float32,
-    float16 or bfloat16.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, stride, padding, dilation, groups,
+    float16, bfloat16 or complex64.  ``causal=False``: equal to ``fft_conv(signal, kernel, bias, stride, padding, dilation, groups,
     padding_mode)`` (cross-correlation; ``padding`` an int, 'same' or 'valid'; ``padding_mode`` constant | reflect |
     replicate | circular), output length (L + 2*padding - dilation*(K-1) - 1) // stride + 1.  ``causal=True`` (``padding``
     must be 0 and ``padding_mode`` constant):
@@ -498,9 +530,14 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     gradient) has the bits of widening the tensors, running the float32 function and rounding with ``.to(dtype)``.
     Autograd saves the 16-bit tensors.  ``FFTCONV_HALF_IO=0`` takes that cast path instead.
 
-    Rows whose padded length is at most 4096 run the ``fft_conv`` kernels; a row that needs more than 2**24 points raises
-    ``NotImplementedError``.  float64 tensors and tensors of different dtypes are not taken by this path
-    (``TypeError``)."""
+    complex64 tensors (all three) run the same transform with one batch item per row of it instead of a packed pair: the
+    product is plain bilinear, nothing is conjugated (as ``torch.nn.functional.conv1d`` on complex tensors), every
+    argument keeps its meaning, the output is complex64 of the same length, arithmetic and spectra are float32.  The
+    gradients follow PyTorch's convention for complex tensors.  Lazy conjugates (``x.conj()``) are resolved on entry.
+
+    Real rows whose padded length is at most 4096 run the ``fft_conv`` kernels (complex rows stay here, at 64 x 64 points);
+    a row that needs more than 2**24 points raises ``NotImplementedError``.  float64 and complex128 tensors, tensors of
+    different dtypes and mixes of real and complex tensors are not taken by this path (``TypeError``)."""
     return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode)
 
 
@@ -515,12 +552,15 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
         if t is not None:
             _require_long_dtype(name, t, signal.dtype)
     _same_device(signal=signal, kernel=kernel, bias=bias)
+    if signal.dtype == torch.complex64:
+        # (the library reads data_ptr(): a conj or neg bit is resolved first, inside the autograd graph)
+        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
     if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
         # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out (what a caller would write by hand)
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
                                   causal, None, stride, dilation, padding_mode)
         return out.to(signal.dtype)
-    if need <= LONG_HANDOFF_POINTS:
+    if need <= LONG_HANDOFF_POINTS and signal.dtype != torch.complex64:      # (fft_conv has no complex route)
         if not causal:
             return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
         # taps at a lag of L or more never reach the output
@@ -540,7 +580,7 @@ def _long_keep(length: int, causal: bool, stride: int) -> int:
     return -(-int(length) // stride) if causal else 0
 
 
-_LONG_DTYPES = (torch.float32,) + _LOW_PRECISION
+_LONG_DTYPES = (torch.float32,) + _LOW_PRECISION + (torch.complex64,)
 
 
 def _require_long_dtype(name: str, t: Tensor, dtype: torch.dtype):
@@ -551,4 +591,6 @@ def _require_long_dtype(name: str, t: Tensor, dtype: torch.dtype):
             f"(no CPU fallback). Move the tensor to 'cuda'.")
     if t.dtype != dtype or dtype not in _LONG_DTYPES:
         raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; fft_long_conv takes signal, kernel and bias "
-                        f"that share one of float32, float16 or bfloat16 (float64 runs through fft_conv only)")
+                        f"that share one of float32, float16, bfloat16 or complex64 (float64 runs through fft_conv only; "
+                        f"complex128, complex32 and mixes of real and complex tensors are not taken: convert with "
+                        f".to(torch.complex64))")

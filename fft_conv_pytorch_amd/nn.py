@@ -188,7 +188,8 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
     ``padding_mode`` 'zeros').  ``stride``, ``dilation`` and ``padding_mode`` are trailing keyword arguments, stored as
     ``nn.Conv1d`` stores them.  The kernel spectrum is cached
     under the rules of ``_SpectrumCache``, for a float32 module and for one in float16 / bfloat16 (``module.bfloat16()``:
-    the kernels read the 16-bit weight and signal and write a 16-bit output; the cached spectrum stays float32)."""
+    the kernels read the 16-bit weight and signal and write a 16-bit output; the cached spectrum stays float32) or in
+    complex64 (``dtype=torch.complex64`` / ``.to(torch.complex64)``; state_dict interchanges with a complex ``nn.Conv1d``)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
                  dtype=None, *, stride=1, dilation=1, padding_mode="zeros"):
@@ -211,9 +212,11 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         pad_left, pad_right, need = F_._long_geometry(signal, weight, bias, padding, self.groups, self.causal, stride,
                                                       dilation, padding_mode)
         spectrum = None
-        if (F_.LONG_HANDOFF_POINTS < need <= F_.LONG_MAX_POINTS and signal.is_cuda and weight.is_cuda
+        cx = signal.dtype == torch.complex64 and (bias is None or bias.dtype == signal.dtype)
+        # (a complex row never hands off to fft_conv; a lazily conjugated signal gets a plan of the same key)
+        if ((cx or F_.LONG_HANDOFF_POINTS < need) and need <= F_.LONG_MAX_POINTS and signal.is_cuda and weight.is_cuda
                 and signal.device == weight.device and signal.dtype == weight.dtype
-                and (signal.dtype == torch.float32 or F_._half_native(signal, weight, bias))):
+                and (signal.dtype == torch.float32 or cx or F_._half_native(signal, weight, bias))):
             plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
                                  F_._long_keep(signal.shape[2], self.causal, stride), bias is not None,
                                  pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)

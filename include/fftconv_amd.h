@@ -38,7 +38,7 @@ enum fc_dtype {
                   prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  N-d plans need
                   fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook take no float64 */
   FC_F16 = 2,
-  FC_BF16 = 3  /* float16 / bfloat16 signal and output (ABI 7): x and y are 16-bit (pass them through the float* parameters);
+  FC_BF16 = 3, /* float16 / bfloat16 signal and output (ABI 7): x and y are 16-bit (pass them through the float* parameters);
                   weight, w_hat and bias stay float32 (the caller widens the weight and the bias).  The kernels widen x exactly as
                   they load it, compute in float32 and round y once as they store it (to nearest even; bfloat16 NaN -> 0x7FC0), so
                   the result has the bits of: widen to float32, run the float32 plan, round.  The plan is the float32 plan of the
@@ -52,6 +52,8 @@ enum fc_dtype {
                   descriptor, and the loads widen exactly, so every partial and dW has the float32 call's bits on the widened
                   tensors; segments of taps add into the float32 dW as they do there.  A library that predates this answers
                   such a descriptor with 0 slices or FC_ERR_UNSUPPORTED: a caller widens x and dy for that gradient. */
+  FC_C64 = 4   /* complex64 tensors, (re, im) float32 pairs (ABI 7 extension): the long-filter calls fc_long_transform_kernel_io
+                  and fc_long_forward_io on a complex plan (fc_long_plan_create_kind) only; no fc_desc takes it */
 };
 
 /* Problem descriptor: the arguments of functional.py:19-28 after to_ntuple
@@ -213,7 +215,7 @@ typedef struct fc_long_plan fc_long_plan;
 
 /* info words of a long plan: N1, N2, output length, kernel-spectrum bytes, workspace bytes, slabs (the batch pairs
  * run in this many rounds of three launches so that the workspace stays inside the budget), output channels per
- * workgroup of the row pass, batch pairs per slab. */
+ * workgroup of the row pass, batch pairs per slab (a complex plan, below: batch items where this says pairs). */
 enum { FC_LONG_INFO_WORDS = 8 };
 
 /* The info words from the descriptor alone: validates it, touches no device.  FFTCONV_LONG_N=<N1>x<N2> forces the
@@ -274,6 +276,29 @@ typedef struct fc_long_ext {
 
 int fc_long_geometry_ext(const fc_long_desc* desc, const fc_long_ext* ext, int64_t info[8]);
 int fc_long_plan_create_ext(const fc_long_desc* desc, const fc_long_ext* ext, fc_long_plan** out_plan);
+
+/* complex64 tensors (ABI 7 extension: new entry points only; fc_long_desc, fc_long_ext and every call above keep their
+ * signatures, and the two calls above are these with kind = FC_LONG_REAL).  The transform underneath is complex: a real
+ * plan packs two batch items into one row of it, a complex plan (FC_LONG_COMPLEX) gives every batch item a row of its own.
+ * It computes the formula above with complex x, weight, bias and y and a plain bilinear product -- nothing is conjugated,
+ * as torch.nn.functional.conv1d on complex tensors.  Its info words count rows where a real plan counts pairs: slabs are
+ * rounds of batch ITEMS, info[7] items per slab, the workspace info[7] * (Cin + Cout) * N * 8 bytes; the spectrum has the
+ * size of the real plan's (N complex bins per filter row either way).  length, kernel and both paddings must stay below
+ * 2^28 (FC_ERR_UNSUPPORTED): a sample has 8 bytes and buffer offsets 32 bits.
+ *   fc_long_transform_kernel_io / fc_long_forward_io on a complex plan take FC_C64 for weight, x and y (complex64 tensors,
+ *   read and written where they lie); bias then points to Cout (re, im) pairs.  Arithmetic, spectrum and workspace are
+ *   float32 as ever.  FC_C64 on a real plan and a real code on a complex plan: FC_ERR_INVALID, the text naming the
+ *   mismatch; FC_F64 and unknown codes answer as on a real plan.  The calls without _io are FC_F32 calls: real plans only.
+ *   FC_LONG_CONJ_SIGNAL  the plan reads x conjugated: y = sum u * conj(xrow) (+ bias)
+ *   FC_LONG_CONJ_TAPS    the plan reads the weight conjugated: u = conj(w) in tap order / flipped
+ * Both are sign flips as a sample is loaded; they exist for the gradients (PyTorch's convention: dX runs dY against
+ * conj(w), dW runs conj(x) against dY as the filter) and go with FC_LONG_COMPLEX only (FC_ERR_INVALID otherwise). */
+enum fc_long_kind { FC_LONG_REAL = 0, FC_LONG_COMPLEX = 1, FC_LONG_CONJ_SIGNAL = 2, FC_LONG_CONJ_TAPS = 4 };
+
+int fc_long_geometry_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, int64_t info[8]);
+int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, fc_long_plan** out_plan);
+/* The kind bits a plan was made with (-1: NULL plan). */
+int fc_long_plan_kind(const fc_long_plan* plan);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@ EXPORTS = (
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
-ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd")
+ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd", "f64_fft_long")
 ROUTE_WORDS = {
     "f32_1d": ("T", "ntiles", "pers_nb", "ph", "ph2", "slot_tiles", "nseg", "diag", "bd_gs", "wide", "dense",
                "chunk_launches", "accumulate", "n_ochunks", "pers_items"),
@@ -40,6 +40,7 @@ ROUTE_WORDS = {
     "f64_direct": (),
     "f64_fft_1d": ("T", "ntiles", "cob"),
     "f64_fft_nd": ("t0", "t1", "t2", "nt0", "nt1", "nt2", "nb", "cob"),
+    "f64_fft_long": ("N1", "N2", "ntiles", "cob"),
 }
 
 

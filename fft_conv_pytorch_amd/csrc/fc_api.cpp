@@ -248,7 +248,7 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   set_channel_layout(p.get(), (int)d.groups, (int)(d.in_channels / d.groups), (int)(d.out_channels / d.groups));
 
   int rc;
-  if (d.dtype == FC_F64) rc = plan_f64(p.get());                 // picks one of the three float64 kinds
+  if (d.dtype == FC_F64) rc = plan_f64(p.get());                 // picks one of the four float64 kinds
   else if (d.ndim == 1) { p->kind = PlanKind::F32_1D; rc = plan_1d(p.get()); }
   else { p->kind = PlanKind::F32_ND; rc = plan_nd(p.get()); }
   if (rc != FC_OK) return rc;
@@ -291,6 +291,7 @@ int fc_plan_tile(const fc_plan* plan) {
     case PlanKind::F64_DIRECT: return 0;
     case PlanKind::F64_FFT_1D:
     case PlanKind::F64_FFT_ND: return plan->f64.T;
+    case PlanKind::F64_FFT_LONG: return plan->f64.N2;
   }
   return 0;
 }
@@ -313,6 +314,9 @@ int fc_plan_layout(const fc_plan* plan, int32_t layout[8]) {
       break;
     case PlanKind::F64_FFT_ND:   // [outermost T, Tx, middle T (3-D)]
       layout[0] = p.f64.t[0]; layout[1] = p.f64.t[p.nd - 1]; layout[2] = p.nd == 3 ? p.f64.t[1] : 0;
+      break;
+    case PlanKind::F64_FFT_LONG:   // the factorisation orders the bins of the spectrum
+      layout[0] = p.f64.N1; layout[1] = p.f64.N2;
       break;
     case PlanKind::F64_DIRECT:
     case PlanKind::F64_FFT_1D:
@@ -370,6 +374,9 @@ int fc_debug_route(const fc_plan* plan, int32_t route[16]) {
       for (int i = 0; i < 3; ++i) { route[1 + i] = p.f64.t[i]; route[4 + i] = p.f64.nt[i]; }
       route[7] = p.f64.nb; route[8] = p.f64.cob;
       break;
+    case PlanKind::F64_FFT_LONG:
+      route[1] = p.f64.N1; route[2] = p.f64.N2; route[3] = p.f64.ntiles; route[4] = p.f64.cob;
+      break;
   }
   return FC_OK;
 }
@@ -386,6 +393,7 @@ int fc_transform_kernel(const fc_plan* plan, const float* weight, void* w_hat, v
     case PlanKind::F64_DIRECT: return transform_kernel_f64_direct(p, weight, w_hat, workspace, st);
     case PlanKind::F64_FFT_1D: return transform_kernel_f64_1d(p, weight, w_hat, workspace, st);
     case PlanKind::F64_FFT_ND: return transform_kernel_f64_nd(p, weight, w_hat, workspace, st);
+    case PlanKind::F64_FFT_LONG: return transform_kernel_f64_long(p, weight, w_hat, workspace, st);
   }
   return fail(FC_ERR_INVALID, "internal: unknown plan kind");
 }
@@ -412,6 +420,7 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
     case PlanKind::F64_DIRECT: return forward_f64_direct(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F64_FFT_1D: return forward_f64_1d(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F64_FFT_ND: return forward_f64_nd(p, x, w_hat, bias, y, workspace, st, stamps);
+    case PlanKind::F64_FFT_LONG: return forward_f64_long(p, x, w_hat, bias, y, workspace, st, stamps);
   }
   return fail(FC_ERR_INVALID, "internal: unknown plan kind");
 }

@@ -1,6 +1,6 @@
 // fc_plan.h -- the plan behind the C ABI (include/fftconv_amd.h) and the host helpers its paths share.
 //
-// A plan runs one of five paths (fc::PlanKind), chosen once when it is created (fc_api.cpp).  Each path plans and
+// A plan runs one of six paths (fc::PlanKind), chosen once when it is created (fc_api.cpp).  Each path plans and
 // launches in a file of its own: host_1d.cpp (float32 1-D), host_nd.cpp (float32 2-D / 3-D), host_f64.cpp (float64).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +58,7 @@ enum class PlanKind {
   F64_DIRECT,   // host_f64.cpp: direct time-domain kernel (any ndim)
   F64_FFT_1D,   // host_f64.cpp: fft_f64.hip
   F64_FFT_ND,   // host_f64.cpp: nd_f64.hip
+  F64_FFT_LONG, // host_f64.cpp: long_f64.hip (1-D, dilated extent past 1025: one transform of N1 x N2 points per row)
 };
 
 }  // namespace fc
@@ -129,10 +130,14 @@ struct fc_plan {
     size_t seg_spectrum_bytes;
   } fnd;
 
-  struct {                    // ---- F64_FFT_1D / F64_FFT_ND
+  struct {                    // ---- F64_FFT_1D / F64_FFT_ND / F64_FFT_LONG
     int T, V, ntiles, cob;      // 1-D (fft_f64.hip): tile, valid samples, tiles per row, out-chunk (N-d: T = the last axis' transform length)
     int t[3], v[3], nt[3];      // N-d (nd_f64.hip): transform length, valid samples, tiles per axis
     int nb;                     // N-d: batch items per workgroup of its fused pass (cob output channels each)
+    // F64_FFT_LONG (long_f64.hip): N = N1 x N2 points per transform (T = N2); V, ntiles and cob as above (one tile: V = Lf);
+    // batch pairs, and how many of them share the workspace at a time
+    int N1, N2;
+    int64_t npairs, slab_pairs;
   } f64;
 };
 
@@ -152,6 +157,7 @@ int transform_kernel_nd(const fc_plan& p, const float* weight, void* w_hat, void
 int transform_kernel_f64_direct(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st);
 int transform_kernel_f64_1d(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st);
 int transform_kernel_f64_nd(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st);
+int transform_kernel_f64_long(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st);
 
 int forward_1d(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
                hipStream_t st, void* stamps);
@@ -163,5 +169,7 @@ int forward_f64_1d(const fc_plan& p, const float* x, const void* w_hat, const fl
                    hipStream_t st, void* stamps);
 int forward_f64_nd(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
                    hipStream_t st, void* stamps);
+int forward_f64_long(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
+                     hipStream_t st, void* stamps);
 
 }  // namespace fc

@@ -16,41 +16,11 @@
 
 #include "axis_map.hpp"
 #include "fft_f64.h"
+#include "fft_f64_core.hpp"
 #include "launch.hpp"
 
 namespace fc {
 namespace {
-
-__device__ __forceinline__ double2 cmul_d(double2 a, double2 b) {
-  return make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
-}
-
-// Stockham radix-2, T points, T/2 threads, natural order in (buffer `a`) and out (returned pointer: a or b).
-// DIR = -1 forward, +1 inverse (unnormalised).  tw[k] = exp(-2 pi i k / T), k < T/2.
-template <int DIR>
-__device__ __forceinline__ double2* fft_stockham(double2* a, double2* b, const double2* tw, int T, int t) {
-  const int half = T >> 1;
-  for (int ns = 1; ns < T; ns <<= 1) {
-    const int k = t & (ns - 1);
-    const double2 u = a[t];
-    double2 v = a[t + half];
-    double2 w = tw[k * (half / ns)];
-    if (DIR > 0) w.y = -w.y;
-    v = cmul_d(v, w);
-    const int j = ((t - k) << 1) + k;
-    b[j] = make_double2(u.x + v.x, u.y + v.y);
-    b[j + ns] = make_double2(u.x - v.x, u.y - v.y);
-    __syncthreads();
-    double2* s = a; a = b; b = s;
-  }
-  return a;
-}
-
-__device__ __forceinline__ void build_table(double2* tw, int T, int t) {
-  double s, c;
-  sincospi(-2.0 * (double)t / (double)T, &s, &c);
-  tw[t] = make_double2(c, s);
-}
 
 // ---- kernel transform: one (o, i) pair per workgroup
 __global__ __launch_bounds__(1024) void spectrum_f64_kernel(const FftF64Args a) {

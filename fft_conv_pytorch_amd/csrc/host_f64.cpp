@@ -1,14 +1,16 @@
-// host_f64.cpp -- float64 plans: the direct time-domain kernel (PlanKind::F64_DIRECT, direct_f64.hip), 1-D FFTs
-// (F64_FFT_1D, fft_f64.hip) and 2-D / 3-D FFTs (F64_FFT_ND, nd_f64.hip): the choice between them, their tiles and
-// sizes, kernel transforms and forwards.  Chosen from the descriptor alone, with no device query: float64 plans can be
+// host_f64.cpp -- float64 plans: the direct time-domain kernel (PlanKind::F64_DIRECT, direct_f64.hip), 1-D FFTs in
+// tiles (F64_FFT_1D, fft_f64.hip) or as one long transform (F64_FFT_LONG, long_f64.hip) and 2-D / 3-D FFTs (F64_FFT_ND,
+// nd_f64.hip): the choice between them, their tiles and sizes, kernel transforms and forwards.  Chosen from the descriptor alone, with no device query: float64 plans can be
 // made anywhere.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "direct_f64.h"
 #include "fft_f64.h"
+#include "long_f64.h"
 #include "nd_f64.h"
 #include "fc_plan.h"
 
@@ -113,6 +115,82 @@ static bool plan_nd_f64(fc_plan* p) {
   return true;
 }
 
+// ---- 1-D plans whose dilated extent no 2048-point tile holds: one cyclic transform of N = N1 x N2 points (long_f64.hip)
+
+// The long route's work follows N log2 N per row whatever the outputs kept; the direct kernel's is nout x Cin/g x K per
+// (batch, output channel) row.  The long route is taken from kF64LongC multiply-adds of the direct kernel per
+// transformed point and stage: nout * Cig * K >= kF64LongC * ntiles * N * log2(N).
+// MI355X sweep (profiles/f64_long.jsonl, scripts/f64_long_bench.py --sweep): not measured yet.
+static const double kF64LongC = 4.0;
+static const int64_t kF64LongMaxN = (int64_t)1 << 22;      // 2048 x 2048: the 2048-point transform takes 80 KiB of LDS
+
+static bool long_tile_len(long long v) { return v >= 64 && v <= 2048 && (v & (v - 1)) == 0; }
+
+// Fills the plan and sets *taken when the plan runs the long route; leaves it untouched (the direct kernel's state)
+// otherwise.  `force`: FFTCONV_F64_LONG=2, no crossover.  Fails on a bad FFTCONV_F64_LONG_N only.
+static int plan_long_f64(fc_plan* p, bool force, bool* taken) {
+  *taken = false;
+  const fc_desc& d = p->d;
+  const int64_t kd = p->kd[0], Lf = p->Lf[0], need = p->need[0];
+  if ((int64_t)p->Sp[0] + kF64LongMaxN >= ((int64_t)1 << 31)) return FC_OK;     // (padded positions are 32-bit in the kernels)
+  // smallest N = N1 * N2 >= need (zero padding absorbs the wrap, fc_api.cpp) with both factors 64 .. 2048; the most
+  // balanced split, N2 >= N1
+  int lg = 12;
+  while (((int64_t)1 << lg) < need && lg < 22) ++lg;
+  int64_t n1 = (int64_t)1 << (lg / 2), n2 = (int64_t)1 << (lg - lg / 2);
+  bool forced_n = false;
+  if (const char* env = getenv("FFTCONV_F64_LONG_N")) {
+    if (*env) {
+      long long a = 0, b = 0;
+      char tail = 0;
+      if (sscanf(env, "%lldx%lld%c", &a, &b, &tail) != 2 || !long_tile_len(a) || !long_tile_len(b))
+        return fail(FC_ERR_INVALID, "FFTCONV_F64_LONG_N=%s: expected <N1>x<N2>, both powers of two from 64 to 2048", env);
+      n1 = a; n2 = b; forced_n = true;
+    }
+  }
+  const int64_t N = n1 * n2;
+  // rows that need more than N points: overlap-save tiles of one transform each, V valid samples per tile
+  int64_t V = Lf, ntiles = 1;
+  if (N < need) {
+    V = N - kd + 1;
+    if (V < N / 2) {
+      if (forced_n)
+        return fail(FC_ERR_INVALID, "FFTCONV_F64_LONG_N=%s holds %lld points, of which a kernel extent of %lld leaves %lld "
+                    "valid: fewer than half", getenv("FFTCONV_F64_LONG_N"), (long long)N, (long long)kd, (long long)(V > 0 ? V : 0));
+      return FC_OK;
+    }
+    ntiles = (Lf + V - 1) / V;
+  }
+  int lgN = 0;
+  while (((int64_t)1 << lgN) < N) ++lgN;
+  if (!force && (double)p->out_sp[0] * p->Cig * (double)d.kernel[0] < kF64LongC * (double)ntiles * (double)N * lgN) return FC_OK;
+  const int nc = fc::long_f64_nc((int)n1), nr = fc::long_f64_nr((int)n2);
+  const int64_t npairs = (d.batch + 1) / 2;
+  // output channels per workgroup of the row pass: the rule of the tiled 1-D plan (8, fewer while CUs would idle)
+  int cob = 8;
+  while (cob > 2 && npairs * d.groups * ((p->Cog + cob - 1) / cob) * (n1 / nr) < 256) cob /= 2;
+  cob = std::min(cob, std::max(p->Cog, 1));
+  const int64_t n_ochunks = (p->Cog + cob - 1) / cob;
+  // batch pairs run in slabs under the workspace budget (W1 + W2 of one slab), every grid below 2^31 workgroups
+  int64_t budget_mb = 8192;
+  if (const char* env = getenv("FFTCONV_LONG_WS_MB"))
+    if (*env && atoll(env) > 0) budget_mb = atoll(env);
+  const int64_t pair_bytes = (d.in_channels + d.out_channels) * N * (int64_t)sizeof(double2);
+  const int64_t pair_grid = std::max({d.in_channels * (n2 / nc), d.groups * n_ochunks * (n1 / nr), d.out_channels * (n2 / nc)});
+  if (pair_grid > 0x7fffffffLL) return FC_OK;
+  int64_t slab_pairs = std::max<int64_t>(1, std::min<int64_t>(npairs, (budget_mb << 20) / pair_bytes));
+  slab_pairs = std::min<int64_t>(slab_pairs, 0x7fffffffLL / pair_grid);
+  p->f64.N1 = (int)n1; p->f64.N2 = (int)n2; p->f64.T = (int)n2;
+  p->f64.V = (int)V; p->f64.ntiles = (int)ntiles; p->f64.cob = cob;
+  p->f64.npairs = npairs; p->f64.slab_pairs = slab_pairs;
+  p->Lfull = (int)Lf;
+  p->spectrum_bytes = (size_t)d.out_channels * p->Cig * (size_t)N * sizeof(double2);
+  p->workspace_bytes = (size_t)(slab_pairs * pair_bytes);
+  p->kind = PlanKind::F64_FFT_LONG;
+  *taken = true;
+  return FC_OK;
+}
+
 int plan_f64(fc_plan* p) {
   const fc_desc& d = p->d;
   // float64: direct time-domain kernel (direct_f64.hip); the "kernel spectrum" is the weight tensor itself
@@ -125,9 +203,12 @@ int plan_f64(fc_plan* p) {
   // The FFT paths in double precision: 1-D plans, forward and transposed, with at least 16 taps (fft_f64.hip);
   // 2-D / 3-D plans, forward and transposed, from kF64MinMacs multiply-adds of the direct kernel per output of the FFT
   // path (nd_f64.hip).
-  // A dilated extent past 1025 on any axis keeps the direct kernel.  FFTCONV_F64_FFT=0 keeps it for everything (A/B
-  // runs, tests).  Chosen from the descriptor alone, with no device query: float64 plans can be made anywhere.
-  // FFTCONV_F64_FFT=2 (crossover sweeps) takes the 2-D / 3-D FFT path at any size.
+  // A dilated extent past 1025 keeps the direct kernel on a 2-D / 3-D plan; a 1-D plan takes one long transform of
+  // N1 x N2 points per row (long_f64.hip) from the crossover of plan_long_f64 on.  FFTCONV_F64_FFT=0 keeps the direct
+  // kernel for everything (A/B runs, tests).  Chosen from the descriptor alone, with no device query: float64 plans can
+  // be made anywhere.  FFTCONV_F64_FFT=2 (crossover sweeps) takes the 2-D / 3-D FFT path at any size.
+  // FFTCONV_F64_LONG=0 keeps the direct kernel for the long 1-D plans, =2 takes the long transform for any 1-D plan of at
+  // least 16 taps; FFTCONV_F64_LONG_N=<N1>x<N2> forces its factorisation.  Both are read here, at plan creation.
   const char* env = getenv("FFTCONV_F64_FFT");
   const bool fft_on = !env || atoi(env) != 0;
   const bool force_nd = env && atoi(env) == 2;
@@ -137,6 +218,13 @@ int plan_f64(fc_plan* p) {
     macs *= d.kernel[i];
     if (!d.transposed) strides *= d.stride[i];
     kd_ok = kd_ok && p->kd[i] <= 1025;
+  }
+  const char* lenv = getenv("FFTCONV_F64_LONG");
+  const int long_knob = lenv && *lenv ? atoi(lenv) : 1;
+  if (fft_on && d.ndim == 1 && long_knob != 0 && (p->kd[0] > 1025 || (long_knob == 2 && d.kernel[0] >= 16))) {
+    bool taken = false;
+    if (int rc = plan_long_f64(p, long_knob == 2, &taken)) return rc;
+    if (taken) return FC_OK;
   }
   if (fft_on && kd_ok && d.ndim == 1 && d.kernel[0] >= 16 &&
       (int64_t)d.batch * d.groups * ((p->out_sp[0] + 255) / 256) < 0x40000000) {
@@ -215,6 +303,69 @@ int forward_f64_1d(const fc_plan& p, const float* x, const void* w_hat, const fl
   a.x = (const double*)x; a.wspec = (double2*)const_cast<void*>(w_hat); a.bias = p.d.has_bias ? (const double*)bias : nullptr;
   a.y = (double*)y;
   FC_HIP(fc::launch_fft_f64(1, a, st));
+  return FC_OK;
+}
+
+// ---- 1-D, one long transform per row (long_f64.hip)
+static fc::LongF64Args long_f64_args(const fc_plan& p) {
+  fc::LongF64Args a{};
+  a.N1 = p.f64.N1; a.N2 = p.f64.N2;
+  while ((1 << a.lgN2) < a.N2) ++a.lgN2;
+  a.B = (int)p.d.batch; a.G = (int)p.d.groups; a.Cig = p.Cig; a.Cog = p.Cog;
+  a.cob = p.f64.cob; a.n_ochunks = (p.Cog + p.f64.cob - 1) / p.f64.cob;
+  a.L = (int)p.d.spatial[0]; a.pad = p.padl[0]; a.pad_mode = p.d.padding_mode; a.up = p.up[0];
+  a.K = (int)p.d.kernel[0]; a.dil = (int)p.d.dilation[0]; a.transposed = p.d.transposed;
+  a.stride = p.ostride[0]; a.Lout = (int)p.out_sp[0];
+  a.scale = 1.0 / ((double)p.f64.N1 * (double)p.f64.N2);
+  return a;
+}
+
+// kernel spectrum: the forward column pass on the dilated taps (flipped, channels exchanged for a transposed plan) and
+// the row pass in its filter mode, which conjugates and scales by 1/N; the filter rows go through the workspace a chunk
+// at a time (it holds at least Cin + Cout >= 2 rows of N points)
+int transform_kernel_f64_long(const fc_plan& p, const float* weight, void* w_hat, void* workspace, hipStream_t st) {
+  const int64_t N = (int64_t)p.f64.N1 * p.f64.N2;
+  const int64_t rows_total = p.d.out_channels * (int64_t)p.Cig;
+  const int64_t fit = std::max<int64_t>(1, (int64_t)(p.workspace_bytes / ((size_t)N * sizeof(double2))));
+  const int64_t grid_cap = 0x7fffffffLL / std::max(p.f64.N2 / fc::long_f64_nc(p.f64.N1), p.f64.N1 / fc::long_f64_nr(p.f64.N2));
+  const int64_t chunk = std::min(fit, grid_cap);
+  for (int64_t r0 = 0; r0 < rows_total; r0 += chunk) {
+    const int64_t n = std::min(chunk, rows_total - r0);
+    fc::LongF64Args a = long_f64_args(p);
+    a.from_kernel = 1; a.row0 = (int)r0;
+    a.src = (const double*)weight; a.w1 = (double2*)workspace;
+    FC_HIP(fc::launch_long_f64_cols_fwd(a, n, st));
+    a.spec_mode = 1;
+    a.spec_out = (double2*)w_hat + (size_t)r0 * N;
+    FC_HIP(fc::launch_long_f64_rows(a, n, st));
+  }
+  return FC_OK;
+}
+
+// forward: three launches per slab of batch pairs and tile
+int forward_f64_long(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
+                     hipStream_t st, void* stamps) {
+  if (stamps) return fail(FC_ERR_UNSUPPORTED, "no timestamp hook in the float64 kernels");
+  const int64_t N = (int64_t)p.f64.N1 * p.f64.N2;
+  const int64_t Cin = p.d.in_channels, Cout = p.d.out_channels;
+  for (int64_t pair0 = 0; pair0 < p.f64.npairs; pair0 += p.f64.slab_pairs) {
+    const int64_t np = std::min(p.f64.slab_pairs, p.f64.npairs - pair0);
+    for (int tile = 0; tile < p.f64.ntiles; ++tile) {
+      fc::LongF64Args a = long_f64_args(p);
+      a.pair0 = (int)pair0;
+      a.src = (const double*)x; a.bias = p.d.has_bias ? (const double*)bias : nullptr; a.y = (double*)y;
+      a.spec = (const double2*)w_hat;
+      a.w1 = (double2*)workspace;
+      a.w2 = a.w1 + (size_t)(p.f64.slab_pairs * Cin * N);
+      a.p0 = a.t0 = tile * p.f64.V;                    // (one tile: V = Lf, the whole stride-1 result)
+      a.limit = std::min(p.f64.V, p.Lf[0] - a.t0);
+      a.C = (int)Cin;
+      FC_HIP(fc::launch_long_f64_cols_fwd(a, np * Cin, st));
+      FC_HIP(fc::launch_long_f64_rows(a, np * p.d.groups * a.n_ochunks, st));
+      a.C = (int)Cout;
+      FC_HIP(fc::launch_long_f64_cols_inv(a, np * Cout, st));
+    }
+  }
   return FC_OK;
 }
 

@@ -35,8 +35,10 @@ enum fc_dtype {
   FC_F64 = 1,  /* float64 tensors: x, weight, w_hat, bias and y are double (pass them through the float* / void*
                   parameters); double-precision FFT kernels compute the same function (the reference is dtype-agnostic):
                   1-D plans with >= 16 taps, 2-D / 3-D plans from 100 multiply-adds per output (Cin/groups x
-                  prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  N-d plans need
-                  fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook take no float64 */
+                  prod(kernel), over prod(stride) when forward), forward and transposed; a direct time-domain kernel the rest.  A 1-D
+                  plan whose dilated kernel extent exceeds 1025 runs one transform of N1 x N2 points per row (three launches,
+                  the scheme of the long filters below in double precision) from its crossover with the direct kernel on.
+                  N-d plans and those long 1-D plans need fc_workspace_bytes of workspace.  fc_wgrad1d, fc_wgrad_nd and the profiling hook take no float64 */
   FC_F16 = 2,
   FC_BF16 = 3, /* float16 / bfloat16 signal and output (ABI 7): x and y are 16-bit (pass them through the float* parameters);
                   weight, w_hat and bias stay float32 (the caller widens the weight and the bias).  The kernels widen x exactly as
@@ -180,7 +182,8 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
 long long fc_debug_grid(const fc_plan* plan);
 
 /* Which kernel build a plan runs, for tests (read-only: no device call, nothing a launch reads changes).
- * route[0] = plan kind (0 float32 1-D, 1 float32 N-d, 2 float64 direct, 3 float64 1-D FFT, 4 float64 N-d FFT); then
+ * route[0] = plan kind (0 float32 1-D, 1 float32 N-d, 2 float64 direct, 3 float64 1-D FFT, 4 float64 N-d FFT,
+ *             5 float64 1-D long transform); then
  *   float32 1-D:  tile, tiles, batch items per workgroup (0 = general kernel), phases, phase pairs (1) / quads (2),
  *                 slots are tiles, segments, depthwise blocks, block-diagonal group size, wide, dense, launches per
  *                 input chunk, running sums, out-chunks, work items
@@ -190,6 +193,7 @@ long long fc_debug_grid(const fc_plan* plan);
  *                 the third axis are 0 in 2-D
  *   float64 1-D:  tile, tiles, channel block
  *   float64 N-d:  tile per axis (3), tiles per axis (3), batch items per workgroup, channel block
+ *   float64 long: N1, N2, overlap-save tiles of N1 x N2 points per row, channel block (fc_plan_tile reports N2)
  * Unused words are 0.  NULL plan or array: FC_ERR_INVALID. */
 int fc_debug_route(const fc_plan* plan, int32_t route[16]);
 

@@ -28,6 +28,7 @@ EXPORTS = (
     "fc_long_forward", "fc_long_transform_kernel_io", "fc_long_forward_io",
     "fc_long_geometry_ext", "fc_long_plan_create_ext",
     "fc_long_geometry_kind", "fc_long_plan_create_kind", "fc_long_plan_kind",
+    "fc_long_forward_lay",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -78,6 +79,9 @@ LONG_EXT_DEFAULT = (0, 1, 1, 1)
 FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans only)
 # enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
 LONG_REAL, LONG_COMPLEX, LONG_CONJ_SIGNAL, LONG_CONJ_TAPS = 0, 1, 2, 4
+# enum fc_long_layout: how x and y of fc_long_forward_lay lie, (B, C, L) contiguous or (B, L, C) contiguous
+LONG_NCL, LONG_NLC = 0, 1
+LONG_NLC_MAX_BYTES = 1 << 31      # one batch item's (L, C) block of a channels-last tensor stays below this
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
@@ -169,6 +173,8 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_plan_create_kind.restype = i32
         lib.fc_long_plan_kind.argtypes = [vp]
         lib.fc_long_plan_kind.restype = i32
+        lib.fc_long_forward_lay.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]
+        lib.fc_long_forward_lay.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -425,6 +431,15 @@ class LongPlan:
                 x_dtype: int = 0, y_dtype: int = 0):
         st = self._lib.fc_long_forward_io(self._h, x_ptr, x_dtype, spectrum_ptr, bias_ptr, y_ptr, y_dtype, workspace_ptr,
                                           stream)
+        if st != FC_OK:
+            _raise(self._lib, st)
+
+    def forward_lay(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int,
+                    stream: int, x_dtype: int = 0, y_dtype: int = 0, x_layout: int = LONG_NCL, y_layout: int = LONG_NCL):
+        """``forward`` with the layouts of x and y named (``fc_long_layout``: LONG_NCL, or LONG_NLC for a tensor that lies
+        as a contiguous (B, L, C)).  A channels-last block of 2**31 bytes or more: ``NotImplementedError``."""
+        st = self._lib.fc_long_forward_lay(self._h, x_ptr, x_dtype, x_layout, spectrum_ptr, bias_ptr, y_ptr, y_dtype,
+                                           y_layout, workspace_ptr, stream)
         if st != FC_OK:
             _raise(self._lib, st)
 

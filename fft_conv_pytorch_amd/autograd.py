@@ -391,24 +391,34 @@ class FFTLongConvFunction(torch.autograd.Function):
     the primitive on a complex plan: dX runs dY against conj(weight), dW runs conj(x) as the signal against dY as the
     filter (K complex lags kept), db is dY summed.  The conjugates are not copies: the plan carries a flag
     (``conj_kernel`` / ``conj_signal`` of ``F_._long_run``) and ``long_cols_fwd`` flips the sign of the imaginary part as it
-    loads.  A lazily conjugated dY is resolved first."""
+    loads.  A lazily conjugated dY is resolved first.
+
+    Layouts (``F_._long_layout``): the forward reads a signal that lies as a contiguous (B, L, C) tensor where it lies and
+    writes y that way with ``channels_last``.  dX is the same primitive, so a dY that lies that way is read where it lies,
+    and dX is written in the signal's layout (after a padding-mode fold, which torch runs on whatever layout dX has, one
+    torch copy restores it).  dW's operands are transposed copies anyway and torch builds them from whichever layout
+    the tensors have; db sums a contiguous dY, so a strided dY is copied for it."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
-                padding_mode="constant"):
+                padding_mode="constant", channels_last=False):
         ctx.save_for_backward(signal, kernel)
         ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None, int(stride), int(dilation),
                    padding_mode)
         return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
                             F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
-                            pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
+                            pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
+                            channels_last=channels_last)
 
     @staticmethod
     def backward(ctx, grad):
         signal, kernel = ctx.saved_tensors
         pad_left, pad_right, flip, g, has_bias, s, d, padding_mode = ctx.cfg
         mode = F_._native.PAD_MODES[padding_mode]
-        grad = F_._resolved(grad.detach()).contiguous()
+        grad = F_._resolved(grad.detach())
+        if F_._long_layout(grad) != "nlc" or not F_._long_nlc_enabled():
+            grad = grad.contiguous()
+        x_nlc = F_._long_layout(signal) == "nlc"          # dX is written as the signal lies
         cx = signal.dtype == torch.complex64
         B, cin, L = signal.shape
         cout, cig, K = kernel.shape
@@ -425,17 +435,20 @@ class FFTLongConvFunction(torch.autograd.Function):
             if tail < 0 and dy.shape[2]:
                 dy, tail = dy[..., :max(0, dy.shape[2] - (-tail) // s)], 0
             if dy.shape[2] == 0:
-                dx = torch.zeros_like(signal)
+                dx = torch.zeros_like(signal)          # (keeps the signal's strides)
             else:
                 fold32 = mode != 0 and grad.dtype in F_._LOW_PRECISION
                 dx = F_._long_run(dy, wt, None, lead, max(tail, 0), not flip, keep, g,
-                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d, conj_kernel=cx)
+                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d, conj_kernel=cx,
+                                  channels_last=x_nlc)
                 if mode != 0:
                     # (_pad_adjoint folds equal paddings: a row padded by the larger one has zero gradient at the rest)
                     p = max(pad_left, pad_right)
                     if p:
                         dx = _pad_adjoint(F.pad(dx, (p - pad_left, p - pad_right)), (L,), (p,), padding_mode)
                     dx = dx.to(grad.dtype)
+                    if x_nlc:
+                        dx = F_._as_channels_last(dx)
         if ctx.needs_input_grad[1]:
             xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
             dyt = grad.permute(1, 0, 2).contiguous()
@@ -443,5 +456,5 @@ class FFTLongConvFunction(torch.autograd.Function):
                               tap_dil=s, out_step=d, conj_signal=cx).permute(1, 0, 2)
             dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = _grad_bias(grad).to(kernel.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+            db = _grad_bias(grad.contiguous()).to(kernel.dtype)
+        return dx, dw, db, None, None, None, None, None, None, None, None, None

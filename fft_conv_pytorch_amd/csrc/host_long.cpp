@@ -271,6 +271,21 @@ int plan_io_code(const fc_long_plan* plan, int dtype, const char* what, int* cod
   return FC_OK;
 }
 
+// a layout code of fc_long_forward_lay, and the size a channels-last tensor may have: one batch item's (len, channels)
+// block lies behind one buffer resource whose offsets from 2^31 on mean "outside"
+int layout_check(int layout, const char* what, int64_t len, int64_t channels, int io) {
+  if (layout == FC_LONG_NCL) return FC_OK;
+  if (layout != FC_LONG_NLC)
+    return fail(FC_ERR_INVALID, "%s has layout code %d; expected FC_LONG_NCL (0) or FC_LONG_NLC (1)", what, layout);
+  const int64_t es = io == IO_CODE_C64 ? 8 : (io ? 2 : 4);
+  const int64_t bytes = len * channels * es;
+  if (bytes >= (int64_t)1 << 31)
+    return fail(FC_ERR_UNSUPPORTED, "%s in the channels-last layout: one batch item is %lld samples x %lld channels x %lld "
+                "bytes = %lld bytes; the long-filter kernels address blocks below 2^31 bytes (pass a (B, C, L) copy)", what,
+                (long long)len, (long long)channels, (long long)es, (long long)bytes);
+  return FC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -375,20 +390,31 @@ int fc_long_forward(const fc_long_plan* plan, const float* x, const void* spectr
 
 int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, const void* spectrum, const float* bias,
                        void* y, int y_dtype, void* workspace, void* hip_stream) {
+  return fc_long_forward_lay(plan, x, x_dtype, FC_LONG_NCL, spectrum, bias, y, y_dtype, FC_LONG_NCL, workspace, hip_stream);
+}
+
+int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, int x_layout, const void* spectrum,
+                        const float* bias, void* y, int y_dtype, int y_layout, void* workspace, void* hip_stream) {
   if (!plan || !x || !spectrum || !y || !workspace) return fail(FC_ERR_INVALID, "null argument");
   if (plan->d.has_bias && !bias) return fail(FC_ERR_INVALID, "the plan was made with a bias");
   int xio = 0, yio = 0;
   if (int e = plan_io_code(plan, x_dtype, "x", &xio)) return e;
   if (int e = plan_io_code(plan, y_dtype, "y", &yio)) return e;
+  if (int e = layout_check(x_layout, "x", plan->g.L, plan->g.Cin, xio)) return e;
+  if (int e = layout_check(y_layout, "y", plan->g.nout, plan->g.Cout, yio)) return e;
   const bool cx = xio == IO_CODE_C64;
+  const bool x_nlc = x_layout == FC_LONG_NLC, y_nlc = y_layout == FC_LONG_NLC;
   const LongGeom& g = plan->g;
   const LongImpl& c = *plan->cols;
-  // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped)
+  // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped; the
+  // channels-last builds are mapped builds and take every launch of that layout)
   const bool map_in = g.pad_mode != PAD_CONSTANT || g.up > 1, map_out = g.step > 1;
-  const auto cols_fwd = cx ? (map_in ? c.cols_fwd_map_cx : c.cols_fwd_cx)
-                           : map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
-  const auto cols_inv = cx ? (map_out ? c.cols_inv_map_cx : c.cols_inv_cx)
-                           : map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
+  const auto cols_fwd = x_nlc ? (cx ? c.cols_fwd_nlc_cx : xio ? c.cols_fwd_nlc_h16 : c.cols_fwd_nlc)
+                        : cx  ? (map_in ? c.cols_fwd_map_cx : c.cols_fwd_cx)
+                        : map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
+  const auto cols_inv = y_nlc ? (cx ? c.cols_inv_nlc_cx : yio ? c.cols_inv_nlc_h16 : c.cols_inv_nlc)
+                        : cx  ? (map_out ? c.cols_inv_map_cx : c.cols_inv_cx)
+                        : map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
   hipStream_t st = (hipStream_t)hip_stream;
   for (int64_t s = 0; s < g.slabs; ++s) {
     const int64_t pair0 = s * g.slab_pairs;
@@ -402,10 +428,10 @@ int fc_long_forward_io(const fc_long_plan* plan, const void* x, int x_dtype, con
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
     a.C = (int)g.Cin;
-    FC_HIP(cols_fwd(a, np * g.Cin, st));
+    FC_HIP(cols_fwd(a, x_nlc ? np : np * g.Cin, st));      // (a channels-last launch counts pairs, not rows)
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;
-    FC_HIP(cols_inv(a, np * g.Cout, st));
+    FC_HIP(cols_inv(a, y_nlc ? np : np * g.Cout, st));
   }
   return FC_OK;
 }

@@ -31,6 +31,17 @@
 // needs (for real taps this is what the real builds do).  conj_src conjugates the rows of a launch once more: backward
 // reads conj(x) and conj(w) that way, without a conjugated copy.  long_rows sees rows and units only and is the same.
 //
+// Both column kernels also have a channels-last build (NC > 0; mapped form only, which computes the plain map too; float32,
+// 16-bit and complex64) for a signal / y that lies as a contiguous (B, L, C) tensor: element (b, c, t) at ((b*L + t)*C + c)
+// samples.  A workgroup still runs NSEQ sequences, but they are NC neighbouring channels x NN = NSEQ / NC neighbouring n2
+// columns of one batch pair; LDS slot rc*NN + rn holds (channel c0 + rc, column n20 + rn).  On the tensor side the lanes
+// run over rc first (runs of NC * ES contiguous bytes per time sample), on the workspace side over rn first (NN * 8
+// contiguous bytes per k1 of each of the block's rows); the transforms in between are the same code on the same slots'
+// worth of data, so a row's arithmetic -- and every bit of the result -- is that of the (B, C, L) builds.  The resource of
+// a row becomes that of a batch item's whole (L, C) block (so L*C*ES < 2^31, checked by the host); channels past C in the
+// last block get the out-of-resource offset.  blockIdx runs over channel blocks first, then n2 blocks, then pairs.  The
+// filter taps always go through the other builds.  NC = 0 compiles to what the kernels were before the parameter existed.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -75,6 +86,8 @@ struct LongArgs {
   FastDiv d_ostep;       // out_step: sample t of the stride-1 result is y[t / out_step] where that divides
   // the complex builds only (wave-uniform):
   int conj_src;          // cols_fwd: the rows of this launch are read conjugated (signal: conj(x); taps: u = conj(w))
+  // the channels-last builds only:
+  FastDiv d_ncb;         // channel blocks of NC channels, ceil(C / NC) (filled by the dispatcher; d_nblk: blocks of NN columns)
 };
 
 constexpr int IO_CODE_C64 = 4;       // fc_dtype code of a launch of a complex build (src_io / y_io)
@@ -86,10 +99,14 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
+  constexpr bool NLC = NC > 0;                  // channels-last signal (header); never a launch of filter rows
+  constexpr int M = NLC ? NC : 1;               // neighbouring channels of the workgroup ...
+  constexpr int NN = NSEQ / M;                  // ... and neighbouring n2 columns of each
+  static_assert(!NLC || (MAP && NC <= NSEQ && (NC & (NC - 1)) == 0), "channels-last: the mapped form, NC * NN == NSEQ");
   const Io<IO> io(a.src_io);
   constexpr unsigned ES = CX ? 8u : Io<IO>::B;  // bytes per sample of the source rows
   constexpr int EW = CX ? 2 : 1;                // elements of Io<IO>::T per sample
@@ -100,16 +117,31 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
   const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
   const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
-  unsigned row;
-  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  unsigned row;                                 // (channels-last: the workspace row of the block's first channel)
+  int n20;
+  [[maybe_unused]] unsigned c0 = 0, pr_nlc = 0;
+  if constexpr (!NLC) {
+    n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  } else {
+    // the channel block varies fastest, then the n2 block, then the pair
+    unsigned q;
+    c0 = fdivmod(blockIdx.x, a.d_ncb, &q) * NC;
+    n20 = (int)fdivmod(q, a.d_nblk, &pr_nlc) * NN;
+    row = pr_nlc * (unsigned)a.C + c0;
+  }
   const size_t N = (size_t)a.N1 << a.lgN2;
 
   // the two real rows of the pair (filter rows: one, the imaginary part stays zero); complex build: the one row of item
-  // pair0 + pr
+  // pair0 + pr.  Channels-last: the (L, C) blocks of the pair's two batch items
   const typename Io<IO>::T* r0;
   bool has1 = false;
   unsigned len;
-  if (a.from_kernel) {
+  if constexpr (NLC) {
+    const int b0 = CX ? a.pair0 + (int)pr_nlc : 2 * (a.pair0 + (int)pr_nlc);
+    r0 = io_ptr<IO>(a.src) + (size_t)b0 * a.C * a.L * EW;
+    has1 = !CX && b0 + 1 < a.B;
+    len = (unsigned)a.L;
+  } else if (a.from_kernel) {
     r0 = io_ptr<IO>(a.src) + (size_t)row * a.K * EW;
     len = (unsigned)a.K;
   } else {
@@ -120,15 +152,17 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
     has1 = !CX && b0 + 1 < a.B;
     len = (unsigned)a.L;
   }
-  const BufRsrc s0 = make_rsrc(r0, len * ES);
-  const BufRsrc s1 = make_rsrc(has1 ? r0 + (size_t)a.C * a.L : r0, len * ES);
+  const unsigned sbytes = NLC ? len * (unsigned)a.C * ES : len * ES;
+  const BufRsrc s0 = make_rsrc(r0, sbytes);
+  const BufRsrc s1 = make_rsrc(has1 ? r0 + (size_t)a.C * a.L : r0, sbytes);
   {
-    // lanes run over the NSEQ neighbouring columns first; every sample of the thread is requested before the first is
-    // stored; positions outside the data get an offset outside the resource and read as zero
+    // lanes run over the NSEQ neighbouring columns first (channels-last: over the NC channels first, then the NN
+    // columns); every sample of the thread is requested before the first is stored; positions outside the data -- and
+    // the channels past C of the last channel block -- get an offset outside the resource and read as zero
     f2 val[P];
     const auto offset = [&](int u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
-      const int p = (n1 << a.lgN2) + n20 + r;
+      const int p = (n1 << a.lgN2) + n20 + (NLC ? r / M : r);
       if constexpr (!MAP) {
         const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
         const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
@@ -137,7 +171,7 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
         // (every branch below is wave-uniform: it tests launch arguments)
         int s;
         bool ok;
-        if (a.from_kernel) {
+        if (!NLC && a.from_kernel) {               // (a channels-last launch never reads filter rows)
           const unsigned q = fdiv((unsigned)p, a.d_tdil);
           ok = p < a.kpos && q * a.d_tdil.d == (unsigned)p;
           s = a.tap0 + a.tstep * (int)q;
@@ -154,7 +188,12 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
           else if (a.pad_mode == PAD_REPLICATE) s = pos < 0 ? 0 : (pos >= n ? n - 1 : pos);
           else if (a.pad_mode == PAD_CIRCULAR) s = pos < 0 ? pos + n : (pos >= n ? pos - n : pos);
         }
-        return ok ? (unsigned)s * ES : 0x80000000u;
+        if constexpr (NLC) {                       // sample s of channel c0 + rc lies at s * C + c samples
+          const unsigned c = c0 + (unsigned)(r & (M - 1));
+          return ok && c < (unsigned)a.C ? ((unsigned)s * (unsigned)a.C + c) * ES : 0x80000000u;
+        } else {
+          return ok ? (unsigned)s * ES : 0x80000000u;
+        }
       }
     };
     if constexpr (CX) {
@@ -188,7 +227,11 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
 #pragma unroll
     for (int u = 0; u < P; ++u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
-      lds[r * LSEQP + G::nat(n1)] = val[u];
+      if constexpr (NLC) {                       // slot (rc, rn) = rc * NN + rn
+        lds[((r & (M - 1)) * NN + r / M) * LSEQP + G::nat(n1)] = val[u];
+      } else {
+        lds[r * LSEQP + G::nat(n1)] = val[u];
+      }
     }
   }
   __syncthreads();
@@ -201,14 +244,18 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   // twiddle w_N^(n2*k1) and store: NSEQ neighbouring n2 per k1
   const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
   const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
-  const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8));
+  // (channels-last: one resource over the block's workspace rows, the NC of them or those up to channel C - 1; the
+  // lanes run over the NN columns first, slot r = (r / NN, r % NN).  NC * N <= 8192 * 4096 points: 2^28 bytes)
+  const unsigned wrows = NLC ? min((unsigned)M, (unsigned)a.C - c0) : 1u;
+  const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8) * wrows);
 #pragma unroll
   for (int u = 0; u < P; ++u) {
     const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
-    const unsigned n2 = (unsigned)(n20 + r);
+    const unsigned n2 = (unsigned)(n20 + (NLC ? r & (NN - 1) : r));
     const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
     const f2 z = lds[r * LSEQP + G::nat(k1)];
-    buf_store_f32x2(cmul(z, w), orr, (((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
+    const unsigned wrow = NLC ? (unsigned)(r / NN) * (unsigned)N : 0u;
+    buf_store_f32x2(cmul(z, w), orr, (wrow + ((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
   }
 }
 
@@ -311,10 +358,14 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
+  constexpr bool NLC = NC > 0;                  // channels-last y, the block map of long_cols_fwd
+  constexpr int M = NLC ? NC : 1;
+  constexpr int NN = NSEQ / M;
+  static_assert(!NLC || (MAP && NC <= NSEQ && (NC & (NC - 1)) == 0), "channels-last: the mapped form, NC * NN == NSEQ");
   const Io<IO> io(a.y_io);
   constexpr unsigned ES = CX ? 8u : Io<IO>::B;  // bytes per sample of y
   constexpr int EW = CX ? 2 : 1;                // elements of Io<IO>::T per sample
@@ -325,22 +376,43 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
   const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
   const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
-  unsigned row;
-  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  unsigned row;                                 // (channels-last: row and o of the block's first channel)
+  int n20;
+  [[maybe_unused]] unsigned o_nlc = 0, pr_nlc = 0;
+  if constexpr (!NLC) {
+    n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  } else {
+    unsigned q;
+    o_nlc = fdivmod(blockIdx.x, a.d_ncb, &q) * NC;
+    n20 = (int)fdivmod(q, a.d_nblk, &pr_nlc) * NN;
+    row = pr_nlc * (unsigned)a.C + o_nlc;
+  }
   const size_t N = (size_t)a.N1 << a.lgN2;
   unsigned pr;
-  const unsigned o = fdivmod(row, a.d_c, &pr);
+  unsigned o;
+  if constexpr (!NLC) {
+    o = fdivmod(row, a.d_c, &pr);
+  } else {
+    o = o_nlc;
+    pr = pr_nlc;
+  }
   const int b0 = CX ? a.pair0 + (int)pr : 2 * (a.pair0 + (int)pr);      // (complex build: one batch item per row)
   const bool has1 = !CX && b0 + 1 < a.B;
   f2 wtw[P];
   passA_twiddle_fetch<G>(wtw, tseq, twA);
   {
-    const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, (unsigned)(N * 8));
+    // (channels-last: the block's workspace rows behind one resource, rows of channels past C read as zero)
+    unsigned wbytes = (unsigned)(N * 8);
+    if constexpr (NLC) wbytes *= min((unsigned)M, (unsigned)a.C - o);
+    const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, wbytes);
     f2 val[P];
 #pragma unroll
     for (int u = 0; u < P; ++u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
-      val[u] = buf_load_f32x2(sr, (((unsigned)k1 << a.lgN2) + (unsigned)(n20 + r)) * 8u, 0);
+      if constexpr (NLC)
+        val[u] = buf_load_f32x2(sr, ((unsigned)(r / NN) * (unsigned)N + ((unsigned)k1 << a.lgN2) + (unsigned)(n20 + (r & (NN - 1)))) * 8u, 0);
+      else
+        val[u] = buf_load_f32x2(sr, (((unsigned)k1 << a.lgN2) + (unsigned)(n20 + r)) * 8u, 0);
     }
 #pragma unroll
     for (int u = 0; u < P; ++u) {
@@ -360,24 +432,39 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
     for (int k = 0; k < P; ++k) lseq[G::nat(nbase + P * k)] = v[k];
   }
   __syncthreads();
-  float b = a.bias ? a.bias[o * EW] : 0.f;
+  // (channels-last: the lanes run over the channels first and NT is a multiple of NSEQ, so a thread stores to one
+  // channel, o + tid % NC, and holds that channel's bias; a channel past C reads the last one's and stores nothing)
+  unsigned oc = o;
+  if constexpr (NLC) oc = min(o + (unsigned)(tid & (M - 1)), (unsigned)a.C - 1u);
+  float b = a.bias ? a.bias[oc * EW] : 0.f;
   asm volatile("" : "+v"(b));
   [[maybe_unused]] float bi = 0.f;              // complex build: the bias is Cout (re, im) pairs
   if constexpr (CX) {
-    bi = a.bias ? a.bias[o * 2 + 1] : 0.f;
+    bi = a.bias ? a.bias[oc * 2 + 1] : 0.f;
     asm volatile("" : "+v"(bi));
   }
   // (the bias is added in float32; a 16-bit y is rounded once, at the store)
-  typename Io<IO>::T* y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout * EW;
-  const BufRsrc o0 = make_rsrc(y0, (unsigned)a.nout * ES);
-  const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, (unsigned)a.nout * ES);
+  typename Io<IO>::T* y0;                       // (channels-last: the (nout, C) blocks of the pair's two batch items)
+  unsigned ybytes;
+  if constexpr (NLC) {
+    y0 = io_ptr<IO>(a.y) + (size_t)b0 * a.C * a.nout * EW;
+    ybytes = (unsigned)a.nout * (unsigned)a.C * ES;
+  } else {
+    y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout * EW;
+    ybytes = (unsigned)a.nout * ES;
+  }
+  const BufRsrc o0 = make_rsrc(y0, ybytes);
+  const BufRsrc o1 = make_rsrc(has1 ? y0 + (size_t)a.C * a.nout : y0, ybytes);
 #pragma unroll
   for (int u = 0; u < P; ++u) {
     const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
-    const f2 z = lds[r * LSEQP + G::nat(n1)];
-    const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
+    const f2 z = lds[(NLC ? (r & (M - 1)) * NN + r / M : r) * LSEQP + G::nat(n1)];
+    const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + (NLC ? r / M : r));
     unsigned off;
-    if constexpr (!MAP) {
+    if constexpr (NLC) {
+      const unsigned q = fdiv(t, a.d_ostep), c = o + (unsigned)(r & (M - 1));
+      off = (q * a.d_ostep.d == t && q < (unsigned)a.nout && c < (unsigned)a.C) ? (q * (unsigned)a.C + c) * ES : 0x80000000u;
+    } else if constexpr (!MAP) {
       off = t < (unsigned)a.nout ? t * ES : 0x80000000u;     // (samples past the kept window: dropped)
     } else {
       const unsigned q = fdiv(t, a.d_ostep);                 // (and those between the kept ones)
@@ -411,6 +498,14 @@ struct LongImpl {
   hipError_t (*cols_inv_cx)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*cols_fwd_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
   hipError_t (*cols_inv_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
+  // the channels-last builds of the column passes (mapped form; they serve plain launches too): signal / y of batch
+  // items' (L, C) blocks, float32, 16-bit and complex64.  `pairs`: batch pairs (complex: items) of the launch; a.C as ever
+  hipError_t (*cols_fwd_nlc)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_inv_nlc)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_fwd_nlc_h16)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_inv_nlc_h16)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_fwd_nlc_cx)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_inv_nlc_cx)(const LongArgs& a, long long pairs, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

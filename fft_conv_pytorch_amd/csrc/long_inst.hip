@@ -1,5 +1,5 @@
-// long_inst.hip -- instantiates the three kernels of long1d.hpp (the two column kernels in six builds each: float32,
-// 16-bit, one build for float16 and bfloat16, and complex64, each plain and mapped) for ONE tile geometry (P, S): built once per geometry
+// long_inst.hip -- instantiates the three kernels of long1d.hpp (the two column kernels in nine builds each: float32,
+// 16-bit, one build for float16 and bfloat16, and complex64, each plain, mapped and channels-last) for ONE tile geometry (P, S): built once per geometry
 // with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
@@ -85,6 +85,50 @@ hipError_t cols_inv_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
   return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true>>(a, a.N2 / kNSEQ, rows, st);
 }
 
+
+// ---- channels-last (long1d.hpp): NC neighbouring channels x NSEQ / NC neighbouring n2 columns per workgroup.  NC makes
+// a time sample's run 16 bytes long on the tensor side, as far as the NSEQ sequences go (the splits tried: DESIGN 4.7)
+constexpr int nlc_nc(int es) {
+  const int nc = 16 / es;
+  return nc < 1 ? 1 : (nc > kNSEQ ? kNSEQ : nc);
+}
+constexpr int kNC32 = nlc_nc(4), kNC16 = nlc_nc(2), kNC64 = nlc_nc(8);
+
+template <auto Kernel, int NC>
+hipError_t launch_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (pairs <= 0 || a.C <= 0) return hipErrorInvalidValue;
+  const long long ncb = (a.C + NC - 1) / NC, nblk = a.N2 / (kNSEQ / NC);
+  LongArgs b = a;
+  b.d_ncb = make_fastdiv((unsigned)ncb);
+  b.d_nblk = make_fastdiv((unsigned)nblk);
+  return launch_kernel<Kernel>(pairs * nblk * ncb, kNT, kLds, st, b);
+}
+
+hipError_t cols_fwd_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || a.src_io != 0 || a.from_kernel) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, false, kNC32>, kNC32>(a, pairs, st);
+}
+hipError_t cols_inv_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, false, kNC32>, kNC32>(a, pairs, st);
+}
+hipError_t cols_fwd_nlc_h16(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || !io_is_h16(a.src_io) || a.from_kernel) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true, false, kNC16>, kNC16>(a, pairs, st);
+}
+hipError_t cols_inv_nlc_h16(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true, false, kNC16>, kNC16>(a, pairs, st);
+}
+hipError_t cols_fwd_nlc_cx(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || a.src_io != IO_CODE_C64 || a.from_kernel) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true, kNC64>, kNC64>(a, pairs, st);
+}
+hipError_t cols_inv_nlc_cx(const LongArgs& a, long long pairs, hipStream_t st) {
+  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
+  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true, kNC64>, kNC64>(a, pairs, st);
+}
+
 }  // namespace
 
 #define FC_CAT_(a, b, c, d) a##b##c##d
@@ -92,7 +136,9 @@ hipError_t cols_inv_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
   static const LongImpl impl = {kT, kNSEQ, kOB, cols_fwd, rows, cols_inv, cols_fwd_h16, cols_inv_h16,
                                 cols_fwd_map, cols_inv_map, cols_fwd_map_h16, cols_inv_map_h16,
-                                cols_fwd_cx, cols_inv_cx, cols_fwd_map_cx, cols_inv_map_cx};
+                                cols_fwd_cx, cols_inv_cx, cols_fwd_map_cx, cols_inv_map_cx,
+                                cols_fwd_nlc, cols_inv_nlc, cols_fwd_nlc_h16, cols_inv_nlc_h16,
+                                cols_fwd_nlc_cx, cols_inv_nlc_cx};
   return &impl;
 }
 

@@ -406,10 +406,34 @@ def _resolved(t: Tensor) -> Tensor:
     return t.resolve_conj().resolve_neg() if t.is_complex() else t
 
 
+def _long_layout(t: Tensor) -> str:
+    """How the long-path kernels take a (B, C, L) tensor (pure: strides and sizes only, any device):
+    ``"ncl"``  contiguous -- read where it lies, as ever;
+    ``"nlc"``  strides exactly (L*C, 1, C) and not contiguous: ``u.transpose(1, 2)`` of a contiguous (B, L, C) tensor, at
+               any storage offset -- read where it lies by the channels-last builds of the column kernels;
+    ``"copy"`` anything else (a slice, an expanded or time-strided view): ``.contiguous()`` first."""
+    if t.is_contiguous():
+        return "ncl"
+    if t.ndim == 3 and tuple(t.stride()) == (t.shape[2] * t.shape[1], 1, t.shape[1]):
+        return "nlc"
+    return "copy"
+
+
+def _long_nlc_enabled() -> bool:
+    """FFTCONV_LONG_NLC=0 (read per call): every strided tensor is copied and a channels-last result is one torch copy."""
+    return os.environ.get("FFTCONV_LONG_NLC", "1") != "0"
+
+
+def _as_channels_last(t: Tensor) -> Tensor:
+    """(B, C, L) values with strides (L*C, 1, C): one torch copy, none if ``t`` already lies so."""
+    return t.transpose(1, 2).contiguous().transpose(1, 2)
+
+
 def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: int, pad_right: int, flip: bool,
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
               out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
-              out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False) -> Tensor:
+              out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False,
+              channels_last: bool = False) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
     u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
@@ -422,8 +446,17 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
 
     complex64 ``signal``, ``kernel`` and ``bias`` (all three) run a complex plan: plain bilinear product, complex64 result,
     the bias read as Cout (re, im) pairs.  ``conj_signal`` / ``conj_kernel`` make that plan read conj(signal) / conj(kernel)
-    (a sign flip as the kernels load; the gradients use it).  Lazy conjugates are resolved here."""
-    signal = _resolved(signal.detach()).contiguous()
+    (a sign flip as the kernels load; the gradients use it).  Lazy conjugates are resolved here.
+
+    A signal that lies as a contiguous (B, L, C) tensor (``_long_layout`` "nlc") is read where it lies, and
+    ``channels_last=True`` has the kernels write the result with strides (nout*Cout, 1, Cout); the two are independent.
+    Either falls back to a torch copy under FFTCONV_LONG_NLC=0 and where one batch item's block reaches 2**31 bytes."""
+    signal = _resolved(signal.detach())
+    native = _long_nlc_enabled()
+    x_nlc = (native and _long_layout(signal) == "nlc"
+             and signal.shape[1] * signal.shape[2] * signal.element_size() < _native.LONG_NLC_MAX_BYTES)
+    if not x_nlc:
+        signal = signal.contiguous()
     cx = signal.dtype == torch.complex64
     out_dtype = signal.dtype if out_dtype is None or cx else out_dtype
     plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
@@ -437,13 +470,25 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
         bias_c = _resolved(bias.detach()).contiguous()
     else:
         bias_c = bias.detach().float().contiguous()
+    batch, cout, nout = int(signal.shape[0]), int(kernel.shape[0]), plan.out_len
     with torch.cuda.device(signal.device):
-        out = torch.empty((signal.shape[0], kernel.shape[0], plan.out_len), dtype=out_dtype, device=signal.device)
+        y_nlc = bool(channels_last) and native
+        if y_nlc:
+            out = torch.empty((batch, nout, cout), dtype=out_dtype, device=signal.device)
+            y_nlc = nout * cout * out.element_size() < _native.LONG_NLC_MAX_BYTES
+            out = out.transpose(1, 2) if y_nlc else out.view(batch, cout, nout)
+        else:
+            out = torch.empty((batch, cout, nout), dtype=out_dtype, device=signal.device)
         ws = new_workspace(plan, signal.device)
         stream = torch.cuda.current_stream(signal.device).cuda_stream
-        plan.forward(signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                     out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out_dtype])
-    return out
+        args = (signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
+                out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out_dtype])
+        if x_nlc or y_nlc:
+            plan.forward_lay(*args, _native.LONG_NLC if x_nlc else _native.LONG_NCL,
+                             _native.LONG_NLC if y_nlc else _native.LONG_NCL)
+        else:
+            plan.forward(*args)
+    return _as_channels_last(out) if channels_last and not y_nlc else out
 
 
 def _long_int(name: str, value) -> int:
@@ -511,7 +556,8 @@ def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal
 
 
 def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
-                  causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant") -> Tensor:
+                  causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant",
+                  channels_last: bool = False) -> Tensor:
     """1-D convolution with a filter as long as the row: ONE transform over the whole padded row (as the reference does,
     functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
 
@@ -535,16 +581,28 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     argument keeps its meaning, the output is complex64 of the same length, arithmetic and spectra are float32.  The
     gradients follow PyTorch's convention for complex tensors.  Lazy conjugates (``x.conj()``) are resolved on entry.
 
+    Sequence models keep (batch, length, channels) activations.  A ``signal`` that is ``u.transpose(1, 2)`` of a contiguous
+    (B, L, C) tensor ``u`` (strides exactly (L*C, 1, C), any storage offset) is read where it lies, with no copy, and
+    ``channels_last=True`` returns the (B, Cout, nout) result with strides (nout*Cout, 1, Cout), so that
+    ``y.transpose(1, 2)`` is a contiguous (B, nout, Cout) tensor; input and output layout are independent.  The values
+    have the bits of the call on contiguous tensors.  In backward a dY that lies that way is read where it lies and dX
+    gets the signal's layout; the weight gradient's transposed operands are torch copies as ever.  Other non-contiguous
+    tensors are copied.  ``FFTCONV_LONG_NLC=0`` (read per call) takes torch copies everywhere, as do rows that hand off
+    to ``fft_conv``, the ``FFTCONV_HALF_IO=0`` path and tensors whose (L, C) block of one batch item reaches 2**31 bytes.
+
     Real rows whose padded length is at most 4096 run the ``fft_conv`` kernels (complex rows stay here, at 64 x 64 points);
     a row that needs more than 2**24 points raises ``NotImplementedError``.  float64 and complex128 tensors, tensors of
     different dtypes and mixes of real and complex tensors are not taken by this path (``TypeError``)."""
-    return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode)
+    return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode,
+                               channels_last)
 
 
 def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum, stride=1, dilation=1,
-                        padding_mode="constant"):
+                        padding_mode="constant", channels_last=False):
     pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal, stride, dilation, padding_mode)
     stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
+    if not isinstance(channels_last, bool):
+        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
     if need > LONG_MAX_POINTS:
         raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
                                   f"2**24 = {LONG_MAX_POINTS}")
@@ -558,21 +616,24 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
     if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
         # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out (what a caller would write by hand)
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
-                                  causal, None, stride, dilation, padding_mode)
-        return out.to(signal.dtype)
+                                  causal, None, stride, dilation, padding_mode, channels_last)
+        return out.to(signal.dtype)          # (keeps the strides)
     if need <= LONG_HANDOFF_POINTS and signal.dtype != torch.complex64:      # (fft_conv has no complex route)
         if not causal:
-            return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
-        # taps at a lag of L or more never reach the output
-        taps = min(int(kernel.shape[2]), (int(signal.shape[2]) - 1) // dilation + 1)
-        padded = torch.nn.functional.pad(signal, (dilation * (taps - 1), 0))
-        return _fft_conv_impl(padded, kernel[..., :taps].flip(-1), bias, stride, 0, dilation, groups, "constant", None)
+            out = _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
+        else:
+            # taps at a lag of L or more never reach the output
+            taps = min(int(kernel.shape[2]), (int(signal.shape[2]) - 1) // dilation + 1)
+            padded = torch.nn.functional.pad(signal, (dilation * (taps - 1), 0))
+            out = _fft_conv_impl(padded, kernel[..., :taps].flip(-1), bias, stride, 0, dilation, groups, "constant", None)
+        return _as_channels_last(out) if channels_last else out
     if _needs_grad(signal, kernel, bias):
         from .autograd import FFTLongConvFunction
         return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum,
-                                         stride, dilation, padding_mode)
+                                         stride, dilation, padding_mode, channels_last)
     return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
-                     spectrum, pad_mode=_native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
+                     spectrum, pad_mode=_native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
+                     channels_last=channels_last)
 
 
 def _long_keep(length: int, causal: bool, stride: int) -> int:

@@ -189,10 +189,16 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
     ``nn.Conv1d`` stores them.  The kernel spectrum is cached
     under the rules of ``_SpectrumCache``, for a float32 module and for one in float16 / bfloat16 (``module.bfloat16()``:
     the kernels read the 16-bit weight and signal and write a 16-bit output; the cached spectrum stays float32) or in
-    complex64 (``dtype=torch.complex64`` / ``.to(torch.complex64)``; state_dict interchanges with a complex ``nn.Conv1d``)."""
+    complex64 (``dtype=torch.complex64`` / ``.to(torch.complex64)``; state_dict interchanges with a complex ``nn.Conv1d``).
+
+    ``channels_last=True`` (keyword-only; an attribute, not part of the state_dict) returns the (B, Cout, nout) result with
+    strides (nout*Cout, 1, Cout), as ``fft_long_conv`` does: ``y.transpose(1, 2)`` is then contiguous, ready for the
+    ``nn.Linear`` of a sequence model.  A signal that lies that way is read where it lies whatever this says."""
+
+    channels_last = False      # (the default of a module pickled before the attribute existed)
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
-                 dtype=None, *, stride=1, dilation=1, padding_mode="zeros"):
+                 dtype=None, *, channels_last=False, stride=1, dilation=1, padding_mode="zeros"):
         if causal and not (isinstance(padding, int) and padding == 0):
             raise ValueError("causal=True pads the row itself: padding must be 0")
         if causal and padding_mode != "zeros":
@@ -200,9 +206,13 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                          groups=groups, bias=bias, padding_mode=padding_mode, device=device, dtype=dtype)
         self.causal = bool(causal)
+        if not isinstance(channels_last, bool):
+            raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+        self.channels_last = channels_last
 
     def extra_repr(self):
-        return super().extra_repr() + (", causal=True" if self.causal else "")
+        return (super().extra_repr() + (", causal=True" if self.causal else "")
+                + (", channels_last=True" if self.channels_last else ""))
 
     def forward(self, signal: Tensor):
         padding = self.padding if isinstance(self.padding, str) else int(self.padding[0])
@@ -222,4 +232,4 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
                                  pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
             spectrum = self._cached_spectrum(plan)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
-                                      padding_mode)
+                                      padding_mode, self.channels_last)

@@ -304,6 +304,22 @@ int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, i
 /* The kind bits a plan was made with (-1: NULL plan). */
 int fc_long_plan_kind(const fc_long_plan* plan);
 
+/* Channels-last tensors (ABI 7 extension: a new entry point only; every call above keeps its signature and meaning, and
+ * fc_long_forward_io is this call with both layouts FC_LONG_NCL).  The layout of x and of y is an argument of the call,
+ * like their element types: the plan, its tables, spectrum, workspace, slabs and launch count do not depend on it.
+ *   FC_LONG_NCL  x (B, Cin, L), y (B, Cout, nout) contiguous, as everywhere above
+ *   FC_LONG_NLC  element (b, c, t) of x lies at ((b*L + t)*Cin + c) samples from x, element (b, o, j) of y at
+ *                ((b*nout + j)*Cout + o) samples from y: contiguous (B, L, Cin) / (B, nout, Cout) tensors
+ * The two layouts are independent of each other and of the dtypes; any channel count is taken.  The tensors are read and
+ * written where they lie -- no transposed copy is made -- and the result has the bits of the FC_LONG_NCL call on
+ * transposed copies.  Every sample of the kept window of y is written and no other byte.  One batch item's block lies
+ * behind one 32-bit buffer resource, so L * Cin * (bytes per sample of x) and nout * Cout * (bytes per sample of y) must
+ * stay below 2^31 for a channels-last tensor: beyond that FC_ERR_UNSUPPORTED, the text naming the size (pass a (B, C, L)
+ * copy).  Any other layout code: FC_ERR_INVALID with text.  weight and bias are what they were. */
+enum fc_long_layout { FC_LONG_NCL = 0, FC_LONG_NLC = 1 };
+int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, int x_layout, const void* spectrum,
+                         const float* bias, void* y, int y_dtype, int y_layout, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,13 +271,16 @@ int plan_io_code(const fc_long_plan* plan, int dtype, const char* what, int* cod
   return FC_OK;
 }
 
+// bytes per sample of an element code
+int64_t io_bytes(int io) { return io == IO_CODE_C64 ? 8 : (io ? 2 : 4); }
+
 // a layout code of fc_long_forward_lay, and the size a channels-last tensor may have: one batch item's (len, channels)
 // block lies behind one buffer resource whose offsets from 2^31 on mean "outside"
 int layout_check(int layout, const char* what, int64_t len, int64_t channels, int io) {
   if (layout == FC_LONG_NCL) return FC_OK;
   if (layout != FC_LONG_NLC)
     return fail(FC_ERR_INVALID, "%s has layout code %d; expected FC_LONG_NCL (0) or FC_LONG_NLC (1)", what, layout);
-  const int64_t es = io == IO_CODE_C64 ? 8 : (io ? 2 : 4);
+  const int64_t es = io_bytes(io);
   const int64_t bytes = len * channels * es;
   if (bytes >= (int64_t)1 << 31)
     return fail(FC_ERR_UNSUPPORTED, "%s in the channels-last layout: one batch item is %lld samples x %lld channels x %lld "
@@ -354,13 +357,7 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
   if (!plan || !weight || !spectrum || !workspace) return fail(FC_ERR_INVALID, "null argument");
   int wio = 0;
   if (int e = plan_io_code(plan, weight_dtype, "weight", &wio)) return e;
-  const bool cx = wio == IO_CODE_C64;
-  const size_t wes = cx ? 8 : (wio ? 2 : 4);
   const LongGeom& g = plan->g;
-  const LongImpl& c = *plan->cols;
-  // (the mapped build only where the taps are spread)
-  const auto cols_fwd = cx ? (g.dil > 1 ? c.cols_fwd_map_cx : c.cols_fwd_cx)
-                           : g.dil > 1 ? (wio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (wio ? c.cols_fwd_h16 : c.cols_fwd);
   hipStream_t st = (hipStream_t)hip_stream;
   // the filter rows go through the workspace a chunk at a time (it holds at least Cin + Cout >= 2 rows of N points)
   const int64_t rows_total = g.Cout * g.Cig;
@@ -373,9 +370,9 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
     a.from_kernel = 1;
     a.src_io = wio;
     a.conj_src = (g.kind & FC_LONG_CONJ_TAPS) != 0;
-    a.src = (const float*)((const char*)weight + (size_t)r0 * g.K * wes);
+    a.src = (const float*)((const char*)weight + (size_t)r0 * g.K * (size_t)io_bytes(wio));
     a.w1 = (f2*)workspace;
-    FC_HIP(cols_fwd(a, n, st));
+    FC_HIP(plan->cols->cols_fwd(a, g.dil > 1, false, n, st));      // (the mapped build only where the taps are spread)
     a.spec_mode = 1;
     a.spec_out = (f2*)spectrum + (size_t)r0 * g.N;
     FC_HIP(plan->rows->rows(a, n, st));
@@ -402,19 +399,10 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
   if (int e = plan_io_code(plan, y_dtype, "y", &yio)) return e;
   if (int e = layout_check(x_layout, "x", plan->g.L, plan->g.Cin, xio)) return e;
   if (int e = layout_check(y_layout, "y", plan->g.nout, plan->g.Cout, yio)) return e;
-  const bool cx = xio == IO_CODE_C64;
   const bool x_nlc = x_layout == FC_LONG_NLC, y_nlc = y_layout == FC_LONG_NLC;
   const LongGeom& g = plan->g;
-  const LongImpl& c = *plan->cols;
-  // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped; the
-  // channels-last builds are mapped builds and take every launch of that layout)
+  // (the mapped builds only where the row is read through a padding mode or spread, and where outputs are skipped)
   const bool map_in = g.pad_mode != PAD_CONSTANT || g.up > 1, map_out = g.step > 1;
-  const auto cols_fwd = x_nlc ? (cx ? c.cols_fwd_nlc_cx : xio ? c.cols_fwd_nlc_h16 : c.cols_fwd_nlc)
-                        : cx  ? (map_in ? c.cols_fwd_map_cx : c.cols_fwd_cx)
-                        : map_in ? (xio ? c.cols_fwd_map_h16 : c.cols_fwd_map) : (xio ? c.cols_fwd_h16 : c.cols_fwd);
-  const auto cols_inv = y_nlc ? (cx ? c.cols_inv_nlc_cx : yio ? c.cols_inv_nlc_h16 : c.cols_inv_nlc)
-                        : cx  ? (map_out ? c.cols_inv_map_cx : c.cols_inv_cx)
-                        : map_out ? (yio ? c.cols_inv_map_h16 : c.cols_inv_map) : (yio ? c.cols_inv_h16 : c.cols_inv);
   hipStream_t st = (hipStream_t)hip_stream;
   for (int64_t s = 0; s < g.slabs; ++s) {
     const int64_t pair0 = s * g.slab_pairs;
@@ -428,10 +416,10 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
     a.C = (int)g.Cin;
-    FC_HIP(cols_fwd(a, x_nlc ? np : np * g.Cin, st));      // (a channels-last launch counts pairs, not rows)
+    FC_HIP(plan->cols->cols_fwd(a, map_in, x_nlc, np, st));
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;
-    FC_HIP(cols_inv(a, y_nlc ? np : np * g.Cout, st));
+    FC_HIP(plan->cols->cols_inv(a, map_out, y_nlc, np, st));
   }
   return FC_OK;
 }

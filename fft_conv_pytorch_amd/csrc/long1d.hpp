@@ -479,33 +479,16 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   }
 }
 
-// what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan
+// what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan.  The host
+// states facts and long_inst.hip picks the build of a column pass: the element type by a.src_io (cols_fwd) / a.y_io
+// (cols_inv), the mapped build where `mapped` (padding mode, src_up, tap_dil / out_step), the channels-last build where
+// `nlc`.  `rows`: rows of the transform per channel in this launch -- batch pairs, batch items of a complex plan, or
+// filter rows with a.C == 1 -- which makes rows * a.C workgroup units, or `rows` units of a channels-last launch
 struct LongImpl {
-  int T, nseq, ob;
-  hipError_t (*cols_fwd)(const LongArgs& a, long long rows, hipStream_t st);
+  int T, ob;
+  hipError_t (*cols_fwd)(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st);
   hipError_t (*rows)(const LongArgs& a, long long units, hipStream_t st);     // units: filter rows, or pairs * G * nob
-  hipError_t (*cols_inv)(const LongArgs& a, long long rows, hipStream_t st);
-  // the 16-bit builds of the column passes: float16 and bfloat16 sources (a.src_io) / outputs (a.y_io)
-  hipError_t (*cols_fwd_h16)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_inv_h16)(const LongArgs& a, long long rows, hipStream_t st);
-  // the mapped builds of the four (padding mode, src_up, tap_dil / out_step)
-  hipError_t (*cols_fwd_map)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_inv_map)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_fwd_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_inv_map_h16)(const LongArgs& a, long long rows, hipStream_t st);
-  // the complex builds of the column passes, plain and mapped: complex64 rows, one batch item each (a.src_io / a.y_io 4)
-  hipError_t (*cols_fwd_cx)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_inv_cx)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_fwd_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
-  hipError_t (*cols_inv_map_cx)(const LongArgs& a, long long rows, hipStream_t st);
-  // the channels-last builds of the column passes (mapped form; they serve plain launches too): signal / y of batch
-  // items' (L, C) blocks, float32, 16-bit and complex64.  `pairs`: batch pairs (complex: items) of the launch; a.C as ever
-  hipError_t (*cols_fwd_nlc)(const LongArgs& a, long long pairs, hipStream_t st);
-  hipError_t (*cols_inv_nlc)(const LongArgs& a, long long pairs, hipStream_t st);
-  hipError_t (*cols_fwd_nlc_h16)(const LongArgs& a, long long pairs, hipStream_t st);
-  hipError_t (*cols_inv_nlc_h16)(const LongArgs& a, long long pairs, hipStream_t st);
-  hipError_t (*cols_fwd_nlc_cx)(const LongArgs& a, long long pairs, hipStream_t st);
-  hipError_t (*cols_inv_nlc_cx)(const LongArgs& a, long long pairs, hipStream_t st);
+  hipError_t (*cols_inv)(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

@@ -1,6 +1,7 @@
-// long_inst.hip -- instantiates the three kernels of long1d.hpp (the two column kernels in nine builds each: float32,
-// 16-bit, one build for float16 and bfloat16, and complex64, each plain, mapped and channels-last) for ONE tile geometry (P, S): built once per geometry
-// with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
+// long_inst.hip -- instantiates the three kernels of long1d.hpp for ONE tile geometry (P, S) and is the one place that
+// picks the build of a column launch (cols_dispatch: float32, 16-bit -- one build for float16 and bfloat16 -- or complex64
+// by the launch's element code, each plain, mapped or channels-last, nine builds of each column kernel): built once per
+// geometry with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
 
@@ -32,59 +33,10 @@ hipError_t launch(const LongArgs& a, int blocks_per_unit, long long units, hipSt
   return launch_kernel<Kernel>(units * blocks_per_unit, kNT, kLds, st, b);
 }
 
-hipError_t cols_fwd(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != 0) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_fwd_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.src_io)) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(a, a.N2 / kNSEQ, rows, st);
-}
 hipError_t rows(const LongArgs& a, long long units, hipStream_t st) {
   if (a.N2 != kT || a.ob != kOB) return hipErrorInvalidValue;
   return launch<long_rows_kernel<FC_P, FC_S, kNSEQ, kNT, kOB>>(a, a.N1 / kNSEQ, units, st);
 }
-hipError_t cols_inv(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_inv_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_fwd_map(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != 0) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_fwd_map_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.src_io)) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_inv_map(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_inv_map_h16(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_fwd_cx(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != IO_CODE_C64) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, false, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_inv_cx(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, false, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_fwd_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != IO_CODE_C64) return hipErrorInvalidValue;
-  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-hipError_t cols_inv_map_cx(const LongArgs& a, long long rows, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
-  return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true>>(a, a.N2 / kNSEQ, rows, st);
-}
-
 
 // ---- channels-last (long1d.hpp): NC neighbouring channels x NSEQ / NC neighbouring n2 columns per workgroup.  NC makes
 // a time sample's run 16 bytes long on the tensor side, as far as the NSEQ sequences go (the splits tried: DESIGN 4.7)
@@ -92,11 +44,9 @@ constexpr int nlc_nc(int es) {
   const int nc = 16 / es;
   return nc < 1 ? 1 : (nc > kNSEQ ? kNSEQ : nc);
 }
-constexpr int kNC32 = nlc_nc(4), kNC16 = nlc_nc(2), kNC64 = nlc_nc(8);
 
 template <auto Kernel, int NC>
 hipError_t launch_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (pairs <= 0 || a.C <= 0) return hipErrorInvalidValue;
   const long long ncb = (a.C + NC - 1) / NC, nblk = a.N2 / (kNSEQ / NC);
   LongArgs b = a;
   b.d_ncb = make_fastdiv((unsigned)ncb);
@@ -104,29 +54,32 @@ hipError_t launch_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
   return launch_kernel<Kernel>(pairs * nblk * ncb, kNT, kLds, st, b);
 }
 
-hipError_t cols_fwd_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != 0 || a.from_kernel) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, false, kNC32>, kNC32>(a, pairs, st);
+// the build of a column kernel: forward or inverse, element type (IO, CX), plain / mapped, channels-last with NC > 0
+template <bool INV, int IO, bool MAP, bool CX, int NC>
+constexpr auto cols_kernel() {
+  if constexpr (INV) return long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO, MAP, CX, NC>;
+  else return long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO, MAP, CX, NC>;
 }
-hipError_t cols_inv_nlc(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != 0) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, false, kNC32>, kNC32>(a, pairs, st);
+
+// ... of one element type, ES bytes per sample: a channels-last build is a mapped build and serves plain launches too
+template <bool INV, int IO, bool CX>
+hipError_t cols_launch(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st) {
+  constexpr int NC = nlc_nc(CX ? 8 : (int)Io<IO>::B);
+  if (nlc) return launch_nlc<cols_kernel<INV, IO, true, CX, NC>(), NC>(a, rows, st);
+  if (mapped) return launch<cols_kernel<INV, IO, true, CX, 0>()>(a, a.N2 / kNSEQ, rows * a.C, st);
+  return launch<cols_kernel<INV, IO, false, CX, 0>()>(a, a.N2 / kNSEQ, rows * a.C, st);
 }
-hipError_t cols_fwd_nlc_h16(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.src_io) || a.from_kernel) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true, false, kNC16>, kNC16>(a, pairs, st);
-}
-hipError_t cols_inv_nlc_h16(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || !io_is_h16(a.y_io)) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true, false, kNC16>, kNC16>(a, pairs, st);
-}
-hipError_t cols_fwd_nlc_cx(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || a.src_io != IO_CODE_C64 || a.from_kernel) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true, kNC64>, kNC64>(a, pairs, st);
-}
-hipError_t cols_inv_nlc_cx(const LongArgs& a, long long pairs, hipStream_t st) {
-  if (a.N1 != kT || a.y_io != IO_CODE_C64) return hipErrorInvalidValue;
-  return launch_nlc<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, true, kNC64>, kNC64>(a, pairs, st);
+
+// a column pass over `rows` rows of the transform per channel (LongImpl); the element type is that of the tensor the
+// pass touches.  A channels-last launch never reads filter rows
+template <bool INV>
+hipError_t cols_dispatch(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st) {
+  if (a.N1 != kT || rows <= 0 || a.C <= 0 || (nlc && a.from_kernel)) return hipErrorInvalidValue;
+  const int code = INV ? a.y_io : a.src_io;
+  if (code == 0) return cols_launch<INV, IO_F32, false>(a, mapped, nlc, rows, st);
+  if (io_is_h16(code)) return cols_launch<INV, IO_H16, false>(a, mapped, nlc, rows, st);
+  if (code == IO_CODE_C64) return cols_launch<INV, IO_F32, true>(a, mapped, nlc, rows, st);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -134,11 +87,7 @@ hipError_t cols_inv_nlc_cx(const LongArgs& a, long long pairs, hipStream_t st) {
 #define FC_CAT_(a, b, c, d) a##b##c##d
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
-  static const LongImpl impl = {kT, kNSEQ, kOB, cols_fwd, rows, cols_inv, cols_fwd_h16, cols_inv_h16,
-                                cols_fwd_map, cols_inv_map, cols_fwd_map_h16, cols_inv_map_h16,
-                                cols_fwd_cx, cols_inv_cx, cols_fwd_map_cx, cols_inv_map_cx,
-                                cols_fwd_nlc, cols_inv_nlc, cols_fwd_nlc_h16, cols_inv_nlc_h16,
-                                cols_fwd_nlc_cx, cols_inv_nlc_cx};
+  static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>};
   return &impl;
 }
 

@@ -347,3 +347,164 @@ for _r in ROUTES:
     if _r.name.startswith("1d-phases"):
         _r.cases.extend(PHASE_CASES)
         _r.cases[0] = Case(**{**_r.cases[0].__dict__, "grads": True, "public": True})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dX of a strided convolution is a transposed plan with up > 1: the input spread over the stride's grid.  Strided transposed
+# plans on every route that takes them (tests/test_gpu_backward_routes.py runs them through test_gpu_routes._run_case).
+# A list of its own: the files that walk ROUTES do not see these cases.
+def tile_step(c, r, ax):
+    """(valid outputs per tile, tiles) of axis ax of a plan, from its route words (a segmented 1-D plan: the tile holds
+    one segment's extent)."""
+    kd = (c.k[ax] - 1) * c.tup(c.d)[ax] + 1
+    kind = r["kind"]
+    if kind in ("f32_1d", "f64_fft_1d"):
+        T, n = r["T"], r["ntiles"]
+        if r.get("nseg", 1) > 1:
+            # segments of taps (plan_1d_inner): 1024 // d + 1 taps each, an extent of at most 1025 samples per segment
+            d = c.tup(c.d)[ax]
+            seg_taps = min(max(1, 1024 // d + 1), c.k[ax])
+            assert -(-c.k[ax] // seg_taps) == r["nseg"], (seg_taps, r)
+            kd = (seg_taps - 1) * d + 1
+    elif kind == "f32_nd":
+        T, n = ((r["T"], r["ntiles"]) if ax == 0 else (r["Tx"], r["nxt"]) if ax == c.nd - 1 else (r["Tm"], r["nyt"]))
+    else:
+        T, n = r[f"t{ax}"], r[f"nt{ax}"]
+    return T - kd + 1, n
+
+
+def seam_phases(c, r, ax):
+    """Where the tile seams of axis ax of a strided transposed plan sit on the stride's grid: input sample i lies at
+    kd - 1 - p + i * s of the padded row whose window [o, o + kd) gives output o, tile j starts at output j * V.  The set of
+    (j * V - (kd - 1 - p)) mod s over the seams; {0}: every seam on the grid."""
+    kd = (c.k[ax] - 1) * c.tup(c.d)[ax] + 1
+    V, n = tile_step(c, r, ax)
+    return {(j * V - (kd - 1 - c.tup(c.p)[ax])) % c.tup(c.s)[ax] for j in range(1, n)}
+
+
+def _t(*a, grid=None, **kw):
+    """A transposed case; grid=(axis, on), or a list of them: the case is sized so that the axis is tiled and its seams lie
+    all on the stride's grid (on) or at least one lies off it."""
+    c = Case(*a, tr=True, **kw)
+    if grid is not None:
+        grid = [grid] if isinstance(grid, tuple) else grid
+        c.expect = lambda r: all(bool(seam_phases(c, r, ax)) and (seam_phases(c, r, ax) == {0}) == on for ax, on in grid)
+    return c
+
+
+TRANSPOSED_ROUTES = [
+    # ------------------------------------------------------------------------------------------------ float32 1-D
+    # (the general kernel is the only 1-D kernel that takes up > 1; "1d-general-single" has its transposed case in ROUTES)
+    Route("1d-general-running-sum", {}, _1d(pers_nb=0, accumulate=1, chunk_launches=0, wide=0, dense=0, nseg=1), [
+        _t(2, 9, 6, (1500,), (33,), s=2, p=16, grads=True, public=True, grid=(0, True)),
+        _t(2, 9, 6, (1500,), (33,), s=2, p=15, op=1, grid=(0, False)),
+        _t(3, 12, 8, (1000,), (31,), s=3, p=4, d=2, op=2),
+        _t(2, 32, 16, (900,), (17,), s=2, p=3, op=1, g=2),
+    ]),
+    Route("1d-chunk-launches", {}, _1d(chunk_launches=1, pers_nb=0), [
+        _t(2, 20, 6, (2000,), (700,), s=2, p=100, d=3, op=1, grads=True, public=True, grid=(0, False)),
+        _t(1, 9, 4, (1500,), (1101,), s=2, d=2, grid=(0, True)),
+        _t(2, 34, 12, (1500,), (2101,), s=2, p=51, op=1, g=2, grid=(0, False)),
+    ]),
+    Route("1d-segments", {}, lambda r: _1d(diag=0)(r) and r["nseg"] > 1, [
+        _t(2, 8, 8, (6000,), (5000,), s=2, grads=True, public=True, grid=(0, False)),
+        _t(2, 16, 16, (3000,), (5000,), s=2, p=1, op=1, g=2, grid=(0, True)),
+        _t(1, 4, 6, (4000,), (3000,), s=2, p=51, d=2, op=1, grid=(0, False)),
+        _t(2, 12, 8, (3000,), (4500,), s=3, p=100, op=2),
+    ]),
+    # ------------------------------------------------------------------------------------------------ float32 N-d
+    Route("2d-separable-cob2", {"FFTCONV_PLANES": "0"}, _nd(planes=0, cob=2, Tm=0), [
+        _t(5, 2, 2, (30, 200), (5, 5), s=2, p=2, op=1, public=True),
+        _t(3, 1, 2, (30, 200), (5, 3), s=2, p=(2, 1)),
+        _t(1, 2, 2, (25, 35), (3, 5), s=(2, 3), p=1, op=(1, 2)),
+    ]),
+    Route("2d-separable-cob4", {"FFTCONV_PLANES": "0"}, _nd(planes=0, cob=4, Tm=0), [
+        _t(5, 3, 4, (30, 200), (5, 5), s=2, p=2, op=1, public=True),
+        _t(3, 4, 4, (20, 250), (3, 3), s=(1, 2), p=1),
+        _t(1, 3, 4, (17, 23), (4, 2), s=(2, 3), p=(1, 0), op=(1, 2)),
+    ]),
+    Route("2d-separable-cob8", {"FFTCONV_PLANES": "0"}, _nd(planes=0, cob=8, Tm=0), [
+        _t(5, 8, 8, (20, 200), (5, 5), s=2, p=2, op=1, public=True),
+        _t(3, 6, 9, (20, 150), (3, 7), s=(1, 2), p=(1, 3), note="cog9"),
+        _t(2, 32, 16, (20, 50), (3, 3), s=2, p=1, d=2, op=1, g=2, note="g2"),
+        _t(2, 17, 8, (10, 25), (3, 3), s=2, p=1, note="cig17"),
+    ]),
+    Route("2d-x-tiles", {"FFTCONV_PLANES": "0"}, lambda r: _nd(planes=0, Tm=0)(r) and r["nxt"] > 1, [
+        _t(2, 4, 4, (30, 300), (3, 7), s=(1, 2), p=(1, 3), public=True, grid=(1, False)),
+        _t(2, 4, 4, (30, 300), (3, 7), s=(1, 2), p=(1, 2), op=(0, 1), g=2, grid=(1, True)),
+        _t(1, 2, 3, (8, 1700), (3, 65), s=(1, 3), p=(1, 32), op=(0, 2)),
+    ]),
+    Route("2d-outer-tiles", {"FFTCONV_PLANES": "0"}, lambda r: _nd(planes=0, Tm=0)(r) and r["ntiles"] > 1, [
+        _t(1, 2, 3, (1000, 9), (40, 3), s=(3, 1), p=(5, 1), d=(2, 1), public=True, grid=(0, False)),
+        _t(2, 4, 4, (1200, 20), (65, 3), s=(2, 1), p=(32, 1), op=(1, 0), grid=(0, True)),
+        _t(2, 4, 4, (1200, 20), (65, 3), s=(2, 1), p=(31, 1), g=2, grid=(0, False)),
+    ]),
+    Route("2d-colz-b1", {"FFTCONV_PLANES": "2"}, _nd(planes=2), [
+        _t(1, 8, 8, (50, 100), (5, 5), s=2, p=2, op=1, public=True),
+        _t(1, 6, 5, (32, 65), (3, 3), s=2, p=1),
+        _t(1, 8, 16, (35, 50), (5, 3), s=(2, 3), p=(2, 1), op=(1, 2)),
+    ]),
+    Route("2d-colz-b2", {"FFTCONV_PLANES": "2"}, _nd(planes=2), [
+        _t(2, 8, 8, (50, 100), (5, 5), s=2, p=2, op=1, public=True),
+        _t(3, 6, 5, (32, 65), (3, 3), s=2, p=1),
+        _t(5, 16, 8, (20, 48), (7, 3), s=(2, 3), p=(3, 1), op=(1, 2), g=2),
+    ]),
+    Route("3d-separable-y-tiles", {"FFTCONV_PLANES": "0"}, lambda r: _nd(planes=0)(r) and r["nyt"] > 1, [
+        _t(1, 2, 3, (8, 260, 20), (3, 7, 3), s=(1, 2, 1), p=(1, 3, 1), d=(1, 2, 1), public=True, grid=(1, False)),
+        _t(2, 4, 4, (6, 300, 10), (3, 5, 3), s=(1, 2, 1), p=(1, 2, 1), op=(0, 1, 0), g=2, grid=(1, True)),
+    ]),
+    Route("3d-planes-untiled", {}, lambda r: _nd(planes=1)(r) and r["nxt"] * r["nyt"] == 1, [
+        _t(2, 8, 8, (10, 20, 20), (3, 3, 3), s=2, p=1, op=1, public=True),
+        _t(1, 8, 16, (15, 33, 16), (5, 3, 2), s=(2, 1, 3), p=(2, 1, 0), op=(1, 0, 2)),
+        _t(3, 6, 6, (17, 16, 20), (2, 3, 3), s=(1, 2, 1), p=1),
+    ]),
+    Route("3d-planes-tiled", {}, lambda r: _nd(planes=1, Tx=64, Tm=64)(r) and r["nxt"] * r["nyt"] > 1, [
+        _t(2, 8, 8, (20, 50, 65), (3, 5, 5), s=(1, 2, 2), p=2, op=(0, 1, 1), public=True, grid=[(1, True), (2, True)]),
+        _t(2, 8, 8, (20, 50, 65), (3, 5, 5), s=(1, 2, 2), p=(2, 1, 1), grid=[(1, False), (2, False)]),
+        _t(1, 8, 16, (30, 35, 30), (5, 3, 7), s=(1, 2, 3), p=(2, 1, 3), op=(0, 1, 2)),
+    ]),
+    # ------------------------------------------------------------------------------------------------ float64
+    Route("f64-direct", {}, _f64("f64_direct"), [
+        _t(2, 3, 4, (10, 15), (3, 3), s=2, p=1, op=1, f64=True, public=True, grads=True),
+        _t(3, 4, 6, (250,), (9,), s=2, p=4, d=2, g=2, f64=True),
+        _t(2, 2, 2, (4, 5, 6), (2, 3, 2), s=2, p=1, op=1, f64=True),
+    ]),
+    Route("f64-nd-nb1", {}, _f64("f64_fft_nd", nb=1), [
+        _t(2, 4, 9, (15, 20), (7, 7), s=2, p=3, op=1, f64=True, public=True, grads=True, note="cog9", grid=(0, False)),
+        _t(1, 4, 2, (15, 20), (7, 7), s=2, p=2, f64=True, grid=(1, True)),
+        _t(2, 4, 6, (6, 7, 5), (3, 3, 3), s=2, p=1, op=1, f64=True),
+    ]),
+    Route("f64-nd-nb2", {}, _f64("f64_fft_nd", nb=2), [
+        _t(3, 4, 3, (15, 20), (7, 7), s=2, p=3, op=1, f64=True, public=True, grads=True, grid=(1, False)),
+        _t(2, 9, 4, (11, 17), (7, 7), s=(2, 3), p=(3, 2), f64=True),
+        _t(2, 6, 4, (5, 6, 7), (3, 3, 4), s=2, p=1, op=1, g=2, f64=True),
+    ]),
+    Route("f64-nd-nb4", {}, _f64("f64_fft_nd", nb=4), [
+        _t(5, 4, 2, (15, 20), (7, 7), s=2, p=3, op=1, f64=True, public=True, grads=True, note="rem1"),
+        _t(6, 4, 2, (13, 16), (7, 7), s=2, p=2, f64=True, note="rem2", grid=(0, True)),
+        _t(7, 6, 2, (5, 6, 7), (3, 3, 3), s=2, p=1, op=1, f64=True, note="rem3"),
+        _t(4, 4, 4, (10, 11), (7, 8), s=2, p=1, op=1, g=2, f64=True, note="g2"),
+    ]),
+    Route("f64-2048-tiles", {}, lambda r: (r["kind"] == "f64_fft_1d" and r["T"] == 2048) or
+          (r["kind"] == "f64_fft_nd" and 2048 in (r["t0"], r["t1"], r["t2"])), [
+        _t(2, 2, 3, (2500,), (601,), s=2, p=10, op=1, f64=True, public=True, grads=True, grid=(0, True)),
+        _t(2, 2, 3, (2500,), (601,), s=2, p=11, f64=True, grid=(0, False)),
+        _t(1, 1, 2, (10, 1250), (3, 513), s=(1, 2), p=(1, 0), d=(1, 2), op=(0, 1), f64=True, grid=(1, True)),
+        _t(1, 1, 2, (10, 1250), (3, 513), s=(1, 2), p=(1, 1), d=(1, 2), f64=True, grid=(1, False)),
+    ]),
+]
+
+# The batch-sharing, wide, dense, depthwise and block-diagonal 1-D kernels refuse strided transposed plans (the
+# d.stride[0] == 1 conditions of csrc/host_1d.cpp: a tile of theirs starts anywhere on the spread row), so TRANSPOSED_ROUTES
+# has no entry for them.  Under each route's knobs the strided plan must land on a general route, and the stride-1 plan of
+# the same shape on the route itself ((name, knobs, strided transposed case, the route's own predicate)).
+GENERAL_1D = _1d(pers_nb=0, wide=0, dense=0, diag=0, bd_gs=0)
+TRANSPOSED_REFUSED = [
+    ("batch-sharing-nb2", {"FFTCONV_PERS": "2"}, _t(3, 8, 8, (1000,), (129,), s=2, op=1), _1d(pers_nb=2)),
+    ("batch-sharing-nb4", {"FFTCONV_PERS": "4"}, _t(5, 8, 8, (1000,), (129,), s=2, op=1), _1d(pers_nb=4)),
+    ("wide", {}, _t(3, 16, 8, (2500,), (100,), s=2, p=16, op=1), _1d(wide=1)),
+    ("dense", {"FFTCONV_DENSE": "2"}, _t(4, 64, 64, (4500,), (129,), s=2, p=64, op=1), _1d(dense=1)),
+    ("depthwise", {}, _t(3, 24, 24, (2500,), (33,), g=24, s=2, p=5, op=1), _1d(diag=1)),
+    ("block-diagonal-gs2", {"FFTCONV_PERS": "2"}, _t(4, 16, 16, (5000,), (257,), g=8, s=2, op=1), _1d(bd_gs=2)),
+    ("block-diagonal-gs4", {"FFTCONV_PERS": "2"}, _t(3, 32, 32, (4500,), (129,), g=8, s=2, p=30, op=1), _1d(bd_gs=4)),
+]

@@ -81,6 +81,11 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   constexpr bool PHASES = (BUILD & pers::phases) != 0, PH2 = (BUILD & pers::pairs) != 0, PH4 = (BUILD & pers::quads) != 0;
   constexpr bool DIAG = (BUILD & pers::depthwise) != 0, SEG = (BUILD & pers::segments) != 0, STAMPS = (BUILD & pers::stamps) != 0;
   constexpr int IO = (BUILD & pers::half_io) ? IO_H16 : IO_F32;
+  // Batch pairs (the dense builds without phases, two slots or more): a complex sequence carries ONE channel of TWO slots,
+  // slot 2j in the real and slot 2j+1 in the imaginary part; sequence (pair j, channel c) at j * CIB + c.  A real kernel
+  // acts on both parts alike, so the mix contracts the packed spectra as they are, Y[o][f] = sum_c H[o][c][f] Z[c][f],
+  // without separating the two real spectra first and re-packing them afterwards as the channel pairs need it.
+  constexpr bool BPAIR = !(BUILD & (pers::phases | pers::depthwise)) && NB >= 2;
   constexpr int RING = 2;                   // spectrum register sets of the mix
   using G = Geo<P, S>;
   constexpr int T = G::T;
@@ -108,8 +113,10 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   // a wave are slots 2j and 2j+1 (even / odd phase) of pair wave % 4
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // (PH4: nb = phase pair of this half-wave, pr = the wave's channel, sequence (pair, channel) at pair * 8 + channel)
-  const int nb = PH4 ? ((tid >> 5) & 1) : (PH2 ? 2 * (wv / NPI) + ((tid >> 5) & 1) : __builtin_amdgcn_readfirstlane(tid / (NPI * G::TS)));
-  const int pr = PH4 ? wv : (PH2 ? wv % NPI : sq % NPI);
+  // (BPAIR: nb = the even slot 2j of this sequence's pair, wave-uniform too; pr = its channel; sequence j * CIB + pr)
+  const int nb = PH4 ? ((tid >> 5) & 1) : (PH2 ? 2 * (wv / NPI) + ((tid >> 5) & 1)
+               : (BPAIR ? 2 * __builtin_amdgcn_readfirstlane(tid / (CIB * G::TS)) : __builtin_amdgcn_readfirstlane(tid / (NPI * G::TS))));
+  const int pr = PH4 ? wv : (PH2 ? wv % NPI : (BPAIR ? sq % CIB : sq % NPI));
   f2* twl = lds;
   f2* zbuf = lds + TWN;                     // [NSEQ][LSEQ], sequence (slot, pair) at slot * NPI + pair
   f2* zseq = PH4 ? zbuf + (nb * 8 + pr) * G::LSEQ : zbuf + (nb * NPI + pr) * G::LSEQ;
@@ -124,6 +131,36 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   // undilated convolution of the phase-p samples, and all phases use the same spectrum -- so they ride
   // the batch-sharing axis as a virtual batch of B*d items (slot vb -> batch vb / d, phase vb % d).
   auto fetch = [&](const WorkItem& wi, f2 (&v)[P]) {
+    if constexpr (BPAIR) {
+      // channel pr of slot nb (real part) and of slot nb + 1 (imaginary part); a slot past the item's last one and a
+      // channel past the group's last one read zeros (an offset outside the resource)
+      const int g = wi.goc / a.n_ochunks;
+      const int bA = a.slot_tiles ? wi.b0 : wi.b0 + nb, bB = a.slot_tiles ? bA : bA + 1;
+      const int tA = a.slot_tiles ? wi.tile + nb : wi.tile, tB = a.slot_tiles ? tA + 1 : tA;
+      const int bfirst = wi.b0, blast = a.slot_tiles ? bfirst : wi.b0 + wi.nbc - 1;
+      const int posA = tA * a.V - a.pad + (SEG ? a.pos_shift : 0), posB = tB * a.V - a.pad + (SEG ? a.pos_shift : 0);
+      const bool interior = (posA >= 0) && (posA + (T - 1) < a.L) && (posB >= 0) && (posB + (T - 1) < a.L);
+      const auto* xbase = io_ptr<IO>(a.x) + ((size_t)bfirst * a.Cin + (size_t)g * a.Cig) * a.L;
+      const BufRsrc xg = make_rsrc(xbase, (unsigned)(((size_t)(blast - bfirst) * a.Cin + a.Cig) * a.L * ES));
+      const bool hasA = nb < wi.nbc && pr < a.Cig, hasB = nb + 1 < wi.nbc && pr < a.Cig;
+      const unsigned roA = ((unsigned)(bA - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * ES;
+      const unsigned roB = ((unsigned)(bB - bfirst) * (unsigned)a.Cin + (unsigned)pr) * (unsigned)a.L * ES;
+      if (interior && hasB) {
+        const unsigned v0 = roA + (unsigned)(posA + tseq) * ES, v1 = roB + (unsigned)(posB + tseq) * ES;
+#pragma unroll
+        for (int n1 = 0; n1 < P; ++n1) {
+          v[n1].x = io.load(xg, v0, G::N2 * n1 * ES);
+          v[n1].y = io.load(xg, v1, G::N2 * n1 * ES);
+        }
+      } else {
+#pragma unroll
+        for (int n1 = 0; n1 < P; ++n1) {
+          v[n1].x = io.load(xg, padded_offset<ES>(roA, posA + G::N2 * n1 + tseq, a.L, a.pad, pm, hasA), 0);
+          v[n1].y = io.load(xg, padded_offset<ES>(roB, posB + G::N2 * n1 + tseq, a.L, a.pad, pm, hasB), 0);
+        }
+      }
+      return;
+    }
     const int g = wi.goc / a.n_ochunks;
     const int vb = a.slot_tiles ? wi.b0 : wi.b0 + nb;
     const int tile = a.slot_tiles ? wi.tile + nb : wi.tile;
@@ -258,13 +295,13 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
     stampi(it, 0);
     stampc(it, 12);
     // bias of this lane's two output channels, requested now and used in the last pass
-    const int cg0 = g * a.Cog + oc * a.cob + (PH4 ? pr : 2 * pr);     // (PH4: one output channel per wave)
-    const bool ok0 = !DIAG || cg0 < a.Cout, ok1 = !DIAG || cg0 + 1 < a.Cout;
+    const int cg0 = g * a.Cog + oc * a.cob + ((PH4 || BPAIR) ? pr : 2 * pr);     // (PH4: one output channel per wave, BPAIR: per sequence)
+    const bool ok0 = !DIAG || cg0 < a.Cout, ok1 = !BPAIR && (!DIAG || cg0 + 1 < a.Cout);
     // (buffer loads: a missing bias is an empty resource, a missing channel an offset outside it -- no branch, so
     // nothing waits for these two values here; they are pinned as arrived after the mix, see below)
     const BufRsrc brs = make_rsrc(a.bias, a.bias ? (unsigned)a.Cout * 4u : 0u);
     float bias0 = buf_load_f32(brs, ok0 ? (unsigned)cg0 * 4u : 0xFFFFFFFFu, 0);
-    float bias1 = buf_load_f32(brs, ok1 ? (unsigned)(cg0 + 1) * 4u : 0xFFFFFFFFu, 0);
+    float bias1 = BPAIR ? 0.f : buf_load_f32(brs, ok1 ? (unsigned)(cg0 + 1) * 4u : 0xFFFFFFFFu, 0);   // (BPAIR: both parts are channel cg0)
     // ------------------------------------------------ forward pass A
     if (STAMPS && a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stampi(it, 1); }
     // (act_in is wave-uniform and the two passes of a sequence only need wave-level ordering)
@@ -438,6 +475,103 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
         *dstf = acc;
       }
     }
+    } else if constexpr (BPAIR) {
+    // ------------------------------------------------ mix, batch pairs: sequence (pair j, channel c) holds slot 2j (re) and
+    // 2j+1 (im) of channel c, and both meet the same real kernel -- the packed spectrum is contracted as it is, bin f
+    // against H[f] and bin T-f against conj H[f] (= H[T-f]).  The spectrum holds H/2 (the channel pairs contract 2X):
+    // the factor 2 rides on the bias add of the output stores.  Spectrum pipeline and register sets as in the mix below.
+    constexpr int NJ = NB / 2;
+    const unsigned ostride = (unsigned)(a.Cig_pad / 2) * (T / 2) * 16u;
+    const unsigned wbase = (unsigned)(oc * a.cob) * ostride;
+    // Self-paired bins 0 and T/2 (H real there; wspec[.][0] = {Re H[0], Re H[T/2]}): lane (pair j, output o, bin)
+    // of wave 0 owns one complex output.
+    const int sb_j = tid / (2 * CIB), sb_o = (tid >> 1) % CIB, sb_f = (tid & 1) ? T / 2 : 0;
+    const bool sb_act = tid < NJ * CIB * 2 && 2 * sb_j < wi.nbc;
+    f4 sbw[NPI];
+    if (sb_act) {
+#pragma unroll
+      for (int p = 0; p < NPI; ++p) sbw[p] = buf_load_f32x4(wg, (unsigned)sb_o * ostride, wbase + p * (T / 2) * 16);
+    }
+    auto issue = [&](int m, int q, f4 (&dst)[2 * NPI]) {
+      const unsigned vo = (unsigned)(tid + m * NT) * 16u;
+      const unsigned sa = wbase + (unsigned)(2 * q) * ostride, sb = sa + ostride;
+#pragma unroll
+      for (int p = 0; p < NPI; ++p) {
+        dst[2 * p] = buf_load_f32x4(wg, vo, sa + p * (T / 2) * 16);
+        dst[2 * p + 1] = buf_load_f32x4(wg, vo, sb + p * (T / 2) * 16);
+      }
+    };
+    f4 wr[RING][2 * NPI];
+    static_for<0, RING>([&](auto sc) {
+      constexpr int s = decltype(sc)::value;
+      if constexpr (s < BP * NPI) issue(s / NPI, s % NPI, wr[s]);
+    });
+    stampi(it, 4);
+    __syncthreads();
+    stampi(it, 5);
+    {
+      f2 sbz[CIB];
+      if (sb_act) {
+#pragma unroll
+        for (int c = 0; c < CIB; ++c) sbz[c] = zbuf[(sb_j * CIB + c) * G::LSEQ + G::nat(sb_f)];
+      }
+      f2 zf[NJ][CIB], zg[NJ][CIB];       // Z of every channel at bins f and T - f
+      // one step: outputs 2q and 2q+1 (set entries 2p / 2p+1 hold {H(o, 2p), H(o, 2p+1)} of the even / odd output)
+      auto contract = [&](int f, int fm, int q, const f4 (&wc)[2 * NPI]) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            f2 yf, yg;
+            cmul2_conj(yf, yg, zf[j][0], zf[j][1], zg[j][0], zg[j][1], wc[e].xy, wc[e].zw);
+#pragma unroll
+            for (int p = 1; p < NPI; ++p) {
+              const f4 h = wc[2 * p + e];
+              cmac2_conj(yf, yg, zf[j][2 * p], zf[j][2 * p + 1], zg[j][2 * p], zg[j][2 * p + 1], h.xy, h.zw);
+            }
+            if (f != 0 && 2 * j < wi.nbc) {
+              f2* zb = zbuf + (j * CIB + 2 * q + e) * G::LSEQ;
+              zb[G::nat(f)] = yf;
+              zb[G::nat(fm)] = yg;
+            }
+          }
+      };
+      static_for<0, BP>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        const int f = tid + m * NT;
+        const int fm = (T - f) & (T - 1);
+        {
+          const unsigned af = lds_off(zbuf + G::nat(f)), ag = lds_off(zbuf + G::nat(fm));
+          static_for<0, NJ>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            const unsigned bf = af + j * CIB * G::LSEQ * 8, bg = ag + j * CIB * G::LSEQ * 8;
+            static_for<0, CIB>([&](auto cc) {
+              constexpr int c = decltype(cc)::value;
+              zf[j][c] = lds_rd_far<c * G::LSEQ * 8>(bf);
+              zg[j][c] = lds_rd_far<c * G::LSEQ * 8>(bg);
+            });
+          });
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) { lds_arrive(zf[j]); lds_arrive(zg[j]); }
+        }
+        static_for<0, NPI>([&](auto qc) {
+          constexpr int q = decltype(qc)::value;
+          constexpr int s = m * NPI + q;               // this step; its set is refilled with step s + RING
+          contract(f, fm, q, wr[s % RING]);
+          if constexpr (s + RING < BP * NPI) issue((s + RING) / NPI, (s + RING) % NPI, wr[s % RING]);
+        });
+      });
+      if (sb_act) {
+        f2 acc = mk2(0.f, 0.f);
+#pragma unroll
+        for (int p = 0; p < NPI; ++p) {
+          const float h0 = (tid & 1) ? sbw[p].y : sbw[p].x, h1 = (tid & 1) ? sbw[p].w : sbw[p].z;
+          acc = pkfma(sbz[2 * p], mk2(h0, h0), acc);
+          acc = pkfma(sbz[2 * p + 1], mk2(h1, h1), acc);
+        }
+        zbuf[(sb_j * CIB + sb_o) * G::LSEQ + G::nat(sb_f)] = acc;
+      }
+    }
     } else {
     // ------------------------------------------------ mix
     // The first two spectrum sets (and the self-paired bins' weights) do not depend on this item's
@@ -588,7 +722,62 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
       const int nbase = o1 + P * P * j;
       auto* y0 = io_ptr<IO>(a.y) + ((size_t)b * a.Cout + cg0) * a.Lout + (size_t)(t0 + nbase) * nph + phase;
       auto* y1 = y0 + a.Lout;
-      if constexpr (DIAG) {
+      if constexpr (BPAIR) {
+        // v.x is slot nb (batch item b, tile `tile`), v.y slot nb + 1 (the next batch item, or with slot_tiles the next
+        // tile) of channel cg0; both take that channel's bias, and the factor 2 the spectrum leaves (see the mix)
+        const bool hasB = nb + 1 < wi.nbc;
+        // (the float32 value is pinned before a 16-bit store rounds it: fused into one v_fma_mixlo_f16 the sum would be rounded
+        // once, not to float32 and then to 16 bits as the float32 plan's result is when it is cast -- the bits the 16-bit plans promise)
+        auto summed = [&](float val, float to) { float r = fmaf(2.f, val, to); asm("" : "+v"(r)); return r; };
+        auto scaled = [&](float val) { return summed(val, bias0); };
+        const int bB = a.slot_tiles ? b : b + 1, t0B = a.slot_tiles ? t0 + a.V : t0;
+        const int limB = hasB ? min(a.V, a.Lfull - t0B) : 0;
+        if (SEG && a.add_out) {
+          // later segments of a long kernel accumulate into the output of the first
+          auto* yB = io_ptr<IO>(a.y) + ((size_t)bB * a.Cout + cg0) * a.Lout + (size_t)(t0B + nbase);
+#pragma unroll
+          for (int k = 0; k < P; ++k) {
+            if (nbase + P * k < limit) y0[P * k] = io.out(summed(v[k].x, io.in(y0[P * k])));
+            if (nbase + P * k < limB) yB[P * k] = io.out(summed(v[k].y, io.in(yB[P * k])));
+          }
+        } else if (S == 1) {
+          // Buffer stores in blocks of 8 rows as below; the two parts go through a resource each (an absent slot B: an
+          // empty one, every store dropped), so that a dead offset stays bit 31 of an offset into ONE item's rows.
+          const int limBs = hasB ? limB : limit;       // (the rows B may skip; equal to A's unless slot B is a shorter tile)
+          const int ka = limit >= P ? (limit - P) / P + 1 : 0, kb = limBs >= P ? (limBs - P) / P + 1 : 0;
+          const size_t crow = (size_t)(g * a.Cog + oc * a.cob);
+          const unsigned ybytes = (unsigned)((size_t)a.cob * a.Lout * ES);
+          const BufRsrc yrA = make_rsrc(io_ptr<IO>(a.y) + ((size_t)b * a.Cout + crow) * a.Lout, ybytes);
+          const BufRsrc yrB = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bB * a.Cout + crow) * a.Lout, hasB ? ybytes : 0u);
+          const unsigned voA = (unsigned)((size_t)pr * a.Lout + (size_t)(t0 + nbase)) * ES;
+          const unsigned voB = (unsigned)((size_t)pr * a.Lout + (size_t)(t0B + nbase)) * ES;
+          static_for<0, P / 8>([&](auto bc) {
+            constexpr int k0 = 8 * decltype(bc)::value;
+            if (kb >= k0 + 8) {
+              static_for<k0, k0 + 8>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                io.store(scaled(v[k].x), yrA, voA, P * k * ES);
+                io.store(scaled(v[k].y), yrB, voB, P * k * ES);
+              });
+            } else if (ka >= k0) {
+              static_for<k0, k0 + 8>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                if (k <= ka) {
+                  io.store(scaled(v[k].x), yrA, voA | ((nbase + P * k < limit) ? 0u : 0x80000000u), P * k * ES);
+                  io.store(scaled(v[k].y), yrB, voB | ((nbase + P * k < limBs) ? 0u : 0x80000000u), P * k * ES);
+                }
+              });
+            }
+          });
+        } else {
+          auto* yB = io_ptr<IO>(a.y) + ((size_t)bB * a.Cout + cg0) * a.Lout + (size_t)(t0B + nbase);
+#pragma unroll
+          for (int k = 0; k < P; ++k) {
+            if (nbase + P * k < limit) y0[P * k] = io.out(scaled(v[k].x));
+            if (nbase + P * k < limB) yB[P * k] = io.out(scaled(v[k].y));
+          }
+        }
+      } else if constexpr (DIAG) {
         // depthwise: the last block may hold fewer than 8 channels, so every row is guarded
         const int ystep = P * nph;
         const bool addo = SEG && a.add_out;

@@ -88,6 +88,32 @@ __device__ __forceinline__ void cmac2x2(f2& ya, f2& yb, f2 xa, f2 xb, f2 ha, f2 
       "v_pk_fma_f32 %1, %3, %7, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
       : "+v"(ya), "+v"(yb) : "v"(xa), "v"(xb), "v"(ha), "v"(hb), "v"(ga), "v"(gb));
 }
+// yf += xa * ha + xb * hb ; yg += za * conj(ha) + zb * conj(hb): bins f and T - f of a sequence that meets a REAL kernel
+// (H[T - f] = conj H[f]), again as two interleaved chains
+__device__ __forceinline__ void cmac2_conj(f2& yf, f2& yg, f2 xa, f2 xb, f2 za, f2 zb, f2 ha, f2 hb) {
+  asm("v_pk_fma_f32 %0, %2, %6, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %4, %6, %1 op_sel_hi:[0,1,1] neg_hi:[0,1,0]\n\t"
+      "v_pk_fma_f32 %0, %2, %6, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]\n\t"
+      "v_pk_fma_f32 %1, %4, %6, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
+      "v_pk_fma_f32 %0, %3, %7, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %5, %7, %1 op_sel_hi:[0,1,1] neg_hi:[0,1,0]\n\t"
+      "v_pk_fma_f32 %0, %3, %7, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]\n\t"
+      "v_pk_fma_f32 %1, %5, %7, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]"
+      : "+v"(yf), "+v"(yg) : "v"(xa), "v"(xb), "v"(za), "v"(zb), "v"(ha), "v"(hb));
+}
+// the same as the first step of the two chains: yf = xa * ha + xb * hb ; yg = za * conj(ha) + zb * conj(hb) (a product
+// where cmac2_conj adds to a zero, so that no register pair has to be cleared first: the same values)
+__device__ __forceinline__ void cmul2_conj(f2& yf, f2& yg, f2 xa, f2 xb, f2 za, f2 zb, f2 ha, f2 hb) {
+  asm("v_pk_mul_f32 %0, %2, %6 op_sel_hi:[0,1]\n\t"
+      "v_pk_mul_f32 %1, %4, %6 op_sel_hi:[0,1] neg_hi:[0,1]\n\t"
+      "v_pk_fma_f32 %0, %2, %6, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]\n\t"
+      "v_pk_fma_f32 %1, %4, %6, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]\n\t"
+      "v_pk_fma_f32 %0, %3, %7, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %5, %7, %1 op_sel_hi:[0,1,1] neg_hi:[0,1,0]\n\t"
+      "v_pk_fma_f32 %0, %3, %7, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]\n\t"
+      "v_pk_fma_f32 %1, %5, %7, %1 op_sel:[1,1,0] op_sel_hi:[1,0,1]"
+      : "=&v"(yf), "=&v"(yg) : "v"(xa), "v"(xb), "v"(za), "v"(zb), "v"(ha), "v"(hb));
+}
 // x * (c + i*s) with compile-time c, s (hipcc folds the modifiers itself)
 __device__ __forceinline__ f2 cmul_const(f2 x, float c, float s) {
   f2 t = mk2(c, c) * x;

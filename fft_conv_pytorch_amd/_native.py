@@ -29,6 +29,7 @@ EXPORTS = (
     "fc_long_geometry_ext", "fc_long_plan_create_ext",
     "fc_long_geometry_kind", "fc_long_plan_create_kind", "fc_long_plan_kind",
     "fc_long_forward_lay",
+    "fc_long_phases_geometry", "fc_long_phases_plan_create",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -73,6 +74,16 @@ class FcLongExt(ctypes.Structure):
     """Mirror of ``struct fc_long_ext`` (padding mode, source spread, tap dilation and output step of a long plan)."""
     _fields_ = [("pad_mode", ctypes.c_int32), ("src_up", ctypes.c_int32), ("tap_dil", ctypes.c_int32),
                 ("out_step", ctypes.c_int32)]
+
+
+class FcLongPhasesDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_phases_desc`` (a transposed convolution run as ``stride`` ordinary ones)."""
+    _fields_ = [
+        ("batch", ctypes.c_int64), ("in_channels", ctypes.c_int64), ("out_channels", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("length", ctypes.c_int64), ("kernel", ctypes.c_int64),
+        ("stride", ctypes.c_int64), ("padding", ctypes.c_int64), ("output_padding", ctypes.c_int64),
+        ("has_bias", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
 
 
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
@@ -175,6 +186,10 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_plan_kind.restype = i32
         lib.fc_long_forward_lay.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]
         lib.fc_long_forward_lay.restype = i32
+        lib.fc_long_phases_geometry.argtypes = [ctypes.POINTER(FcLongPhasesDesc), i64x8]
+        lib.fc_long_phases_geometry.restype = i32
+        lib.fc_long_phases_plan_create.argtypes = [ctypes.POINTER(FcLongPhasesDesc), ctypes.POINTER(vp)]
+        lib.fc_long_phases_plan_create.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -402,12 +417,7 @@ class LongPlan:
 
     def __init__(self, key: Tuple, device_index: int = 0):
         lib = load_library()
-        handle = ctypes.c_void_p()
-        desc = long_desc(key)
-        st = lib.fc_long_plan_create_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key),
-                                          ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
+        handle = self._create(lib, key)
         self._lib, self._h, self.key = lib, handle, key
         self.device_index = int(device_index)
         info = (ctypes.c_int64 * 8)()
@@ -420,6 +430,16 @@ class LongPlan:
         self.complex = bool(self.kind & LONG_COMPLEX)
         import torch
         self.dtype = self.weight_dtype = torch.complex64 if self.complex else torch.float32
+
+    @staticmethod
+    def _create(lib, key: Tuple):
+        handle = ctypes.c_void_p()
+        desc = long_desc(key)
+        st = lib.fc_long_plan_create_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key),
+                                          ctypes.byref(handle))
+        if st != FC_OK:
+            _raise(lib, st)
+        return handle
 
     def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int,
                          weight_dtype: int = 0):
@@ -452,6 +472,48 @@ class LongPlan:
             pass
 
 
+def phases_desc(key: Tuple) -> FcLongPhasesDesc:
+    """``struct fc_long_phases_desc`` of a phases-plan key: (batch, cin, cout, groups, L, K, stride, padding,
+    output_padding, has_bias)."""
+    if len(key) != 10:
+        raise ValueError(f"a phases-plan key has 10 words, got {len(key)}")
+    d = FcLongPhasesDesc()
+    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.stride, d.padding, d.output_padding,
+     d.has_bias) = (int(v) for v in key)
+    d.reserved = 0
+    return d
+
+
+def phases_geometry(key: Tuple) -> dict:
+    """``fc_long_phases_geometry``: the info words of the phases plan this key would get (no device); ``out_len`` is the
+    output length of the transposed convolution."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    st = lib.fc_long_phases_geometry(ctypes.byref(phases_desc(key)), ctypes.byref(info))
+    if st != FC_OK:
+        _raise(lib, st)
+    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+
+
+class LongPhasesPlan(LongPlan):
+    """A long plan that runs a transposed convolution of dilation 1 as ``stride`` ordinary convolutions of the unspread row
+    (``fc_long_phases_plan_create``).  ``transform_kernel`` takes the (Cin, Cout/groups, K) weight where it lies,
+    ``forward`` x (B, Cin, L) and y (B, Cout, out_len), contiguous; ``forward_lay`` with LONG_NLC raises
+    ``NotImplementedError``."""
+
+    @staticmethod
+    def _create(lib, key: Tuple):
+        handle = ctypes.c_void_p()
+        st = lib.fc_long_phases_plan_create(ctypes.byref(phases_desc(key)), ctypes.byref(handle))
+        if st != FC_OK:
+            _raise(lib, st)
+        return handle
+
+
+# the tag of a long-filter key -> the class that owns its plan
+_LONG_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan}
+
+
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
 # otherwise keep one plan (and its device work list) alive per shape ever seen.  An evicted plan is
 # destroyed when the last KernelSpectrum / module that still refers to it lets go.
@@ -477,7 +539,8 @@ def get_plan(device_index: int, key: Tuple) -> Plan:
         plan = _plans.get(full)
         if plan is None:
             # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
-            plan = LongPlan(key[1:], device_index) if key and key[0] == "long" else Plan(key, device_index)
+            cls = _LONG_TAGS.get(key[0]) if key else None
+            plan = cls(key[1:], device_index) if cls is not None else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):
                 _plans.popitem(last=False)

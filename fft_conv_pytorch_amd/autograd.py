@@ -458,3 +458,57 @@ class FFTLongConvFunction(torch.autograd.Function):
         if has_bias and ctx.needs_input_grad[2]:
             db = _grad_bias(grad.contiguous()).to(kernel.dtype)
         return dx, dw, db, None, None, None, None, None, None, None, None, None
+
+
+class FFTLongConvTransposeFunction(torch.autograd.Function):
+    """``fft_long_conv_transpose`` with its three gradients.  The forward runs on the route the functional picked
+    (``F_._long_transpose_run``: by phases, or on the zero-spread row); the gradients are runs of the long primitive
+    (``F_._long_run``) whatever the route, with the roles of ``FFTConvTransposeFunction``.  With y = convT(x, W), W of shape
+    (Cin, Cout/g, K), stride s, dilation d, padding p and Lout the output length:
+
+        dX = the FORWARD strided primitive on dY: tap_dil = d, out_step = s, the taps in tensor order, p zeros on both
+             sides, L samples kept.  W (Cin, Cout/g, K) already is the (out, in/g, K) weight of that convolution: no copy;
+        dW = the primitive with batch and channels exchanged: signal' = dY as (Cout/g, g*B, Lout) read with p zeros in
+             front, filter' = x as (Cin, B, L) at tap_dil = s, out_step = d, the first K lags kept, permuted to
+             (Cin, Cout/g, K).  torch builds the two transposed copies;
+        db = dY summed over batch and row.
+
+    float16 / bfloat16 and complex64 calls follow the rules of ``FFTLongConvFunction``: autograd saves the 16-bit tensors, dX
+    is written in 16 bits, dW comes back float32 and is rounded once, db is summed in float32 -- each gradient has the bits
+    of the float32 cast path; complex gradients follow PyTorch's convention, dX runs dY against conj(W) (``conj_kernel``) and
+    dW runs dY against conj(x), which here is the FILTER of the run (``conj_kernel`` again), without conjugated copies.  A dY
+    that lies as a contiguous (B, L, C) tensor is read where it lies for dX, and dX is written as the signal lies."""
+
+    @staticmethod
+    def forward(ctx, signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum, channels_last, route):
+        ctx.save_for_backward(signal, kernel)
+        ctx.cfg = (int(stride), int(padding), int(output_padding), int(dilation), int(groups), bias is not None)
+        return F_._long_transpose_run(signal, kernel, bias, stride, padding, output_padding, dilation, groups, route, spectrum,
+                                      channels_last)
+
+    @staticmethod
+    def backward(ctx, grad):
+        signal, kernel = ctx.saved_tensors
+        s, p, op, d, g, has_bias = ctx.cfg
+        grad = F_._resolved(grad.detach())
+        if F_._long_layout(grad) != "nlc" or not F_._long_nlc_enabled():
+            grad = grad.contiguous()
+        x_nlc = F_._long_layout(signal) == "nlc"          # dX is written as the signal lies
+        cx = signal.dtype == torch.complex64
+        B, cin, L = signal.shape
+        cog, K = kernel.shape[1], kernel.shape[2]
+        cig, lout = cin // g, grad.shape[2]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = F_._long_run(grad, kernel.detach().contiguous(), None, p, p, False, L, g, tap_dil=d, out_step=s,
+                              conj_kernel=cx, channels_last=x_nlc)
+        if ctx.needs_input_grad[1]:
+            dyt = grad.reshape(B, g, cog, lout).permute(2, 1, 0, 3).reshape(cog, g * B, lout).contiguous()
+            xt = signal.detach().permute(1, 0, 2).contiguous()
+            # (the row must reach lag K - 1 of the last signal sample: max(0, p - op) zeros behind it)
+            du = F_._long_run(dyt, xt, None, p, max(0, p - op), False, K, g, out_dtype=torch.float32, tap_dil=s, out_step=d,
+                              conj_kernel=cx)
+            dw = du.permute(1, 0, 2).contiguous().to(kernel.dtype)
+        if has_bias and ctx.needs_input_grad[2]:
+            db = _grad_bias(grad.contiguous()).to(kernel.dtype)
+        return dx, dw, db, None, None, None, None, None, None, None, None

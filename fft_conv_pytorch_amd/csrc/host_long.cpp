@@ -44,6 +44,8 @@ struct LongGeom {
   int64_t npairs, slab_pairs, slabs;      // rows of the transform per channel: batch pairs, or batch items of a complex plan
   int ob;
   size_t spectrum_bytes, workspace_bytes;
+  // a phases plan (phases_geometry below): Cout, Cog and nout above count the s phases of every filter
+  int64_t ph_s, ph_cog, ph_off, ph_lout;      // stride (0: not a phases plan), filters per group, y index of sample 0 of phase 0, length of y
 };
 
 bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 0; }
@@ -163,8 +165,59 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
   return FC_OK;
 }
 
+// A transposed convolution of stride s and dilation 1 as s ordinary convolutions of the unspread row:
+//   y[s*T + p - padding] = sum_j w[p + s*j] * x[T - j],   0 <= p < s,   Kp = ceil(K / s) taps per phase,
+// the forward long plan with s*Cout output channels (o*s + p: phase p of filter o), Kp flipped taps per filter row, Kp - 1
+// zeros in front of the row and the samples T0 <= T <= (Lout - 1 + padding) / s kept, T0 = min(padding / s, Kp - 1) (a
+// padding wider than the filter leaves a few samples in front that the store drops).  Sample t of the plan is T = T0 + t.
+int phases_geometry(const fc_long_phases_desc* desc, LongGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_phases_desc& d = *desc;
+  if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
+    return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
+  if (d.in_channels % d.groups || d.out_channels % d.groups)
+    return fail(FC_ERR_INVALID, "in_channels (%lld) and out_channels (%lld) must be divisible by groups (%lld)",
+                (long long)d.in_channels, (long long)d.out_channels, (long long)d.groups);
+  if (d.length < 1 || d.kernel < 1) return fail(FC_ERR_INVALID, "length and kernel must be positive");
+  if (d.stride < 1) return fail(FC_ERR_INVALID, "stride (%lld) must be >= 1", (long long)d.stride);
+  if (d.padding < 0) return fail(FC_ERR_INVALID, "padding must not be negative");
+  if (d.output_padding < 0 || d.output_padding >= d.stride)
+    return fail(FC_ERR_INVALID, "output_padding (%lld) must lie in [0, stride = %lld)", (long long)d.output_padding, (long long)d.stride);
+  const int64_t lim = (int64_t)1 << 29;      // (4-byte samples: a row of y and a row of the weight lie behind one resource)
+  if (d.length >= lim || d.kernel >= lim || d.padding >= lim || d.stride > 4096 || d.out_channels > lim / d.stride)
+    return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of 2^29 samples or more and strides above 4096 are not addressed by "
+                "the phases plan of the long-filter kernels");
+  const int64_t s = d.stride, K = d.kernel, L = d.length;
+  const int64_t lout = (L - 1) * s - 2 * d.padding + (K - 1) + d.output_padding + 1;
+  if (lout < 1) return fail(FC_ERR_INVALID, "the output length (%lld) must be positive", (long long)lout);
+  if (lout >= lim) return fail(FC_ERR_UNSUPPORTED, "an output row of %lld samples: the phases plan addresses rows below 2^29", (long long)lout);
+  const int64_t Kp = (K + s - 1) / s;
+  const int64_t t0 = std::min(d.padding / s, Kp - 1), t1 = (lout - 1 + d.padding) / s, nt = t1 - t0 + 1;
+  fc_long_desc f{};
+  f.batch = d.batch; f.in_channels = d.in_channels; f.out_channels = d.out_channels * s; f.groups = d.groups;
+  f.length = L; f.kernel = Kp;
+  f.pad_left = Kp - 1 - t0;
+  f.pad_right = std::max<int64_t>(0, nt + Kp - 1 - f.pad_left - L);
+  f.out_keep = nt; f.flip = 1; f.has_bias = d.has_bias;
+  LongGeom g;
+  const int st = long_geometry(&f, nullptr, FC_LONG_REAL, &g);
+  if (st != FC_OK) return st;
+  if (s * g.N > (int64_t)1 << 30)      // (s*t + p as a 32-bit index for every sample t of the transform)
+    return fail(FC_ERR_UNSUPPORTED, "stride %lld x a transform of %lld points exceeds the 2^30 samples the phases plan indexes",
+                (long long)s, (long long)g.N);
+  // the grid of the inverse pass: up to (s + 3) / NC phase blocks of NC phases x N2 * NC / (columns per workgroup >= 2) column blocks
+  // per filter and pair
+  if (g.slab_pairs * d.out_channels * (g.N2 / 2) * (s + 3) > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch pairs x %lld filters x %lld phases x %lld points exceeds the 2^31 workgroups of "
+                "one launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, (long long)d.out_channels, (long long)s, (long long)g.N);
+  g.K = K;      // (the filter rows are read from the weight's rows of K taps)
+  g.ph_s = s; g.ph_cog = d.out_channels / d.groups; g.ph_off = s * t0 - d.padding; g.ph_lout = lout;
+  *out = g;
+  return FC_OK;
+}
+
 void fill_info(const LongGeom& g, int64_t info[8]) {
-  info[0] = g.N1; info[1] = g.N2; info[2] = g.nout; info[3] = (int64_t)g.spectrum_bytes;
+  info[0] = g.N1; info[1] = g.N2; info[2] = g.ph_s ? g.ph_lout : g.nout; info[3] = (int64_t)g.spectrum_bytes;
   info[4] = (int64_t)g.workspace_bytes; info[5] = g.slabs; info[6] = g.ob; info[7] = g.slab_pairs;
 }
 
@@ -237,6 +290,7 @@ LongArgs base_args(const fc_long_plan& p) {
   a.kpos = (int)(g.dil * (g.keff - 1) + 1);
   a.d_up = make_fastdiv((unsigned)g.up); a.d_tdil = make_fastdiv((unsigned)g.dil); a.d_ostep = make_fastdiv((unsigned)g.step);
   a.conj_src = 0;
+  a.ph_s = (int)g.ph_s; a.ph_cog = (int)g.ph_cog; a.ph_off = (int)g.ph_off;
   return a;
 }
 
@@ -318,14 +372,9 @@ int fc_long_plan_create_ext(const fc_long_desc* desc, const fc_long_ext* ext, fc
 
 int fc_long_plan_kind(const fc_long_plan* plan) { return plan ? plan->g.kind : -1; }
 
-int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, fc_long_plan** out_plan) {
-  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
-  (void)hipGetLastError();
-  *out_plan = nullptr;
-  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
-  p->d = *desc;
-  int st = long_geometry(desc, ext, kind, &p->g);
-  if (st != FC_OK) return st;
+// the kernels and tables of a plan whose geometry is known
+static int finish_long_plan(std::unique_ptr<fc_long_plan>& p, fc_long_plan** out_plan) {
+  int st;
   p->cols = find_long(p->g.N1);
   p->rows = find_long(p->g.N2);
   const fc::TileImpl* t1 = find_tile(p->g.N1);
@@ -337,6 +386,38 @@ int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, i
   if ((st = get_long_tables(p->g.N, &p->lt)) != FC_OK) return st;
   *out_plan = p.release();
   return FC_OK;
+}
+
+int fc_long_plan_create_kind(const fc_long_desc* desc, const fc_long_ext* ext, int kind, fc_long_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
+  p->d = *desc;
+  const int st = long_geometry(desc, ext, kind, &p->g);
+  if (st != FC_OK) return st;
+  return finish_long_plan(p, out_plan);
+}
+
+int fc_long_phases_geometry(const fc_long_phases_desc* desc, int64_t info[8]) {
+  if (!info) return fail(FC_ERR_INVALID, "null argument");
+  LongGeom g;
+  const int st = phases_geometry(desc, &g);
+  if (st != FC_OK) return st;
+  fill_info(g, info);
+  return FC_OK;
+}
+
+int fc_long_phases_plan_create(const fc_long_phases_desc* desc, fc_long_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
+  const int st = phases_geometry(desc, &p->g);
+  if (st != FC_OK) return st;
+  p->d = fc_long_desc{};
+  p->d.has_bias = desc->has_bias;      // (the one field of the descriptor that the launches read)
+  return finish_long_plan(p, out_plan);
 }
 
 void fc_long_plan_destroy(fc_long_plan* plan) { delete plan; }
@@ -370,7 +451,9 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
     a.from_kernel = 1;
     a.src_io = wio;
     a.conj_src = (g.kind & FC_LONG_CONJ_TAPS) != 0;
-    a.src = (const float*)((const char*)weight + (size_t)r0 * g.K * (size_t)io_bytes(wio));
+    // (a phases plan reads the (Cin, Cout/g, K) weight where it lies: the kernel maps spectrum row r0 + q to its weight row)
+    a.ph_row0 = (int)r0;
+    a.src = g.ph_s ? (const float*)weight : (const float*)((const char*)weight + (size_t)r0 * g.K * (size_t)io_bytes(wio));
     a.w1 = (f2*)workspace;
     FC_HIP(plan->cols->cols_fwd(a, g.dil > 1, false, n, st));      // (the mapped build only where the taps are spread)
     a.spec_mode = 1;
@@ -397,6 +480,10 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
   int xio = 0, yio = 0;
   if (int e = plan_io_code(plan, x_dtype, "x", &xio)) return e;
   if (int e = plan_io_code(plan, y_dtype, "y", &yio)) return e;
+  if (plan->g.ph_s && (x_layout != FC_LONG_NCL || y_layout != FC_LONG_NCL))
+    return fail(FC_ERR_UNSUPPORTED, "a phases plan reads and writes (B, C, L) tensors only: its inverse pass gives the lanes that "
+                "a channels-last store runs over the channels to the phases of one filter (run the zero-spread long plan, or "
+                "pass contiguous tensors)");
   if (int e = layout_check(x_layout, "x", plan->g.L, plan->g.Cin, xio)) return e;
   if (int e = layout_check(y_layout, "y", plan->g.nout, plan->g.Cout, yio)) return e;
   const bool x_nlc = x_layout == FC_LONG_NLC, y_nlc = y_layout == FC_LONG_NLC;
@@ -419,6 +506,10 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     FC_HIP(plan->cols->cols_fwd(a, map_in, x_nlc, np, st));
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;
+    if (g.ph_s) {      // (the inverse pass of a phases plan counts filters, and y in its own samples)
+      a.C = (int)(g.Cout / g.ph_s);
+      a.nout = (int)g.ph_lout;
+    }
     FC_HIP(plan->cols->cols_inv(a, map_out, y_nlc, np, st));
   }
   return FC_OK;

@@ -42,6 +42,16 @@
 // last block get the out-of-resource offset.  blockIdx runs over channel blocks first, then n2 blocks, then pairs.  The
 // filter taps always go through the other builds.  NC = 0 compiles to what the kernels were before the parameter existed.
 //
+// Phases builds (PHS; float32 and 16-bit, (B, C, L) tensors) run a transposed convolution of stride s and dilation 1 as
+// the s ordinary convolutions it is, y[s*t + p - padding] = sum_j w[p + s*j] * x[t - j]: the plan has s output channels per
+// filter, channel o*s + p carrying phase p of filter o, on the unspread row.  long_cols_fwd in filter mode reads spectrum
+// row (g, o, p, i) from row (g*Cig + i)*Cog + o of the (Cin, Cout/g, K) weight where it lies: position j of the row holds
+// w[p + s*(tap0 + tstep*j)], and a tap past K - 1 (a shorter phase, or a phase with no tap at all) lies outside the row's
+// resource and reads as zero.  long_cols_inv interleaves: its workgroup is laid out as a channels-last one with the
+// phases of ONE filter in the place of the channels (NC phases x NN columns, the lanes over the phases first on the tensor
+// side), sample t of phase p goes to y[b][o][s*t + p + ph_off] where that lies inside the row, the bias is the filter's,
+// and a phase past s in the last block reads zeros and stores nothing.  long_rows sees s*Cog output channels.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -88,6 +98,12 @@ struct LongArgs {
   int conj_src;          // cols_fwd: the rows of this launch are read conjugated (signal: conj(x); taps: u = conj(w))
   // the channels-last builds only:
   FastDiv d_ncb;         // channel blocks of NC channels, ceil(C / NC) (filled by the dispatcher; d_nblk: blocks of NN columns)
+  // the phases builds only (wave-uniform; ph_s == 0: not a phases plan):
+  int ph_s;              // stride s: output channel o*s + p of the plan carries phase p of filter o (Cog == s * ph_cog)
+  int ph_cog;            // filters per group, Cout/g of the transposed convolution
+  int ph_row0;           // cols_fwd: the first filter row of this launch, in the spectrum's order
+  int ph_off;            // cols_inv: sample t of phase p is y[s*t + p + ph_off] where that lies in [0, nout)
+  FastDiv d_ph_s, d_ph_cig, d_ph_cogs;   // s, Cig and s * ph_cog: spectrum row -> (g, o, p, i)
 };
 
 constexpr int IO_CODE_C64 = 4;       // fc_dtype code of a launch of a complex build (src_io / y_io)
@@ -99,10 +115,11 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
+  static_assert(!PHS || (!MAP && !CX && NC == 0), "phases: the filter rows of a real plan, dilation 1");
   constexpr bool NLC = NC > 0;                  // channels-last signal (header); never a launch of filter rows
   constexpr int M = NLC ? NC : 1;               // neighbouring channels of the workgroup ...
   constexpr int NN = NSEQ / M;                  // ... and neighbouring n2 columns of each
@@ -136,7 +153,16 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const typename Io<IO>::T* r0;
   bool has1 = false;
   unsigned len;
-  if constexpr (NLC) {
+  [[maybe_unused]] unsigned ph = 0;             // phases build: the phase this filter row carries
+  if constexpr (PHS) {
+    // (always a launch of filter rows) spectrum row (g, o, p, i) reads weight row (g*Cig + i)*Cog + o where it lies
+    unsigned q, g, o;
+    const unsigned i = fdivmod((unsigned)a.ph_row0 + row, a.d_ph_cig, &q);
+    const unsigned op = fdivmod(q, a.d_ph_cogs, &g);
+    ph = fdivmod(op, a.d_ph_s, &o);
+    r0 = io_ptr<IO>(a.src) + ((size_t)(g * (unsigned)a.Cig + i) * a.ph_cog + o) * a.K;
+    len = (unsigned)a.K;
+  } else if constexpr (NLC) {
     const int b0 = CX ? a.pair0 + (int)pr_nlc : 2 * (a.pair0 + (int)pr_nlc);
     r0 = io_ptr<IO>(a.src) + (size_t)b0 * a.C * a.L * EW;
     has1 = !CX && b0 + 1 < a.B;
@@ -163,7 +189,11 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
     const auto offset = [&](int u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
       const int p = (n1 << a.lgN2) + n20 + (NLC ? r / M : r);
-      if constexpr (!MAP) {
+      if constexpr (PHS) {
+        // position p < keff holds w[ph + s*(tap0 + tstep*p)]; a tap past K - 1 reads as zero (the resource says so too)
+        const unsigned e = ph + (unsigned)a.ph_s * (unsigned)(a.tap0 + a.tstep * p);
+        return p < a.keff && e < len ? e * ES : 0x80000000u;
+      } else if constexpr (!MAP) {
         const int s = a.from_kernel ? a.tap0 + a.tstep * p : p - a.padl;
         const bool ok = a.from_kernel ? p < a.keff : (unsigned)s < len;
         return ok ? (unsigned)s * ES : 0x80000000u;
@@ -358,11 +388,12 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
-  constexpr bool NLC = NC > 0;                  // channels-last y, the block map of long_cols_fwd
+  static_assert(!PHS || (NC > 0 && !CX), "phases: the block layout of the channels-last build, real rows");
+  constexpr bool NLC = NC > 0;                  // channels-last y, the block map of long_cols_fwd (PHS: phases for channels)
   constexpr int M = NLC ? NC : 1;
   constexpr int NN = NSEQ / M;
   static_assert(!NLC || (MAP && NC <= NSEQ && (NC & (NC - 1)) == 0), "channels-last: the mapped form, NC * NN == NSEQ");
@@ -378,9 +409,17 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
   unsigned row;                                 // (channels-last: row and o of the block's first channel)
   int n20;
-  [[maybe_unused]] unsigned o_nlc = 0, pr_nlc = 0;
+  [[maybe_unused]] unsigned o_nlc = 0, pr_nlc = 0, ph0 = 0;
   if constexpr (!NLC) {
     n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  } else if constexpr (PHS) {
+    // the phase block of a filter varies fastest, then the filter (a.C of them), then the n2 block, then the pair; the
+    // workspace rows of a filter's phases are neighbours, o * s + p
+    unsigned q, q2;
+    ph0 = fdivmod(blockIdx.x, a.d_ncb, &q) * NC;
+    o_nlc = fdivmod(q, a.d_c, &q2);
+    n20 = (int)fdivmod(q2, a.d_nblk, &pr_nlc) * NN;
+    row = (pr_nlc * (unsigned)a.C + o_nlc) * (unsigned)a.ph_s + ph0;
   } else {
     unsigned q;
     o_nlc = fdivmod(blockIdx.x, a.d_ncb, &q) * NC;
@@ -403,7 +442,8 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   {
     // (channels-last: the block's workspace rows behind one resource, rows of channels past C read as zero)
     unsigned wbytes = (unsigned)(N * 8);
-    if constexpr (NLC) wbytes *= min((unsigned)M, (unsigned)a.C - o);
+    if constexpr (PHS) wbytes *= min((unsigned)M, (unsigned)a.ph_s - ph0);      // (rows of phases past s read as zero)
+    else if constexpr (NLC) wbytes *= min((unsigned)M, (unsigned)a.C - o);
     const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, wbytes);
     f2 val[P];
 #pragma unroll
@@ -435,7 +475,7 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   // (channels-last: the lanes run over the channels first and NT is a multiple of NSEQ, so a thread stores to one
   // channel, o + tid % NC, and holds that channel's bias; a channel past C reads the last one's and stores nothing)
   unsigned oc = o;
-  if constexpr (NLC) oc = min(o + (unsigned)(tid & (M - 1)), (unsigned)a.C - 1u);
+  if constexpr (NLC && !PHS) oc = min(o + (unsigned)(tid & (M - 1)), (unsigned)a.C - 1u);      // (phases share the filter's)
   float b = a.bias ? a.bias[oc * EW] : 0.f;
   asm volatile("" : "+v"(b));
   [[maybe_unused]] float bi = 0.f;              // complex build: the bias is Cout (re, im) pairs
@@ -446,7 +486,7 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   // (the bias is added in float32; a 16-bit y is rounded once, at the store)
   typename Io<IO>::T* y0;                       // (channels-last: the (nout, C) blocks of the pair's two batch items)
   unsigned ybytes;
-  if constexpr (NLC) {
+  if constexpr (NLC && !PHS) {
     y0 = io_ptr<IO>(a.y) + (size_t)b0 * a.C * a.nout * EW;
     ybytes = (unsigned)a.nout * (unsigned)a.C * ES;
   } else {
@@ -461,7 +501,13 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
     const f2 z = lds[(NLC ? (r & (M - 1)) * NN + r / M : r) * LSEQP + G::nat(n1)];
     const unsigned t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + (NLC ? r / M : r));
     unsigned off;
-    if constexpr (NLC) {
+    if constexpr (PHS) {
+      // sample t of phase p is y[s*t + p + ph_off]: the lanes run over the phases first, runs of NC * ES bytes per t
+      // (of NSEQ * ES where NC == s); samples in front of y, behind it, and of phases past s are dropped
+      const unsigned p = ph0 + (unsigned)(r & (M - 1));
+      const int n = (int)(t * (unsigned)a.ph_s + p) + a.ph_off;
+      off = (p < (unsigned)a.ph_s && (unsigned)n < (unsigned)a.nout) ? (unsigned)n * ES : 0x80000000u;
+    } else if constexpr (NLC) {
       const unsigned q = fdiv(t, a.d_ostep), c = o + (unsigned)(r & (M - 1));
       off = (q * a.d_ostep.d == t && q < (unsigned)a.nout && c < (unsigned)a.C) ? (q * (unsigned)a.C + c) * ES : 0x80000000u;
     } else if constexpr (!MAP) {
@@ -482,7 +528,7 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
 // what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan.  The host
 // states facts and long_inst.hip picks the build of a column pass: the element type by a.src_io (cols_fwd) / a.y_io
 // (cols_inv), the mapped build where `mapped` (padding mode, src_up, tap_dil / out_step), the channels-last build where
-// `nlc`.  `rows`: rows of the transform per channel in this launch -- batch pairs, batch items of a complex plan, or
+// `nlc`, the phases builds for the filter rows and the inverse pass of a launch with a.ph_s > 0.  `rows`: rows of the transform per channel in this launch -- batch pairs, batch items of a complex plan, or
 // filter rows with a.C == 1 -- which makes rows * a.C workgroup units, or `rows` units of a channels-last launch
 struct LongImpl {
   int T, ob;

@@ -18,7 +18,7 @@ from torch import Tensor
 from . import _native
 from .utils import to_ntuple
 
-__all__ = ["fft_conv", "fft_long_conv", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
+__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
 
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
@@ -433,7 +433,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
               out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
               out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False,
-              channels_last: bool = False) -> Tensor:
+              channels_last: bool = False, weight_shape: Optional[tuple] = None) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
     u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
@@ -450,8 +450,11 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
 
     A signal that lies as a contiguous (B, L, C) tensor (``_long_layout`` "nlc") is read where it lies, and
     ``channels_last=True`` has the kernels write the result with strides (nout*Cout, 1, Cout); the two are independent.
-    Either falls back to a torch copy under FFTCONV_LONG_NLC=0 and where one batch item's block reaches 2**31 bytes."""
+    Either falls back to a torch copy under FFTCONV_LONG_NLC=0 and where one batch item's block reaches 2**31 bytes.
+
+    ``weight_shape`` = (Cout, taps) lets a caller that holds this plan's ``spectrum`` pass ``kernel=None``."""
     signal = _resolved(signal.detach())
+    cout, taps = (int(kernel.shape[0]), int(kernel.shape[2])) if weight_shape is None else weight_shape
     native = _long_nlc_enabled()
     x_nlc = (native and _long_layout(signal) == "nlc"
              and signal.shape[1] * signal.shape[2] * signal.element_size() < _native.LONG_NLC_MAX_BYTES)
@@ -459,7 +462,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
         signal = signal.contiguous()
     cx = signal.dtype == torch.complex64
     out_dtype = signal.dtype if out_dtype is None or cx else out_dtype
-    plan = _long_plan(signal, kernel.shape[0], groups, kernel.shape[2], pad_left, pad_right, flip, out_keep,
+    plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, flip, out_keep,
                       bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step,
                       conj_signal=conj_signal, conj_kernel=conj_kernel)
     if spectrum is None or spectrum.plan is not plan:
@@ -470,7 +473,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
         bias_c = _resolved(bias.detach()).contiguous()
     else:
         bias_c = bias.detach().float().contiguous()
-    batch, cout, nout = int(signal.shape[0]), int(kernel.shape[0]), plan.out_len
+    batch, nout = int(signal.shape[0]), plan.out_len
     with torch.cuda.device(signal.device):
         y_nlc = bool(channels_last) and native
         if y_nlc:
@@ -655,3 +658,250 @@ def _require_long_dtype(name: str, t: Tensor, dtype: torch.dtype):
                         f"that share one of float32, float16, bfloat16 or complex64 (float64 runs through fft_conv only; "
                         f"complex128, complex32 and mixes of real and complex tensors are not taken: convert with "
                         f".to(torch.complex64))")
+
+
+# ---------------------------------------------------------------------------------- long transposed filters
+LONG_PHASES_MAX_OUT = 1 << 29     # longest output row the phases plan addresses (include/fftconv_amd.h)
+LONG_PHASES_MAX_STRIDE = 64       # (stride x transform points stays below 2**30 up to the 2**24-point limit)
+
+
+def _long_poly_enabled() -> bool:
+    """FFTCONV_LONG_POLY=0 (read per call): every long transposed convolution takes the zero-spread route."""
+    return os.environ.get("FFTCONV_LONG_POLY", "1") != "0"
+
+
+def _long_transpose_len(length: int, taps: int, stride: int, padding: int, output_padding: int, dilation: int) -> int:
+    return (length - 1) * stride - 2 * padding + dilation * (taps - 1) + output_padding + 1
+
+
+def _long_spread_args(length: int, taps: int, stride: int, padding: int, output_padding: int, dilation: int):
+    """The zero-spread row of a transposed convolution as ``_long_run`` takes it -> (leading signal samples to drop, signal
+    samples to read, pad_left, pad_right).  The row is the signal spread over a grid of ``stride`` with d*(K-1) - padding
+    zeros in front; a padding wider than the filter cuts into the data, and then the leading (trailing) samples that no
+    kept output meets are dropped, as the dX of ``FFTLongConvFunction`` drops them.  Zero samples to read: every output is
+    bias alone."""
+    lout = _long_transpose_len(length, taps, stride, padding, output_padding, dilation)
+    ext = dilation * (taps - 1)
+    lead, drop, n = ext - padding, 0, length
+    if lead < 0:
+        drop = min(n, -(lead // stride))
+        lead, n = lead + drop * stride, n - drop
+    if n:
+        tail = lout + ext - lead - (stride * (n - 1) + 1)
+        if tail < 0:
+            n, tail = max(0, n - (-tail) // stride), 0
+    if n == 0:
+        return length, 0, 0, 0
+    return drop, n, lead, max(tail, 0)
+
+
+def _long_transpose_needs(length: int, taps: int, stride: int, padding: int, output_padding: int, dilation: int):
+    """(points the zero-spread row needs, points the phases row needs): upper bounds of the cyclic lengths of the two
+    plans (the library may still trim taps that meet padding only)."""
+    lout = _long_transpose_len(length, taps, stride, padding, output_padding, dilation)
+    kp = -(-taps // stride)
+    t0 = min(padding // stride, kp - 1)
+    t1 = (lout - 1 + padding) // stride
+    return lout + dilation * (taps - 1), (t1 - t0 + 1) + kp - 1
+
+
+def _long_transpose_route(signal_shape, kernel_shape, stride=1, padding=0, output_padding=0, dilation=1, groups=1,
+                          dtype=torch.float32, layouts=("ncl", False)) -> str:
+    """Which route a ``fft_long_conv_transpose`` call takes (pure: shapes, numbers and FFTCONV_LONG_POLY only):
+
+    ``"handoff"``  a real row whose zero-spread form, Lout + dilation*(K-1) points, fits LONG_HANDOFF_POINTS: the
+                   ``fft_conv_transpose`` kernels;
+    ``"phases"``   stride >= 2 (at most 64), dilation 1, float32 / float16 / bfloat16, a signal that is not read as
+                   channels-last and a contiguous result: ``stride`` ordinary convolutions of the unspread row, interleaved
+                   by the store (a row of about L + 2*ceil(K/stride) points);
+    ``"spread"``   everything else -- complex64, channels-last tensors, dilation > 1, stride 1, FFTCONV_LONG_POLY=0: the
+                   long primitive on the row spread over a grid of ``stride`` (about stride*L + 2*dilation*K points).
+
+    ``layouts``: (``_long_layout`` of the signal, ``channels_last``).  A row that fits neither long route inside 2**24
+    points raises ``NotImplementedError`` with the count."""
+    length, taps = int(signal_shape[2]), int(kernel_shape[2])
+    x_layout, y_nlc = layouts
+    spread, phases = _long_transpose_needs(length, taps, stride, padding, output_padding, dilation)
+    lout = _long_transpose_len(length, taps, stride, padding, output_padding, dilation)
+    if spread <= LONG_HANDOFF_POINTS and dtype != torch.complex64:
+        return "handoff"
+    if (_long_poly_enabled() and 2 <= stride <= LONG_PHASES_MAX_STRIDE and dilation == 1 and dtype in (torch.float32,) + _LOW_PRECISION
+            and x_layout != "nlc" and not y_nlc and phases <= LONG_MAX_POINTS and lout < LONG_PHASES_MAX_OUT):
+        return "phases"
+    drop, n, lead, tail = _long_spread_args(length, taps, stride, padding, output_padding, dilation)
+    need = lout + dilation * (taps - 1) if n else 1
+    if need > LONG_MAX_POINTS:
+        raise NotImplementedError(f"fft_long_conv_transpose: the row needs a transform of {need} points; the long-filter path "
+                                  f"stops at 2**24 = {LONG_MAX_POINTS}")
+    return "spread"
+
+
+def _long_transpose_geometry(signal: Tensor, kernel: Tensor, bias, stride, padding, output_padding, dilation, groups):
+    """Argument checks of ``fft_long_conv_transpose`` (ValueError, before any device call) -> (stride, padding,
+    output_padding, dilation, output length)."""
+    if signal.ndim != 3 or kernel.ndim != 3:
+        raise ValueError(f"fft_long_conv_transpose expects a (batch, channels, length) signal and an (in, out/groups, taps) "
+                         f"kernel, got shapes {tuple(signal.shape)} and {tuple(kernel.shape)}")
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1:
+        raise ValueError(f"groups must be a positive int, got {groups!r}")
+    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
+
+    def count(name, value):
+        if isinstance(value, (tuple, list)) and len(value) == 1:
+            value = value[0]
+        if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+            raise ValueError(f"{name} must be a non-negative int, got {value!r}")
+        return int(value)
+    padding, output_padding = count("padding", padding), count("output_padding", output_padding)
+    if output_padding >= max(stride, dilation):
+        raise ValueError(f"output_padding ({output_padding}) must be smaller than either stride ({stride}) or dilation "
+                         f"({dilation})")
+    cin, length, taps = int(signal.shape[1]), int(signal.shape[2]), int(kernel.shape[2])
+    cout = int(kernel.shape[1]) * groups
+    if cin % groups or int(kernel.shape[0]) != cin:
+        raise ValueError(f"channel mismatch: signal has {cin} channels, transposed kernel is {tuple(kernel.shape)} with "
+                         f"groups={groups} (need kernel.shape[0] == in_channels and in_channels % groups == 0)")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
+    if length < 1 or taps < 1 or signal.shape[0] < 1 or kernel.shape[1] < 1:
+        raise ValueError("batch, channels, length and taps must be positive")
+    lout = _long_transpose_len(length, taps, stride, padding, output_padding, dilation)
+    if lout < 1:
+        raise ValueError(f"the output length (L-1)*stride - 2*padding + dilation*(K-1) + output_padding + 1 = {lout} must be "
+                         f"positive")
+    return stride, padding, output_padding, dilation, lout
+
+
+def _long_phases_plan(signal: Tensor, cout: int, groups: int, taps: int, stride: int, padding: int, output_padding: int,
+                      has_bias: bool):
+    """Cached phases plan (``fc_long_phases_plan_create``) of a (B, Cin, L) signal; its cache key carries a tag of its own."""
+    key = ("long_phases", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
+           int(stride), int(padding), int(output_padding), int(bool(has_bias)))
+    index = _device_index(signal.device)
+    plan = _native.lookup_plan(index, key)
+    if plan is None:
+        with torch.cuda.device(index):
+            plan = _native.get_plan(index, key)
+    return plan
+
+
+def _long_transposed_weight(kernel: Tensor, groups: int) -> Tensor:
+    """The (Cin, Cout/g, K) weight of a transposed convolution as the (Cout, Cin/g, K) weight of the forward convolution on
+    the spread row: in and out channels exchanged inside every group, one torch copy of the weight (the taps are flipped by
+    the plan)."""
+    cin, cog, taps = kernel.shape
+    return kernel.detach().contiguous().view(groups, cin // groups, cog, taps).transpose(1, 2).reshape(groups * cog, cin // groups, taps).contiguous()
+
+
+def _long_transpose_plan(signal: Tensor, kernel: Tensor, has_bias: bool, stride, padding, output_padding, dilation, groups,
+                         route: str):
+    """(plan, the part of the signal it reads, pad_left, pad_right) of a call on ``route`` ("phases" | "spread"); the
+    plan is None where the spread row holds no sample any output meets.  The two paddings are the spread plan's."""
+    length, cout, taps = int(signal.shape[2]), int(kernel.shape[1]) * groups, int(kernel.shape[2])
+    if route == "phases":
+        return _long_phases_plan(signal, cout, groups, taps, stride, padding, output_padding, has_bias), signal, 0, 0
+    assert route == "spread", route
+    drop, n, lead, tail = _long_spread_args(length, taps, stride, padding, output_padding, dilation)
+    if n == 0:
+        return None, signal, 0, 0
+    sig = signal if (drop, n) == (0, length) else signal[..., drop:drop + n]
+    lout = _long_transpose_len(length, taps, stride, padding, output_padding, dilation)
+    return _long_plan(sig, cout, groups, taps, lead, tail, True, lout, has_bias, src_up=stride, tap_dil=dilation), sig, lead, tail
+
+
+def _long_transpose_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], stride: int, padding: int, output_padding: int,
+                        dilation: int, groups: int, route: str, spectrum: Optional[KernelSpectrum] = None,
+                        channels_last: bool = False) -> Tensor:
+    """One long transposed convolution on ``route`` ("phases" | "spread"), no autograd.  ``spectrum``: the cached transform
+    of the weight for this route's plan (phases: of the weight itself; spread: of ``_long_transposed_weight``)."""
+    batch, cout, taps = int(signal.shape[0]), int(kernel.shape[1]) * groups, int(kernel.shape[2])
+    lout = _long_transpose_len(int(signal.shape[2]), taps, stride, padding, output_padding, dilation)
+    if route == "phases":
+        signal = signal.detach().contiguous()
+    plan, sig, lead, tail = _long_transpose_plan(signal, kernel, bias is not None, stride, padding, output_padding, dilation,
+                                                 groups, route)
+    if plan is None:       # padding wider than everything the data reaches: the bias alone
+        sig = _resolved(sig.detach())
+        out = sig.new_zeros((batch, cout, lout)) if bias is None else \
+            _resolved(bias.detach()).to(sig.dtype).view(1, cout, 1).expand(batch, cout, lout).contiguous()
+        return _as_channels_last(out) if channels_last else out
+    if spectrum is None or spectrum.plan is not plan:
+        spectrum = transform_kernel(plan, kernel if route == "phases" else _long_transposed_weight(_resolved(kernel), groups))
+    if route == "spread":
+        return _long_run(sig, None, bias, lead, tail, True, lout, groups, spectrum, src_up=stride, tap_dil=dilation,
+                         channels_last=channels_last, weight_shape=(cout, taps))
+    bias_c = None if bias is None else bias.detach().float().contiguous()
+    with torch.cuda.device(sig.device):
+        out = torch.empty((batch, cout, plan.out_len), dtype=sig.dtype, device=sig.device)
+        ws = new_workspace(plan, sig.device)
+        stream = torch.cuda.current_stream(sig.device).cuda_stream
+        plan.forward(sig.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
+                     out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[sig.dtype], _DTYPE_CODES[sig.dtype])
+    return out
+
+
+def fft_long_conv_transpose(signal: Tensor, kernel: Tensor, bias: Tensor = None, stride: int = 1, padding: int = 0,
+                            output_padding: int = 0, dilation: int = 1, groups: int = 1, *,
+                            channels_last: bool = False) -> Tensor:
+    """1-D transposed convolution with a filter as long as the row, equal to ``torch.nn.functional.conv_transpose1d(signal,
+    kernel, bias, stride, padding, output_padding, groups, dilation)``: ``signal`` (B, Cin, L), ``kernel`` (Cin, Cout/groups,
+    K), ``bias`` (Cout,) or None, on a ROCm device, all three float32, float16, bfloat16 or complex64; the argument order is
+    that of ``fft_conv_transpose``.  ``stride`` and ``dilation`` are ints (or 1-tuples) >= 1, ``padding`` >= 0,
+    0 <= ``output_padding`` < max(stride, dilation); the output length is (L-1)*stride - 2*padding + dilation*(K-1) +
+    output_padding + 1 (``ValueError`` below 1).  Differentiable in signal, kernel and bias.
+
+    Routes (``_long_transpose_route`` names the one a call takes):
+
+    * a real row whose zero-spread form, Lout + dilation*(K-1) points, fits 4096 runs the ``fft_conv_transpose`` kernels
+      (complex rows never hand off);
+    * stride >= 2 with dilation 1 on float32 / float16 / bfloat16 tensors, a signal that is not read as channels-last and
+      a contiguous result runs by PHASES: y[stride*t + p - padding] = sum_j kernel[p + stride*j] * x[t - j] is ``stride``
+      ordinary convolutions of the row as it is, so the transform covers about L + 2*ceil(K/stride) points, the input side
+      is transformed once for all phases, and the store interleaves them.  The weight is read where it lies: no flipped,
+      transposed or phase-split copy exists;
+    * everything else -- complex64 tensors, a channels-last signal or result, dilation > 1, stride 1 and every call under
+      ``FFTCONV_LONG_POLY=0`` (read per call) -- runs the long primitive on the row spread over a grid of ``stride`` (about
+      stride*L + 2*dilation*K points), with one torch copy of the weight (in and out channels exchanged).
+
+    A row that fits neither long route inside 2**24 points raises ``NotImplementedError``.  Leading outputs that see only
+    padding and the ``output_padding`` tail come out as the bias, as torch gives them.
+
+    float16 / bfloat16 tensors are read and written by the kernels: float32 arithmetic, one rounding at the store, the bits
+    of widening the tensors, running the float32 function and ``.to(dtype)`` -- for the result and for each gradient;
+    autograd saves the 16-bit tensors.  ``FFTCONV_HALF_IO=0`` takes that cast path.  complex64: the product is plain
+    bilinear (as torch's complex ``conv_transpose1d``), gradients follow PyTorch's convention, lazy conjugates are resolved
+    on entry.  ``channels_last`` and a signal that lies as a contiguous (B, L, C) tensor mean what they mean in
+    ``fft_long_conv``."""
+    return _fft_long_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, None,
+                                         channels_last)
+
+
+def _fft_long_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum,
+                                  channels_last=False):
+    """Shared by the functional and ``FFTLongConvTranspose1d`` (``spectrum``: the module's cached one for this call's plan)."""
+    stride, padding, output_padding, dilation, lout = _long_transpose_geometry(signal, kernel, bias, stride, padding,
+                                                                               output_padding, dilation, groups)
+    if not isinstance(channels_last, bool):
+        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+    route = _long_transpose_route(signal.shape, kernel.shape, stride, padding, output_padding, dilation, groups, signal.dtype,
+                                  (_long_layout(signal) if _long_nlc_enabled() else "ncl", channels_last))
+    for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
+        if t is not None:
+            _require_long_dtype(name, t, signal.dtype)
+    _same_device(signal=signal, kernel=kernel, bias=bias)
+    if signal.dtype == torch.complex64:
+        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
+    if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
+        # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out
+        out = _fft_long_conv_transpose_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride,
+                                            padding, output_padding, dilation, groups, None, channels_last)
+        return out.to(signal.dtype)
+    if route == "handoff":
+        out = _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, None)
+        return _as_channels_last(out) if channels_last else out
+    if _needs_grad(signal, kernel, bias):
+        from .autograd import FFTLongConvTransposeFunction
+        return FFTLongConvTransposeFunction.apply(signal, kernel, bias, stride, padding, output_padding, dilation, groups,
+                                                  spectrum, channels_last, route)
+    return _long_transpose_run(signal, kernel, bias, stride, padding, output_padding, dilation, groups, route, spectrum,
+                               channels_last)

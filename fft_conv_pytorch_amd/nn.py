@@ -37,7 +37,9 @@ class _SpectrumCache:
         self.__dict__.pop("_spectrum_cache", None)
         self.__dict__.pop("_bias_cache", None)
 
-    def _cached_spectrum(self, plan):
+    def _cached_spectrum(self, plan, prepare=None):
+        """``prepare``: what the plan transforms where that is not the weight itself (a rearranged copy), built only when
+        the transform runs."""
         weight = self.weight
         usable = (self.cache_kernel_spectrum and not _is_parametrized(self)
                   and not (self.training and weight.requires_grad and torch.is_grad_enabled()))
@@ -47,7 +49,7 @@ class _SpectrumCache:
         tag = (id(plan), weight.data_ptr(), weight._version)
         cached = self.__dict__.get("_spectrum_cache")
         if cached is None or cached[0] != tag:
-            cached = (tag, F_.transform_kernel(plan, weight))
+            cached = (tag, F_.transform_kernel(plan, weight if prepare is None else prepare(weight)))
             self.__dict__["_spectrum_cache"] = cached
         return cached[1]
 
@@ -233,3 +235,55 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
             spectrum = self._cached_spectrum(plan)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
                                       padding_mode, self.channels_last)
+
+
+class FFTLongConvTranspose1d(_SpectrumCache, nn.ConvTranspose1d):
+    """``nn.ConvTranspose1d`` (same parameters and attributes, so state_dict, deepcopy and pickle interchange with
+    ``nn.ConvTranspose1d`` and ``FFTConvTranspose1d``) whose forward is ``fft_long_conv_transpose``: one transform over the
+    whole row, for filters as long as the row -- by phases where the stride is at least 2 and the dilation 1, on the
+    zero-spread row otherwise (the functional's docstring has the routes).  The kernel spectrum of the route's plan is
+    cached under the rules of ``_SpectrumCache``, for float32, float16 / bfloat16 and complex64 modules.
+    ``forward(signal, output_size=None)`` resolves ``output_size`` to an output padding as ``nn.ConvTranspose1d`` does.
+
+    ``channels_last=True`` (keyword-only; an attribute, not part of the state_dict) returns the result with strides
+    (Lout*Cout, 1, Cout), as ``fft_long_conv_transpose`` does."""
+
+    channels_last = False
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, groups=1, bias=True,
+                 dilation=1, padding_mode="zeros", device=None, dtype=None, *, channels_last=False):
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding,
+                         output_padding=output_padding, groups=groups, bias=bias, dilation=dilation,
+                         padding_mode=padding_mode, device=device, dtype=dtype)
+        if not isinstance(channels_last, bool):
+            raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+        self.channels_last = channels_last
+
+    def extra_repr(self):
+        return super().extra_repr() + (", channels_last=True" if self.channels_last else "")
+
+    def forward(self, signal: Tensor, output_size=None):
+        stride, padding, dilation = int(self.stride[0]), int(self.padding[0]), int(self.dilation[0])
+        if output_size is None:
+            output_padding = int(self.output_padding[0])
+        else:
+            output_padding = int(self._output_padding(signal, output_size, list(self.stride), list(self.padding),
+                                                      list(self.kernel_size), 1, list(self.dilation))[0])
+        weight, bias = self.weight, self.bias
+        stride, padding, output_padding, dilation, _ = F_._long_transpose_geometry(signal, weight, bias, stride, padding,
+                                                                                   output_padding, dilation, self.groups)
+        spectrum = None
+        cx = signal.dtype == torch.complex64 and (bias is None or bias.dtype == signal.dtype)
+        if (signal.is_cuda and weight.is_cuda and signal.device == weight.device and signal.dtype == weight.dtype
+                and (signal.dtype == torch.float32 or cx or F_._half_native(signal, weight, bias))):
+            layouts = (F_._long_layout(signal) if F_._long_nlc_enabled() else "ncl", self.channels_last)
+            route = F_._long_transpose_route(signal.shape, weight.shape, stride, padding, output_padding, dilation,
+                                             self.groups, signal.dtype, layouts)
+            if route != "handoff":
+                plan = F_._long_transpose_plan(signal, weight, bias is not None, stride, padding, output_padding, dilation,
+                                               self.groups, route)[0]
+                if plan is not None:
+                    prepare = None if route == "phases" else (lambda w: F_._long_transposed_weight(F_._resolved(w), self.groups))
+                    spectrum = self._cached_spectrum(plan, prepare)
+        return F_._fft_long_conv_transpose_impl(signal, weight, bias, stride, padding, output_padding, dilation, self.groups,
+                                                spectrum, self.channels_last)

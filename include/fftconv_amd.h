@@ -320,6 +320,40 @@ enum fc_long_layout { FC_LONG_NCL = 0, FC_LONG_NLC = 1 };
 int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, int x_layout, const void* spectrum,
                          const float* bias, void* y, int y_dtype, int y_layout, void* workspace, void* hip_stream);
 
+/* Transposed convolution by phases (ABI 7 extension: new entry points only; every struct, enum value and call above keeps
+ * its layout, value and meaning).  A transposed 1-D convolution of stride s and dilation 1,
+ *   y[b][(g,o)][n] = bias[(g,o)] + sum_i sum_k w[(g,i)][o][k] * x[b][(g,i)][t],   n = s*t + k - padding,   0 <= n < Lout,
+ *   Lout = (L - 1)*s - 2*padding + K + output_padding,   weight (Cin, Cout/groups, K) as torch.nn.ConvTranspose1d holds it,
+ * is s ordinary convolutions of the row with the phase filters w_p[j] = w[p + s*j], interleaved:
+ *   y[s*T + p - padding] = sum_j w[p + s*j] * x[T - j].
+ * A phases plan is the long plan of those: s * Cout output channels (o*s + p carries phase p of filter o) on the UNSPREAD
+ * row, ceil(K / s) taps per filter row, one cyclic transform of N = N1 * N2 >= (kept samples T) + ceil(K / s) - 1 points
+ * per row where the zero-spread long plan (src_up = s) needs about s times as many.  The input side is transformed once and
+ * shared by the phases; the spectrum holds s * Cout * Cin/groups rows of N bins, in the order [(g*Cog + o)*s + p][i].
+ * The filter rows are read from the weight where it lies -- phase, flip and the exchange of in and out channels are index
+ * arithmetic of the load, no copy is made, a tap past K - 1 reads as zero (shorter phases; phases p >= K have no tap) --
+ * and the inverse pass stores sample T of phase p at y[s*T + p - padding]: every sample of y is written exactly once, the
+ * output_padding tail and the samples of tap-less phases (bias alone) included, and no other byte.
+ *   The geometry call validates the descriptor and touches no device; info words as fc_long_plan_info, info[2] = Lout.
+ *   The plan is an fc_long_plan: fc_long_plan_info, fc_long_transform_kernel_io (weight (Cin, Cout/groups, K), FC_F32 /
+ *   FC_F16 / FC_BF16), fc_long_forward_io (x (B, Cin, L) -> y (B, Cout, Lout), bias Cout float32 values or NULL) and
+ *   fc_long_plan_destroy take it; fc_long_plan_kind answers FC_LONG_REAL.  Slabs, workspace and dtype rules are those of
+ *   any real long plan.  fc_long_forward_lay with FC_LONG_NLC for x or y answers FC_ERR_UNSUPPORTED with text.
+ * stride >= 1, padding >= 0, 0 <= output_padding < stride, Lout >= 1 (FC_ERR_INVALID otherwise); L, K, padding and Lout
+ * below 2^29, stride <= 4096 and stride * N <= 2^30 (FC_ERR_UNSUPPORTED); a row that needs more than 2^24 points answers as
+ * fc_long_geometry does. */
+typedef struct fc_long_phases_desc {
+  int64_t batch, in_channels, out_channels, groups;
+  int64_t length;        /* L: samples per signal row */
+  int64_t kernel;        /* K: taps per filter row; weight is (Cin, Cout/groups, K) */
+  int64_t stride, padding, output_padding;
+  int32_t has_bias;
+  int32_t reserved;      /* 0 */
+} fc_long_phases_desc;
+
+int fc_long_phases_geometry(const fc_long_phases_desc* desc, int64_t info[8]);
+int fc_long_phases_plan_create(const fc_long_phases_desc* desc, fc_long_plan** out_plan);
+
 #ifdef __cplusplus
 }
 #endif

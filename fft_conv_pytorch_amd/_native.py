@@ -30,6 +30,7 @@ EXPORTS = (
     "fc_long_geometry_kind", "fc_long_plan_create_kind", "fc_long_plan_kind",
     "fc_long_forward_lay",
     "fc_long_phases_geometry", "fc_long_phases_plan_create",
+    "fc_long_decim_geometry", "fc_long_decim_plan_create",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -83,6 +84,17 @@ class FcLongPhasesDesc(ctypes.Structure):
         ("groups", ctypes.c_int64), ("length", ctypes.c_int64), ("kernel", ctypes.c_int64),
         ("stride", ctypes.c_int64), ("padding", ctypes.c_int64), ("output_padding", ctypes.c_int64),
         ("has_bias", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class FcLongDecimDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_decim_desc`` (a strided convolution run on the ``stride`` decimated rows of the signal)."""
+    _fields_ = [
+        ("batch", ctypes.c_int64), ("in_channels", ctypes.c_int64), ("out_channels", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("length", ctypes.c_int64), ("kernel", ctypes.c_int64),
+        ("stride", ctypes.c_int64), ("pad_left", ctypes.c_int64), ("pad_right", ctypes.c_int64),
+        ("out_keep", ctypes.c_int64),
+        ("flip", ctypes.c_int32), ("has_bias", ctypes.c_int32),
     ]
 
 
@@ -190,6 +202,10 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_phases_geometry.restype = i32
         lib.fc_long_phases_plan_create.argtypes = [ctypes.POINTER(FcLongPhasesDesc), ctypes.POINTER(vp)]
         lib.fc_long_phases_plan_create.restype = i32
+        lib.fc_long_decim_geometry.argtypes = [ctypes.POINTER(FcLongDecimDesc), i64x8]
+        lib.fc_long_decim_geometry.restype = i32
+        lib.fc_long_decim_plan_create.argtypes = [ctypes.POINTER(FcLongDecimDesc), ctypes.POINTER(vp)]
+        lib.fc_long_decim_plan_create.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -510,8 +526,45 @@ class LongPhasesPlan(LongPlan):
         return handle
 
 
+def decim_desc(key: Tuple) -> FcLongDecimDesc:
+    """``struct fc_long_decim_desc`` of a decimation-plan key: (batch, cin, cout, groups, L, K, stride, pad_left, pad_right,
+    out_keep, flip, has_bias)."""
+    if len(key) != 12:
+        raise ValueError(f"a decimation-plan key has 12 words, got {len(key)}")
+    d = FcLongDecimDesc()
+    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.stride, d.pad_left, d.pad_right, d.out_keep,
+     d.flip, d.has_bias) = (int(v) for v in key)
+    return d
+
+
+def decim_geometry(key: Tuple) -> dict:
+    """``fc_long_decim_geometry``: the info words of the decimation plan this key would get (no device)."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    st = lib.fc_long_decim_geometry(ctypes.byref(decim_desc(key)), ctypes.byref(info))
+    if st != FC_OK:
+        _raise(lib, st)
+    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+
+
+class LongDecimPlan(LongPlan):
+    """A long plan that runs a strided convolution of dilation 1 on the ``stride`` decimated rows of the signal
+    (``fc_long_decim_plan_create``): ``transform_kernel`` takes the (Cout, Cin/groups, K) weight where it lies, ``forward``
+    a contiguous x (B, Cin, L); ``forward_lay`` takes LONG_NLC for y only (for x: ``NotImplementedError``)."""
+
+    @staticmethod
+    def _create(lib, key: Tuple):
+        handle = ctypes.c_void_p()
+        st = lib.fc_long_decim_plan_create(ctypes.byref(decim_desc(key)), ctypes.byref(handle))
+        if st != FC_OK:
+            _raise(lib, st)
+        return handle
+
+
 # the tag of a long-filter key -> the class that owns its plan
 _LONG_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan}
+# ... and of the plans added since (get_plan looks here second)
+_LONG_TAGS_MORE = {"long_decim": LongDecimPlan}
 
 
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
@@ -539,7 +592,7 @@ def get_plan(device_index: int, key: Tuple) -> Plan:
         plan = _plans.get(full)
         if plan is None:
             # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
-            cls = _LONG_TAGS.get(key[0]) if key else None
+            cls = (_LONG_TAGS.get(key[0]) or _LONG_TAGS_MORE.get(key[0])) if key and isinstance(key[0], str) else None
             plan = cls(key[1:], device_index) if cls is not None else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):

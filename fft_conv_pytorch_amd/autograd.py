@@ -366,6 +366,31 @@ class FFTConvTransposeFunction(torch.autograd.Function):
         return d_signal, d_kernel, d_bias, None, None, None, None, None, None
 
 
+def _phase_rows(t: Tensor, front: int, stride: int, rows: int, groups: int) -> Tensor:
+    """The ``stride`` decimated rows of a (B, C, n) tensor read with ``front`` zeros in front, with batch and channels
+    exchanged: (C/g * stride, g*B, rows), element [(c, p), (g, b), r] = trow[b, (g, c), stride*r + p] (zero past the data).
+    The operand of a weight gradient by phases: the phase is a batch-like index of that run.  torch builds it."""
+    B, C, n = t.shape
+    row = F.pad(t, (front, stride * rows - front - n))          # (a negative count crops what no kept lag reaches)
+    return row.view(B, groups, C // groups, rows, stride).permute(2, 4, 1, 0, 3).reshape(C // groups * stride, groups * B, rows).contiguous()
+
+
+def _interleave_lags(du: Tensor, stride: int, taps: int) -> Tensor:
+    """(C' * stride, O, Kp) lags of ``_phase_rows`` operands -> (O, C', K): lag stride*m + p from [(c, p), o, m]."""
+    cs, o, kp = du.shape
+    return du.view(cs // stride, stride, o, kp).permute(2, 0, 3, 1).reshape(o, cs // stride, kp * stride)[..., :taps]
+
+
+def _fits_plain(key) -> bool:
+    """Whether the long plan of this key (``_native.long_desc`` words) fits the 2**24 points of the path: its geometry, asked
+    of the library from the descriptor alone (no device)."""
+    try:
+        F_._native.long_geometry(tuple(int(v) for v in key))
+    except NotImplementedError:
+        return False
+    return True
+
+
 class FFTLongConvFunction(torch.autograd.Function):
     """``fft_long_conv`` with its three gradients, each through the same three kernels (``F_._long_run``, the primitive
     y[j] = sum_k u[k] * xrow[out_step*j + tap_dil*k] with separate left / right padding in a padding mode, a tap order, a
@@ -381,6 +406,13 @@ class FFTLongConvFunction(torch.autograd.Function):
         db = dY summed over batch and row.
 
     torch builds the transposed copies of the operands.
+
+    A non-causal forward that ran by phases (``decim``: ``F_._long_route`` "phases", a decimation plan) has the gradients of
+    the same length: dX is the transposed convolution of dY run by PHASES (``F_._long_transpose_run``: stride s, padding p,
+    output_padding (L + 2p - K) mod s, the (Cout, Cin/g, K) weight read where it lies), and dW the primitive with the phase
+    as a batch-like index: signal' = the s decimated rows of x as (Cin/g * s, g*B, nout + Kp - 1), kernel' = dY as
+    (Cout, B, nout) at tap_dil 1, Kp = ceil(K / s) lags kept, interleaved into K by the permute copy.  A CAUSAL forward
+    keeps the constructions above whatever its route: a causal row past 2**24 points runs forward and cannot be trained.
 
     float16 / bfloat16 calls run on their 16-bit tensors (autograd saves 16-bit signal and weight): dX reads 16-bit dY
     and the 16-bit transposed weight and is written in 16 bits (with a padding mode to fold: in float32, folded, rounded
@@ -401,10 +433,15 @@ class FFTLongConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
-                padding_mode="constant", channels_last=False):
+                padding_mode="constant", channels_last=False, decim=False):
         ctx.save_for_backward(signal, kernel)
         ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None, int(stride), int(dilation),
                    padding_mode)
+        ctx.decim = bool(decim)
+        if decim:
+            return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
+                                F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
+                                channels_last=channels_last, decim=stride)
         return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
                             F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
                             pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
@@ -424,6 +461,20 @@ class FFTLongConvFunction(torch.autograd.Function):
         cout, cig, K = kernel.shape
         cog = cout // g
         dx = dw = db = None
+        if ctx.decim and not flip:
+            # (non-causal: pad_left == pad_right; the transposed convolution of dY by phases, and dW with the phase as batch)
+            nout, kp = grad.shape[2], -(-K // s)
+            if ctx.needs_input_grad[0]:
+                dx = F_._long_transpose_run(grad, kernel.detach().contiguous(), None, s, pad_left,
+                                            (L + 2 * pad_left - K) % s, 1, g, "phases")
+            if ctx.needs_input_grad[1]:
+                xt = _phase_rows(signal.detach(), pad_left, s, nout + kp - 1, g)
+                dyt = grad.permute(1, 0, 2).contiguous()
+                du = F_._long_run(xt, dyt, None, 0, 0, False, kp, g, out_dtype=torch.float32)
+                dw = _interleave_lags(du, s, K).contiguous().to(kernel.dtype)
+            if has_bias and ctx.needs_input_grad[2]:
+                db = _grad_bias(grad.contiguous()).to(kernel.dtype)
+            return dx, dw, db, None, None, None, None, None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
             # zero padding: the gradient of the row itself; another mode: of the padded row, folded below
@@ -457,7 +508,7 @@ class FFTLongConvFunction(torch.autograd.Function):
             dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             db = _grad_bias(grad.contiguous()).to(kernel.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None, None, None
 
 
 class FFTLongConvTransposeFunction(torch.autograd.Function):
@@ -477,7 +528,17 @@ class FFTLongConvTransposeFunction(torch.autograd.Function):
     is written in 16 bits, dW comes back float32 and is rounded once, db is summed in float32 -- each gradient has the bits
     of the float32 cast path; complex gradients follow PyTorch's convention, dX runs dY against conj(W) (``conj_kernel``) and
     dW runs dY against conj(x), which here is the FILTER of the run (``conj_kernel`` again), without conjugated copies.  A dY
-    that lies as a contiguous (B, L, C) tensor is read where it lies for dX, and dX is written as the signal lies."""
+    that lies as a contiguous (B, L, C) tensor is read where it lies for dX, and dX is written as the signal lies.
+
+    With dilation 1, stride 2 ... 64 and real tensors both gradients also run on rows s times shorter, where
+    FFTCONV_LONG_DECIM selects it ("1": wherever eligible; unset: only where the construction above does not fit 2**24
+    points; "0": never):
+
+        dX = the same strided primitive on a DECIMATION plan (``F_._long_run(decim=s)``): the s decimated rows of dY against
+             the phases of W, a transform of about L + ceil(K/s) points.  dY is read contiguous;
+        dW = the primitive with the phase as a batch-like index: signal' = the s decimated rows of dY read with p zeros in
+             front as (Cout/g * s, g*B, L + Kp - 1), filter' = x as (Cin, B, L) at tap_dil 1, Kp = ceil(K/s) lags kept,
+             interleaved into K by the permute copy.  One copy of dY, as above."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum, channels_last, route):
@@ -499,10 +560,24 @@ class FFTLongConvTransposeFunction(torch.autograd.Function):
         cog, K = kernel.shape[1], kernel.shape[2]
         cig, lout = cin // g, grad.shape[2]
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
+        mode = F_._long_decim_mode()
+        kp = -(-K // s)
+        eligible = mode is not False and F_._long_decim_eligible(lout, K, s, p, p, L, d, 0, signal.dtype)
+        # (unset: only where the plan of the construction above does not fit)
+        dx_decim = eligible and (mode or not _fits_plain((B, cog * g, cin, g, lout, K, p, p, L, 0, 0, 0, 1, d, s)))
+        dw_decim = eligible and L + kp - 1 <= F_.LONG_MAX_POINTS and (
+            mode or not _fits_plain((cog, g * B, cin, g, lout, L, p, max(0, p - op), K, 0, 0, 0, 1, s, d)))
+        if ctx.needs_input_grad[0] and dx_decim:
+            dx = F_._long_run(grad, kernel.detach().contiguous(), None, p, p, False, L, g, channels_last=x_nlc, decim=s)
+        elif ctx.needs_input_grad[0]:
             dx = F_._long_run(grad, kernel.detach().contiguous(), None, p, p, False, L, g, tap_dil=d, out_step=s,
                               conj_kernel=cx, channels_last=x_nlc)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and dw_decim:
+            dyt = _phase_rows(grad, p, s, L + kp - 1, g)
+            xt = signal.detach().permute(1, 0, 2).contiguous()
+            du = F_._long_run(dyt, xt, None, 0, 0, False, kp, g, out_dtype=torch.float32)
+            dw = _interleave_lags(du, s, K).contiguous().to(kernel.dtype)
+        elif ctx.needs_input_grad[1]:
             dyt = grad.reshape(B, g, cog, lout).permute(2, 1, 0, 3).reshape(cog, g * B, lout).contiguous()
             xt = signal.detach().permute(1, 0, 2).contiguous()
             # (the row must reach lag K - 1 of the last signal sample: max(0, p - op) zeros behind it)

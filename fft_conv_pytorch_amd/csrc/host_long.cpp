@@ -46,6 +46,9 @@ struct LongGeom {
   size_t spectrum_bytes, workspace_bytes;
   // a phases plan (phases_geometry below): Cout, Cog and nout above count the s phases of every filter
   int64_t ph_s, ph_cog, ph_off, ph_lout;      // stride (0: not a phases plan), filters per group, y index of sample 0 of phase 0, length of y
+  // a decimation plan (decim_geometry below): Cin and Cig above count the s decimated rows of every input channel, L and K
+  // are those of the tensors
+  int64_t dc_s, dc_padl, dc_flip;             // stride (0: not a decimation plan), the phase origin (pad_left), the tap order
 };
 
 bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 0; }
@@ -216,6 +219,58 @@ int phases_geometry(const fc_long_phases_desc* desc, LongGeom* out) {
   return FC_OK;
 }
 
+// A strided convolution of stride s and dilation 1 on the s decimated rows of the signal, the adjoint of the phases store
+// (DESIGN 4.7): with k = s*m + p,
+//   y[j] = sum_k u[k] * xrow[s*j + k] = sum_p sum_m u_p[m] * x_p[j + m],   x_p[t] = xrow[s*t + p],   u_p[m] = u[s*m + p],
+// the plain long plan with s*Cin input channels (i*s + p: decimated row p of channel i), Kp = ceil(K / s) taps per filter
+// row and rows of T = nout + Kp - 1 positions.  The descriptor goes to long_geometry in those units, so factorisation,
+// slabs, FFTCONV_LONG_N and the limits are those of every long plan.
+int decim_geometry(const fc_long_decim_desc* desc, LongGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_decim_desc& d = *desc;
+  if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
+    return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
+  if (d.in_channels % d.groups || d.out_channels % d.groups)
+    return fail(FC_ERR_INVALID, "in_channels (%lld) and out_channels (%lld) must be divisible by groups (%lld)",
+                (long long)d.in_channels, (long long)d.out_channels, (long long)d.groups);
+  if (d.length < 1 || d.kernel < 1) return fail(FC_ERR_INVALID, "length and kernel must be positive");
+  if (d.stride < 2 || d.stride > 64)
+    return fail(FC_ERR_INVALID, "stride (%lld) of a decimation plan must lie in [2, 64]", (long long)d.stride);
+  if (d.pad_left < 0 || d.pad_right < 0 || d.out_keep < 0) return fail(FC_ERR_INVALID, "padding and out_keep must not be negative");
+  if (d.flip != 0 && d.flip != 1) return fail(FC_ERR_INVALID, "flip must be 0 or 1");
+  const int64_t lim = (int64_t)1 << 29;      // (4-byte samples: a row of x and a row of the weight lie behind one resource)
+  if (d.length >= lim || d.kernel >= lim || d.pad_left >= lim || d.pad_right >= lim)
+    return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of 2^29 samples or more are not addressed by the decimation plan of "
+                "the long-filter kernels");
+  const int64_t s = d.stride, K = d.kernel, L = d.length;
+  const int64_t Lp = L + d.pad_left + d.pad_right;
+  if (K > Lp)
+    return fail(FC_ERR_INVALID, "kernel (%lld taps) is longer than the padded row (%lld samples)", (long long)K, (long long)Lp);
+  const int64_t full = (Lp - K) / s + 1;
+  if (d.out_keep > full)
+    return fail(FC_ERR_INVALID, "out_keep (%lld) exceeds the output length %lld", (long long)d.out_keep, (long long)full);
+  const int64_t nout = d.out_keep ? d.out_keep : full, Kp = (K + s - 1) / s;
+  fc_long_desc f{};
+  f.batch = d.batch; f.in_channels = d.in_channels * s; f.out_channels = d.out_channels; f.groups = d.groups;
+  f.length = nout + Kp - 1; f.kernel = Kp;
+  f.pad_left = 0; f.pad_right = 0; f.out_keep = nout; f.flip = 0; f.has_bias = d.has_bias;
+  LongGeom g;
+  const int st = long_geometry(&f, nullptr, FC_LONG_REAL, &g);
+  if (st != FC_OK) return st;
+  if (s * g.N > (int64_t)1 << 30)      // (s*t + p as a 32-bit index for every position t of the transform)
+    return fail(FC_ERR_UNSUPPORTED, "stride %lld x a transform of %lld points exceeds the 2^30 samples the decimation plan indexes",
+                (long long)s, (long long)g.N);
+  // the grid of the forward column pass: up to (s + 3) / NC phase blocks of NC phases x N2 * NC / (columns per workgroup >= 2)
+  // column blocks per channel and pair
+  if (g.slab_pairs * d.in_channels * (g.N2 / 2) * (s + 3) > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch pairs x %lld channels x %lld phases x %lld points exceeds the 2^31 workgroups of "
+                "one launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, (long long)d.in_channels, (long long)s, (long long)g.N);
+  g.L = L; g.K = K;      // (the rows are read from the tensors: x rows of L samples, weight rows of K taps)
+  g.dc_s = s; g.dc_padl = d.pad_left; g.dc_flip = d.flip;
+  *out = g;
+  return FC_OK;
+}
+
 void fill_info(const LongGeom& g, int64_t info[8]) {
   info[0] = g.N1; info[1] = g.N2; info[2] = g.ph_s ? g.ph_lout : g.nout; info[3] = (int64_t)g.spectrum_bytes;
   info[4] = (int64_t)g.workspace_bytes; info[5] = g.slabs; info[6] = g.ob; info[7] = g.slab_pairs;
@@ -291,6 +346,10 @@ LongArgs base_args(const fc_long_plan& p) {
   a.d_up = make_fastdiv((unsigned)g.up); a.d_tdil = make_fastdiv((unsigned)g.dil); a.d_ostep = make_fastdiv((unsigned)g.step);
   a.conj_src = 0;
   a.ph_s = (int)g.ph_s; a.ph_cog = (int)g.ph_cog; a.ph_off = (int)g.ph_off;
+  if (g.dc_s) {      // (a decimation plan lends the words of the phases builds, long1d.hpp LongArgs)
+    a.ph_s = (int)g.dc_s; a.ph_cog = 0; a.ph_off = (int)g.dc_padl;
+    a.tap0 = g.dc_flip ? (int)g.K - 1 : 0; a.tstep = g.dc_flip ? -1 : 1;
+  }
   return a;
 }
 
@@ -420,6 +479,27 @@ int fc_long_phases_plan_create(const fc_long_phases_desc* desc, fc_long_plan** o
   return finish_long_plan(p, out_plan);
 }
 
+int fc_long_decim_geometry(const fc_long_decim_desc* desc, int64_t info[8]) {
+  if (!info) return fail(FC_ERR_INVALID, "null argument");
+  LongGeom g;
+  const int st = decim_geometry(desc, &g);
+  if (st != FC_OK) return st;
+  fill_info(g, info);
+  return FC_OK;
+}
+
+int fc_long_decim_plan_create(const fc_long_decim_desc* desc, fc_long_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
+  const int st = decim_geometry(desc, &p->g);
+  if (st != FC_OK) return st;
+  p->d = fc_long_desc{};
+  p->d.has_bias = desc->has_bias;      // (the one field of the descriptor that the launches read)
+  return finish_long_plan(p, out_plan);
+}
+
 void fc_long_plan_destroy(fc_long_plan* plan) { delete plan; }
 
 int fc_long_plan_info(const fc_long_plan* plan, int64_t info[8]) {
@@ -453,7 +533,8 @@ int fc_long_transform_kernel_io(const fc_long_plan* plan, const void* weight, in
     a.conj_src = (g.kind & FC_LONG_CONJ_TAPS) != 0;
     // (a phases plan reads the (Cin, Cout/g, K) weight where it lies: the kernel maps spectrum row r0 + q to its weight row)
     a.ph_row0 = (int)r0;
-    a.src = g.ph_s ? (const float*)weight : (const float*)((const char*)weight + (size_t)r0 * g.K * (size_t)io_bytes(wio));
+    // (so does a decimation plan, from the (Cout, Cin/g, K) weight)
+    a.src = g.ph_s || g.dc_s ? (const float*)weight : (const float*)((const char*)weight + (size_t)r0 * g.K * (size_t)io_bytes(wio));
     a.w1 = (f2*)workspace;
     FC_HIP(plan->cols->cols_fwd(a, g.dil > 1, false, n, st));      // (the mapped build only where the taps are spread)
     a.spec_mode = 1;
@@ -484,6 +565,10 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     return fail(FC_ERR_UNSUPPORTED, "a phases plan reads and writes (B, C, L) tensors only: its inverse pass gives the lanes that "
                 "a channels-last store runs over the channels to the phases of one filter (run the zero-spread long plan, or "
                 "pass contiguous tensors)");
+  if (plan->g.dc_s && x_layout != FC_LONG_NCL)
+    return fail(FC_ERR_UNSUPPORTED, "a decimation plan reads a (B, C, L) signal only: its forward column pass gives the lanes that "
+                "a channels-last load runs over the channels to the decimated rows of one channel (run the plain long plan, or "
+                "pass a contiguous signal)");
   if (int e = layout_check(x_layout, "x", plan->g.L, plan->g.Cin, xio)) return e;
   if (int e = layout_check(y_layout, "y", plan->g.nout, plan->g.Cout, yio)) return e;
   const bool x_nlc = x_layout == FC_LONG_NLC, y_nlc = y_layout == FC_LONG_NLC;
@@ -502,7 +587,7 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     a.spec = (const f2*)spectrum;
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
-    a.C = (int)g.Cin;
+    a.C = (int)(g.dc_s ? g.Cin / g.dc_s : g.Cin);      // (the forward pass of a decimation plan counts the tensor's channels)
     FC_HIP(plan->cols->cols_fwd(a, map_in, x_nlc, np, st));
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;

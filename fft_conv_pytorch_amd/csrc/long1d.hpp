@@ -52,6 +52,20 @@
 // side), sample t of phase p goes to y[b][o][s*t + p + ph_off] where that lies inside the row, the bias is the filter's,
 // and a phase past s in the last block reads zeros and stores nothing.  long_rows sees s*Cog output channels.
 //
+// Decimation builds of long_cols_fwd (DEC; float32 and 16-bit, a (B, C, L) signal) run a STRIDED convolution of stride s
+// and dilation 1 as the sum of s ordinary ones, the adjoint of the phases store: with k = s*m + p,
+// y[j] = sum_k u[k] * xrow[s*j + k] = sum_p (u_p * x_p)[j], x_p[t] = xrow[s*t + p], u_p[m] = u[s*m + p].  The plan has s
+// input channels per input channel of the tensor, channel i*s + p carrying the decimated row p of channel i, and
+// ceil(K / s) taps per filter row.  The signal build (NC > 0) lays its workgroup out as a channels-last one with the
+// phases of ONE input channel in the place of the channels (NC phases x NN columns; the lanes run over the phases first on
+// the tensor side, so a workgroup reads runs of NC * ES contiguous bytes, and over the columns first on the workspace
+// side, whose rows i*s + p0 ... are neighbours): position t of phase p reads x[b][i][s*t + p - pad_left] where that lies
+// in [0, L) and p < s; front padding, positions past the data and the idle phases of a last block get the
+// out-of-resource offset and read zero.  The filter build (NC == 0) reads spectrum row (g*Cog + o)*Cig*s + i*s + p from
+// row (g*Cog + o)*Cig + i of the (Cout, Cin/g, K) weight where it lies: position m holds u[s*m + p], u the taps in tensor
+// order or flipped; a tap past K - 1 ends a shorter phase, a phase p >= K has no tap.  long_rows sees s*Cig input
+// channels per group and long_cols_inv is the unchanged one, its channels-last build included.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -104,6 +118,12 @@ struct LongArgs {
   int ph_row0;           // cols_fwd: the first filter row of this launch, in the spectrum's order
   int ph_off;            // cols_inv: sample t of phase p is y[s*t + p + ph_off] where that lies in [0, nout)
   FastDiv d_ph_s, d_ph_cig, d_ph_cogs;   // s, Cig and s * ph_cog: spectrum row -> (g, o, p, i)
+  // A decimation plan is no phases plan and lends the words above other meanings (the struct keeps its size, and with it
+  // every build that existed its registers): ph_s > 0 with ph_cog == 0 says decimation, ph_s = stride s (input channel
+  // i*s + p of the plan carries the decimated row p of channel i), d_ph_s: spectrum row -> (weight row, p), ph_row0 as
+  // above, ph_off = the phase origin: position t of phase p of a signal row holds x[s*t + p - ph_off] where that lies in
+  // [0, L).  Position m < keff of a filter row holds taps[tap0 + tstep*(s*m + p)] where s*m + p < K: tap0, tstep = 0, 1
+  // (tensor order) or K - 1, -1 (flipped)
 };
 
 constexpr int IO_CODE_C64 = 4;       // fc_dtype code of a launch of a complex build (src_io / y_io)
@@ -115,15 +135,21 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false>
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false,
+          bool DEC = false>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
   static_assert(!PHS || (!MAP && !CX && NC == 0), "phases: the filter rows of a real plan, dilation 1");
-  constexpr bool NLC = NC > 0;                  // channels-last signal (header); never a launch of filter rows
-  constexpr int M = NLC ? NC : 1;               // neighbouring channels of the workgroup ...
+  static_assert(!DEC || (!MAP && !CX && !PHS), "decimation: the rows of a real plan, zero padding, dilation 1");
+  constexpr bool BLK = NC > 0;                  // the workgroup is NC rows x NN columns (channels-last, decimated signal)
+  constexpr bool NLC = BLK && !DEC;             // channels-last signal (header); never a launch of filter rows
+  constexpr bool DSIG = BLK && DEC;             // decimated signal rows: the phases of one channel for the channels
+  constexpr bool DFIL = DEC && !BLK;            // the filter rows of a decimation plan
+  constexpr int M = BLK ? NC : 1;               // neighbouring channels (phases) of the workgroup ...
   constexpr int NN = NSEQ / M;                  // ... and neighbouring n2 columns of each
-  static_assert(!NLC || (MAP && NC <= NSEQ && (NC & (NC - 1)) == 0), "channels-last: the mapped form, NC * NN == NSEQ");
+  static_assert(!NLC || MAP, "channels-last: the mapped form");
+  static_assert(!BLK || (NC <= NSEQ && (NC & (NC - 1)) == 0), "a block of NC rows: NC * NN == NSEQ");
   const Io<IO> io(a.src_io);
   constexpr unsigned ES = CX ? 8u : Io<IO>::B;  // bytes per sample of the source rows
   constexpr int EW = CX ? 2 : 1;                // elements of Io<IO>::T per sample
@@ -136,9 +162,17 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
   unsigned row;                                 // (channels-last: the workspace row of the block's first channel)
   int n20;
-  [[maybe_unused]] unsigned c0 = 0, pr_nlc = 0;
-  if constexpr (!NLC) {
+  [[maybe_unused]] unsigned c0 = 0, pr_nlc = 0, dph0 = 0;
+  if constexpr (!BLK) {
     n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  } else if constexpr (DSIG) {
+    // the phase block of a channel varies fastest, then the channel (a.C of them), then the n2 block, then the pair; the
+    // workspace rows of a channel's phases are neighbours, c * s + p
+    unsigned q, q2;
+    dph0 = fdivmod(blockIdx.x, a.d_ncb, &q) * NC;
+    c0 = fdivmod(q, a.d_c, &q2);
+    n20 = (int)fdivmod(q2, a.d_nblk, &pr_nlc) * NN;
+    row = (pr_nlc * (unsigned)a.C + c0) * (unsigned)a.ph_s + dph0;
   } else {
     // the channel block varies fastest, then the n2 block, then the pair
     unsigned q;
@@ -154,7 +188,18 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   bool has1 = false;
   unsigned len;
   [[maybe_unused]] unsigned ph = 0;             // phases build: the phase this filter row carries
-  if constexpr (PHS) {
+  if constexpr (DFIL) {
+    // (always a launch of filter rows) spectrum row wr * s + p reads row wr of the (Cout, Cin/g, K) weight where it lies
+    unsigned wr;
+    ph = fdivmod((unsigned)a.ph_row0 + row, a.d_ph_s, &wr);
+    r0 = io_ptr<IO>(a.src) + (size_t)wr * a.K;
+    len = (unsigned)a.K;
+  } else if constexpr (DSIG) {
+    const int b0 = 2 * (a.pair0 + (int)pr_nlc);
+    r0 = io_ptr<IO>(a.src) + ((size_t)b0 * a.C + c0) * a.L;
+    has1 = b0 + 1 < a.B;
+    len = (unsigned)a.L;
+  } else if constexpr (PHS) {
     // (always a launch of filter rows) spectrum row (g, o, p, i) reads weight row (g*Cig + i)*Cog + o where it lies
     unsigned q, g, o;
     const unsigned i = fdivmod((unsigned)a.ph_row0 + row, a.d_ph_cig, &q);
@@ -188,8 +233,17 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
     f2 val[P];
     const auto offset = [&](int u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
-      const int p = (n1 << a.lgN2) + n20 + (NLC ? r / M : r);
-      if constexpr (PHS) {
+      const int p = (n1 << a.lgN2) + n20 + (BLK ? r / M : r);
+      if constexpr (DSIG) {
+        // position p of phase q holds x[s*p + q - ph_off]; padding, positions past the data and idle phases read as zero
+        const unsigned q = dph0 + (unsigned)(r & (M - 1));
+        const unsigned e = (unsigned)(p * a.ph_s + (int)q - a.ph_off);
+        return q < (unsigned)a.ph_s && e < len ? e * ES : 0x80000000u;
+      } else if constexpr (DFIL) {
+        // position p < keff holds u[s*p + ph], u = the taps in tensor order or flipped; a tap past K - 1 reads as zero
+        const unsigned e = ph + (unsigned)a.ph_s * (unsigned)p;
+        return p < a.keff && e < len ? (unsigned)(a.tap0 + a.tstep * (int)e) * ES : 0x80000000u;
+      } else if constexpr (PHS) {
         // position p < keff holds w[ph + s*(tap0 + tstep*p)]; a tap past K - 1 reads as zero (the resource says so too)
         const unsigned e = ph + (unsigned)a.ph_s * (unsigned)(a.tap0 + a.tstep * p);
         return p < a.keff && e < len ? e * ES : 0x80000000u;
@@ -257,7 +311,7 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
 #pragma unroll
     for (int u = 0; u < P; ++u) {
       const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
-      if constexpr (NLC) {                       // slot (rc, rn) = rc * NN + rn
+      if constexpr (BLK) {                       // slot (rc, rn) = rc * NN + rn
         lds[((r & (M - 1)) * NN + r / M) * LSEQP + G::nat(n1)] = val[u];
       } else {
         lds[r * LSEQP + G::nat(n1)] = val[u];
@@ -276,15 +330,16 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
   // (channels-last: one resource over the block's workspace rows, the NC of them or those up to channel C - 1; the
   // lanes run over the NN columns first, slot r = (r / NN, r % NN).  NC * N <= 8192 * 4096 points: 2^28 bytes)
-  const unsigned wrows = NLC ? min((unsigned)M, (unsigned)a.C - c0) : 1u;
+  // (decimated signal: the rows of the block's phases, those up to phase s - 1)
+  const unsigned wrows = DSIG ? min((unsigned)M, (unsigned)a.ph_s - dph0) : NLC ? min((unsigned)M, (unsigned)a.C - c0) : 1u;
   const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8) * wrows);
 #pragma unroll
   for (int u = 0; u < P; ++u) {
     const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
-    const unsigned n2 = (unsigned)(n20 + (NLC ? r & (NN - 1) : r));
+    const unsigned n2 = (unsigned)(n20 + (BLK ? r & (NN - 1) : r));
     const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
     const f2 z = lds[r * LSEQP + G::nat(k1)];
-    const unsigned wrow = NLC ? (unsigned)(r / NN) * (unsigned)N : 0u;
+    const unsigned wrow = BLK ? (unsigned)(r / NN) * (unsigned)N : 0u;
     buf_store_f32x2(cmul(z, w), orr, (wrow + ((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
   }
 }
@@ -528,7 +583,8 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
 // what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan.  The host
 // states facts and long_inst.hip picks the build of a column pass: the element type by a.src_io (cols_fwd) / a.y_io
 // (cols_inv), the mapped build where `mapped` (padding mode, src_up, tap_dil / out_step), the channels-last build where
-// `nlc`, the phases builds for the filter rows and the inverse pass of a launch with a.ph_s > 0.  `rows`: rows of the transform per channel in this launch -- batch pairs, batch items of a complex plan, or
+// `nlc`, the phases builds for the filter rows and the inverse pass of a launch with a.ph_s > 0, the decimation builds for
+// the filter rows and the signal rows of a launch with a.ph_s > 0 and a.ph_cog == 0.  `rows`: rows of the transform per channel in this launch -- batch pairs, batch items of a complex plan, or
 // filter rows with a.C == 1 -- which makes rows * a.C workgroup units, or `rows` units of a channels-last launch
 struct LongImpl {
   int T, ob;

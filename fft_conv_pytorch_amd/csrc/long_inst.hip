@@ -1,7 +1,8 @@
 // long_inst.hip -- instantiates the three kernels of long1d.hpp for ONE tile geometry (P, S) and is the one place that
 // picks the build of a column launch (cols_dispatch: float32, 16-bit -- one build for float16 and bfloat16 -- or complex64
 // by the launch's element code, each plain, mapped or channels-last, nine builds of each column kernel; for a phases plan,
-// a.ph_s > 0, the phases builds of the filter rows and of the inverse pass, float32 and 16-bit): built once per
+// a.ph_s > 0, the phases builds of the filter rows and of the inverse pass, float32 and 16-bit; for a decimation plan,
+// a.ph_s > 0 with a.ph_cog == 0, the decimation builds of the filter rows and of the signal rows, float32 and 16-bit): built once per
 // geometry with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
@@ -106,13 +107,43 @@ hipError_t phs_inv_pick(const LongArgs& a, long long pairs, hipStream_t st) {
   return phs_inv_launch<IO, 2>(a, pairs, st);
 }
 
+// ---- decimation (long1d.hpp).  The filter rows of a decimation plan: the plain block map, one build per element type
+template <int IO>
+hipError_t dec_filter_launch(const LongArgs& a, long long rows, hipStream_t st) {
+  LongArgs b = a;
+  b.d_ph_s = make_fastdiv((unsigned)a.ph_s);
+  return launch<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO, false, false, 0, false, true>>(b, a.N2 / kNSEQ, rows * a.C, st);
+}
+
+// The signal rows: NC decimated rows of one input channel x kNSEQ / NC neighbouring n2 columns per workgroup, a.C channels
+// of the tensor.  The two widths and the rule that picks between them are those of the phases inverse pass above
+template <int IO, int NC>
+hipError_t dec_signal_launch(const LongArgs& a, long long pairs, hipStream_t st) {
+  const long long npb = (a.ph_s + NC - 1) / NC, nblk = a.N2 / (kNSEQ / NC);
+  const long long blocks = pairs * nblk * a.C * npb;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  LongArgs b = a;
+  b.d_ncb = make_fastdiv((unsigned)npb);
+  b.d_nblk = make_fastdiv((unsigned)nblk);
+  b.d_c = make_fastdiv((unsigned)a.C);
+  return launch_kernel<long_cols_fwd_kernel<FC_P, FC_S, kNSEQ, kNT, IO, false, false, NC, false, true>>(blocks, kNT, kLds, st, b);
+}
+
+template <int IO>
+hipError_t dec_signal_pick(const LongArgs& a, long long pairs, hipStream_t st) {
+  if constexpr (kPhsWide > 2) {
+    if ((a.ph_s + 3) / 4 * 4 <= (a.ph_s + 1) / 2 * 2) return dec_signal_launch<IO, kPhsWide>(a, pairs, st);
+  }
+  return dec_signal_launch<IO, 2>(a, pairs, st);
+}
+
 // a column pass over `rows` rows of the transform per channel (LongImpl); the element type is that of the tensor the
 // pass touches.  A channels-last launch never reads filter rows
 template <bool INV>
 hipError_t cols_dispatch(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st) {
   if (a.N1 != kT || rows <= 0 || a.C <= 0 || (nlc && a.from_kernel)) return hipErrorInvalidValue;
   const int code = INV ? a.y_io : a.src_io;
-  if (a.ph_s > 0 && (INV || a.from_kernel)) {      // (the signal rows of a phases plan are plain rows)
+  if (a.ph_s > 0 && a.ph_cog > 0 && (INV || a.from_kernel)) {      // (the signal rows of a phases plan are plain rows)
     if (mapped || nlc || a.ph_cog <= 0) return hipErrorInvalidValue;
     if constexpr (INV) {
       if (code == 0) return phs_inv_pick<IO_F32>(a, rows, st);
@@ -122,6 +153,14 @@ hipError_t cols_dispatch(const LongArgs& a, bool mapped, bool nlc, long long row
       if (io_is_h16(code)) return phs_filter_launch<IO_H16>(a, rows, st);
     }
     return hipErrorInvalidValue;
+  }
+  if constexpr (!INV) {
+    if (a.ph_s > 0 && a.ph_cog == 0) {      // (a decimation plan)
+      if (mapped || nlc) return hipErrorInvalidValue;
+      if (code == 0) return a.from_kernel ? dec_filter_launch<IO_F32>(a, rows, st) : dec_signal_pick<IO_F32>(a, rows, st);
+      if (io_is_h16(code)) return a.from_kernel ? dec_filter_launch<IO_H16>(a, rows, st) : dec_signal_pick<IO_H16>(a, rows, st);
+      return hipErrorInvalidValue;
+    }
   }
   if (code == 0) return cols_launch<INV, IO_F32, false>(a, mapped, nlc, rows, st);
   if (io_is_h16(code)) return cols_launch<INV, IO_H16, false>(a, mapped, nlc, rows, st);

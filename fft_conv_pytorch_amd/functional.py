@@ -400,6 +400,20 @@ def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int,
     return plan
 
 
+def _long_decim_plan(signal: Tensor, cout: int, groups: int, taps: int, stride: int, pad_left: int, pad_right: int,
+                     out_keep: int, flip: bool, has_bias: bool):
+    """Cached decimation plan (``fc_long_decim_plan_create``) of a (B, Cin, L) signal: the strided primitive of dilation 1
+    on the ``stride`` decimated rows.  Its cache key carries a tag of its own."""
+    key = ("long_decim", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
+           int(stride), int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)))
+    index = _device_index(signal.device)
+    plan = _native.lookup_plan(index, key)
+    if plan is None:
+        with torch.cuda.device(index):
+            plan = _native.get_plan(index, key)
+    return plan
+
+
 def _resolved(t: Tensor) -> Tensor:
     """A complex tensor with its lazy conjugate / negation materialised: the library reads ``data_ptr()``, which knows of
     neither bit.  Real tensors pass through."""
@@ -433,7 +447,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
               out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
               out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False,
-              channels_last: bool = False, weight_shape: Optional[tuple] = None) -> Tensor:
+              channels_last: bool = False, weight_shape: Optional[tuple] = None, decim: int = 0) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
     u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
@@ -452,19 +466,27 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
     ``channels_last=True`` has the kernels write the result with strides (nout*Cout, 1, Cout); the two are independent.
     Either falls back to a torch copy under FFTCONV_LONG_NLC=0 and where one batch item's block reaches 2**31 bytes.
 
-    ``weight_shape`` = (Cout, taps) lets a caller that holds this plan's ``spectrum`` pass ``kernel=None``."""
+    ``weight_shape`` = (Cout, taps) lets a caller that holds this plan's ``spectrum`` pass ``kernel=None``.
+
+    ``decim`` = s >= 2 runs the primitive with out_step = s on a decimation plan (``_long_decim_plan``: real tensors, zero
+    padding, dilation 1): the s decimated rows of every input channel against the s phases of the taps, a transform of
+    about nout + ceil(taps / s) points.  The signal is read contiguous; a channels-last result is written as ever."""
     signal = _resolved(signal.detach())
     cout, taps = (int(kernel.shape[0]), int(kernel.shape[2])) if weight_shape is None else weight_shape
     native = _long_nlc_enabled()
-    x_nlc = (native and _long_layout(signal) == "nlc"
+    x_nlc = (native and not decim and _long_layout(signal) == "nlc"
              and signal.shape[1] * signal.shape[2] * signal.element_size() < _native.LONG_NLC_MAX_BYTES)
     if not x_nlc:
         signal = signal.contiguous()
     cx = signal.dtype == torch.complex64
     out_dtype = signal.dtype if out_dtype is None or cx else out_dtype
-    plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, flip, out_keep,
-                      bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step,
-                      conj_signal=conj_signal, conj_kernel=conj_kernel)
+    if decim:
+        assert (pad_mode, src_up, tap_dil, out_step) == (0, 1, 1, 1) and not cx, "a decimation plan: zero padding, dilation 1, real rows"
+        plan = _long_decim_plan(signal, cout, groups, taps, decim, pad_left, pad_right, out_keep, flip, bias is not None)
+    else:
+        plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, flip, out_keep,
+                          bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step,
+                          conj_signal=conj_signal, conj_kernel=conj_kernel)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)
     if bias is None:
@@ -558,6 +580,68 @@ def _long_geometry(signal: Tensor, kernel: Tensor, bias, padding, groups, causal
     return pad_left, pad_right, length + pad_left + pad_right
 
 
+LONG_DECIM_MAX_STRIDE = 64        # (stride x transform points stays below 2**30 up to the 2**24-point limit)
+LONG_DECIM_MAX_LEN = 1 << 29      # a row of the signal lies behind one buffer resource (include/fftconv_amd.h)
+
+
+def _long_decim_mode() -> Optional[bool]:
+    """FFTCONV_LONG_DECIM (read per call): ``False`` for "0" (never), ``True`` for "1" (wherever eligible), ``None`` when
+    unset or anything else: only where the construction the call takes otherwise does not fit 2**24 points."""
+    return {"0": False, "1": True}.get(os.environ.get("FFTCONV_LONG_DECIM", ""))
+
+
+def _long_decim_points(length: int, taps: int, stride: int, pad_left: int, pad_right: int, out_keep: int = 0) -> int:
+    """Points a decimated row needs: the kept outputs and the ceil(taps / stride) - 1 positions behind the last."""
+    nout = out_keep or (length + pad_left + pad_right - taps) // stride + 1
+    return nout + -(-taps // stride) - 1
+
+
+def _long_decim_eligible(length: int, taps: int, stride: int, pad_left: int, pad_right: int, out_keep: int, dilation: int = 1,
+                         pad_mode: int = 0, dtype=torch.float32, x_layout: str = "ncl") -> bool:
+    """Whether a decimation plan takes the strided primitive (pure): stride 2 ... 64, dilation 1, zero padding, float32 /
+    float16 / bfloat16, a signal that is not read as channels-last, L < 2**29, decimated points <= 2**24."""
+    return (2 <= stride <= LONG_DECIM_MAX_STRIDE and dilation == 1 and pad_mode == 0
+            and dtype in (torch.float32,) + _LOW_PRECISION and x_layout != "nlc" and length < LONG_DECIM_MAX_LEN
+            and _long_decim_points(length, taps, stride, pad_left, pad_right, out_keep) <= LONG_MAX_POINTS)
+
+
+def _long_route_of(length: int, taps: int, pad_left: int, pad_right: int, need: int, causal: bool, stride: int, dilation: int,
+                   pad_mode: int, dtype, x_layout: str) -> str:
+    """``_long_route`` from the numbers ``_long_geometry`` returns."""
+    if need <= LONG_HANDOFF_POINTS and dtype != torch.complex64:
+        return "handoff"
+    mode = _long_decim_mode()
+    if (mode is True or (mode is None and need > LONG_MAX_POINTS)) and _long_decim_eligible(
+            length, taps, stride, pad_left, pad_right, _long_keep(length, causal, stride), dilation, pad_mode, dtype, x_layout):
+        return "phases"
+    if need > LONG_MAX_POINTS:
+        raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
+                                  f"2**24 = {LONG_MAX_POINTS}")
+    return "plain"
+
+
+def _long_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, groups=1, causal=False,
+                padding_mode="constant", dtype=torch.float32, x_layout="ncl") -> str:
+    """Which route a ``fft_long_conv`` call takes (pure: shapes, numbers and FFTCONV_LONG_DECIM only):
+
+    ``"handoff"``  a real row whose padded length fits LONG_HANDOFF_POINTS: the ``fft_conv`` kernels;
+    ``"phases"``   stride 2 ... 64, dilation 1, ``padding_mode`` constant, float32 / float16 / bfloat16, a signal that is not
+                   read as channels-last, L < 2**29 and a decimated row of at most 2**24 points, causal or not:
+                   y[j] = sum_p (u_p * x_p)[j] on the ``stride`` decimated rows x_p[t] = xrow[stride*t + p] against the
+                   phases u_p[m] = u[stride*m + p] of the taps, a transform of about nout + ceil(K / stride) points.  Taken
+                   wherever eligible under FFTCONV_LONG_DECIM=1, never under =0 and, with the variable unset, only where
+                   the plain row does not fit 2**24 points;
+    ``"plain"``    everything else: the long primitive on the whole padded row, its stride skipping outputs.
+
+    ``x_layout``: ``_long_layout`` of the signal.  A row that fits no long route raises ``NotImplementedError`` with the count."""
+    meta = dict(device="meta")
+    signal, kernel = torch.empty(tuple(signal_shape), **meta), torch.empty(tuple(kernel_shape), **meta)
+    pad_left, pad_right, need = _long_geometry(signal, kernel, None, padding, groups, causal, stride, dilation, padding_mode)
+    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
+    return _long_route_of(int(signal_shape[2]), int(kernel_shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
+                          _native.PAD_MODES[padding_mode], dtype, x_layout)
+
+
 def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
                   causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant",
                   channels_last: bool = False) -> Tensor:
@@ -593,8 +677,17 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     tensors are copied.  ``FFTCONV_LONG_NLC=0`` (read per call) takes torch copies everywhere, as do rows that hand off
     to ``fft_conv``, the ``FFTCONV_HALF_IO=0`` path and tensors whose (L, C) block of one batch item reaches 2**31 bytes.
 
+    With stride s = 2 ... 64, dilation 1 and ``padding_mode`` constant on float32 / float16 / bfloat16 tensors (a signal
+    that is not read as channels-last; causal or not) the call can run BY PHASES instead: y[j] = sum_p (u_p * x_p)[j] on the
+    s decimated rows x_p[t] = xrow[s*t + p] against the phases u_p[m] = u[s*m + p] of the taps, one transform of about
+    nout + ceil(K/s) points per decimated row where the plain row needs L + 2*padding; signal and weight are read where
+    they lie.  ``FFTCONV_LONG_DECIM`` (read per call) selects it: "0" never, "1" wherever eligible, unset only where the
+    plain row does not fit 2**24 points (``_long_route`` names the route of a call).  A non-causal forward that ran by
+    phases has gradients of the same length (dX the transposed convolution of dY by phases, dW with the phases of x as a
+    batch-like index); a causal one keeps the plain gradients, so a causal row past 2**24 points cannot be trained.
+
     Real rows whose padded length is at most 4096 run the ``fft_conv`` kernels (complex rows stay here, at 64 x 64 points);
-    a row that needs more than 2**24 points raises ``NotImplementedError``.  float64 and complex128 tensors, tensors of
+    a row that fits no route inside 2**24 points raises ``NotImplementedError``.  float64 and complex128 tensors, tensors of
     different dtypes and mixes of real and complex tensors are not taken by this path (``TypeError``)."""
     return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode,
                                channels_last)
@@ -606,9 +699,8 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
     stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
     if not isinstance(channels_last, bool):
         raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
-    if need > LONG_MAX_POINTS:
-        raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
-                                  f"2**24 = {LONG_MAX_POINTS}")
+    route = _long_route_of(int(signal.shape[2]), int(kernel.shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
+                           _native.PAD_MODES[padding_mode], signal.dtype, _long_layout(signal) if _long_nlc_enabled() else "ncl")
     for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
         if t is not None:
             _require_long_dtype(name, t, signal.dtype)
@@ -621,7 +713,7 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
                                   causal, None, stride, dilation, padding_mode, channels_last)
         return out.to(signal.dtype)          # (keeps the strides)
-    if need <= LONG_HANDOFF_POINTS and signal.dtype != torch.complex64:      # (fft_conv has no complex route)
+    if route == "handoff":      # (fft_conv has no complex route: a complex row never gets here)
         if not causal:
             out = _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
         else:
@@ -633,7 +725,10 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
     if _needs_grad(signal, kernel, bias):
         from .autograd import FFTLongConvFunction
         return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum,
-                                         stride, dilation, padding_mode, channels_last)
+                                         stride, dilation, padding_mode, channels_last, route == "phases")
+    if route == "phases":
+        return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
+                         spectrum, channels_last=channels_last, decim=stride)
     return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
                      spectrum, pad_mode=_native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
                      channels_last=channels_last)

@@ -226,13 +226,24 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         spectrum = None
         cx = signal.dtype == torch.complex64 and (bias is None or bias.dtype == signal.dtype)
         # (a complex row never hands off to fft_conv; a lazily conjugated signal gets a plan of the same key)
-        if ((cx or F_.LONG_HANDOFF_POINTS < need) and need <= F_.LONG_MAX_POINTS and signal.is_cuda and weight.is_cuda
-                and signal.device == weight.device and signal.dtype == weight.dtype
+        if (signal.is_cuda and weight.is_cuda and signal.device == weight.device and signal.dtype == weight.dtype
                 and (signal.dtype == torch.float32 or cx or F_._half_native(signal, weight, bias))):
-            plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
-                                 F_._long_keep(signal.shape[2], self.causal, stride), bias is not None,
-                                 pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride)
-            spectrum = self._cached_spectrum(plan)
+            try:
+                route = F_._long_route_of(int(signal.shape[2]), int(weight.shape[2]), pad_left, pad_right, need, self.causal,
+                                          stride, dilation, F_._native.PAD_MODES[padding_mode], signal.dtype,
+                                          F_._long_layout(signal) if F_._long_nlc_enabled() else "ncl")
+            except NotImplementedError:
+                route = None      # (the functional raises it again, after its own checks)
+            keep = F_._long_keep(signal.shape[2], self.causal, stride)
+            if route == "phases":      # the decimation plan transforms the weight itself, as the plain plan does
+                plan = F_._long_decim_plan(signal, weight.shape[0], self.groups, weight.shape[2], stride, pad_left, pad_right,
+                                           keep, self.causal, bias is not None)
+                spectrum = self._cached_spectrum(plan)
+            elif route == "plain":
+                plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
+                                     keep, bias is not None, pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation,
+                                     out_step=stride)
+                spectrum = self._cached_spectrum(plan)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
                                       padding_mode, self.channels_last)
 

@@ -354,6 +354,43 @@ typedef struct fc_long_phases_desc {
 int fc_long_phases_geometry(const fc_long_phases_desc* desc, int64_t info[8]);
 int fc_long_phases_plan_create(const fc_long_phases_desc* desc, fc_long_plan** out_plan);
 
+/* Strided convolution by decimation (ABI 7 extension: new entry points only; every struct, enum value and call above keeps
+ * its layout, value and meaning).  The strided long primitive of dilation 1 on a zero-padded row,
+ *   y[b][(g,o)][j] = bias[(g,o)] + sum_i sum_k u[(g,o)][i][k] * xrow[b][(g,i)][s*j + k],   0 <= j < nout,
+ * xrow = x with pad_left zeros in front and pad_right behind, u = w in tensor order (flip 0) or flipped (flip 1), nout =
+ * out_keep or floor((L + pad_left + pad_right - K) / s) + 1, is the sum of s ordinary convolutions of decimated rows, the
+ * adjoint of the phases plan above: with k = s*m + p,
+ *   y[j] = sum_p sum_m u_p[m] * x_p[j + m],   x_p[t] = xrow[s*t + p],   u_p[m] = u[s*m + p].
+ * A decimation plan is the long plan of those: s * Cin input channels (i*s + p carries decimated row p of channel i),
+ * ceil(K / s) taps per filter row, one cyclic transform of N = N1 * N2 >= nout + ceil(K / s) - 1 points per row where the
+ * plain plan with out_step = s needs s*(nout - 1) + K.  The input side transforms the same samples in s shorter rows; the
+ * inverse side, W2 and the 2^24-point limit shrink s-fold.  The spectrum holds Cout * s * Cin/groups rows of N bins in the
+ * order [(g*Cog + o)][i*s + p].  Nothing is copied: the forward column pass reads position t of phase p from
+ * x[s*t + p - pad_left] where that lies in the row (zero elsewhere), and the filter rows are read from the (Cout,
+ * Cin/groups, K) weight where it lies, in either tap order; a tap past K - 1 ends a shorter phase, a phase p >= K has none.
+ *   The geometry call validates the descriptor and touches no device; info words as fc_long_plan_info.
+ *   The plan is an fc_long_plan: fc_long_plan_info, fc_long_transform_kernel_io (FC_F32 / FC_F16 / FC_BF16),
+ *   fc_long_forward_io (x (B, Cin, L) -> y (B, Cout, nout)) and fc_long_plan_destroy take it; fc_long_plan_kind answers
+ *   FC_LONG_REAL; slabs, workspace, FFTCONV_LONG_N and dtype rules are those of any real long plan.  fc_long_forward_lay
+ *   takes FC_LONG_NLC for y (the last pass is that of every long plan) and answers FC_ERR_UNSUPPORTED with text for a
+ *   channels-last x.
+ * 2 <= stride <= 64, paddings and out_keep >= 0, K <= L + pad_left + pad_right, out_keep <= the output length
+ * (FC_ERR_INVALID otherwise); L, K and the paddings below 2^29, stride * N <= 2^30 and the forward grid of a slab inside 2^31
+ * workgroups (FC_ERR_UNSUPPORTED); a decimated row that needs more than 2^24 points answers as fc_long_geometry does. */
+typedef struct fc_long_decim_desc {
+  int64_t batch, in_channels, out_channels, groups;
+  int64_t length;        /* L: samples per signal row */
+  int64_t kernel;        /* K: taps per filter row; weight is (Cout, Cin/groups, K) */
+  int64_t stride;
+  int64_t pad_left, pad_right;
+  int64_t out_keep;      /* leading output samples kept; 0 = all of them */
+  int32_t flip;          /* tap order, as in fc_long_desc */
+  int32_t has_bias;
+} fc_long_decim_desc;
+
+int fc_long_decim_geometry(const fc_long_decim_desc* desc, int64_t info[8]);
+int fc_long_decim_plan_create(const fc_long_decim_desc* desc, fc_long_plan** out_plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,14 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
         return fail(FC_ERR_INVALID, "axis %d: spatial/kernel/stride/dilation must be >= 1 and padding >= 0", i);
     }
     p->kd[i] = (d.kernel[i] - 1) * d.dilation[i] + 1;
+    {
+      // padded extent and stride-1 output count of an axis are held as int here and in every kernel's arguments
+      const int64_t ext = d.transposed ? (d.spatial[i] - 1) * d.stride[i] + 2 * (p->kd[i] - 1) + d.output_padding[i] + 1
+                                       : d.spatial[i] + 2 * d.padding[i];
+      if (ext >= ((int64_t)1 << 31))
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: padded extent %lld exceeds 32-bit positions (must be < 2^31 samples)", i,
+                    (long long)ext);
+    }
     if (d.transposed) {
       // functional.py:126-154: spread by the stride, full correlation, keep out samples from `padding`
       const int64_t out = (d.spatial[i] - 1) * d.stride[i] - 2 * d.padding[i] + p->kd[i] - 1 + d.output_padding[i] + 1;

@@ -16,6 +16,10 @@ static bool fast_path_eligible(const fc_plan* p) {
   const fc_desc& d = p->d;
   if (p->CB != 8 || p->accumulate || p->f1d.chunk_launches || p->Cog % 8 != 0 || d.stride[0] != 1) return false;   // (a transposed plan with stride 1 is a padded correlation: same kernel)
   if (((int64_t)d.in_channels * 3 + p->Cig) * d.spatial[0] * 4 >= ((int64_t)1 << 32)) return false;
+  // the kernel stores through a resource over one out-chunk's rows of a batch item (cob * Lout samples) and marks a dead
+  // store with bit 31 of its offset: that stays outside only while the rows end below bit 31, a few KB of immediate
+  // offsets included (zero padding makes Lout as long as it likes while L stays short)
+  if ((int64_t)p->cob * p->out_sp[0] * 4 >= 0x7F000000LL) return false;
   return true;
 }
 

@@ -75,10 +75,11 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
     return fail(FC_ERR_INVALID, "src_up (%d), tap_dil (%d) and out_step (%d) must be >= 1", e.src_up, e.tap_dil, e.out_step);
   if (e.src_up > 1 && e.pad_mode != PAD_CONSTANT)
     return fail(FC_ERR_INVALID, "src_up (%d) spreads the row over zeros: it goes with pad_mode constant only", e.src_up);
-  const int64_t lim = (int64_t)1 << 30;
+  // (4-byte samples: a row lies behind one resource of at most 2^31 bytes, where the offset 2^31 still reads as zero)
+  const int64_t lim = (int64_t)1 << 29;
   if (d.length > lim || d.kernel > lim || d.pad_left > lim || d.pad_right > lim || e.src_up > lim || e.tap_dil > lim ||
       e.out_step > lim)
-    return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of more than 2^30 samples are not addressed by the long-filter kernels");
+    return fail(FC_ERR_UNSUPPORTED, "rows, filters and paddings of more than 2^29 samples are not addressed by the long-filter kernels");
   // (8-byte samples: the byte size of a row and every offset in use stay below the 2^31 that reads as zero)
   const int64_t clim = (int64_t)1 << 28;
   if (cx && (d.length >= clim || d.kernel >= clim || d.pad_left >= clim || d.pad_right >= clim))

@@ -301,7 +301,8 @@ def test_tensor_on_a_non_current_device():
 def test_nd_block_of_bin_columns_beyond_2_gib_is_refused(monkeypatch):
     """The row passes address one block of bin columns per workgroup with 32-bit byte offsets: a second-to-last axis so long
     that Tx/2 bin columns of it span 2 GiB is refused at plan creation (a documented limit) instead of
-    computing with wrapped offsets.  Just below the limit the same shape family still runs.  (Since round 3 the planner cuts a
+    computing with wrapped offsets.  Just below the limit the same shape family still runs (here at 77 MB; at 0.92 of the
+    limit, every sample checked: the entry nd-bin-columns of tests/test_gpu_thresholds.py).  (Since round 3 the planner cuts a
     600-sample row into 64-point tiles -- 32 bin columns, far below the limit -- so the refusal is provoked with the single
     1024-point transform of round 2, FFTCONV_XTILE=0.)"""
     from fft_conv_pytorch_amd import _native

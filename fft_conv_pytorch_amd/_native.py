@@ -31,6 +31,8 @@ EXPORTS = (
     "fc_long_forward_lay",
     "fc_long_phases_geometry", "fc_long_phases_plan_create",
     "fc_long_decim_geometry", "fc_long_decim_plan_create",
+    "fc_long_wgrad_geometry", "fc_long_wgrad_check_io", "fc_long_wgrad_plan_create", "fc_long_wgrad_plan_destroy",
+    "fc_long_wgrad_plan_info", "fc_long_wgrad",
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
@@ -98,6 +100,16 @@ class FcLongDecimDesc(ctypes.Structure):
     ]
 
 
+class FcLongWgradDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_wgrad_desc`` (the weight gradient of the layer a long plan runs)."""
+    _fields_ = [
+        ("batch", ctypes.c_int64), ("in_channels", ctypes.c_int64), ("out_channels", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("length", ctypes.c_int64), ("kernel", ctypes.c_int64),
+        ("pad_left", ctypes.c_int64), ("pad_right", ctypes.c_int64), ("out_len", ctypes.c_int64),
+        ("flip", ctypes.c_int32), ("pad_mode", ctypes.c_int32), ("stride", ctypes.c_int32), ("dilation", ctypes.c_int32),
+    ]
+
+
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
 FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans only)
 # enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
@@ -106,6 +118,8 @@ LONG_REAL, LONG_COMPLEX, LONG_CONJ_SIGNAL, LONG_CONJ_TAPS = 0, 1, 2, 4
 LONG_NCL, LONG_NLC = 0, 1
 LONG_NLC_MAX_BYTES = 1 << 31      # one batch item's (L, C) block of a channels-last tensor stays below this
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
+# ... of a weight-gradient plan: no spectrum; the taps of a row and how many of their lags are transformed
+LONG_WGRAD_INFO_WORDS = ("N1", "N2", "taps", "lags", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
 class NativeLibraryMissing(ImportError):
@@ -206,6 +220,19 @@ def load_library() -> ctypes.CDLL:
         lib.fc_long_decim_geometry.restype = i32
         lib.fc_long_decim_plan_create.argtypes = [ctypes.POINTER(FcLongDecimDesc), ctypes.POINTER(vp)]
         lib.fc_long_decim_plan_create.restype = i32
+        wdesc = ctypes.POINTER(FcLongWgradDesc)
+        lib.fc_long_wgrad_geometry.argtypes = [wdesc, i64x8]
+        lib.fc_long_wgrad_geometry.restype = i32
+        lib.fc_long_wgrad_check_io.argtypes = [wdesc, i32, i32, i32, i32, i32]
+        lib.fc_long_wgrad_check_io.restype = i32
+        lib.fc_long_wgrad_plan_create.argtypes = [wdesc, ctypes.POINTER(vp)]
+        lib.fc_long_wgrad_plan_create.restype = i32
+        lib.fc_long_wgrad_plan_destroy.argtypes = [vp]
+        lib.fc_long_wgrad_plan_destroy.restype = None
+        lib.fc_long_wgrad_plan_info.argtypes = [vp, i64x8]
+        lib.fc_long_wgrad_plan_info.restype = i32
+        lib.fc_long_wgrad.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]
+        lib.fc_long_wgrad.restype = i32
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
@@ -561,10 +588,78 @@ class LongDecimPlan(LongPlan):
         return handle
 
 
+def wgrad_desc(key: Tuple) -> FcLongWgradDesc:
+    """``struct fc_long_wgrad_desc`` of a weight-gradient key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_len,
+    flip, pad_mode, stride, dilation)."""
+    if len(key) != 13:
+        raise ValueError(f"a weight-gradient key has 13 words, got {len(key)}")
+    d = FcLongWgradDesc()
+    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_len, d.flip,
+     d.pad_mode, d.stride, d.dilation) = (int(v) for v in key)
+    return d
+
+
+def wgrad_geometry(key: Tuple) -> dict:
+    """``fc_long_wgrad_geometry``: the info words of the weight-gradient plan this key would get (no device)."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    st = lib.fc_long_wgrad_geometry(ctypes.byref(wgrad_desc(key)), ctypes.byref(info))
+    if st != FC_OK:
+        _raise(lib, st)
+    return {name: int(info[i]) for i, name in enumerate(LONG_WGRAD_INFO_WORDS)}
+
+
+def wgrad_check_io(key: Tuple, x_dtype: int = 0, x_layout: int = LONG_NCL, dy_dtype: int = 0, dy_layout: int = LONG_NCL,
+                   dw_dtype: int = 0):
+    """``fc_long_wgrad_check_io``: raises what ``LongWgradPlan.run`` would raise for these element types and layouts, from
+    the descriptor alone (no device)."""
+    lib = load_library()
+    st = lib.fc_long_wgrad_check_io(ctypes.byref(wgrad_desc(key)), x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype)
+    if st != FC_OK:
+        _raise(lib, st)
+
+
+class LongWgradPlan:
+    """Owns one ``fc_long_wgrad_plan`` (immutable after creation; created on the CURRENT HIP device, which the caller sets to
+    ``device_index``): dW of the layer a long plan runs, from x and dY where they lie.  Element types (fc_dtype codes 0, 2,
+    3) and layouts (LONG_NCL / LONG_NLC) of x and dY and the element type of dW are named per ``run``; the workspace is
+    float32.  ``new_workspace`` sizes it by ``workspace_bytes``."""
+
+    def __init__(self, key: Tuple, device_index: int = 0):
+        lib = load_library()
+        handle = ctypes.c_void_p()
+        st = lib.fc_long_wgrad_plan_create(ctypes.byref(wgrad_desc(key)), ctypes.byref(handle))
+        if st != FC_OK:
+            _raise(lib, st)
+        self._lib, self._h, self.key = lib, handle, key
+        self.device_index = int(device_index)
+        info = (ctypes.c_int64 * 8)()
+        lib.fc_long_wgrad_plan_info(handle, ctypes.byref(info))
+        self.info = {name: int(info[i]) for i, name in enumerate(LONG_WGRAD_INFO_WORDS)}
+        self.workspace_bytes = self.info["workspace_bytes"]
+
+    def run(self, x_ptr: int, dy_ptr: int, dw_ptr: int, workspace_ptr: int, stream: int, x_dtype: int = 0,
+            dy_dtype: int = 0, dw_dtype: int = 0, x_layout: int = LONG_NCL, dy_layout: int = LONG_NCL):
+        st = self._lib.fc_long_wgrad(self._h, x_ptr, x_dtype, x_layout, dy_ptr, dy_dtype, dy_layout, dw_ptr, dw_dtype,
+                                     workspace_ptr, stream)
+        if st != FC_OK:
+            _raise(self._lib, st)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                self._lib.fc_long_wgrad_plan_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
 # the tag of a long-filter key -> the class that owns its plan
 _LONG_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan}
 # ... and of the plans added since (get_plan looks here second)
 _LONG_TAGS_MORE = {"long_decim": LongDecimPlan}
+# ... and of the plans of the same cache that are no forward plans (get_plan looks here third)
+_WGRAD_TAGS = {"long_wgrad": LongWgradPlan}
 
 
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
@@ -592,7 +687,8 @@ def get_plan(device_index: int, key: Tuple) -> Plan:
         plan = _plans.get(full)
         if plan is None:
             # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
-            cls = (_LONG_TAGS.get(key[0]) or _LONG_TAGS_MORE.get(key[0])) if key and isinstance(key[0], str) else None
+            cls = ((_LONG_TAGS.get(key[0]) or _LONG_TAGS_MORE.get(key[0]) or _WGRAD_TAGS.get(key[0]))
+                   if key and isinstance(key[0], str) else None)
             plan = cls(key[1:], device_index) if cls is not None else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):

@@ -407,6 +407,12 @@ class FFTLongConvFunction(torch.autograd.Function):
 
     torch builds the transposed copies of the operands.
 
+    FFTCONV_LONG_WGRAD=1 (read per call; ``F_._long_wgrad_route`` names the route) takes dW on this branch from a
+    weight-gradient plan instead (``F_._long_wgrad_run``, float32 / float16 / bfloat16): x and dY are read where they lie,
+    contiguous or channels-last, the correlation is summed over the batch pairs in registers, and dW is stored in the
+    weight's own order and dtype (16-bit: the float32 result rounded once) -- no ``xt``, ``dyt`` or flipped copy exists.
+    Its bits differ from the exchanged route's.  dX and db are unchanged.
+
     A non-causal forward that ran by phases (``decim``: ``F_._long_route`` "phases", a decimation plan) has the gradients of
     the same length: dX is the transposed convolution of dY run by PHASES (``F_._long_transpose_run``: stride s, padding p,
     output_padding (L + 2p - K) mod s, the (Cout, Cin/g, K) weight read where it lies), and dW the primitive with the phase
@@ -500,7 +506,11 @@ class FFTLongConvFunction(torch.autograd.Function):
                     dx = dx.to(grad.dtype)
                     if x_nlc:
                         dx = F_._as_channels_last(dx)
-        if ctx.needs_input_grad[1]:
+        wkey = F_._long_wgrad_key(B, cin, cout, g, L, K, pad_left, pad_right, grad.shape[2], flip, mode, s, d)
+        if ctx.needs_input_grad[1] and F_._long_wgrad_eligible(wkey, signal.dtype):
+            # FFTCONV_LONG_WGRAD=1: x and dY where they lie, dW in the weight's own order and dtype
+            dw = F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype)
+        elif ctx.needs_input_grad[1]:
             xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
             dyt = grad.permute(1, 0, 2).contiguous()
             du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32, pad_mode=mode,

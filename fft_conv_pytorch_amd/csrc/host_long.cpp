@@ -272,6 +272,63 @@ int decim_geometry(const fc_long_decim_desc* desc, LongGeom* out) {
   return FC_OK;
 }
 
+// The weight gradient of the layer a forward long plan runs: the forward plan's own geometry -- N1 x N2, the
+// taps it reads (keff of them from tap0 in steps of tstep), padl -- with a workspace of its own: W1 of x and W1 of dY for
+// the batch pairs of a slab, and W2 for all Cout * Cin/g rows of dW, which the slabs add into.
+struct WgradGeom {
+  LongGeom f;                   // the forward plan of the layer, out_keep = out_len
+  int64_t rows;                 // Cout * Cin/g rows of dW
+  int ob;                       // output channels per workgroup of the row pass
+  int64_t slab_pairs, slabs;
+  size_t workspace_bytes;
+};
+
+int wgrad_geometry(const fc_long_wgrad_desc* desc, WgradGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_wgrad_desc& d = *desc;
+  if (d.out_len < 1) return fail(FC_ERR_INVALID, "out_len (%lld) must be positive", (long long)d.out_len);
+  if (d.stride < 1 || d.dilation < 1)
+    return fail(FC_ERR_INVALID, "stride (%d) and dilation (%d) must be >= 1", d.stride, d.dilation);
+  fc_long_desc f{};
+  f.batch = d.batch; f.in_channels = d.in_channels; f.out_channels = d.out_channels; f.groups = d.groups;
+  f.length = d.length; f.kernel = d.kernel; f.pad_left = d.pad_left; f.pad_right = d.pad_right;
+  f.out_keep = d.out_len; f.flip = d.flip; f.has_bias = 0;
+  const fc_long_ext e = {d.pad_mode, 1, d.dilation, d.stride};
+  WgradGeom w{};
+  const int st = long_geometry(&f, &e, FC_LONG_REAL, &w.f);
+  if (st != FC_OK) return st;
+  const LongGeom& g = w.f;
+  const LongImpl* rows = find_long(g.N2);
+  w.ob = rows ? rows->wg_ob : 1;
+  w.rows = g.Cout * g.Cig;
+  int64_t budget_mb = kDefaultBudgetMB;
+  if (const char* env = getenv("FFTCONV_LONG_WS_MB"))
+    if (*env && atoll(env) > 0) budget_mb = atoll(env);
+  const int64_t row_bytes = g.N * 8, budget = budget_mb << 20;
+  if (w.rows > budget / row_bytes)
+    return fail(FC_ERR_UNSUPPORTED, "the weight gradient keeps %lld x %lld rows of %lld points (%lld MiB) in its workspace, more than "
+                "the budget of %lld MiB (FFTCONV_LONG_WS_MB)", (long long)g.Cout, (long long)g.Cig, (long long)g.N,
+                (long long)((w.rows * row_bytes) >> 20), (long long)budget_mb);
+  const int64_t pair_bytes = (g.Cin + g.Cout) * row_bytes;
+  w.slab_pairs = std::max<int64_t>(1, std::min<int64_t>(g.npairs, (budget - w.rows * row_bytes) / pair_bytes));
+  w.slabs = (g.npairs + w.slab_pairs - 1) / w.slab_pairs;
+  w.workspace_bytes = (size_t)(w.slab_pairs * pair_bytes + w.rows * row_bytes);
+  // grids are 32-bit: the column passes over x and dY (as the forward's), the row pass and the inverse pass over dW's rows
+  const int64_t nob = (g.Cog + w.ob - 1) / w.ob;
+  const int64_t worst = std::max<int64_t>(std::max<int64_t>(g.N2 / 2, g.N1 / 2) * std::max(w.slab_pairs * std::max(g.Cin, g.Cout), w.rows),
+                                          (g.N1 / 2) * g.G * g.Cig * nob);
+  if (worst > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "a weight gradient of %lld x %lld rows, %lld batch pairs per slab and %lld points exceeds the 2^31 "
+                "workgroups of one launch", (long long)g.Cout, (long long)g.Cig, (long long)w.slab_pairs, (long long)g.N);
+  *out = w;
+  return FC_OK;
+}
+
+void fill_wgrad_info(const WgradGeom& w, int64_t info[8]) {
+  info[0] = w.f.N1; info[1] = w.f.N2; info[2] = w.f.K; info[3] = w.f.keff;
+  info[4] = (int64_t)w.workspace_bytes; info[5] = w.slabs; info[6] = w.ob; info[7] = w.slab_pairs;
+}
+
 void fill_info(const LongGeom& g, int64_t info[8]) {
   info[0] = g.N1; info[1] = g.N2; info[2] = g.ph_s ? g.ph_lout : g.nout; info[3] = (int64_t)g.spectrum_bytes;
   info[4] = (int64_t)g.workspace_bytes; info[5] = g.slabs; info[6] = g.ob; info[7] = g.slab_pairs;
@@ -322,6 +379,11 @@ struct fc_long_plan {
   const fc::LongImpl* rows;    // N2-point geometry
   fc::Twiddles tw1, tw2;
   LongTables lt;
+};
+
+struct fc_long_wgrad_plan {
+  WgradGeom w;
+  std::unique_ptr<fc_long_plan> f;      // kernels and tables: those of the forward plan of the layer
 };
 
 namespace {
@@ -598,6 +660,120 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     }
     FC_HIP(plan->cols->cols_inv(a, map_out, y_nlc, np, st));
   }
+  return FC_OK;
+}
+
+// ---- the weight gradient (include/fftconv_amd.h "Weight gradient of a long plan")
+
+int fc_long_wgrad_geometry(const fc_long_wgrad_desc* desc, int64_t info[8]) {
+  if (!info) return fail(FC_ERR_INVALID, "null argument");
+  WgradGeom w;
+  const int st = wgrad_geometry(desc, &w);
+  if (st != FC_OK) return st;
+  fill_wgrad_info(w, info);
+  return FC_OK;
+}
+
+// the element codes of a call and its layouts against the sizes of the plan's tensors
+static int wgrad_io(const WgradGeom& w, int x_dtype, int x_layout, int dy_dtype, int dy_layout, int dw_dtype, int* xio,
+                    int* dyio, int* dwio) {
+  if (int e = io_code(x_dtype, "x", xio)) return e;
+  if (int e = io_code(dy_dtype, "dy", dyio)) return e;
+  if (int e = io_code(dw_dtype, "dw", dwio)) return e;
+  if (int e = layout_check(x_layout, "x", w.f.L, w.f.Cin, *xio)) return e;
+  return layout_check(dy_layout, "dy", w.f.nout, w.f.Cout, *dyio);
+}
+
+int fc_long_wgrad_check_io(const fc_long_wgrad_desc* desc, int x_dtype, int x_layout, int dy_dtype, int dy_layout,
+                           int dw_dtype) {
+  WgradGeom w;
+  if (int e = wgrad_geometry(desc, &w)) return e;
+  int xio = 0, dyio = 0, dwio = 0;
+  return wgrad_io(w, x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype, &xio, &dyio, &dwio);
+}
+
+int fc_long_wgrad_plan_create(const fc_long_wgrad_desc* desc, fc_long_wgrad_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_wgrad_plan> p(new fc_long_wgrad_plan());
+  int st = wgrad_geometry(desc, &p->w);
+  if (st != FC_OK) return st;
+  // (the tables and kernels of the forward plan of the layer)
+  std::unique_ptr<fc_long_plan> f(new fc_long_plan());
+  f->g = p->w.f;
+  fc_long_plan* fp = nullptr;
+  if ((st = finish_long_plan(f, &fp)) != FC_OK) return st;
+  p->f.reset(fp);
+  *out_plan = p.release();
+  return FC_OK;
+}
+
+void fc_long_wgrad_plan_destroy(fc_long_wgrad_plan* plan) { delete plan; }
+
+int fc_long_wgrad_plan_info(const fc_long_wgrad_plan* plan, int64_t info[8]) {
+  if (!plan || !info) return fail(FC_ERR_INVALID, "null argument");
+  fill_wgrad_info(plan->w, info);
+  return FC_OK;
+}
+
+int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
+                  int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream) {
+  if (!plan || !x || !dy || !dw || !workspace) return fail(FC_ERR_INVALID, "null argument");
+  const WgradGeom& w = plan->w;
+  int xio = 0, dyio = 0, dwio = 0;
+  if (int e = wgrad_io(w, x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype, &xio, &dyio, &dwio)) return e;
+  const LongGeom& g = w.f;
+  const fc_long_plan& fp = *plan->f;
+  hipStream_t st = (hipStream_t)hip_stream;
+  f2* const w1x = (f2*)workspace;
+  f2* const w1dy = w1x + (size_t)(w.slab_pairs * g.Cin * g.N);
+  f2* const w2 = w1dy + (size_t)(w.slab_pairs * g.Cout * g.N);
+  const int64_t nob = (g.Cog + w.ob - 1) / w.ob;
+  for (int64_t s = 0; s < w.slabs; ++s) {
+    const int64_t pair0 = s * w.slab_pairs;
+    const int64_t np = std::min(w.slab_pairs, g.npairs - pair0);
+    // x: the rows the forward reads, its padding mode and paddings
+    LongArgs a = base_args(fp);
+    a.pair0 = (int)pair0;
+    a.src = (const float*)x; a.src_io = xio;
+    a.w1 = w1x;
+    a.C = (int)g.Cin;
+    FC_HIP(fp.cols->cols_fwd(a, g.pad_mode != PAD_CONSTANT, x_layout == FC_LONG_NLC, np, st));
+    // dY: rows of nout samples spread over the grid of the stride, zero elsewhere
+    LongArgs b = base_args(fp);
+    b.pair0 = (int)pair0;
+    b.src = (const float*)dy; b.src_io = dyio;
+    b.w1 = w1dy;
+    b.C = (int)g.Cout;
+    b.L = (int)g.nout; b.padl = 0;
+    b.pad_mode = PAD_CONSTANT; b.mpadl = 0; b.mpadr = 0;
+    b.src_up = (int)g.step; b.d_up = make_fastdiv((unsigned)g.step);
+    FC_HIP(fp.cols->cols_fwd(b, g.step > 1, dy_layout == FC_LONG_NLC, np, st));
+    // the product summed over the pairs of the slab, transformed back into W2 (a later slab adds)
+    LongArgs r = base_args(fp);
+    r.w1 = w1x; r.spec = w1dy; r.w2 = w2;
+    r.B = (int)np;
+    r.spec_mode = s > 0;
+    r.ob = w.ob; r.nob = (int)nob;
+    r.C = 1;
+    FC_HIP(fp.rows->wgrad_rows(r, g.G * g.Cig * nob, st));
+  }
+  // one item of Cout * Cin/g rows: lag dilation * q -> the element of tap q, the imaginary part dropped
+  LongArgs c = base_args(fp);
+  c.B = 1; c.pair0 = 0;
+  c.w2 = w2;
+  c.y = (float*)dw; c.y_io = dwio; c.bias = nullptr;
+  c.C = (int)w.rows;
+  c.d_ostep = make_fastdiv((unsigned)g.dil);
+  FC_HIP(fp.cols->wgrad_inv(c, st));
+  // the elements whose tap meets no data for any output: zero (two strided fills, in front of and behind the kept taps)
+  const int64_t es = io_bytes(dwio);
+  const int64_t first = g.tstep > 0 ? g.tap0 : g.tap0 - (g.keff - 1), behind = g.K - (first + g.keff);
+  if (first > 0)
+    FC_HIP(hipMemset2DAsync(dw, (size_t)(g.K * es), 0, (size_t)(first * es), (size_t)w.rows, st));
+  if (behind > 0)
+    FC_HIP(hipMemset2DAsync((char*)dw + (first + g.keff) * es, (size_t)(g.K * es), 0, (size_t)(behind * es), (size_t)w.rows, st));
   return FC_OK;
 }
 

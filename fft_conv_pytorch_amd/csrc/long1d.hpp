@@ -66,6 +66,14 @@
 // order or flipped; a tap past K - 1 ends a shorter phase, a phase p >= K has no tap.  long_rows sees s*Cig input
 // channels per group and long_cols_inv is the unchanged one, its channels-last build included.
 //
+// The weight gradient (long_wgrad_rows and the WG build of long_cols_inv; host_long.cpp fc_long_wgrad) reads x and dY where
+// they lie: both are signal-shaped, so long_cols_fwd transforms both with its signal builds (dY spread by the stride,
+// src_up), z = x[2p] + i*x[2p+1] and w = dY[2p] + i*dY[2p+1] riding one complex row each.  The correlation theorem,
+//   IFFT( FFT(z) * conj(FFT(w)) )[m] = sum_t conj(w[t]) * z[t + m],
+// has the pair's contribution to dW in its real part (the cross terms are imaginary), so long_wgrad_rows sums the product
+// over the batch pairs in registers, bin by bin, and transforms back once per (o, i); long_cols_inv drops the imaginary
+// part (one item with no partner) and stores lag tap_dil*q at the place of tap q in the weight's own order.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -82,7 +90,7 @@ struct LongArgs {
   float* y;              // (B, Cout, nout); element type y_io
   f2* w1;                // [row][k1][n2]   rows: (pair, input channel) or filter rows of this launch
   f2* w2;                // [row][k1][n2]   rows: (pair, output channel)
-  const f2* spec;        // [(g*Cog + o)*Cig + i][k1][k2]
+  const f2* spec;        // [(g*Cog + o)*Cig + i][k1][k2]   (long_wgrad_rows: W1 of dY, rows (pair, output channel))
   f2* spec_out;          // rows mode 1: first filter row of this launch
   const f2* thi;         // [N >> 12]  w_N^(a * 4096)
   const f2* tlo;         // [4096]     w_N^b
@@ -90,8 +98,8 @@ struct LongArgs {
   const f2* twA2; const f2* twB2;    // ... of the N2-point tile
   int N1, N2, lgN2;
   int from_kernel;       // cols_fwd: 0 signal rows, 1 filter rows
-  int spec_mode;         // rows: 1 = finish the filter spectrum
-  int B, pair0;          // batch size, first pair of this slab
+  int spec_mode;         // rows: 1 = finish the filter spectrum   (long_wgrad_rows: 1 = add to what W2 holds, a later slab)
+  int B, pair0;          // batch size, first pair of this slab   (long_wgrad_rows: B = the batch pairs of this slab)
   int C;                 // channels of the source tensor (signal) / of y
   int G, Cig, Cog, ob, nob;
   int L, padl;           // signal: row position p holds x[p - padl]
@@ -442,12 +450,118 @@ __global__ __launch_bounds__(NT) void long_rows_kernel(const LongArgs a) {
   });
 }
 
+// ------------------------------------------------------------------------------------------ long_wgrad_rows
+// acc += x * conj(d)
+__device__ __forceinline__ void cmac_conj(f2& acc, f2 x, f2 d) {
+  asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_hi:[0,1,0]" : "+v"(acc) : "v"(d), "v"(x));
+}
+
+// The middle pass of the weight gradient.  NSEQ neighbouring k1 rows per workgroup, one sequence each; ONE input channel
+// i of a group and OB output channels of that group per workgroup.  For every batch pair of the slab (a.B of them) the
+// W1 row of x (pair, (g, i)) and the W1 rows of dY (pair, (g, o)), a.spec, are transformed and X * conj(D) is summed in
+// registers, in the order the inverse transform starts from; then, per output channel, the inverse transform, 1 / N and
+// the conjugate twiddle as in long_rows, into W2 row (g*Cog + o)*Cig + i -- the row order of the weight.  With
+// a.spec_mode the result is added to what W2 holds (the pairs of an earlier slab).
+template <int P, int S, int NSEQ, int NT, int OB>
+__global__ __launch_bounds__(NT) void long_wgrad_rows_kernel(const LongArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;                       // == a.N2
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS, "one thread slot per point group");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA2, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB2, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  f2* lseq = lds + sq * LSEQP;
+  unsigned q;
+  const int k1 = (int)fdivmod(blockIdx.x, a.d_nblk, &q) * NSEQ + sq;
+  const size_t N = (size_t)a.N1 * T;
+  const unsigned rowoff = (unsigned)k1 * (unsigned)(T * 8);      // byte offset of this k1 row inside a row of N points
+  const unsigned toff = rowoff + (unsigned)tseq * 8u;
+  const int ob0 = (int)fdivmod(q, a.d_nob, &q) * OB;
+  const int g = (int)fdivmod(q, a.d_g, &q);
+  const int i = (int)q;
+  const int Cin = a.G * a.Cig, Cout = a.G * a.Cog;
+  f2 acc[OB][P];
+#pragma unroll
+  for (int o = 0; o < OB; ++o)
+#pragma unroll
+    for (int i1 = 0; i1 < P; ++i1) acc[o][i1] = mk2(0.f, 0.f);
+
+  const unsigned rbytes = (unsigned)(N * 8);
+  // (ONE transform in the code for the row of x, h == 0, and the rows of dY, h - 1 == o: the scalar registers hold the
+  // constants of one)
+  const int nrows = 1 + min(OB, a.Cog - ob0);
+#pragma unroll 1
+  for (int pr = 0; pr < a.B; ++pr) {
+    f2 v[P];
+#pragma unroll 1
+    for (int h = 0; h < nrows; ++h) {    // (workgroup-uniform, so the barriers inside are met by all)
+      // the W1 row of x (pair, (g, i)), or of dY (pair, (g, ob0 + h - 1))
+      const size_t row = h ? (size_t)pr * Cout + (size_t)(g * a.Cog + ob0 + h - 1) : (size_t)pr * Cin + (size_t)(g * a.Cig + i);
+      const BufRsrc sr = make_rsrc((h ? a.spec : a.w1) + row * N, rbytes);
+      f2 d[P];
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) d[n1] = buf_load_f32x2(sr, toff, G::N2 * n1 * 8);
+      fwd_from_regs<G>(d, lseq, tseq, true, twA, twB);
+      seq_sync<G>();
+      nat_load<G>(d, lseq, tseq);
+      seq_sync<G>();                     // the next transform writes this sequence's slots
+      if (h == 0) {
+#pragma unroll
+        for (int i1 = 0; i1 < P; ++i1) v[i1] = d[i1];
+      }
+      static_for<0, OB>([&](auto oc) {
+        constexpr int o = decltype(oc)::value;
+        if (h == o + 1) {
+#pragma unroll
+          for (int i1 = 0; i1 < P; ++i1) cmac_conj(acc[o][i1], v[i1], d[i1]);
+        }
+      });
+    }
+  }
+
+  const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
+  const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
+  static_for<0, OB>([&](auto oc) {
+    constexpr int o = decltype(oc)::value;
+    if (ob0 + o < a.Cog) {               // (workgroup-uniform, so the barriers inside are met by all)
+      passA_fft_twiddle_store<G, +1>(acc[o], lseq, tseq, twA);
+      seq_sync<G>();
+      f2 v[P];
+      passB_load<G>(v, lseq, tseq);
+      const int j = passB_compute<G, +1>(v, tseq, twB);
+      seq_sync<G>();
+      const int nbase = (tseq >> G::LGS) + P * P * j;
+      const BufRsrc orr = make_rsrc(a.w2 + (((size_t)g * a.Cog + ob0 + o) * a.Cig + i) * N, (unsigned)(N * 8));
+      // (the first slab reads what W2 holds at an offset outside the resource, that is as zero; a later slab adds to it)
+      const unsigned poff = a.spec_mode ? 0u : 0x80000000u;
+#pragma unroll
+      for (int k = 0; k < P; ++k) {
+        const unsigned n2 = (unsigned)(nbase + P * k);
+        const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
+        const f2 prev = buf_load_f32x2(orr, poff + rowoff + n2 * 8u, 0);
+        const f2 r = cmulc(v[k], w);
+        buf_store_f32x2(mk2(prev.x + r.x * a.scale, prev.y + r.y * a.scale), orr, rowoff + n2 * 8u, 0);
+      }
+    }
+  });
+}
+
 // ------------------------------------------------------------------------------------------ long_cols_inv
-template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false>
+// The weight-gradient build (WG; mapped form, real rows, (rows, K) weight): a launch of ONE item (a.B == 1, so the
+// imaginary part is dropped) whose "channels" are the a.C = Cout * Cin/g rows of dW, each a.K elements long: sample
+// out_step * q of the row, q < a.keff, is the lag of tap q and goes where long_cols_fwd reads that tap of a filter row,
+// element a.tap0 + a.tstep * q (tensor order or flipped); the elements no kept lag reaches are not touched (the host
+// zeroes them).
+template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false,
+          bool WG = false>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   using G = Geo<P, S>;
   static_assert(!CX || IO == IO_F32, "a complex sample is a pair of float32");
   static_assert(!PHS || (NC > 0 && !CX), "phases: the block layout of the channels-last build, real rows");
+  static_assert(!WG || (MAP && !CX && NC == 0 && !PHS), "weight gradient: the mapped form, real rows, no block layout");
   constexpr bool NLC = NC > 0;                  // channels-last y, the block map of long_cols_fwd (PHS: phases for channels)
   constexpr int M = NLC ? NC : 1;
   constexpr int NN = NSEQ / M;
@@ -544,6 +658,9 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   if constexpr (NLC && !PHS) {
     y0 = io_ptr<IO>(a.y) + (size_t)b0 * a.C * a.nout * EW;
     ybytes = (unsigned)a.nout * (unsigned)a.C * ES;
+  } else if constexpr (WG) {
+    y0 = io_ptr<IO>(a.y) + (size_t)o * a.K;
+    ybytes = (unsigned)a.K * ES;
   } else {
     y0 = io_ptr<IO>(a.y) + ((size_t)b0 * a.C + o) * a.nout * EW;
     ybytes = (unsigned)a.nout * ES;
@@ -565,6 +682,9 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
     } else if constexpr (NLC) {
       const unsigned q = fdiv(t, a.d_ostep), c = o + (unsigned)(r & (M - 1));
       off = (q * a.d_ostep.d == t && q < (unsigned)a.nout && c < (unsigned)a.C) ? (q * (unsigned)a.C + c) * ES : 0x80000000u;
+    } else if constexpr (WG) {
+      const unsigned q = fdiv(t, a.d_ostep);                 // (lag out_step * q -> the element of tap q)
+      off = (q * a.d_ostep.d == t && q < (unsigned)a.keff) ? (unsigned)(a.tap0 + a.tstep * (int)q) * ES : 0x80000000u;
     } else if constexpr (!MAP) {
       off = t < (unsigned)a.nout ? t * ES : 0x80000000u;     // (samples past the kept window: dropped)
     } else {
@@ -591,6 +711,10 @@ struct LongImpl {
   hipError_t (*cols_fwd)(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st);
   hipError_t (*rows)(const LongArgs& a, long long units, hipStream_t st);     // units: filter rows, or pairs * G * nob
   hipError_t (*cols_inv)(const LongArgs& a, bool mapped, bool nlc, long long rows, hipStream_t st);
+  // the weight gradient: its row pass (units: G * Cig * ceil(Cog / wg_ob)) and its inverse pass over a.C rows of dW
+  int wg_ob;
+  hipError_t (*wgrad_rows)(const LongArgs& a, long long units, hipStream_t st);
+  hipError_t (*wgrad_inv)(const LongArgs& a, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

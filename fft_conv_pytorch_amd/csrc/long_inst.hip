@@ -2,7 +2,8 @@
 // picks the build of a column launch (cols_dispatch: float32, 16-bit -- one build for float16 and bfloat16 -- or complex64
 // by the launch's element code, each plain, mapped or channels-last, nine builds of each column kernel; for a phases plan,
 // a.ph_s > 0, the phases builds of the filter rows and of the inverse pass, float32 and 16-bit; for a decimation plan,
-// a.ph_s > 0 with a.ph_cog == 0, the decimation builds of the filter rows and of the signal rows, float32 and 16-bit): built once per
+// a.ph_s > 0 with a.ph_cog == 0, the decimation builds of the filter rows and of the signal rows, float32 and 16-bit; the row pass
+// of the weight gradient and the float32 and 16-bit builds of its inverse pass have entries of their own): built once per
 // geometry with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
@@ -38,6 +39,14 @@ hipError_t launch(const LongArgs& a, int blocks_per_unit, long long units, hipSt
 hipError_t rows(const LongArgs& a, long long units, hipStream_t st) {
   if (a.N2 != kT || a.ob != kOB) return hipErrorInvalidValue;
   return launch<long_rows_kernel<FC_P, FC_S, kNSEQ, kNT, kOB>>(a, a.N1 / kNSEQ, units, st);
+}
+
+// ---- the weight gradient (long1d.hpp): its row pass keeps the x spectrum live across the transforms of the dY rows
+constexpr int kWgOB = kOB;
+
+hipError_t wgrad_rows(const LongArgs& a, long long units, hipStream_t st) {
+  if (a.N2 != kT || a.ob != kWgOB) return hipErrorInvalidValue;
+  return launch<long_wgrad_rows_kernel<FC_P, FC_S, kNSEQ, kNT, kWgOB>>(a, a.N1 / kNSEQ, units, st);
 }
 
 // ---- channels-last (long1d.hpp): NC neighbouring channels x NSEQ / NC neighbouring n2 columns per workgroup.  NC makes
@@ -168,12 +177,22 @@ hipError_t cols_dispatch(const LongArgs& a, bool mapped, bool nlc, long long row
   return hipErrorInvalidValue;
 }
 
+// the inverse pass of the weight gradient: one item, a.C rows of dW, the element type of dW
+hipError_t wgrad_inv(const LongArgs& a, hipStream_t st) {
+  if (a.N1 != kT || a.C <= 0 || a.B != 1 || a.pair0 != 0) return hipErrorInvalidValue;
+  if (a.y_io == 0)
+    return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32, true, false, 0, false, true>>(a, a.N2 / kNSEQ, a.C, st);
+  if (io_is_h16(a.y_io))
+    return launch<long_cols_inv_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16, true, false, 0, false, true>>(a, a.N2 / kNSEQ, a.C, st);
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 #define FC_CAT_(a, b, c, d) a##b##c##d
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
-  static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>};
+  static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>, kWgOB, wgrad_rows, wgrad_inv};
   return &impl;
 }
 

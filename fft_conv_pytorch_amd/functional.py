@@ -642,6 +642,83 @@ def _long_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, gro
                           _native.PAD_MODES[padding_mode], dtype, x_layout)
 
 
+def _long_wgrad_mode() -> bool:
+    """FFTCONV_LONG_WGRAD (read per call): "1" takes the weight-gradient plan wherever eligible; unset or anything else never."""
+    return os.environ.get("FFTCONV_LONG_WGRAD", "0") == "1"
+
+
+def _long_wgrad_key(batch: int, cin: int, cout: int, groups: int, length: int, taps: int, pad_left: int, pad_right: int,
+                    nout: int, flip: bool, pad_mode: int, stride: int, dilation: int) -> tuple:
+    """The words of ``_native.wgrad_desc`` for the layer of a forward long plan."""
+    return (int(batch), int(cin), int(cout), int(groups), int(length), int(taps), int(pad_left), int(pad_right), int(nout),
+            int(bool(flip)), int(pad_mode), int(stride), int(dilation))
+
+
+def _long_wgrad_eligible(key: tuple, dtype) -> bool:
+    """Whether dW of this layer takes the weight-gradient plan (pure: the switch, the dtype, and the library's geometry call
+    on the descriptor, which touches no device): FFTCONV_LONG_WGRAD=1, float32 / float16 / bfloat16, and a geometry the
+    library does not refuse (2**24 points, the rows of W2 inside the workspace budget, 32-bit grids)."""
+    if not _long_wgrad_mode() or dtype not in (torch.float32,) + _LOW_PRECISION:
+        return False
+    try:
+        _native.wgrad_geometry(key)
+    except NotImplementedError:
+        return False
+    return True
+
+
+def _long_wgrad_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, groups=1, causal=False,
+                      padding_mode="constant", dtype=torch.float32, x_layout="ncl") -> str:
+    """Which route the weight gradient of a ``fft_long_conv`` call takes in ``FFTLongConvFunction.backward`` (pure: shapes,
+    numbers, FFTCONV_LONG_WGRAD and FFTCONV_LONG_DECIM, and the library's geometry call):
+
+    ``"plan"``       FFTCONV_LONG_WGRAD=1 on the plain branch of backward (a forward on the plain route, or a causal one
+                     whatever its route), float32 / float16 / bfloat16: ``_long_wgrad_run``, x and dY read where they lie;
+    ``"exchanged"``  everything else: the route of a call with the switch unset (the forward primitive with batch and
+                     channels exchanged on transposed copies; by phases where the forward ran so; ``fft_conv``'s own
+                     gradient for a row that hands off)."""
+    meta = dict(device="meta")
+    signal, kernel = torch.empty(tuple(signal_shape), **meta), torch.empty(tuple(kernel_shape), **meta)
+    pad_left, pad_right, need = _long_geometry(signal, kernel, None, padding, groups, causal, stride, dilation, padding_mode)
+    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
+    length, taps, mode = int(signal_shape[2]), int(kernel_shape[2]), _native.PAD_MODES[padding_mode]
+    route = _long_route_of(length, taps, pad_left, pad_right, need, bool(causal), stride, dilation, mode, dtype, x_layout)
+    if route == "handoff" or (route == "phases" and not causal):
+        return "exchanged"
+    nout = _long_keep(length, causal, stride) or (length + pad_left + pad_right - dilation * (taps - 1) - 1) // stride + 1
+    key = _long_wgrad_key(signal_shape[0], signal_shape[1], kernel_shape[0], groups, length, taps, pad_left, pad_right, nout,
+                          causal, mode, stride, dilation)
+    return "plan" if _long_wgrad_eligible(key, dtype) else "exchanged"
+
+
+def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype: torch.dtype) -> Tensor:
+    """dW (``wshape``, ``out_dtype``) of the layer ``key`` describes (``_long_wgrad_key``) on its weight-gradient plan, no
+    autograd.  ``signal`` (B, Cin, L) and ``grad`` (B, Cout, nout) are float32, float16 or bfloat16, each on its own, and
+    each is read where it lies: contiguous, or as the channels-last view ``_long_layout`` recognises (another layout, a
+    block of 2**31 bytes or more, FFTCONV_LONG_NLC=0: one torch copy of that tensor).  No transposed operand and no
+    flipped copy of the result exists; the float32 result is rounded once as it is stored."""
+    native = _long_nlc_enabled()
+    tensors, layouts = [], []
+    for t in (signal.detach(), grad.detach()):
+        nlc = (native and _long_layout(t) == "nlc" and t.shape[1] * t.shape[2] * t.element_size() < _native.LONG_NLC_MAX_BYTES)
+        tensors.append(t if nlc else t.contiguous())
+        layouts.append(_native.LONG_NLC if nlc else _native.LONG_NCL)
+    x, dy = tensors
+    index = _device_index(x.device)
+    pkey = ("long_wgrad",) + tuple(key)
+    plan = _native.lookup_plan(index, pkey)
+    if plan is None:
+        with torch.cuda.device(index):      # the twiddle tables are allocated on the current device
+            plan = _native.get_plan(index, pkey)
+    with torch.cuda.device(x.device):
+        dw = torch.empty(tuple(wshape), dtype=out_dtype, device=x.device)
+        ws = new_workspace(plan, x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        plan.run(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[x.dtype],
+                 _DTYPE_CODES[dy.dtype], _DTYPE_CODES[out_dtype], layouts[0], layouts[1])
+    return dw
+
+
 def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
                   causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant",
                   channels_last: bool = False) -> Tensor:
@@ -673,7 +750,9 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     ``channels_last=True`` returns the (B, Cout, nout) result with strides (nout*Cout, 1, Cout), so that
     ``y.transpose(1, 2)`` is a contiguous (B, nout, Cout) tensor; input and output layout are independent.  The values
     have the bits of the call on contiguous tensors.  In backward a dY that lies that way is read where it lies and dX
-    gets the signal's layout; the weight gradient's transposed operands are torch copies as ever.  Other non-contiguous
+    gets the signal's layout; the weight gradient's transposed operands are torch copies as ever, unless FFTCONV_LONG_WGRAD=1
+    (read per call; opt-in, the bits of dW change) selects the weight-gradient plan, which reads x and dY where they lie in
+    either layout (``_long_wgrad_route`` names the route; ``FFTLongConvFunction``).  Other non-contiguous
     tensors are copied.  ``FFTCONV_LONG_NLC=0`` (read per call) takes torch copies everywhere, as do rows that hand off
     to ``fft_conv``, the ``FFTCONV_HALF_IO=0`` path and tensors whose (L, C) block of one batch item reaches 2**31 bytes.
 

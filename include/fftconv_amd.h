@@ -391,6 +391,52 @@ typedef struct fc_long_decim_desc {
 int fc_long_decim_geometry(const fc_long_decim_desc* desc, int64_t info[8]);
 int fc_long_decim_plan_create(const fc_long_decim_desc* desc, fc_long_plan** out_plan);
 
+/* Weight gradient of a long plan (ABI 7 extension: new entry points only; every struct, enum value and call above keeps
+ * its layout, value and meaning).  For the layer whose forward is the long primitive with out_step = stride and tap_dil =
+ * dilation on x (B, Cin, L) and a (Cout, Cin/groups, K) weight, the call computes from x and dY (B, Cout, out_len)
+ *   dW[(g,o)][i][k] = sum_b sum_j dY[b][(g,o)][j] * xrow[b][(g,i)][stride*j + dilation*k'],   k' = k (flip 0) or K-1-k (flip 1),
+ * xrow = x read through pad_left / pad_right in pad_mode exactly as the forward plan reads it.  Both operands are read
+ * where they lie: x and dY are signal-shaped, so the forward column pass transforms both, two batch items to a complex
+ * row (z = x[2p] + i*x[2p+1], w = dY[2p] + i*dY[2p+1], dY spread over the grid of the stride), and
+ *   IFFT( FFT(z) * conj(FFT(w)) )[m] = sum_t conj(w[t]) * z[t + m]
+ * has the pair's contribution to the lag m in its real part.  The row pass sums the product over the batch pairs in
+ * registers and transforms back once per (o, i); the last pass keeps the real part of every dilation-th lag and stores it
+ * at the place of its tap, in the weight's own order for either flip.  No transposed copy and no spectrum buffer exists.
+ *   Geometry: N1 x N2 is that of the forward plan of the same layer (out_keep = out_len), FFTCONV_LONG_N and the 2^24-point
+ *   refusal included.  With pad_mode constant the lags of taps that can meet no data for any output are not transformed;
+ *   they are written as zero.  Every element of dW is written exactly once and no other byte.
+ *   info words: N1, N2, K, lags transformed, workspace bytes, slabs, output channels per workgroup of the row pass, batch
+ *   pairs per slab.  The workspace holds W1 of x and of dY for the pairs of a slab and W2 for all of dW:
+ *   (info[7] * (Cin + Cout) + Cout * Cin/groups) * N * 8 bytes, under FFTCONV_LONG_WS_MB.  The sum over the pairs crosses
+ *   slabs: every slab after the first ADDS its transformed sum into W2, so the bits of dW depend on the slab count (not on
+ *   anything else).  W2 alone above the budget, or a grid above 2^31 workgroups: FC_ERR_UNSUPPORTED with text.
+ *   x_dtype, dy_dtype and dw_dtype are FC_F32 / FC_F16 / FC_BF16, x_layout and dy_layout FC_LONG_NCL / FC_LONG_NLC, each
+ *   on its own; dW is (Cout, Cin/groups, K) contiguous, float32 arithmetic rounded once at the store.  A channels-last block
+ *   of 2^31 bytes or more answers FC_ERR_UNSUPPORTED as in fc_long_forward_lay; fc_long_wgrad_check_io answers for a call
+ *   from the descriptor alone (no device).  Three launches per slab, one more and up to two strided fills on hip_stream;
+ *   after plan creation nothing is allocated or synchronised. */
+typedef struct fc_long_wgrad_desc {
+  int64_t batch, in_channels, out_channels, groups;
+  int64_t length;              /* L: samples per row of x */
+  int64_t kernel;              /* K: dW is (Cout, Cin/groups, K) */
+  int64_t pad_left, pad_right; /* of the forward's row */
+  int64_t out_len;             /* nout: samples per row of dY */
+  int32_t flip;                /* the forward's tap order */
+  int32_t pad_mode;            /* the forward's PadMode code */
+  int32_t stride, dilation;    /* the forward's out_step and tap_dil */
+} fc_long_wgrad_desc;
+
+typedef struct fc_long_wgrad_plan fc_long_wgrad_plan;
+
+int fc_long_wgrad_geometry(const fc_long_wgrad_desc* desc, int64_t info[8]);
+int fc_long_wgrad_check_io(const fc_long_wgrad_desc* desc, int x_dtype, int x_layout, int dy_dtype, int dy_layout,
+                            int dw_dtype);
+int fc_long_wgrad_plan_create(const fc_long_wgrad_desc* desc, fc_long_wgrad_plan** out_plan);
+void fc_long_wgrad_plan_destroy(fc_long_wgrad_plan* plan);
+int fc_long_wgrad_plan_info(const fc_long_wgrad_plan* plan, int64_t info[8]);
+int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
+                  int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,8 +60,14 @@ def _pad_adjoint(dxp: Tensor, in_spatial, padding, mode: str) -> Tensor:
             core.narrow(ax, 1, p).add_(left.flip(ax))
             core.narrow(ax, n - 1 - p, p).add_(right.flip(ax))
         elif mode == "replicate":
-            core.narrow(ax, 0, 1).add_(left.sum(dim=ax, keepdim=True))
-            core.narrow(ax, n - 1, 1).add_(right.sum(dim=ax, keepdim=True))
+            # (accumulated in float64 and rounded once: the edge sample takes up to n border samples.  A tensor that does
+            # not lie contiguous is summed on compact copies of its borders, in the order of the contiguous one, whose
+            # bits a channels-last gradient must have)
+            wide = torch.complex128 if t.is_complex() else torch.float64
+            if not t.is_contiguous():
+                left, right = left.contiguous(), right.contiguous()
+            core.narrow(ax, 0, 1).add_(left.sum(dim=ax, keepdim=True, dtype=wide).to(core.dtype))
+            core.narrow(ax, n - 1, 1).add_(right.sum(dim=ax, keepdim=True, dtype=wide).to(core.dtype))
         elif mode == "circular":       # padded j < p reads source n - p + j; padded n + p + j reads source j
             core.narrow(ax, n - p, p).add_(left)
             core.narrow(ax, 0, p).add_(right)
@@ -434,8 +440,9 @@ class FFTLongConvFunction(torch.autograd.Function):
     Layouts (``F_._long_layout``): the forward reads a signal that lies as a contiguous (B, L, C) tensor where it lies and
     writes y that way with ``channels_last``.  dX is the same primitive, so a dY that lies that way is read where it lies,
     and dX is written in the signal's layout (after a padding-mode fold, which torch runs on whatever layout dX has, one
-    torch copy restores it).  dW's operands are transposed copies anyway and torch builds them from whichever layout
-    the tensors have; db sums a contiguous dY, so a strided dY is copied for it."""
+    torch copy restores it; so does one after the dX by phases, whose plan writes contiguous rows: a signal that lies
+    that way runs by phases under FFTCONV_LONG_NLC=0 only).  dW's operands are transposed copies anyway and torch builds
+    them from whichever layout the tensors have; db sums a contiguous dY, so a strided dY is copied for it."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
@@ -473,6 +480,8 @@ class FFTLongConvFunction(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = F_._long_transpose_run(grad, kernel.detach().contiguous(), None, s, pad_left,
                                             (L + 2 * pad_left - K) % s, 1, g, "phases")
+                if x_nlc:       # (FFTCONV_LONG_NLC=0 only: otherwise such a signal does not run by phases)
+                    dx = F_._as_channels_last(dx)
             if ctx.needs_input_grad[1]:
                 xt = _phase_rows(signal.detach(), pad_left, s, nout + kp - 1, g)
                 dyt = grad.permute(1, 0, 2).contiguous()

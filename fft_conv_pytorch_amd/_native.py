@@ -36,7 +36,7 @@ EXPORTS = (
 )
 
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
-ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd", "f64_fft_long")
+ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd", "f64_fft_long", "c64_nd")
 ROUTE_WORDS = {
     "f32_1d": ("T", "ntiles", "pers_nb", "ph", "ph2", "slot_tiles", "nseg", "diag", "bd_gs", "wide", "dense",
                "chunk_launches", "accumulate", "n_ochunks", "pers_items"),
@@ -47,6 +47,7 @@ ROUTE_WORDS = {
     "f64_fft_nd": ("t0", "t1", "t2", "nt0", "nt1", "nt2", "nb", "cob"),
     "f64_fft_long": ("N1", "N2", "ntiles", "cob"),
 }
+ROUTE_WORDS["c64_nd"] = ROUTE_WORDS["f32_nd"]      # a complex64 2-D / 3-D plan: the same words (planes is always 0)
 
 
 class FcDesc(ctypes.Structure):
@@ -111,7 +112,7 @@ class FcLongWgradDesc(ctypes.Structure):
 
 
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
-FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans only)
+FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans; 2-D / 3-D fc_desc)
 # enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
 LONG_REAL, LONG_COMPLEX, LONG_CONJ_SIGNAL, LONG_CONJ_TAPS = 0, 1, 2, 4
 # enum fc_long_layout: how x and y of fc_long_forward_lay lie, (B, C, L) contiguous or (B, L, C) contiguous
@@ -361,9 +362,10 @@ class Plan:
         self.device_index = int(device_index)
         import torch
         # dtype: of the signal and the output; weight_dtype: of the weight and bias the library reads (a float16 /
-        # bfloat16 plan reads and writes 16-bit x / y and takes a float32 weight and bias)
-        self.dtype = {1: torch.float64, 2: torch.float16, 3: torch.bfloat16}.get(dtype_code, torch.float32)
-        self.weight_dtype = torch.float64 if dtype_code == 1 else torch.float32
+        # bfloat16 plan reads and writes 16-bit x / y and takes a float32 weight and bias; a complex64 plan reads and
+        # writes complex64 throughout, its spectrum and workspace stay float32 pairs)
+        self.dtype = {1: torch.float64, 2: torch.float16, 3: torch.bfloat16, FC_C64: torch.complex64}.get(dtype_code, torch.float32)
+        self.weight_dtype = {1: torch.float64, FC_C64: torch.complex64}.get(dtype_code, torch.float32)
         out = (ctypes.c_int64 * 3)()
         lib.fc_output_shape(handle, ctypes.byref(out))
         self.out_spatial = tuple(int(out[i]) for i in range(ndim))

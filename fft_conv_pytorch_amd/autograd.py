@@ -22,6 +22,11 @@ path (widen, run the float32 function, round): the kernels read 16-bit dY and x 
 same route computes; dX is written in 16 bits by its transposed plan, dW and db are summed in float32 and rounded once.
 Where no 16-bit route exists (a refused dX plan, non-constant padding, the forward-plan dW, a library that predates 16-bit
 weight gradients) dY and x are widened for that gradient only.
+
+complex64 calls (2-D / 3-D) return gradients in PyTorch's convention for complex tensors, each one complex plan of the same
+library: dX runs dY against conj(W) (a conjugated copy of the small weight), dW is the role-swapped forward plan of
+``_grad_weight_plans`` on conj(x) and dY (the conjugate is written by the permuted copy that function builds anyway; no
+conjugation flag exists in the C ABI), db is dY summed.  ``fc_wgrad_nd`` takes no complex tensors.
 """
 from __future__ import annotations
 
@@ -114,10 +119,22 @@ def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, 
     return _pad_adjoint(dx, in_spatial, padding, padding_mode)
 
 
-def _grad_weight_plans(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Tensor:
+def _permuted_copy(view: Tensor, shape, conj: bool) -> Tensor:
+    """A contiguous copy of a permuted view, reshaped; ``conj``: the copy holds the conjugate (one pass either way)."""
+    if not conj:
+        return view.reshape(shape).contiguous()
+    out = torch.empty(tuple(view.shape), dtype=view.dtype, device=view.device)
+    torch.conj_physical(view, out=out)
+    return out.view(shape)
+
+
+def _grad_weight_plans(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode,
+                       conj: str = "") -> Tensor:
     """dW through forward plans with the roles of batch and channels swapped, ALL channel groups in one call
     (they ride the group axis of the swapped convolution).  x: (B, Cin, *S), grad: (B, Cout, *Lout) -> (Cout, Cin/g, *k).
-    16-bit x and dY are widened here (the float32 plans; dW comes back float32)."""
+    16-bit x and dY are widened here (the float32 plans; dW comes back float32).  complex64 operands (2-D / 3-D) run a
+    complex plan; ``conj`` = "x" or "grad" has the permuted copy of that operand hold its conjugate (the gradient of a
+    bilinear product in PyTorch's convention conjugates the operand that is not dY)."""
     if x.dtype in F_._LOW_PRECISION:
         x, grad = x.float(), grad.float()
     n = x.ndim - 2
@@ -158,8 +175,9 @@ def _grad_weight_plans(x: Tensor, grad: Tensor, wshape, stride, padding, dilatio
         part = part.reshape(cig, g, nchunk, cog, -1).sum(dim=2)      # (Cig, g, Cog, >= k)
         return part[..., : ksize[0]].permute(1, 2, 0, 3).reshape(g * cog, cig, ksize[0]).contiguous()
     # signal' (Cig, [g, b], *S), kernel' ([g, o], b, *Lout), groups' = g
-    xt = x.reshape((b, g, cig) + sp).permute((2, 1, 0) + tuple(range(3, 3 + n))).reshape((cig, g * b) + sp).contiguous()
-    gt = grad.reshape((b, g, cog) + lo).permute((1, 2, 0) + tuple(range(3, 3 + n))).reshape((g * cog, b) + lo).contiguous()
+    xt = _permuted_copy(x.reshape((b, g, cig) + sp).permute((2, 1, 0) + tuple(range(3, 3 + n))), (cig, g * b) + sp, conj == "x")
+    gt = _permuted_copy(grad.reshape((b, g, cog) + lo).permute((1, 2, 0) + tuple(range(3, 3 + n))), (g * cog, b) + lo,
+                        conj == "grad")
     key = ("dwp", tuple(xt.shape), tuple(gt.shape), stride, padding, dilation, g, padding_mode, xt.device, xt.dtype)
     plan = _BWD_PLANS.get(key)
     if plan is None:
@@ -255,10 +273,12 @@ def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dil
 
 
 def _grad_weight_db(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode,
-                    want_db: bool = False):
+                    want_db: bool = False, conj: str = ""):
     """(dW, db or None) in float32 by the first route that covers the shape: fc_wgrad1d (db riding it where offered),
     fc_wgrad_nd, forward plans.  16-bit x and dY that no 16-bit launch takes (a library without 16-bit weight gradients)
     are widened for this gradient, and the float32 routes decide -- the bits of the cast path either way."""
+    if x.is_complex():      # (no complex weight-gradient launch: the role-swapped forward plan)
+        return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode, conj), None
     native = _grad_weight_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode, want_db)
     if native is not None:
         return native
@@ -267,11 +287,11 @@ def _grad_weight_db(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, 
         return nd, None
     if x.dtype in F_._LOW_PRECISION:
         return _grad_weight_db(x.float(), grad.float(), wshape, stride, padding, dilation, groups, padding_mode, want_db)
-    return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode), None
+    return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode, conj), None
 
 
-def _grad_weight(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Tensor:
-    return _grad_weight_db(x, grad, wshape, stride, padding, dilation, groups, padding_mode)[0]
+def _grad_weight(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode, conj: str = "") -> Tensor:
+    return _grad_weight_db(x, grad, wshape, stride, padding, dilation, groups, padding_mode, conj=conj)[0]
 
 
 def _grad_bias(grad: Tensor) -> Tensor:
@@ -298,18 +318,19 @@ class FFTConvFunction(torch.autograd.Function):
     def backward(ctx, grad: Tensor):
         signal, kernel = ctx.saved_tensors
         stride, padding, dilation, groups, padding_mode, has_bias = ctx.conf
-        grad = grad.contiguous()
+        grad = F_._resolved(grad).contiguous()
+        cx = signal.is_complex()      # PyTorch's convention: dW from conj(x), dX against conj(W)
         d_signal = d_kernel = d_bias = None
         want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             # (db rides the weight-gradient launch where the kernel offers it; dW goes first: widened 16-bit operands of a
             # weight-gradient route are freed before dX is allocated)
             d_kernel, d_bias = _grad_weight_db(signal.detach(), grad, tuple(kernel.shape), stride, padding, dilation,
-                                               groups, padding_mode, want_db)
+                                               groups, padding_mode, want_db, conj="x" if cx else "")
             d_kernel = d_kernel.to(kernel.dtype)     # (16-bit: the float32 sum rounded once)
         if ctx.needs_input_grad[0]:
-            d_signal = _grad_input(grad, kernel.detach(), tuple(signal.shape[2:]), stride, padding, dilation, groups,
-                                   padding_mode)
+            d_signal = _grad_input(grad, kernel.detach().conj() if cx else kernel.detach(), tuple(signal.shape[2:]), stride,
+                                   padding, dilation, groups, padding_mode)
         if want_db and d_bias is None:
             d_bias = _grad_bias(grad)
         if d_bias is not None:
@@ -345,7 +366,8 @@ class FFTConvTransposeFunction(torch.autograd.Function):
     def backward(ctx, grad: Tensor):
         signal, kernel = ctx.saved_tensors
         stride, padding, dilation, groups, has_bias = ctx.conf
-        grad = grad.contiguous()
+        grad = F_._resolved(grad).contiguous()
+        cx = signal.is_complex()      # (as in FFTConvFunction: x is the "output gradient" operand of dW here)
         n = grad.ndim - 2
         in_spatial = tuple(signal.shape[2:])
         # extent of conv(dY, W) per axis: >= the input extent; larger only when output_padding >= stride
@@ -353,8 +375,8 @@ class FFTConvTransposeFunction(torch.autograd.Function):
                         for i in range(n))
         d_signal = d_kernel = d_bias = None
         if ctx.needs_input_grad[0]:
-            dx = F_.fft_conv(grad, kernel.detach(), None, stride=stride, padding=padding, dilation=dilation,
-                             groups=groups)
+            dx = F_.fft_conv(grad, kernel.detach().conj() if cx else kernel.detach(), None, stride=stride, padding=padding,
+                             dilation=dilation, groups=groups)
             if conv_sp != in_spatial:
                 dx = dx[(slice(None), slice(None)) + tuple(slice(0, s) for s in in_spatial)].contiguous()
             d_signal = dx
@@ -365,7 +387,8 @@ class FFTConvTransposeFunction(torch.autograd.Function):
                 for i in reversed(range(n)):
                     flat += [0, conv_sp[i] - in_spatial[i]]
                 xg = F.pad(xg, flat)
-            d_kernel = _grad_weight(grad, xg, tuple(kernel.shape), stride, padding, dilation, groups, "constant")
+            d_kernel = _grad_weight(grad, xg, tuple(kernel.shape), stride, padding, dilation, groups, "constant",
+                                    conj="grad" if cx else "")
             d_kernel = d_kernel.to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             d_bias = _grad_bias(grad).to(kernel.dtype)

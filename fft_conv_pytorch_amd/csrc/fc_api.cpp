@@ -156,9 +156,13 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   *out_plan = nullptr;
   const fc_desc& d = *desc;
   if (d.ndim < 1 || d.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", d.ndim);
-  if (d.dtype != FC_F32 && d.dtype != FC_F64 && d.dtype != FC_F16 && d.dtype != FC_BF16)
-    return fail(FC_ERR_UNSUPPORTED, "dtype must be FC_F32, FC_F64, FC_F16 or FC_BF16");
-  if (sw && d.dtype == FC_F64) return fail(FC_ERR_UNSUPPORTED, "weight-gradient plans take float32, float16 or bfloat16 x and dY");
+  if (d.dtype != FC_F32 && d.dtype != FC_F64 && d.dtype != FC_F16 && d.dtype != FC_BF16 && d.dtype != FC_C64)
+    return fail(FC_ERR_UNSUPPORTED, "dtype must be FC_F32, FC_F64, FC_F16, FC_BF16 or (2-D / 3-D) FC_C64");
+  if (sw && (d.dtype == FC_F64 || d.dtype == FC_C64))
+    return fail(FC_ERR_UNSUPPORTED, "weight-gradient plans take float32, float16 or bfloat16 x and dY");
+  if (d.dtype == FC_C64 && d.ndim == 1)
+    return fail(FC_ERR_UNSUPPORTED, "a 1-D descriptor takes no FC_C64: complex rows run the long-filter calls "
+                "(fc_long_plan_create_kind with FC_LONG_COMPLEX, fc_long_transform_kernel_io, fc_long_forward_io)");
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1)
     return fail(FC_ERR_INVALID, "batch, channels and groups must be positive");
   if (d.in_channels % d.groups || d.out_channels % d.groups)
@@ -173,7 +177,7 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
   // 16-bit x / y: planned exactly as the float32 plan of the descriptor (same route, spectrum layout and sizes, so a
   // float32 plan's kernel spectrum serves it); only the launches' loads of x and stores of y take the element type
   p->io = d.dtype == FC_F64 ? FC_F32 : d.dtype;
-  if (p->io != FC_F32) p->d.dtype = FC_F32;
+  if (p->io != FC_F32 && p->io != FC_C64) p->d.dtype = FC_F32;   // (a complex64 plan is a kind of its own, below)
   // a weight-gradient plan reads 16-bit x and dY but writes a float32 dW (which segments of taps may add into)
   p->io_y = sw ? FC_F32 : p->io;
   if (sw) { p->fnd.swap = 1; p->fnd.sw_B = sw->B; p->fnd.sw_Cig = sw->Cig; p->fnd.sw_Cog = sw->Cog; p->fnd.sw_g = sw->g; }
@@ -257,6 +261,7 @@ static int plan_create_impl(const fc_desc* desc, const WgradSwap* sw, fc_plan** 
 
   int rc;
   if (d.dtype == FC_F64) rc = plan_f64(p.get());                 // picks one of the four float64 kinds
+  else if (d.dtype == FC_C64) { p->kind = PlanKind::C64_ND; rc = plan_nd(p.get()); }   // (2-D / 3-D: checked above)
   else if (d.ndim == 1) { p->kind = PlanKind::F32_1D; rc = plan_1d(p.get()); }
   else { p->kind = PlanKind::F32_ND; rc = plan_nd(p.get()); }
   if (rc != FC_OK) return rc;
@@ -295,7 +300,8 @@ int fc_plan_tile(const fc_plan* plan) {
   if (!plan) return 0;
   switch (plan->kind) {
     case PlanKind::F32_1D:
-    case PlanKind::F32_ND: return plan->tile->T;
+    case PlanKind::F32_ND:
+    case PlanKind::C64_ND: return plan->tile->T;
     case PlanKind::F64_DIRECT: return 0;
     case PlanKind::F64_FFT_1D:
     case PlanKind::F64_FFT_ND: return plan->f64.T;
@@ -315,6 +321,7 @@ int fc_plan_layout(const fc_plan* plan, int32_t layout[8]) {
       layout[4] = p.f1d.diag; layout[5] = p.f1d.bd_gs; layout[6] = p.f1d.dense ? 2 : p.f1d.wide; layout[7] = p.f1d.pers_nb;
       break;
     case PlanKind::F32_ND:   // the spectrum is laid out over the row / middle-axis transform lengths and the segments too
+    case PlanKind::C64_ND:   // (Tx bin columns where the real plan has Tx/2: the spectrum bytes differ, the words do not)
       layout[0] = p.tile->T;
       layout[1] = p.fnd.tx->T; layout[2] = p.fnd.tm ? p.fnd.tm->T : 0; layout[3] = p.fnd.cob;   // (x tiles share one kernel spectrum)
       for (int a = 0; a < p.nd; ++a) layout[4 + a] = p.fnd.nseg[a] > 1 ? p.fnd.seg_taps[a] : 0;   // taps per segment (0: whole axis)
@@ -341,6 +348,7 @@ long long fc_debug_grid(const fc_plan* plan) {
       if (p.f1d.pers_nb) return (long long)p.f1d.pers_items * 16;   // one record per wave (up to 16) of every work item
       return (long long)p.d.batch * p.ntiles * p.n_ochunks * p.G;
     case PlanKind::F32_ND:
+    case PlanKind::C64_ND:
       if (p.fnd.planes) {   // upper bound of colz's grid (one batch item per workgroup)
         const long long ncol = p.fnd.planes == 1 ? (long long)fc::kPlCols * p.fnd.nxt * p.fnd.nyt : p.fnd.Fxt;
         return (long long)p.d.batch * p.ntiles * (p.fnd.Cog_pad / p.fnd.cob) * p.d.groups * ((ncol / 16 + 7) / 8) * 8;
@@ -366,7 +374,8 @@ int fc_debug_route(const fc_plan* plan, int32_t route[16]) {
       for (int i = 0; i < 15; ++i) route[1 + i] = w[i];
       break;
     }
-    case PlanKind::F32_ND: {
+    case PlanKind::F32_ND:
+    case PlanKind::C64_ND: {   // (word 0 tells the complex plan apart; the words behind it mean what they mean for F32_ND)
       const int32_t w[] = {p.tile->T, p.ntiles, p.fnd.tx->T, p.fnd.nxt, p.fnd.tm ? p.fnd.tm->T : 0, p.fnd.nyt,
                            p.fnd.planes, p.fnd.cob, p.accumulate};
       for (int i = 0; i < 9; ++i) route[1 + i] = w[i];
@@ -397,7 +406,8 @@ int fc_transform_kernel(const fc_plan* plan, const float* weight, void* w_hat, v
   if (p.workspace_bytes && !workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
   switch (p.kind) {
     case PlanKind::F32_1D: return transform_kernel_1d(p, weight, w_hat, workspace, st);
-    case PlanKind::F32_ND: return transform_kernel_nd(p, weight, w_hat, workspace, st);
+    case PlanKind::F32_ND:
+    case PlanKind::C64_ND: return transform_kernel_nd(p, weight, w_hat, workspace, st);
     case PlanKind::F64_DIRECT: return transform_kernel_f64_direct(p, weight, w_hat, workspace, st);
     case PlanKind::F64_FFT_1D: return transform_kernel_f64_1d(p, weight, w_hat, workspace, st);
     case PlanKind::F64_FFT_ND: return transform_kernel_f64_nd(p, weight, w_hat, workspace, st);
@@ -419,12 +429,13 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
   const fc_plan& p = *plan;
   if (p.d.has_bias && !bias) return fail(FC_ERR_INVALID, "plan was created with has_bias=1 but bias is NULL");
   if (p.workspace_bytes && !workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
-  if (stamps && p.io != FC_F32) return fail(FC_ERR_UNSUPPORTED, "a float16 / bfloat16 plan has no stamped forward");
+  if (stamps && p.io != FC_F32) return fail(FC_ERR_UNSUPPORTED, "a float16 / bfloat16 / complex64 plan has no stamped forward");
   if (stamps && p.kind == PlanKind::F32_ND && p.fnd.nseg_total > 1)
     return fail(FC_ERR_UNSUPPORTED, "a plan that runs its kernel in %d segments of taps has no stamped forward", p.fnd.nseg_total);
   switch (p.kind) {
     case PlanKind::F32_1D: return forward_1d(p, x, w_hat, bias, y, workspace, st, stamps);
-    case PlanKind::F32_ND: return forward_nd(p, x, w_hat, bias, y, workspace, st, stamps);
+    case PlanKind::F32_ND:
+    case PlanKind::C64_ND: return forward_nd(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F64_DIRECT: return forward_f64_direct(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F64_FFT_1D: return forward_f64_1d(p, x, w_hat, bias, y, workspace, st, stamps);
     case PlanKind::F64_FFT_ND: return forward_f64_nd(p, x, w_hat, bias, y, workspace, st, stamps);
@@ -443,6 +454,9 @@ int fc_wgrad_nd_plan_create(const fc_desc* conv, fc_plan** out_plan) {
   *out_plan = nullptr;
   const fc_desc& c = *conv;
   if (c.ndim < 2 || c.ndim > 3) return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd covers 2-D and 3-D convolutions (1-D: fc_wgrad1d)");
+  if (c.dtype == FC_C64)
+    return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd takes no complex64 tensors: run the exchanged forward plan (FC_C64 fc_plan_create) "
+                "on conj(x) and dY");
   if ((c.dtype != FC_F32 && c.dtype != FC_F16 && c.dtype != FC_BF16) || c.transposed)
     return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_nd: float32, float16 or bfloat16 x and dY, not transposed");
   if (c.batch < 1 || c.in_channels < 1 || c.out_channels < 1 || c.groups < 1 || c.in_channels % c.groups || c.out_channels % c.groups)

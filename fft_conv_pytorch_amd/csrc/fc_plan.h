@@ -1,7 +1,8 @@
 // fc_plan.h -- the plan behind the C ABI (include/fftconv_amd.h) and the host helpers its paths share.
 //
-// A plan runs one of six paths (fc::PlanKind), chosen once when it is created (fc_api.cpp).  Each path plans and
-// launches in a file of its own: host_1d.cpp (float32 1-D), host_nd.cpp (float32 2-D / 3-D), host_f64.cpp (float64).
+// A plan runs one of seven paths (fc::PlanKind), chosen once when it is created (fc_api.cpp).  Each path plans and
+// launches in a file of its own: host_1d.cpp (float32 1-D), host_nd.cpp (float32 and complex64 2-D / 3-D), host_f64.cpp
+// (float64).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +60,8 @@ enum class PlanKind {
   F64_FFT_1D,   // host_f64.cpp: fft_f64.hip
   F64_FFT_ND,   // host_f64.cpp: nd_f64.hip
   F64_FFT_LONG, // host_f64.cpp: long_f64.hip (1-D, dilated extent past 1025: one transform of N1 x N2 points per row)
+  C64_ND,       // host_nd.cpp: complex64 2-D / 3-D on the separable passes (one row per sequence, Fx = Tx bin columns; the
+                // state of F32_ND in `fnd`, planes = 0, no segments of taps)
 };
 
 }  // namespace fc
@@ -68,7 +71,7 @@ struct fc_plan {
   fc::PlanKind kind;
   int nd;
   int io;                     // fc_dtype of x (and of the kernel' dY of a weight-gradient plan): FC_F32, FC_F16 or FC_BF16 on
-                              // the float32 kinds (Io<> in fft_engine.hpp)
+                              // the float32 kinds (Io<> in fft_engine.hpp); FC_C64 on C64_ND (x, weight, bias and y)
   int io_y;                   // fc_dtype of y: io, but FC_F32 for a weight-gradient plan (dW is float32 whatever x and dY are)
   // ---- axis geometry (axis 0 = fused (outermost), axis nd-1 = rows (x), middle axis only in 3-D)
   int64_t out_sp[3];
@@ -112,7 +115,7 @@ struct fc_plan {
     const fc::TileImpl* tx;     // rows (last axis)
     const fc::TileImpl* tm;     // middle axis (3-D)
     fc::Twiddles twx, twm;
-    int Fx;                     // Tx/2
+    int Fx;                     // Tx/2 (C64_ND: Tx)
     int nxt, Vx, Fxt;           // overlap-save tiles along the rows axis (nxt = 1: one full-length transform), valid
                                 // stride-1 samples per tile, bin columns per plane = nxt * Fx
     int nyt, Vy;                // the same for the middle axis of a 3-D problem (one c2c launch per tile)

@@ -1,7 +1,9 @@
 // host_nd.cpp -- float32 2-D / 3-D plans (PlanKind::F32_ND): transforms of the rows and middle axes (full length or
 // overlap-save tiles), the fused outermost-axis tile, the plane-major pipeline and the 2-D column pass (`planes`),
 // workspace and spectrum sizes, kernels longer than a tile in segments of taps; the kernel transform and the forward of
-// such a plan, the N-d weight gradient's image maps included (`swap`, fc_wgrad_nd).
+// such a plan, the N-d weight gradient's image maps included (`swap`, fc_wgrad_nd).  A complex64 plan (PlanKind::C64_ND)
+// is planned and launched here too: the same separable passes with the complex builds of the two row passes
+// (nd_passes.hpp), Tx bin columns per x tile, 8-byte samples; no plane-major / row-major pipeline, no segments of taps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -172,14 +174,19 @@ static int plan_nd_segments(fc_plan* p) {
 int plan_nd(fc_plan* p) {
   const fc_desc& d = p->d;
   const int nd = p->nd;
+  const bool cplx = p->kind == PlanKind::C64_ND;
   int rc = plan_nd_segments(p);
   if (rc != FC_OK) return rc;
   const bool segmented = p->fnd.nseg_total > 1;
+  if (cplx && segmented)
+    return fail(FC_ERR_UNSUPPORTED, "a complex64 plan does not run its kernel in segments of taps (a dilated kernel extent past "
+                "4096 on an axis, or FFTCONV_NDSEG): the accumulating store of the last pass is float32-only");
   // rows axis: one full-length transform when the padded row fits the largest FFT, overlap-save tiles otherwise
   // (the reference has no size limit: functional.py:66-70); middle axis (3-D): the same
   rc = plan_axis_tiles(p, nd - 1, "FFTCONV_XTILE", INT64_MAX, "the last axis", &p->fnd.tx, &p->fnd.Vx, &p->fnd.nxt);
   if (rc != FC_OK) return rc;
-  p->fnd.Fx = p->fnd.tx->T / 2;        // odd-frequency bins along the rows axis (nd_passes.hpp, rows_r2c)
+  // odd-frequency bins along the rows axis (nd_passes.hpp, rows_r2c); a complex row keeps all Tx bins (rows_c2c_fwd)
+  p->fnd.Fx = cplx ? p->fnd.tx->T : p->fnd.tx->T / 2;
   p->fnd.Fxt = p->fnd.nxt * p->fnd.Fx;
   {
     // the row passes address one (bin column, row) block per workgroup with 32-bit byte offsets
@@ -187,8 +194,8 @@ int plan_nd(fc_plan* p) {
     if ((int64_t)p->fnd.Fx * rows * 8 >= ((int64_t)1 << 31))
       return fail(FC_ERR_UNSUPPORTED, "%lld rows of %d-point transforms along the last axis exceed the 2 GiB a block of bin "
                   "columns may span (split the second-to-last axis)", (long long)rows, p->fnd.tx->T);
-    // ... and the rows_c2r output stores a workgroup's (at most 32) output rows the same way
-    if (p->out_sp[nd - 1] * 4 * 32 >= ((int64_t)1 << 31))
+    // ... and the rows_c2r output stores a workgroup's (at most 32) output rows the same way (8-byte samples when complex)
+    if (p->out_sp[nd - 1] * (cplx ? 8 : 4) * 32 >= ((int64_t)1 << 31))
       return fail(FC_ERR_UNSUPPORTED, "output rows of %lld samples exceed the 2 GiB a workgroup's block of rows may span "
                   "(2-D / 3-D plans; 1-D rows have no such limit)", (long long)p->out_sp[nd - 1]);
   }
@@ -204,7 +211,7 @@ int plan_nd(fc_plan* p) {
   // 3-D planes larger than 64 x 64 after padding: cut into overlap-save tiles of 64 x 64 so that the plane-major pipeline
   // (below) still applies -- each tile is one workgroup of planes_fwd / planes_inv and one block of 2048 columns of colz.
   // Measured against the separable passes with the planner's own x / y tiles (profiles/r03_experiments.md block 12).
-  if (nd == 3 && !getenv("FFTCONV_XTILE") && !getenv("FFTCONV_YTILE") && !p->fnd.swap && !d.tile_hint && !segmented) {
+  if (nd == 3 && !getenv("FFTCONV_XTILE") && !getenv("FFTCONV_YTILE") && !p->fnd.swap && !d.tile_hint && !segmented && !cplx) {
     const char* pl = getenv("FFTCONV_PLANES");
     const fc::TileImpl* t64 = find_tile(64);
     const bool wide = p->fnd.tx->T > 64 || p->fnd.tm->T > 64 || p->fnd.nxt > 1 || p->fnd.nyt > 1;
@@ -255,7 +262,7 @@ int plan_nd(fc_plan* p) {
                   (int64_t)4 * std::max(d.in_channels, d.out_channels) * std::max<int64_t>(p->Sp[0], p->out_sp[0]) * p->fnd.Fxt * 8 < ((int64_t)1 << 31);
     }
   }
-  if (segmented) planes_ok = false;   // (segments run the separable passes only)
+  if (segmented || cplx) planes_ok = false;   // (segments and complex64 plans run the separable passes only)
   // overlap-save tiles along the outermost axis
   const int64_t Kd = p->kd[0], Lfull = p->Lf[0];
   const fc::TileImpl* best = nullptr;
@@ -373,6 +380,7 @@ static int transform_kernel_nd_segment(const fc_plan& p, const float* weight, vo
     if (nd == 3) { r.kz = seg_taps(0); r.toz = j[0] * p.fnd.seg_taps[0]; }
   }
   r.nxt = 1; r.Vx = 0;                       // the kernel sits in the first x tile
+  if (p.io == FC_C64) r.io = FC_C64;         // complex taps, conjugated as rows_c2c_fwd loads them
   r.transposed = p.d.transposed; r.Cig = p.Cig; r.Cog = p.Cog;
   if (p.fnd.swap) {   // "kernel" = the output gradient (B, g*Cog, *Lout), read as ((g, o), b): image o_all*B + b sits at b*(g*Cog) + o_all
     r.im.on = 1; r.im.n1 = 1; r.im.n2 = (int)p.fnd.sw_B; r.im.s0 = 1; r.im.s1 = 0; r.im.s2 = p.fnd.sw_g * p.fnd.sw_Cog;
@@ -471,7 +479,8 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   r.nxt = p.fnd.nxt; r.Vx = p.fnd.Vx;
   const int Fs = p.fnd.Fxt;                       // signal-side bin columns per plane (all x tiles)
   {
-    const unsigned long long bytes = (p.io == FC_F32 ? 4ull : 2ull) * (unsigned long long)B * Ci * r.SZ * r.SY * r.SX;
+    const unsigned long long es = p.io == FC_C64 ? 8ull : (p.io == FC_F32 ? 4ull : 2ull);
+    const unsigned long long bytes = es * (unsigned long long)B * Ci * r.SZ * r.SY * r.SX;
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
   r.rowmajor = p.fnd.planes == 2;

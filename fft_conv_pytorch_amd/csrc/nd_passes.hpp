@@ -625,6 +625,180 @@ __global__ __launch_bounds__(NT) void rows_c2r_kernel(const RowsC2RArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------ complex rows
+// The last-axis passes of a complex64 plan (PlanKind::C64_ND): siblings of rows_r2c_kernel / rows_c2r_kernel above, launched
+// with the same argument structs when `io` is IO_CODE_ND_C64.  src / dst / bias of the tensors are (re, im) float32 pairs.
+//   * one row per engine sequence: a workgroup covers NSEQ rows (the real builds: 2*NSEQ), nothing is packed or unpacked;
+//   * all T bins of a row are kept (a.Fx == T): the middle passes see T bin columns per x tile;
+//   * no odd-frequency turn: a complex row has no self-paired bins to avoid, so the transform is the plain cyclic one on
+//     the signal, the taps and the inverse alike (overlap-save discards the wrapped samples either way);
+//   * taps are conjugated as they are loaded: the spectrum's last pass stores conj(.) * scale (c2c_fwd, store_mode 1), so
+//     H = conj(DFT(conj(w))) = sum_k w[k] e^{+2 pi i f k / T} and X * H is the plain bilinear correlation
+//     y[t] = sum_k w[k] x[t + k], nothing conjugated in the result.
+// The row-major pipeline (a.rowmajor) and the accumulating store (a.accum) have no complex build: the host never asks.
+constexpr int IO_CODE_ND_C64 = 4;   // fc_dtype code FC_C64 in a launch's `io` field
+
+template <int P, int S, int NSEQ, int NT>
+__global__ __launch_bounds__(NT) void rows_c2c_fwd_kernel(const RowsR2CArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  constexpr int RB = NSEQ;
+  static_assert(NT == NSEQ * G::TS, "one thread slot per sequence point group");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const f2* src = (const f2*)a.src;
+  const BufRsrc twA = make_rsrc(a.twA, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned q;
+  const int yb = (int)fdivmod(blockIdx.x, a.d_nyb, &q);
+  const int xt = (int)fdivmod(q, a.d_nxt, &q);
+  const int c = (int)fdivmod(q, a.d_nc, &q);
+  const int img = (int)q;
+  const int y0 = yb * RB;
+  const int x0 = xt * a.Vx;              // padded position of this tile's first sample
+
+  f2 v[P];
+  {
+    const int yp = y0 + sq;
+    int ys, zs;
+    if (a.from_kernel) {
+      ys = yp < a.NY ? tap_src(yp, a.dy, a.ky) : -1;
+      zs = tap_src(c, a.dz, a.kz);
+      if (ys >= 0) ys += a.toy;
+      if (zs >= 0) zs += a.toz;
+    } else {
+      ys = yp < a.NY ? axis_src(a.my, yp + a.shy) : -1;
+      zs = axis_src(a.mz, c + a.shz);       // (2-D plans carry an identity map here)
+    }
+    const bool ok = ys >= 0 && zs >= 0;
+    size_t simg = map_img(a.im, img);
+    if (a.from_kernel && a.transposed) {
+      const int o_all = img / a.Cig, i = img % a.Cig;
+      simg = (size_t)((o_all / a.Cog) * a.Cig + i) * a.Cog + (o_all % a.Cog);
+      ys = a.SY - 1 - ys; zs = a.SZ - 1 - zs;
+    }
+    const f2* row = src + ((simg * a.SZ + (ok ? zs : 0)) * a.SY + (ok ? ys : 0)) * a.SX;
+    if (!a.from_kernel && a.mx.up == 1 && a.mx.mode == PAD_CONSTANT && a.src_bytes != 0) {
+      // fast path (zero padding): unrolled 8-byte buffer loads over the whole source tensor; a sample outside its row
+      // gets an out-of-range offset and reads as zero -- no masks live across the loads
+      const BufRsrc sg = make_rsrc(a.src, a.src_bytes);
+      const unsigned ro = ok ? (unsigned)((row - src) * 8) : 0xFFFFFFFFu;
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) {
+        const int xs = x0 + G::N2 * n1 + tseq + a.shx - a.mx.pad;
+        const bool in = (unsigned)xs < (unsigned)a.mx.size;
+        v[n1] = buf_load_f32x2(sg, (in && ok) ? ro + (unsigned)xs * 8u : 0xFFFFFFFFu, 0);
+      }
+    } else {
+      const float cj = a.from_kernel ? -1.f : 1.f;      // taps: conjugated as they are loaded
+      f2* col = lds + sq * LSEQP + tseq;
+#pragma unroll 1
+      for (int n1 = 0; n1 < P; ++n1) {
+        const int xp = x0 + G::N2 * n1 + tseq;
+        int xs = a.from_kernel ? tap_src(xp, a.dx, a.kx) : axis_src(a.mx, xp + a.shx);
+        if (a.from_kernel && xs >= 0) xs += a.tox;
+        if (a.from_kernel && a.transposed && xs >= 0) xs = a.SX - 1 - xs;
+        const f2 s = (ok && xs >= 0) ? row[xs] : mk2(0.f, 0.f);
+        col[n1 * G::RS] = mk2(s.x, cj * s.y);
+      }
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) v[n1] = col[n1 * G::RS];
+    }
+  }
+  fwd_from_regs<G>(v, lds + sq * LSEQP, tseq, true, twA, twB);
+  __syncthreads();
+  // all T bins of every row, stored transposed: RB rows contiguous per bin (a thread keeps its row r = tid % RB over all
+  // rounds and steps NT/RB bins per round: every LDS read is requested before the first store, and the stores are buffer
+  // stores relative to this workgroup's block of bin columns -- 32-bit offsets, rows past NY get bit 31 instead of a branch)
+  static_assert(NT % RB == 0 && (T * RB) % NT == 0, "whole rounds, fixed row per thread");
+  constexpr int NROUND = T * RB / NT, FSTEP = NT / RB;
+  f2* out = a.dst + (((size_t)img * a.NC + c) * a.nxt + xt) * a.Fx * a.NYa + y0;
+  const BufRsrc orr = make_rsrc(out, (unsigned)(((size_t)(T - 1) * a.NYa + min(RB, a.NYa - y0)) * 8));
+  const int r = tid % RB, fx0 = tid / RB;
+  const f2* z = lds + r * LSEQP;
+  f2 zf[NROUND];
+#pragma unroll
+  for (int u = 0; u < NROUND; ++u) zf[u] = z[G::nat(fx0 + u * FSTEP)];
+  const unsigned rofs = (unsigned)r * 8u, rbad = (y0 + r < a.NY) ? 0u : 0x80000000u;
+#pragma unroll
+  for (int u = 0; u < NROUND; ++u) {
+    const int fx = fx0 + u * FSTEP;
+    buf_store_f32x2(zf[u], orr, (rofs + (unsigned)(fx * a.NYa) * 8u) | rbad, 0);
+  }
+}
+
+template <int P, int S, int NSEQ, int NT>
+__global__ __launch_bounds__(NT) void rows_c2c_inv_kernel(const RowsC2RArgs a) {
+  using G = Geo<P, S>;
+  constexpr int T = G::T;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  constexpr int RB = NSEQ;
+  static_assert(NT == NSEQ * G::TS, "thread count");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned q;
+  const int yb = (int)fdivmod(blockIdx.x, a.d_nyb, &q);
+  const int xt = (int)fdivmod(q, a.d_nxt, &q);
+  const int c = (int)fdivmod(q, a.d_nc, &q);
+  const int img = (int)q;
+  const int y0 = yb * RB;
+  const int x0 = xt * a.Vx;                    // first stride-1 sample of this tile
+  const int xlim = min(a.Vx, a.NV - x0);       // valid samples the tile contributes
+  f2 wtw[P];
+  passA_twiddle_fetch<G>(wtw, tseq, twA);      // requested first: lands while the spectra are loaded
+  {
+    // the T bins of NSEQ rows: ALL of a thread's bins are requested before the first goes to LDS, through a buffer
+    // resource over this plane of bin columns; rows past NY get an offset outside it and read as zero
+    const f2* in = a.src + (((size_t)img * a.NC + c) * a.nxt + xt) * a.Fx * a.NYa + y0;
+    static_assert((T * NSEQ) % NT == 0, "whole rounds of the gather");
+    constexpr int NITER = T * NSEQ / NT;
+    const BufRsrc sr = make_rsrc(in, (unsigned)(((size_t)(T - 1) * a.NYa + min(RB, a.NYa - y0)) * 8));
+    f2 val[NITER];
+#pragma unroll
+    for (int u = 0; u < NITER; ++u) {
+      const int idx = u * NT + tid, s = idx % NSEQ, fx = idx / NSEQ;
+      val[u] = buf_load_f32x2(sr, y0 + s < a.NY ? (unsigned)(((size_t)fx * a.NYa + s) * 8) : 0xFFFFFFFFu, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < NITER; ++u) {
+      const int idx = u * NT + tid, s = idx % NSEQ, fx = idx / NSEQ;
+      lds[s * LSEQP + G::nat(fx)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  const int j = inv_to_regs_pre<G>(v, wtw, lds + sq * LSEQP, tseq, true, twB);
+  // (declared arrived before the guarded stores, as in rows_c2r_kernel)
+  f2 b = a.bias ? ((const f2*)a.bias)[img % a.Cout] : mk2(0.f, 0.f);
+  asm volatile("" : "+v"(b.x), "+v"(b.y));
+  // 8-byte buffer stores relative to this workgroup's RB output rows (32-bit offsets; samples past the valid window,
+  // decimated away or in rows past NY get bit 31 instead of a branch)
+  f2* orow = (f2*)a.dst + ((map_img(a.im, img) * a.NC + c) * a.NY + y0) * a.Xo;
+  const BufRsrc orr = make_rsrc(orow, (unsigned)((size_t)min(RB, a.NY - y0) * a.Xo * 8));
+  const unsigned r0 = (unsigned)(sq * a.Xo) * 8u, bad = (y0 + sq < a.NY) ? 0u : 0x80000000u;
+  const int nbase = (tseq >> G::LGS) + P * P * j;
+  if (a.stride == 1) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      const int n = nbase + P * k;
+      const unsigned xo = (unsigned)(x0 + n) * 8u, badx = n < xlim ? 0u : 0x80000000u;
+      buf_store_f32x2(mk2(v[k].x + b.x, v[k].y + b.y), orr, (r0 + xo) | bad | badx, 0);
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    const int n = nbase + P * k;
+    const int t = x0 + n;
+    const int idx = t / a.stride;
+    const unsigned xo = (unsigned)idx * 8u, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
+    buf_store_f32x2(mk2(v[k].x + b.x, v[k].y + b.y), orr, (r0 + xo) | bad | badx, 0);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ fusedc
 // Outermost-axis pass: CIB complex sequences (one per input channel of the group) per workgroup.
 struct FusedCArgs {

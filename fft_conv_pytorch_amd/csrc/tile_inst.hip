@@ -54,17 +54,27 @@ hipError_t spec1d_dispatch(const Spec1dArgs& a, int grid, size_t lds, hipStream_
 
 // first and last pass of the N-d plans: Kernel is a build of rows_r2c_kernel (Args = RowsR2CArgs) or rows_c2r_kernel
 constexpr int kNT_R = kNSEQ_R * GG::TS;
-template <auto Kernel, class Args>
+// (RB: rows per workgroup -- two per sequence in the real builds, one in the complex ones)
+template <auto Kernel, class Args, int RB = 2 * kNSEQ_R>
 hipError_t launch_rows(const Args& a, hipStream_t st) {
-  const long long nyb = (a.NY + 2 * kNSEQ_R - 1) / (2 * kNSEQ_R);
+  const long long nyb = (a.NY + RB - 1) / RB;
   Args b = a;
   b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
   return launch_kernel<Kernel>((long long)a.NA * a.NC * a.nxt * nyb, kNT_R, (size_t)kNSEQ_R * kLSEQP * sizeof(float2), st, b);
 }
+// io == IO_CODE_ND_C64: the complex siblings (a complex64 plan's signal and taps; no row-major pipeline, no accumulating store)
 hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
+  if (a.io == IO_CODE_ND_C64) {
+    if (a.rowmajor) return hipErrorInvalidValue;
+    return launch_rows<rows_c2c_fwd_kernel<FC_P, FC_S, kNSEQ_R, kNT_R>, RowsR2CArgs, kNSEQ_R>(a, st);
+  }
   return with_io(a.io, [&](auto io) { return launch_rows<rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, FC_IO(io)>>(a, st); });
 }
 hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
+  if (a.io == IO_CODE_ND_C64) {
+    if (a.rowmajor || a.accum) return hipErrorInvalidValue;
+    return launch_rows<rows_c2c_inv_kernel<FC_P, FC_S, kNSEQ_R, kNT_R>, RowsC2RArgs, kNSEQ_R>(a, st);
+  }
   return with_io(a.io, [&](auto io) { return launch_rows<rows_c2r_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, FC_IO(io)>>(a, st); });
 }
 

@@ -23,6 +23,7 @@ __all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_transpose", "fft_conv_tra
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
 _CONV_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)      # of fft_conv / fft_conv_transpose plans
+_CONV_ND_DTYPES = _CONV_DTYPES + (torch.complex64,)                               # ... of their 2-D and 3-D plans
 
 
 def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
@@ -31,11 +32,13 @@ def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
         raise RuntimeError(
             f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
             f"(no CPU fallback). Move the tensor to 'cuda'.")
-    if t.dtype != dtype or dtype not in _CONV_DTYPES:
+    if t.dtype != dtype or dtype not in _CONV_ND_DTYPES:
         raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; signal, kernel and bias must share one of "
                         f"float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
-                        f"their crossover) or float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
-                        f"kernels, which widen the signal as they load it and round the output once as they store it)")
+                        f"their crossover), float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
+                        f"kernels, which widen the signal as they load it and round the output once as they store it) or, "
+                        f"for 4-D and 5-D tensors, complex64 (1-D complex rows: fft_long_conv; complex128, complex32 and "
+                        f"mixes of real and complex tensors are not taken: convert with .to(torch.complex64))")
 
 
 class KernelSpectrum:
@@ -110,7 +113,8 @@ def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, g
                 f"(need kernel.shape[1] * groups == in_channels and out_channels % groups == 0)")
     if bias is not None and tuple(bias.shape) != (cout,):
         raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
-    dtype = signal.dtype if signal.dtype in _CONV_DTYPES else torch.float32
+    # (complex64: 2-D and 3-D plans only; a 1-D complex signal fails the dtype gate below)
+    dtype = signal.dtype if signal.dtype in (_CONV_DTYPES if n == 1 else _CONV_ND_DTYPES) else torch.float32
     key = (n, int(signal.shape[0]), cin, cout, groups,
            tuple(int(s) for s in signal.shape[2:]), tuple(int(k) for k in kernel.shape[2:]),
            tuple(int(s) for s in stride_), tuple(int(p) for p in padding_), tuple(int(d) for d in dilation_),
@@ -159,7 +163,8 @@ def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
         io = (_DTYPE_CODES[kernel.dtype],)
     else:
         _require_gpu_f32("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype)
-        kernel = kernel.detach().to(plan.weight_dtype).contiguous()
+        # (a complex64 plan: the library reads data_ptr(), a lazy conjugate is resolved first)
+        kernel = _resolved(kernel.detach()).to(plan.weight_dtype).contiguous()
     if _device_index(kernel.device) != plan.device_index:
         raise ValueError(f"kernel is on {kernel.device} but the plan was made for cuda:{plan.device_index}")
     with torch.cuda.device(kernel.device):
@@ -181,9 +186,9 @@ def _launch_forward(signal: Tensor, spectrum: KernelSpectrum, bias_c: Optional[T
 
 
 def _forward_native(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Tensor]) -> Tensor:
-    signal = signal.detach().contiguous()
-    # (a float16 / bfloat16 plan reads a float32 bias: Cout values)
-    bias_c = bias.detach().to(spectrum.plan.weight_dtype).contiguous() if bias is not None else None
+    signal = _resolved(signal.detach()).contiguous()
+    # (a float16 / bfloat16 plan reads a float32 bias: Cout values; a complex64 plan Cout (re, im) pairs)
+    bias_c = _resolved(bias.detach()).to(spectrum.plan.weight_dtype).contiguous() if bias is not None else None
     index = _device_index(signal.device)
     if signal.dtype != spectrum.plan.dtype:
         raise TypeError(f"signal is {signal.dtype} but the plan was made for {spectrum.plan.dtype}")
@@ -216,6 +221,13 @@ def fft_conv(
     input's device.  Unlike the reference, a kernel larger than the padded
     input raises ``ValueError`` (torch's behaviour) instead of returning a
     wrongly shaped tensor.
+
+    4-D and 5-D complex64 ``signal``, ``kernel`` and ``bias`` (all three) run a complex plan: plain bilinear product,
+    nothing conjugated (``torch.nn.functional.conv2d`` / ``conv3d`` on complex tensors), every argument with its meaning,
+    a complex64 result, gradients in PyTorch's convention for complex tensors; lazy conjugates and negations are resolved
+    on entry.  complex128, complex32, mixes of real and complex tensors and 3-D (one spatial axis) complex tensors raise
+    ``TypeError`` (complex rows: ``fft_long_conv``); a kernel that would run in segments of taps (a dilated extent past 4096
+    on an axis) raises ``NotImplementedError``.
     """
     return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
 
@@ -265,6 +277,9 @@ def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padd
             # larger buffer and break downstream .view() calls)
             out = out[(slice(None), slice(None)) + tuple(slice(d, None) for d in drop)].contiguous()
         return out
+    if signal.is_complex():
+        # (the library reads data_ptr(): a conj or neg bit is resolved here, inside the autograd graph)
+        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
     if _half_native(signal, kernel, bias):
         # the kernels read x and write y in the tensors' dtype (float32 arithmetic, the bits of the cast path below)
         try:
@@ -315,7 +330,8 @@ def fft_conv_transpose(
     ``kernel`` is (Cin, Cout/groups, *k).  The same HIP kernels as ``fft_conv`` run it: the stride
     becomes a zero-spread of the input folded into the load index map, the kernel flip and the
     in/out channel swap are folded into the kernel transform, padding / output_padding only move
-    the window of kept samples -- no intermediate tensor is materialised.
+    the window of kept samples -- no intermediate tensor is materialised.  4-D and 5-D complex64 tensors (all three)
+    are taken as ``fft_conv`` takes them.
     """
     return _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, None)
 
@@ -323,6 +339,8 @@ def fft_conv_transpose(
 def _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum,
                              plan=None):
     """Shared by the functional and the transposed modules (``spectrum`` / ``plan``: see ``_fft_conv_impl``)."""
+    if signal.is_complex():
+        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
     if _half_native(signal, kernel, bias):
         try:
             if plan is None:

@@ -4,7 +4,8 @@ Mirrors /root/reference/fft_conv_pytorch/nn.py:7-51: constructor, parameters
 and ``state_dict`` come unchanged from ``torch.nn.Conv{N}d`` through the MRO;
 only ``forward`` differs.  On top of the reference, inference (``eval()`` or a
 frozen weight) reuses the transformed kernel per (weight version, input geometry);
-see ``_SpectrumCache`` for exactly when.
+see ``_SpectrumCache`` for exactly when.  The 2-D and 3-D modules also run in complex64
+(``dtype=torch.complex64`` or ``.to(torch.complex64)``): one complex plan, the same cache.
 """
 import os
 
@@ -99,7 +100,7 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
     def forward(self, signal: Tensor):
         assert signal.ndim == self.weight.ndim
         padding_mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
-        if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64)
+        if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64, torch.complex64)
                                              and not F_._half_native(signal, self.weight, self.bias)):
             # padding='same' / 'valid' (torch stores the string) and half-precision calls the kernels do not read and write
             # in their own dtype (FFTCONV_HALF_IO=0, mixed dtypes): the functional resolves them

@@ -54,8 +54,19 @@ enum fc_dtype {
                   descriptor, and the loads widen exactly, so every partial and dW has the float32 call's bits on the widened
                   tensors; segments of taps add into the float32 dW as they do there.  A library that predates this answers
                   such a descriptor with 0 slices or FC_ERR_UNSUPPORTED: a caller widens x and dy for that gradient. */
-  FC_C64 = 4   /* complex64 tensors, (re, im) float32 pairs (ABI 7 extension): the long-filter calls fc_long_transform_kernel_io
-                  and fc_long_forward_io on a complex plan (fc_long_plan_create_kind) only; no fc_desc takes it */
+  FC_C64 = 4   /* complex64 tensors, (re, im) float32 pairs (ABI 7 extension).  Two homes:
+                  1-D rows: the long-filter calls fc_long_transform_kernel_io and fc_long_forward_io on a complex plan
+                  (fc_long_plan_create_kind); a 1-D fc_desc with this dtype answers FC_ERR_UNSUPPORTED naming them.
+                  2-D / 3-D: an fc_desc with this dtype, forward or transposed (fc_plan_create): x, weight, bias and y are
+                  complex64 and travel through the float* parameters as float64 tensors do (bias: Cout (re, im) pairs); w_hat
+                  and the workspace stay float32 pairs, sized by fc_kernel_spectrum_bytes / fc_workspace_bytes.  The product
+                  is plain bilinear, y[t] = sum w[k] * x[t + k], nothing conjugated (torch.nn.functional.conv2d on complex
+                  tensors).  The plan runs the separable passes with one row per transform of the last axis and all of its
+                  bins kept (twice the bin columns of the float32 plan of the same shape); fc_debug_route reports word 0 = 6
+                  and behind it the words of a float32 2-D / 3-D plan (planes is always 0).  Not offered, each
+                  FC_ERR_UNSUPPORTED with text: segments of taps (a dilated kernel extent past 4096 on an axis, or
+                  FFTCONV_NDSEG), fc_wgrad_nd_plan_create, fc_forward_stamped with stamps.  Rows of the output are addressed
+                  with 32-bit byte offsets of 8-byte samples: the guards of the float32 plans hold at half the samples. */
 };
 
 /* Problem descriptor: the arguments of functional.py:19-28 after to_ntuple

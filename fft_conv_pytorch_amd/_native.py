@@ -19,22 +19,6 @@ FC_OK, FC_ERR_INVALID, FC_ERR_UNSUPPORTED, FC_ERR_HIP = 0, 1, 2, 3
 PAD_MODES = {"constant": 0, "zeros": 0, "reflect": 1, "replicate": 2, "circular": 3}
 ABI_VERSION = 7
 
-EXPORTS = (
-    "fc_version", "fc_last_error", "fc_plan_create", "fc_plan_destroy", "fc_output_shape",
-    "fc_kernel_spectrum_bytes", "fc_workspace_bytes", "fc_plan_tile", "fc_plan_layout", "fc_transform_kernel",
-    "fc_forward", "fc_forward_stamped", "fc_wgrad1d_slices", "fc_wgrad1d", "fc_wgrad1d_db", "fc_wgrad1d_db_supported",
-    "fc_debug_grid", "fc_wgrad_nd_plan_create", "fc_wgrad_nd", "fc_debug_route",
-    "fc_long_geometry", "fc_long_plan_create", "fc_long_plan_destroy", "fc_long_plan_info", "fc_long_transform_kernel",
-    "fc_long_forward", "fc_long_transform_kernel_io", "fc_long_forward_io",
-    "fc_long_geometry_ext", "fc_long_plan_create_ext",
-    "fc_long_geometry_kind", "fc_long_plan_create_kind", "fc_long_plan_kind",
-    "fc_long_forward_lay",
-    "fc_long_phases_geometry", "fc_long_phases_plan_create",
-    "fc_long_decim_geometry", "fc_long_decim_plan_create",
-    "fc_long_wgrad_geometry", "fc_long_wgrad_check_io", "fc_long_wgrad_plan_create", "fc_long_wgrad_plan_destroy",
-    "fc_long_wgrad_plan_info", "fc_long_wgrad",
-)
-
 # words of fc_debug_route after the plan kind, per kind (include/fftconv_amd.h)
 ROUTE_KINDS = ("f32_1d", "f32_nd", "f64_direct", "f64_fft_1d", "f64_fft_nd", "f64_fft_long", "c64_nd")
 ROUTE_WORDS = {
@@ -123,6 +107,64 @@ LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "
 LONG_WGRAD_INFO_WORDS = ("N1", "N2", "taps", "lags", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
 
+def _signatures() -> dict:
+    vp, sz, i32, ll = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_longlong
+    ptr = ctypes.POINTER
+    desc, out, i64x8 = ptr(FcDesc), ptr(vp), ptr(ctypes.c_int64 * 8)
+    ldesc, lext, wdesc = ptr(FcLongDesc), ptr(FcLongExt), ptr(FcLongWgradDesc)
+    return {
+        "fc_version": (i32, ()),
+        "fc_last_error": (ctypes.c_char_p, ()),
+        "fc_plan_create": (i32, (desc, out)),
+        "fc_plan_destroy": (None, (vp,)),
+        "fc_output_shape": (i32, (vp, ptr(ctypes.c_int64 * 3))),
+        "fc_kernel_spectrum_bytes": (sz, (vp,)),
+        "fc_workspace_bytes": (sz, (vp,)),
+        "fc_plan_tile": (i32, (vp,)),
+        "fc_plan_layout": (i32, (vp, ptr(ctypes.c_int32 * 8))),
+        "fc_transform_kernel": (i32, (vp, vp, vp, vp, vp)),
+        "fc_forward": (i32, (vp, vp, vp, vp, vp, vp, vp)),
+        "fc_forward_stamped": (i32, (vp, vp, vp, vp, vp, vp, vp, vp)),
+        "fc_wgrad1d_slices": (i32, (desc,)),
+        "fc_wgrad1d": (i32, (desc, vp, vp, vp, i32, vp)),
+        "fc_wgrad1d_db": (i32, (desc, vp, vp, vp, vp, ll, i32, vp)),
+        "fc_wgrad1d_db_supported": (i32, (desc,)),
+        "fc_debug_grid": (ll, (vp,)),
+        "fc_wgrad_nd_plan_create": (i32, (desc, out)),
+        "fc_wgrad_nd": (i32, (vp, vp, vp, vp, vp, vp, vp)),
+        "fc_debug_route": (i32, (vp, ptr(ctypes.c_int32 * 16))),
+        "fc_long_geometry": (i32, (ldesc, i64x8)),
+        "fc_long_plan_create": (i32, (ldesc, out)),
+        "fc_long_plan_destroy": (None, (vp,)),
+        "fc_long_plan_info": (i32, (vp, i64x8)),
+        "fc_long_transform_kernel": (i32, (vp, vp, vp, vp, vp)),
+        "fc_long_forward": (i32, (vp, vp, vp, vp, vp, vp, vp)),
+        "fc_long_transform_kernel_io": (i32, (vp, vp, i32, vp, vp, vp)),
+        "fc_long_forward_io": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
+        "fc_long_geometry_ext": (i32, (ldesc, lext, i64x8)),
+        "fc_long_plan_create_ext": (i32, (ldesc, lext, out)),
+        "fc_long_geometry_kind": (i32, (ldesc, lext, i32, i64x8)),
+        "fc_long_plan_create_kind": (i32, (ldesc, lext, i32, out)),
+        "fc_long_plan_kind": (i32, (vp,)),
+        "fc_long_forward_lay": (i32, (vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp)),
+        "fc_long_phases_geometry": (i32, (ptr(FcLongPhasesDesc), i64x8)),
+        "fc_long_phases_plan_create": (i32, (ptr(FcLongPhasesDesc), out)),
+        "fc_long_decim_geometry": (i32, (ptr(FcLongDecimDesc), i64x8)),
+        "fc_long_decim_plan_create": (i32, (ptr(FcLongDecimDesc), out)),
+        "fc_long_wgrad_geometry": (i32, (wdesc, i64x8)),
+        "fc_long_wgrad_check_io": (i32, (wdesc, i32, i32, i32, i32, i32)),
+        "fc_long_wgrad_plan_create": (i32, (wdesc, out)),
+        "fc_long_wgrad_plan_destroy": (None, (vp,)),
+        "fc_long_wgrad_plan_info": (i32, (vp, i64x8)),
+        "fc_long_wgrad": (i32, (vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp)),
+    }
+
+
+# every export of include/fftconv_amd.h -> (restype, argtypes); the tests compare both with the header's declarations
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
+
+
 class NativeLibraryMissing(ImportError):
     pass
 
@@ -144,184 +186,13 @@ def load_library() -> ctypes.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"(or `make -C fft_conv_pytorch_amd/csrc`). There is no CPU fallback.")
         lib = ctypes.CDLL(LIB_PATH)
-        vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-        lib.fc_version.restype = i32
-        lib.fc_last_error.restype = ctypes.c_char_p
-        lib.fc_plan_create.argtypes = [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]
-        lib.fc_plan_create.restype = i32
-        lib.fc_plan_destroy.argtypes = [vp]
-        lib.fc_plan_destroy.restype = None
-        lib.fc_output_shape.argtypes = [vp, ctypes.POINTER(ctypes.c_int64 * 3)]
-        lib.fc_output_shape.restype = i32
-        lib.fc_kernel_spectrum_bytes.argtypes = [vp]
-        lib.fc_kernel_spectrum_bytes.restype = sz
-        lib.fc_workspace_bytes.argtypes = [vp]
-        lib.fc_workspace_bytes.restype = sz
-        lib.fc_plan_tile.argtypes = [vp]
-        lib.fc_plan_tile.restype = i32
-        lib.fc_transform_kernel.argtypes = [vp, vp, vp, vp, vp]
-        lib.fc_transform_kernel.restype = i32
-        lib.fc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        lib.fc_forward.restype = i32
-        lib.fc_wgrad1d_slices.argtypes = [ctypes.POINTER(FcDesc)]
-        lib.fc_wgrad1d_slices.restype = i32
-        lib.fc_wgrad1d.argtypes = [ctypes.POINTER(FcDesc), vp, vp, vp, i32, vp]
-        lib.fc_wgrad1d.restype = i32
-        lib.fc_wgrad1d_db.argtypes = [ctypes.POINTER(FcDesc), vp, vp, vp, vp, ctypes.c_longlong, i32, vp]
-        lib.fc_wgrad1d_db.restype = i32
-        lib.fc_wgrad1d_db_supported.argtypes = [ctypes.POINTER(FcDesc)]
-        lib.fc_wgrad1d_db_supported.restype = i32
-        lib.fc_wgrad_nd_plan_create.argtypes = [ctypes.POINTER(FcDesc), ctypes.POINTER(vp)]
-        lib.fc_wgrad_nd_plan_create.restype = i32
-        lib.fc_wgrad_nd.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        lib.fc_wgrad_nd.restype = i32
-        lib.fc_forward_stamped.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.fc_forward_stamped.restype = i32
-        lib.fc_plan_layout.argtypes = [vp, ctypes.POINTER(ctypes.c_int32 * 8)]
-        lib.fc_plan_layout.restype = i32
-        lib.fc_debug_grid.argtypes = [vp]
-        lib.fc_debug_grid.restype = ctypes.c_longlong
-        lib.fc_debug_route.argtypes = [vp, ctypes.POINTER(ctypes.c_int32 * 16)]
-        lib.fc_debug_route.restype = i32
-        i64x8 = ctypes.POINTER(ctypes.c_int64 * 8)
-        lib.fc_long_geometry.argtypes = [ctypes.POINTER(FcLongDesc), i64x8]
-        lib.fc_long_geometry.restype = i32
-        lib.fc_long_plan_create.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(vp)]
-        lib.fc_long_plan_create.restype = i32
-        lib.fc_long_plan_destroy.argtypes = [vp]
-        lib.fc_long_plan_destroy.restype = None
-        lib.fc_long_plan_info.argtypes = [vp, i64x8]
-        lib.fc_long_plan_info.restype = i32
-        lib.fc_long_transform_kernel.argtypes = [vp, vp, vp, vp, vp]
-        lib.fc_long_transform_kernel.restype = i32
-        lib.fc_long_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        lib.fc_long_forward.restype = i32
-        lib.fc_long_transform_kernel_io.argtypes = [vp, vp, i32, vp, vp, vp]
-        lib.fc_long_transform_kernel_io.restype = i32
-        lib.fc_long_forward_io.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp]
-        lib.fc_long_forward_io.restype = i32
-        lib.fc_long_geometry_ext.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i64x8]
-        lib.fc_long_geometry_ext.restype = i32
-        lib.fc_long_plan_create_ext.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), ctypes.POINTER(vp)]
-        lib.fc_long_plan_create_ext.restype = i32
-        lib.fc_long_geometry_kind.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i32, i64x8]
-        lib.fc_long_geometry_kind.restype = i32
-        lib.fc_long_plan_create_kind.argtypes = [ctypes.POINTER(FcLongDesc), ctypes.POINTER(FcLongExt), i32,
-                                                 ctypes.POINTER(vp)]
-        lib.fc_long_plan_create_kind.restype = i32
-        lib.fc_long_plan_kind.argtypes = [vp]
-        lib.fc_long_plan_kind.restype = i32
-        lib.fc_long_forward_lay.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]
-        lib.fc_long_forward_lay.restype = i32
-        lib.fc_long_phases_geometry.argtypes = [ctypes.POINTER(FcLongPhasesDesc), i64x8]
-        lib.fc_long_phases_geometry.restype = i32
-        lib.fc_long_phases_plan_create.argtypes = [ctypes.POINTER(FcLongPhasesDesc), ctypes.POINTER(vp)]
-        lib.fc_long_phases_plan_create.restype = i32
-        lib.fc_long_decim_geometry.argtypes = [ctypes.POINTER(FcLongDecimDesc), i64x8]
-        lib.fc_long_decim_geometry.restype = i32
-        lib.fc_long_decim_plan_create.argtypes = [ctypes.POINTER(FcLongDecimDesc), ctypes.POINTER(vp)]
-        lib.fc_long_decim_plan_create.restype = i32
-        wdesc = ctypes.POINTER(FcLongWgradDesc)
-        lib.fc_long_wgrad_geometry.argtypes = [wdesc, i64x8]
-        lib.fc_long_wgrad_geometry.restype = i32
-        lib.fc_long_wgrad_check_io.argtypes = [wdesc, i32, i32, i32, i32, i32]
-        lib.fc_long_wgrad_check_io.restype = i32
-        lib.fc_long_wgrad_plan_create.argtypes = [wdesc, ctypes.POINTER(vp)]
-        lib.fc_long_wgrad_plan_create.restype = i32
-        lib.fc_long_wgrad_plan_destroy.argtypes = [vp]
-        lib.fc_long_wgrad_plan_destroy.restype = None
-        lib.fc_long_wgrad_plan_info.argtypes = [vp, i64x8]
-        lib.fc_long_wgrad_plan_info.restype = i32
-        lib.fc_long_wgrad.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp]
-        lib.fc_long_wgrad.restype = i32
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
         if lib.fc_version() != ABI_VERSION:
             raise ImportError(f"{LIB_NAME}: ABI version {lib.fc_version()} != {ABI_VERSION}")
         _lib = lib
     return _lib
-
-
-def conv_desc(ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode, dtype=0) -> FcDesc:
-    """``struct fc_desc`` of a forward convolution (used by the calls that take a descriptor, not a plan).  ``dtype``: the
-    fc_dtype code of x and dY for the weight-gradient calls (0 float32, 2 float16, 3 bfloat16; dW stays float32)."""
-    d = FcDesc()
-    d.ndim, d.dtype = ndim, dtype
-    d.batch, d.in_channels, d.out_channels, d.groups = batch, cin, cout, groups
-    for i in range(3):
-        d.spatial[i] = spatial[i] if i < ndim else 1
-        d.kernel[i] = kernel[i] if i < ndim else 1
-        d.stride[i] = stride[i] if i < ndim else 1
-        d.padding[i] = padding[i] if i < ndim else 0
-        d.dilation[i] = dilation[i] if i < ndim else 1
-        d.output_padding[i] = 0
-    d.padding_mode, d.has_bias, d.tile_hint, d.transposed = mode, 0, 0, 0
-    return d
-
-
-def wgrad1d_slices(desc: FcDesc) -> int:
-    """Partial-result count of ``fc_wgrad1d`` for this shape on the current device; 0 = not covered."""
-    return int(load_library().fc_wgrad1d_slices(ctypes.byref(desc)))
-
-
-def wgrad1d(desc: FcDesc, x_ptr: int, dy_ptr: int, partial_ptr: int, slices: int, stream: int):
-    lib = load_library()
-    st = lib.fc_wgrad1d(ctypes.byref(desc), x_ptr, dy_ptr, partial_ptr, slices, stream)
-    if st != FC_OK:
-        _raise(lib, st)
-
-
-def wgrad1d_db_supported(desc: FcDesc) -> bool:
-    return bool(load_library().fc_wgrad1d_db_supported(ctypes.byref(desc)))
-
-
-def wgrad1d_db(desc: FcDesc, x_ptr: int, dy_ptr: int, partial_ptr: int, db_ptr: Optional[int], slice_stride: int,
-               slices: int, stream: int):
-    """fc_wgrad1d with the bias gradient folded in: rows [dW | db] of ``slice_stride`` floats per slice."""
-    lib = load_library()
-    st = lib.fc_wgrad1d_db(ctypes.byref(desc), x_ptr, dy_ptr, partial_ptr, db_ptr, slice_stride, slices, stream)
-    if st != FC_OK:
-        _raise(lib, st)
-
-
-class WgradPlan:
-    """Owns the plan of ``fc_wgrad_nd`` for one convolution descriptor (2-D / 3-D; x and dY float32, float16 or bfloat16
-    as the descriptor's dtype says): created on the CURRENT HIP device.  ``run`` reads x (B, Cin, *S) and dY (B, Cout, *Lout)
-    and writes a float32 dW (Cout, Cin/g, *k) -- no copies around it."""
-
-    def __init__(self, desc: FcDesc):
-        lib = load_library()
-        handle = ctypes.c_void_p()
-        st = lib.fc_wgrad_nd_plan_create(ctypes.byref(desc), ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        self._lib, self._h = lib, handle
-        self.spectrum_bytes = int(lib.fc_kernel_spectrum_bytes(handle))
-        self.workspace_bytes = int(lib.fc_workspace_bytes(handle))
-        self.tile = int(lib.fc_plan_tile(handle))
-
-    def run(self, x_ptr: int, dy_ptr: int, dw_ptr: int, spectrum_ptr: int, workspace_ptr: Optional[int], stream: int):
-        st = self._lib.fc_wgrad_nd(self._h, x_ptr, dy_ptr, dw_ptr, spectrum_ptr, workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.fc_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-
-def read_route(lib, handle) -> dict:
-    """``fc_debug_route`` as a dict: ``kind`` (a ROUTE_KINDS name) and that kind's ROUTE_WORDS (tests)."""
-    words = (ctypes.c_int32 * 16)()
-    st = lib.fc_debug_route(handle, ctypes.byref(words))
-    if st != FC_OK:
-        _raise(lib, st)
-    kind = ROUTE_KINDS[words[0]]
-    route = {"kind": kind}
-    route.update({name: int(words[1 + i]) for i, name in enumerate(ROUTE_WORDS[kind])})
-    return route
 
 
 def _raise(lib, status: int):
@@ -333,7 +204,107 @@ def _raise(lib, status: int):
     raise RuntimeError(f"libfftconv_amd: {msg}")
 
 
-class Plan:
+def _check(lib, status: int):
+    if status != FC_OK:
+        _raise(lib, status)
+
+
+def _refs(args):
+    """The arguments of a library call: structs by reference, everything else as it is."""
+    return [ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args]
+
+
+class _Handle:
+    """Owns one native handle: ``_open`` creates it, ``_check`` raises what a failed call reports, and the call named
+    ``_destroy`` frees it with the Python object."""
+
+    _destroy = "fc_plan_destroy"
+
+    def _open(self, create: str, *args):
+        self._lib = load_library()
+        handle = ctypes.c_void_p()
+        self._check(getattr(self._lib, create)(*_refs(args), ctypes.byref(handle)))
+        self._h = handle
+        return self._lib, handle
+
+    def _check(self, status: int):
+        _check(self._lib, status)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                getattr(self._lib, self._destroy)(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def conv_desc(ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode, dtype=0, *,
+              has_bias=False, tile_hint=0, transposed=False, output_padding=(0, 0, 0)) -> FcDesc:
+    """``struct fc_desc`` of a convolution (the calls that take a descriptor, and ``Plan``; the keywords default to a
+    forward convolution without bias).  ``dtype``: the
+    fc_dtype code of x and dY for the weight-gradient calls (0 float32, 2 float16, 3 bfloat16; dW stays float32)."""
+    d = FcDesc()
+    d.ndim, d.dtype = ndim, dtype
+    d.batch, d.in_channels, d.out_channels, d.groups = batch, cin, cout, groups
+    for i in range(3):
+        d.spatial[i] = spatial[i] if i < ndim else 1
+        d.kernel[i] = kernel[i] if i < ndim else 1
+        d.stride[i] = stride[i] if i < ndim else 1
+        d.padding[i] = padding[i] if i < ndim else 0
+        d.dilation[i] = dilation[i] if i < ndim else 1
+        d.output_padding[i] = output_padding[i] if i < ndim else 0
+    d.padding_mode, d.has_bias, d.tile_hint, d.transposed = mode, int(has_bias), tile_hint, int(transposed)
+    return d
+
+
+def wgrad1d_slices(desc: FcDesc) -> int:
+    """Partial-result count of ``fc_wgrad1d`` for this shape on the current device; 0 = not covered."""
+    return int(load_library().fc_wgrad1d_slices(ctypes.byref(desc)))
+
+
+def wgrad1d(desc: FcDesc, x_ptr: int, dy_ptr: int, partial_ptr: int, slices: int, stream: int):
+    lib = load_library()
+    _check(lib, lib.fc_wgrad1d(ctypes.byref(desc), x_ptr, dy_ptr, partial_ptr, slices, stream))
+
+
+def wgrad1d_db_supported(desc: FcDesc) -> bool:
+    return bool(load_library().fc_wgrad1d_db_supported(ctypes.byref(desc)))
+
+
+def wgrad1d_db(desc: FcDesc, x_ptr: int, dy_ptr: int, partial_ptr: int, db_ptr: Optional[int], slice_stride: int,
+               slices: int, stream: int):
+    """fc_wgrad1d with the bias gradient folded in: rows [dW | db] of ``slice_stride`` floats per slice."""
+    lib = load_library()
+    _check(lib, lib.fc_wgrad1d_db(ctypes.byref(desc), x_ptr, dy_ptr, partial_ptr, db_ptr, slice_stride, slices, stream))
+
+
+class WgradPlan(_Handle):
+    """Owns the plan of ``fc_wgrad_nd`` for one convolution descriptor (2-D / 3-D; x and dY float32, float16 or bfloat16
+    as the descriptor's dtype says): created on the CURRENT HIP device.  ``run`` reads x (B, Cin, *S) and dY (B, Cout, *Lout)
+    and writes a float32 dW (Cout, Cin/g, *k) -- no copies around it."""
+
+    def __init__(self, desc: FcDesc):
+        lib, handle = self._open("fc_wgrad_nd_plan_create", desc)
+        self.spectrum_bytes = int(lib.fc_kernel_spectrum_bytes(handle))
+        self.workspace_bytes = int(lib.fc_workspace_bytes(handle))
+        self.tile = int(lib.fc_plan_tile(handle))
+
+    def run(self, x_ptr: int, dy_ptr: int, dw_ptr: int, spectrum_ptr: int, workspace_ptr: Optional[int], stream: int):
+        self._check(self._lib.fc_wgrad_nd(self._h, x_ptr, dy_ptr, dw_ptr, spectrum_ptr, workspace_ptr, stream))
+
+
+def read_route(lib, handle) -> dict:
+    """``fc_debug_route`` as a dict: ``kind`` (a ROUTE_KINDS name) and that kind's ROUTE_WORDS (tests)."""
+    words = (ctypes.c_int32 * 16)()
+    _check(lib, lib.fc_debug_route(handle, ctypes.byref(words)))
+    kind = ROUTE_KINDS[words[0]]
+    route = {"kind": kind}
+    route.update({name: int(words[1 + i]) for i, name in enumerate(ROUTE_WORDS[kind])})
+    return route
+
+
+class Plan(_Handle):
     """Owns one ``fc_plan`` (immutable after creation; shareable between threads and streams).
 
     The library builds a plan for the HIP device that is current at creation (twiddle tables, work list,
@@ -342,23 +313,10 @@ class Plan:
     def __init__(self, key: Tuple, device_index: int = 0):
         (ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode, has_bias, tile_hint,
          transposed, output_padding, dtype_code) = key
-        lib = load_library()
-        d = FcDesc()
-        d.ndim, d.dtype = ndim, dtype_code
-        d.batch, d.in_channels, d.out_channels, d.groups = batch, cin, cout, groups
-        for i in range(3):
-            d.spatial[i] = spatial[i] if i < ndim else 1
-            d.kernel[i] = kernel[i] if i < ndim else 1
-            d.stride[i] = stride[i] if i < ndim else 1
-            d.padding[i] = padding[i] if i < ndim else 0
-            d.dilation[i] = dilation[i] if i < ndim else 1
-            d.output_padding[i] = output_padding[i] if i < ndim else 0
-        d.padding_mode, d.has_bias, d.tile_hint, d.transposed = mode, int(has_bias), tile_hint, int(transposed)
-        handle = ctypes.c_void_p()
-        st = lib.fc_plan_create(ctypes.byref(d), ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        self._lib, self._h, self.key = lib, handle, key
+        lib, handle = self._open("fc_plan_create", conv_desc(
+            ndim, batch, cin, cout, groups, spatial, kernel, stride, padding, dilation, mode, dtype_code,
+            has_bias=has_bias, tile_hint=tile_hint, transposed=transposed, output_padding=output_padding))
+        self.key = key
         self.device_index = int(device_index)
         import torch
         # dtype: of the signal and the output; weight_dtype: of the weight and bias the library reads (a float16 /
@@ -385,9 +343,7 @@ class Plan:
         return (self.spectrum_bytes,) + self.layout
 
     def transform_kernel(self, weight_ptr: int, w_hat_ptr: int, workspace_ptr: Optional[int], stream: int):
-        st = self._lib.fc_transform_kernel(self._h, weight_ptr, w_hat_ptr, workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
+        self._check(self._lib.fc_transform_kernel(self._h, weight_ptr, w_hat_ptr, workspace_ptr, stream))
 
     def forward(self, x_ptr: int, w_hat_ptr: int, bias_ptr: Optional[int], y_ptr: int,
                 workspace_ptr: Optional[int], stream: int):
@@ -396,8 +352,7 @@ class Plan:
                                               self._stamps)
         else:
             st = self._lib.fc_forward(self._h, x_ptr, w_hat_ptr, bias_ptr, y_ptr, workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
+        self._check(st)
 
     def debug_set_stamps(self, ptr: Optional[int]):
         """Profiling hook of this Python handle (the native plan stays immutable): while set, ``forward``
@@ -407,13 +362,20 @@ class Plan:
     def debug_grid(self) -> int:
         return int(self._lib.fc_debug_grid(self._h))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.fc_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+
+def _struct_of(cls, key: Tuple, words: int, what: str):
+    """A descriptor struct filled from a key of ``words`` words in ``_fields_`` order (a field past them stays zero)."""
+    if len(key) != words:
+        raise ValueError(f"a {what} key has {words} words, got {len(key)}")
+    return cls(*(int(v) for v in key))
+
+
+def _info_words(call: str, names: Tuple, *args) -> dict:
+    """The eight info words a geometry or plan-info call fills in, by name."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    _check(lib, getattr(lib, call)(*_refs(args), ctypes.byref(info)))
+    return {name: int(info[i]) for i, name in enumerate(names)}
 
 
 def long_desc(key: Tuple) -> FcLongDesc:
@@ -422,18 +384,13 @@ def long_desc(key: Tuple) -> FcLongDesc:
     if len(key) not in (11, 15, 16):
         raise ValueError(f"a long-plan key has 11 words, 15 with (pad_mode, src_up, tap_dil, out_step), or 16 with those and "
                          f"the kind of a complex plan; got {len(key)}")
-    d = FcLongDesc()
-    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_keep,
-     d.flip, d.has_bias) = (int(v) for v in key[:11])
-    return d
+    return _struct_of(FcLongDesc, key[:11], 11, "long-plan")
 
 
 def long_ext(key: Tuple) -> FcLongExt:
     """``struct fc_long_ext`` of a long-plan key: words 11 to 14 (pad_mode, src_up, tap_dil, out_step) when it has 15 or
     16, the defaults (constant, 1, 1, 1) when it has 11."""
-    e = FcLongExt()
-    e.pad_mode, e.src_up, e.tap_dil, e.out_step = (int(v) for v in (key[11:15] if len(key) >= 15 else LONG_EXT_DEFAULT))
-    return e
+    return _struct_of(FcLongExt, key[11:15] if len(key) >= 15 else LONG_EXT_DEFAULT, 4, "long-plan extension")
 
 
 def long_kind(key: Tuple) -> int:
@@ -441,18 +398,16 @@ def long_kind(key: Tuple) -> int:
     return int(key[15]) if len(key) == 16 else LONG_REAL
 
 
+def _long_args(key: Tuple):
+    return long_desc(key), long_ext(key), long_kind(key)
+
+
 def long_geometry(key: Tuple) -> dict:
     """``fc_long_geometry``: the info words of the plan this key would get, from the descriptor alone (no device)."""
-    lib = load_library()
-    info = (ctypes.c_int64 * 8)()
-    desc = long_desc(key)
-    st = lib.fc_long_geometry_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key), ctypes.byref(info))
-    if st != FC_OK:
-        _raise(lib, st)
-    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+    return _info_words("fc_long_geometry_kind", LONG_INFO_WORDS, *_long_args(key))
 
 
-class LongPlan:
+class LongPlan(_Handle):
     """Owns one ``fc_long_plan`` (long-filter path; immutable after creation): created on the CURRENT HIP device, which the
     caller sets to ``device_index``.  Quacks like ``Plan`` where ``KernelSpectrum`` and ``new_workspace`` look.
 
@@ -460,14 +415,14 @@ class LongPlan:
     as fc_dtype codes (0 float32, 2 float16, 3 bfloat16; default float32).  Spectrum, workspace and bias are float32.
     A complex plan (a key of 16 words, ``complex`` True) takes code 4, complex64, for every tensor and a complex64 bias."""
 
+    _destroy = "fc_long_plan_destroy"
+    _create, _describe = "fc_long_plan_create_kind", staticmethod(_long_args)      # which create call, its descriptor(s)
+
     def __init__(self, key: Tuple, device_index: int = 0):
-        lib = load_library()
-        handle = self._create(lib, key)
-        self._lib, self._h, self.key = lib, handle, key
+        lib, handle = self._open(self._create, *self._describe(key))
+        self.key = key
         self.device_index = int(device_index)
-        info = (ctypes.c_int64 * 8)()
-        lib.fc_long_plan_info(handle, ctypes.byref(info))
-        self.info = {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+        self.info = _info_words("fc_long_plan_info", LONG_INFO_WORDS, handle)
         self.out_len = self.info["out_len"]
         self.spectrum_bytes = self.info["spectrum_bytes"]
         self.workspace_bytes = self.info["workspace_bytes"]
@@ -476,68 +431,34 @@ class LongPlan:
         import torch
         self.dtype = self.weight_dtype = torch.complex64 if self.complex else torch.float32
 
-    @staticmethod
-    def _create(lib, key: Tuple):
-        handle = ctypes.c_void_p()
-        desc = long_desc(key)
-        st = lib.fc_long_plan_create_kind(ctypes.byref(desc), ctypes.byref(long_ext(key)), long_kind(key),
-                                          ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        return handle
-
     def transform_kernel(self, weight_ptr: int, spectrum_ptr: int, workspace_ptr: int, stream: int,
                          weight_dtype: int = 0):
-        st = self._lib.fc_long_transform_kernel_io(self._h, weight_ptr, weight_dtype, spectrum_ptr, workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
+        self._check(self._lib.fc_long_transform_kernel_io(self._h, weight_ptr, weight_dtype, spectrum_ptr, workspace_ptr,
+                                                          stream))
 
     def forward(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int, stream: int,
                 x_dtype: int = 0, y_dtype: int = 0):
-        st = self._lib.fc_long_forward_io(self._h, x_ptr, x_dtype, spectrum_ptr, bias_ptr, y_ptr, y_dtype, workspace_ptr,
-                                          stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
+        self._check(self._lib.fc_long_forward_io(self._h, x_ptr, x_dtype, spectrum_ptr, bias_ptr, y_ptr, y_dtype,
+                                                 workspace_ptr, stream))
 
     def forward_lay(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int,
                     stream: int, x_dtype: int = 0, y_dtype: int = 0, x_layout: int = LONG_NCL, y_layout: int = LONG_NCL):
         """``forward`` with the layouts of x and y named (``fc_long_layout``: LONG_NCL, or LONG_NLC for a tensor that lies
         as a contiguous (B, L, C)).  A channels-last block of 2**31 bytes or more: ``NotImplementedError``."""
-        st = self._lib.fc_long_forward_lay(self._h, x_ptr, x_dtype, x_layout, spectrum_ptr, bias_ptr, y_ptr, y_dtype,
-                                           y_layout, workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.fc_long_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._check(self._lib.fc_long_forward_lay(self._h, x_ptr, x_dtype, x_layout, spectrum_ptr, bias_ptr, y_ptr, y_dtype,
+                                                  y_layout, workspace_ptr, stream))
 
 
 def phases_desc(key: Tuple) -> FcLongPhasesDesc:
     """``struct fc_long_phases_desc`` of a phases-plan key: (batch, cin, cout, groups, L, K, stride, padding,
     output_padding, has_bias)."""
-    if len(key) != 10:
-        raise ValueError(f"a phases-plan key has 10 words, got {len(key)}")
-    d = FcLongPhasesDesc()
-    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.stride, d.padding, d.output_padding,
-     d.has_bias) = (int(v) for v in key)
-    d.reserved = 0
-    return d
+    return _struct_of(FcLongPhasesDesc, key, 10, "phases-plan")
 
 
 def phases_geometry(key: Tuple) -> dict:
     """``fc_long_phases_geometry``: the info words of the phases plan this key would get (no device); ``out_len`` is the
     output length of the transposed convolution."""
-    lib = load_library()
-    info = (ctypes.c_int64 * 8)()
-    st = lib.fc_long_phases_geometry(ctypes.byref(phases_desc(key)), ctypes.byref(info))
-    if st != FC_OK:
-        _raise(lib, st)
-    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+    return _info_words("fc_long_phases_geometry", LONG_INFO_WORDS, phases_desc(key))
 
 
 class LongPhasesPlan(LongPlan):
@@ -546,34 +467,18 @@ class LongPhasesPlan(LongPlan):
     ``forward`` x (B, Cin, L) and y (B, Cout, out_len), contiguous; ``forward_lay`` with LONG_NLC raises
     ``NotImplementedError``."""
 
-    @staticmethod
-    def _create(lib, key: Tuple):
-        handle = ctypes.c_void_p()
-        st = lib.fc_long_phases_plan_create(ctypes.byref(phases_desc(key)), ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        return handle
+    _create, _describe = "fc_long_phases_plan_create", staticmethod(lambda key: (phases_desc(key),))
 
 
 def decim_desc(key: Tuple) -> FcLongDecimDesc:
     """``struct fc_long_decim_desc`` of a decimation-plan key: (batch, cin, cout, groups, L, K, stride, pad_left, pad_right,
     out_keep, flip, has_bias)."""
-    if len(key) != 12:
-        raise ValueError(f"a decimation-plan key has 12 words, got {len(key)}")
-    d = FcLongDecimDesc()
-    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.stride, d.pad_left, d.pad_right, d.out_keep,
-     d.flip, d.has_bias) = (int(v) for v in key)
-    return d
+    return _struct_of(FcLongDecimDesc, key, 12, "decimation-plan")
 
 
 def decim_geometry(key: Tuple) -> dict:
     """``fc_long_decim_geometry``: the info words of the decimation plan this key would get (no device)."""
-    lib = load_library()
-    info = (ctypes.c_int64 * 8)()
-    st = lib.fc_long_decim_geometry(ctypes.byref(decim_desc(key)), ctypes.byref(info))
-    if st != FC_OK:
-        _raise(lib, st)
-    return {name: int(info[i]) for i, name in enumerate(LONG_INFO_WORDS)}
+    return _info_words("fc_long_decim_geometry", LONG_INFO_WORDS, decim_desc(key))
 
 
 class LongDecimPlan(LongPlan):
@@ -581,34 +486,18 @@ class LongDecimPlan(LongPlan):
     (``fc_long_decim_plan_create``): ``transform_kernel`` takes the (Cout, Cin/groups, K) weight where it lies, ``forward``
     a contiguous x (B, Cin, L); ``forward_lay`` takes LONG_NLC for y only (for x: ``NotImplementedError``)."""
 
-    @staticmethod
-    def _create(lib, key: Tuple):
-        handle = ctypes.c_void_p()
-        st = lib.fc_long_decim_plan_create(ctypes.byref(decim_desc(key)), ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        return handle
+    _create, _describe = "fc_long_decim_plan_create", staticmethod(lambda key: (decim_desc(key),))
 
 
 def wgrad_desc(key: Tuple) -> FcLongWgradDesc:
     """``struct fc_long_wgrad_desc`` of a weight-gradient key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_len,
     flip, pad_mode, stride, dilation)."""
-    if len(key) != 13:
-        raise ValueError(f"a weight-gradient key has 13 words, got {len(key)}")
-    d = FcLongWgradDesc()
-    (d.batch, d.in_channels, d.out_channels, d.groups, d.length, d.kernel, d.pad_left, d.pad_right, d.out_len, d.flip,
-     d.pad_mode, d.stride, d.dilation) = (int(v) for v in key)
-    return d
+    return _struct_of(FcLongWgradDesc, key, 13, "weight-gradient")
 
 
 def wgrad_geometry(key: Tuple) -> dict:
     """``fc_long_wgrad_geometry``: the info words of the weight-gradient plan this key would get (no device)."""
-    lib = load_library()
-    info = (ctypes.c_int64 * 8)()
-    st = lib.fc_long_wgrad_geometry(ctypes.byref(wgrad_desc(key)), ctypes.byref(info))
-    if st != FC_OK:
-        _raise(lib, st)
-    return {name: int(info[i]) for i, name in enumerate(LONG_WGRAD_INFO_WORDS)}
+    return _info_words("fc_long_wgrad_geometry", LONG_WGRAD_INFO_WORDS, wgrad_desc(key))
 
 
 def wgrad_check_io(key: Tuple, x_dtype: int = 0, x_layout: int = LONG_NCL, dy_dtype: int = 0, dy_layout: int = LONG_NCL,
@@ -616,52 +505,32 @@ def wgrad_check_io(key: Tuple, x_dtype: int = 0, x_layout: int = LONG_NCL, dy_dt
     """``fc_long_wgrad_check_io``: raises what ``LongWgradPlan.run`` would raise for these element types and layouts, from
     the descriptor alone (no device)."""
     lib = load_library()
-    st = lib.fc_long_wgrad_check_io(ctypes.byref(wgrad_desc(key)), x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype)
-    if st != FC_OK:
-        _raise(lib, st)
+    _check(lib, lib.fc_long_wgrad_check_io(ctypes.byref(wgrad_desc(key)), x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype))
 
 
-class LongWgradPlan:
+class LongWgradPlan(_Handle):
     """Owns one ``fc_long_wgrad_plan`` (immutable after creation; created on the CURRENT HIP device, which the caller sets to
     ``device_index``): dW of the layer a long plan runs, from x and dY where they lie.  Element types (fc_dtype codes 0, 2,
     3) and layouts (LONG_NCL / LONG_NLC) of x and dY and the element type of dW are named per ``run``; the workspace is
     float32.  ``new_workspace`` sizes it by ``workspace_bytes``."""
 
+    _destroy = "fc_long_wgrad_plan_destroy"
+
     def __init__(self, key: Tuple, device_index: int = 0):
-        lib = load_library()
-        handle = ctypes.c_void_p()
-        st = lib.fc_long_wgrad_plan_create(ctypes.byref(wgrad_desc(key)), ctypes.byref(handle))
-        if st != FC_OK:
-            _raise(lib, st)
-        self._lib, self._h, self.key = lib, handle, key
+        _, handle = self._open("fc_long_wgrad_plan_create", wgrad_desc(key))
+        self.key = key
         self.device_index = int(device_index)
-        info = (ctypes.c_int64 * 8)()
-        lib.fc_long_wgrad_plan_info(handle, ctypes.byref(info))
-        self.info = {name: int(info[i]) for i, name in enumerate(LONG_WGRAD_INFO_WORDS)}
+        self.info = _info_words("fc_long_wgrad_plan_info", LONG_WGRAD_INFO_WORDS, handle)
         self.workspace_bytes = self.info["workspace_bytes"]
 
     def run(self, x_ptr: int, dy_ptr: int, dw_ptr: int, workspace_ptr: int, stream: int, x_dtype: int = 0,
             dy_dtype: int = 0, dw_dtype: int = 0, x_layout: int = LONG_NCL, dy_layout: int = LONG_NCL):
-        st = self._lib.fc_long_wgrad(self._h, x_ptr, x_dtype, x_layout, dy_ptr, dy_dtype, dy_layout, dw_ptr, dw_dtype,
-                                     workspace_ptr, stream)
-        if st != FC_OK:
-            _raise(self._lib, st)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.fc_long_wgrad_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._check(self._lib.fc_long_wgrad(self._h, x_ptr, x_dtype, x_layout, dy_ptr, dy_dtype, dy_layout, dw_ptr, dw_dtype,
+                                            workspace_ptr, stream))
 
 
-# the tag of a long-filter key -> the class that owns its plan
-_LONG_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan}
-# ... and of the plans added since (get_plan looks here second)
-_LONG_TAGS_MORE = {"long_decim": LongDecimPlan}
-# ... and of the plans of the same cache that are no forward plans (get_plan looks here third)
-_WGRAD_TAGS = {"long_wgrad": LongWgradPlan}
+# the tag of a long-filter key -> the class that owns its plan (forward plans and the weight-gradient plan: one cache)
+_PLAN_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan, "long_decim": LongDecimPlan, "long_wgrad": LongWgradPlan}
 
 
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
@@ -683,14 +552,13 @@ def lookup_plan(device_index: int, key: Tuple) -> Optional[Plan]:
 
 def get_plan(device_index: int, key: Tuple) -> Plan:
     """Cached plan for (device, descriptor); creates it on the CURRENT HIP device, which the caller
-    must have set to ``device_index`` (``functional._plan_for`` does)."""
+    must have set to ``device_index`` (``functional._cached_plan`` does)."""
     full = (device_index,) + key
     with _plans_lock:
         plan = _plans.get(full)
         if plan is None:
             # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
-            cls = ((_LONG_TAGS.get(key[0]) or _LONG_TAGS_MORE.get(key[0]) or _WGRAD_TAGS.get(key[0]))
-                   if key and isinstance(key[0], str) else None)
+            cls = _PLAN_TAGS.get(key[0]) if key and isinstance(key[0], str) else None
             plan = cls(key[1:], device_index) if cls is not None else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):

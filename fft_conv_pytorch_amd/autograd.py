@@ -410,6 +410,42 @@ def _interleave_lags(du: Tensor, stride: int, taps: int) -> Tensor:
     return du.view(cs // stride, stride, o, kp).permute(2, 0, 3, 1).reshape(o, cs // stride, kp * stride)[..., :taps]
 
 
+def _long_backward_operands(signal: Tensor, grad: Tensor):
+    """What both long backward functions start from -> (dY with a lazy conjugate resolved, read where it lies if the
+    kernels read it channels-last (``F_._long_reads_nlc``) and contiguous otherwise; whether dX is written as a
+    channels-last signal lies; whether the call is complex)."""
+    grad = F_._resolved(grad.detach())
+    if not F_._long_reads_nlc(grad):
+        grad = grad.contiguous()
+    return grad, F_._long_layout(signal) == "nlc", signal.dtype == torch.complex64
+
+
+def _long_grad_bias(grad: Tensor, dtype: torch.dtype) -> Tensor:
+    """db of the long functions: ``_grad_bias`` sums a contiguous dY, so a strided dY is copied for it."""
+    return _grad_bias(grad.contiguous()).to(dtype)
+
+
+def _long_dw_exchanged(rows: Tensor, taps: Tensor, groups: int, pad_left: int, pad_right: int, lags: int, **run) -> Tensor:
+    """The weight gradient as the long primitive with batch and channels exchanged (the docstrings of the two functions
+    below): signal' = ``rows`` (B, C, n) as (C/g, g*B, n), filter' = ``taps`` (B, O, m) as (O, B, m), the first ``lags`` lags
+    kept -> float32 (O, C/g, lags).  ``run``: further keywords of ``F_._long_run``.  torch builds the transposed copies."""
+    B, C, n = rows.shape
+    sig = rows.reshape(B, groups, C // groups, n).permute(2, 1, 0, 3).reshape(C // groups, groups * B, n).contiguous()
+    du = F_._long_run(sig, taps.permute(1, 0, 2).contiguous(), None, pad_left, pad_right, False, lags, groups,
+                      out_dtype=torch.float32, **run)
+    return du.permute(1, 0, 2)
+
+
+def _long_dw_by_phases(rows: Tensor, taps: Tensor, groups: int, front: int, stride: int, lags: int) -> Tensor:
+    """The weight gradient with the phase as a batch-like index: signal' = the ``stride`` decimated rows of ``rows``
+    (B, C, n) read with ``front`` zeros in front (``_phase_rows``), filter' = ``taps`` (B, O, m) as (O, B, m) at tap_dil 1,
+    ceil(lags / stride) lags kept and interleaved into ``lags`` by the permute copy -> float32 (O, C/g, lags)."""
+    kp = -(-lags // stride)
+    sig = _phase_rows(rows, front, stride, taps.shape[2] + kp - 1, groups)
+    du = F_._long_run(sig, taps.permute(1, 0, 2).contiguous(), None, 0, 0, False, kp, groups, out_dtype=torch.float32)
+    return _interleave_lags(du, stride, lags).contiguous()
+
+
 def _fits_plain(key) -> bool:
     """Whether the long plan of this key (``_native.long_desc`` words) fits the 2**24 points of the path: its geometry, asked
     of the library from the descriptor alone (no device)."""
@@ -474,45 +510,32 @@ class FFTLongConvFunction(torch.autograd.Function):
         ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None, int(stride), int(dilation),
                    padding_mode)
         ctx.decim = bool(decim)
-        if decim:
-            return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
-                                F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
-                                channels_last=channels_last, decim=stride)
-        return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal,
-                            F_._long_keep(signal.shape[2], causal, stride), groups, spectrum,
-                            pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
-                            channels_last=channels_last)
+        run = F_._long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, stride,
+                                    dilation, F_._native.PAD_MODES[padding_mode], "phases" if decim else "plain")[1]
+        return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal, groups=groups, spectrum=spectrum,
+                            channels_last=channels_last, **run)
 
     @staticmethod
     def backward(ctx, grad):
         signal, kernel = ctx.saved_tensors
         pad_left, pad_right, flip, g, has_bias, s, d, padding_mode = ctx.cfg
         mode = F_._native.PAD_MODES[padding_mode]
-        grad = F_._resolved(grad.detach())
-        if F_._long_layout(grad) != "nlc" or not F_._long_nlc_enabled():
-            grad = grad.contiguous()
-        x_nlc = F_._long_layout(signal) == "nlc"          # dX is written as the signal lies
-        cx = signal.dtype == torch.complex64
+        grad, x_nlc, cx = _long_backward_operands(signal, grad)
         B, cin, L = signal.shape
         cout, cig, K = kernel.shape
         cog = cout // g
-        dx = dw = db = None
+        dx = dw = None
+        want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.decim and not flip:
             # (non-causal: pad_left == pad_right; the transposed convolution of dY by phases, and dW with the phase as batch)
-            nout, kp = grad.shape[2], -(-K // s)
             if ctx.needs_input_grad[0]:
                 dx = F_._long_transpose_run(grad, kernel.detach().contiguous(), None, s, pad_left,
                                             (L + 2 * pad_left - K) % s, 1, g, "phases")
                 if x_nlc:       # (FFTCONV_LONG_NLC=0 only: otherwise such a signal does not run by phases)
                     dx = F_._as_channels_last(dx)
             if ctx.needs_input_grad[1]:
-                xt = _phase_rows(signal.detach(), pad_left, s, nout + kp - 1, g)
-                dyt = grad.permute(1, 0, 2).contiguous()
-                du = F_._long_run(xt, dyt, None, 0, 0, False, kp, g, out_dtype=torch.float32)
-                dw = _interleave_lags(du, s, K).contiguous().to(kernel.dtype)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = _grad_bias(grad.contiguous()).to(kernel.dtype)
-            return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+                dw = _long_dw_by_phases(signal.detach(), grad, g, pad_left, s, K).to(kernel.dtype)
+            return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 10
         if ctx.needs_input_grad[0]:
             wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
             # zero padding: the gradient of the row itself; another mode: of the padded row, folded below
@@ -543,14 +566,10 @@ class FFTLongConvFunction(torch.autograd.Function):
             # FFTCONV_LONG_WGRAD=1: x and dY where they lie, dW in the weight's own order and dtype
             dw = F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype)
         elif ctx.needs_input_grad[1]:
-            xt = signal.detach().view(B, g, cig, L).permute(2, 1, 0, 3).reshape(cig, g * B, L).contiguous()
-            dyt = grad.permute(1, 0, 2).contiguous()
-            du = F_._long_run(xt, dyt, None, pad_left, pad_right, False, K, g, out_dtype=torch.float32, pad_mode=mode,
-                              tap_dil=s, out_step=d, conj_signal=cx).permute(1, 0, 2)
+            du = _long_dw_exchanged(signal.detach(), grad, g, pad_left, pad_right, K, pad_mode=mode, tap_dil=s, out_step=d,
+                                    conj_signal=cx)
             dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
-        if has_bias and ctx.needs_input_grad[2]:
-            db = _grad_bias(grad.contiguous()).to(kernel.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+        return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 10
 
 
 class FFTLongConvTransposeFunction(torch.autograd.Function):
@@ -593,14 +612,10 @@ class FFTLongConvTransposeFunction(torch.autograd.Function):
     def backward(ctx, grad):
         signal, kernel = ctx.saved_tensors
         s, p, op, d, g, has_bias = ctx.cfg
-        grad = F_._resolved(grad.detach())
-        if F_._long_layout(grad) != "nlc" or not F_._long_nlc_enabled():
-            grad = grad.contiguous()
-        x_nlc = F_._long_layout(signal) == "nlc"          # dX is written as the signal lies
-        cx = signal.dtype == torch.complex64
+        grad, x_nlc, cx = _long_backward_operands(signal, grad)
         B, cin, L = signal.shape
         cog, K = kernel.shape[1], kernel.shape[2]
-        cig, lout = cin // g, grad.shape[2]
+        lout = grad.shape[2]
         dx = dw = db = None
         mode = F_._long_decim_mode()
         kp = -(-K // s)
@@ -615,17 +630,11 @@ class FFTLongConvTransposeFunction(torch.autograd.Function):
             dx = F_._long_run(grad, kernel.detach().contiguous(), None, p, p, False, L, g, tap_dil=d, out_step=s,
                               conj_kernel=cx, channels_last=x_nlc)
         if ctx.needs_input_grad[1] and dw_decim:
-            dyt = _phase_rows(grad, p, s, L + kp - 1, g)
-            xt = signal.detach().permute(1, 0, 2).contiguous()
-            du = F_._long_run(dyt, xt, None, 0, 0, False, kp, g, out_dtype=torch.float32)
-            dw = _interleave_lags(du, s, K).contiguous().to(kernel.dtype)
+            dw = _long_dw_by_phases(grad, signal.detach(), g, p, s, K).to(kernel.dtype)
         elif ctx.needs_input_grad[1]:
-            dyt = grad.reshape(B, g, cog, lout).permute(2, 1, 0, 3).reshape(cog, g * B, lout).contiguous()
-            xt = signal.detach().permute(1, 0, 2).contiguous()
             # (the row must reach lag K - 1 of the last signal sample: max(0, p - op) zeros behind it)
-            du = F_._long_run(dyt, xt, None, p, max(0, p - op), False, K, g, out_dtype=torch.float32, tap_dil=s, out_step=d,
-                              conj_kernel=cx)
-            dw = du.permute(1, 0, 2).contiguous().to(kernel.dtype)
+            dw = _long_dw_exchanged(grad, signal.detach(), g, p, max(0, p - op), K, tap_dil=s, out_step=d,
+                                    conj_kernel=cx).contiguous().to(kernel.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = _grad_bias(grad.contiguous()).to(kernel.dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+            db = _long_grad_bias(grad, kernel.dtype)
+        return (dx, dw, db) + (None,) * 8

@@ -26,19 +26,25 @@ _CONV_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)    
 _CONV_ND_DTYPES = _CONV_DTYPES + (torch.complex64,)                               # ... of their 2-D and 3-D plans
 
 
-def _require_gpu_f32(name: str, t: Tensor, dtype: torch.dtype = torch.float32):
-    """Device + dtype gate of everything handed to the library (``dtype``: the signal's, float32 or float64)."""
+def _require_gpu(name: str, t: Tensor, dtype: torch.dtype, gate: tuple):
+    """Device + dtype gate of everything handed to the library: ``t`` on a ROCm device and of ``dtype`` (the signal's).
+    ``gate``: (the dtypes the op takes, what its TypeError says it takes) -- _CONV_GATE or _LONG_GATE."""
+    allowed, takes = gate
     if not t.is_cuda:
         raise RuntimeError(
             f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
             f"(no CPU fallback). Move the tensor to 'cuda'.")
-    if t.dtype != dtype or dtype not in _CONV_ND_DTYPES:
-        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; signal, kernel and bias must share one of "
-                        f"float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
-                        f"their crossover), float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
-                        f"kernels, which widen the signal as they load it and round the output once as they store it) or, "
-                        f"for 4-D and 5-D tensors, complex64 (1-D complex rows: fft_long_conv; complex128, complex32 and "
-                        f"mixes of real and complex tensors are not taken: convert with .to(torch.complex64))")
+    if t.dtype != dtype or dtype not in allowed:
+        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; {takes}")
+
+
+_CONV_GATE = (_CONV_ND_DTYPES,
+              "signal, kernel and bias must share one of "
+              "float32 (the FFT kernels), float64 (double-precision FFT kernels; a direct float64 kernel below "
+              "their crossover), float16 / bfloat16 (read and written as 16-bit by the float32 FFT "
+              "kernels, which widen the signal as they load it and round the output once as they store it) or, "
+              "for 4-D and 5-D tensors, complex64 (1-D complex rows: fft_long_conv; complex128, complex32 and "
+              "mixes of real and complex tensors are not taken: convert with .to(torch.complex64))")
 
 
 class KernelSpectrum:
@@ -76,6 +82,23 @@ def new_workspace(plan, device) -> Optional[Tensor]:
     if not plan.workspace_bytes:
         return None
     return torch.empty(plan.workspace_bytes // 4, dtype=torch.float32, device=device)
+
+
+def _scratch_and_stream(plan, device):
+    """What every launch on ``plan`` takes last: (the workspace tensor, to be held until the launch is queued; its pointer
+    or None; the handle of the current stream of ``device``)."""
+    ws = new_workspace(plan, device)
+    return ws, ws.data_ptr() if ws is not None else None, torch.cuda.current_stream(device).cuda_stream
+
+
+def _cached_plan(index: int, key: tuple):
+    """The cached plan of (device, key); on a miss it is created with that device current: the library allocates twiddle
+    tables and work lists on the CURRENT HIP device and sizes the work list for its CU count."""
+    plan = _native.lookup_plan(index, key)
+    if plan is None:
+        with torch.cuda.device(index):
+            plan = _native.get_plan(index, key)
+    return plan
 
 
 def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, groups, padding_mode, tile_hint=None,
@@ -121,28 +144,22 @@ def _plan_for(signal: Tensor, kernel: Tensor, bias, stride, padding, dilation, g
            _native.PAD_MODES[padding_mode], bias is not None, int(tile_hint), bool(transposed),
            tuple(int(o) for o in output_padding_), _DTYPE_CODES[dtype])
     # host-side validation is complete; only now touch the device library
-    _require_gpu_f32("signal", signal, dtype)
-    _require_gpu_f32("kernel", kernel, dtype)
+    _require_gpu("signal", signal, dtype, _CONV_GATE)
+    _require_gpu("kernel", kernel, dtype, _CONV_GATE)
     if bias is not None:
-        _require_gpu_f32("bias", bias, dtype)
+        _require_gpu("bias", bias, dtype, _CONV_GATE)
     dev = _same_device(signal=signal, kernel=kernel, bias=bias)
     index = _device_index(dev)
-    plan = _native.lookup_plan(index, key)
-    if plan is None:
-        if (index,) + key in _REFUSED_HALF:
-            raise NotImplementedError(_REFUSED_HALF[(index,) + key])
-        # the library allocates twiddle tables and work lists on the CURRENT HIP device and sizes the work
-        # list for its CU count: create the plan with the tensors' device current
-        try:
-            with torch.cuda.device(index):
-                plan = _native.get_plan(index, key)
-        except NotImplementedError as e:
-            if dtype in _LOW_PRECISION:      # a route that reads y back: remembered, the caller takes the cast path
-                _REFUSED_HALF[(index,) + key] = str(e)
-                while len(_REFUSED_HALF) > 256:
-                    _REFUSED_HALF.popitem(last=False)
-            raise
-    return plan
+    if dtype in _LOW_PRECISION and (index,) + key in _REFUSED_HALF:      # (a refused key has no cached plan)
+        raise NotImplementedError(_REFUSED_HALF[(index,) + key])
+    try:
+        return _cached_plan(index, key)
+    except NotImplementedError as e:
+        if dtype in _LOW_PRECISION:      # a route that reads y back: remembered, the caller takes the cast path
+            _REFUSED_HALF[(index,) + key] = str(e)
+            while len(_REFUSED_HALF) > 256:
+                _REFUSED_HALF.popitem(last=False)
+        raise
 
 
 def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
@@ -154,34 +171,32 @@ def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
     if isinstance(plan, _native.LongPlan) and plan.complex:
         if kernel.dtype != torch.complex64:
             raise TypeError(f"kernel is {kernel.dtype} but the plan is a complex64 long plan")
-        _require_long_dtype("kernel", kernel, kernel.dtype)
+        _require_gpu("kernel", kernel, kernel.dtype, _LONG_GATE)
         kernel = _resolved(kernel.detach()).contiguous()
         io = (_DTYPE_CODES[kernel.dtype],)
     elif isinstance(plan, _native.LongPlan) and kernel.dtype in _LOW_PRECISION:
-        _require_gpu_f32("kernel", kernel, kernel.dtype)
+        _require_gpu("kernel", kernel, kernel.dtype, _CONV_GATE)
         kernel = kernel.detach().contiguous()
         io = (_DTYPE_CODES[kernel.dtype],)
     else:
-        _require_gpu_f32("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype)
+        _require_gpu("kernel", kernel, plan.weight_dtype if kernel.dtype == plan.weight_dtype else plan.dtype, _CONV_GATE)
         # (a complex64 plan: the library reads data_ptr(), a lazy conjugate is resolved first)
         kernel = _resolved(kernel.detach()).to(plan.weight_dtype).contiguous()
     if _device_index(kernel.device) != plan.device_index:
         raise ValueError(f"kernel is on {kernel.device} but the plan was made for cuda:{plan.device_index}")
     with torch.cuda.device(kernel.device):
         buf = torch.empty(max(plan.spectrum_bytes, 16) // 4, dtype=torch.float32, device=kernel.device)
-        ws = new_workspace(plan, kernel.device)      # scratch of this call only
-        stream = torch.cuda.current_stream(kernel.device).cuda_stream
-        plan.transform_kernel(kernel.data_ptr(), buf.data_ptr(), ws.data_ptr() if ws is not None else None, stream, *io)
+        ws, ws_ptr, stream = _scratch_and_stream(plan, kernel.device)      # scratch of this call only
+        plan.transform_kernel(kernel.data_ptr(), buf.data_ptr(), ws_ptr, stream, *io)
     return KernelSpectrum(plan, buf)
 
 
 def _launch_forward(signal: Tensor, spectrum: KernelSpectrum, bias_c: Optional[Tensor]) -> Tensor:
     plan = spectrum.plan
     out = torch.empty((signal.shape[0], plan.key[3]) + plan.out_spatial, dtype=plan.dtype, device=signal.device)
-    ws = new_workspace(plan, signal.device)
-    stream = torch.cuda.current_stream(signal.device).cuda_stream
+    ws, ws_ptr, stream = _scratch_and_stream(plan, signal.device)
     plan.forward(signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                 out.data_ptr(), ws.data_ptr() if ws is not None else None, stream)
+                 out.data_ptr(), ws_ptr, stream)
     return out
 
 
@@ -265,10 +280,10 @@ def _needs_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, spectrum, plan=None):
-    """Shared by the functional and the modules; ``spectrum`` is an optional cached kernel transform and
-    ``plan`` the plan the caller already looked up (and validated) for exactly these arguments."""
-    if isinstance(padding, str) and signal.ndim >= 3:
+def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
+               spectrum, plan):
+    """The body of ``_fft_conv_impl`` and ``_fft_conv_transpose_impl``."""
+    if isinstance(padding, str) and signal.ndim >= 3 and not transposed:
         n = signal.ndim - 2
         pads, drop = _string_padding(padding, kernel, stride, dilation, n)
         out = _fft_conv_impl(signal, kernel, bias, stride, pads, dilation, groups, padding_mode, spectrum, plan)
@@ -280,38 +295,43 @@ def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padd
     if signal.is_complex():
         # (the library reads data_ptr(): a conj or neg bit is resolved here, inside the autograd graph)
         signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
-    if _half_native(signal, kernel, bias):
-        # the kernels read x and write y in the tensors' dtype (float32 arithmetic, the bits of the cast path below)
+    conf = (stride, padding, dilation, groups, padding_mode, None, transposed, output_padding)      # of _plan_for
+    # float16 / bfloat16: the kernels read x and write y in the tensors' dtype (float32 arithmetic, the bits of the cast
+    # path below) -- unless the library refuses the route (it reads y back between launches): then the cast path
+    native16 = _half_native(signal, kernel, bias)
+    if native16 and plan is None:
         try:
-            if plan is None:
-                plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
+            plan = _plan_for(signal, kernel, bias, *conf)
         except NotImplementedError:
-            plan = None       # a refused route (reads y back between launches): the cast path
-        if plan is not None:
-            if _needs_grad(signal, kernel, bias):
-                # 16-bit tensors saved for backward, whose kernels read 16-bit dY and x (autograd.py)
-                from .autograd import FFTConvFunction
-                n = signal.ndim - 2
-                return FFTConvFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
-                                             to_ntuple(dilation, n), groups, padding_mode, spectrum)
-            if spectrum is None or spectrum.plan is not plan:
-                spectrum = transform_kernel(plan, kernel)
-            return _forward_native(signal, spectrum, bias)
-    if signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype and (bias is None or bias.dtype == signal.dtype):
+            native16 = False
+    if (not native16 and signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype
+            and (bias is None or bias.dtype == signal.dtype)):
         # half-precision tensors in, half-precision tensor out; the arithmetic is the fp32 path (one cast pass each way)
-        out = _fft_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride, padding,
-                             dilation, groups, padding_mode, None, None)
+        out = _conv_impl(transposed, signal.float(), kernel.float(), None if bias is None else bias.float(), stride, padding,
+                         output_padding, dilation, groups, padding_mode, None, None)
         return out.to(signal.dtype)
     if _needs_grad(signal, kernel, bias):
-        from .autograd import FFTConvFunction        # backward built from the same kernels (row N1)
+        # backward built from the same kernels (row N1; transposed: differentiable like the reference's op graph); native
+        # 16-bit tensors are saved for backward, whose kernels read 16-bit dY and x (autograd.py)
+        from . import autograd
         n = signal.ndim - 2
-        return FFTConvFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
-                                     to_ntuple(dilation, n), groups, padding_mode, spectrum)
+        if transposed:
+            return autograd.FFTConvTransposeFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
+                                                           to_ntuple(output_padding, n), to_ntuple(dilation, n), groups,
+                                                           spectrum)
+        return autograd.FFTConvFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
+                                              to_ntuple(dilation, n), groups, padding_mode, spectrum)
     if plan is None:
-        plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
+        plan = _plan_for(signal, kernel, bias, *conf)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)   # the reference also re-transforms per call (functional.py:71)
     return _forward_native(signal, spectrum, bias)
+
+
+def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, spectrum, plan=None):
+    """Shared by the functional and the modules; ``spectrum`` is an optional cached kernel transform and
+    ``plan`` the plan the caller already looked up (and validated) for exactly these arguments."""
+    return _conv_impl(False, signal, kernel, bias, stride, padding, 0, dilation, groups, padding_mode, spectrum, plan)
 
 
 def fft_conv_transpose(
@@ -339,41 +359,8 @@ def fft_conv_transpose(
 def _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum,
                              plan=None):
     """Shared by the functional and the transposed modules (``spectrum`` / ``plan``: see ``_fft_conv_impl``)."""
-    if signal.is_complex():
-        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
-    if _half_native(signal, kernel, bias):
-        try:
-            if plan is None:
-                plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, "constant",
-                                 transposed=True, output_padding=output_padding)
-        except NotImplementedError:
-            plan = None
-        if plan is not None:
-            if _needs_grad(signal, kernel, bias):
-                from .autograd import FFTConvTransposeFunction
-                n = signal.ndim - 2
-                return FFTConvTransposeFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
-                                                      to_ntuple(output_padding, n), to_ntuple(dilation, n), groups,
-                                                      spectrum)
-            if spectrum is None or spectrum.plan is not plan:
-                spectrum = transform_kernel(plan, kernel)
-            return _forward_native(signal, spectrum, bias)
-    if signal.dtype in _LOW_PRECISION and kernel.dtype == signal.dtype and (bias is None or bias.dtype == signal.dtype):
-        # half-precision tensors: fp32 arithmetic, one cast pass each way (as the forward op)
-        out = _fft_conv_transpose_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride,
-                                       padding, output_padding, dilation, groups, None, None)
-        return out.to(signal.dtype)
-    if _needs_grad(signal, kernel, bias):
-        from .autograd import FFTConvTransposeFunction     # differentiable like the reference's op graph
-        n = signal.ndim - 2
-        return FFTConvTransposeFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
-                                              to_ntuple(output_padding, n), to_ntuple(dilation, n), groups, spectrum)
-    if plan is None:
-        plan = _plan_for(signal, kernel, bias, stride, padding, dilation, groups, "constant",
-                         transposed=True, output_padding=output_padding)
-    if spectrum is None or spectrum.plan is not plan:
-        spectrum = transform_kernel(plan, kernel)
-    return _forward_native(signal, spectrum, bias)
+    return _conv_impl(True, signal, kernel, bias, stride, padding, output_padding, dilation, groups, "constant", spectrum,
+                      plan)
 
 
 def complex_matmul(a: Tensor, b: Tensor, groups: int = 1) -> Tensor:
@@ -410,12 +397,7 @@ def _long_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int,
         raise ValueError("conjugated reads go with complex64 tensors only")
     elif ext != _native.LONG_EXT_DEFAULT:
         key += ext
-    index = _device_index(signal.device)
-    plan = _native.lookup_plan(index, key)
-    if plan is None:
-        with torch.cuda.device(index):      # the twiddle tables are allocated on the current device
-            plan = _native.get_plan(index, key)
-    return plan
+    return _cached_plan(_device_index(signal.device), key)
 
 
 def _long_decim_plan(signal: Tensor, cout: int, groups: int, taps: int, stride: int, pad_left: int, pad_right: int,
@@ -424,12 +406,7 @@ def _long_decim_plan(signal: Tensor, cout: int, groups: int, taps: int, stride: 
     on the ``stride`` decimated rows.  Its cache key carries a tag of its own."""
     key = ("long_decim", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
            int(stride), int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)))
-    index = _device_index(signal.device)
-    plan = _native.lookup_plan(index, key)
-    if plan is None:
-        with torch.cuda.device(index):
-            plan = _native.get_plan(index, key)
-    return plan
+    return _cached_plan(_device_index(signal.device), key)
 
 
 def _resolved(t: Tensor) -> Tensor:
@@ -456,6 +433,14 @@ def _long_nlc_enabled() -> bool:
     return os.environ.get("FFTCONV_LONG_NLC", "1") != "0"
 
 
+def _long_reads_nlc(t: Tensor) -> bool:
+    """Whether the long-path kernels read this (B, C, L) tensor channels-last where it lies: FFTCONV_LONG_NLC is not 0, it
+    lies that way (``_long_layout`` "nlc") and one batch item's (L, C) block stays below LONG_NLC_MAX_BYTES.  Otherwise
+    the caller takes ``.contiguous()``."""
+    return (_long_layout(t) == "nlc" and _long_nlc_enabled()
+            and t.shape[1] * t.shape[2] * t.element_size() < _native.LONG_NLC_MAX_BYTES)
+
+
 def _as_channels_last(t: Tensor) -> Tensor:
     """(B, C, L) values with strides (L*C, 1, C): one torch copy, none if ``t`` already lies so."""
     return t.transpose(1, 2).contiguous().transpose(1, 2)
@@ -465,7 +450,7 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
               out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None,
               out_dtype: Optional[torch.dtype] = None, *, pad_mode: int = 0, src_up: int = 1, tap_dil: int = 1,
               out_step: int = 1, conj_signal: bool = False, conj_kernel: bool = False,
-              channels_last: bool = False, weight_shape: Optional[tuple] = None, decim: int = 0) -> Tensor:
+              channels_last: bool = False, weight_shape: Optional[tuple] = None, decim: int = 0, plan=None) -> Tensor:
     """The primitive every role of the long-filter path runs (include/fftconv_amd.h "Long filters"), no autograd:
     y[b, o, j] = bias[o] + sum_i sum_k u[o, i, k] * xrow[b, (g, i), out_step*j + tap_dil*k] for j < out_keep (0: all),
     u = the taps in tensor order or flipped, xrow = the signal padded in ``pad_mode`` (a PadMode code), or spread over a
@@ -488,20 +473,21 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
 
     ``decim`` = s >= 2 runs the primitive with out_step = s on a decimation plan (``_long_decim_plan``: real tensors, zero
     padding, dilation 1): the s decimated rows of every input channel against the s phases of the taps, a transform of
-    about nout + ceil(taps / s) points.  The signal is read contiguous; a channels-last result is written as ever."""
+    about nout + ceil(taps / s) points.  The signal is read contiguous; a channels-last result is written as ever.
+
+    ``plan``: the plan of these arguments where the caller holds it already (``_long_forward_plan``,
+    ``_long_transpose_plan``); a phases plan runs here too, on a contiguous signal."""
     signal = _resolved(signal.detach())
     cout, taps = (int(kernel.shape[0]), int(kernel.shape[2])) if weight_shape is None else weight_shape
-    native = _long_nlc_enabled()
-    x_nlc = (native and not decim and _long_layout(signal) == "nlc"
-             and signal.shape[1] * signal.shape[2] * signal.element_size() < _native.LONG_NLC_MAX_BYTES)
+    x_nlc = not decim and _long_reads_nlc(signal)
     if not x_nlc:
         signal = signal.contiguous()
     cx = signal.dtype == torch.complex64
     out_dtype = signal.dtype if out_dtype is None or cx else out_dtype
-    if decim:
+    if plan is None and decim:
         assert (pad_mode, src_up, tap_dil, out_step) == (0, 1, 1, 1) and not cx, "a decimation plan: zero padding, dilation 1, real rows"
         plan = _long_decim_plan(signal, cout, groups, taps, decim, pad_left, pad_right, out_keep, flip, bias is not None)
-    else:
+    elif plan is None:
         plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, flip, out_keep,
                           bias is not None, pad_mode=pad_mode, src_up=src_up, tap_dil=tap_dil, out_step=out_step,
                           conj_signal=conj_signal, conj_kernel=conj_kernel)
@@ -515,17 +501,16 @@ def _long_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], pad_left: 
         bias_c = bias.detach().float().contiguous()
     batch, nout = int(signal.shape[0]), plan.out_len
     with torch.cuda.device(signal.device):
-        y_nlc = bool(channels_last) and native
+        y_nlc = bool(channels_last) and _long_nlc_enabled()
         if y_nlc:
             out = torch.empty((batch, nout, cout), dtype=out_dtype, device=signal.device)
             y_nlc = nout * cout * out.element_size() < _native.LONG_NLC_MAX_BYTES
             out = out.transpose(1, 2) if y_nlc else out.view(batch, cout, nout)
         else:
             out = torch.empty((batch, cout, nout), dtype=out_dtype, device=signal.device)
-        ws = new_workspace(plan, signal.device)
-        stream = torch.cuda.current_stream(signal.device).cuda_stream
+        ws, ws_ptr, stream = _scratch_and_stream(plan, signal.device)
         args = (signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out_dtype])
+                out.data_ptr(), ws_ptr, stream, _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out_dtype])
         if x_nlc or y_nlc:
             plan.forward_lay(*args, _native.LONG_NLC if x_nlc else _native.LONG_NCL,
                              _native.LONG_NLC if y_nlc else _native.LONG_NCL)
@@ -652,12 +637,19 @@ def _long_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, gro
     ``"plain"``    everything else: the long primitive on the whole padded row, its stride skipping outputs.
 
     ``x_layout``: ``_long_layout`` of the signal.  A row that fits no long route raises ``NotImplementedError`` with the count."""
+    return _long_route_numbers(signal_shape, kernel_shape, stride, padding, dilation, groups, causal, padding_mode, dtype,
+                               x_layout)[0]
+
+
+def _long_route_numbers(signal_shape, kernel_shape, stride, padding, dilation, groups, causal, padding_mode, dtype, x_layout):
+    """``_long_route`` of a call from its shapes -> (route, pad_left, pad_right, stride, dilation, PadMode code)."""
     meta = dict(device="meta")
     signal, kernel = torch.empty(tuple(signal_shape), **meta), torch.empty(tuple(kernel_shape), **meta)
     pad_left, pad_right, need = _long_geometry(signal, kernel, None, padding, groups, causal, stride, dilation, padding_mode)
-    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
-    return _long_route_of(int(signal_shape[2]), int(kernel_shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
-                          _native.PAD_MODES[padding_mode], dtype, x_layout)
+    stride, dilation, mode = _long_int("stride", stride), _long_int("dilation", dilation), _native.PAD_MODES[padding_mode]
+    route = _long_route_of(int(signal_shape[2]), int(kernel_shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
+                           mode, dtype, x_layout)
+    return route, pad_left, pad_right, stride, dilation, mode
 
 
 def _long_wgrad_mode() -> bool:
@@ -695,12 +687,9 @@ def _long_wgrad_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=
     ``"exchanged"``  everything else: the route of a call with the switch unset (the forward primitive with batch and
                      channels exchanged on transposed copies; by phases where the forward ran so; ``fft_conv``'s own
                      gradient for a row that hands off)."""
-    meta = dict(device="meta")
-    signal, kernel = torch.empty(tuple(signal_shape), **meta), torch.empty(tuple(kernel_shape), **meta)
-    pad_left, pad_right, need = _long_geometry(signal, kernel, None, padding, groups, causal, stride, dilation, padding_mode)
-    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
-    length, taps, mode = int(signal_shape[2]), int(kernel_shape[2]), _native.PAD_MODES[padding_mode]
-    route = _long_route_of(length, taps, pad_left, pad_right, need, bool(causal), stride, dilation, mode, dtype, x_layout)
+    route, pad_left, pad_right, stride, dilation, mode = _long_route_numbers(
+        signal_shape, kernel_shape, stride, padding, dilation, groups, causal, padding_mode, dtype, x_layout)
+    length, taps = int(signal_shape[2]), int(kernel_shape[2])
     if route == "handoff" or (route == "phases" and not causal):
         return "exchanged"
     nout = _long_keep(length, causal, stride) or (length + pad_left + pad_right - dilation * (taps - 1) - 1) // stride + 1
@@ -715,24 +704,17 @@ def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype:
     each is read where it lies: contiguous, or as the channels-last view ``_long_layout`` recognises (another layout, a
     block of 2**31 bytes or more, FFTCONV_LONG_NLC=0: one torch copy of that tensor).  No transposed operand and no
     flipped copy of the result exists; the float32 result is rounded once as it is stored."""
-    native = _long_nlc_enabled()
     tensors, layouts = [], []
     for t in (signal.detach(), grad.detach()):
-        nlc = (native and _long_layout(t) == "nlc" and t.shape[1] * t.shape[2] * t.element_size() < _native.LONG_NLC_MAX_BYTES)
+        nlc = _long_reads_nlc(t)
         tensors.append(t if nlc else t.contiguous())
         layouts.append(_native.LONG_NLC if nlc else _native.LONG_NCL)
     x, dy = tensors
-    index = _device_index(x.device)
-    pkey = ("long_wgrad",) + tuple(key)
-    plan = _native.lookup_plan(index, pkey)
-    if plan is None:
-        with torch.cuda.device(index):      # the twiddle tables are allocated on the current device
-            plan = _native.get_plan(index, pkey)
+    plan = _cached_plan(_device_index(x.device), ("long_wgrad",) + tuple(key))
     with torch.cuda.device(x.device):
         dw = torch.empty(tuple(wshape), dtype=out_dtype, device=x.device)
-        ws = new_workspace(plan, x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        plan.run(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[x.dtype],
+        ws, ws_ptr, stream = _scratch_and_stream(plan, x.device)
+        plan.run(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws_ptr, stream, _DTYPE_CODES[x.dtype],
                  _DTYPE_CODES[dy.dtype], _DTYPE_CODES[out_dtype], layouts[0], layouts[1])
     return dw
 
@@ -793,20 +775,11 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
 def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum, stride=1, dilation=1,
                         padding_mode="constant", channels_last=False):
     pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal, stride, dilation, padding_mode)
-    stride, dilation = _long_int("stride", stride), _long_int("dilation", dilation)
-    if not isinstance(channels_last, bool):
-        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+    stride, dilation, mode = _long_int("stride", stride), _long_int("dilation", dilation), _native.PAD_MODES[padding_mode]
     route = _long_route_of(int(signal.shape[2]), int(kernel.shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
-                           _native.PAD_MODES[padding_mode], signal.dtype, _long_layout(signal) if _long_nlc_enabled() else "ncl")
-    for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
-        if t is not None:
-            _require_long_dtype(name, t, signal.dtype)
-    _same_device(signal=signal, kernel=kernel, bias=bias)
-    if signal.dtype == torch.complex64:
-        # (the library reads data_ptr(): a conj or neg bit is resolved first, inside the autograd graph)
-        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
-    if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
-        # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out (what a caller would write by hand)
+                           mode, signal.dtype, _long_call_layout(signal, channels_last))
+    signal, kernel, bias, cast = _long_operands(signal, kernel, bias)
+    if cast:      # FFTCONV_HALF_IO=0
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
                                   causal, None, stride, dilation, padding_mode, channels_last)
         return out.to(signal.dtype)          # (keeps the strides)
@@ -823,12 +796,10 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
         from .autograd import FFTLongConvFunction
         return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum,
                                          stride, dilation, padding_mode, channels_last, route == "phases")
-    if route == "phases":
-        return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
-                         spectrum, channels_last=channels_last, decim=stride)
-    return _long_run(signal, kernel, bias, pad_left, pad_right, causal, _long_keep(signal.shape[2], causal, stride), groups,
-                     spectrum, pad_mode=_native.PAD_MODES[padding_mode], tap_dil=dilation, out_step=stride,
-                     channels_last=channels_last)
+    run = _long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, stride, dilation,
+                             mode, route)[1]
+    return _long_run(signal, kernel, bias, pad_left, pad_right, causal, groups=groups, spectrum=spectrum,
+                     channels_last=channels_last, **run)
 
 
 def _long_keep(length: int, causal: bool, stride: int) -> int:
@@ -836,20 +807,53 @@ def _long_keep(length: int, causal: bool, stride: int) -> int:
     return -(-int(length) // stride) if causal else 0
 
 
+def _long_forward_plan(signal: Tensor, wshape, has_bias: bool, pad_left: int, pad_right: int, causal: bool, groups: int,
+                       stride: int, dilation: int, pad_mode: int, route: str):
+    """(plan, the keyword arguments ``_long_run`` takes for it) of a ``fft_long_conv`` call on ``route`` ("plain" |
+    "phases"), from the numbers ``_long_geometry`` returns: the one place that maps a forward route to its plan (the
+    functional, ``FFTLongConvFunction.forward`` and ``FFTLongConv1d``, which caches the spectrum of this plan).  Both plans
+    transform the (Cout, Cin/groups, K) weight ``wshape`` itself."""
+    cout, taps, keep = int(wshape[0]), int(wshape[2]), _long_keep(signal.shape[2], causal, stride)
+    if route == "phases":
+        run = dict(out_keep=keep, decim=stride)
+        plan = _long_decim_plan(signal, cout, groups, taps, stride, pad_left, pad_right, keep, causal, has_bias)
+    else:
+        assert route == "plain", route
+        run = dict(out_keep=keep, pad_mode=pad_mode, tap_dil=dilation, out_step=stride)
+        plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, causal, has_bias=has_bias, **run)
+    run["plan"] = plan
+    return plan, run
+
+
 _LONG_DTYPES = (torch.float32,) + _LOW_PRECISION + (torch.complex64,)
+_LONG_GATE = (_LONG_DTYPES,
+              "fft_long_conv takes signal, kernel and bias "
+              "that share one of float32, float16, bfloat16 or complex64 (float64 runs through fft_conv only; "
+              "complex128, complex32 and mixes of real and complex tensors are not taken: convert with "
+              ".to(torch.complex64))")
 
 
-def _require_long_dtype(name: str, t: Tensor, dtype: torch.dtype):
-    """Device + dtype gate of ``fft_long_conv`` (``dtype``: the signal's)."""
-    if not t.is_cuda:
-        raise RuntimeError(
-            f"fft_conv_pytorch_amd: `{name}` is on {t.device}; this implementation runs on ROCm devices only "
-            f"(no CPU fallback). Move the tensor to 'cuda'.")
-    if t.dtype != dtype or dtype not in _LONG_DTYPES:
-        raise TypeError(f"fft_conv_pytorch_amd: `{name}` has dtype {t.dtype}; fft_long_conv takes signal, kernel and bias "
-                        f"that share one of float32, float16, bfloat16 or complex64 (float64 runs through fft_conv only; "
-                        f"complex128, complex32 and mixes of real and complex tensors are not taken: convert with "
-                        f".to(torch.complex64))")
+def _long_call_layout(signal: Tensor, channels_last) -> str:
+    """The layout a long op routes its signal by: ``_long_layout``, "ncl" for every tensor under FFTCONV_LONG_NLC=0.  (The
+    ``channels_last`` argument is checked here: after the geometry, before the route.)"""
+    if not isinstance(channels_last, bool):
+        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+    layout = _long_layout(signal)
+    return layout if layout == "ncl" or _long_nlc_enabled() else "ncl"
+
+
+def _long_operands(signal: Tensor, kernel: Tensor, bias: Optional[Tensor]):
+    """What the two long ops do between their route and their launch: the device and dtype gate, one device, complex
+    tensors resolved (the library reads data_ptr(): a conj or neg bit is resolved first, inside the autograd graph) ->
+    (signal, kernel, bias, whether the call takes the cast path).  The cast path is FFTCONV_HALF_IO=0: float32 copies in,
+    one rounding pass out (what a caller would write by hand)."""
+    for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
+        if t is not None:
+            _require_gpu(name, t, signal.dtype, _LONG_GATE)
+    _same_device(signal=signal, kernel=kernel, bias=bias)
+    if signal.dtype == torch.complex64:
+        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
+    return signal, kernel, bias, signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias)
 
 
 # ---------------------------------------------------------------------------------- long transposed filters
@@ -969,12 +973,7 @@ def _long_phases_plan(signal: Tensor, cout: int, groups: int, taps: int, stride:
     """Cached phases plan (``fc_long_phases_plan_create``) of a (B, Cin, L) signal; its cache key carries a tag of its own."""
     key = ("long_phases", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
            int(stride), int(padding), int(output_padding), int(bool(has_bias)))
-    index = _device_index(signal.device)
-    plan = _native.lookup_plan(index, key)
-    if plan is None:
-        with torch.cuda.device(index):
-            plan = _native.get_plan(index, key)
-    return plan
+    return _cached_plan(_device_index(signal.device), key)
 
 
 def _long_transposed_weight(kernel: Tensor, groups: int) -> Tensor:
@@ -1019,17 +1018,9 @@ def _long_transpose_run(signal: Tensor, kernel: Tensor, bias: Optional[Tensor], 
         return _as_channels_last(out) if channels_last else out
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel if route == "phases" else _long_transposed_weight(_resolved(kernel), groups))
-    if route == "spread":
-        return _long_run(sig, None, bias, lead, tail, True, lout, groups, spectrum, src_up=stride, tap_dil=dilation,
-                         channels_last=channels_last, weight_shape=(cout, taps))
-    bias_c = None if bias is None else bias.detach().float().contiguous()
-    with torch.cuda.device(sig.device):
-        out = torch.empty((batch, cout, plan.out_len), dtype=sig.dtype, device=sig.device)
-        ws = new_workspace(plan, sig.device)
-        stream = torch.cuda.current_stream(sig.device).cuda_stream
-        plan.forward(sig.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                     out.data_ptr(), ws.data_ptr(), stream, _DTYPE_CODES[sig.dtype], _DTYPE_CODES[sig.dtype])
-    return out
+    # (the numbers are the spread plan's; a phases plan, whose route has a contiguous signal and result, carries its own)
+    return _long_run(sig, None, bias, lead, tail, True, lout, groups, spectrum, src_up=stride, tap_dil=dilation,
+                     channels_last=channels_last and route == "spread", weight_shape=(cout, taps), plan=plan)
 
 
 def fft_long_conv_transpose(signal: Tensor, kernel: Tensor, bias: Tensor = None, stride: int = 1, padding: int = 0,
@@ -1073,18 +1064,10 @@ def _fft_long_conv_transpose_impl(signal, kernel, bias, stride, padding, output_
     """Shared by the functional and ``FFTLongConvTranspose1d`` (``spectrum``: the module's cached one for this call's plan)."""
     stride, padding, output_padding, dilation, lout = _long_transpose_geometry(signal, kernel, bias, stride, padding,
                                                                                output_padding, dilation, groups)
-    if not isinstance(channels_last, bool):
-        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
     route = _long_transpose_route(signal.shape, kernel.shape, stride, padding, output_padding, dilation, groups, signal.dtype,
-                                  (_long_layout(signal) if _long_nlc_enabled() else "ncl", channels_last))
-    for name, t in (("signal", signal), ("kernel", kernel), ("bias", bias)):
-        if t is not None:
-            _require_long_dtype(name, t, signal.dtype)
-    _same_device(signal=signal, kernel=kernel, bias=bias)
-    if signal.dtype == torch.complex64:
-        signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
-    if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
-        # FFTCONV_HALF_IO=0: float32 copies in, one rounding pass out
+                                  (_long_call_layout(signal, channels_last), channels_last))
+    signal, kernel, bias, cast = _long_operands(signal, kernel, bias)
+    if cast:      # FFTCONV_HALF_IO=0
         out = _fft_long_conv_transpose_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), stride,
                                             padding, output_padding, dilation, groups, None, channels_last)
         return out.to(signal.dtype)

@@ -229,21 +229,16 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         # (a complex row never hands off to fft_conv; a lazily conjugated signal gets a plan of the same key)
         if (signal.is_cuda and weight.is_cuda and signal.device == weight.device and signal.dtype == weight.dtype
                 and (signal.dtype == torch.float32 or cx or F_._half_native(signal, weight, bias))):
+            mode = F_._native.PAD_MODES[padding_mode]
             try:
                 route = F_._long_route_of(int(signal.shape[2]), int(weight.shape[2]), pad_left, pad_right, need, self.causal,
-                                          stride, dilation, F_._native.PAD_MODES[padding_mode], signal.dtype,
+                                          stride, dilation, mode, signal.dtype,
                                           F_._long_layout(signal) if F_._long_nlc_enabled() else "ncl")
             except NotImplementedError:
                 route = None      # (the functional raises it again, after its own checks)
-            keep = F_._long_keep(signal.shape[2], self.causal, stride)
-            if route == "phases":      # the decimation plan transforms the weight itself, as the plain plan does
-                plan = F_._long_decim_plan(signal, weight.shape[0], self.groups, weight.shape[2], stride, pad_left, pad_right,
-                                           keep, self.causal, bias is not None)
-                spectrum = self._cached_spectrum(plan)
-            elif route == "plain":
-                plan = F_._long_plan(signal, weight.shape[0], self.groups, weight.shape[2], pad_left, pad_right, self.causal,
-                                     keep, bias is not None, pad_mode=F_._native.PAD_MODES[padding_mode], tap_dil=dilation,
-                                     out_step=stride)
+            if route not in (None, "handoff"):      # the plan the functional will run: both routes transform the weight itself
+                plan = F_._long_forward_plan(signal, weight.shape, bias is not None, pad_left, pad_right, self.causal,
+                                             self.groups, stride, dilation, mode, route)[0]
                 spectrum = self._cached_spectrum(plan)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
                                       padding_mode, self.channels_last)

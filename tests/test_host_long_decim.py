@@ -359,8 +359,9 @@ def test_new_entry_points_only_and_abi_7():
     # nothing that existed changes
     assert ctypes.sizeof(_native.FcLongDesc) == 80 and ctypes.sizeof(_native.FcLongExt) == 16
     assert ctypes.sizeof(_native.FcLongPhasesDesc) == 80 and ctypes.sizeof(_native.FcLongDecimDesc) == 88
-    assert _native._LONG_TAGS == {"long": _native.LongPlan, "long_phases": _native.LongPhasesPlan}
-    assert _native._LONG_TAGS_MORE == {"long_decim": _native.LongDecimPlan} and issubclass(_native.LongDecimPlan, _native.LongPlan)
+    assert _native._PLAN_TAGS == {"long": _native.LongPlan, "long_phases": _native.LongPhasesPlan, "long_decim": _native.LongDecimPlan,
+                                  "long_wgrad": _native.LongWgradPlan}
+    assert issubclass(_native.LongDecimPlan, _native.LongPlan)
 
 
 def test_the_switch_is_read_per_call(monkeypatch):

@@ -86,7 +86,8 @@ def test_new_entry_points_only_and_abi_7():
         _native.long_desc((1,) * 12)
     with pytest.raises(ValueError):
         _native.phases_desc((1,) * 11)
-    assert _native._LONG_TAGS == {"long": _native.LongPlan, "long_phases": _native.LongPhasesPlan}
+    assert _native._PLAN_TAGS == {"long": _native.LongPlan, "long_phases": _native.LongPhasesPlan, "long_decim": _native.LongDecimPlan,
+                                  "long_wgrad": _native.LongWgradPlan}
     assert issubclass(_native.LongPhasesPlan, _native.LongPlan)
 
 

@@ -107,7 +107,8 @@ def test_new_entry_points_only_and_abi_7():
     # nothing that existed changes
     assert ctypes.sizeof(_native.FcLongDesc) == 80 and ctypes.sizeof(_native.FcLongExt) == 16
     assert ctypes.sizeof(_native.FcLongPhasesDesc) == 80 and ctypes.sizeof(_native.FcLongDecimDesc) == 88
-    assert _native._WGRAD_TAGS == {"long_wgrad": _native.LongWgradPlan}
+    assert _native._PLAN_TAGS == {"long": _native.LongPlan, "long_phases": _native.LongPhasesPlan, "long_decim": _native.LongDecimPlan,
+                                  "long_wgrad": _native.LongWgradPlan}
 
 
 # ------------------------------------------------------------------------------------------------ geometry

@@ -89,19 +89,16 @@ struct fc_plan {
   size_t spectrum_bytes, workspace_bytes;
   size_t ws_a, ws_b;          // element counts of the two workspace regions (F32_ND: fc::f2, F64_FFT_ND: double2)
 
-  struct {                    // ---- F32_1D
+  struct F1d {                // ---- F32_1D
     size_t lds_conv, lds_spec;
     int pers_nb;                // batch items per workgroup of the batch-sharing kernel (0 = not used)
-    int pers_nb_choice;         // planner's pick for this plan (0 = general kernel)
     int pers_grid, pers_items;
-    int chunk_launches;         // general kernel launched once per input chunk, later chunks add into y (see plan_1d)
+    int chunk_launches;         // general kernel launched once per input chunk, later chunks add into y (host_1d.cpp decide_route)
     int wide;                   // > 8 input channels per group on the batch-sharing work list (conv1d_wide.hpp)
     int dense;                  // >= 16 channels per group on both sides: spectra through HBM + MFMA contraction (dense1d.hpp)
     int dense_mslab;            // rows (batch x tiles) per slab of that pipeline's workspace
     int dense_cus;              // CUs of the plan's device (grid of its persistent GEMM)
-    size_t dense_pers_bytes;    // its kernel spectrum before the bin-major re-layout (scratch of the kernel transform)
     int nseg, seg_taps;         // the kernel runs in nseg segments of seg_taps taps (1 = whole kernel)
-    int64_t kd_plan;            // dilated extent the tiles are planned for (of one segment)
     size_t seg_spectrum_bytes;  // kernel-spectrum bytes of one segment
     int diag;                   // depthwise (groups == Cin == Cout, multiple of 8): 8-channel blocks, per-channel mix
     int bd_gs;                  // groups of 2 or 4 channels regrouped into block-diagonal 8 x 8 blocks (0 = off)

@@ -100,7 +100,7 @@ def fusedc_nb(r, B, cog, G=1):
 
 
 def tail_split(r, B, nb, G=1):
-    """plan_1d_persistent's tail split: full items (nb batch items that share a tile and an out-chunk) in excess of whole
+    """build_work_list's tail split: full items (nb batch items that share a tile and an out-chunk) in excess of whole
     residency rounds are halved when they fill at most half a round.  True if pers_items is what that rule gives for one
     of the possible slot counts (CUs x resident workgroups per CU) and a split happened."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -361,7 +361,7 @@ def tile_step(c, r, ax):
     if kind in ("f32_1d", "f64_fft_1d"):
         T, n = r["T"], r["ntiles"]
         if r.get("nseg", 1) > 1:
-            # segments of taps (plan_1d_inner): 1024 // d + 1 taps each, an extent of at most 1025 samples per segment
+            # segments of taps (decide_route): 1024 // d + 1 taps each, an extent of at most 1025 samples per segment
             d = c.tup(c.d)[ax]
             seg_taps = min(max(1, 1024 // d + 1), c.k[ax])
             assert -(-c.k[ax] // seg_taps) == r["nseg"], (seg_taps, r)

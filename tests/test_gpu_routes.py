@@ -261,3 +261,27 @@ def test_route(route, monkeypatch):
         except AssertionError as e:
             raise AssertionError(f"{route.name} / {c.ident()}: {e}") from None
     print(f"\nroute {route.name}: {len(route.cases)} cases, worst element-wise error {worst:.2e}")
+
+
+def test_refused_block_layout_leaves_no_trace(monkeypatch):
+    """Depthwise channels and groups of 2 channels are first planned as 8 x 8 blocks for the batch-sharing kernel.  Under
+    FFTCONV_PERS=0 that kernel refuses them, and the plan must be the one the plain grouped layout gets when the blocks
+    are never tried (FFTCONV_DIAG=0): same route, layout and sizes, and a forward that matches float64."""
+    from fft_conv_pytorch_amd import functional as fc
+    for c in (ru.Case(2, 16, 16, (4096,), (33,), g=16, note="depthwise"), ru.Case(2, 16, 16, (4096,), (33,), g=8, note="gs2")):
+        gen = torch.Generator(device=DEV).manual_seed(11)
+        x = torch.randn((c.B, c.cin) + c.size, generator=gen, device=DEV)
+        w = torch.randn(c.wshape, generator=gen, device=DEV) / math.sqrt(math.prod(c.wshape[1:]))
+        b = torch.randn(c.cout, generator=gen, device=DEV)
+        seen = []
+        for env in ({"FFTCONV_PERS": "0"}, {"FFTCONV_PERS": "0", "FFTCONV_DIAG": "0"}):
+            _knobs(monkeypatch, env)
+            plan = fc._plan_for(x, w, b, 1, 0, 1, c.g, "constant")
+            seen.append((plan.route, plan.layout, plan.tile, plan.spectrum_bytes, plan.workspace_bytes, plan.out_spatial,
+                         plan.debug_grid()))
+        assert seen[0] == seen[1], f"{c.ident()}: a refused block layout shows in the plan: {seen}"
+        assert ru.GENERAL_1D(seen[0][0]), f"{c.ident()}: {seen[0][0]}"
+        _knobs(monkeypatch, {"FFTCONV_PERS": "0"})
+        plan = fc._plan_for(x, w, b, 1, 0, 1, c.g, "constant")
+        err = _check(c, [[]], _plan_forward(plan, x, fc.transform_kernel(plan, w), b), x, w, b, ru.TOL32, "forward")
+        print(f"\n{c.ident()}: element-wise error {err:.2e}")

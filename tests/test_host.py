@@ -108,6 +108,37 @@ def test_scripts_and_entry_points_compile():
         py_compile.compile(os.path.join(ROOT, name), doraise=True)
 
 
+def test_route_dump_inputs_are_seeded_capped_and_cover_the_planner():
+    """scripts/route_dump.py compares two builds of the planner: its inputs must be the same in both runs, keep every work
+    list under its cap, and reach every value the sweep is meant to draw."""
+    import importlib.util
+    from tests import route_util as ru
+    spec = importlib.util.spec_from_file_location("route_dump", os.path.join(ROOT, "scripts", "route_dump.py"))
+    rd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rd)
+    sweep = rd.sweep(600, 20)
+    assert sweep == rd.sweep(600, 20) and sweep[:50] != rd.sweep(50, 21)
+    for kw in sweep:
+        (L,), (K,), (s,), (p,), (d,), (op,) = (kw[n] for n in ("spatial", "kernel", "stride", "padding", "dilation", "output_padding"))
+        assert rd.items_bound(kw["batch"], kw["cout"], L, K, s, p, d, kw["transposed"], op, kw["tile_hint"]) <= rd.MAX_ITEMS
+        assert 64 <= L <= 1 << 20 and 1 <= K <= 6000 and 1 <= s <= 3 and 1 <= d <= 8
+        assert kw["cin"] % kw["groups"] == 0 and kw["cout"] % kw["groups"] == 0 and max(kw["cin"], kw["cout"]) <= 64 * kw["groups"]
+    seen = {n: {kw[n] for kw in sweep} for n in ("batch", "mode", "tile_hint", "dtype", "transposed")}
+    assert seen == {"batch": {1, 2, 3, 4, 5, 8, 32, 64}, "mode": {0, 1, 2, 3}, "tile_hint": {0, 256, 1024, 2048, 4096},
+                    "dtype": {rd.F32, rd.F16}, "transposed": {False, True}}
+    assert any(kw["transposed"] and kw["output_padding"][0] for kw in sweep)
+    depthwise = {kw["groups"] for kw in sweep if kw["groups"] == kw["cin"] == kw["cout"] and kw["groups"] >= 5}
+    assert depthwise >= {5, 7, 8, 16, 24}
+    for gs in (2, 4):      # groups of gs channels that fill 8 x 8 blocks, and ones that do not
+        fills = {kw["groups"] % (8 // gs) == 0 for kw in sweep if kw["cin"] == kw["cout"] == gs * kw["groups"]}
+        assert fills == {True, False}
+    assert rd.KNOB_STATES[0] == {} and len(rd.KNOB_STATES) == 11 and all(len(e) == 1 for e in rd.KNOB_STATES[1:])
+    cases = rd.route_cases()
+    assert len(cases) == sum(1 for r in ru.ROUTES for c in r.cases if c.nd == 1 and not c.f64)
+    sizes = {kw["spatial"] for kw, _ in cases}
+    assert all(c.size in sizes for c in ru.TAIL_SPLIT_CASES)
+
+
 # ---------------------------------------------------------------- round 2: device handling, caches, signatures
 class _FakeCudaTensor:
     """Just enough of a tensor for functional._plan_for's host-side checks (no device is touched)."""

@@ -102,6 +102,8 @@ LONG_REAL, LONG_COMPLEX, LONG_CONJ_SIGNAL, LONG_CONJ_TAPS = 0, 1, 2, 4
 # enum fc_long_layout: how x and y of fc_long_forward_lay lie, (B, C, L) contiguous or (B, L, C) contiguous
 LONG_NCL, LONG_NLC = 0, 1
 LONG_NLC_MAX_BYTES = 1 << 31      # one batch item's (L, C) block of a channels-last tensor stays below this
+# enum fc_nd_layout: how x and y of fc_forward_lay lie, (B, C, *spatial) contiguous or channels-last (B, *spatial, C)
+ND_PLANAR, ND_CHANNELS_LAST = 0, 1
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 # ... of a weight-gradient plan: no spectrum; the taps of a row and how many of their lags are transformed
 LONG_WGRAD_INFO_WORDS = ("N1", "N2", "taps", "lags", "workspace_bytes", "slabs", "out_block", "slab_pairs")
@@ -157,6 +159,8 @@ def _signatures() -> dict:
         "fc_long_wgrad_plan_destroy": (None, (vp,)),
         "fc_long_wgrad_plan_info": (i32, (vp, i64x8)),
         "fc_long_wgrad": (i32, (vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp)),
+        "fc_plan_takes_layout": (i32, (vp, i32, i32)),
+        "fc_forward_lay": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
     }
 
 
@@ -337,6 +341,7 @@ class Plan(_Handle):
         self.layout = tuple(int(v) for v in lay)
         self.route = read_route(lib, handle)
         self._stamps = None
+        self._takes: dict = {}      # (x_layout, y_layout) -> answer of fc_plan_takes_layout (the plan is immutable)
 
     def signature(self) -> Tuple:
         """(spectrum bytes, layout words) -- equal on two plans iff a kernel spectrum is interchangeable."""
@@ -353,6 +358,29 @@ class Plan(_Handle):
         else:
             st = self._lib.fc_forward(self._h, x_ptr, w_hat_ptr, bias_ptr, y_ptr, workspace_ptr, stream)
         self._check(st)
+
+    def takes_layout(self, x_layout: int, y_layout: int) -> Optional[str]:
+        """``fc_plan_takes_layout`` (no device call): None when this plan's launches take x / y in these ``fc_nd_layout``
+        layouts, else the library's sentence on why not.  An unknown code raises ``ValueError``."""
+        key = (int(x_layout), int(y_layout))
+        if key not in self._takes:
+            st = self._lib.fc_plan_takes_layout(self._h, *key)
+            if st not in (FC_OK, FC_ERR_UNSUPPORTED):
+                self._check(st)
+            self._takes[key] = None if st == FC_OK else self._lib.fc_last_error().decode("utf-8", "replace")
+        return self._takes[key]
+
+    def forward_lay(self, x_ptr: int, w_hat_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: Optional[int],
+                    stream: int, x_layout: int = ND_PLANAR, y_layout: int = ND_PLANAR):
+        """``forward`` with the layouts of x and y named (``fc_nd_layout``: ND_PLANAR, or ND_CHANNELS_LAST for a tensor that
+        lies as a contiguous (B, *spatial, C)).  A plan that does not take a layout: ``NotImplementedError``.  There is no
+        stamped launch with layouts (``fc_forward_stamped`` takes none): while a profiling buffer is set
+        (``debug_set_stamps``) this raises ``NotImplementedError`` instead of recording nothing."""
+        if self._stamps is not None:
+            raise NotImplementedError("a stamped (profiling) forward reads and writes contiguous tensors only: unset "
+                                      "channels_last / FFTCONV_ND_CL for the profiled call")
+        self._check(self._lib.fc_forward_lay(self._h, x_ptr, x_layout, w_hat_ptr, bias_ptr, y_ptr, y_layout, workspace_ptr,
+                                             stream))
 
     def debug_set_stamps(self, ptr: Optional[int]):
         """Profiling hook of this Python handle (the native plan stays immutable): while set, ``forward``

@@ -82,20 +82,26 @@ def _pad_adjoint(dxp: Tensor, in_spatial, padding, mode: str) -> Tensor:
     return t.contiguous()
 
 
-def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode) -> Tensor:
+def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode,
+                channels_last: bool = False, native: bool = False) -> Tensor:
+    """dX of ``fft_conv``.  ``native``: a ``grad`` that lies channels-last is read where it lies
+    (``F_._forward_native``); ``channels_last``: dX lies that way (the layout of the signal) -- written so by the
+    transposed plan's last pass where the padding is zeros, one torch copy behind ``_pad_adjoint`` otherwise."""
+    lay = (channels_last, native)
     if grad.dtype in F_._LOW_PRECISION:
         if padding_mode == "constant":
             try:
-                return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode)
+                return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode, *lay)
             except NotImplementedError:
                 pass      # a route the 16-bit transposed plan refuses (it would round dX between launches)
         # float32 dX (and the padding adjoint in float32), rounded once; the widened dY lives for this call only
         return _grad_input_plan(grad.float(), weight.float(), in_spatial, stride, padding, dilation, groups,
-                                padding_mode).to(grad.dtype)
-    return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode)
+                                padding_mode, *lay).to(grad.dtype)
+    return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode, *lay)
 
 
-def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode) -> Tensor:
+def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode,
+                     channels_last: bool = False, native: bool = False) -> Tensor:
     n = grad.ndim - 2
     key = ("dx", tuple(grad.shape), tuple(weight.shape), tuple(in_spatial), stride, padding, dilation, groups, padding_mode,
            grad.device, grad.dtype)
@@ -113,10 +119,11 @@ def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, 
         if len(_BWD_PLANS) > 256:
             _BWD_PLANS.clear()
         _BWD_PLANS[key] = plan
-    dx = F_._forward_native(grad, F_.transform_kernel(plan, weight), None)
     if padding_mode == "constant":
-        return dx
-    return _pad_adjoint(dx, in_spatial, padding, padding_mode)
+        return F_._forward_lay(grad, F_.transform_kernel(plan, weight), None, channels_last, native)
+    dx = _pad_adjoint(F_._forward_lay(grad, F_.transform_kernel(plan, weight), None, False, native), in_spatial, padding,
+                      padding_mode)
+    return F_._to_channels_last(dx) if channels_last else dx
 
 
 def _permuted_copy(view: Tensor, shape, conj: bool) -> Tensor:
@@ -294,6 +301,22 @@ def _grad_weight(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, gro
     return _grad_weight_db(x, grad, wshape, stride, padding, dilation, groups, padding_mode, conj=conj)[0]
 
 
+def _backward_operands(signal: Tensor, grad: Tensor, need_contiguous: bool, channels_last: bool):
+    """What both N-d backward functions start from.  ``channels_last``: the keyword of the forward call.  -> (dY as the
+    dX launch takes it: where it lies if it lies channels-last and the call takes layouts natively
+    (``F_._nd_cl_native``), a contiguous copy otherwise; the contiguous dY that dW and db read -- one copy serves both,
+    None when neither is wanted; whether dX gets the channels-last layout of the signal: in a call with the keyword, or
+    under FFTCONV_ND_CL=1; whether the call takes layouts natively).  A call without the keyword and without the knob
+    gets what it always got: one contiguous dY for all three gradients, a contiguous dX."""
+    grad = F_._resolved(grad)
+    nd = grad.ndim >= 4
+    native = nd and F_._nd_cl_native(channels_last)
+    follows = nd and (channels_last or native)
+    lies_cl = native and F_._nd_layout(grad) == "cl"
+    gradc = grad.contiguous() if (need_contiguous or not lies_cl) else None
+    return (grad if lies_cl else gradc), gradc, follows and F_._nd_layout(signal) == "cl", native
+
+
 def _grad_bias(grad: Tensor) -> Tensor:
     """Sum of dY over batch and space; a 16-bit dY is summed as the float32 cast path sums it (widened first)."""
     if grad.dtype in F_._LOW_PRECISION:
@@ -306,22 +329,25 @@ class FFTConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, signal: Tensor, kernel: Tensor, bias: Optional[Tensor], stride: Tuple[int, ...],
-                padding: Tuple[int, ...], dilation: Tuple[int, ...], groups: int, padding_mode: str, spectrum):
+                padding: Tuple[int, ...], dilation: Tuple[int, ...], groups: int, padding_mode: str, spectrum,
+                channels_last: bool = False):
         plan = F_._plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
         if spectrum is None or spectrum.plan is not plan:
             spectrum = F_.transform_kernel(plan, kernel)
         ctx.save_for_backward(signal, kernel)
         ctx.conf = (stride, padding, dilation, groups, padding_mode, bias is not None)
-        return F_._forward_native(signal, spectrum, bias)
+        ctx.channels_last = bool(channels_last)
+        return F_._forward_lay(signal, spectrum, bias, channels_last)
 
     @staticmethod
     def backward(ctx, grad: Tensor):
         signal, kernel = ctx.saved_tensors
         stride, padding, dilation, groups, padding_mode, has_bias = ctx.conf
-        grad = F_._resolved(grad).contiguous()
+        want_db = has_bias and ctx.needs_input_grad[2]
+        # (dW and db keep contiguous operands -- their bits stay; dX reads a channels-last dY where it lies)
+        grad_x, grad, dx_cl, native = _backward_operands(signal, grad, ctx.needs_input_grad[1] or want_db, ctx.channels_last)
         cx = signal.is_complex()      # PyTorch's convention: dW from conj(x), dX against conj(W)
         d_signal = d_kernel = d_bias = None
-        want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             # (db rides the weight-gradient launch where the kernel offers it; dW goes first: widened 16-bit operands of a
             # weight-gradient route are freed before dX is allocated)
@@ -329,13 +355,13 @@ class FFTConvFunction(torch.autograd.Function):
                                                groups, padding_mode, want_db, conj="x" if cx else "")
             d_kernel = d_kernel.to(kernel.dtype)     # (16-bit: the float32 sum rounded once)
         if ctx.needs_input_grad[0]:
-            d_signal = _grad_input(grad, kernel.detach().conj() if cx else kernel.detach(), tuple(signal.shape[2:]), stride,
-                                   padding, dilation, groups, padding_mode)
+            d_signal = _grad_input(grad_x, kernel.detach().conj() if cx else kernel.detach(), tuple(signal.shape[2:]), stride,
+                                   padding, dilation, groups, padding_mode, dx_cl, native)
         if want_db and d_bias is None:
             d_bias = _grad_bias(grad)
         if d_bias is not None:
             d_bias = d_bias.to(kernel.dtype)
-        return d_signal, d_kernel, d_bias, None, None, None, None, None, None
+        return d_signal, d_kernel, d_bias, None, None, None, None, None, None, None
 
 
 class FFTConvTransposeFunction(torch.autograd.Function):
@@ -353,32 +379,37 @@ class FFTConvTransposeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, signal: Tensor, kernel: Tensor, bias: Optional[Tensor], stride: Tuple[int, ...],
                 padding: Tuple[int, ...], output_padding: Tuple[int, ...], dilation: Tuple[int, ...], groups: int,
-                spectrum):
+                spectrum, channels_last: bool = False):
         plan = F_._plan_for(signal, kernel, bias, stride, padding, dilation, groups, "constant",
                             transposed=True, output_padding=output_padding)
         if spectrum is None or spectrum.plan is not plan:
             spectrum = F_.transform_kernel(plan, kernel)
         ctx.save_for_backward(signal, kernel)
         ctx.conf = (stride, padding, dilation, groups, bias is not None)
-        return F_._forward_native(signal, spectrum, bias)
+        ctx.channels_last = bool(channels_last)
+        return F_._forward_lay(signal, spectrum, bias, channels_last)
 
     @staticmethod
     def backward(ctx, grad: Tensor):
         signal, kernel = ctx.saved_tensors
         stride, padding, dilation, groups, has_bias = ctx.conf
-        grad = F_._resolved(grad).contiguous()
+        want_db = has_bias and ctx.needs_input_grad[2]
+        grad_x, grad, dx_cl, native = _backward_operands(signal, grad, ctx.needs_input_grad[1] or want_db, ctx.channels_last)
         cx = signal.is_complex()      # (as in FFTConvFunction: x is the "output gradient" operand of dW here)
-        n = grad.ndim - 2
+        n = grad_x.ndim - 2      # (``grad``, the contiguous dY of dW and db, is None when neither is wanted)
         in_spatial = tuple(signal.shape[2:])
         # extent of conv(dY, W) per axis: >= the input extent; larger only when output_padding >= stride
-        conv_sp = tuple((grad.shape[2 + i] + 2 * padding[i] - dilation[i] * (kernel.shape[2 + i] - 1) - 1) // stride[i] + 1
+        conv_sp = tuple((grad_x.shape[2 + i] + 2 * padding[i] - dilation[i] * (kernel.shape[2 + i] - 1) - 1) // stride[i] + 1
                         for i in range(n))
         d_signal = d_kernel = d_bias = None
         if ctx.needs_input_grad[0]:
-            dx = F_.fft_conv(grad, kernel.detach().conj() if cx else kernel.detach(), None, stride=stride, padding=padding,
-                             dilation=dilation, groups=groups)
+            # (under create_graph this call becomes FFTConvFunction.apply, which carries the keyword but not ``native``: a
+            #  channels-last dY of a planar signal is then copied -- the same values)
+            dx = F_._fft_conv_impl(grad_x, kernel.detach().conj() if cx else kernel.detach(), None, stride, padding, dilation,
+                                   groups, "constant", None, channels_last=dx_cl, native=native)
             if conv_sp != in_spatial:
-                dx = dx[(slice(None), slice(None)) + tuple(slice(0, s) for s in in_spatial)].contiguous()
+                dx = dx[(slice(None), slice(None)) + tuple(slice(0, s) for s in in_spatial)]
+                dx = F_._to_channels_last(dx) if dx_cl else dx.contiguous()
             d_signal = dx
         if ctx.needs_input_grad[1]:
             xg = signal.detach()
@@ -390,9 +421,9 @@ class FFTConvTransposeFunction(torch.autograd.Function):
             d_kernel = _grad_weight(grad, xg, tuple(kernel.shape), stride, padding, dilation, groups, "constant",
                                     conj="grad" if cx else "")
             d_kernel = d_kernel.to(kernel.dtype)
-        if has_bias and ctx.needs_input_grad[2]:
+        if want_db:
             d_bias = _grad_bias(grad).to(kernel.dtype)
-        return d_signal, d_kernel, d_bias, None, None, None, None, None, None
+        return d_signal, d_kernel, d_bias, None, None, None, None, None, None, None
 
 
 def _phase_rows(t: Tensor, front: int, stride: int, rows: int, groups: int) -> Tensor:

@@ -444,6 +444,44 @@ int fc_forward_stamped(const fc_plan* plan, const float* x, const void* w_hat, c
   return fail(FC_ERR_INVALID, "internal: unknown plan kind");
 }
 
+// ---- channels-last tensors of the 2-D / 3-D plans (host_nd.cpp, plan_takes_layout_nd)
+static int check_layouts(const fc_plan* plan, int x_layout, int y_layout) {
+  if (!plan) return fail(FC_ERR_INVALID, "null argument");
+  for (int lay : {x_layout, y_layout})
+    if (lay != FC_ND_PLANAR && lay != FC_ND_CHANNELS_LAST)
+      return fail(FC_ERR_INVALID, "unknown layout code %d (fc_nd_layout: 0 planar, 1 channels-last)", lay);
+  if (x_layout == FC_ND_PLANAR && y_layout == FC_ND_PLANAR) return FC_OK;
+  switch (plan->kind) {
+    case PlanKind::F32_ND:
+    case PlanKind::C64_ND: return plan_takes_layout_nd(*plan, x_layout == FC_ND_CHANNELS_LAST, y_layout == FC_ND_CHANNELS_LAST);
+    case PlanKind::F32_1D:
+    case PlanKind::F64_FFT_1D:
+    case PlanKind::F64_FFT_LONG:
+      return fail(FC_ERR_UNSUPPORTED, "a 1-D plan reads and writes contiguous (B, C, L) tensors only (channels-last rows: "
+                  "fc_long_forward_lay)");
+    case PlanKind::F64_DIRECT:
+    case PlanKind::F64_FFT_ND:
+      return fail(FC_ERR_UNSUPPORTED, "a float64 plan reads and writes contiguous (B, C, *spatial) tensors only");
+  }
+  return fail(FC_ERR_INVALID, "internal: unknown plan kind");
+}
+
+int fc_plan_takes_layout(const fc_plan* plan, int x_layout, int y_layout) { return check_layouts(plan, x_layout, y_layout); }
+
+int fc_forward_lay(const fc_plan* plan, const float* x, int x_layout, const void* w_hat, const float* bias, float* y,
+                   int y_layout, void* workspace, void* hip_stream) {
+  const int rc = check_layouts(plan, x_layout, y_layout);
+  if (rc != FC_OK) return rc;
+  if (x_layout == FC_ND_PLANAR && y_layout == FC_ND_PLANAR) return fc_forward(plan, x, w_hat, bias, y, workspace, hip_stream);
+  if (!x || !w_hat || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward_stamped)
+  const fc_plan& p = *plan;
+  if (p.d.has_bias && !bias) return fail(FC_ERR_INVALID, "plan was created with has_bias=1 but bias is NULL");
+  if (p.workspace_bytes && !workspace) return fail(FC_ERR_INVALID, "workspace is NULL but %zu bytes are required", p.workspace_bytes);
+  return forward_nd(p, x, w_hat, bias, y, workspace, (hipStream_t)hip_stream, nullptr, x_layout == FC_ND_CHANNELS_LAST,
+                    y_layout == FC_ND_CHANNELS_LAST);
+}
+
 // ---- N-d weight gradient (the reference's dW comes from autograd through its
 // rfftn / einsum / irfftn graph, tests/test_functional.py:111-117): dW[(g,o)][i][k] = sum_b sum_t dY[b][(g,o)][t] *
 // Xp[b][(g,i)][t*s + k*d] is the convolution of signal' = X with batch and channels exchanged against kernel' = dY,

@@ -47,6 +47,8 @@ struct TileImpl {
   hipError_t (*planes_fwd)(const PlaneFwdArgs& a, int n_images, hipStream_t st);
   hipError_t (*colz)(const ColZArgs& a, hipStream_t st);
   hipError_t (*planes_inv)(const PlaneInvArgs& a, int n_images, hipStream_t st);
+  // channels per workgroup of the channels-last builds of rows_r2c / rows_c2r (launches with cl_C > 0); 0 when not built
+  int rows_cl_nch;
 };
 
 #define FC_DECLARE_TILE(P, S) const TileImpl* get_tile_P##P##_S##S();

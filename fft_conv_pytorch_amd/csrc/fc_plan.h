@@ -161,8 +161,11 @@ int transform_kernel_f64_long(const fc_plan& p, const float* weight, void* w_hat
 
 int forward_1d(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
                hipStream_t st, void* stamps);
+// (x_cl / y_cl: the signal / the output lies channels-last -- only where plan_takes_layout_nd says so)
 int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
-               hipStream_t st, void* stamps);
+               hipStream_t st, void* stamps, bool x_cl = false, bool y_cl = false);
+// FC_OK when the kernels of an N-d plan read x (x_cl) / write y (y_cl) channels-last, else FC_ERR_UNSUPPORTED with text
+int plan_takes_layout_nd(const fc_plan& p, bool x_cl, bool y_cl);
 int forward_f64_direct(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
                        hipStream_t st, void* stamps);
 int forward_f64_1d(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,

@@ -442,12 +442,57 @@ static fc::ColZArgs colz_args(const fc_plan& p, const fc::f2* src, const void* w
   return cz;
 }
 
+// Channels-last tensors: the first and the last pass of a separable float32 / float16 / bfloat16 plan have
+// builds that read the signal / write the output where element (b, ch, z, y, x) lies at ((((b*SZ + z)*SY + y)*SX + x)*C + ch).
+// The layout never enters the plan: this only says whether this plan's launches can take it.
+int plan_takes_layout_nd(const fc_plan& p, bool x_cl, bool y_cl) {
+  if (!x_cl && !y_cl) return FC_OK;
+  if (p.kind == PlanKind::C64_ND)
+    return fail(FC_ERR_UNSUPPORTED, "a complex64 plan reads and writes contiguous (B, C, *spatial) tensors only: the complex row "
+                "passes have no channels-last build");
+  if (p.kind != PlanKind::F32_ND)
+    return fail(FC_ERR_UNSUPPORTED, "channels-last tensors are taken by float32 / float16 / bfloat16 2-D and 3-D plans only "
+                "(float64 plans and 1-D plans read and write contiguous tensors; 1-D rows: fc_long_forward_lay)");
+  if (p.fnd.swap)
+    return fail(FC_ERR_UNSUPPORTED, "a weight-gradient plan (fc_wgrad_nd_plan_create) reads x and dY and writes dW contiguous");
+  if (p.fnd.nseg_total > 1)
+    return fail(FC_ERR_UNSUPPORTED, "a plan that runs its kernel in %d segments of taps has no channels-last launch (the "
+                "accumulating store of the last pass is contiguous-only)", p.fnd.nseg_total);
+  if (p.fnd.planes == 1)
+    return fail(FC_ERR_UNSUPPORTED, "the plane-major 3-D pipeline (planes_fwd / planes_inv) has no channels-last build");
+  if (!p.fnd.tx->rows_cl_nch)
+    return fail(FC_ERR_UNSUPPORTED, "the %d-point row transform has no channels-last build (its workgroups hold fewer than "
+                "four sequences; 64 ... 1024 points have one)", p.fnd.tx->T);
+  const int nd = p.nd;
+  const int64_t es = p.io == FC_F32 ? 4 : 2;
+  if (x_cl) {
+    // rows_r2c_cl: byte offsets from the start of x (buffer loads over the whole tensor)
+    int64_t bytes = es * p.d.batch * p.d.in_channels;
+    for (int i = 0; i < nd; ++i) bytes *= p.d.spatial[i];
+    if (bytes >= 0xFFFFFFFFLL)
+      return fail(FC_ERR_UNSUPPORTED, "a channels-last signal of %lld bytes exceeds the 4 GiB its 32-bit offsets span", (long long)bytes);
+  }
+  if (y_cl) {
+    // rows_c2r_cl: byte offsets from a workgroup's first output row over its (at most 16) rows, the x positions of an
+    // overlap-save tile past the row's end included (they get bit 31 and must not wrap)
+    const int64_t span = (16 * p.out_sp[nd - 1] + p.Lf[nd - 1] + 2 * 4096) * p.d.out_channels * es;
+    if (span >= ((int64_t)1 << 31))
+      return fail(FC_ERR_UNSUPPORTED, "channels-last output rows of %lld x %lld samples exceed the 2 GiB a workgroup's block of "
+                  "rows may span", (long long)p.out_sp[nd - 1], (long long)p.d.out_channels);
+  }
+  return FC_OK;
+}
+
 int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float* bias, float* y, void* workspace,
-               hipStream_t st, void* stamps) {
+               hipStream_t st, void* stamps, bool x_cl, bool y_cl) {
   fc::f2* wsA = (fc::f2*)workspace;
   fc::f2* wsB = wsA + p.ws_a;
   const int nd = p.nd;
   const int B = (int)p.d.batch, Ci = (int)p.d.in_channels, Co = (int)p.d.out_channels;
+  if (x_cl || y_cl) {
+    const int rc = plan_takes_layout_nd(p, x_cl, y_cl);
+    if (rc != FC_OK) return rc;
+  }
   if (p.fnd.planes == 1) {
     // x (B,Ci,Z,Y,X) -> S[(b,ci)][zp][col] -> O[(b,co)][z_out][col] -> y; col = fx*64 + fy
     fc::PlaneFwdArgs f1{};
@@ -484,6 +529,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
     r.src_bytes = bytes < 0xFFFFFFFFull ? (unsigned)bytes : 0u;
   }
   r.rowmajor = p.fnd.planes == 2;
+  if (x_cl) r.cl_C = Ci;
   const int64_t dil[3] = {p.d.dilation[0], p.d.dilation[1], p.d.dilation[2]};
   if (p.fnd.swap) {   // signal = x (B, g*Cig, *S) read as (i, (g, b)): image (i*g + gi)*B + b sits at b*(g*Cig) + gi*Cig + i
     r.im.on = 1; r.im.n1 = (int)p.fnd.sw_g; r.im.n2 = (int)p.fnd.sw_B; r.im.s0 = 1; r.im.s1 = p.fnd.sw_Cig; r.im.s2 = p.fnd.sw_g * p.fnd.sw_Cig;
@@ -502,6 +548,7 @@ int forward_nd(const fc_plan& p, const float* x, const void* w_hat, const float*
   f.wfx = p.fnd.Fx; f.wty = nd == 3 ? p.fnd.tm->T : 1; f.wrep = nd == 3 ? p.fnd.nyt : 1; f.wncol = f.wfx * f.wty;
   o.NV = p.Lf[nd - 1]; o.stride = p.ostride[nd - 1]; o.Xo = (int)p.out_sp[nd - 1];
   o.NY = (int)p.out_sp[nd - 2]; o.NYa = o.NY;
+  if (y_cl) o.cl_C = Co;
   if (p.fnd.swap) {   // output (i, (g, o), *k) written as dW ((g, o), i, *k): image i*(g*Cog) + o_all goes to o_all*Cig + i
     o.im.on = 1; o.im.n1 = 1; o.im.n2 = (int)(p.fnd.sw_g * p.fnd.sw_Cog); o.im.s0 = 1; o.im.s1 = 0; o.im.s2 = p.fnd.sw_Cig;
   }

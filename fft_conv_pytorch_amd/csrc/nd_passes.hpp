@@ -127,6 +127,9 @@ struct RowsR2CArgs {
   int tox, toy, toz;
   int io = 0;            // element type of a signal source (fc_dtype: 0 float32, 2 float16, 3 bfloat16; src_bytes counts
                          // its bytes); kernel taps are float32
+  int cl_C = 0;          // > 0: the signal lies channels-last, (B, [Z,] Y, X, C) contiguous with C = cl_C channels, and the
+                         // launch runs rows_r2c_cl_kernel (NA == B * cl_C; signal source, identity image map)
+  FastDiv d_chb{};       // ... its blocks of channels per batch item (filled by the dispatcher)
 };
 
 template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
@@ -443,6 +446,9 @@ struct RowsC2RArgs {
   int rowmajor;          // src [(a*NC + c)][NY][nxt*Fx] (see RowsR2CArgs)
   int accum;             // add into dst instead of storing, no bias (later segments of taps, host_nd.cpp)
   int io = 0;            // element type of dst (fc_dtype: 0 float32, 2 float16, 3 bfloat16; float32 with accum)
+  int cl_C = 0;          // > 0: dst lies channels-last, (B, [Zo,] Yo, Xo, Cout) contiguous with Cout = cl_C, and the launch
+                         // runs rows_c2r_cl_kernel (NA == B * cl_C; no accum, identity image map)
+  FastDiv d_chb{};       // ... its blocks of channels per batch item (filled by the dispatcher)
 };
 
 template <int P, int S, int NSEQ, int NT, int IO = IO_F32>
@@ -796,6 +802,292 @@ __global__ __launch_bounds__(NT) void rows_c2c_inv_kernel(const RowsC2RArgs a) {
     const int idx = t / a.stride;
     const unsigned xo = (unsigned)idx * 8u, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
     buf_store_f32x2(mk2(v[k].x + b.x, v[k].y + b.y), orr, (r0 + xo) | bad | badx, 0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------ channels-last rows
+// Siblings of rows_r2c_kernel / rows_c2r_kernel for a signal / an output that lies channels-last: element (b, ch, z, y, x)
+// at ((((b*SZ + z)*SY + y)*SX + x)*C + ch) samples (a.cl_C = C).  The workspace side keeps its layout, and so does the
+// arithmetic: rows 2s and 2s+1 of one (image, plane) still share one complex transform (y0 stays even), every sequence
+// runs the register FFT of the planar build on the same samples, so every value has the planar build's bits.  What changes:
+//   * a workgroup takes NCH neighbouring channels x NSEQ/NCH row pairs of one (batch item, plane, x tile) instead of NSEQ
+//     row pairs of one channel: sequence slot s holds channel s % NCH of pair s / NCH;
+//   * on the tensor side lanes run over the channels fastest (NCH * ES contiguous bytes per x position) and the samples
+//     are staged through the sequences' LDS slots: written there by the lane that loaded them (r2c, as the padding-mode
+//     path of rows_r2c_kernel stages its own), or read from there by the lane that stores them (c2r; LDS is free after
+//     the last exchange of the inverse);
+//   * with the transposed workspace layout a channel plane gets 2*NSEQ/NCH rows per bin column (planar: 2*NSEQ).  The NCH
+//     planes of a workgroup lie an image apart, so the workspace is addressed with plain 64-bit pointers (loads from a
+//     clamped address, so that none sits in a branch), not through one buffer resource.
+// No kernel-tap source, no image map (weight-gradient plans), no accumulating store: the host never asks
+// (fc_plan_takes_layout).  The tensor side uses 32-bit byte offsets: the host checks the sizes.
+template <int P, int S, int NSEQ, int NT, int NCH, int IO = IO_F32>
+__global__ __launch_bounds__(NT) void rows_r2c_cl_kernel(const RowsR2CArgs a) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
+  const auto* src = io_ptr<IO>(a.src);
+  constexpr int T = G::T;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  constexpr int RB = 2 * NSEQ, NPAIR = NSEQ / NCH, RBC = 2 * NPAIR;      // rows per workgroup over all channels / per channel
+  static_assert(NT == NSEQ * G::TS, "one thread slot per sequence point group");
+  static_assert(NCH >= 1 && NSEQ % NCH == 0, "whole row pairs per channel");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned q;
+  const int yb = (int)fdivmod(blockIdx.x, a.d_nyb, &q);
+  const int xt = (int)fdivmod(q, a.d_nxt, &q);
+  const int c = (int)fdivmod(q, a.d_nc, &q);
+  const int ch0 = (int)fdivmod(q, a.d_chb, &q) * NCH;
+  const int b = (int)q;
+  const int C = a.cl_C;
+  const int y0 = yb * RBC;
+  const int x0 = xt * a.Vx;              // padded position of this tile's first sample
+
+  f2 v[P];
+  {
+    // loading role of this thread: channel lch of pair lpair, samples lt + N2*n1 -- lanes over the channels fastest
+    const int lch = tid % NCH, lpair = (tid / NCH) % NPAIR, lt = tid / (NCH * NPAIR);
+    const typename Io<IO>::T* rows[2];
+    bool ok[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int yp = y0 + 2 * lpair + h;
+      const int ys = yp < a.NY ? axis_src(a.my, yp + a.shy) : -1;
+      const int zs = axis_src(a.mz, c + a.shz);       // (2-D plans carry an identity map here)
+      ok[h] = ys >= 0 && zs >= 0 && ch0 + lch < C;
+      rows[h] = src + ((((size_t)b * a.SZ + (ok[h] ? zs : 0)) * a.SY + (ok[h] ? ys : 0)) * a.SX) * C + (ok[h] ? ch0 + lch : 0);
+    }
+    f2* col = lds + (lpair * NCH + lch) * LSEQP + lt;
+    if (a.mx.up == 1 && a.mx.mode == PAD_CONSTANT && a.src_bytes != 0) {
+      // fast path (zero padding): unrolled buffer loads over the whole source tensor; a sample outside
+      // its row gets an out-of-range offset and reads as zero -- no masks live across the loads
+      const BufRsrc sg = make_rsrc(a.src, a.src_bytes);
+      const unsigned ro0 = ok[0] ? (unsigned)((rows[0] - src) * ES) : 0xFFFFFFFFu;
+      const unsigned ro1 = ok[1] ? (unsigned)((rows[1] - src) * ES) : 0xFFFFFFFFu;
+      const unsigned xstep = (unsigned)C * ES;
+      f2 st[P];
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) {
+        const int xs = x0 + G::N2 * n1 + lt + a.shx - a.mx.pad;
+        const bool in = (unsigned)xs < (unsigned)a.mx.size;
+        st[n1].x = io.load(sg, (in && ok[0]) ? ro0 + (unsigned)xs * xstep : 0xFFFFFFFFu, 0);
+        st[n1].y = io.load(sg, (in && ok[1]) ? ro1 + (unsigned)xs * xstep : 0xFFFFFFFFu, 0);
+      }
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) col[n1 * G::RS] = st[n1];
+    } else {
+#pragma unroll 1
+      for (int n1 = 0; n1 < P; ++n1) {
+        const int xs = axis_src(a.mx, x0 + G::N2 * n1 + lt + a.shx);
+        const float v0 = (ok[0] && xs >= 0) ? io.in(rows[0][(size_t)xs * C]) : 0.f;
+        const float v1 = (ok[1] && xs >= 0) ? io.in(rows[1][(size_t)xs * C]) : 0.f;
+        col[n1 * G::RS] = mk2(v0, v1);
+      }
+    }
+    __syncthreads();
+    const f2* own = lds + sq * LSEQP + tseq;
+#pragma unroll
+    for (int n1 = 0; n1 < P; ++n1) v[n1] = own[n1 * G::RS];
+    seq_sync<G>();      // (the first pass writes where other lanes of the sequence have just read)
+  }
+  {
+    // odd-frequency transform of the real axis (see rows_r2c_kernel)
+    float ws, wc;
+    sincospif(-(float)tseq / (float)T, &ws, &wc);
+    const f2 wt = mk2(wc, ws);
+    static_for<0, P>([&](auto ic) {
+      constexpr int n1 = decltype(ic)::value;
+      constexpr float c = (float)cospi_q(n1, P), s = (float)sinpi_q(n1, P);
+      v[n1] = cmul(v[n1], cmul_const(wt, c, -s));
+    });
+  }
+  fwd_from_regs<G>(v, lds + sq * LSEQP, tseq, true, twA, twB);
+  __syncthreads();
+  // unpack the two real spectra of every pair (partner of bin k: T-1-k) and store
+  constexpr int FXC = T / 2;                       // == a.Fx
+  static_assert(NT % RB == 0 && (FXC * RB) % NT == 0, "whole rounds, fixed row per thread");
+  if (a.rowmajor) {
+    // rows as they are: lanes over 64 neighbouring bins of one row of one channel, both rows of a pair from the same two
+    // LDS reads
+    constexpr int NIT = FXC * NSEQ / NT;
+    static_assert(NIT * NT == FXC * NSEQ, "whole rounds");
+    const size_t pitch = (size_t)a.nxt * a.Fx;
+    f2 zf[NIT], zg[NIT];
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+      const int idx = u * NT + tid, s = idx / FXC, fx = idx % FXC;
+      const f2* z = lds + s * LSEQP;
+      zf[u] = z[G::nat(fx)];
+      zg[u] = z[G::nat(T - 1 - fx)];
+    }
+#pragma unroll
+    for (int u = 0; u < NIT; ++u) {
+      const int idx = u * NT + tid, s = idx / FXC, fx = idx % FXC;
+      const int ch = ch0 + s % NCH, row = y0 + 2 * (s / NCH);
+      const f2 ev = mk2(0.5f * (zf[u].x + zg[u].x), 0.5f * (zf[u].y - zg[u].y));
+      const f2 ov = mk2(0.5f * (zf[u].y + zg[u].y), 0.5f * (zg[u].x - zf[u].x));
+      f2* out = a.dst + ((((size_t)b * C + ch) * a.NC + c) * a.NY + row) * pitch + (size_t)xt * a.Fx + fx;
+      if (ch < C && row < a.NY) out[0] = ev;
+      if (ch < C && row + 1 < a.NY) out[pitch] = ov;
+    }
+    return;
+  }
+  // transposed: the RBC rows of a channel contiguous per bin (a thread keeps its channel and row over all rounds and steps
+  // NT/RB bins per round; every LDS read of the thread is requested before the first value is used)
+  constexpr int NROUND = FXC * RB / NT, FSTEP = NT / RB;
+  const int r = tid % RBC, ch = ch0 + (tid / RBC) % NCH, fx0 = tid / RB;
+  const f2* z = lds + ((r >> 1) * NCH + (tid / RBC) % NCH) * LSEQP;
+  f2 zf[NROUND], zg[NROUND];
+#pragma unroll
+  for (int u = 0; u < NROUND; ++u) {
+    const int fx = fx0 + u * FSTEP;
+    zf[u] = z[G::nat(fx)];
+    zg[u] = z[G::nat(T - 1 - fx)];
+  }
+  const bool odd = (r & 1) != 0;
+  const bool live = ch < C && y0 + r < a.NY;
+  f2* out = a.dst + ((((size_t)b * C + (live ? ch : 0)) * a.NC + c) * a.nxt + xt) * a.Fx * a.NYa + y0 + r;
+#pragma unroll
+  for (int u = 0; u < NROUND; ++u) {
+    const int fx = fx0 + u * FSTEP;
+    const f2 ev = mk2(0.5f * (zf[u].x + zg[u].x), 0.5f * (zf[u].y - zg[u].y));
+    const f2 ov = mk2(0.5f * (zf[u].y + zg[u].y), 0.5f * (zg[u].x - zf[u].x));
+    if (live) out[(size_t)fx * a.NYa] = odd ? ov : ev;
+  }
+}
+
+template <int P, int S, int NSEQ, int NT, int NCH, int IO = IO_F32>
+__global__ __launch_bounds__(NT) void rows_c2r_cl_kernel(const RowsC2RArgs a) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.io);
+  constexpr unsigned ES = Io<IO>::B;
+  constexpr int T = G::T;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  constexpr int NPAIR = NSEQ / NCH, RBC = 2 * NPAIR;
+  static_assert(NT == NSEQ * G::TS, "thread count");
+  static_assert(NCH >= 1 && NSEQ % NCH == 0, "whole row pairs per channel");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned q;
+  const int yb = (int)fdivmod(blockIdx.x, a.d_nyb, &q);
+  const int xt = (int)fdivmod(q, a.d_nxt, &q);
+  const int c = (int)fdivmod(q, a.d_nc, &q);
+  const int ch0 = (int)fdivmod(q, a.d_chb, &q) * NCH;
+  const int b = (int)q;
+  const int C = a.cl_C;
+  const int y0 = yb * RBC;
+  const int x0 = xt * a.Vx;                    // first stride-1 sample of this tile
+  const int xlim = min(a.Vx, a.NV - x0);       // valid samples the tile contributes
+  f2 wtw[P];
+  passA_twiddle_fetch<G>(wtw, tseq, twA);      // requested first: lands while the spectra are loaded
+  {
+    // rows 2s (-> real part) and 2s+1 (-> imaginary part) of a channel share one complex inverse FFT (see rows_c2r_kernel).
+    // ALL of a thread's bins are requested before the first is consumed: a row that does not exist is read from the start
+    // of the workspace instead (no load in a branch) and replaced by zero afterwards.
+    constexpr int FXC = T / 2;                           // == a.Fx
+    constexpr int TOTAL = FXC * NSEQ;
+    constexpr int NITER = (TOTAL + NT - 1) / NT;
+    const size_t pitch = (size_t)a.nxt * a.Fx;
+    f2 ya[NITER], yb2[NITER];
+#pragma unroll
+    for (int u = 0; u < NITER; ++u) {
+      const int idx = u * NT + tid;
+      int pair, chl, fx;
+      size_t step;      // from a row to the next one of its plane
+      const f2* p;
+      if (a.rowmajor) {   // lanes over neighbouring bins of one row
+        const int s = idx / FXC;
+        fx = idx % FXC; pair = s / NCH; chl = s % NCH; step = pitch;
+        p = a.src + ((((size_t)b * C + ch0 + chl) * a.NC + c) * a.NY + y0 + 2 * pair) * pitch + (size_t)xt * a.Fx + fx;
+      } else {            // lanes over the RBC rows of a channel, then the channels, then the bins
+        const int s = idx % NSEQ;
+        fx = idx / NSEQ; pair = s % NPAIR; chl = s / NPAIR; step = 1;
+        p = a.src + (((((size_t)b * C + ch0 + chl) * a.NC + c) * a.nxt + xt) * a.Fx + fx) * a.NYa + y0 + 2 * pair;
+      }
+      const bool one = idx < TOTAL && ch0 + chl < C && y0 + 2 * pair < a.NY;
+      const bool both = one && y0 + 2 * pair + 1 < a.NY;
+      const f2 r0 = *(one ? p : a.src), r1 = *(both ? p + step : a.src);
+      ya[u] = one ? r0 : mk2(0.f, 0.f);
+      yb2[u] = both ? r1 : mk2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < NITER; ++u) {
+      const int idx = u * NT + tid;
+      if (idx < TOTAL) {
+        int slot, fx;
+        if (a.rowmajor) { slot = idx / FXC; fx = idx % FXC; }
+        else { const int s = idx % NSEQ; slot = (s % NPAIR) * NCH + s / NPAIR; fx = idx / NSEQ; }
+        f2* z = lds + slot * LSEQP;
+        z[G::nat(fx)] = mk2(ya[u].x - yb2[u].y, ya[u].y + yb2[u].x);
+        z[G::nat(T - 1 - fx)] = mk2(ya[u].x + yb2[u].y, yb2[u].x - ya[u].y);
+      }
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  const int j = inv_to_regs_pre<G>(v, wtw, lds + sq * LSEQP, tseq, true, twB);
+  {
+    // undo the half-bin shift: sample n = nbase + P*k is turned back by e^{+i*pi*n/T}
+    const int nb0 = (tseq >> G::LGS) + P * P * j;
+    float ws, wc;
+    sincospif((float)nb0 / (float)T, &ws, &wc);
+    const f2 wb = mk2(wc, ws);
+    static_for<0, P>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      constexpr float c = (float)cospi_q(k, G::N2), s = (float)sinpi_q(k, G::N2);
+      v[k] = cmul(v[k], cmul_const(wb, c, s));
+    });
+  }
+  // the samples of every sequence in their order, in its LDS slot (free once every lane has read its last exchange)
+  __syncthreads();
+  {
+    f2* zs = lds + sq * LSEQP + (tseq >> G::LGS) + P * P * j;
+#pragma unroll
+    for (int k = 0; k < P; ++k) zs[P * k] = v[k];
+  }
+  __syncthreads();
+  // storing role of this thread: channel lch of pair lpair, samples lt + TS*k -- lanes over the channels fastest
+  const int lch = tid % NCH, lpair = (tid / NCH) % NPAIR, lt = tid / (NCH * NPAIR);
+  const int ch = ch0 + lch, ya_row = y0 + 2 * lpair;
+  // (declared arrived before the guarded stores, as in rows_c2r_kernel)
+  float bv = (a.bias && ch < C) ? a.bias[ch] : 0.f;
+  asm volatile("" : "+v"(bv));
+  // buffer stores relative to this workgroup's RBC output rows, from its first channel on (32-bit offsets; samples past the
+  // valid window, decimated away, in rows past NY or of channels past C get bit 31 instead of a branch)
+  const int rows_here = min(RBC, a.NY - y0);
+  auto* orow = io_ptr<IO>(a.dst) + ((((size_t)b * a.NC + c) * a.NY + y0) * a.Xo) * C + ch0;
+  const BufRsrc orr = make_rsrc(orow, (unsigned)(((size_t)rows_here * a.Xo * C - ch0) * ES));
+  const bool has0 = ch < C && ya_row < a.NY, has1 = ch < C && ya_row + 1 < a.NY;
+  const unsigned xstep = (unsigned)C * ES;
+  const unsigned r0 = (unsigned)(2 * lpair * a.Xo) * xstep + (unsigned)lch * ES, r1 = r0 + (unsigned)a.Xo * xstep;
+  const unsigned bad0 = has0 ? 0u : 0x80000000u, bad1 = has1 ? 0u : 0x80000000u;
+  const f2* zl = lds + (lpair * NCH + lch) * LSEQP + lt;
+  f2 val[P];
+#pragma unroll
+  for (int k = 0; k < P; ++k) val[k] = zl[G::TS * k];
+  if (a.stride == 1) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      const int n = lt + G::TS * k;
+      const unsigned xo = (unsigned)(x0 + n) * xstep, badx = n < xlim ? 0u : 0x80000000u;
+      io.store(val[k].x + bv, orr, (r0 + xo) | bad0 | badx, 0);
+      io.store(val[k].y + bv, orr, (r1 + xo) | bad1 | badx, 0);
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    const int n = lt + G::TS * k;
+    const int t = x0 + n;
+    const int idx = t / a.stride;
+    const unsigned xo = (unsigned)idx * xstep, badx = (n < xlim && idx * a.stride == t) ? 0u : 0x80000000u;
+    io.store(val[k].x + bv, orr, (r0 + xo) | bad0 | badx, 0);
+    io.store(val[k].y + bv, orr, (r1 + xo) | bad1 | badx, 0);
   }
 }
 

@@ -62,8 +62,50 @@ hipError_t launch_rows(const Args& a, hipStream_t st) {
   b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
   return launch_kernel<Kernel>((long long)a.NA * a.NC * a.nxt * nyb, kNT_R, (size_t)kNSEQ_R * kLSEQP * sizeof(float2), st, b);
 }
+// Channels-last builds of the two (a.cl_C > 0; rows_r2c_cl_kernel / rows_c2r_cl_kernel): NCH neighbouring channels x
+// kNSEQ_R / NCH row pairs per workgroup.  NCH per tile geometry and element size is the one that measured fastest for
+// the two launches together (2, 4 and 8 at T = 64, 128, 512; 2 and 4 at 1024): 4, but 2 for 16-bit samples
+// at T <= 128.  The 2048- and 4096-point tiles hold two and one sequence and have no such build.  -DFC_CL_NCH=<n> forces
+// one count (the A/B builds of that sweep, scripts/nd_channels_last_nch.py).
+template <int IO>
+constexpr int nch_cl() {
+  if (kNSEQ_R < 4) return 0;
+#ifdef FC_CL_NCH
+  return FC_CL_NCH < kNSEQ_R ? FC_CL_NCH : kNSEQ_R;
+#else
+  return (IO == IO_H16 && kT <= 128) ? 2 : 4;
+#endif
+}
+constexpr int kNchCl = nch_cl<IO_F32>();      // (TileImpl: nonzero where the builds exist)
+template <template <int, int> class K, class Args, int IO>
+hipError_t launch_rows_cl_io(const Args& a, hipStream_t st) {
+  constexpr int NCH = nch_cl<IO>();
+  if constexpr (NCH == 0) {      // (no build, nothing instantiated)
+    return hipErrorInvalidValue;
+  } else {
+    constexpr int RBC = 2 * kNSEQ_R / NCH;
+    if (a.cl_C <= 0 || a.NA % a.cl_C) return hipErrorInvalidValue;
+    const long long nyb = (a.NY + RBC - 1) / RBC, nchb = (a.cl_C + NCH - 1) / NCH;
+    Args b = a;
+    b.d_nyb = make_fastdiv((unsigned)nyb); b.d_nxt = make_fastdiv((unsigned)a.nxt); b.d_nc = make_fastdiv((unsigned)a.NC);
+    b.d_chb = make_fastdiv((unsigned)nchb);
+    const long long grid = (long long)(a.NA / a.cl_C) * nchb * a.NC * a.nxt * nyb;
+    return launch_kernel<K<IO, NCH>::kernel>(grid, kNT_R, (size_t)kNSEQ_R * kLSEQP * sizeof(float2), st, b);
+  }
+}
+template <template <int, int> class K, class Args>
+hipError_t launch_rows_cl(const Args& a, hipStream_t st) {
+  return with_io(a.io, [&](auto io) { return launch_rows_cl_io<K, Args, FC_IO(io)>(a, st); });
+}
+template <int IO, int NCH> struct R2CCl { static constexpr auto kernel = rows_r2c_cl_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, NCH, IO>; };
+template <int IO, int NCH> struct C2RCl { static constexpr auto kernel = rows_c2r_cl_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, NCH, IO>; };
+
 // io == IO_CODE_ND_C64: the complex siblings (a complex64 plan's signal and taps; no row-major pipeline, no accumulating store)
 hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
+  if (a.cl_C) {
+    if (a.from_kernel || a.im.on) return hipErrorInvalidValue;
+    return launch_rows_cl<R2CCl>(a, st);
+  }
   if (a.io == IO_CODE_ND_C64) {
     if (a.rowmajor) return hipErrorInvalidValue;
     return launch_rows<rows_c2c_fwd_kernel<FC_P, FC_S, kNSEQ_R, kNT_R>, RowsR2CArgs, kNSEQ_R>(a, st);
@@ -71,6 +113,10 @@ hipError_t rows_r2c_dispatch(const RowsR2CArgs& a, hipStream_t st) {
   return with_io(a.io, [&](auto io) { return launch_rows<rows_r2c_kernel<FC_P, FC_S, kNSEQ_R, kNT_R, FC_IO(io)>>(a, st); });
 }
 hipError_t rows_c2r_dispatch(const RowsC2RArgs& a, hipStream_t st) {
+  if (a.cl_C) {
+    if (a.accum || a.im.on) return hipErrorInvalidValue;
+    return launch_rows_cl<C2RCl>(a, st);
+  }
   if (a.io == IO_CODE_ND_C64) {
     if (a.rowmajor || a.accum) return hipErrorInvalidValue;
     return launch_rows<rows_c2c_inv_kernel<FC_P, FC_S, kNSEQ_R, kNT_R>, RowsC2RArgs, kNSEQ_R>(a, st);
@@ -364,6 +410,7 @@ const TileImpl* FC_CAT(get_tile_P, FC_P, _S, FC_S)() {
 #else
                                 nullptr, nullptr, nullptr
 #endif
+                                , kNchCl
   };
   return &impl;
 }

@@ -191,17 +191,89 @@ def transform_kernel(plan, kernel: Tensor) -> KernelSpectrum:
     return KernelSpectrum(plan, buf)
 
 
-def _launch_forward(signal: Tensor, spectrum: KernelSpectrum, bias_c: Optional[Tensor]) -> Tensor:
-    plan = spectrum.plan
-    out = torch.empty((signal.shape[0], plan.key[3]) + plan.out_spatial, dtype=plan.dtype, device=signal.device)
-    ws, ws_ptr, stream = _scratch_and_stream(plan, signal.device)
-    plan.forward(signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
-                 out.data_ptr(), ws_ptr, stream)
+def _nd_layout(t: Tensor) -> str:
+    """How the 2-D / 3-D kernels take a (B, C, *spatial) tensor (pure: sizes and strides only, any device):
+    ``"planar"`` contiguous -- read where it lies, as ever (a tensor with one channel lies both ways and counts here);
+    ``"cl"``     4-D and ``torch.channels_last`` / 5-D and ``torch.channels_last_3d`` contiguous, at any storage offset:
+                 a contiguous (B, *spatial, C) tensor seen through ``permute`` -- read where it lies by the channels-last
+                 build of the first pass;
+    ``"copy"``   anything else (a channel slice, an expanded or spatially strided view, a 3-D tensor that is not
+                 contiguous): ``.contiguous()`` first."""
+    if t.is_contiguous():
+        return "planar"
+    if (t.ndim == 4 and t.is_contiguous(memory_format=torch.channels_last)) or (
+            t.ndim == 5 and t.is_contiguous(memory_format=torch.channels_last_3d)):
+        return "cl"
+    return "copy"
+
+
+def _nd_cl_native(channels_last: bool) -> bool:
+    """Whether a 2-D / 3-D call has the kernels take channels-last tensors where they lie (FFTCONV_ND_CL, read per call):
+    unset -- a call that asks for a channels-last result (``channels_last=True``) does, for its signal, its result and in
+    its backward; a call that does not is the call it always was, copies included (measured: the training step of such a
+    call lost to the copy, whose contiguous dY the weight gradient needs anyway -- DESIGN.md 4.3g);
+    ``1`` -- every call does, whatever its keyword; ``0`` -- none does."""
+    knob = os.environ.get("FFTCONV_ND_CL", "")
+    return knob != "0" and (bool(channels_last) or knob == "1")
+
+
+def _empty_channels_last(shape, dtype, device) -> Tensor:
+    """An uninitialised (B, C, *spatial) tensor that lies as a contiguous (B, *spatial, C)."""
+    n = len(shape) - 2
+    return torch.empty((shape[0],) + tuple(shape[2:]) + (shape[1],), dtype=dtype, device=device).permute(
+        (0, n + 1) + tuple(range(1, n + 1)))
+
+
+def _to_channels_last(t: Tensor) -> Tensor:
+    """The values of a (B, C, *spatial) tensor with the strides of ``_empty_channels_last``: one torch copy."""
+    out = _empty_channels_last(tuple(t.shape), t.dtype, t.device)
+    out.copy_(t)
     return out
 
 
-def _forward_native(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Tensor]) -> Tensor:
-    signal = _resolved(signal.detach()).contiguous()
+def _check_channels_last(channels_last, signal: Tensor):
+    """The ``channels_last`` keyword of ``fft_conv`` / ``fft_conv_transpose`` (ValueError, before any device call)."""
+    if not isinstance(channels_last, bool):
+        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+    if channels_last and signal.ndim == 3:
+        raise ValueError("channels_last=True goes with 4-D and 5-D tensors; a (batch, channels, length) signal has no "
+                         "channels-last result here: fft_long_conv(..., channels_last=True) returns one")
+
+
+def _launch_forward(signal: Tensor, spectrum: KernelSpectrum, bias_c: Optional[Tensor], x_cl: bool = False,
+                    y_cl: bool = False) -> Tensor:
+    plan = spectrum.plan
+    shape = (signal.shape[0], plan.key[3]) + plan.out_spatial
+    if y_cl:
+        out = _empty_channels_last(shape, plan.dtype, signal.device)
+    else:
+        out = torch.empty(shape, dtype=plan.dtype, device=signal.device)
+    ws, ws_ptr, stream = _scratch_and_stream(plan, signal.device)
+    args = (signal.data_ptr(), spectrum.buf.data_ptr(), bias_c.data_ptr() if bias_c is not None else None,
+            out.data_ptr(), ws_ptr, stream)
+    if x_cl or y_cl:
+        plan.forward_lay(*args, _native.ND_CHANNELS_LAST if x_cl else _native.ND_PLANAR,
+                         _native.ND_CHANNELS_LAST if y_cl else _native.ND_PLANAR)
+    else:
+        plan.forward(*args)
+    return out
+
+
+def _forward_native(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Tensor], channels_last: bool = False,
+                    native: bool = False) -> Tensor:
+    """One forward launch of ``spectrum.plan``.  ``channels_last=True`` returns the result lying channels-last.  Where the
+    call takes layouts natively (``_nd_cl_native``; ``native``: the caller has decided so, a backward of such a call) a
+    signal that lies channels-last (``_nd_layout`` "cl") is read where it lies and the last pass writes the channels-last
+    result, if the plan takes the layout (``Plan.takes_layout``); otherwise one torch copy each keeps values and strides."""
+    signal = _resolved(signal.detach())
+    # (``native`` comes from ``_nd_cl_native`` too, in the backward that passes it: FFTCONV_ND_CL=0 is honoured there)
+    nd_cl = signal.ndim >= 4 and (native or _nd_cl_native(channels_last))
+    x_cl = (nd_cl and _nd_layout(signal) == "cl"
+            and spectrum.plan.takes_layout(_native.ND_CHANNELS_LAST, _native.ND_PLANAR) is None)
+    y_cl = (channels_last and nd_cl
+            and spectrum.plan.takes_layout(_native.ND_PLANAR, _native.ND_CHANNELS_LAST) is None)
+    if not x_cl:
+        signal = signal.contiguous()
     # (a float16 / bfloat16 plan reads a float32 bias: Cout values; a complex64 plan Cout (re, im) pairs)
     bias_c = _resolved(bias.detach()).to(spectrum.plan.weight_dtype).contiguous() if bias is not None else None
     index = _device_index(signal.device)
@@ -211,9 +283,19 @@ def _forward_native(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Ten
         raise ValueError(f"signal is on {signal.device} but the kernel spectrum / plan belong to "
                          f"cuda:{spectrum.plan.device_index}")
     if torch.cuda.current_device() == index:      # the common case: no device switch to pay for
-        return _launch_forward(signal, spectrum, bias_c)
-    with torch.cuda.device(signal.device):
-        return _launch_forward(signal, spectrum, bias_c)
+        out = _launch_forward(signal, spectrum, bias_c, x_cl, y_cl)
+    else:
+        with torch.cuda.device(signal.device):
+            out = _launch_forward(signal, spectrum, bias_c, x_cl, y_cl)
+    return _to_channels_last(out) if channels_last and not y_cl else out
+
+
+def _forward_lay(signal: Tensor, spectrum: KernelSpectrum, bias: Optional[Tensor], channels_last: bool,
+                 native: bool = False) -> Tensor:
+    """``_forward_native``; a call that asks for no channels-last result is the three-argument call it always was."""
+    if channels_last or native:
+        return _forward_native(signal, spectrum, bias, channels_last, native)
+    return _forward_native(signal, spectrum, bias)
 
 
 def fft_conv(
@@ -225,6 +307,8 @@ def fft_conv(
     dilation: Union[int, Iterable[int]] = 1,
     groups: int = 1,
     padding_mode: str = "constant",
+    *,
+    channels_last: bool = False,
 ) -> Tensor:
     """N-d (1/2/3) cross-correlation through FFTs, equal to ``torch.nn.functional.conv{N}d``.
 
@@ -243,8 +327,20 @@ def fft_conv(
     on entry.  complex128, complex32, mixes of real and complex tensors and 3-D (one spatial axis) complex tensors raise
     ``TypeError`` (complex rows: ``fft_long_conv``); a kernel that would run in segments of taps (a dilated extent past 4096
     on an axis) raises ``NotImplementedError``.
+
+    Channels-last tensors (4-D and 5-D).  ``channels_last=True`` (keyword-only) returns the (B, Cout, *out) result with
+    the strides of a contiguous (B, *out, Cout) tensor, written that way by the last pass; such a call also reads a
+    ``signal`` that lies as ``torch.channels_last`` / ``channels_last_3d`` (``_nd_layout`` "cl") where it lies, and its
+    backward reads a channels-last dY where it lies and returns dX in the signal's layout.  Every value has the bits of
+    the call on contiguous copies.  Where the library does not take the layout (float64, complex64, the plane-major 3-D
+    pipeline, segments of taps, 2048- / 4096-point row transforms, tensors past its 32-bit guards, FFTCONV_ND_CL=0) one
+    torch copy per tensor keeps values and strides.  A call without the keyword is the call it always was (a strided
+    signal is copied); FFTCONV_ND_CL=1 has every call read a channels-last signal and dY where they lie.  A non-bool
+    raises ``ValueError``, and so does ``True`` with a 3-D signal (``fft_long_conv`` has the keyword for rows).
     """
-    return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None)
+    _check_channels_last(channels_last, signal)
+    return _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, None,
+                          channels_last=channels_last)
 
 
 _LOW_PRECISION = (torch.float16, torch.bfloat16)
@@ -281,16 +377,18 @@ def _needs_grad(*tensors) -> bool:
 
 
 def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
-               spectrum, plan):
-    """The body of ``_fft_conv_impl`` and ``_fft_conv_transpose_impl``."""
+               spectrum, plan, channels_last: bool = False, native: bool = False):
+    """The body of ``_fft_conv_impl`` and ``_fft_conv_transpose_impl`` (``native``: see ``_forward_native``)."""
     if isinstance(padding, str) and signal.ndim >= 3 and not transposed:
         n = signal.ndim - 2
         pads, drop = _string_padding(padding, kernel, stride, dilation, n)
-        out = _fft_conv_impl(signal, kernel, bias, stride, pads, dilation, groups, padding_mode, spectrum, plan)
+        out = _fft_conv_impl(signal, kernel, bias, stride, pads, dilation, groups, padding_mode, spectrum, plan,
+                             channels_last=channels_last, native=native)
         if any(drop):
             # (a fresh contiguous tensor, as documented and as torch's convolutions return: a view would pin the
-            # larger buffer and break downstream .view() calls)
-            out = out[(slice(None), slice(None)) + tuple(slice(d, None) for d in drop)].contiguous()
+            # larger buffer and break downstream .view() calls; channels_last: a fresh tensor that lies that way)
+            out = out[(slice(None), slice(None)) + tuple(slice(d, None) for d in drop)]
+            out = _to_channels_last(out) if channels_last else out.contiguous()
         return out
     if signal.is_complex():
         # (the library reads data_ptr(): a conj or neg bit is resolved here, inside the autograd graph)
@@ -308,8 +406,8 @@ def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_p
             and (bias is None or bias.dtype == signal.dtype)):
         # half-precision tensors in, half-precision tensor out; the arithmetic is the fp32 path (one cast pass each way)
         out = _conv_impl(transposed, signal.float(), kernel.float(), None if bias is None else bias.float(), stride, padding,
-                         output_padding, dilation, groups, padding_mode, None, None)
-        return out.to(signal.dtype)
+                         output_padding, dilation, groups, padding_mode, None, None, channels_last, native)
+        return out.to(signal.dtype)      # (.float() and .to() keep the strides of a channels-last tensor)
     if _needs_grad(signal, kernel, bias):
         # backward built from the same kernels (row N1; transposed: differentiable like the reference's op graph); native
         # 16-bit tensors are saved for backward, whose kernels read 16-bit dY and x (autograd.py)
@@ -318,20 +416,22 @@ def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_p
         if transposed:
             return autograd.FFTConvTransposeFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
                                                            to_ntuple(output_padding, n), to_ntuple(dilation, n), groups,
-                                                           spectrum)
+                                                           spectrum, channels_last)
         return autograd.FFTConvFunction.apply(signal, kernel, bias, to_ntuple(stride, n), to_ntuple(padding, n),
-                                              to_ntuple(dilation, n), groups, padding_mode, spectrum)
+                                              to_ntuple(dilation, n), groups, padding_mode, spectrum, channels_last)
     if plan is None:
         plan = _plan_for(signal, kernel, bias, *conf)
     if spectrum is None or spectrum.plan is not plan:
         spectrum = transform_kernel(plan, kernel)   # the reference also re-transforms per call (functional.py:71)
-    return _forward_native(signal, spectrum, bias)
+    return _forward_lay(signal, spectrum, bias, channels_last, native)
 
 
-def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, spectrum, plan=None):
+def _fft_conv_impl(signal, kernel, bias, stride, padding, dilation, groups, padding_mode, spectrum, plan=None, *,
+                   channels_last: bool = False, native: bool = False):
     """Shared by the functional and the modules; ``spectrum`` is an optional cached kernel transform and
     ``plan`` the plan the caller already looked up (and validated) for exactly these arguments."""
-    return _conv_impl(False, signal, kernel, bias, stride, padding, 0, dilation, groups, padding_mode, spectrum, plan)
+    return _conv_impl(False, signal, kernel, bias, stride, padding, 0, dilation, groups, padding_mode, spectrum, plan,
+                      channels_last, native)
 
 
 def fft_conv_transpose(
@@ -343,6 +443,8 @@ def fft_conv_transpose(
     output_padding: Union[int, Iterable[int]] = 0,
     dilation: Union[int, Iterable[int]] = 1,
     groups: int = 1,
+    *,
+    channels_last: bool = False,
 ) -> Tensor:
     """N-d transposed convolution through FFTs, equal to ``torch.nn.functional.conv_transpose{N}d``
     (reference: functional.py:92-176).
@@ -351,16 +453,18 @@ def fft_conv_transpose(
     becomes a zero-spread of the input folded into the load index map, the kernel flip and the
     in/out channel swap are folded into the kernel transform, padding / output_padding only move
     the window of kept samples -- no intermediate tensor is materialised.  4-D and 5-D complex64 tensors (all three)
-    are taken as ``fft_conv`` takes them.
+    are taken as ``fft_conv`` takes them, and so are channels-last tensors (``channels_last``, keyword-only: see there).
     """
-    return _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, None)
+    _check_channels_last(channels_last, signal)
+    return _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, None,
+                                    channels_last=channels_last)
 
 
 def _fft_conv_transpose_impl(signal, kernel, bias, stride, padding, output_padding, dilation, groups, spectrum,
-                             plan=None):
+                             plan=None, *, channels_last: bool = False):
     """Shared by the functional and the transposed modules (``spectrum`` / ``plan``: see ``_fft_conv_impl``)."""
     return _conv_impl(True, signal, kernel, bias, stride, padding, output_padding, dilation, groups, "constant", spectrum,
-                      plan)
+                      plan, channels_last)
 
 
 def complex_matmul(a: Tensor, b: Tensor, groups: int = 1) -> Tensor:

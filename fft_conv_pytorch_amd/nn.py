@@ -97,15 +97,18 @@ class _SpectrumCache:
 class _FFTConvForward(_SpectrumCache, nn.Module):
     """Shared ``forward`` for FFTConv1d/2d/3d (reference: nn.py:7-22)."""
 
+    channels_last = False      # (the 2-D and 3-D modules take it at construction: _ChannelsLastOption)
+
     def forward(self, signal: Tensor):
         assert signal.ndim == self.weight.ndim
         padding_mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
+        cl = self.channels_last
         if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64, torch.complex64)
                                              and not F_._half_native(signal, self.weight, self.bias)):
             # padding='same' / 'valid' (torch stores the string) and half-precision calls the kernels do not read and write
             # in their own dtype (FFTCONV_HALF_IO=0, mixed dtypes): the functional resolves them
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                                     self.groups, padding_mode, None)
+                                     self.groups, padding_mode, None, channels_last=cl)
         try:
             plan = self._plan(signal, padding_mode)
         except NotImplementedError:
@@ -113,13 +116,13 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
                 raise
             # a float16 / bfloat16 shape whose route the library refuses: the functional's cast path
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                                     self.groups, padding_mode, None)
+                                     self.groups, padding_mode, None, channels_last=cl)
         spectrum = self._cached_spectrum(plan)
         if (spectrum is not None and signal.dtype in F_._LOW_PRECISION      # (no widening kernel per call)
                 and not F_._needs_grad(signal, self.weight, self.bias)):
-            return F_._forward_native(signal, spectrum, self._cached_bias(plan))
+            return F_._forward_lay(signal, spectrum, self._cached_bias(plan), cl)
         return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                                 self.groups, padding_mode, spectrum, plan)
+                                 self.groups, padding_mode, spectrum, plan, channels_last=cl)
 
     def _plan(self, signal: Tensor, padding_mode: str):
         """Plan for this call; the argument validation and descriptor lookup are skipped while the call looks
@@ -139,10 +142,14 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
 class _FFTConvTransposeForward(_SpectrumCache, nn.Module):
     """Shared ``forward`` for FFTConvTranspose1d/2d/3d (reference: nn.py:25-39)."""
 
+    channels_last = False
+
     def forward(self, signal: Tensor):
         assert signal.ndim == self.weight.ndim
+        cl = self.channels_last
         cast = lambda: F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,  # noqa: E731
-                                                   self.output_padding, self.dilation, self.groups, None, None)
+                                                   self.output_padding, self.dilation, self.groups, None, None,
+                                                   channels_last=cl)
         if signal.dtype in F_._LOW_PRECISION and not F_._half_native(signal, self.weight, self.bias):
             return cast()      # half-precision call the kernels do not read and write natively: the functional casts
         try:
@@ -154,20 +161,40 @@ class _FFTConvTransposeForward(_SpectrumCache, nn.Module):
             return cast()      # a float16 / bfloat16 shape whose route the library refuses
         spectrum = self._cached_spectrum(plan)
         if spectrum is not None and signal.dtype in F_._LOW_PRECISION and not F_._needs_grad(signal, self.weight, self.bias):
-            return F_._forward_native(signal, spectrum, self._cached_bias(plan))
+            return F_._forward_lay(signal, spectrum, self._cached_bias(plan), cl)
         return F_._fft_conv_transpose_impl(signal, self.weight, self.bias, self.stride, self.padding,
-                                           self.output_padding, self.dilation, self.groups, spectrum, plan)
+                                           self.output_padding, self.dilation, self.groups, spectrum, plan,
+                                           channels_last=cl)
+
+
+class _ChannelsLastOption:
+    """``channels_last=True`` (keyword-only at construction; an attribute, shown by ``extra_repr``, not part of the
+    state_dict, kept by deepcopy and pickle) of the 2-D and 3-D modules: the result comes back with the strides of a
+    contiguous (B, *out, Cout) tensor, as ``fft_conv(..., channels_last=True)`` returns it -- from the cached spectrum too --
+    and a signal that lies channels-last is then read where it lies.  A module without it copies such a signal, as ever,
+    unless FFTCONV_ND_CL=1 (``functional._nd_cl_native``)."""
+
+    channels_last = False      # (the default of a module pickled before the attribute existed)
+
+    def __init__(self, *args, channels_last=False, **kwargs):
+        if not isinstance(channels_last, bool):
+            raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+        super().__init__(*args, **kwargs)
+        self.channels_last = channels_last
+
+    def extra_repr(self):
+        return super().extra_repr() + (", channels_last=True" if self.channels_last else "")
 
 
 class FFTConv1d(_FFTConvForward, nn.Conv1d):
     ...
 
 
-class FFTConv2d(_FFTConvForward, nn.Conv2d):
+class FFTConv2d(_ChannelsLastOption, _FFTConvForward, nn.Conv2d):
     ...
 
 
-class FFTConv3d(_FFTConvForward, nn.Conv3d):
+class FFTConv3d(_ChannelsLastOption, _FFTConvForward, nn.Conv3d):
     ...
 
 
@@ -175,11 +202,11 @@ class FFTConvTranspose1d(_FFTConvTransposeForward, nn.ConvTranspose1d):
     ...
 
 
-class FFTConvTranspose2d(_FFTConvTransposeForward, nn.ConvTranspose2d):
+class FFTConvTranspose2d(_ChannelsLastOption, _FFTConvTransposeForward, nn.ConvTranspose2d):
     ...
 
 
-class FFTConvTranspose3d(_FFTConvTransposeForward, nn.ConvTranspose3d):
+class FFTConvTranspose3d(_ChannelsLastOption, _FFTConvTransposeForward, nn.ConvTranspose3d):
     ...
 
 

@@ -448,6 +448,33 @@ int fc_long_wgrad_plan_info(const fc_long_wgrad_plan* plan, int64_t info[8]);
 int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
                   int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream);
 
+/* ---- Channels-last tensors of the 2-D / 3-D plans (ABI 7 extension: new entry points only; fc_desc keeps its size, every
+ * call above keeps its signature and meaning, and the route words of fc_debug_route are what they were).  The layout of x
+ * and of y is an argument of the call: plan creation, the plan's route, its spectrum and its workspace do not depend on it.
+ *   FC_ND_PLANAR         x (B, Cin, *spatial), y (B, Cout, *out) contiguous, as fc_forward takes them
+ *   FC_ND_CHANNELS_LAST  the channel index runs fastest: element (b, ch, z, y, x) of a tensor with C channels and spatial
+ *                        extents (SZ, SY, SX) -- SZ = 1 for a 2-D plan -- lies at ((((b*SZ + z)*SY + y)*SX + x)*C + ch)
+ *                        samples from the pointer; a contiguous (B, Y, X, C) / (B, Z, Y, X, C) tensor, what torch calls
+ *                        torch.channels_last / torch.channels_last_3d.  For y: C = Cout and the extents of fc_output_shape.
+ * The two layouts are independent of each other.  The tensors are read and written where they lie -- no copy is made -- by
+ * channels-last builds of the first and the last pass; the passes between them and the workspace are those of fc_forward.
+ * Every value has the bits of fc_forward on contiguous copies; every sample of y is written and no other byte.
+ * fc_forward_lay with both layouts FC_ND_PLANAR is fc_forward.
+ *
+ * fc_plan_takes_layout tells, without touching a device, whether a plan's launches take the two layouts: FC_OK, or
+ * FC_ERR_UNSUPPORTED with text (fc_forward_lay answers the same and launches nothing; the caller then passes contiguous
+ * copies).  Taken: a float32 / float16 / bfloat16 2-D or 3-D plan of fc_plan_create, forward or transposed, that is
+ * unsegmented, runs the separable passes or the 2-D row-major pipeline (route word `planes` 0 or 2), transforms its rows
+ * with 64 ... 1024 points (route word `x tile`), and whose tensors fit 32-bit addressing: a channels-last x below 2^32 - 1
+ * bytes, and for a channels-last y (16 * Xo + Lx + 8192) * Cout * (bytes per sample) below 2^31 (Xo: the output's last
+ * extent, Lx: its stride-1 extent).  Not taken: the plane-major 3-D pipeline (`planes` 1), a kernel that runs in segments of
+ * taps, 2048- and 4096-point row transforms, complex64 and float64 plans, weight-gradient plans, 1-D plans (rows:
+ * fc_long_forward_lay).  Any other layout code: FC_ERR_INVALID with text. */
+enum fc_nd_layout { FC_ND_PLANAR = 0, FC_ND_CHANNELS_LAST = 1 };
+int fc_plan_takes_layout(const fc_plan* plan, int x_layout, int y_layout);
+int fc_forward_lay(const fc_plan* plan, const float* x, int x_layout, const void* w_hat, const float* bias, float* y,
+                   int y_layout, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

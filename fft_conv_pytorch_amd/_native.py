@@ -161,6 +161,7 @@ def _signatures() -> dict:
         "fc_long_wgrad": (i32, (vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp)),
         "fc_plan_takes_layout": (i32, (vp, i32, i32)),
         "fc_forward_lay": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
+        "fc_long_forward_gated": (i32, (vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp)),
     }
 
 
@@ -475,6 +476,18 @@ class LongPlan(_Handle):
         as a contiguous (B, L, C)).  A channels-last block of 2**31 bytes or more: ``NotImplementedError``."""
         self._check(self._lib.fc_long_forward_lay(self._h, x_ptr, x_dtype, x_layout, spectrum_ptr, bias_ptr, y_ptr, y_dtype,
                                                   y_layout, workspace_ptr, stream))
+
+    def forward_gated(self, x_ptr: int, spectrum_ptr: int, bias_ptr: Optional[int], y_ptr: int, workspace_ptr: int,
+                      stream: int, x_dtype: int = 0, y_dtype: int = 0, *, pregate_ptr: Optional[int] = None,
+                      gate_ptr: Optional[int] = None, y2_ptr: Optional[int] = None, gate2_ptr: Optional[int] = None,
+                      y2_dtype: Optional[int] = None):
+        """``forward`` with gates fused into the column passes (``fc_long_forward_gated``): the rows are pregate * x,
+        y = gate * c and, where ``y2_ptr`` is given, y2 = gate2 * c for c = conv + bias; an absent gate is all ones.
+        (B, C, L) contiguous tensors; ``y2_dtype`` is y's (default) or float32 with no gate2.  A plan the gated builds do
+        not take (complex, a non-default ``fc_long_ext``, phases, decimation): ``NotImplementedError``, nothing launched."""
+        self._check(self._lib.fc_long_forward_gated(self._h, x_ptr, x_dtype, pregate_ptr, spectrum_ptr, bias_ptr, y_ptr,
+                                                    gate_ptr, y2_ptr, gate2_ptr, y_dtype,
+                                                    y_dtype if y2_dtype is None else y2_dtype, workspace_ptr, stream))
 
 
 def phases_desc(key: Tuple) -> FcLongPhasesDesc:

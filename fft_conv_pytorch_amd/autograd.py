@@ -592,15 +592,107 @@ class FFTLongConvFunction(torch.autograd.Function):
                     dx = dx.to(grad.dtype)
                     if x_nlc:
                         dx = F_._as_channels_last(dx)
-        wkey = F_._long_wgrad_key(B, cin, cout, g, L, K, pad_left, pad_right, grad.shape[2], flip, mode, s, d)
-        if ctx.needs_input_grad[1] and F_._long_wgrad_eligible(wkey, signal.dtype):
-            # FFTCONV_LONG_WGRAD=1: x and dY where they lie, dW in the weight's own order and dtype
-            dw = F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype)
-        elif ctx.needs_input_grad[1]:
-            du = _long_dw_exchanged(signal.detach(), grad, g, pad_left, pad_right, K, pad_mode=mode, tap_dil=s, out_step=d,
-                                    conj_signal=cx)
-            dw = (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
+        if ctx.needs_input_grad[1]:
+            dw = _long_grad_weight(signal, grad, kernel, g, pad_left, pad_right, flip, mode, s, d, cx)
         return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 10
+
+
+def _long_grad_weight(signal: Tensor, grad: Tensor, kernel: Tensor, g: int, pad_left: int, pad_right: int, flip: bool,
+                      mode: int, s: int, d: int, cx: bool) -> Tensor:
+    """dW of the plain branch of ``FFTLongConvFunction.backward`` (its docstring): the weight-gradient plan under
+    FFTCONV_LONG_WGRAD=1, else the primitive with batch and channels exchanged; ``kernel`` gives shape and dtype."""
+    B, cin, L = signal.shape
+    cout, _, K = kernel.shape
+    wkey = F_._long_wgrad_key(B, cin, cout, g, L, K, pad_left, pad_right, grad.shape[2], flip, mode, s, d)
+    if F_._long_wgrad_eligible(wkey, signal.dtype):
+        # FFTCONV_LONG_WGRAD=1: x and dY where they lie, dW in the weight's own order and dtype
+        return F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype)
+    du = _long_dw_exchanged(signal.detach(), grad, g, pad_left, pad_right, K, pad_mode=mode, tap_dil=s, out_step=d,
+                            conj_signal=cx)
+    return (du.flip(-1) if flip else du).contiguous().to(kernel.dtype)
+
+
+class FFTLongConvGatedFunction(torch.autograd.Function):
+    """The fused route of ``fft_long_conv_gated`` (``F_._long_gated_route`` "fused": real tensors, the plain primitive at
+    stride 1, dilation 1, zero padding, contiguous rows) with its five gradients.  With z = pregate * x, c = conv(z) + bias,
+    y = postgate * c and g = postgate * dY (an absent gate: all ones):
+
+        forward      one ``F_._long_run_gated``.  Saved: x, kernel, bias, the gates -- never z or y -- and c only where
+                     ``postgate`` needs a gradient: the same launch stores it as its second result (float32 for 16-bit
+                     tensors, so that d(postgate) is rounded once);
+        dX, dPre     ONE run of the dX construction of ``FFTLongConvFunction`` (the same plan on the same transposed
+                     weight, dY and ``postgate`` trimmed alike): ``postgate`` gates dY as the first pass loads it, the last
+                     pass stores dX = pregate * dZ and d(pregate) = x * dZ, or the one of them that is wanted;
+        dPost        dY * c, one torch multiply (in float32, rounded once);
+        dW, db       the routes of ``FFTLongConvFunction`` (FFTCONV_LONG_WGRAD included) on the products z and g, which
+                     torch forms in float32: transient tensors.
+
+    Each gradient has the bits of autograd through ``postgate * fft_long_conv(pregate * x, ...)`` on float32 tensors,
+    rounded once.  A backward that itself records a graph (``create_graph=True``) differentiates that composed line."""
+
+    @staticmethod
+    def forward(ctx, signal, kernel, bias, pregate, postgate, pad_left, pad_right, causal, groups, spectrum):
+        keep_c = postgate is not None and ctx.needs_input_grad[4]
+        plan, run = F_._long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, 1, 1, 0,
+                                          "plain")
+        y, c = F_._long_run_gated(signal, kernel, bias, pad_left, pad_right, causal, run["out_keep"], groups, spectrum,
+                                  pregate=pregate, gate=postgate, second=keep_c, second_dtype=torch.float32, plan=plan)
+        ctx.save_for_backward(signal, kernel, bias, pregate, postgate, c)
+        ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        signal, kernel, bias, pregate, postgate, c = ctx.saved_tensors
+        pad_left, pad_right, flip, g = ctx.cfg
+        need = ctx.needs_input_grad
+        if torch.is_grad_enabled():      # a backward that records a graph: the composed line, which torch differentiates
+            with torch.enable_grad():
+                z = signal if pregate is None else pregate * signal
+                out = FFTLongConvFunction.apply(z, kernel, bias, pad_left, pad_right, flip, g, None)
+                out = out if postgate is None else postgate * out
+            inputs = [t for t, n in zip((signal, kernel, bias, pregate, postgate), need) if n]
+            grads = iter(torch.autograd.grad(out, inputs, grad, create_graph=True, allow_unused=True))
+            return tuple(next(grads) if n else None for n in need[:5]) + (None,) * 5
+        grad = grad.detach().contiguous()
+        B, cin, L = signal.shape
+        cout, cig, K = kernel.shape
+        cog = cout // g
+        low = signal.dtype in F_._LOW_PRECISION
+        dx = dw = db = dpre = dpost = None
+        want_dpre = pregate is not None and need[3]
+        if postgate is not None and need[4]:
+            dpost = grad.float().mul_(c).to(grad.dtype) if low else grad * c
+        if need[0] or want_dpre:
+            wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
+            lead, dy, pg = K - 1 - pad_left, grad, postgate
+            if lead < 0:        # padding wider than the filter: those leading output samples never met the data
+                dy, pg, lead = dy[..., -lead:], None if pg is None else pg[..., -lead:], 0
+            tail = L + K - 1 - lead - dy.shape[2]
+            if tail < 0 and dy.shape[2]:
+                keep = max(0, dy.shape[2] + tail)
+                dy, pg, tail = dy[..., :keep], None if pg is None else pg[..., :keep], 0
+            if dy.shape[2] == 0:
+                dx = torch.zeros_like(signal) if need[0] else None
+                dpre = torch.zeros_like(signal) if want_dpre else None
+            else:
+                # the results of the last pass: dX = pregate * dZ where wanted, then d(pregate) = x * dZ where wanted
+                gates = ([pregate] if need[0] else []) + ([signal] if want_dpre else [])
+                res = F_._long_run_gated(dy, wt, None, lead, max(tail, 0), not flip, L, g, pregate=pg, gate=gates[0],
+                                         gate2=gates[1] if len(gates) > 1 else None)
+                dx = res[0] if need[0] else None
+                dpre = res[len(gates) - 1] if want_dpre else None
+        if need[1] or (bias is not None and need[2]):
+            # (the float32 products torch forms; an absent gate leaves the tensor as it is)
+            # (16-bit: a float32 copy times the 16-bit tensor, widened as mul_ reads it: two passes, one float32 tensor)
+            wide = (lambda a, b: a.float().mul_(b)) if low else torch.mul
+            gq = grad if postgate is None else wide(grad, postgate.detach())
+            if need[1]:
+                z = signal.detach() if pregate is None else wide(signal.detach(), pregate.detach())
+                dw = _long_grad_weight(z, gq, kernel, g, pad_left, pad_right, flip, 0, 1, 1, False)
+            if bias is not None and need[2]:
+                db = _long_grad_bias(gq, kernel.dtype)
+        return (dx, dw, db, dpre, dpost) + (None,) * 5
 
 
 class FFTLongConvTransposeFunction(torch.autograd.Function):

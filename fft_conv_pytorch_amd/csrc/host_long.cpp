@@ -663,6 +663,55 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
   return FC_OK;
 }
 
+// ---- gates fused into the column passes (include/fftconv_amd.h "Gated long forward")
+
+int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, const void* pregate, const void* spectrum,
+                          const float* bias, void* y, const void* gate, void* y2, const void* gate2, int y_dtype,
+                          int y2_dtype, void* workspace, void* hip_stream) {
+  if (!plan || !x || !spectrum || !y || !workspace) return fail(FC_ERR_INVALID, "null argument");
+  if (plan->d.has_bias && !bias) return fail(FC_ERR_INVALID, "the plan was made with a bias");
+  const LongGeom& g = plan->g;
+  if (g.kind & FC_LONG_COMPLEX)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes real plans only: the gated builds of the column kernels read two "
+                "real rows per row of the transform (multiply complex tensors around fc_long_forward_io)");
+  if (g.ph_s || g.dc_s)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes neither a phases plan nor a decimation plan: their column passes "
+                "give the block layout to phases, and no gated build of those exists");
+  if (g.pad_mode != PAD_CONSTANT || g.up != 1 || g.dil != 1 || g.step != 1)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes plans with the default fc_long_ext only (pad_mode constant, "
+                "src_up, tap_dil and out_step 1): the gated builds are builds of the unmapped column kernels");
+  if (gate2 && !y2) return fail(FC_ERR_INVALID, "gate2 without y2: the second gate belongs to the second result");
+  int xio = 0, yio = 0, y2io = 0;
+  if (int e = plan_io_code(plan, x_dtype, "x", &xio)) return e;
+  if (int e = plan_io_code(plan, y_dtype, "y", &yio)) return e;
+  if (int e = plan_io_code(plan, y2 ? y2_dtype : y_dtype, "y2", &y2io)) return e;
+  if (y2io != yio && !(y2io == 0 && !gate2))
+    return fail(FC_ERR_INVALID, "y2 has dtype code %d and y %d: y2 shares y's element type, or is float32 with no gate2 (the "
+                "unrounded c = z + bias of a 16-bit launch)", y2_dtype, y_dtype);
+  const LongGates gt = {(const float*)pregate, (const float*)gate, (float*)y2, (const float*)gate2, y2 && y2io != yio};
+  const bool gated_out = gate || y2;
+  hipStream_t st = (hipStream_t)hip_stream;
+  for (int64_t s = 0; s < g.slabs; ++s) {
+    const int64_t pair0 = s * g.slab_pairs;
+    const int64_t np = std::min(g.slab_pairs, g.npairs - pair0);
+    LongArgs a = base_args(*plan);
+    a.pair0 = (int)pair0;      // (the gates advance with pair0 as x and y do: the kernels index them by the batch item)
+    a.src = (const float*)x; a.bias = bias; a.y = (float*)y;
+    a.src_io = xio; a.y_io = yio;
+    a.spec = (const f2*)spectrum;
+    a.w1 = (f2*)workspace;
+    a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
+    a.C = (int)g.Cin;
+    if (pregate) FC_HIP(plan->cols->cols_fwd_gated(a, gt, np, st));
+    else FC_HIP(plan->cols->cols_fwd(a, false, false, np, st));
+    FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
+    a.C = (int)g.Cout;
+    if (gated_out) FC_HIP(plan->cols->cols_inv_gated(a, gt, np, st));
+    else FC_HIP(plan->cols->cols_inv(a, false, false, np, st));
+  }
+  return FC_OK;
+}
+
 // ---- the weight gradient (include/fftconv_amd.h "Weight gradient of a long plan")
 
 int fc_long_wgrad_geometry(const fc_long_wgrad_desc* desc, int64_t info[8]) {

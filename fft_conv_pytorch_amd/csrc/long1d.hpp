@@ -74,6 +74,11 @@
 // over the batch pairs in registers, bin by bin, and transforms back once per (o, i); long_cols_inv drops the imaginary
 // part (one item with no partner) and stores lag tap_dil*q at the place of tap q in the weight's own order.
 //
+// Gated builds of the two column kernels (long_cols_fwd_gated_kernel, long_cols_inv_gated_kernel; real rows, the plain
+// form, float32 and 16-bit) multiply by elementwise gates where the tensors are touched anyway: the signal by a pregate as
+// it is loaded, the result by up to two gates as up to two results are stored (LongGates, a second kernel argument of
+// those builds alone).  They are kernels of their own: no build that existed changes by an instruction.
+//
 // The bins stay in the order [k1][k2] on both operands, so the product needs no transposition.  The filter is real,
 // hence conj(H) is the spectrum of the correlation and y[t] = sum_k u[k] * z[t + k] comes out in place.
 #pragma once
@@ -136,6 +141,16 @@ struct LongArgs {
 
 constexpr int IO_CODE_C64 = 4;       // fc_dtype code of a launch of a complex build (src_io / y_io)
 
+// The second kernel argument of the gated builds of the two column kernels (fc_long_forward_gated).  The builds without
+// gates do not take it: LongArgs, and with it their arguments and registers, stay what they were.
+struct LongGates {
+  const float* pregate;  // cols_fwd: (B, C, L) like the signal, element type src_io; the row is pregate * x
+  const float* gate;     // cols_inv: (B, Cout, nout) like y, element type y_io, or null: y = gate * c, c = z + bias
+  float* y2;             // cols_inv: a second result of y's shape, or null: y2 = gate2 * c
+  const float* gate2;    // cols_inv: like gate, or null (y2 = c)
+  int y2_f32;            // cols_inv, 16-bit build: y2 is float32 (c unrounded) and gate2 null
+};
+
 __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m) {
   const f2 hi = buf_load_f32x2(thi, (m >> kLongLoBits) * 8u, 0);
   const f2 lo = buf_load_f32x2(tlo, (m & ((1u << kLongLoBits) - 1u)) * 8u, 0);
@@ -143,6 +158,8 @@ __device__ __forceinline__ f2 long_twiddle(BufRsrc thi, BufRsrc tlo, unsigned m)
 }
 
 // ------------------------------------------------------------------------------------------ long_cols_fwd
+// (long_cols_fwd_gated_kernel below repeats the plain signal path of this kernel -- offsets, LDS staging, transform, twiddle
+// and store: a fix to any of those here is a fix there too)
 template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false,
           bool DEC = false>
 __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
@@ -352,6 +369,92 @@ __global__ __launch_bounds__(NT) void long_cols_fwd_kernel(const LongArgs a) {
   }
 }
 
+// The gated build of long_cols_fwd: the signal rows of a real plan in the plain form ((B, C, L) tensors, zero padding, no
+// spread; float32 or 16-bit), each sample times its pregate as it is loaded.  The pregate rows of the pair's two items are
+// read at the offsets of the signal's through resources of the same size, so a position that reads the signal as zero
+// reads the gate as zero too.  The product is one float32 multiply of the widened operands (of two 16-bit values: exact),
+// the bits of torch's pregate * x on float32 tensors; transform, twiddle and store are those of the kernel above on those
+// values.  It is a kernel of its own, so that every build above keeps its code: filter rows never come here.
+template <int P, int S, int NSEQ, int NT, int IO>
+__global__ __launch_bounds__(NT) void long_cols_fwd_gated_kernel(const LongArgs a, const LongGates gt) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.src_io);
+  constexpr unsigned ES = Io<IO>::B;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row, pr;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+  const unsigned c = fdivmod(row, a.d_c, &pr);
+  const int b0 = 2 * (a.pair0 + (int)pr);
+  const bool has1 = b0 + 1 < a.B;
+  const size_t first = ((size_t)b0 * a.C + c) * a.L, next = has1 ? (size_t)a.C * a.L : 0;
+  const unsigned len = (unsigned)a.L, sbytes = len * ES;
+  const BufRsrc s0 = make_rsrc(io_ptr<IO>(a.src) + first, sbytes), s1 = make_rsrc(io_ptr<IO>(a.src) + first + next, sbytes);
+  const BufRsrc g0 = make_rsrc(io_ptr<IO>(gt.pregate) + first, sbytes), g1 = make_rsrc(io_ptr<IO>(gt.pregate) + first + next, sbytes);
+  {
+    // all 4 P loads are issued before the first sample is widened or multiplied (as the 16-bit build above)
+    f2 val[P];
+    const auto offset = [&](int u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      const int s = (n1 << a.lgN2) + n20 + r - a.padl;
+      return (unsigned)s < len ? (unsigned)s * ES : 0x80000000u;
+    };
+    if constexpr (IO == IO_F32) {
+      f2 gv[P];
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const unsigned off = offset(u), off1 = has1 ? off : 0x80000000u;
+        val[u] = mk2(buf_load_f32(s0, off, 0), buf_load_f32(s1, off1, 0));
+        gv[u] = mk2(buf_load_f32(g0, off, 0), buf_load_f32(g1, off1, 0));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u] = mk2(__fmul_rn(gv[u].x, val[u].x), __fmul_rn(gv[u].y, val[u].y));
+    } else {
+      unsigned h0[P], h1[P], q0[P], q1[P];
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const unsigned off = offset(u), off1 = has1 ? off : 0x80000000u;
+        h0[u] = __builtin_amdgcn_raw_buffer_load_b16(s0, off, 0, 0);
+        h1[u] = __builtin_amdgcn_raw_buffer_load_b16(s1, off1, 0, 0);
+        q0[u] = __builtin_amdgcn_raw_buffer_load_b16(g0, off, 0, 0);
+        q1[u] = __builtin_amdgcn_raw_buffer_load_b16(g1, off1, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u] = mk2(__fmul_rn(io.in(q0[u]), io.in(h0[u])), __fmul_rn(io.in(q1[u]), io.in(h1[u])));
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(n1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  nat_load<G>(v, lseq, tseq);
+  seq_sync<G>();
+  fwd_from_regs<G>(v, lseq, tseq, true, twA, twB);
+  __syncthreads();
+  const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
+  const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
+  const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8));
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+    const unsigned n2 = (unsigned)(n20 + r);
+    const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
+    const f2 z = lds[r * LSEQP + G::nat(k1)];
+    buf_store_f32x2(cmul(z, w), orr, (((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ long_rows
 // NSEQ neighbouring k1 rows per workgroup, one sequence each; OB output channels of one group per workgroup, their
 // running sums in registers in the order the inverse transform starts from (bins N2e*i1 + tseq of the thread).
@@ -555,6 +658,8 @@ __global__ __launch_bounds__(NT) void long_wgrad_rows_kernel(const LongArgs a) {
 // out_step * q of the row, q < a.keff, is the lag of tap q and goes where long_cols_fwd reads that tap of a filter row,
 // element a.tap0 + a.tstep * q (tensor order or flipped); the elements no kept lag reaches are not touched (the host
 // zeroes them).
+// (long_cols_inv_gated_kernel below repeats the plain real path of this kernel -- W2 loads, inverse transform, the trip
+// through LDS, bias and store offsets: a fix to any of those here is a fix there too)
 template <int P, int S, int NSEQ, int NT, int IO = IO_F32, bool MAP = false, bool CX = false, int NC = 0, bool PHS = false,
           bool WG = false>
 __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
@@ -700,6 +805,123 @@ __global__ __launch_bounds__(NT) void long_cols_inv_kernel(const LongArgs a) {
   }
 }
 
+// The gated build of long_cols_inv: real rows, the plain form, (B, C, L) tensors, float32 or 16-bit.  Up to two results
+// from the one value c = z + bias it holds per sample: y = gate * c and y2 = gate2 * c, a null gate being all ones and a
+// null y2 not stored.  The gates lie as y does and are loaded at the offset of the store through resources of y's row;
+// the product is one float32 multiply -- (z + b) * gate, never fused with the bias add -- and is rounded once, at the
+// store.  With y2_f32 a 16-bit launch stores c itself, unrounded, into a float32 y2.  A kernel of its own, as the gated
+// build of long_cols_fwd is.
+template <int P, int S, int NSEQ, int NT, int IO>
+__global__ __launch_bounds__(NT) void long_cols_inv_gated_kernel(const LongArgs a, const LongGates gt) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.y_io);
+  constexpr unsigned ES = Io<IO>::B;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row, pr;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+  const unsigned o = fdivmod(row, a.d_c, &pr);
+  const int b0 = 2 * (a.pair0 + (int)pr);
+  const bool has1 = b0 + 1 < a.B;
+  f2 wtw[P];
+  passA_twiddle_fetch<G>(wtw, tseq, twA);
+  {
+    const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, (unsigned)(N * 8));
+    f2 val[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      val[u] = buf_load_f32x2(sr, (((unsigned)k1 << a.lgN2) + (unsigned)(n20 + r)) * 8u, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(k1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  const int j = inv_to_regs_pre<G>(v, wtw, lseq, tseq, true, twB);
+  seq_sync<G>();
+  {
+    const int nbase = (tseq >> G::LGS) + P * P * j;
+#pragma unroll
+    for (int k = 0; k < P; ++k) lseq[G::nat(nbase + P * k)] = v[k];
+  }
+  __syncthreads();
+  float b = a.bias ? a.bias[o] : 0.f;
+  asm volatile("" : "+v"(b));
+  // the rows of the pair's two items in y and in every tensor that lies as y does; an absent tensor gets y's address and
+  // is never touched (every branch on gt below is wave-uniform)
+  const size_t first = ((size_t)b0 * a.C + o) * a.nout, next = has1 ? (size_t)a.C * a.nout : 0;
+  const unsigned ybytes = (unsigned)a.nout * ES;
+  const auto like_y = [&](const float* p, size_t at) { return make_rsrc(io_ptr<IO>(p ? p : a.y) + at, ybytes); };
+  const bool wide2 = IO != IO_F32 && gt.y2_f32;
+  const BufRsrc o0 = like_y(a.y, first), o1 = like_y(a.y, first + next);
+  const BufRsrc ga0 = like_y(gt.gate, first), ga1 = like_y(gt.gate, first + next);
+  const BufRsrc gb0 = like_y(gt.gate2, first), gb1 = like_y(gt.gate2, first + next);
+  const BufRsrc p0 = wide2 ? make_rsrc(gt.y2 + first, (unsigned)a.nout * 4u) : like_y(gt.y2, first);
+  const BufRsrc p1 = wide2 ? make_rsrc(gt.y2 + first + next, (unsigned)a.nout * 4u) : like_y(gt.y2, first + next);
+  // every gate sample of the thread is requested before the first is widened or used (as the loads of long_cols_fwd)
+  const auto raw = [&](const BufRsrc& g, unsigned at) {
+    if constexpr (IO == IO_F32) return __builtin_amdgcn_raw_buffer_load_b32(g, at, 0, 0);
+    else return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(g, at, 0, 0);
+  };
+  const auto widen = [&](unsigned h) {
+    if constexpr (IO == IO_F32) return __uint_as_float(h);
+    else return io.in(h);
+  };
+  const auto place = [&](int u, unsigned* t) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+    *t = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
+    return *t < (unsigned)a.nout ? *t * ES : 0x80000000u;       // (samples past the kept window: dropped)
+  };
+  unsigned ra0[P], ra1[P], rb0[P], rb1[P];
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    unsigned t;
+    const unsigned off = place(u, &t), off1 = has1 ? off : 0x80000000u;
+    ra0[u] = gt.gate ? raw(ga0, off) : 0u;
+    ra1[u] = gt.gate ? raw(ga1, off1) : 0u;
+    rb0[u] = gt.gate2 ? raw(gb0, off) : 0u;
+    rb1[u] = gt.gate2 ? raw(gb1, off1) : 0u;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // gate * c as a float32 value of its own: the empty asm keeps the compiler from folding the multiply into the 16-bit
+  // conversion of the store (v_fma_mixlo_f16 rounds the exact product once; torch rounds to float32, then to 16 bits)
+  const auto times = [&](unsigned h, float c) {
+    float p = __fmul_rn(widen(h), c);
+    asm volatile("" : "+v"(p));
+    return p;
+  };
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+    const f2 z = lds[r * LSEQP + G::nat(n1)];
+    unsigned t;
+    const unsigned off = place(u, &t), off1 = has1 ? off : 0x80000000u;
+    const bool keep = off != 0x80000000u;
+    const float c0 = z.x + b, c1 = z.y + b;
+    io.store(gt.gate ? times(ra0[u], c0) : c0, o0, off, 0);
+    io.store(gt.gate ? times(ra1[u], c1) : c1, o1, off1, 0);
+    if (gt.y2) {
+      if (wide2) {
+        buf_store_f32(c0, p0, keep ? t * 4u : 0x80000000u, 0);
+        buf_store_f32(c1, p1, keep && has1 ? t * 4u : 0x80000000u, 0);
+      } else {
+        io.store(gt.gate2 ? times(rb0[u], c0) : c0, p0, off, 0);
+        io.store(gt.gate2 ? times(rb1[u], c1) : c1, p1, off1, 0);
+      }
+    }
+  }
+}
+
 // what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan.  The host
 // states facts and long_inst.hip picks the build of a column pass: the element type by a.src_io (cols_fwd) / a.y_io
 // (cols_inv), the mapped build where `mapped` (padding mode, src_up, tap_dil / out_step), the channels-last build where
@@ -715,6 +937,9 @@ struct LongImpl {
   int wg_ob;
   hipError_t (*wgrad_rows)(const LongArgs& a, long long units, hipStream_t st);
   hipError_t (*wgrad_inv)(const LongArgs& a, hipStream_t st);
+  // the gated builds of the column passes (float32 and 16-bit, plain form): `rows` batch pairs
+  hipError_t (*cols_fwd_gated)(const LongArgs& a, const LongGates& gt, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_gated)(const LongArgs& a, const LongGates& gt, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

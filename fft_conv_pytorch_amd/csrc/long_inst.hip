@@ -187,12 +187,34 @@ hipError_t wgrad_inv(const LongArgs& a, hipStream_t st) {
   return hipErrorInvalidValue;
 }
 
+// ---- gates (long1d.hpp LongGates): the gated builds of the two column passes, float32 and 16-bit, the plain block map.
+// They take the gates as a second kernel argument; every other build keeps the one it had
+template <bool INV>
+hipError_t cols_gated(const LongArgs& a, const LongGates& gt, long long rows, hipStream_t st) {
+  if (a.N1 != kT || rows <= 0 || a.C <= 0 || a.from_kernel || a.ph_s > 0) return hipErrorInvalidValue;
+  if (INV ? (gt.gate2 && !gt.y2) || (gt.y2_f32 && (gt.gate2 || !gt.y2)) : !gt.pregate) return hipErrorInvalidValue;
+  LongArgs b = a;
+  b.d_nblk = make_fastdiv((unsigned)(a.N2 / kNSEQ));
+  b.d_c = make_fastdiv((unsigned)a.C);
+  const long long grid = rows * a.C * (a.N2 / kNSEQ);
+  const int code = INV ? a.y_io : a.src_io;
+  if constexpr (INV) {
+    if (code == 0) return launch_kernel<long_cols_inv_gated_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32>>(grid, kNT, kLds, st, b, gt);
+    if (io_is_h16(code)) return launch_kernel<long_cols_inv_gated_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(grid, kNT, kLds, st, b, gt);
+  } else {
+    if (code == 0) return launch_kernel<long_cols_fwd_gated_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32>>(grid, kNT, kLds, st, b, gt);
+    if (io_is_h16(code)) return launch_kernel<long_cols_fwd_gated_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(grid, kNT, kLds, st, b, gt);
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 #define FC_CAT_(a, b, c, d) a##b##c##d
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
-  static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>, kWgOB, wgrad_rows, wgrad_inv};
+  static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>, kWgOB, wgrad_rows, wgrad_inv,
+                                cols_gated<false>, cols_gated<true>};
   return &impl;
 }
 

@@ -18,7 +18,7 @@ from torch import Tensor
 from . import _native
 from .utils import to_ntuple
 
-__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
+__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_gated", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
 
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
@@ -958,6 +958,149 @@ def _long_operands(signal: Tensor, kernel: Tensor, bias: Optional[Tensor]):
     if signal.dtype == torch.complex64:
         signal, kernel, bias = _resolved(signal), _resolved(kernel), None if bias is None else _resolved(bias)
     return signal, kernel, bias, signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias)
+
+
+# ---------------------------------------------------------------------------------- gated long filters
+def _long_out_len(length: int, taps: int, pad_left: int, pad_right: int, causal: bool, stride: int, dilation: int) -> int:
+    """Output length of a ``fft_long_conv`` call from the numbers ``_long_geometry`` returns."""
+    return _long_keep(length, causal, stride) or (length + pad_left + pad_right - dilation * (taps - 1) - 1) // stride + 1
+
+
+def _long_gates(signal: Tensor, pregate: Optional[Tensor], postgate: Optional[Tensor], out_shape: tuple):
+    """Argument checks of the gates of ``fft_long_conv_gated`` (before any device call): ``pregate`` has the signal's shape
+    and ``postgate`` the result's (ValueError), each the signal's dtype (TypeError) and device (ValueError)."""
+    for name, t, shape, of in (("pregate", pregate, tuple(signal.shape), "signal"), ("postgate", postgate, tuple(out_shape), "result")):
+        if t is None:
+            continue
+        if not isinstance(t, Tensor):
+            raise TypeError(f"`{name}` must be a tensor or None, got {type(t).__name__}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"`{name}` must have the {of}'s shape {shape}, got {tuple(t.shape)}")
+        if t.dtype != signal.dtype:
+            raise TypeError(f"`{name}` has dtype {t.dtype} but the signal is {signal.dtype}; the gates share the signal's dtype")
+        if t.device != signal.device:
+            raise ValueError(f"`{name}` is on {t.device} but the signal is on {signal.device}; all tensors of one call must be "
+                             f"on the same device")
+
+
+def _long_gated_route_of(route: str, stride: int, dilation: int, pad_mode: int, dtype, x_layout: str, channels_last: bool) -> str:
+    """``_long_gated_route`` from the route ``_long_route_of`` names and the numbers of the call."""
+    fused = (dtype in (torch.float32,) + _LOW_PRECISION and route == "plain" and stride == 1 and dilation == 1
+             and pad_mode == 0 and not channels_last and x_layout != "nlc"
+             and not (dtype in _LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0"))
+    return "fused" if fused else "composed"
+
+
+def _long_gated_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, groups=1, causal=False,
+                      padding_mode="constant", dtype=torch.float32, x_layout="ncl", channels_last=False) -> str:
+    """Which route a ``fft_long_conv_gated`` call with a gate takes (pure: shapes, dtypes, strides and numbers only; no
+    switch selects between the two):
+
+    ``"fused"``     float32 / float16 / bfloat16 tensors, ``_long_route`` "plain", stride 1, dilation 1, ``padding_mode``
+                    constant (the unmapped builds of the column kernels), neither a signal read channels-last
+                    (``x_layout``: ``_long_layout`` of the signal) nor a channels-last result: the gates ride the column
+                    passes of the one call (``fc_long_forward_gated``);
+    ``"composed"``  everything else -- complex64, the phases route, a stride, a dilation, a padding mode, channels-last
+                    signal or result, a row that hands off to ``fft_conv``, the FFTCONV_HALF_IO=0 cast path: the line
+                    ``postgate * fft_long_conv(pregate * signal, ...)`` with torch multiplies."""
+    route, _, _, stride, dilation, mode = _long_route_numbers(signal_shape, kernel_shape, stride, padding, dilation, groups,
+                                                              causal, padding_mode, dtype, x_layout)
+    return _long_gated_route_of(route, stride, dilation, mode, dtype, x_layout, bool(channels_last))
+
+
+def _long_run_gated(signal: Tensor, kernel: Optional[Tensor], bias: Optional[Tensor], pad_left: int, pad_right: int,
+                    flip: bool, out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None, *,
+                    pregate: Optional[Tensor] = None, gate: Optional[Tensor] = None, gate2: Optional[Tensor] = None,
+                    second: bool = False, second_dtype: Optional[torch.dtype] = None, weight_shape: Optional[tuple] = None,
+                    plan=None):
+    """The plain primitive of ``_long_run`` (zero padding, no spread, dilation 1, every output kept; float32 / float16 /
+    bfloat16, contiguous (B, C, L) tensors) with gates in its column passes, no autograd -> (y, y2):
+    rows = pregate * signal, c = conv(rows) + bias, y = gate * c and, with ``second`` or a ``gate2``, y2 = gate2 * c from
+    the same launch; an absent gate is all ones and y2 is None where not asked for.  ``second_dtype`` float32 on 16-bit
+    tensors (no ``gate2``) stores c unrounded.  Tensors that do not lie contiguous are copied first."""
+    signal = signal.detach().contiguous()
+    pregate, gate, gate2 = (None if t is None else t.detach().contiguous() for t in (pregate, gate, gate2))
+    cout, taps = (int(kernel.shape[0]), int(kernel.shape[2])) if weight_shape is None else weight_shape
+    if plan is None:
+        plan = _long_plan(signal, cout, groups, taps, pad_left, pad_right, flip, out_keep, bias is not None)
+    if spectrum is None or spectrum.plan is not plan:
+        spectrum = transform_kernel(plan, kernel)
+    bias_c = None if bias is None else bias.detach().float().contiguous()
+    shape = (int(signal.shape[0]), cout, plan.out_len)
+    second = second or gate2 is not None
+    with torch.cuda.device(signal.device):
+        out = torch.empty(shape, dtype=signal.dtype, device=signal.device)
+        out2 = torch.empty(shape, dtype=second_dtype or signal.dtype, device=signal.device) if second else None
+        ws, ws_ptr, stream = _scratch_and_stream(plan, signal.device)
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        plan.forward_gated(signal.data_ptr(), spectrum.buf.data_ptr(), ptr(bias_c), out.data_ptr(), ws_ptr, stream,
+                           _DTYPE_CODES[signal.dtype], _DTYPE_CODES[out.dtype], pregate_ptr=ptr(pregate), gate_ptr=ptr(gate),
+                           y2_ptr=ptr(out2), gate2_ptr=ptr(gate2),
+                           y2_dtype=None if out2 is None else _DTYPE_CODES[out2.dtype])
+    return out, out2
+
+
+def fft_long_conv_gated(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
+                        causal: bool = False, *, pregate: Tensor = None, postgate: Tensor = None, stride: int = 1,
+                        dilation: int = 1, padding_mode: str = "constant", channels_last: bool = False) -> Tensor:
+    """The gated long convolution of Hyena / H3 / M2 layers, defined for every call ``fft_long_conv`` accepts:
+
+        postgate * fft_long_conv(pregate * signal, kernel, bias, padding, groups, causal, stride=..., dilation=...,
+                                 padding_mode=..., channels_last=...)
+
+    ``pregate`` has the signal's shape and ``postgate`` the result's, each the signal's dtype and device; either may be
+    None, and with both None the call IS ``fft_long_conv``, bit for bit.  A wrong shape or device raises ``ValueError``, a
+    wrong dtype ``TypeError``, before any device call.
+
+    On float32 / float16 / bfloat16 tensors, where ``fft_long_conv`` takes its plain route with stride 1, dilation 1 and
+    ``padding_mode`` constant and neither the signal is read channels-last nor the result asked for that way, the gates
+    are FUSED into the two column passes of the one call: each sample of the signal is multiplied by its pregate as it is
+    loaded, each sample of the result by its postgate as it is stored -- no product tensor exists.  Signal and gates are
+    read as contiguous (B, C, L) tensors (anything else is copied first).  The products are float32 multiplies and the
+    result is rounded once, so it has the bits of: widen every tensor to float32, run the line above, round with
+    ``.to(dtype)`` (float32 tensors: the bits of the line itself).  Every other call -- complex64, the phases route, a
+    stride, a dilation, a padding mode, channels-last signal or result, rows that hand off to ``fft_conv``,
+    FFTCONV_HALF_IO=0 -- runs the line above with torch multiplies.  ``_long_gated_route`` names the route; no switch
+    selects it.
+
+    Differentiable in signal, kernel, bias and both gates.  On the fused route autograd saves signal, kernel and the gates
+    -- never ``pregate * signal`` nor the gated result -- and the ungated c = conv + bias only when ``postgate`` needs a
+    gradient (stored by the same launch; float32 for 16-bit tensors, so that d(postgate) is rounded once).  dX and
+    d(pregate) come from ONE run of the dX primitive: ``postgate`` gates dY as it is loaded and the last pass stores
+    pregate * dZ and signal * dZ.  d(postgate) = dY * c is one torch multiply; dW and db take the routes of
+    ``fft_long_conv`` on the float32 products torch forms.  Each gradient has the bits of autograd through the line above
+    on float32 tensors, rounded once.  Double backward goes through the composed line.
+
+    A skip term needs no argument: for a causal depthwise layer ``kernel[..., 0] += D`` adds ``D * (pregate * signal)``."""
+    return _fft_long_conv_gated_impl(signal, kernel, bias, padding, groups, causal, None, pregate, postgate, stride, dilation,
+                                     padding_mode, channels_last)
+
+
+def _fft_long_conv_gated_impl(signal, kernel, bias, padding, groups, causal, spectrum, pregate, postgate, stride=1, dilation=1,
+                              padding_mode="constant", channels_last=False):
+    if pregate is None and postgate is None:
+        return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum, stride, dilation, padding_mode,
+                                   channels_last)
+    pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal, stride, dilation, padding_mode)
+    s, d, mode = _long_int("stride", stride), _long_int("dilation", dilation), _native.PAD_MODES[padding_mode]
+    length, taps = int(signal.shape[2]), int(kernel.shape[2])
+    _long_gates(signal, pregate, postgate,
+                (int(signal.shape[0]), int(kernel.shape[0]), _long_out_len(length, taps, pad_left, pad_right, bool(causal), s, d)))
+    layout = _long_call_layout(signal, channels_last)
+    route = _long_gated_route_of(_long_route_of(length, taps, pad_left, pad_right, need, bool(causal), s, d, mode, signal.dtype,
+                                                layout), s, d, mode, signal.dtype, layout, channels_last)
+    if route == "composed":
+        out = _fft_long_conv_impl(signal if pregate is None else pregate * signal, kernel, bias, padding, groups, causal,
+                                  spectrum, stride, dilation, padding_mode, channels_last)
+        return out if postgate is None else postgate * out
+    signal, kernel, bias, _ = _long_operands(signal, kernel, bias)
+    if _needs_grad(signal, kernel, bias, pregate, postgate):
+        from .autograd import FFTLongConvGatedFunction
+        return FFTLongConvGatedFunction.apply(signal, kernel, bias, pregate, postgate, pad_left, pad_right, bool(causal), groups,
+                                              spectrum)
+    plan, run = _long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, 1, 1, 0, "plain")
+    return _long_run_gated(signal, kernel, bias, pad_left, pad_right, causal, run["out_keep"], groups, spectrum,
+                           pregate=pregate, gate=postgate, plan=plan)[0]
 
 
 # ---------------------------------------------------------------------------------- long transposed filters

@@ -223,7 +223,10 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
 
     ``channels_last=True`` (keyword-only; an attribute, not part of the state_dict) returns the (B, Cout, nout) result with
     strides (nout*Cout, 1, Cout), as ``fft_long_conv`` does: ``y.transpose(1, 2)`` is then contiguous, ready for the
-    ``nn.Linear`` of a sequence model.  A signal that lies that way is read where it lies whatever this says."""
+    ``nn.Linear`` of a sequence model.  A signal that lies that way is read where it lies whatever this says.
+
+    ``forward(signal, pregate=None, postgate=None)``: with a gate the forward is ``fft_long_conv_gated`` on the cached
+    spectrum, postgate * conv(pregate * signal); without gates it is the call it always was."""
 
     channels_last = False      # (the default of a module pickled before the attribute existed)
 
@@ -244,7 +247,7 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         return (super().extra_repr() + (", causal=True" if self.causal else "")
                 + (", channels_last=True" if self.channels_last else ""))
 
-    def forward(self, signal: Tensor):
+    def forward(self, signal: Tensor, pregate: Tensor = None, postgate: Tensor = None):
         padding = self.padding if isinstance(self.padding, str) else int(self.padding[0])
         stride, dilation = int(self.stride[0]), int(self.dilation[0])
         padding_mode = "constant" if self.padding_mode == "zeros" else self.padding_mode
@@ -267,6 +270,9 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
                 plan = F_._long_forward_plan(signal, weight.shape, bias is not None, pad_left, pad_right, self.causal,
                                              self.groups, stride, dilation, mode, route)[0]
                 spectrum = self._cached_spectrum(plan)
+        if pregate is not None or postgate is not None:      # (the spectrum is that of the ungated call: the gates change no plan)
+            return F_._fft_long_conv_gated_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, pregate,
+                                                postgate, stride, dilation, padding_mode, self.channels_last)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
                                       padding_mode, self.channels_last)
 

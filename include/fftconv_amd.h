@@ -475,6 +475,30 @@ int fc_plan_takes_layout(const fc_plan* plan, int x_layout, int y_layout);
 int fc_forward_lay(const fc_plan* plan, const float* x, int x_layout, const void* w_hat, const float* bias, float* y,
                    int y_layout, void* workspace, void* hip_stream);
 
+/* ---- Gated long forward (ABI 7 extension: one new entry point; every struct and call above keeps its layout, signature
+ * and meaning, and every kernel that existed its arguments).  fc_long_forward_io with elementwise gates fused into the two
+ * column passes, which touch every sample of x and of y once anyway:
+ *   row  = pregate * x                      (pregate: like x, (B, Cin, L) contiguous, x_dtype; NULL: all ones)
+ *   c    = the plan's convolution of the rows + bias
+ *   y    = gate  * c                        (gate:  like y, (B, Cout, out_len) contiguous, y_dtype; NULL: all ones)
+ *   y2   = gate2 * c                        (y2: a second result like y, NULL: not stored; gate2: like gate, NULL: all ones)
+ * Every product is one float32 multiply of the widened operands -- of two 16-bit values: exact -- and y, y2 are rounded once,
+ * at the store; the product with c is never fused with the bias add.  So the results have the bits of widening the
+ * tensors, multiplying in float32 around fc_long_forward_io on float32 tensors, and rounding.  y2_dtype is y_dtype, or
+ * FC_F32 with gate2 NULL on a 16-bit launch: y2 then holds c unrounded (what the gradient of `gate` needs).  gate2 without
+ * y2: FC_ERR_INVALID.  A gate is read at the offset of the store it scales, the pregate at the offset of its sample of x,
+ * both through buffer resources of that tensor's row: no byte outside the tensors named is read or written.
+ *   Slabs are those of fc_long_forward_io; the gates and y2 are indexed by the batch item as x and y are.  Launches: three
+ *   per slab as ever, the gated build of a column pass where that pass has a gate (or a y2), the plain one where not;
+ *   with every optional pointer NULL the call is fc_long_forward_io.
+ *   Taken: real plans of fc_long_plan_create / _ext / _kind whose fc_long_ext words are the defaults (zero padding, no
+ *   spread, dilation 1, every output kept), (B, C, L) tensors.  Complex plans, a non-default fc_long_ext, phases plans and
+ *   decimation plans answer FC_ERR_UNSUPPORTED with text and launch nothing (multiply around the call instead); a
+ *   weight-gradient plan is another type. */
+int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, const void* pregate, const void* spectrum,
+                          const float* bias, void* y, const void* gate, void* y2, const void* gate2, int y_dtype,
+                          int y2_dtype, void* workspace, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

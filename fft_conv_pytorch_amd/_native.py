@@ -159,6 +159,7 @@ def _signatures() -> dict:
         "fc_long_wgrad_plan_destroy": (None, (vp,)),
         "fc_long_wgrad_plan_info": (i32, (vp, i64x8)),
         "fc_long_wgrad": (i32, (vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp)),
+        "fc_long_wgrad_gated": (i32, (vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp)),
         "fc_plan_takes_layout": (i32, (vp, i32, i32)),
         "fc_forward_lay": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
         "fc_long_forward_gated": (i32, (vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp)),
@@ -568,6 +569,17 @@ class LongWgradPlan(_Handle):
             dy_dtype: int = 0, dw_dtype: int = 0, x_layout: int = LONG_NCL, dy_layout: int = LONG_NCL):
         self._check(self._lib.fc_long_wgrad(self._h, x_ptr, x_dtype, x_layout, dy_ptr, dy_dtype, dy_layout, dw_ptr, dw_dtype,
                                             workspace_ptr, stream))
+
+    def run_gated(self, x_ptr: int, pregate_ptr: Optional[int], dy_ptr: int, postgate_ptr: Optional[int], dw_ptr: int,
+                  workspace_ptr: int, stream: int, x_dtype: int = 0, dy_dtype: int = 0, dw_dtype: int = 0,
+                  x_layout: int = LONG_NCL, dy_layout: int = LONG_NCL):
+        """``run`` on the rows pregate * x and postgate * dY, the gates multiplied in as the two column passes load their
+        samples (``fc_long_wgrad_gated``): no product tensor exists.  A gate lies as its tensor does, contiguous (B, C, L)
+        in that tensor's dtype; None: all ones, and with both None the call is ``run``.  A pregate on a plan with a padding
+        mode or with a channels-last x, a postgate on a strided plan or with a channels-last dY:
+        ``NotImplementedError``, nothing launched."""
+        self._check(self._lib.fc_long_wgrad_gated(self._h, x_ptr, pregate_ptr, x_dtype, x_layout, dy_ptr, postgate_ptr,
+                                                  dy_dtype, dy_layout, dw_ptr, dw_dtype, workspace_ptr, stream))
 
 
 # the tag of a long-filter key -> the class that owns its plan (forward plans and the weight-gradient plan: one cache)

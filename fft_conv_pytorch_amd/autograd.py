@@ -624,8 +624,13 @@ class FFTLongConvGatedFunction(torch.autograd.Function):
                      weight, dY and ``postgate`` trimmed alike): ``postgate`` gates dY as the first pass loads it, the last
                      pass stores dX = pregate * dZ and d(pregate) = x * dZ, or the one of them that is wanted;
         dPost        dY * c, one torch multiply (in float32, rounded once);
-        dW, db       the routes of ``FFTLongConvFunction`` (FFTCONV_LONG_WGRAD included) on the products z and g, which
-                     torch forms in float32: transient tensors.
+        dW, db       with FFTCONV_LONG_WGRAD unset (or a layer the weight-gradient plan refuses; ``F_._long_gated_dw_route``
+                     "products") the routes of ``FFTLongConvFunction`` on the products z and g, which torch forms in
+                     float32: transient tensors.  Under FFTCONV_LONG_WGRAD=1 ("gated-plan") dW is ONE run of the
+                     weight-gradient plan on the saved x, dY and the gates in their own dtype, each gate multiplied in as
+                     the plan's column pass loads its sample (``F_._long_wgrad_run`` with gates): z is never formed, and g
+                     only where db is wanted, as above, dropped before the plan runs.  dW then has the bits of that plan on
+                     the float32 products, which is what the composed line computes under the same switch.
 
     Each gradient has the bits of autograd through ``postgate * fft_long_conv(pregate * x, ...)`` on float32 tensors,
     rounded once.  A backward that itself records a graph (``create_graph=True``) differentiates that composed line."""
@@ -682,7 +687,16 @@ class FFTLongConvGatedFunction(torch.autograd.Function):
                                          gate2=gates[1] if len(gates) > 1 else None)
                 dx = res[0] if need[0] else None
                 dpre = res[len(gates) - 1] if want_dpre else None
-        if need[1] or (bias is not None and need[2]):
+        wkey = F_._long_wgrad_key(B, cin, cout, g, L, K, pad_left, pad_right, grad.shape[2], flip, 0, 1, 1)
+        if need[1] and F_._long_wgrad_eligible(wkey, signal.dtype):
+            # FFTCONV_LONG_WGRAD=1 (``F_._long_gated_dw_route`` "gated-plan"): the gates ride the plan's two column reads, so
+            # z never exists, and g only for db -- formed as below, and gone before the plan runs
+            if bias is not None and need[2]:
+                gq = grad if postgate is None else (grad.float().mul_(postgate.detach()) if low else grad * postgate.detach())
+                db = _long_grad_bias(gq, kernel.dtype)
+                del gq
+            dw = F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype, pregate=pregate, postgate=postgate)
+        elif need[1] or (bias is not None and need[2]):
             # (the float32 products torch forms; an absent gate leaves the tensor as it is)
             # (16-bit: a float32 copy times the 16-bit tensor, widened as mul_ reads it: two passes, one float32 tensor)
             wide = (lambda a, b: a.float().mul_(b)) if low else torch.mul

@@ -766,13 +766,30 @@ int fc_long_wgrad_plan_info(const fc_long_wgrad_plan* plan, int64_t info[8]) {
   return FC_OK;
 }
 
-int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
-                  int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream) {
+// fc_long_wgrad and fc_long_wgrad_gated: a side with a gate (NULL: none) runs the gated build of its column pass
+static int wgrad_run(const fc_long_wgrad_plan* plan, const void* x, const void* pregate, int x_dtype, int x_layout,
+                     const void* dy, const void* postgate, int dy_dtype, int dy_layout, void* dw, int dw_dtype,
+                     void* workspace, void* hip_stream) {
   if (!plan || !x || !dy || !dw || !workspace) return fail(FC_ERR_INVALID, "null argument");
   const WgradGeom& w = plan->w;
   int xio = 0, dyio = 0, dwio = 0;
   if (int e = wgrad_io(w, x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype, &xio, &dyio, &dwio)) return e;
   const LongGeom& g = w.f;
+  // (the gated builds are builds of the unmapped (B, C, L) column kernel: what the plain call reads through a mapped or a
+  // channels-last build takes no gate)
+  if (pregate && g.pad_mode != PAD_CONSTANT)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes a pregate on plans with pad_mode constant only: pad_mode %d reads x "
+                "through the mapped build of the column kernel, and no gated build of that exists", g.pad_mode);
+  if (pregate && x_layout == FC_LONG_NLC)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes a pregate with a (B, C, L) x only: a channels-last x is read by the "
+                "channels-last build of the column kernel, and no gated build of that exists");
+  if (postgate && g.step > 1)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes a postgate on plans with stride 1 only: at stride %lld dY is read "
+                "spread over the grid of the stride by the mapped build of the column kernel, and no gated build of that exists",
+                (long long)g.step);
+  if (postgate && dy_layout == FC_LONG_NLC)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes a postgate with a (B, C, L) dY only: a channels-last dY is read by "
+                "the channels-last build of the column kernel, and no gated build of that exists");
   const fc_long_plan& fp = *plan->f;
   hipStream_t st = (hipStream_t)hip_stream;
   f2* const w1x = (f2*)workspace;
@@ -788,7 +805,8 @@ int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, in
     a.src = (const float*)x; a.src_io = xio;
     a.w1 = w1x;
     a.C = (int)g.Cin;
-    FC_HIP(fp.cols->cols_fwd(a, g.pad_mode != PAD_CONSTANT, x_layout == FC_LONG_NLC, np, st));
+    if (pregate) FC_HIP(fp.cols->cols_fwd_gated(a, LongGates{(const float*)pregate}, np, st));
+    else FC_HIP(fp.cols->cols_fwd(a, g.pad_mode != PAD_CONSTANT, x_layout == FC_LONG_NLC, np, st));
     // dY: rows of nout samples spread over the grid of the stride, zero elsewhere
     LongArgs b = base_args(fp);
     b.pair0 = (int)pair0;
@@ -798,7 +816,9 @@ int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, in
     b.L = (int)g.nout; b.padl = 0;
     b.pad_mode = PAD_CONSTANT; b.mpadl = 0; b.mpadr = 0;
     b.src_up = (int)g.step; b.d_up = make_fastdiv((unsigned)g.step);
-    FC_HIP(fp.cols->cols_fwd(b, g.step > 1, dy_layout == FC_LONG_NLC, np, st));
+    // (the gated build reads the words above -- L, padl, C -- and the gate, which lies as dY does, in LongGates::pregate)
+    if (postgate) FC_HIP(fp.cols->cols_fwd_gated(b, LongGates{(const float*)postgate}, np, st));
+    else FC_HIP(fp.cols->cols_fwd(b, g.step > 1, dy_layout == FC_LONG_NLC, np, st));
     // the product summed over the pairs of the slab, transformed back into W2 (a later slab adds)
     LongArgs r = base_args(fp);
     r.w1 = w1x; r.spec = w1dy; r.w2 = w2;
@@ -824,6 +844,17 @@ int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, in
   if (behind > 0)
     FC_HIP(hipMemset2DAsync((char*)dw + (first + g.keff) * es, (size_t)(g.K * es), 0, (size_t)(behind * es), (size_t)w.rows, st));
   return FC_OK;
+}
+
+int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
+                  int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream) {
+  return wgrad_run(plan, x, nullptr, x_dtype, x_layout, dy, nullptr, dy_dtype, dy_layout, dw, dw_dtype, workspace, hip_stream);
+}
+
+int fc_long_wgrad_gated(const fc_long_wgrad_plan* plan, const void* x, const void* pregate, int x_dtype, int x_layout,
+                        const void* dy, const void* postgate, int dy_dtype, int dy_layout, void* dw, int dw_dtype,
+                        void* workspace, void* hip_stream) {
+  return wgrad_run(plan, x, pregate, x_dtype, x_layout, dy, postgate, dy_dtype, dy_layout, dw, dw_dtype, workspace, hip_stream);
 }
 
 }  // extern "C"

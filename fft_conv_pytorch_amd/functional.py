@@ -802,24 +802,41 @@ def _long_wgrad_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=
     return "plan" if _long_wgrad_eligible(key, dtype) else "exchanged"
 
 
-def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype: torch.dtype) -> Tensor:
+def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype: torch.dtype, *,
+                    pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
     """dW (``wshape``, ``out_dtype``) of the layer ``key`` describes (``_long_wgrad_key``) on its weight-gradient plan, no
     autograd.  ``signal`` (B, Cin, L) and ``grad`` (B, Cout, nout) are float32, float16 or bfloat16, each on its own, and
     each is read where it lies: contiguous, or as the channels-last view ``_long_layout`` recognises (another layout, a
     block of 2**31 bytes or more, FFTCONV_LONG_NLC=0: one torch copy of that tensor).  No transposed operand and no
-    flipped copy of the result exists; the float32 result is rounded once as it is stored."""
+    flipped copy of the result exists; the float32 result is rounded once as it is stored.
+
+    ``pregate`` (like ``signal``) and ``postgate`` (like ``grad``), each in its tensor's dtype: dW of the rows
+    pregate * signal and the gradient postgate * grad, multiplied as the column passes load them
+    (``LongWgradPlan.run_gated``: neither product exists, the bits are those of this call on the float32 products).  A
+    gated side and its gate are read as contiguous (B, C, L) tensors.  The plan is the one of the call without gates; what
+    it refuses under a gate (a padding mode under ``pregate``, a stride under ``postgate``) raises ``NotImplementedError``."""
+    gates = (pregate, postgate)
     tensors, layouts = [], []
-    for t in (signal.detach(), grad.detach()):
-        nlc = _long_reads_nlc(t)
+    for t, gate in zip((signal.detach(), grad.detach()), gates):
+        # (the kernel reads the gate at the offsets of its tensor: same shape, element size and device, or it reads elsewhere)
+        if gate is not None and (tuple(gate.shape) != tuple(t.shape) or gate.dtype != t.dtype or gate.device != t.device):
+            raise ValueError(f"a gate of the weight-gradient plan must match its tensor {tuple(t.shape)} {t.dtype} on "
+                             f"{t.device}, got {tuple(gate.shape)} {gate.dtype} on {gate.device}")
+        nlc = gate is None and _long_reads_nlc(t)
         tensors.append(t if nlc else t.contiguous())
         layouts.append(_native.LONG_NLC if nlc else _native.LONG_NCL)
     x, dy = tensors
+    pregate, postgate = (None if t is None else t.detach().contiguous() for t in gates)
     plan = _cached_plan(_device_index(x.device), ("long_wgrad",) + tuple(key))
     with torch.cuda.device(x.device):
         dw = torch.empty(tuple(wshape), dtype=out_dtype, device=x.device)
         ws, ws_ptr, stream = _scratch_and_stream(plan, x.device)
-        plan.run(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws_ptr, stream, _DTYPE_CODES[x.dtype],
-                 _DTYPE_CODES[dy.dtype], _DTYPE_CODES[out_dtype], layouts[0], layouts[1])
+        codes = (_DTYPE_CODES[x.dtype], _DTYPE_CODES[dy.dtype], _DTYPE_CODES[out_dtype], layouts[0], layouts[1])
+        if pregate is None and postgate is None:
+            plan.run(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), ws_ptr, stream, *codes)
+        else:
+            ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+            plan.run_gated(x.data_ptr(), ptr(pregate), dy.data_ptr(), ptr(postgate), dw.data_ptr(), ws_ptr, stream, *codes)
     return dw
 
 
@@ -1008,6 +1025,29 @@ def _long_gated_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=
     return _long_gated_route_of(route, stride, dilation, mode, dtype, x_layout, bool(channels_last))
 
 
+def _long_gated_dw_route(signal_shape, kernel_shape, padding=0, groups=1, causal=False, dtype=torch.float32, *, stride=1,
+                         dilation=1, padding_mode="constant", x_layout="ncl", channels_last=False) -> str:
+    """Where the weight gradient of a ``fft_long_conv_gated`` call with a gate comes from in
+    ``FFTLongConvGatedFunction.backward`` (pure: shapes, numbers, FFTCONV_LONG_WGRAD read per call, and the library's
+    geometry call, which touches no device):
+
+    ``"gated-plan"``  ``_long_gated_route`` "fused" and a layer the weight-gradient plan takes (``_long_wgrad_eligible``:
+                      FFTCONV_LONG_WGRAD=1 and a geometry the library does not refuse): ``_long_wgrad_run`` with the gates,
+                      x, dY and the gates read where they lie in their own dtype, no product tensor;
+    ``"products"``    everything else: the route of ``fft_long_conv``'s weight gradient on the float32 products
+                      pregate * x and postgate * dY that torch forms (and, off the fused route, whatever the composed line's
+                      autograd does)."""
+    route, pad_left, pad_right, stride, dilation, mode = _long_route_numbers(
+        signal_shape, kernel_shape, stride, padding, dilation, groups, causal, padding_mode, dtype, x_layout)
+    if _long_gated_route_of(route, stride, dilation, mode, dtype, x_layout, bool(channels_last)) != "fused":
+        return "products"
+    length, taps = int(signal_shape[2]), int(kernel_shape[2])
+    nout = _long_out_len(length, taps, pad_left, pad_right, bool(causal), 1, 1)
+    key = _long_wgrad_key(signal_shape[0], signal_shape[1], kernel_shape[0], groups, length, taps, pad_left, pad_right, nout,
+                          causal, 0, 1, 1)
+    return "gated-plan" if _long_wgrad_eligible(key, dtype) else "products"
+
+
 def _long_run_gated(signal: Tensor, kernel: Optional[Tensor], bias: Optional[Tensor], pad_left: int, pad_right: int,
                     flip: bool, out_keep: int, groups: int, spectrum: Optional[KernelSpectrum] = None, *,
                     pregate: Optional[Tensor] = None, gate: Optional[Tensor] = None, gate2: Optional[Tensor] = None,
@@ -1068,7 +1108,10 @@ def fft_long_conv_gated(signal: Tensor, kernel: Tensor, bias: Tensor = None, pad
     gradient (stored by the same launch; float32 for 16-bit tensors, so that d(postgate) is rounded once).  dX and
     d(pregate) come from ONE run of the dX primitive: ``postgate`` gates dY as it is loaded and the last pass stores
     pregate * dZ and signal * dZ.  d(postgate) = dY * c is one torch multiply; dW and db take the routes of
-    ``fft_long_conv`` on the float32 products torch forms.  Each gradient has the bits of autograd through the line above
+    ``fft_long_conv`` on the float32 products torch forms -- except under FFTCONV_LONG_WGRAD=1 (read per call;
+    ``_long_gated_dw_route`` "gated-plan"), where dW comes from the weight-gradient plan with both gates inside its column
+    reads: the saved tensors are read in their own dtype and neither product exists (the bits of dW are those of that plan
+    on the products).  Each gradient has the bits of autograd through the line above
     on float32 tensors, rounded once.  Double backward goes through the composed line.
 
     A skip term needs no argument: for a causal depthwise layer ``kernel[..., 0] += D`` adds ``D * (pregate * signal)``."""

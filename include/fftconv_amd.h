@@ -448,6 +448,26 @@ int fc_long_wgrad_plan_info(const fc_long_wgrad_plan* plan, int64_t info[8]);
 int fc_long_wgrad(const fc_long_wgrad_plan* plan, const void* x, int x_dtype, int x_layout, const void* dy, int dy_dtype,
                   int dy_layout, void* dw, int dw_dtype, void* workspace, void* hip_stream);
 
+/* fc_long_wgrad with elementwise gates inside its two column reads (ABI 7 extension: one new entry point; the plan, its
+ * geometry, its info words and its workspace are those of fc_long_wgrad): dW of the plan's layer for the signal rows
+ * pregate * x and the output gradient postgate * dY, neither of which exists as a tensor.
+ *   pregate   like x:  (B, Cin, L) contiguous, x_dtype;  NULL: all ones
+ *   postgate  like dY: (B, Cout, out_len) contiguous, dy_dtype; NULL: all ones
+ * Each product is one float32 multiply of the widened operands as the sample is loaded -- of two 16-bit values: exact -- so
+ * dW has the bits of fc_long_wgrad on the float32 products.  A gate is read at the offset of its sample, through a buffer
+ * resource of that tensor's row; the gates advance with the slabs as x and dY do.  No byte outside the five tensors and the
+ * workspace is read or written.
+ *   Launches: those of fc_long_wgrad per slab; a side with a gate runs the gated build of the forward column pass (the one
+ *   fc_long_forward_gated runs for a pregate), a side without runs the build it runs in fc_long_wgrad.  With both gates
+ *   NULL the call is fc_long_wgrad.
+ *   The gated builds are builds of the unmapped (B, C, L) column kernel, so these answer FC_ERR_UNSUPPORTED with text and
+ *   launch nothing: a pregate on a plan whose pad_mode is not constant, a pregate with x_layout FC_LONG_NLC, a postgate on
+ *   a plan with stride > 1 (dY is then read spread over the grid of the stride), a postgate with dy_layout FC_LONG_NLC.
+ *   The dilation is free: it only chooses the lags the last pass keeps. */
+int fc_long_wgrad_gated(const fc_long_wgrad_plan* plan, const void* x, const void* pregate, int x_dtype, int x_layout,
+                        const void* dy, const void* postgate, int dy_dtype, int dy_layout, void* dw, int dw_dtype,
+                        void* workspace, void* hip_stream);
+
 /* ---- Channels-last tensors of the 2-D / 3-D plans (ABI 7 extension: new entry points only; fc_desc keeps its size, every
  * call above keeps its signature and meaning, and the route words of fc_debug_route are what they were).  The layout of x
  * and of y is an argument of the call: plan creation, the plan's route, its spectrum and its workspace do not depend on it.

@@ -95,6 +95,11 @@ class FcLongWgradDesc(ctypes.Structure):
     ]
 
 
+class FcLongBlocksDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_blocks_desc`` (the plain real row in overlap-save blocks of ``block_points`` points)."""
+    _fields_ = [("row", FcLongDesc), ("block_points", ctypes.c_int64)]
+
+
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
 FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans; 2-D / 3-D fc_desc)
 # enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
@@ -105,6 +110,9 @@ LONG_NLC_MAX_BYTES = 1 << 31      # one batch item's (L, C) block of a channels-
 # enum fc_nd_layout: how x and y of fc_forward_lay lie, (B, C, *spatial) contiguous or channels-last (B, *spatial, C)
 ND_PLANAR, ND_CHANNELS_LAST = 0, 1
 LONG_INFO_WORDS = ("N1", "N2", "out_len", "spectrum_bytes", "workspace_bytes", "slabs", "out_block", "slab_pairs")
+# the four words a blocks geometry call fills in besides: kept samples per block, blocks per row, units B * T, unit pairs
+LONG_BLOCKS_WORDS = ("V", "T", "U", "pairs")
+LONG_BLOCK_MIN, LONG_BLOCK_MAX = 1 << 12, 1 << 24      # block_points: a power of two in this range, 0 = the planner's choice
 # ... of a weight-gradient plan: no spectrum; the taps of a row and how many of their lags are transformed
 LONG_WGRAD_INFO_WORDS = ("N1", "N2", "taps", "lags", "workspace_bytes", "slabs", "out_block", "slab_pairs")
 
@@ -114,6 +122,7 @@ def _signatures() -> dict:
     ptr = ctypes.POINTER
     desc, out, i64x8 = ptr(FcDesc), ptr(vp), ptr(ctypes.c_int64 * 8)
     ldesc, lext, wdesc = ptr(FcLongDesc), ptr(FcLongExt), ptr(FcLongWgradDesc)
+    bdesc, i64, i64x4 = ptr(FcLongBlocksDesc), ctypes.c_int64, ptr(ctypes.c_int64 * 4)
     return {
         "fc_version": (i32, ()),
         "fc_last_error": (ctypes.c_char_p, ()),
@@ -160,6 +169,10 @@ def _signatures() -> dict:
         "fc_long_wgrad_plan_info": (i32, (vp, i64x8)),
         "fc_long_wgrad": (i32, (vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, vp)),
         "fc_long_wgrad_gated": (i32, (vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp)),
+        "fc_long_blocks_geometry": (i32, (bdesc, i64x8, i64x4)),
+        "fc_long_blocks_plan_create": (i32, (bdesc, out)),
+        "fc_long_wgrad_blocks_geometry": (i32, (wdesc, i64, i64x8, i64x4)),
+        "fc_long_wgrad_blocks_plan_create": (i32, (wdesc, i64, out)),
         "fc_plan_takes_layout": (i32, (vp, i32, i32)),
         "fc_forward_lay": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
         "fc_long_forward_gated": (i32, (vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp)),
@@ -531,6 +544,43 @@ class LongDecimPlan(LongPlan):
     _create, _describe = "fc_long_decim_plan_create", staticmethod(lambda key: (decim_desc(key),))
 
 
+def blocks_desc(key: Tuple) -> FcLongBlocksDesc:
+    """``struct fc_long_blocks_desc`` of a blocks-plan key: the eleven words of a plain long-plan key, then block_points
+    (0: the planner's choice)."""
+    if len(key) != 12:
+        raise ValueError(f"a blocks-plan key has 12 words, got {len(key)}")
+    return FcLongBlocksDesc(long_desc(tuple(key[:11])), int(key[11]))
+
+
+def _blocks_words(call: str, names: Tuple, *args) -> dict:
+    """The eight info words and the four block words (LONG_BLOCKS_WORDS) of a blocks geometry call, by name."""
+    lib = load_library()
+    info, blocks = (ctypes.c_int64 * 8)(), (ctypes.c_int64 * 4)()
+    _check(lib, getattr(lib, call)(*_refs(args), ctypes.byref(info), ctypes.byref(blocks)))
+    words = {name: int(info[i]) for i, name in enumerate(names)}
+    words.update({name: int(blocks[i]) for i, name in enumerate(LONG_BLOCKS_WORDS)})
+    return words
+
+
+def blocks_geometry(key: Tuple) -> dict:
+    """``fc_long_blocks_geometry``: the info words of the blocks plan this key would get and V, T, U, pairs (no device)."""
+    return _blocks_words("fc_long_blocks_geometry", LONG_INFO_WORDS, blocks_desc(key))
+
+
+class LongBlocksPlan(LongPlan):
+    """A long plan that runs the plain real primitive (zero padding, stride 1, dilation 1) on a row longer than its
+    transform, in overlap-save blocks of ``N1 * N2`` points against one filter spectrum (``fc_long_blocks_plan_create``).
+    ``transform_kernel`` takes the (Cout, Cin/groups, K) weight, ``forward`` x (B, Cin, L) and y (B, Cout, out_len),
+    contiguous; ``forward_lay`` with LONG_NLC and ``forward_gated`` raise ``NotImplementedError``.  ``blocks``: V, T, U, pairs."""
+
+    _create, _describe = "fc_long_blocks_plan_create", staticmethod(lambda key: (blocks_desc(key),))
+
+    def __init__(self, key: Tuple, device_index: int = 0):
+        super().__init__(key, device_index)
+        words = blocks_geometry(key)
+        self.blocks = {name: words[name] for name in LONG_BLOCKS_WORDS}
+
+
 def wgrad_desc(key: Tuple) -> FcLongWgradDesc:
     """``struct fc_long_wgrad_desc`` of a weight-gradient key: (batch, cin, cout, groups, L, K, pad_left, pad_right, out_len,
     flip, pad_mode, stride, dilation)."""
@@ -582,8 +632,32 @@ class LongWgradPlan(_Handle):
                                                   dy_dtype, dy_layout, dw_ptr, dw_dtype, workspace_ptr, stream))
 
 
+def wgrad_blocks_geometry(key: Tuple) -> dict:
+    """``fc_long_wgrad_blocks_geometry`` of a key of 14 words, a weight-gradient key and block_points: the info words of the
+    weight-gradient plan by blocks and V, T, U, pairs (no device)."""
+    return _blocks_words("fc_long_wgrad_blocks_geometry", LONG_WGRAD_INFO_WORDS, wgrad_desc(tuple(key[:13])),
+                         ctypes.c_int64(int(key[13])))
+
+
+class LongWgradBlocksPlan(LongWgradPlan):
+    """The weight-gradient plan of a layer whose forward runs by blocks (``fc_long_wgrad_blocks_plan_create``; a key of 14
+    words: a weight-gradient key with stride 1, dilation 1 and pad_mode constant, then block_points).  ``run`` takes
+    contiguous (B, C, L) tensors; ``run_gated`` with a gate and channels-last operands raise ``NotImplementedError``."""
+
+    def __init__(self, key: Tuple, device_index: int = 0):
+        if len(key) != 14:
+            raise ValueError(f"a weight-gradient key by blocks has 14 words, got {len(key)}")
+        _, handle = self._open("fc_long_wgrad_blocks_plan_create", wgrad_desc(tuple(key[:13])), ctypes.c_int64(int(key[13])))
+        self.key = key
+        self.device_index = int(device_index)
+        self.info = _info_words("fc_long_wgrad_plan_info", LONG_WGRAD_INFO_WORDS, handle)
+        self.workspace_bytes = self.info["workspace_bytes"]
+
+
 # the tag of a long-filter key -> the class that owns its plan (forward plans and the weight-gradient plan: one cache)
 _PLAN_TAGS = {"long": LongPlan, "long_phases": LongPhasesPlan, "long_decim": LongDecimPlan, "long_wgrad": LongWgradPlan}
+# ... of the plans by blocks (a table of their own: the one above is what it was)
+_BLOCKS_PLAN_TAGS = {"long_blocks": LongBlocksPlan, "long_wgrad_blocks": LongWgradBlocksPlan}
 
 
 # Plan cache keyed on (device, descriptor): least-recently-used, bounded -- variable-length inputs would
@@ -611,7 +685,7 @@ def get_plan(device_index: int, key: Tuple) -> Plan:
         plan = _plans.get(full)
         if plan is None:
             # (a long-filter key is tagged: it shares the cache and its bound with the convolution plans)
-            cls = _PLAN_TAGS.get(key[0]) if key and isinstance(key[0], str) else None
+            cls = (_PLAN_TAGS.get(key[0]) or _BLOCKS_PLAN_TAGS.get(key[0])) if key and isinstance(key[0], str) else None
             plan = cls(key[1:], device_index) if cls is not None else Plan(key, device_index)
             _plans[full] = plan
             while len(_plans) > max(1, PLAN_CACHE_SIZE):

@@ -532,17 +532,26 @@ class FFTLongConvFunction(torch.autograd.Function):
     and dX is written in the signal's layout (after a padding-mode fold, which torch runs on whatever layout dX has, one
     torch copy restores it; so does one after the dX by phases, whose plan writes contiguous rows: a signal that lies
     that way runs by phases under FFTCONV_LONG_NLC=0 only).  dW's operands are transposed copies anyway and torch builds
-    them from whichever layout the tensors have; db sums a contiguous dY, so a strided dY is copied for it."""
+    them from whichever layout the tensors have; db sums a contiguous dY, so a strided dY is copied for it.
+
+    ``blocks`` = (the ``blocks`` keyword of the call, the block_points its forward runs by or None;
+    ``F_._long_blocks_route_of``).  A forward by blocks runs the blocks plan.  dX is the same primitive on dY with the
+    opposite tap order and runs by blocks under the keyword's own rule (``F_._long_blocks_choice`` on dX's numbers: with an
+    int N by blocks of N wherever its row needs more, with True only where its row does not fit 2**24 points).  dW of a
+    forward that ran by blocks comes from the weight-gradient plan by blocks whatever FFTCONV_LONG_WGRAD says (the
+    exchanged route would need dY as a filter of nout taps); db is as ever."""
 
     @staticmethod
     def forward(ctx, signal, kernel, bias, pad_left, pad_right, causal, groups, spectrum, stride=1, dilation=1,
-                padding_mode="constant", channels_last=False, decim=False):
+                padding_mode="constant", channels_last=False, decim=False, blocks=(False, None)):
         ctx.save_for_backward(signal, kernel)
         ctx.cfg = (int(pad_left), int(pad_right), bool(causal), int(groups), bias is not None, int(stride), int(dilation),
                    padding_mode)
         ctx.decim = bool(decim)
+        ctx.blocks = blocks
+        route = "blocks" if blocks[1] is not None else "phases" if decim else "plain"
         run = F_._long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, stride,
-                                    dilation, F_._native.PAD_MODES[padding_mode], "phases" if decim else "plain")[1]
+                                    dilation, F_._native.PAD_MODES[padding_mode], route, block_points=blocks[1])[1]
         return F_._long_run(signal, kernel, bias, pad_left, pad_right, causal, groups=groups, spectrum=spectrum,
                             channels_last=channels_last, **run)
 
@@ -566,7 +575,7 @@ class FFTLongConvFunction(torch.autograd.Function):
                     dx = F_._as_channels_last(dx)
             if ctx.needs_input_grad[1]:
                 dw = _long_dw_by_phases(signal.detach(), grad, g, pad_left, s, K).to(kernel.dtype)
-            return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 10
+            return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 11
         if ctx.needs_input_grad[0]:
             wt = kernel.detach().view(g, cog, cig, K).transpose(1, 2).reshape(cin, cog, K).contiguous()
             # zero padding: the gradient of the row itself; another mode: of the padded row, folded below
@@ -581,9 +590,17 @@ class FFTLongConvFunction(torch.autograd.Function):
                 dx = torch.zeros_like(signal)          # (keeps the signal's strides)
             else:
                 fold32 = mode != 0 and grad.dtype in F_._LOW_PRECISION
-                dx = F_._long_run(dy, wt, None, lead, max(tail, 0), not flip, keep, g,
-                                  out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d, conj_kernel=cx,
-                                  channels_last=x_nlc)
+                tail = max(tail, 0)
+                # (the keyword's rule on dX's own row: cout -> cin channels, dY's length, the row of lead + dY + tail samples)
+                points = F_._long_blocks_choice(ctx.blocks[0], B, cout, cin, g, dy.shape[2], K, lead, tail, keep, not flip,
+                                                lead + dy.shape[2] + tail, s, d, mode, dy.dtype, F_._long_route_layout(dy), x_nlc)
+                if points is not None:
+                    plan = F_._long_blocks_plan(dy, cin, g, K, lead, tail, not flip, keep, False, points)
+                    dx = F_._long_run(dy, wt, None, lead, tail, not flip, keep, g, plan=plan)
+                else:
+                    dx = F_._long_run(dy, wt, None, lead, tail, not flip, keep, g,
+                                      out_dtype=torch.float32 if fold32 else None, src_up=s, tap_dil=d, conj_kernel=cx,
+                                      channels_last=x_nlc)
                 if mode != 0:
                     # (_pad_adjoint folds equal paddings: a row padded by the larger one has zero gradient at the rest)
                     p = max(pad_left, pad_right)
@@ -592,9 +609,12 @@ class FFTLongConvFunction(torch.autograd.Function):
                     dx = dx.to(grad.dtype)
                     if x_nlc:
                         dx = F_._as_channels_last(dx)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and ctx.blocks[1] is not None:
+            wkey = F_._long_wgrad_key(B, cin, cout, g, L, K, pad_left, pad_right, grad.shape[2], flip, 0, 1, 1)
+            dw = F_._long_wgrad_run(signal, grad, tuple(kernel.shape), wkey, kernel.dtype, block_points=ctx.blocks[1])
+        elif ctx.needs_input_grad[1]:
             dw = _long_grad_weight(signal, grad, kernel, g, pad_left, pad_right, flip, mode, s, d, cx)
-        return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 10
+        return (dx, dw, _long_grad_bias(grad, kernel.dtype) if want_db else None) + (None,) * 11
 
 
 def _long_grad_weight(signal: Tensor, grad: Tensor, kernel: Tensor, g: int, pad_left: int, pad_right: int, flip: bool,

@@ -49,13 +49,18 @@ struct LongGeom {
   // a decimation plan (decim_geometry below): Cin and Cig above count the s decimated rows of every input channel, L and K
   // are those of the tensors
   int64_t dc_s, dc_padl, dc_flip;             // stride (0: not a decimation plan), the phase origin (pad_left), the tap order
+  // a blocks plan (blocks_geometry below): npairs counts pairs of units (batch item, block); N is the block's
+  int64_t bk_V, bk_T, bk_U;                   // kept samples per block, blocks per row (0: not a blocks plan), units B * T
+  int pad_only;                               // every kept output sees padding only: padl is a marker, not a place (long_row)
 };
 
 bool is_tile_len(long long v) { return v >= 64 && v <= 4096 && (v & (v - 1)) == 0; }
 
 const fc_long_ext kDefaultExt = {0, 1, 1, 1};
 
-int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, LongGeom* out) {
+// The row of a long plan: descriptor checks, the output length, the taps that are read and where the data lies (everything
+// up to g.need, the points one cyclic transform of the whole row must hold)
+int long_row(const fc_long_desc* desc, const fc_long_ext* ext, int kind, LongGeom* out) {
   if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
   if (kind & ~(FC_LONG_COMPLEX | FC_LONG_CONJ_SIGNAL | FC_LONG_CONJ_TAPS)) return fail(FC_ERR_INVALID, "unknown long-plan kind %d", kind);
   const bool cx = (kind & FC_LONG_COMPLEX) != 0;
@@ -122,6 +127,7 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
   if (khi < klo) {               // every kept output sees padding only: one tap against a row that reads as zero, y = bias
     g.keff = 1; g.tap0 = 0; g.tstep = 1;
     g.padl = kMaxN + 1;          // the data lies past every position of the transform
+    g.pad_only = 1;
   } else {
     g.keff = khi - klo + 1;
     g.padl = d.pad_left - dil * klo;
@@ -129,9 +135,15 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
     g.tstep = d.flip ? -1 : 1;
   }
   g.need = step * (g.nout - 1) + dil * (g.keff - 1) + 1;
-  if (g.need > kMaxN)
-    return fail(FC_ERR_UNSUPPORTED, "the row needs a transform of %lld points; the long-filter path stops at 2^24 = %lld "
-                "(4096 x 4096)", (long long)g.need, (long long)kMaxN);
+  g.kind = kind;
+  *out = g;
+  return FC_OK;
+}
+
+// The transform of a plan whose row is known: N = N1 * N2 for g.need points, the slabs over `npairs` rows of the transform
+// per channel, sizes and the grid check.  `exact`: g.need is the N of a blocks plan, which FFTCONV_LONG_N must factor
+int long_factor(LongGeom& g, int64_t npairs, bool exact) {
+  const bool cx = (g.kind & FC_LONG_COMPLEX) != 0;
   // smallest N = N1 * N2 >= need with both factors tile lengths; the most balanced split, N2 >= N1
   int lg = 12;
   while (((int64_t)1 << lg) < g.need) ++lg;
@@ -144,14 +156,16 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
         return fail(FC_ERR_INVALID, "FFTCONV_LONG_N=%s: expected <N1>x<N2>, both powers of two from 64 to 4096", env);
       if (n1 * n2 < g.need)
         return fail(FC_ERR_INVALID, "FFTCONV_LONG_N=%s holds %lld points but the row needs %lld", env, n1 * n2, (long long)g.need);
+      if (exact && n1 * n2 != g.need)
+        return fail(FC_ERR_INVALID, "FFTCONV_LONG_N=%s holds %lld points but the blocks of the plan have %lld", env, n1 * n2,
+                    (long long)g.need);
       g.N1 = (int)n1; g.N2 = (int)n2;
     }
   }
   g.N = (int64_t)g.N1 * g.N2;
   const LongImpl* rows = find_long(g.N2);
   g.ob = rows ? rows->ob : 1;
-  g.kind = kind;
-  g.npairs = cx ? g.B : (g.B + 1) / 2;
+  g.npairs = npairs;
   int64_t budget_mb = kDefaultBudgetMB;
   if (const char* env = getenv("FFTCONV_LONG_WS_MB"))
     if (*env && atoll(env) > 0) budget_mb = atoll(env);
@@ -163,10 +177,92 @@ int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, Lo
   // grids are 32-bit: (blocks per row) x rows
   const int64_t worst = std::max<int64_t>(g.N2 / 2, g.N1 / 2) * std::max<int64_t>(g.slab_pairs * std::max(g.Cin, g.Cout), 1);
   if (worst > 0x7fffffffLL)
-    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld batch %s x %lld channels x %lld points exceeds the 2^31 workgroups of one "
-                "launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, cx ? "items" : "pairs", (long long)std::max(g.Cin, g.Cout), (long long)g.N);
+    return fail(FC_ERR_UNSUPPORTED, "a slab of %lld %s x %lld channels x %lld points exceeds the 2^31 workgroups of one "
+                "launch: lower FFTCONV_LONG_WS_MB", (long long)g.slab_pairs, exact ? "unit pairs" : cx ? "batch items" : "batch pairs",
+                (long long)std::max(g.Cin, g.Cout), (long long)g.N);
+  return FC_OK;
+}
+
+int long_geometry(const fc_long_desc* desc, const fc_long_ext* ext, int kind, LongGeom* out) {
+  LongGeom g;
+  int st = long_row(desc, ext, kind, &g);
+  if (st != FC_OK) return st;
+  if (g.need > kMaxN)
+    return fail(FC_ERR_UNSUPPORTED, "the row needs a transform of %lld points; the long-filter path stops at 2^24 = %lld "
+                "(4096 x 4096)", (long long)g.need, (long long)kMaxN);
+  if ((st = long_factor(g, (kind & FC_LONG_COMPLEX) ? g.B : (g.B + 1) / 2, false)) != FC_OK) return st;
   *out = g;
   return FC_OK;
+}
+
+// A row longer than the transform as overlap-save blocks (include/fftconv_amd.h "Rows in overlap-save blocks"): the row of
+// the plain real plan with the default fc_long_ext, cut into T blocks of N points that start hop = N - keff + 1 samples
+// apart; unit u = b*T + t, two units to a complex row.  Everything but the two tensor sides is the long plan of U / 2
+// "batch pairs" at N points.
+constexpr int64_t kMinBlock = 4096;
+
+int blocks_points(int64_t keff, int64_t block_points, int64_t* N) {
+  if (block_points == 0) {
+    // the planner's choice: blocks keep 3/4 of their points, N1 = 512 still reads whole 128-byte segments
+    int64_t n = (int64_t)1 << 18;
+    while (n < 4 * keff && n < kMaxN) n <<= 1;
+    *N = n;
+    return FC_OK;
+  }
+  if (block_points < kMinBlock || block_points > kMaxN || (block_points & (block_points - 1)))
+    return fail(FC_ERR_INVALID, "block_points (%lld) must be a power of two from 4096 to 2^24, or 0 for the planner's choice",
+                (long long)block_points);
+  *N = block_points;
+  return FC_OK;
+}
+
+int blocks_row(const fc_long_desc* desc, int64_t block_points, LongGeom* out) {
+  LongGeom g;
+  int st = long_row(desc, nullptr, FC_LONG_REAL, &g);
+  if (st != FC_OK) return st;
+  int64_t N = 0;
+  if ((st = blocks_points(g.keff, block_points, &N)) != FC_OK) return st;
+  if (g.keff > N / 2)
+    return fail(FC_ERR_UNSUPPORTED, "a filter of K = %lld taps (%lld of them read) against blocks of N = %lld points: a block must "
+                "keep at least half of its points, so it takes at most N / 2 = %lld taps", (long long)g.K, (long long)g.keff,
+                (long long)N, (long long)(N / 2));
+  // (a row of y lies behind one buffer resource, as a row of x does)
+  if (g.nout > (int64_t)1 << 29)
+    return fail(FC_ERR_UNSUPPORTED, "an output row of %lld samples: rows of more than 2^29 samples are not addressed by the "
+                "long-filter kernels", (long long)g.nout);
+  g.bk_V = N - g.keff + 1;
+  g.bk_T = (g.nout + g.bk_V - 1) / g.bk_V;
+  if (g.B > 0x7ffffff0LL / g.bk_T)
+    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld blocks exceed the 2^31 units of a blocks plan", (long long)g.B,
+                (long long)g.bk_T);
+  g.bk_U = g.B * g.bk_T;
+  // (every kept output sees padding only: the data lies past every position t*V + q of every block, all below 2^31.  A
+  // real padl is a place in the row, min(pad_left, nout - 1) <= 2^29, and stays what it is: t*V + q - padl fits an int)
+  if (g.pad_only) g.padl = 0x7fffffff;
+  g.need = N;
+  *out = g;
+  return FC_OK;
+}
+
+int blocks_geometry(const fc_long_blocks_desc* desc, LongGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  LongGeom g;
+  int st = blocks_row(&desc->row, desc->block_points, &g);
+  if (st != FC_OK) return st;
+  if ((st = long_factor(g, (g.bk_U + 1) / 2, true)) != FC_OK) return st;
+  *out = g;
+  return FC_OK;
+}
+
+void fill_blocks(const LongGeom& g, int64_t blocks[4]) {
+  blocks[0] = g.bk_V; blocks[1] = g.bk_T; blocks[2] = g.bk_U; blocks[3] = (g.bk_U + 1) / 2;
+}
+
+LongBlocks blocks_args(const LongGeom& g, int64_t win) {
+  LongBlocks bk{};
+  bk.d_T = make_fastdiv((unsigned)g.bk_T);
+  bk.U = (int)g.bk_U; bk.hop = (int)g.bk_V; bk.win = (int)win;
+  return bk;
 }
 
 // A transposed convolution of stride s and dilation 1 as s ordinary convolutions of the unspread row:
@@ -283,6 +379,8 @@ struct WgradGeom {
   size_t workspace_bytes;
 };
 
+int wgrad_sizes(WgradGeom& w, WgradGeom* out);
+
 int wgrad_geometry(const fc_long_wgrad_desc* desc, WgradGeom* out) {
   if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
   const fc_long_wgrad_desc& d = *desc;
@@ -297,6 +395,32 @@ int wgrad_geometry(const fc_long_wgrad_desc* desc, WgradGeom* out) {
   WgradGeom w{};
   const int st = long_geometry(&f, &e, FC_LONG_REAL, &w.f);
   if (st != FC_OK) return st;
+  return wgrad_sizes(w, out);
+}
+
+// the blocks twin: the row of the plain layer in overlap-save blocks of block_points (blocks_row above); x is read through
+// the N-point window of a block, dY through the window of the V samples the block keeps
+int wgrad_blocks_geometry(const fc_long_wgrad_desc* desc, int64_t block_points, WgradGeom* out) {
+  if (!desc || !out) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_wgrad_desc& d = *desc;
+  if (d.out_len < 1) return fail(FC_ERR_INVALID, "out_len (%lld) must be positive", (long long)d.out_len);
+  if (d.stride != 1 || d.dilation != 1 || d.pad_mode != PAD_CONSTANT)
+    return fail(FC_ERR_UNSUPPORTED, "the weight gradient by blocks takes stride 1, dilation 1 and pad_mode constant only (got "
+                "stride %d, dilation %d, pad_mode %d): a block is a window of the zero-padded stride-1 row", d.stride, d.dilation,
+                d.pad_mode);
+  fc_long_desc f{};
+  f.batch = d.batch; f.in_channels = d.in_channels; f.out_channels = d.out_channels; f.groups = d.groups;
+  f.length = d.length; f.kernel = d.kernel; f.pad_left = d.pad_left; f.pad_right = d.pad_right;
+  f.out_keep = d.out_len; f.flip = d.flip; f.has_bias = 0;
+  WgradGeom w{};
+  int st = blocks_row(&f, block_points, &w.f);
+  if (st != FC_OK) return st;
+  if ((st = long_factor(w.f, (w.f.bk_U + 1) / 2, true)) != FC_OK) return st;
+  return wgrad_sizes(w, out);
+}
+
+// the workspace, slabs and grids of a weight-gradient plan whose forward geometry w.f is known
+int wgrad_sizes(WgradGeom& w, WgradGeom* out) {
   const LongGeom& g = w.f;
   const LongImpl* rows = find_long(g.N2);
   w.ob = rows ? rows->wg_ob : 1;
@@ -563,6 +687,27 @@ int fc_long_decim_plan_create(const fc_long_decim_desc* desc, fc_long_plan** out
   return finish_long_plan(p, out_plan);
 }
 
+int fc_long_blocks_geometry(const fc_long_blocks_desc* desc, int64_t info[8], int64_t blocks[4]) {
+  if (!info || !blocks) return fail(FC_ERR_INVALID, "null argument");
+  LongGeom g;
+  const int st = blocks_geometry(desc, &g);
+  if (st != FC_OK) return st;
+  fill_info(g, info);
+  fill_blocks(g, blocks);
+  return FC_OK;
+}
+
+int fc_long_blocks_plan_create(const fc_long_blocks_desc* desc, fc_long_plan** out_plan) {
+  if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();
+  *out_plan = nullptr;
+  std::unique_ptr<fc_long_plan> p(new fc_long_plan());
+  const int st = blocks_geometry(desc, &p->g);
+  if (st != FC_OK) return st;
+  p->d = desc->row;
+  return finish_long_plan(p, out_plan);
+}
+
 void fc_long_plan_destroy(fc_long_plan* plan) { delete plan; }
 
 int fc_long_plan_info(const fc_long_plan* plan, int64_t info[8]) {
@@ -632,6 +777,9 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     return fail(FC_ERR_UNSUPPORTED, "a decimation plan reads a (B, C, L) signal only: its forward column pass gives the lanes that "
                 "a channels-last load runs over the channels to the decimated rows of one channel (run the plain long plan, or "
                 "pass a contiguous signal)");
+  if (plan->g.bk_T && (x_layout != FC_LONG_NCL || y_layout != FC_LONG_NCL))
+    return fail(FC_ERR_UNSUPPORTED, "a blocks plan reads and writes (B, C, L) tensors only: no channels-last build of the blocks "
+                "column kernels exists (pass contiguous tensors)");
   if (int e = layout_check(x_layout, "x", plan->g.L, plan->g.Cin, xio)) return e;
   if (int e = layout_check(y_layout, "y", plan->g.nout, plan->g.Cout, yio)) return e;
   const bool x_nlc = x_layout == FC_LONG_NLC, y_nlc = y_layout == FC_LONG_NLC;
@@ -651,6 +799,13 @@ int fc_long_forward_lay(const fc_long_plan* plan, const void* x, int x_dtype, in
     a.w1 = (f2*)workspace;
     a.w2 = a.w1 + (size_t)(g.slab_pairs * g.Cin * g.N);
     a.C = (int)(g.dc_s ? g.Cin / g.dc_s : g.Cin);      // (the forward pass of a decimation plan counts the tensor's channels)
+    if (g.bk_T) {      // (a blocks plan: np pairs of units, the two tensor sides through the block map)
+      FC_HIP(plan->cols->cols_fwd_blocks(a, blocks_args(g, g.N), np, st));
+      FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
+      a.C = (int)g.Cout;
+      FC_HIP(plan->cols->cols_inv_blocks(a, blocks_args(g, g.N), np, st));
+      continue;
+    }
     FC_HIP(plan->cols->cols_fwd(a, map_in, x_nlc, np, st));
     FC_HIP(plan->rows->rows(a, np * g.G * a.nob, st));
     a.C = (int)g.Cout;
@@ -677,6 +832,9 @@ int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, 
   if (g.ph_s || g.dc_s)
     return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes neither a phases plan nor a decimation plan: their column passes "
                 "give the block layout to phases, and no gated build of those exists");
+  if (g.bk_T)
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes no blocks plan: no gated build of the blocks column kernels "
+                "exists (multiply around fc_long_forward_io)");
   if (g.pad_mode != PAD_CONSTANT || g.up != 1 || g.dil != 1 || g.step != 1)
     return fail(FC_ERR_UNSUPPORTED, "fc_long_forward_gated takes plans with the default fc_long_ext only (pad_mode constant, "
                 "src_up, tap_dil and out_step 1): the gated builds are builds of the unmapped column kernels");
@@ -723,6 +881,16 @@ int fc_long_wgrad_geometry(const fc_long_wgrad_desc* desc, int64_t info[8]) {
   return FC_OK;
 }
 
+int fc_long_wgrad_blocks_geometry(const fc_long_wgrad_desc* desc, int64_t block_points, int64_t info[8], int64_t blocks[4]) {
+  if (!info || !blocks) return fail(FC_ERR_INVALID, "null argument");
+  WgradGeom w;
+  const int st = wgrad_blocks_geometry(desc, block_points, &w);
+  if (st != FC_OK) return st;
+  fill_wgrad_info(w, info);
+  fill_blocks(w.f, blocks);
+  return FC_OK;
+}
+
 // the element codes of a call and its layouts against the sizes of the plan's tensors
 static int wgrad_io(const WgradGeom& w, int x_dtype, int x_layout, int dy_dtype, int dy_layout, int dw_dtype, int* xio,
                     int* dyio, int* dwio) {
@@ -741,12 +909,13 @@ int fc_long_wgrad_check_io(const fc_long_wgrad_desc* desc, int x_dtype, int x_la
   return wgrad_io(w, x_dtype, x_layout, dy_dtype, dy_layout, dw_dtype, &xio, &dyio, &dwio);
 }
 
-int fc_long_wgrad_plan_create(const fc_long_wgrad_desc* desc, fc_long_wgrad_plan** out_plan) {
+// block_points < 0: the plan of the whole row; else by blocks (0: the planner's choice)
+static int wgrad_plan_create(const fc_long_wgrad_desc* desc, int64_t block_points, fc_long_wgrad_plan** out_plan) {
   if (!desc || !out_plan) return fail(FC_ERR_INVALID, "null argument");
   (void)hipGetLastError();
   *out_plan = nullptr;
   std::unique_ptr<fc_long_wgrad_plan> p(new fc_long_wgrad_plan());
-  int st = wgrad_geometry(desc, &p->w);
+  int st = block_points < 0 ? wgrad_geometry(desc, &p->w) : wgrad_blocks_geometry(desc, block_points, &p->w);
   if (st != FC_OK) return st;
   // (the tables and kernels of the forward plan of the layer)
   std::unique_ptr<fc_long_plan> f(new fc_long_plan());
@@ -756,6 +925,15 @@ int fc_long_wgrad_plan_create(const fc_long_wgrad_desc* desc, fc_long_wgrad_plan
   p->f.reset(fp);
   *out_plan = p.release();
   return FC_OK;
+}
+
+int fc_long_wgrad_plan_create(const fc_long_wgrad_desc* desc, fc_long_wgrad_plan** out_plan) {
+  return wgrad_plan_create(desc, -1, out_plan);
+}
+
+int fc_long_wgrad_blocks_plan_create(const fc_long_wgrad_desc* desc, int64_t block_points, fc_long_wgrad_plan** out_plan) {
+  if (block_points < 0) return fail(FC_ERR_INVALID, "block_points (%lld) must not be negative", (long long)block_points);
+  return wgrad_plan_create(desc, block_points, out_plan);
 }
 
 void fc_long_wgrad_plan_destroy(fc_long_wgrad_plan* plan) { delete plan; }
@@ -790,6 +968,12 @@ static int wgrad_run(const fc_long_wgrad_plan* plan, const void* x, const void* 
   if (postgate && dy_layout == FC_LONG_NLC)
     return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes a postgate with a (B, C, L) dY only: a channels-last dY is read by "
                 "the channels-last build of the column kernel, and no gated build of that exists");
+  if (g.bk_T && (pregate || postgate))
+    return fail(FC_ERR_UNSUPPORTED, "fc_long_wgrad_gated takes no gate on a blocks plan: no gated build of the blocks column "
+                "kernel exists (multiply before fc_long_wgrad)");
+  if (g.bk_T && (x_layout != FC_LONG_NCL || dy_layout != FC_LONG_NCL))
+    return fail(FC_ERR_UNSUPPORTED, "a weight gradient by blocks reads (B, C, L) tensors only: no channels-last build of the "
+                "blocks column kernel exists (pass contiguous tensors)");
   const fc_long_plan& fp = *plan->f;
   hipStream_t st = (hipStream_t)hip_stream;
   f2* const w1x = (f2*)workspace;
@@ -805,7 +989,8 @@ static int wgrad_run(const fc_long_wgrad_plan* plan, const void* x, const void* 
     a.src = (const float*)x; a.src_io = xio;
     a.w1 = w1x;
     a.C = (int)g.Cin;
-    if (pregate) FC_HIP(fp.cols->cols_fwd_gated(a, LongGates{(const float*)pregate}, np, st));
+    if (g.bk_T) FC_HIP(fp.cols->cols_fwd_blocks(a, blocks_args(g, g.N), np, st));      // (the N-point window of each unit)
+    else if (pregate) FC_HIP(fp.cols->cols_fwd_gated(a, LongGates{(const float*)pregate}, np, st));
     else FC_HIP(fp.cols->cols_fwd(a, g.pad_mode != PAD_CONSTANT, x_layout == FC_LONG_NLC, np, st));
     // dY: rows of nout samples spread over the grid of the stride, zero elsewhere
     LongArgs b = base_args(fp);
@@ -817,7 +1002,9 @@ static int wgrad_run(const fc_long_wgrad_plan* plan, const void* x, const void* 
     b.pad_mode = PAD_CONSTANT; b.mpadl = 0; b.mpadr = 0;
     b.src_up = (int)g.step; b.d_up = make_fastdiv((unsigned)g.step);
     // (the gated build reads the words above -- L, padl, C -- and the gate, which lies as dY does, in LongGates::pregate)
-    if (postgate) FC_HIP(fp.cols->cols_fwd_gated(b, LongGates{(const float*)postgate}, np, st));
+    // (by blocks: the V samples each unit keeps, [t*V, t*V + V) of the row; the rest of the block reads zero)
+    if (g.bk_T) FC_HIP(fp.cols->cols_fwd_blocks(b, blocks_args(g, g.bk_V), np, st));
+    else if (postgate) FC_HIP(fp.cols->cols_fwd_gated(b, LongGates{(const float*)postgate}, np, st));
     else FC_HIP(fp.cols->cols_fwd(b, g.step > 1, dy_layout == FC_LONG_NLC, np, st));
     // the product summed over the pairs of the slab, transformed back into W2 (a later slab adds)
     LongArgs r = base_args(fp);

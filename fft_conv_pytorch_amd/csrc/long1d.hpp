@@ -922,6 +922,175 @@ __global__ __launch_bounds__(NT) void long_cols_inv_gated_kernel(const LongArgs 
   }
 }
 
+// ------------------------------------------------------------------------------------------ blocks (overlap-save)
+// The blocks builds of the two column kernels (long_cols_fwd_blocks_kernel, long_cols_inv_blocks_kernel; real rows, the
+// plain form, (B, C, L) tensors, float32 and 16-bit) run a row that is longer than the transform as overlap-save blocks of
+// N points against ONE filter spectrum of N bins: block t of a row starts hop = N - keff + 1 samples behind block t - 1
+// and keeps its first hop results.  The block index is a batch-like index: unit u = b*T + t, T blocks per row, and the
+// complex row of pair p carries units 2p and 2p + 1, which may lie in different rows of the tensor -- each unit has a
+// row resource and a sample origin of its own.  Everything between the two tensor sides (W1, long_rows, W2) sees pairs
+// and channels as ever.  LongBlocks is a second kernel argument of these builds alone, as LongGates is of the gated ones.
+struct LongBlocks {
+  FastDiv d_T;           // blocks per row: unit u -> (b, t)
+  int U;                 // units, B * T; a last odd unit has no partner
+  int hop;               // V = N - keff + 1: block t starts at sample t * hop of the padded row / of y
+  int win;               // cols_fwd: positions q < win of a block hold samples, the rest reads zero (N for x; hop for the
+                         // dY of the weight gradient)
+};
+
+// The blocks build of long_cols_fwd: position q of unit (b, t) of channel c holds x[b][c][t*hop + q - padl] where q < win
+// and that index lies in [0, L), zero elsewhere.  The index is compared with the row length in SAMPLES and only then
+// scaled to bytes: t*hop + q passes 2^29 on long rows (the host keeps it below 2^31), and a scaled value must not wrap
+// onto an offset that is read.  Lane order, LDS staging, transform, twiddle and store are those of the plain build.
+template <int P, int S, int NSEQ, int NT, int IO>
+__global__ __launch_bounds__(NT) void long_cols_fwd_blocks_kernel(const LongArgs a, const LongBlocks bk) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.src_io);
+  constexpr unsigned ES = Io<IO>::B;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row, pr;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+  const unsigned c = fdivmod(row, a.d_c, &pr);
+  // the pair's two units: batch item, block and the row of the tensor each reads
+  const unsigned u0 = 2u * ((unsigned)a.pair0 + pr);
+  const bool has1 = u0 + 1u < (unsigned)bk.U;
+  unsigned bt0, bt1;
+  const unsigned t0 = fdivmod(u0, bk.d_T, &bt0), t1 = fdivmod(has1 ? u0 + 1u : u0, bk.d_T, &bt1);
+  const unsigned len = (unsigned)a.L, sbytes = len * ES;
+  const BufRsrc s0 = make_rsrc(io_ptr<IO>(a.src) + ((size_t)bt0 * a.C + c) * a.L, sbytes);
+  const BufRsrc s1 = make_rsrc(io_ptr<IO>(a.src) + ((size_t)bt1 * a.C + c) * a.L, sbytes);
+  const int org0 = (int)(t0 * (unsigned)bk.hop) - a.padl, org1 = (int)(t1 * (unsigned)bk.hop) - a.padl;
+  {
+    f2 val[P];
+    const auto place = [&](int u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      return (n1 << a.lgN2) + n20 + r;
+    };
+    const auto offset = [&](int q, int org, bool on) {
+      const unsigned e = (unsigned)(q + org);
+      return on && q < bk.win && e < len ? e * ES : 0x80000000u;
+    };
+    if constexpr (IO == IO_F32) {
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const int q = place(u);
+        val[u].x = buf_load_f32(s0, offset(q, org0, true), 0);
+        val[u].y = buf_load_f32(s1, offset(q, org1, has1), 0);
+      }
+    } else {
+      // (all 2 P loads are issued before the first sample is widened, as in the plain build)
+      unsigned h0[P], h1[P];
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const int q = place(u);
+        h0[u] = __builtin_amdgcn_raw_buffer_load_b16(s0, offset(q, org0, true), 0, 0);
+        h1[u] = __builtin_amdgcn_raw_buffer_load_b16(s1, offset(q, org1, has1), 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < P; ++u) val[u] = mk2(io.in(h0[u]), io.in(h1[u]));
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(n1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  nat_load<G>(v, lseq, tseq);
+  seq_sync<G>();
+  fwd_from_regs<G>(v, lseq, tseq, true, twA, twB);
+  __syncthreads();
+  const BufRsrc thi = make_rsrc(a.thi, (unsigned)((N >> kLongLoBits) * 8));
+  const BufRsrc tlo = make_rsrc(a.tlo, (unsigned)(8u << kLongLoBits));
+  const BufRsrc orr = make_rsrc(a.w1 + (size_t)row * N, (unsigned)(N * 8));
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+    const unsigned n2 = (unsigned)(n20 + r);
+    const f2 w = long_twiddle(thi, tlo, n2 * (unsigned)k1);
+    const f2 z = lds[r * LSEQP + G::nat(k1)];
+    buf_store_f32x2(cmul(z, w), orr, (((unsigned)k1 << a.lgN2) + n2) * 8u, 0);
+  }
+}
+
+// The blocks build of long_cols_inv: the real part is unit 2p, the imaginary part unit 2p + 1; sample j < hop of unit
+// (b, t) goes to y[b][o][t*hop + j] where that lies below nout, everything else is dropped (the wrapped-around samples
+// behind the hop, and the tail of a row's last block).  The index is compared in samples before it is scaled to bytes.
+// W2 loads, inverse transform, the trip through LDS and the bias are those of the plain build.
+template <int P, int S, int NSEQ, int NT, int IO>
+__global__ __launch_bounds__(NT) void long_cols_inv_blocks_kernel(const LongArgs a, const LongBlocks bk) {
+  using G = Geo<P, S>;
+  const Io<IO> io(a.y_io);
+  constexpr unsigned ES = Io<IO>::B;
+  constexpr int LSEQP = SeqLayout<G>::LSEQP;
+  static_assert(NT == NSEQ * G::TS && (NSEQ & (NSEQ - 1)) == 0, "one thread slot per point group, column block a power of two");
+  extern __shared__ __attribute__((aligned(16))) f2 lds[];
+  const BufRsrc twA = make_rsrc(a.twA1, (unsigned)(P * G::N2 * 8));
+  const BufRsrc twB = make_rsrc(a.twB1, (unsigned)(S * P * 8));
+  const int tid = threadIdx.x, sq = tid / G::TS, tseq = tid % G::TS;
+  unsigned row, pr;
+  const int n20 = (int)fdivmod(blockIdx.x, a.d_nblk, &row) * NSEQ;
+  const size_t N = (size_t)a.N1 << a.lgN2;
+  const unsigned o = fdivmod(row, a.d_c, &pr);
+  const unsigned u0 = 2u * ((unsigned)a.pair0 + pr);
+  const bool has1 = u0 + 1u < (unsigned)bk.U;
+  unsigned bt0, bt1;
+  const unsigned t0 = fdivmod(u0, bk.d_T, &bt0), t1 = fdivmod(has1 ? u0 + 1u : u0, bk.d_T, &bt1);
+  f2 wtw[P];
+  passA_twiddle_fetch<G>(wtw, tseq, twA);
+  {
+    const BufRsrc sr = make_rsrc(a.w2 + (size_t)row * N, (unsigned)(N * 8));
+    f2 val[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      val[u] = buf_load_f32x2(sr, (((unsigned)k1 << a.lgN2) + (unsigned)(n20 + r)) * 8u, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      const int idx = tid + u * NT, r = idx & (NSEQ - 1), k1 = idx / NSEQ;
+      lds[r * LSEQP + G::nat(k1)] = val[u];
+    }
+  }
+  __syncthreads();
+  f2 v[P];
+  f2* lseq = lds + sq * LSEQP;
+  const int j = inv_to_regs_pre<G>(v, wtw, lseq, tseq, true, twB);
+  seq_sync<G>();
+  {
+    const int nbase = (tseq >> G::LGS) + P * P * j;
+#pragma unroll
+    for (int k = 0; k < P; ++k) lseq[G::nat(nbase + P * k)] = v[k];
+  }
+  __syncthreads();
+  float b = a.bias ? a.bias[o] : 0.f;
+  asm volatile("" : "+v"(b));
+  // (the bias is added in float32; a 16-bit y is rounded once, at the store)
+  const unsigned nout = (unsigned)a.nout, ybytes = nout * ES;
+  const BufRsrc o0 = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bt0 * a.C + o) * a.nout, ybytes);
+  const BufRsrc o1 = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bt1 * a.C + o) * a.nout, ybytes);
+  const unsigned at0 = t0 * (unsigned)bk.hop, at1 = t1 * (unsigned)bk.hop;
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const int idx = tid + u * NT, r = idx & (NSEQ - 1), n1 = idx / NSEQ;
+    const f2 z = lds[r * LSEQP + G::nat(n1)];
+    const unsigned s = ((unsigned)n1 << a.lgN2) + (unsigned)(n20 + r);
+    const bool kept = s < (unsigned)bk.hop;
+    const unsigned e0 = at0 + s, e1 = at1 + s;
+    io.store(z.x + b, o0, kept && e0 < nout ? e0 * ES : 0x80000000u, 0);
+    io.store(z.y + b, o1, kept && has1 && e1 < nout ? e1 * ES : 0x80000000u, 0);
+  }
+}
+
 // what one tile geometry contributes: the column passes of an N1 = T plan and the row pass of an N2 = T plan.  The host
 // states facts and long_inst.hip picks the build of a column pass: the element type by a.src_io (cols_fwd) / a.y_io
 // (cols_inv), the mapped build where `mapped` (padding mode, src_up, tap_dil / out_step), the channels-last build where
@@ -940,6 +1109,9 @@ struct LongImpl {
   // the gated builds of the column passes (float32 and 16-bit, plain form): `rows` batch pairs
   hipError_t (*cols_fwd_gated)(const LongArgs& a, const LongGates& gt, long long rows, hipStream_t st);
   hipError_t (*cols_inv_gated)(const LongArgs& a, const LongGates& gt, long long rows, hipStream_t st);
+  // the blocks builds of the column passes (float32 and 16-bit, plain form): `rows` unit pairs
+  hipError_t (*cols_fwd_blocks)(const LongArgs& a, const LongBlocks& bk, long long rows, hipStream_t st);
+  hipError_t (*cols_inv_blocks)(const LongArgs& a, const LongBlocks& bk, long long rows, hipStream_t st);
 };
 
 #define FC_DECLARE_LONG(P, S) const LongImpl* get_long_P##P##_S##S();

@@ -3,7 +3,8 @@
 // by the launch's element code, each plain, mapped or channels-last, nine builds of each column kernel; for a phases plan,
 // a.ph_s > 0, the phases builds of the filter rows and of the inverse pass, float32 and 16-bit; for a decimation plan,
 // a.ph_s > 0 with a.ph_cog == 0, the decimation builds of the filter rows and of the signal rows, float32 and 16-bit; the row pass
-// of the weight gradient and the float32 and 16-bit builds of its inverse pass have entries of their own): built once per
+// of the weight gradient and the float32 and 16-bit builds of its inverse pass have entries of their own, and so have the
+// gated and the blocks builds of the column passes): built once per
 // geometry with -DFC_P=.. -DFC_S=.. like tile_inst.hip, in an object of its own so that the two compile side by side.
 #include "launch.hpp"
 #include "long1d.hpp"
@@ -208,13 +209,35 @@ hipError_t cols_gated(const LongArgs& a, const LongGates& gt, long long rows, hi
   return hipErrorInvalidValue;
 }
 
+// ---- blocks (long1d.hpp LongBlocks): the blocks builds of the two column passes, float32 and 16-bit, the plain block
+// map over `rows` unit pairs.  They take the block map as a second kernel argument; every other build keeps the one it had
+template <bool INV>
+hipError_t cols_blocks(const LongArgs& a, const LongBlocks& bk, long long rows, hipStream_t st) {
+  if (a.N1 != kT || rows <= 0 || a.C <= 0 || a.from_kernel || a.ph_s > 0) return hipErrorInvalidValue;
+  if (bk.U <= 0 || bk.hop <= 0 || bk.d_T.d == 0 || (!INV && bk.win <= 0)) return hipErrorInvalidValue;
+  const long long grid = rows * a.C * (a.N2 / kNSEQ);
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  LongArgs b = a;
+  b.d_nblk = make_fastdiv((unsigned)(a.N2 / kNSEQ));
+  b.d_c = make_fastdiv((unsigned)a.C);
+  const int code = INV ? a.y_io : a.src_io;
+  if constexpr (INV) {
+    if (code == 0) return launch_kernel<long_cols_inv_blocks_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32>>(grid, kNT, kLds, st, b, bk);
+    if (io_is_h16(code)) return launch_kernel<long_cols_inv_blocks_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(grid, kNT, kLds, st, b, bk);
+  } else {
+    if (code == 0) return launch_kernel<long_cols_fwd_blocks_kernel<FC_P, FC_S, kNSEQ, kNT, IO_F32>>(grid, kNT, kLds, st, b, bk);
+    if (io_is_h16(code)) return launch_kernel<long_cols_fwd_blocks_kernel<FC_P, FC_S, kNSEQ, kNT, IO_H16>>(grid, kNT, kLds, st, b, bk);
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 #define FC_CAT_(a, b, c, d) a##b##c##d
 #define FC_CAT(a, b, c, d) FC_CAT_(a, b, c, d)
 const LongImpl* FC_CAT(get_long_P, FC_P, _S, FC_S)() {
   static const LongImpl impl = {kT, kOB, cols_dispatch<false>, rows, cols_dispatch<true>, kWgOB, wgrad_rows, wgrad_inv,
-                                cols_gated<false>, cols_gated<true>};
+                                cols_gated<false>, cols_gated<true>, cols_blocks<false>, cols_blocks<true>};
   return &impl;
 }
 

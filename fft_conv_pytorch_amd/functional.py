@@ -513,6 +513,15 @@ def _long_decim_plan(signal: Tensor, cout: int, groups: int, taps: int, stride: 
     return _cached_plan(_device_index(signal.device), key)
 
 
+def _long_blocks_plan(signal: Tensor, cout: int, groups: int, taps: int, pad_left: int, pad_right: int, flip: bool,
+                      out_keep: int, has_bias: bool, block_points: int):
+    """Cached blocks plan (``fc_long_blocks_plan_create``) of a (B, Cin, L) signal: the plain real primitive in overlap-save
+    blocks of ``block_points`` points (0: the planner's choice).  Its cache key carries a tag of its own."""
+    key = ("long_blocks", int(signal.shape[0]), int(signal.shape[1]), int(cout), int(groups), int(signal.shape[2]), int(taps),
+           int(pad_left), int(pad_right), int(out_keep), int(bool(flip)), int(bool(has_bias)), int(block_points))
+    return _cached_plan(_device_index(signal.device), key)
+
+
 def _resolved(t: Tensor) -> Tensor:
     """A complex tensor with its lazy conjugate / negation materialised: the library reads ``data_ptr()``, which knows of
     neither bit.  Real tensors pass through."""
@@ -723,8 +732,77 @@ def _long_route_of(length: int, taps: int, pad_left: int, pad_right: int, need: 
         return "phases"
     if need > LONG_MAX_POINTS:
         raise NotImplementedError(f"fft_long_conv: the row needs a transform of {need} points; the long-filter path stops at "
-                                  f"2**24 = {LONG_MAX_POINTS}")
+                                  f"2**24 = {LONG_MAX_POINTS} (blocks=True runs a stride-1, zero-padded row past it in "
+                                  f"overlap-save blocks)")
     return "plain"
+
+
+def _long_blocks_arg(blocks):
+    """The ``blocks`` keyword of ``fft_long_conv`` checked (ValueError, before any device call) -> False, True or the int."""
+    if isinstance(blocks, bool):
+        return blocks
+    if (not isinstance(blocks, int) or not _native.LONG_BLOCK_MIN <= blocks <= _native.LONG_BLOCK_MAX
+            or blocks & (blocks - 1)):
+        raise ValueError(f"blocks must be a bool or a power of two from {_native.LONG_BLOCK_MIN} to 2**24 = "
+                         f"{_native.LONG_BLOCK_MAX} (the points of one block), got {blocks!r}")
+    return int(blocks)
+
+
+def _long_blocks_choice(blocks, batch: int, cin: int, cout: int, groups: int, length: int, taps: int, pad_left: int,
+                        pad_right: int, out_keep: int, flip: bool, need: int, stride: int = 1, dilation: int = 1,
+                        pad_mode: int = 0, dtype=torch.float32, x_layout: str = "ncl", channels_last: bool = False):
+    """Whether the primitive of these numbers runs by blocks under ``blocks`` (pure: numbers and the library's geometry call,
+    which touches no device) -> the block_points of its plan (0: the planner's choice, for ``True``), or None where it runs
+    as without the keyword.  By blocks: float32 / float16 / bfloat16, stride 1, dilation 1, zero padding, a signal that is
+    not read as channels-last and a contiguous result, a row that is no hand-off (``need`` > 4096 points) and needs more
+    points than fit -- 2**24 for ``True``, N for an int N -- and taps read <= N / 2 (the library's refusal)."""
+    if blocks is False or dtype not in (torch.float32,) + _LOW_PRECISION:
+        return None
+    if stride != 1 or dilation != 1 or pad_mode != 0 or x_layout == "nlc" or channels_last:
+        return None
+    if need <= LONG_HANDOFF_POINTS or need <= (LONG_MAX_POINTS if blocks is True else blocks):
+        return None
+    points = 0 if blocks is True else int(blocks)
+    try:
+        _native.blocks_geometry((int(batch), int(cin), int(cout), int(groups), int(length), int(taps), int(pad_left),
+                                 int(pad_right), int(out_keep), int(bool(flip)), 0, points))
+    except NotImplementedError:
+        return None
+    return points
+
+
+def _long_blocks_route_of(blocks, batch: int, cin: int, cout: int, groups: int, length: int, taps: int, pad_left: int,
+                          pad_right: int, need: int, causal: bool, stride: int, dilation: int, pad_mode: int, dtype,
+                          x_layout: str, channels_last: bool):
+    """``_long_blocks_route`` from the numbers ``_long_geometry`` returns -> (route, block_points of a "blocks" route)."""
+    points = _long_blocks_choice(blocks, batch, cin, cout, groups, length, taps, pad_left, pad_right,
+                                 _long_keep(length, causal, stride), causal, need, stride, dilation, pad_mode, dtype, x_layout,
+                                 channels_last)
+    if points is not None:
+        return "blocks", points
+    return _long_route_of(length, taps, pad_left, pad_right, need, causal, stride, dilation, pad_mode, dtype, x_layout), None
+
+
+def _long_blocks_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, groups=1, causal=False,
+                       padding_mode="constant", dtype=torch.float32, x_layout="ncl", channels_last=False, blocks=False) -> str:
+    """Which route a ``fft_long_conv(..., blocks=blocks)`` call takes (pure: shapes, numbers, the switches ``_long_route``
+    reads and the library's geometry call):
+
+    ``"blocks"``   ``blocks`` is True or an int N, float32 / float16 / bfloat16, stride 1, dilation 1, ``padding_mode``
+                   constant, a signal that is not read as channels-last, ``channels_last=False``, a row that is no hand-off
+                   and needs more points than 2**24 (True) or than N (int), taps read <= N / 2: overlap-save blocks of N
+                   points against one filter spectrum of N bins (True: the planner's N);
+    otherwise      whatever ``_long_route`` answers for the call without the keyword, its error included."""
+    blocks = _long_blocks_arg(blocks)
+    meta = dict(device="meta")
+    signal, kernel = torch.empty(tuple(signal_shape), **meta), torch.empty(tuple(kernel_shape), **meta)
+    pad_left, pad_right, need = _long_geometry(signal, kernel, None, padding, groups, causal, stride, dilation, padding_mode)
+    stride, dilation, mode = _long_int("stride", stride), _long_int("dilation", dilation), _native.PAD_MODES[padding_mode]
+    if not isinstance(channels_last, bool):
+        raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
+    return _long_blocks_route_of(blocks, int(signal_shape[0]), int(signal_shape[1]), int(kernel_shape[0]), groups,
+                                 int(signal_shape[2]), int(kernel_shape[2]), pad_left, pad_right, need, bool(causal), stride,
+                                 dilation, mode, dtype, x_layout, channels_last)[0]
 
 
 def _long_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=1, groups=1, causal=False,
@@ -803,7 +881,8 @@ def _long_wgrad_route(signal_shape, kernel_shape, stride=1, padding=0, dilation=
 
 
 def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype: torch.dtype, *,
-                    pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
+                    pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None,
+                    block_points: Optional[int] = None) -> Tensor:
     """dW (``wshape``, ``out_dtype``) of the layer ``key`` describes (``_long_wgrad_key``) on its weight-gradient plan, no
     autograd.  ``signal`` (B, Cin, L) and ``grad`` (B, Cout, nout) are float32, float16 or bfloat16, each on its own, and
     each is read where it lies: contiguous, or as the channels-last view ``_long_layout`` recognises (another layout, a
@@ -814,7 +893,10 @@ def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype:
     pregate * signal and the gradient postgate * grad, multiplied as the column passes load them
     (``LongWgradPlan.run_gated``: neither product exists, the bits are those of this call on the float32 products).  A
     gated side and its gate are read as contiguous (B, C, L) tensors.  The plan is the one of the call without gates; what
-    it refuses under a gate (a padding mode under ``pregate``, a stride under ``postgate``) raises ``NotImplementedError``."""
+    it refuses under a gate (a padding mode under ``pregate``, a stride under ``postgate``) raises ``NotImplementedError``.
+
+    ``block_points`` (not None): the weight-gradient plan BY BLOCKS of that many points (0: the planner's choice), for a
+    layer whose forward ran by blocks (``fc_long_wgrad_blocks_plan_create``): both tensors are read contiguous, no gates."""
     gates = (pregate, postgate)
     tensors, layouts = [], []
     for t, gate in zip((signal.detach(), grad.detach()), gates):
@@ -822,12 +904,15 @@ def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype:
         if gate is not None and (tuple(gate.shape) != tuple(t.shape) or gate.dtype != t.dtype or gate.device != t.device):
             raise ValueError(f"a gate of the weight-gradient plan must match its tensor {tuple(t.shape)} {t.dtype} on "
                              f"{t.device}, got {tuple(gate.shape)} {gate.dtype} on {gate.device}")
-        nlc = gate is None and _long_reads_nlc(t)
+        nlc = gate is None and block_points is None and _long_reads_nlc(t)
         tensors.append(t if nlc else t.contiguous())
         layouts.append(_native.LONG_NLC if nlc else _native.LONG_NCL)
     x, dy = tensors
     pregate, postgate = (None if t is None else t.detach().contiguous() for t in gates)
-    plan = _cached_plan(_device_index(x.device), ("long_wgrad",) + tuple(key))
+    if block_points is None:
+        plan = _cached_plan(_device_index(x.device), ("long_wgrad",) + tuple(key))
+    else:
+        plan = _cached_plan(_device_index(x.device), ("long_wgrad_blocks",) + tuple(key) + (int(block_points),))
     with torch.cuda.device(x.device):
         dw = torch.empty(tuple(wshape), dtype=out_dtype, device=x.device)
         ws, ws_ptr, stream = _scratch_and_stream(plan, x.device)
@@ -842,7 +927,7 @@ def _long_wgrad_run(signal: Tensor, grad: Tensor, wshape, key: tuple, out_dtype:
 
 def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: Union[int, str] = 0, groups: int = 1,
                   causal: bool = False, *, stride: int = 1, dilation: int = 1, padding_mode: str = "constant",
-                  channels_last: bool = False) -> Tensor:
+                  channels_last: bool = False, blocks: Union[bool, int] = False) -> Tensor:
     """1-D convolution with a filter as long as the row: ONE transform over the whole padded row (as the reference does,
     functional.py:66-75) instead of overlap-save tiles, so the work does not grow with the number of taps.
 
@@ -886,23 +971,42 @@ def fft_long_conv(signal: Tensor, kernel: Tensor, bias: Tensor = None, padding: 
     phases has gradients of the same length (dX the transposed convolution of dY by phases, dW with the phases of x as a
     batch-like index); a causal one keeps the plain gradients, so a causal row past 2**24 points cannot be trained.
 
+    ``blocks`` (keyword-only) runs a row IN OVERLAP-SAVE BLOCKS over the long transform: the padded row is cut into blocks
+    of N points that overlap by (taps read) - 1, each block is one cyclic transform against ONE filter spectrum of N bins,
+    and the block index rides where the batch index does, so a row may be longer than 2**24 points and the spectrum and the
+    workspace grow with the filter, not with the row.  ``False``: the call it always was.  ``True``: by blocks where the
+    whole row does not fit 2**24 points (N: the planner's choice, the smallest power of two >= 4 * taps, at least 2**18).
+    An int N (a power of two 4096 ... 2**24, else ``ValueError``): by blocks of N points wherever the row needs more than N.
+    Either only where the call is eligible -- float32 / float16 / bfloat16, stride 1, dilation 1, ``padding_mode`` constant, a
+    signal that is not read as channels-last, ``channels_last=False``, taps read <= N / 2, a row that is no hand-off; causal
+    or not, any groups -- and otherwise the call is that of ``blocks=False`` (``_long_blocks_route`` names the route).  In
+    backward dX is the same primitive on dY and runs by blocks under the same rule, and dW of a forward that ran by blocks
+    comes from the weight-gradient plan by blocks (x and dY read where they lie, the unit pairs summed as batch pairs are).
+
     Real rows whose padded length is at most 4096 run the ``fft_conv`` kernels (complex rows stay here, at 64 x 64 points);
-    a row that fits no route inside 2**24 points raises ``NotImplementedError``.  float64 and complex128 tensors, tensors of
+    a row that fits no route inside 2**24 points raises ``NotImplementedError`` (``blocks=True`` is the way past it).  float64 and complex128 tensors, tensors of
     different dtypes and mixes of real and complex tensors are not taken by this path (``TypeError``)."""
     return _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, None, stride, dilation, padding_mode,
-                               channels_last)
+                               channels_last, blocks)
 
 
 def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum, stride=1, dilation=1,
-                        padding_mode="constant", channels_last=False):
+                        padding_mode="constant", channels_last=False, blocks=False):
+    blocks = _long_blocks_arg(blocks)
     pad_left, pad_right, need = _long_geometry(signal, kernel, bias, padding, groups, causal, stride, dilation, padding_mode)
     stride, dilation, mode = _long_int("stride", stride), _long_int("dilation", dilation), _native.PAD_MODES[padding_mode]
-    route = _long_route_of(int(signal.shape[2]), int(kernel.shape[2]), pad_left, pad_right, need, bool(causal), stride, dilation,
-                           mode, signal.dtype, _long_call_layout(signal, channels_last))
+    layout = _long_call_layout(signal, channels_last)
+    if blocks is False:      # (the call it always was)
+        route, points = _long_route_of(int(signal.shape[2]), int(kernel.shape[2]), pad_left, pad_right, need, bool(causal),
+                                       stride, dilation, mode, signal.dtype, layout), None
+    else:
+        route, points = _long_blocks_route_of(blocks, int(signal.shape[0]), int(signal.shape[1]), int(kernel.shape[0]), groups,
+                                              int(signal.shape[2]), int(kernel.shape[2]), pad_left, pad_right, need,
+                                              bool(causal), stride, dilation, mode, signal.dtype, layout, channels_last)
     signal, kernel, bias, cast = _long_operands(signal, kernel, bias)
     if cast:      # FFTCONV_HALF_IO=0
         out = _fft_long_conv_impl(signal.float(), kernel.float(), None if bias is None else bias.float(), padding, groups,
-                                  causal, None, stride, dilation, padding_mode, channels_last)
+                                  causal, None, stride, dilation, padding_mode, channels_last, blocks)
         return out.to(signal.dtype)          # (keeps the strides)
     if route == "handoff":      # (fft_conv has no complex route: a complex row never gets here)
         if not causal:
@@ -916,9 +1020,10 @@ def _fft_long_conv_impl(signal, kernel, bias, padding, groups, causal, spectrum,
     if _needs_grad(signal, kernel, bias):
         from .autograd import FFTLongConvFunction
         return FFTLongConvFunction.apply(signal, kernel, bias, pad_left, pad_right, bool(causal), groups, spectrum,
-                                         stride, dilation, padding_mode, channels_last, route == "phases")
+                                         stride, dilation, padding_mode, channels_last, route == "phases",
+                                         (blocks, points))
     run = _long_forward_plan(signal, kernel.shape, bias is not None, pad_left, pad_right, causal, groups, stride, dilation,
-                             mode, route)[1]
+                             mode, route, block_points=points)[1]
     return _long_run(signal, kernel, bias, pad_left, pad_right, causal, groups=groups, spectrum=spectrum,
                      channels_last=channels_last, **run)
 
@@ -929,13 +1034,17 @@ def _long_keep(length: int, causal: bool, stride: int) -> int:
 
 
 def _long_forward_plan(signal: Tensor, wshape, has_bias: bool, pad_left: int, pad_right: int, causal: bool, groups: int,
-                       stride: int, dilation: int, pad_mode: int, route: str):
+                       stride: int, dilation: int, pad_mode: int, route: str, *, block_points: Optional[int] = None):
     """(plan, the keyword arguments ``_long_run`` takes for it) of a ``fft_long_conv`` call on ``route`` ("plain" |
-    "phases"), from the numbers ``_long_geometry`` returns: the one place that maps a forward route to its plan (the
+    "phases" | "blocks", the last with the ``block_points`` ``_long_blocks_route_of`` returns), from the numbers ``_long_geometry`` returns: the one place that maps a forward route to its plan (the
     functional, ``FFTLongConvFunction.forward`` and ``FFTLongConv1d``, which caches the spectrum of this plan).  Both plans
     transform the (Cout, Cin/groups, K) weight ``wshape`` itself."""
     cout, taps, keep = int(wshape[0]), int(wshape[2]), _long_keep(signal.shape[2], causal, stride)
-    if route == "phases":
+    if route == "blocks":
+        assert block_points is not None and (stride, dilation, pad_mode) == (1, 1, 0), "by blocks: the plain zero-padded primitive"
+        run = dict(out_keep=keep)
+        plan = _long_blocks_plan(signal, cout, groups, taps, pad_left, pad_right, causal, keep, has_bias, block_points)
+    elif route == "phases":
         run = dict(out_keep=keep, decim=stride)
         plan = _long_decim_plan(signal, cout, groups, taps, stride, pad_left, pad_right, keep, causal, has_bias)
     else:
@@ -959,7 +1068,13 @@ def _long_call_layout(signal: Tensor, channels_last) -> str:
     ``channels_last`` argument is checked here: after the geometry, before the route.)"""
     if not isinstance(channels_last, bool):
         raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
-    layout = _long_layout(signal)
+    return _long_route_layout(signal)
+
+
+def _long_route_layout(t: Tensor) -> str:
+    """``_long_layout``, "ncl" for every tensor under FFTCONV_LONG_NLC=0: the layout a signal is routed by, in the forward
+    and (dY as the signal of dX) in backward."""
+    layout = _long_layout(t)
     return layout if layout == "ncl" or _long_nlc_enabled() else "ncl"
 
 

@@ -225,13 +225,18 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
     strides (nout*Cout, 1, Cout), as ``fft_long_conv`` does: ``y.transpose(1, 2)`` is then contiguous, ready for the
     ``nn.Linear`` of a sequence model.  A signal that lies that way is read where it lies whatever this says.
 
+    ``blocks`` (keyword-only; an attribute, not part of the state_dict): the ``blocks`` keyword of ``fft_long_conv`` --
+    False, True, or the points of one block -- for the ungated forward; the spectrum cached is then that of the blocks
+    plan, N bins per filter row however long the signal is.
+
     ``forward(signal, pregate=None, postgate=None)``: with a gate the forward is ``fft_long_conv_gated`` on the cached
     spectrum, postgate * conv(pregate * signal); without gates it is the call it always was."""
 
     channels_last = False      # (the default of a module pickled before the attribute existed)
+    blocks = False             # (likewise)
 
     def __init__(self, in_channels, out_channels, kernel_size, padding=0, groups=1, bias=True, causal=False, device=None,
-                 dtype=None, *, channels_last=False, stride=1, dilation=1, padding_mode="zeros"):
+                 dtype=None, *, channels_last=False, blocks=False, stride=1, dilation=1, padding_mode="zeros"):
         if causal and not (isinstance(padding, int) and padding == 0):
             raise ValueError("causal=True pads the row itself: padding must be 0")
         if causal and padding_mode != "zeros":
@@ -242,10 +247,12 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         if not isinstance(channels_last, bool):
             raise ValueError(f"channels_last must be a bool, got {channels_last!r}")
         self.channels_last = channels_last
+        self.blocks = F_._long_blocks_arg(blocks)
 
     def extra_repr(self):
         return (super().extra_repr() + (", causal=True" if self.causal else "")
-                + (", channels_last=True" if self.channels_last else ""))
+                + (", channels_last=True" if self.channels_last else "")
+                + (f", blocks={self.blocks}" if self.blocks is not False else ""))
 
     def forward(self, signal: Tensor, pregate: Tensor = None, postgate: Tensor = None):
         padding = self.padding if isinstance(self.padding, str) else int(self.padding[0])
@@ -260,21 +267,29 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         if (signal.is_cuda and weight.is_cuda and signal.device == weight.device and signal.dtype == weight.dtype
                 and (signal.dtype == torch.float32 or cx or F_._half_native(signal, weight, bias))):
             mode = F_._native.PAD_MODES[padding_mode]
+            gated = pregate is not None or postgate is not None      # (the gated function does not take the keyword)
+            layout = F_._long_layout(signal) if F_._long_nlc_enabled() else "ncl"
+            points = None
             try:
-                route = F_._long_route_of(int(signal.shape[2]), int(weight.shape[2]), pad_left, pad_right, need, self.causal,
-                                          stride, dilation, mode, signal.dtype,
-                                          F_._long_layout(signal) if F_._long_nlc_enabled() else "ncl")
+                if self.blocks is False or gated:
+                    route = F_._long_route_of(int(signal.shape[2]), int(weight.shape[2]), pad_left, pad_right, need, self.causal,
+                                              stride, dilation, mode, signal.dtype, layout)
+                else:
+                    route, points = F_._long_blocks_route_of(
+                        self.blocks, int(signal.shape[0]), int(signal.shape[1]), int(weight.shape[0]), self.groups,
+                        int(signal.shape[2]), int(weight.shape[2]), pad_left, pad_right, need, self.causal, stride, dilation,
+                        mode, signal.dtype, layout, self.channels_last)
             except NotImplementedError:
                 route = None      # (the functional raises it again, after its own checks)
-            if route not in (None, "handoff"):      # the plan the functional will run: both routes transform the weight itself
+            if route not in (None, "handoff"):      # the plan the functional will run: every route transforms the weight itself
                 plan = F_._long_forward_plan(signal, weight.shape, bias is not None, pad_left, pad_right, self.causal,
-                                             self.groups, stride, dilation, mode, route)[0]
+                                             self.groups, stride, dilation, mode, route, block_points=points)[0]
                 spectrum = self._cached_spectrum(plan)
         if pregate is not None or postgate is not None:      # (the spectrum is that of the ungated call: the gates change no plan)
             return F_._fft_long_conv_gated_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, pregate,
                                                 postgate, stride, dilation, padding_mode, self.channels_last)
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
-                                      padding_mode, self.channels_last)
+                                      padding_mode, self.channels_last, self.blocks)
 
 
 class FFTLongConvTranspose1d(_SpectrumCache, nn.ConvTranspose1d):

@@ -468,6 +468,47 @@ int fc_long_wgrad_gated(const fc_long_wgrad_plan* plan, const void* x, const voi
                         const void* dy, const void* postgate, int dy_dtype, int dy_layout, void* dw, int dw_dtype,
                         void* workspace, void* hip_stream);
 
+/* Rows in overlap-save blocks (ABI 7 extension: new entry points only; every struct, enum value and call above keeps its
+ * layout, value and meaning, and every kernel that existed its code).  The plain real primitive -- fc_long_desc with the
+ * default fc_long_ext: zero padding, stride 1, dilation 1 -- on a row that is longer than the transform: the padded row is
+ * cut into blocks of N = block_points points that overlap by (taps read) - 1, each block is one cyclic transform against
+ * ONE filter spectrum of N bins, and the block index is treated like the batch index.
+ *   nout, the taps read (keff of them; taps that meet only padding are not read) and the place of the data are those of
+ *   fc_long_geometry for the row.  V = N - keff + 1 samples of a block are kept, T = ceil(nout / V) blocks make a row, the
+ *   units (b, t) = u = b*T + t number U = B*T, and pair p carries units 2p and 2p+1 in one complex row (a last odd unit has
+ *   no partner).  Position q in [0, N) of unit (b, t) of channel c holds xrow[b][c][t*V + q]; sample j in [0, V) of the
+ *   unit's result is y[b][o][t*V + j] where t*V + j < nout, everything else is dropped.  Every sample of y is written
+ *   exactly once and no other byte.
+ *   The spectrum is Cout * Cin/groups rows of N bins whatever T is; the workspace holds (pairs per slab) * (Cin + Cout) * N
+ *   * 8 bytes under FFTCONV_LONG_WS_MB, the slabs run over unit pairs; FFTCONV_LONG_N must factor N itself.
+ *   info words as fc_long_plan_info (info[2] = nout); blocks[4] = V, T, U, unit pairs.
+ *   block_points: a power of two 4096 ... 2^24 (FC_ERR_INVALID otherwise), or 0 for the planner's choice: the smallest power
+ *   of two >= 4 * keff, not below 2^18, not above 2^24.
+ *   The plan is an fc_long_plan: fc_long_plan_info, fc_long_transform_kernel_io, fc_long_forward_io (FC_F32 / FC_F16 /
+ *   FC_BF16, each on its own) and fc_long_plan_destroy take it, fc_long_plan_kind answers FC_LONG_REAL.
+ *   fc_long_forward_lay with FC_LONG_NLC on either side and fc_long_forward_gated answer FC_ERR_UNSUPPORTED with text and
+ *   launch nothing.
+ *   FC_ERR_UNSUPPORTED with text: keff > N / 2 (a block keeps at least half of its points, so K <= 2^23), grids past 2^31
+ *   workgroups, B * T past 2^31, and rows of x, of the weight or of y past 2^29 samples (a row lies behind one buffer
+ *   resource). */
+typedef struct fc_long_blocks_desc {
+  fc_long_desc row;        /* the primitive of fc_long_desc with the default fc_long_ext */
+  int64_t block_points;    /* N of one block, a power of two 4096 .. 2^24; 0 = the planner's choice */
+} fc_long_blocks_desc;
+
+int fc_long_blocks_geometry(const fc_long_blocks_desc* desc, int64_t info[8], int64_t blocks[4]);
+int fc_long_blocks_plan_create(const fc_long_blocks_desc* desc, fc_long_plan** out_plan);
+
+/* The weight gradient of a layer that runs by blocks: fc_long_wgrad_desc with stride 1, dilation 1 and pad_mode constant
+ * (FC_ERR_UNSUPPORTED otherwise) and the block_points of the forward.  The plan is an fc_long_wgrad_plan and fc_long_wgrad
+ * runs it on (B, C, L) tensors: x is read through the N-point window of each unit, dY through the window of the V samples
+ * the unit keeps, [t*V, t*V + V) of the row (the rest of its block reads zero), the row pass sums FFT(x) * conj(FFT(dY))
+ * over the unit pairs exactly as it sums batch pairs, and the last pass stores lags 0 ... keff - 1 in the weight's order.
+ * info words as fc_long_wgrad_plan_info, blocks[4] as above.  fc_long_wgrad_gated with a gate and channels-last operands
+ * on such a plan answer FC_ERR_UNSUPPORTED with text. */
+int fc_long_wgrad_blocks_geometry(const fc_long_wgrad_desc* desc, int64_t block_points, int64_t info[8], int64_t blocks[4]);
+int fc_long_wgrad_blocks_plan_create(const fc_long_wgrad_desc* desc, int64_t block_points, fc_long_wgrad_plan** out_plan);
+
 /* ---- Channels-last tensors of the 2-D / 3-D plans (ABI 7 extension: new entry points only; fc_desc keeps its size, every
  * call above keeps its signature and meaning, and the route words of fc_debug_route are what they were).  The layout of x
  * and of y is an argument of the call: plan creation, the plan's route, its spectrum and its workspace do not depend on it.

@@ -8,7 +8,8 @@
 //     HBM reads of one item hide behind the arithmetic of the other;
 //   * the NB batch items of an item share every kernel-spectrum load of the mix step, which is what
 //     bounds the one-item-per-workgroup kernel (L2 -> L1 traffic of the spectrum);
-//   * the pass-A twiddle table lives in LDS for the lifetime of the workgroup;
+//   * the pass-A twiddle table lives in LDS for the lifetime of the workgroup -- or, in the four-slot dense builds
+//     (pers::reg_twiddles), a thread's 31 entries of it in registers: no table, no copy, no barrier before the first item;
 //   * the mix streams the spectrum through two register sets that are both in flight (set A holds step
 //     s, set B step s+1; each is refilled with step s+2 right after use); the first two sets of an item
 //     are requested before the barrier in front of the mix;
@@ -75,6 +76,24 @@ constexpr bool valid(unsigned build, int S, int CIB, int NB) {
 }
 }  // namespace pers
 
+// LDS image of a workgroup of NB slots (four sequences each), with the pass-A twiddle table in front of the sequences.
+// The four-slot dense builds on the P*P tile (batch pairs: no phases, not depthwise) run one workgroup per CU whatever
+// they do -- their sequences alone are past half of the CU's 160 KB -- and have registers to spare at the two waves per
+// SIMD that their 512 threads make (212 of 256): they hold the item-invariant pass-A twiddles in registers, so their
+// image has no table.  (The phase builds and the 2048-point tile sit at 214 .. 236 VGPRs and would spill the 62.)
+namespace pers {
+template <int P, int S>
+constexpr size_t lds_with_table(int nb) { return ((size_t)P * Geo<P, S>::N2 + (size_t)nb * 4 * Geo<P, S>::LSEQ) * sizeof(f2); }
+template <int P, int S>
+constexpr bool reg_twiddles(unsigned build, int nb) {
+  return lds_with_table<P, S>(nb) > 80 * 1024 && S == 1 && nb >= 2 && !(build & (phases | depthwise));
+}
+template <int P, int S>
+constexpr size_t lds_bytes(unsigned build, int nb) {
+  return lds_with_table<P, S>(nb) - (reg_twiddles<P, S>(build, nb) ? (size_t)P * Geo<P, S>::N2 * sizeof(f2) : 0);
+}
+}  // namespace pers
+
 template <int P, int S, int CIB, int NB, int NT, unsigned BUILD>
 __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs pa) {
   static_assert(pers::valid(BUILD, S, CIB, NB), "no such build: see pers::valid");
@@ -117,8 +136,9 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   const int nb = PH4 ? ((tid >> 5) & 1) : (PH2 ? 2 * (wv / NPI) + ((tid >> 5) & 1)
                : (BPAIR ? 2 * __builtin_amdgcn_readfirstlane(tid / (CIB * G::TS)) : __builtin_amdgcn_readfirstlane(tid / (NPI * G::TS))));
   const int pr = PH4 ? wv : (PH2 ? wv % NPI : (BPAIR ? sq % CIB : sq % NPI));
+  constexpr bool REGTW = pers::reg_twiddles<P, S>(BUILD, NB);   // pass-A twiddles in registers, no table in LDS
   f2* twl = lds;
-  f2* zbuf = lds + TWN;                     // [NSEQ][LSEQ], sequence (slot, pair) at slot * NPI + pair
+  f2* zbuf = lds + (REGTW ? 0 : TWN);       // [NSEQ][LSEQ], sequence (slot, pair) at slot * NPI + pair
   f2* zseq = PH4 ? zbuf + (nb * 8 + pr) * G::LSEQ : zbuf + (nb * NPI + pr) * G::LSEQ;
 
   const PadMap pm = make_padmap(a.pad_mode, a.L);
@@ -286,7 +306,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   };
 
   // ---- one item: forward FFT, mix, [request the next item's samples], inverse FFT, store
-  auto run = [&](const WorkItem& wi, int it, f2 (&v)[P], bool more, const WorkItem& wnext, f2 (&vnext)[P]) {
+  f2 twr[P];                                // REGTW: twA[k1 * N2 + tseq], k1 = 1 .. P - 1, for both items and all four passes
+  auto run = [&](const WorkItem& wi, int it, f2 (&v)[P], bool more, const WorkItem& wnext, f2 (&vnext)[P], auto firstc) {
     const int g = wi.goc / a.n_ochunks, oc = wi.goc % a.n_ochunks;
     const bool act_in = PH4 ? true : nb < wi.nbc;          // (phase quads: every item holds its four slots)
     // DIAG (depthwise): the spectrum is [channel pair][T/2] float4 = {H(2p)[f], H(2p+1)[f]}, 8 channels per block g
@@ -305,9 +326,18 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
     // ------------------------------------------------ forward pass A
     if (STAMPS && a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stampi(it, 1); }
     // (act_in is wave-uniform and the two passes of a sequence only need wave-level ordering)
+    if constexpr (REGTW && decltype(firstc)::value) {
+      // the samples were requested first, the twiddles right behind them: both are declared arrived here, so that no
+      // later use of a twiddle waits for younger memory instructions
+#pragma unroll
+      for (int n1 = 0; n1 < P; ++n1) asm volatile("" : "+v"(v[n1]));
+#pragma unroll
+      for (int k1 = 1; k1 < P; ++k1) asm volatile("" : "+v"(twr[k1]));
+    }
     if (act_in) {
       fetch_finish(wi, v);
-      passA_fft_twiddle_store_lds<G, -1>(v, zseq, tseq, twl);
+      if constexpr (REGTW) passA_fft_twiddle_store_regs<G, -1>(v, zseq, tseq, twr);
+      else passA_fft_twiddle_store_lds<G, -1>(v, zseq, tseq, twl);
       stampi(it, 2);
       seq_sync<G>();
       stampi(it, 3);
@@ -700,7 +730,8 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
     if (act_in) {
       nat_load<G>(v, zseq, tseq);
       seq_sync<G>();
-      passA_fft_twiddle_store_lds<G, +1>(v, zseq, tseq, twl);
+      if constexpr (REGTW) passA_fft_twiddle_store_regs<G, +1>(v, zseq, tseq, twr);
+      else passA_fft_twiddle_store_lds<G, +1>(v, zseq, tseq, twl);
       stampi(it, 8);
       seq_sync<G>();
       stampi(it, 9);
@@ -920,11 +951,15 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   const WorkItem w0 = pa.items[it0];
   const WorkItem w1 = pa.items[two ? it1 : it0];
   f2 va[P], vb[P];
-  fetch(w0, va);                             // first item's samples and the twiddle table travel together
-  copy_table_to_lds<TWN, NT>(twl, a.twA, tid);
-  __syncthreads();
-  run(w0, it0, va, two, w1, vb);
-  if (two) run(w1, it1, vb, false, w1, va);
+  fetch(w0, va);                             // first item's samples and the twiddles travel together
+  if constexpr (REGTW) {
+    passA_twiddle_fetch<G>(twr, tseq, make_rsrc(a.twA, (unsigned)(TWN * 8)));
+  } else {
+    copy_table_to_lds<TWN, NT>(twl, a.twA, tid);
+    __syncthreads();
+  }
+  run(w0, it0, va, two, w1, vb, std::true_type{});
+  if (two) run(w1, it1, vb, false, w1, va, std::false_type{});
 }
 
 }  // namespace fc

@@ -484,6 +484,16 @@ __device__ __forceinline__ void passA_fft_twiddle_store(f2 (&v)[G::P], f2* __res
   fft_regs<G::P, DIR>(v);
   passA_twiddle_apply<G, DIR>(v, w, lseq, n2);
 }
+// same with the twiddles already in registers (w[k1] = twA[k1 * N2 + n2], held by the caller across passes and work
+// items): between the transform and the row stores nothing is read and nothing waits
+template <class G, int DIR, class H = NoHook>
+__device__ __forceinline__ void passA_fft_twiddle_store_regs(f2 (&v)[G::P], f2* __restrict__ lseq, int n2,
+                                                             const f2 (&w)[G::P], H&& hook = H{}) {
+  fft_regs<G::P, DIR>(v, hook);
+  lseq[n2] = v[0];
+#pragma unroll
+  for (int k1 = 1; k1 < G::P; ++k1) lseq[k1 * G::RS + n2] = (DIR > 0) ? cmulc(v[k1], w[k1]) : cmul(v[k1], w[k1]);
+}
 // same with the twiddle table in LDS
 template <class G, int DIR, class H = NoHook>
 __device__ __forceinline__ void passA_fft_twiddle_store_lds(f2 (&v)[G::P], f2* __restrict__ lseq, int n2,

@@ -189,7 +189,8 @@ constexpr int kPersNb0 = 2, kPersNb1 = 4;
 #else
 constexpr int kPersNb0 = 0, kPersNb1 = 0;
 #endif
-constexpr size_t pers_lds_bytes(int nb) { return ((size_t)FC_P * GG::N2 + (size_t)nb * 4 * GG::LSEQ) * sizeof(float2); }
+// (the planner's figure, table included; a build that holds the twiddles in registers is launched with pers::lds_bytes)
+constexpr size_t pers_lds_bytes(int nb) { return pers::lds_with_table<FC_P, FC_S>(nb); }
 
 // The build of the batch-sharing kernel (a mask of the pers:: features, conv1d_pers.hpp) that a launch of NB slots
 // runs, float32 and 16-bit alike; kNoBuild if there is none.  In the order of precedence:
@@ -222,7 +223,7 @@ hipError_t launch_pers_among(unsigned build, const Conv1dPersArgs& a, int grid, 
   auto launch = [&](auto b) {
     constexpr unsigned B = decltype(b)::value;
     if constexpr (pers::valid(B, FC_S, 8, NB))      // (pairs: only on the P*P tiles; quads: only with four slots)
-      if (build == B) e = launch_kernel<conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, B>>(grid, NT, pers_lds_bytes(NB), st, a);
+      if (build == B) e = launch_kernel<conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, B>>(grid, NT, pers::lds_bytes<FC_P, FC_S>(B, NB), st, a);
   };
   (launch(std::integral_constant<unsigned, BUILDS>{}), ...);
   return e;

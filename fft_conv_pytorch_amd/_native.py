@@ -100,6 +100,15 @@ class FcLongBlocksDesc(ctypes.Structure):
     _fields_ = [("row", FcLongDesc), ("block_points", ctypes.c_int64)]
 
 
+class FcLongStepDesc(ctypes.Structure):
+    """Mirror of ``struct fc_long_step_desc`` (one decoding step of a causal long filter)."""
+    _fields_ = [
+        ("batch", ctypes.c_int64), ("in_channels", ctypes.c_int64), ("out_channels", ctypes.c_int64),
+        ("groups", ctypes.c_int64), ("kernel", ctypes.c_int64), ("head", ctypes.c_int64), ("max_len", ctypes.c_int64),
+        ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
 LONG_EXT_DEFAULT = (0, 1, 1, 1)
 FC_C64 = 4                                            # fc_dtype code of complex64 tensors (complex long plans; 2-D / 3-D fc_desc)
 # enum fc_long_kind: the rows of a long plan, and what a complex plan reads conjugated
@@ -175,6 +184,8 @@ def _signatures() -> dict:
         "fc_long_wgrad_blocks_plan_create": (i32, (wdesc, i64, out)),
         "fc_plan_takes_layout": (i32, (vp, i32, i32)),
         "fc_forward_lay": (i32, (vp, vp, i32, vp, vp, vp, i32, vp, vp)),
+        # (the decoding step; the table's last entry stays the gated forward, which tests pin)
+        "fc_long_step": (i32, (ptr(FcLongStepDesc), vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp)),
         "fc_long_forward_gated": (i32, (vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp)),
     }
 
@@ -652,6 +663,22 @@ class LongWgradBlocksPlan(LongWgradPlan):
         self.device_index = int(device_index)
         self.info = _info_words("fc_long_wgrad_plan_info", LONG_WGRAD_INFO_WORDS, handle)
         self.workspace_bytes = self.info["workspace_bytes"]
+
+
+LONG_STEP_HEAD_MIN, LONG_STEP_HEAD_MAX = 8, 1024      # head of fc_long_step: a power of two in this range
+
+
+def long_step_desc(batch: int, cin: int, cout: int, groups: int, taps: int, head: int, max_len: int, dtype: int = 0) -> FcLongStepDesc:
+    """``struct fc_long_step_desc`` of a stream: made once, passed to every ``long_step``."""
+    return FcLongStepDesc(int(batch), int(cin), int(cout), int(groups), int(taps), int(head), int(max_len), int(dtype), 0)
+
+
+def long_step(desc: FcLongStepDesc, x_ptr: int, pregate_ptr: Optional[int], postgate_ptr: Optional[int], taps_ptr: int,
+              bias_ptr: Optional[int], hist_ptr: int, acc_ptr: int, y_ptr: int, t: int, first: int, stream: int):
+    """``fc_long_step``: the one launch of a decoding step (the head taps, the gates, the store of column ``t`` of hist)."""
+    lib = load_library()
+    _check(lib, lib.fc_long_step(ctypes.byref(desc), x_ptr, pregate_ptr, postgate_ptr, taps_ptr, bias_ptr, hist_ptr, acc_ptr,
+                                 y_ptr, t, first, stream))
 
 
 # the tag of a long-filter key -> the class that owns its plan (forward plans and the weight-gradient plan: one cache)

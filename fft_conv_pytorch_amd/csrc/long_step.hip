@@ -1,0 +1,15 @@
+// long_step.hip -- the builds of long_step_kernel (long_step.hpp) and their launch: an object of its own.
+#include "long_step.hpp"
+
+#include "launch.hpp"
+
+namespace fc {
+
+hipError_t long_step_launch(const LongStepArgs& a, long long grid, int waves, hipStream_t st) {
+  if (waves < 1 || waves > kLongStepWaves) return hipErrorInvalidValue;
+  if (a.io == 0) return launch_kernel<long_step_kernel<IO_F32>>(grid, 64u * waves, 0, st, a);
+  if (io_is_h16(a.io)) return launch_kernel<long_step_kernel<IO_H16>>(grid, 64u * waves, 0, st, a);
+  return hipErrorInvalidValue;
+}
+
+}  // namespace fc

@@ -18,7 +18,7 @@ from torch import Tensor
 from . import _native
 from .utils import to_ntuple
 
-__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_gated", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum"]
+__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_gated", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum", "FFTLongConvStream"]
 
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
@@ -1261,8 +1261,235 @@ def _fft_long_conv_gated_impl(signal, kernel, bias, padding, groups, causal, spe
                            pregate=pregate, gate=postgate, plan=plan)[0]
 
 
+# ---------------------------------------------------------------------------------- decoding: one token at a time
+LONG_STREAM_HEAD = 64             # taps a step applies itself when ``head`` is None (DESIGN 4.7 has the sweep behind it)
+_STREAM_DTYPES = (torch.float32,) + _LOW_PRECISION
+
+
+def _long_stream_blocks(i: int, head: int, taps: int, first: int) -> list:
+    """The blocks that fall due once ``i`` samples of the row are known (after the step at position i - 1), pure:
+    a list of (n, lo, tap0, tap1, out0).  Level n = head, 2*head, 4*head, ... (while n < taps) is due when n divides i: the
+    samples [lo, i), lo = max(i - n, first), against the taps [tap0, tap1) = [n, min(2n, taps)) form a full linear
+    convolution whose first sample lands on position out0 = lo + n >= i.  Every pair (sample t >= first, tap k >= head)
+    is in exactly one block, and that block is due before output t + k is emitted; taps below ``head`` are the step's own,
+    samples below ``first`` the prefill's.  The only place the schedule lives."""
+    due, n = [], int(head)
+    while n < taps and i % n == 0:
+        lo = max(i - n, first)
+        if lo < i:
+            due.append((n, lo, n, min(2 * n, taps), lo + n))
+        n *= 2
+    return due
+
+
+def _long_stream_args(kernel, bias, groups, batch, max_len, head):
+    """Argument checks of ``FFTLongConvStream`` (ValueError for shapes, counts and devices, TypeError for dtypes; before any
+    device call) -> (cin, cout, taps, head)."""
+    if not isinstance(kernel, Tensor):
+        raise TypeError(f"`kernel` must be a tensor, got {type(kernel).__name__}")
+    if kernel.ndim != 3:
+        raise ValueError(f"FFTLongConvStream expects an (out, in/groups, taps) kernel, got shape {tuple(kernel.shape)}")
+    if isinstance(groups, bool) or not isinstance(groups, int) or groups < 1:
+        raise ValueError(f"groups must be a positive int, got {groups!r}")
+    for name, value in (("batch", batch), ("max_len", max_len)):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError(f"{name} must be a positive int, got {value!r}")
+    head = LONG_STREAM_HEAD if head is None else head
+    if (isinstance(head, bool) or not isinstance(head, int) or head & (head - 1)
+            or not _native.LONG_STEP_HEAD_MIN <= head <= _native.LONG_STEP_HEAD_MAX):
+        raise ValueError(f"head must be a power of two from {_native.LONG_STEP_HEAD_MIN} to {_native.LONG_STEP_HEAD_MAX}, "
+                         f"got {head!r}")
+    cout, cig, taps = (int(s) for s in kernel.shape)
+    if cout < 1 or cig < 1 or taps < 1 or cout % groups:
+        raise ValueError(f"channel mismatch: kernel is {tuple(kernel.shape)} with groups={groups} (need positive sizes and "
+                         f"out_channels % groups == 0)")
+    if bias is not None and not isinstance(bias, Tensor):
+        raise TypeError(f"`bias` must be a tensor or None, got {type(bias).__name__}")
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise ValueError(f"bias must have shape ({cout},), got {tuple(bias.shape)}")
+    if kernel.dtype not in _STREAM_DTYPES:
+        raise TypeError(f"`kernel` has dtype {kernel.dtype}; a stream takes float32, float16 or bfloat16 tensors")
+    if bias is not None and bias.dtype != kernel.dtype:
+        raise TypeError(f"`bias` has dtype {bias.dtype} but the kernel is {kernel.dtype}")
+    if not kernel.is_cuda:
+        raise ValueError(f"`kernel` is on {kernel.device}; a stream lives on a ROCm device (no CPU fallback)")
+    if bias is not None and bias.device != kernel.device:
+        raise ValueError(f"`bias` is on {bias.device} but the kernel is on {kernel.device}")
+    if cig * max_len >= 1 << 29:
+        raise NotImplementedError(f"a group's history of {cig} channels x {max_len} positions: the step kernel addresses "
+                                  f"fewer than 2**29 samples per group")
+    return cig * groups, cout, taps, head
+
+
+def _long_step_args(x_t, pregate, postgate, batch: int, cin: int, cout: int, dtype, device):
+    """Argument checks of ``FFTLongConvStream.step`` (before any device call), as ``_long_gates`` checks gates: a wrong
+    shape or device raises ValueError, a wrong dtype TypeError."""
+    for name, t, shape in (("x_t", x_t, (batch, cin)), ("pregate", pregate, (batch, cin)), ("postgate", postgate, (batch, cout))):
+        if t is None and name != "x_t":
+            continue
+        if not isinstance(t, Tensor):
+            raise TypeError(f"`{name}` must be a tensor{'' if name == 'x_t' else ' or None'}, got {type(t).__name__}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"`{name}` must have shape {shape}, got {tuple(t.shape)}")
+        if t.dtype != dtype:
+            raise TypeError(f"`{name}` has dtype {t.dtype} but the stream was made for {dtype}")
+        if t.device != device:
+            raise ValueError(f"`{name}` is on {t.device} but the stream is on {device}")
+
+
+class FFTLongConvStream:
+    """Token-by-token decoding of a causal long filter: after ``prefill`` and ``step`` calls the outputs, in order, are the
+    columns of ``fft_long_conv(z, kernel, bias, groups=groups, causal=True)`` on the row z = pregate * x seen so far, each
+    multiplied by its postgate:  y[t] = postgate[t] * (bias + sum_k kernel[k] * z[t - k]).
+
+    ``kernel`` (Cout, Cin/groups, K) and ``bias`` (Cout,) or None are float32, float16 or bfloat16 tensors on a ROCm
+    device; the stream keeps float32 copies made at construction (a snapshot: later changes of the weight do not reach
+    it).  ``batch`` and ``max_len`` size the state, ``head`` (a power of two 8 ... 1024; None: LONG_STREAM_HEAD) is the
+    number of taps a step applies itself.  Inference only: nothing is differentiable, outputs are detached.
+
+    Only the kernel is known in advance, so the convolution is cut into a fixed schedule of power-of-two blocks
+    (``_long_stream_blocks``): once i samples are known, every level n = head, 2 head, 4 head, ... < K that divides i
+    convolves the last n samples with the taps [n, 2n) -- a full linear convolution through ``fft_long_conv`` (small
+    blocks hand off to the ``fft_conv`` kernels), spectra and plans made once at construction -- and adds the result
+    to ``acc`` at the positions it reaches.  A step is then ONE launch (``fc_long_step``): it stores z_t, applies the head
+    taps to the last ``head`` samples, adds ``acc`` and the bias and applies the gates.  O(L log^2 L) per sequence where
+    re-running the causal call per token costs O(L^2 log L).  At positions divisible by a large power of two all levels
+    fall due together: the cost is amortised, not flat.
+
+    State (float32 whatever the tensors' dtype): ``hist`` (B, Cin, max_len) holds z, ``acc`` (B, Cout, max_len) the block
+    results that have landed on future positions; ``state_bytes`` reports both.  16-bit streams compute what the float32
+    stream on the widened tensors computes and round each output once.
+
+    ``prefill(x)``      x (B, Cin, L0), only at position 0, L0 <= max_len -> y (B, Cout, L0); ungated.
+    ``step(x_t, pregate=None, postgate=None)``   x_t, pregate (B, Cin), postgate (B, Cout) -> y_t (B, Cout).
+    ``reset()``         back to position 0.
+    Stepping past ``max_len`` raises ``RuntimeError``; wrong shapes and devices ``ValueError``, wrong dtypes ``TypeError``,
+    before any device call."""
+
+    def __init__(self, kernel: Tensor, bias: Optional[Tensor] = None, groups: int = 1, *, batch: int, max_len: int,
+                 head: Optional[int] = None):
+        cin, cout, taps, head = _long_stream_args(kernel, bias, groups, batch, max_len, head)
+        self.batch, self.in_channels, self.out_channels, self.groups = batch, cin, cout, groups
+        self.taps, self.head, self.max_len = taps, head, max_len
+        self.dtype, self.device = kernel.dtype, kernel.device
+        self._position = self._first = 0
+        self._desc = _native.long_step_desc(batch, cin, cout, groups, taps, head, max_len, _DTYPE_CODES[kernel.dtype])
+        with torch.no_grad(), torch.cuda.device(self.device):
+            wide = kernel.detach().float()
+            self._flipped = wide.flip(-1).contiguous()      # the prefill's operand: the whole filter in float32
+            self._bias = None if bias is None else bias.detach().float().contiguous().clone()
+            self._head_taps = torch.zeros((cout, cin // groups, head), dtype=torch.float32, device=self.device)
+            self._head_taps[..., :min(head, taps)] = wide[..., :min(head, taps)]
+            self.hist = torch.zeros((batch, cin, max_len), dtype=torch.float32, device=self.device)
+            self.acc = torch.zeros((batch, cout, max_len), dtype=torch.float32, device=self.device)
+            # one geometry, one plan and one spectrum per level that can fall due inside max_len
+            self._levels, n = {}, head
+            while n < taps and n < max_len:
+                seg = wide[..., n:min(2 * n, taps)].flip(-1).contiguous()
+                self._levels[n] = self._level(n, seg)
+                n *= 2
+
+    def _level(self, n: int, seg: Tensor):
+        """(flipped taps, padding, plan of the hand-off or None, spectrum) of the full convolution of n samples with ``seg``:
+        the non-causal ``fft_long_conv(X, seg, None, padding=len - 1, groups=g)`` on X (B, Cin, n)."""
+        pad = int(seg.shape[2]) - 1
+        probe = torch.empty((self.batch, self.in_channels, n), dtype=torch.float32, device=self.device)
+        pad_left, pad_right, need = _long_geometry(probe, seg, None, pad, self.groups, False)
+        route = _long_route_of(n, pad + 1, pad_left, pad_right, need, False, 1, 1, 0, torch.float32, "ncl")
+        if route == "handoff":
+            plan = _plan_for(probe, seg, None, 1, pad, 1, self.groups, "constant")
+            return seg, pad, plan, transform_kernel(plan, seg)
+        plan = _long_forward_plan(probe, seg.shape, False, pad_left, pad_right, False, self.groups, 1, 1, 0, route)[0]
+        return seg, pad, None, transform_kernel(plan, seg)
+
+    def _full_conv(self, rows: Tensor, level) -> Tensor:
+        seg, pad, plan, spectrum = level
+        if plan is not None:
+            return _fft_conv_impl(rows, seg, None, 1, pad, 1, self.groups, "constant", spectrum, plan)
+        return _fft_long_conv_impl(rows, seg, None, pad, self.groups, False, spectrum)
+
+    @property
+    def position(self) -> int:
+        """Samples of the row seen so far: the position the next ``step`` writes."""
+        return self._position
+
+    @property
+    def state_bytes(self) -> int:
+        """Bytes of ``hist`` and ``acc``."""
+        return (self.hist.numel() + self.acc.numel()) * 4
+
+    def reset(self):
+        """Back to position 0: the history and the accumulator are cleared, plans and spectra stay."""
+        self.hist.zero_()
+        self.acc.zero_()
+        self._position = self._first = 0
+
+    @torch.no_grad()
+    def prefill(self, x: Tensor) -> Tensor:
+        if not isinstance(x, Tensor):
+            raise TypeError(f"`x` must be a tensor, got {type(x).__name__}")
+        if x.ndim != 3 or tuple(x.shape[:2]) != (self.batch, self.in_channels) or not 1 <= x.shape[2] <= self.max_len:
+            raise ValueError(f"`x` must have shape ({self.batch}, {self.in_channels}, 1 ... max_len = {self.max_len}), got "
+                             f"{tuple(x.shape)}")
+        if x.dtype != self.dtype:
+            raise TypeError(f"`x` has dtype {x.dtype} but the stream was made for {self.dtype}")
+        if x.device != self.device:
+            raise ValueError(f"`x` is on {x.device} but the stream is on {self.device}")
+        if self._position:
+            raise RuntimeError(f"prefill is allowed at position 0 only; the stream is at {self._position} (reset() first)")
+        length = int(x.shape[2])
+        rows = x.detach().float().contiguous()
+        full = _fft_long_conv_impl(rows, self._flipped, None, self.taps - 1, self.groups, False, None)
+        y = full[:, :, :length]
+        if self._bias is not None:
+            y = y + self._bias.view(1, -1, 1)
+        reach = min(self.taps - 1, self.max_len - length)
+        if reach > 0:
+            self.acc[:, :, length:length + reach] += full[:, :, length:length + reach]
+        self.hist[:, :, :length] = rows
+        self._position = self._first = length
+        return y.to(self.dtype).contiguous()
+
+    @torch.no_grad()
+    def step(self, x_t: Tensor, pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
+        _long_step_args(x_t, pregate, postgate, self.batch, self.in_channels, self.out_channels, self.dtype, self.device)
+        t = self._position
+        if t >= self.max_len:
+            raise RuntimeError(f"the stream is at position {t} = max_len: no further step (reset() starts a new row)")
+        x_t, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x_t, pregate, postgate))
+        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
+            y = self._launch_step(x_t, pregate, postgate, t, ptr)
+        else:
+            with torch.cuda.device(self.device):
+                y = self._launch_step(x_t, pregate, postgate, t, ptr)
+        self._position = i = t + 1
+        if i % self.head == 0 and i < self.max_len:
+            for n, lo, _, _, _ in _long_stream_blocks(i, self.head, self.taps, self._first):
+                self._run_block(i, n, lo)
+        return y
+
+    def _launch_step(self, x_t, pregate, postgate, t, ptr) -> Tensor:
+        y = torch.empty((self.batch, self.out_channels), dtype=self.dtype, device=self.device)
+        _native.long_step(self._desc, x_t.data_ptr(), ptr(pregate), ptr(postgate), self._head_taps.data_ptr(),
+                          ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(), t, self._first,
+                          torch.cuda.current_stream(self.device).cuda_stream)
+        return y
+
+    def _run_block(self, i: int, n: int, lo: int):
+        """Level n at i known samples: the full convolution of the samples [i - n, i) -- those below ``lo`` (the
+        prefill's) as zeros, so that a level has one geometry -- with the level's taps, added to ``acc`` from position i
+        on (the first lo - (i - n) results of a partial block are zero) and clipped at ``max_len``."""
+        rows = self.hist[:, :, i - n:i].contiguous()
+        if lo > i - n:
+            rows[:, :, :lo - (i - n)] = 0.0
+        out = self._full_conv(rows, self._levels[n])
+        keep = min(int(out.shape[2]), self.max_len - i)
+        self.acc[:, :, i:i + keep] += out[:, :, :keep]
+
+
 # ---------------------------------------------------------------------------------- long transposed filters
-LONG_PHASES_MAX_OUT = 1 << 29     # longest output row the phases plan addresses (include/fftconv_amd.h)
+LONG_PHASES_MAX_OUT = 1 << 29    # longest output row the phases plan addresses (include/fftconv_amd.h)
 LONG_PHASES_MAX_STRIDE = 64       # (stride x transform points stays below 2**30 up to the 2**24-point limit)
 
 

@@ -291,6 +291,16 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
         return F_._fft_long_conv_impl(signal, weight, bias, padding, self.groups, self.causal, spectrum, stride, dilation,
                                       padding_mode, self.channels_last, self.blocks)
 
+    def stream(self, batch: int, max_len: int, head=None):
+        """A ``FFTLongConvStream`` on this module's weight and bias as they are now (a snapshot), for decoding one token at
+        a time: its outputs are the columns of this module's forward on the whole row.  Only for a module with
+        ``causal=True``, stride 1, dilation 1, padding_mode 'zeros' and ``channels_last=False`` (else ``ValueError``)."""
+        if not (self.causal and int(self.stride[0]) == 1 and int(self.dilation[0]) == 1 and self.padding_mode == "zeros"
+                and not self.channels_last):
+            raise ValueError("stream() decodes a causal row one sample at a time: the module needs causal=True, stride 1, "
+                             "dilation 1, padding_mode 'zeros' and channels_last=False")
+        return F_.FFTLongConvStream(self.weight, self.bias, self.groups, batch=batch, max_len=max_len, head=head)
+
 
 class FFTLongConvTranspose1d(_SpectrumCache, nn.ConvTranspose1d):
     """``nn.ConvTranspose1d`` (same parameters and attributes, so state_dict, deepcopy and pickle interchange with

@@ -560,6 +560,42 @@ int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, 
                           const float* bias, void* y, const void* gate, void* y2, const void* gate2, int y_dtype,
                           int y2_dtype, void* workspace, void* hip_stream);
 
+/* ---- Token-by-token decoding of a causal long filter (ABI 7 extension: one new struct and one new entry point; every
+ * struct and call above keeps its layout, signature and meaning, and every kernel that existed its arguments).
+ * A causal convolution y[t] = bias + sum_k kernel[k] * z[t - k] whose input arrives one sample at a time can be cut into
+ * power-of-two blocks of history against segments of the taps; the caller runs those blocks with the calls above as they
+ * fall due and adds them to a float32 accumulator `acc` at the positions they reach.  What is left for position t are the
+ * first `head` taps, and fc_long_step is that remainder, ONE launch:
+ *   z[b][c]     = pregate[b][c] * x_t[b][c]                (pregate: like x_t; NULL: all ones); stored to hist[b][c][t]
+ *   y_t[b][o]   = postgate[b][o] * (bias[o] + acc[b][o][t]
+ *                 + sum over the group's input channels c and the taps k < head with t - k >= first of
+ *                   head_taps[o][c][k] * (k == 0 ? z[b][c] : hist[b][c][t - k]))
+ * x_t, pregate (B, Cin) and y_t, postgate (B, Cout) are contiguous tensors of the descriptor's dtype (FC_F32, FC_F16 or
+ * FC_BF16); hist (B, Cin, max_len), acc (B, Cout, max_len), head_taps (Cout, Cin/groups, head; zero past `kernel` taps)
+ * and bias (Cout, or NULL) are float32.  The arithmetic is float32: 16-bit values are widened as they are loaded, each
+ * product with a gate is one float32 multiply, y_t is rounded once as it is stored.  Column t of hist is the only place
+ * of hist that is written, acc is only read, and y_t is written in full and no other byte.  `first` is the position at
+ * which stepping began (history below it belongs to blocks the caller has already run): such positions read as zero.
+ *   The call is stateless -- no plan, no allocation, no synchronisation -- and the position is an argument, so a step
+ *   captured into a HIP graph replays the position it was captured at.
+ *   One workgroup per (batch item, group); a group's history lies behind one buffer resource.
+ *   FC_ERR_INVALID with text: a null tensor, a non-positive count, channels not divisible by groups, another dtype,
+ *   t outside [0, max_len), first outside [0, t].  FC_ERR_UNSUPPORTED with text: head outside 8 ... 1024 or not a power of
+ *   two, a group's history of 2^29 samples or more (Cin/groups * max_len), 2^20 channels per group or more, B * groups past
+ *   2^31 workgroups.  Either launches nothing. */
+typedef struct fc_long_step_desc {
+  int64_t batch, in_channels, out_channels, groups;
+  int64_t kernel;       /* K taps of the filter (head_taps rows are zero from tap K on) */
+  int64_t head;         /* taps the step itself applies: a power of two 8 .. 1024 */
+  int64_t max_len;      /* positions of hist and acc */
+  int32_t dtype;        /* fc_dtype of x_t, the gates and y_t */
+  int32_t reserved;     /* 0 */
+} fc_long_step_desc;
+
+int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pregate, const void* postgate,
+                 const float* head_taps, const float* bias, float* hist, const float* acc, void* y_t, int64_t t,
+                 int64_t first, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,19 +1,18 @@
-// host_step.cpp -- fc_long_step (include/fftconv_amd.h "Token-by-token decoding"): descriptor checks and the one launch
-// of long_step_kernel (long_step.hpp).  Stateless: no plan, no allocation, nothing but the launch on the caller's stream.
+// host_step.cpp -- fc_long_step and fc_long_push (include/fftconv_amd.h "Token-by-token decoding"): descriptor checks and
+// the one launch of long_step_kernel (long_step.hpp) or long_push_kernel (long_push.hpp).  Stateless: no plan, no
+// allocation, nothing but the launch on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "fc_plan.h"
+#include "long_push.hpp"
 #include "long_step.hpp"
 
 using namespace fc;
 
-extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pregate, const void* postgate,
-                            const float* head_taps, const float* bias, float* hist, const float* acc, void* y_t, int64_t t,
-                            int64_t first, void* hip_stream) {
-  if (!desc || !x_t || !head_taps || !hist || !acc || !y_t) return fail(FC_ERR_INVALID, "null argument");
-  const fc_long_step_desc& d = *desc;
+// the descriptor's counts and dtype (FC_ERR_INVALID), checked before the position of a call ...
+static int step_desc_counts(const fc_long_step_desc& d) {
   if (d.batch < 1 || d.in_channels < 1 || d.out_channels < 1 || d.groups < 1 || d.kernel < 1 || d.max_len < 1)
     return fail(FC_ERR_INVALID, "batch, channels, groups, kernel and max_len must be positive");
   if (d.in_channels % d.groups || d.out_channels % d.groups)
@@ -21,19 +20,35 @@ extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, cons
                 (long long)d.in_channels, (long long)d.out_channels, (long long)d.groups);
   if (d.dtype != FC_F32 && d.dtype != FC_F16 && d.dtype != FC_BF16)
     return fail(FC_ERR_INVALID, "dtype %d: a step reads and writes FC_F32, FC_F16 or FC_BF16 tensors", d.dtype);
-  if (t < 0 || t >= d.max_len)
-    return fail(FC_ERR_INVALID, "position %lld lies outside the stream's max_len = %lld", (long long)t, (long long)d.max_len);
-  if (first < 0 || first > t)
-    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t = %lld]", (long long)first, (long long)t);
+  return FC_OK;
+}
+
+// ... and what the kernels address (FC_ERR_UNSUPPORTED), checked after it
+static int step_desc_limits(const fc_long_step_desc& d) {
   if (d.head < 8 || d.head > 1024 || (d.head & (d.head - 1)))
     return fail(FC_ERR_UNSUPPORTED, "head (%lld) must be a power of two from 8 to 1024", (long long)d.head);
-  const int64_t cig = d.in_channels / d.groups, cog = d.out_channels / d.groups;
+  const int64_t cig = d.in_channels / d.groups;
   if (d.max_len >= ((int64_t)1 << 29) || cig >= ((int64_t)1 << 20) || cig * d.max_len >= ((int64_t)1 << 29))
     return fail(FC_ERR_UNSUPPORTED, "a group's history of %lld channels x %lld positions: the step kernel addresses fewer "
                 "than 2^29 samples behind one buffer resource and fewer than 2^20 channels per group",(long long)cig, (long long)d.max_len);
   if (d.batch * d.groups > 0x7fffffffLL || d.out_channels > 0x7fffffffLL)
     return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups exceed the 2^31 workgroups of one launch",
                 (long long)d.batch, (long long)d.groups);
+  return FC_OK;
+}
+
+extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pregate, const void* postgate,
+                            const float* head_taps, const float* bias, float* hist, const float* acc, void* y_t, int64_t t,
+                            int64_t first, void* hip_stream) {
+  if (!desc || !x_t || !head_taps || !hist || !acc || !y_t) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_step_desc& d = *desc;
+  if (int st = step_desc_counts(d)) return st;
+  if (t < 0 || t >= d.max_len)
+    return fail(FC_ERR_INVALID, "position %lld lies outside the stream's max_len = %lld", (long long)t, (long long)d.max_len);
+  if (first < 0 || first > t)
+    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t = %lld]", (long long)first, (long long)t);
+  if (int st = step_desc_limits(d)) return st;
+  const int64_t cog = d.out_channels / d.groups;
   LongStepArgs a;
   a.x = x_t; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
   a.hist = hist; a.acc = acc; a.y = y_t;
@@ -44,5 +59,39 @@ extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, cons
   a.io = d.dtype;
   const int waves = (int)std::min<int64_t>(cog, kLongStepWaves);
   FC_HIP(long_step_launch(a, d.batch * d.groups, waves, static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_long_push(const fc_long_step_desc* desc, const void* x, const void* pregate, const void* postgate,
+                            const float* head_taps, const float* bias, float* hist, const float* acc, void* y, int64_t t0,
+                            int64_t count, int64_t first, void* hip_stream) {
+  if (!desc || !x || !head_taps || !hist || !acc || !y) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_step_desc& d = *desc;
+  if (int st = step_desc_counts(d)) return st;
+  if (count < 1) return fail(FC_ERR_INVALID, "count (%lld) must be positive", (long long)count);
+  if (t0 < 0 || t0 > d.max_len - count)
+    return fail(FC_ERR_INVALID, "the columns [%lld, %lld + %lld) lie outside the stream's max_len = %lld", (long long)t0,
+                (long long)t0, (long long)count, (long long)d.max_len);
+  if (first < 0 || first > t0)
+    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t0 = %lld]", (long long)first, (long long)t0);
+  if (int st = step_desc_limits(d)) return st;
+  const int64_t cig = d.in_channels / d.groups, cog = d.out_channels / d.groups;
+  const int64_t tiles = (count + 63) / 64;      // (count <= max_len < 2^29)
+  if (d.batch * d.groups > 0x7fffffffLL / tiles)
+    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups x %lld tiles of 64 columns exceed the 2^31 workgroups of "
+                "one launch", (long long)d.batch, (long long)d.groups, (long long)tiles);
+  LongPushArgs a;
+  a.x = x; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
+  a.hist = hist; a.acc = acc; a.y = y;
+  a.t0 = t0; a.count = count; a.first = first; a.max_len = d.max_len;
+  a.tiles = (int)tiles;
+  const int64_t window = (64 + d.head - 1) * 4;      // bytes of one channel's staged samples: at most 4348
+  a.cblock = (int)std::min<int64_t>(cig, kLongPushLds / window);
+  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
+  a.ulog = __builtin_ctzll((unsigned long long)d.head);
+  a.io = d.dtype;
+  const int waves = (int)std::min<int64_t>(cog, kLongPushWaves);
+  FC_HIP(long_push_launch(a, d.batch * d.groups * tiles, waves, (size_t)(a.cblock * window),
+                          static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

@@ -1282,6 +1282,48 @@ def _long_stream_blocks(i: int, head: int, taps: int, first: int) -> list:
     return due
 
 
+def _long_push_bulk_enabled() -> bool:
+    """FFTCONV_LONG_PUSH_BULK=0 (read per call): a push runs by windows and the step's own blocks only."""
+    return os.environ.get("FFTCONV_LONG_PUSH_BULK", "1") != "0"
+
+
+def _long_push_plan(p: int, T: int, head: int, taps: int, first: int, bulk: bool = True) -> list:
+    """The ops of a push of ``T`` tokens at position ``p``, in order, pure; the only place the push's schedule lives:
+
+      ("window", t, m)                         one ``fc_long_push`` launch over the columns [t, t + m);
+      ("block", i, n, lo, tap0, tap1, out0)    one entry of ``_long_stream_blocks(i, ...)``, run as a step runs it;
+      ("bulk", i, n, head, min(2n, taps))      the samples [i, i + n) of the chunk against the taps [head, min(2n, taps)),
+                                               ONE full linear convolution that lands on the positions from i + head on.
+
+    A bulk is emitted where i is a multiple of ``head`` and ``head < taps``: n is the largest power of two >= 2 head that
+    divides i and fits the chunk (it stops doubling once it reaches ``taps``).  Because n divides i, every level <= n was
+    due at i for the samples before i, and every block of a higher level that is still open lands at or after i + n: after
+    the bulk, ``acc`` is complete on [i, i + n), so ONE window over all n columns follows, and at i + n only the due
+    blocks of the levels > n run (the bulk has covered every (sample, tap) pair of the levels <= n).  Everywhere else a
+    window runs up to the next multiple of ``head`` (or the end of the chunk), followed by all blocks due there.
+    ``bulk=False``: windows and blocks only.  ``first`` is the prefill's and is not moved by a push."""
+    ops, i, end = [], int(p), int(p) + int(T)
+
+    def due(at, above):
+        return [("block", at) + b for b in _long_stream_blocks(at, head, taps, first) if b[0] > above]
+
+    while i < end:
+        if bulk and head < taps and i % (2 * head) == 0 and i + 2 * head <= end:
+            n = 2 * head
+            while n < taps and i % (2 * n) == 0 and i + 2 * n <= end:
+                n *= 2
+            ops += [("bulk", i, n, head, min(2 * n, taps)), ("window", i, n)]
+            i += n
+            ops += due(i, n)
+            continue
+        m = min(head - i % head, end - i)
+        ops.append(("window", i, m))
+        i += m
+        if i % head == 0:
+            ops += due(i, 0)
+    return ops
+
+
 def _long_stream_args(kernel, bias, groups, batch, max_len, head):
     """Argument checks of ``FFTLongConvStream`` (ValueError for shapes, counts and devices, TypeError for dtypes; before any
     device call) -> (cin, cout, taps, head)."""
@@ -1337,6 +1379,28 @@ def _long_step_args(x_t, pregate, postgate, batch: int, cin: int, cout: int, dty
             raise ValueError(f"`{name}` is on {t.device} but the stream is on {device}")
 
 
+def _long_push_args(x, pregate, postgate, batch: int, cin: int, cout: int, dtype, device) -> int:
+    """Argument checks of ``FFTLongConvStream.push`` (before any device call), as ``_long_step_args`` does it -> T."""
+    if not isinstance(x, Tensor):
+        raise TypeError(f"`x` must be a tensor, got {type(x).__name__}")
+    if x.ndim != 3 or tuple(x.shape[:2]) != (batch, cin) or x.shape[2] < 1:
+        raise ValueError(f"`x` must have shape ({batch}, {cin}, T >= 1), got {tuple(x.shape)}")
+    count = int(x.shape[2])
+    for name, t, shape in (("x", x, (batch, cin, count)), ("pregate", pregate, (batch, cin, count)),
+                           ("postgate", postgate, (batch, cout, count))):
+        if t is None and name != "x":
+            continue
+        if not isinstance(t, Tensor):
+            raise TypeError(f"`{name}` must be a tensor or None, got {type(t).__name__}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"`{name}` must have shape {shape}, got {tuple(t.shape)}")
+        if t.dtype != dtype:
+            raise TypeError(f"`{name}` has dtype {t.dtype} but the stream was made for {dtype}")
+        if t.device != device:
+            raise ValueError(f"`{name}` is on {t.device} but the stream is on {device}")
+    return count
+
+
 class FFTLongConvStream:
     """Token-by-token decoding of a causal long filter: after ``prefill`` and ``step`` calls the outputs, in order, are the
     columns of ``fft_long_conv(z, kernel, bias, groups=groups, causal=True)`` on the row z = pregate * x seen so far, each
@@ -1358,12 +1422,17 @@ class FFTLongConvStream:
 
     State (float32 whatever the tensors' dtype): ``hist`` (B, Cin, max_len) holds z, ``acc`` (B, Cout, max_len) the block
     results that have landed on future positions; ``state_bytes`` reports both.  16-bit streams compute what the float32
-    stream on the widened tensors computes and round each output once.
+    stream on the widened tensors computes and round each output once.  The plan and spectrum of a push's bulk level are
+    made at the first push that needs them (``bulk_spectrum_bytes``); a stream that never pushes a bulk holds none.
 
     ``prefill(x)``      x (B, Cin, L0), only at position 0, L0 <= max_len -> y (B, Cout, L0); ungated.
     ``step(x_t, pregate=None, postgate=None)``   x_t, pregate (B, Cin), postgate (B, Cout) -> y_t (B, Cout).
+    ``push(x, pregate=None, postgate=None)``     x, pregate (B, Cin, T), postgate (B, Cout, T), at any position -> y
+                        (B, Cout, T): the columns T steps would have returned, through the schedule of ``_long_push_plan``
+                        (windows of ``fc_long_push``, the step's blocks, and one bulk convolution per aligned run of the
+                        chunk; FFTCONV_LONG_PUSH_BULK=0: no bulks).  May be mixed freely with ``step``.
     ``reset()``         back to position 0.
-    Stepping past ``max_len`` raises ``RuntimeError``; wrong shapes and devices ``ValueError``, wrong dtypes ``TypeError``,
+    Stepping or pushing past ``max_len`` raises ``RuntimeError``; wrong shapes and devices ``ValueError``, wrong dtypes ``TypeError``,
     before any device call."""
 
     def __init__(self, kernel: Tensor, bias: Optional[Tensor] = None, groups: int = 1, *, batch: int, max_len: int,
@@ -1388,6 +1457,7 @@ class FFTLongConvStream:
                 seg = wide[..., n:min(2 * n, taps)].flip(-1).contiguous()
                 self._levels[n] = self._level(n, seg)
                 n *= 2
+        self._bulk_levels = {}      # level n of a push's bulk (``_run_bulk``): made at the first push that needs it
 
     def _level(self, n: int, seg: Tensor):
         """(flipped taps, padding, plan of the hand-off or None, spectrum) of the full convolution of n samples with ``seg``:
@@ -1468,6 +1538,72 @@ class FFTLongConvStream:
             for n, lo, _, _, _ in _long_stream_blocks(i, self.head, self.taps, self._first):
                 self._run_block(i, n, lo)
         return y
+
+    @torch.no_grad()
+    def push(self, x: Tensor, pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
+        """Append T tokens at the current position: the T columns that T calls of ``step`` would have returned, in order
+        (``_long_push_plan`` has the schedule; a window is ONE launch of ``fc_long_push``)."""
+        count = _long_push_args(x, pregate, postgate, self.batch, self.in_channels, self.out_channels, self.dtype, self.device)
+        p = self._position
+        if p + count > self.max_len:
+            raise RuntimeError(f"a push of T = {count} tokens at position {p} passes max_len = {self.max_len} "
+                               f"(reset() starts a new row)")
+        x, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x, pregate, postgate))
+        ops = _long_push_plan(p, count, self.head, self.taps, self._first, _long_push_bulk_enabled())
+        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
+            y = self._run_push(ops, x, pregate, postgate, p, count)
+        else:
+            with torch.cuda.device(self.device):
+                y = self._run_push(ops, x, pregate, postgate, p, count)
+        self._position = p + count
+        return y
+
+    def _run_push(self, ops, x, pregate, postgate, p: int, count: int) -> Tensor:
+        y = torch.empty((self.batch, self.out_channels, count), dtype=self.dtype, device=self.device)
+        for op in ops:
+            if op[0] == "window":
+                self._push_window(x, pregate, postgate, y, p, op[1], op[2])
+            elif op[0] == "bulk":
+                self._run_bulk(x, pregate, p, op[1], op[2])
+            elif op[1] < self.max_len:       # (as a step: nothing is due at max_len)
+                self._run_block(op[1], op[2], op[3])
+        return y
+
+    def _push_window(self, x, pregate, postgate, y, p: int, t: int, m: int):
+        """One ``fc_long_push`` launch over the columns [t, t + m) of a chunk that began at ``p``.  The call reads chunk
+        tensors of row length m: a window that is not the whole chunk runs on contiguous copies of its columns."""
+        whole = m == int(x.shape[2])
+        cut = lambda v: v if v is None or whole else v[:, :, t - p:t - p + m].contiguous()      # noqa: E731
+        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+        xs, pre, post = cut(x), cut(pregate), cut(postgate)
+        out = y if whole else torch.empty((self.batch, self.out_channels, m), dtype=self.dtype, device=self.device)
+        _native.long_push(self._desc, xs.data_ptr(), ptr(pre), ptr(post), self._head_taps.data_ptr(), ptr(self._bias),
+                          self.hist.data_ptr(), self.acc.data_ptr(), out.data_ptr(), t, m, self._first,
+                          torch.cuda.current_stream(self.device).cuda_stream)
+        if not whole:
+            y[:, :, t - p:t - p + m] = out
+
+    def _run_bulk(self, x, pregate, p: int, i: int, n: int):
+        """The chunk's samples [i, i + n) against the taps [head, min(2n, taps)): one full convolution added to ``acc`` from
+        position i + head on, clipped at ``max_len``.  The level (geometry, plan, spectrum) is made at the first push that
+        needs it and kept in ``_bulk_levels``."""
+        level = self._bulk_levels.get(n)
+        if level is None:
+            hi = min(2 * n, self.taps)
+            seg = self._flipped[..., self.taps - hi:self.taps - self.head].contiguous()      # the taps [head, hi), flipped
+            level = self._bulk_levels[n] = self._level(n, seg)
+        rows = x[:, :, i - p:i - p + n].float()
+        if pregate is not None:
+            rows = rows * pregate[:, :, i - p:i - p + n].float()
+        out = self._full_conv(rows.contiguous(), level)
+        at = i + self.head
+        keep = min(int(out.shape[2]), self.max_len - at)
+        self.acc[:, :, at:at + keep] += out[:, :, :keep]
+
+    @property
+    def bulk_spectrum_bytes(self) -> int:
+        """Bytes of the spectra that pushes have made so far (``_bulk_levels``; none until a push runs a bulk)."""
+        return sum(level[3].buf.numel() * level[3].buf.element_size() for level in self._bulk_levels.values())
 
     def _launch_step(self, x_t, pregate, postgate, t, ptr) -> Tensor:
         y = torch.empty((self.batch, self.out_channels), dtype=self.dtype, device=self.device)

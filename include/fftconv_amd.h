@@ -560,7 +560,7 @@ int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, 
                           const float* bias, void* y, const void* gate, void* y2, const void* gate2, int y_dtype,
                           int y2_dtype, void* workspace, void* hip_stream);
 
-/* ---- Token-by-token decoding of a causal long filter (ABI 7 extension: one new struct and one new entry point; every
+/* ---- Token-by-token decoding of a causal long filter (ABI 7 extension: one new struct and two new entry points; every
  * struct and call above keeps its layout, signature and meaning, and every kernel that existed its arguments).
  * A causal convolution y[t] = bias + sum_k kernel[k] * z[t - k] whose input arrives one sample at a time can be cut into
  * power-of-two blocks of history against segments of the taps; the caller runs those blocks with the calls above as they
@@ -595,6 +595,28 @@ typedef struct fc_long_step_desc {
 int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pregate, const void* postgate,
                  const float* head_taps, const float* bias, float* hist, const float* acc, void* y_t, int64_t t,
                  int64_t first, void* hip_stream);
+
+/* `count` consecutive steps in ONE launch: the columns t = t0 ... t0 + count - 1 that `count` calls of fc_long_step would
+ * have produced, for a chunk of tokens that is known at once (a further chunk of a prompt, speculative tokens to verify).
+ * The chunk tensors are indexed by j = t - t0:
+ *   z[b][c][t]  = pregate[b][c][j] * x[b][c][j]            (one float32 multiply of the widened samples); stored to hist[b][c][t]
+ *   y[b][o][j]  = postgate[b][o][j] * (bias[o] + acc[b][o][t]
+ *                 + sum over the group's input channels c and the taps k < head with t - k >= first of
+ *                   head_taps[o][c][k] * z[b][c][t - k])
+ * x, pregate (B, Cin, count) and y, postgate (B, Cout, count) are contiguous tensors of the descriptor's dtype; the other
+ * arguments are those of fc_long_step.  A sample t - k >= t0 is taken from the chunk (the product is formed again), never
+ * from hist; one below t0 is read from hist, one below `first` is zero.  The columns [t0, t0 + count) of hist are the only
+ * place of hist that is written, acc is only read -- that it is complete for these columns is the caller's affair: the
+ * call has no alignment rule of its own -- and y is written in full and no other byte.  Each output is one chain of
+ * float32 fused multiply-adds over c ascending, then k ascending, so the bits of a column do not depend on how a row is
+ * cut into calls (they are not those of fc_long_step, whose lanes share the sum differently).
+ *   One workgroup per (batch item, group, tile of 64 columns); stateless like the step.
+ *   FC_ERR_INVALID with text: a null tensor, the descriptor errors of fc_long_step, count < 1, t0 < 0,
+ *   t0 + count > max_len, first outside [0, t0].  FC_ERR_UNSUPPORTED with text: as for the step, and
+ *   B * groups * ceil(count / 64) past 2^31 workgroups.  Either launches nothing. */
+int fc_long_push(const fc_long_step_desc* desc, const void* x, const void* pregate, const void* postgate,
+                 const float* head_taps, const float* bias, float* hist, const float* acc, void* y,
+                 int64_t t0, int64_t count, int64_t first, void* hip_stream);
 
 #ifdef __cplusplus
 }

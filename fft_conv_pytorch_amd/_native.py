@@ -187,6 +187,7 @@ def _signatures() -> dict:
         # (the decoding step; the table's last entry stays the gated forward, which tests pin)
         "fc_long_step": (i32, (ptr(FcLongStepDesc), vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp)),
         "fc_long_push": (i32, (ptr(FcLongStepDesc), vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp)),
+        "fc_long_spec": (i32, (ptr(FcLongStepDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp)),
         "fc_long_forward_gated": (i32, (vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp)),
     }
 
@@ -688,6 +689,15 @@ def long_push(desc: FcLongStepDesc, x_ptr: int, pregate_ptr: Optional[int], post
     lib = load_library()
     _check(lib, lib.fc_long_push(ctypes.byref(desc), x_ptr, pregate_ptr, postgate_ptr, taps_ptr, bias_ptr, hist_ptr, acc_ptr,
                                  y_ptr, t0, count, first, stream))
+
+
+def long_spec(desc: FcLongStepDesc, x_ptr: int, pregate_ptr: Optional[int], postgate_ptr: Optional[int], taps_ptr: int,
+              flipped_ptr: int, bias_ptr: Optional[int], hist_ptr: int, acc_ptr: int, y_ptr: int, t0: int, count: int,
+              first: int, stream: int):
+    """``fc_long_spec``: ``count`` <= head draft columns from position ``t0`` in one launch that only reads ``acc``."""
+    lib = load_library()
+    _check(lib, lib.fc_long_spec(ctypes.byref(desc), x_ptr, pregate_ptr, postgate_ptr, taps_ptr, flipped_ptr, bias_ptr,
+                                 hist_ptr, acc_ptr, y_ptr, t0, count, first, stream))
 
 
 # the tag of a long-filter key -> the class that owns its plan (forward plans and the weight-gradient plan: one cache)

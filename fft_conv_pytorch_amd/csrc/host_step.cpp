@@ -1,12 +1,13 @@
-// host_step.cpp -- fc_long_step and fc_long_push (include/fftconv_amd.h "Token-by-token decoding"): descriptor checks and
-// the one launch of long_step_kernel (long_step.hpp) or long_push_kernel (long_push.hpp).  Stateless: no plan, no
-// allocation, nothing but the launch on the caller's stream.
+// host_step.cpp -- fc_long_step, fc_long_push and fc_long_spec (include/fftconv_amd.h "Token-by-token decoding"):
+// descriptor checks and the one launch of long_step_kernel (long_step.hpp), long_push_kernel (long_push.hpp) or
+// long_spec_kernel (long_spec.hpp).  Stateless: no plan, no allocation, nothing but the launch on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "fc_plan.h"
 #include "long_push.hpp"
+#include "long_spec.hpp"
 #include "long_step.hpp"
 
 using namespace fc;
@@ -92,6 +93,51 @@ extern "C" int fc_long_push(const fc_long_step_desc* desc, const void* x, const 
   a.io = d.dtype;
   const int waves = (int)std::min<int64_t>(cog, kLongPushWaves);
   FC_HIP(long_push_launch(a, d.batch * d.groups * tiles, waves, (size_t)(a.cblock * window),
+                          static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_long_spec(const fc_long_step_desc* desc, const void* x, const void* pregate, const void* postgate,
+                            const float* head_taps, const float* filter_flipped, const float* bias, float* hist,
+                            const float* acc, void* y, int64_t t0, int64_t count, int64_t first, void* hip_stream) {
+  if (!desc || !x || !head_taps || !filter_flipped || !hist || !acc || !y) return fail(FC_ERR_INVALID, "null argument");
+  const fc_long_step_desc& d = *desc;
+  if (int st = step_desc_counts(d)) return st;
+  if (count < 1) return fail(FC_ERR_INVALID, "count (%lld) must be positive", (long long)count);
+  if (t0 < 0 || t0 > d.max_len - count)
+    return fail(FC_ERR_INVALID, "the columns [%lld, %lld + %lld) lie outside the stream's max_len = %lld", (long long)t0,
+                (long long)t0, (long long)count, (long long)d.max_len);
+  if (first < 0 || first > t0)
+    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t0 = %lld]", (long long)first, (long long)t0);
+  if (int st = step_desc_limits(d)) return st;
+  if (count > d.head)
+    return fail(FC_ERR_INVALID, "count (%lld) exceeds head = %lld: a draft is verified against the head taps and the blocks "
+                "due at one multiple of head", (long long)count, (long long)d.head);
+  const int64_t cig = d.in_channels / d.groups, cog = d.out_channels / d.groups;
+  const int64_t tiles = (count + 63) / 64;      // (count <= head <= 1024: at most 16)
+  if (d.batch * d.groups > 0x7fffffffLL / tiles)
+    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups x %lld tiles of 64 columns exceed the 2^31 workgroups of "
+                "one launch", (long long)d.batch, (long long)d.groups, (long long)tiles);
+  LongSpecArgs s;
+  LongPushArgs& a = s.p;
+  a.x = x; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
+  a.hist = hist; a.acc = acc; a.y = y;
+  a.t0 = t0; a.count = count; a.first = first; a.max_len = d.max_len;
+  a.tiles = (int)tiles;
+  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
+  a.ulog = __builtin_ctzll((unsigned long long)d.head);
+  a.io = d.dtype;
+  // the one multiple of head that can lie inside (t0, t0 + count); its blocks are due only if it does and below max_len
+  const int64_t m = (t0 / d.head + 1) * d.head;
+  s.flipped = filter_flipped; s.K = d.kernel; s.M = t0 + count; s.levels = 0;      // (M = the end: no column at or past it)
+  if (m < t0 + count && m < d.max_len) {
+    s.M = m;
+    for (int64_t n = d.head; n < d.kernel && m % n == 0; n *= 2) ++s.levels;      // (n <= m < 2^29: at most 26 levels)
+  }
+  const int64_t window = (64 + d.head - 1) * 4;      // bytes of one channel's staged samples, as the push stages them
+  a.cblock = (int)std::min<int64_t>(cig, kLongPushLds / window);
+  const int waves = (int)std::min<int64_t>(cog, kLongPushWaves);
+  FC_HIP(long_spec_launch(s, d.batch * d.groups * tiles, waves, (size_t)(a.cblock * window),
                           static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

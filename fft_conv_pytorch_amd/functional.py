@@ -1324,6 +1324,24 @@ def _long_push_plan(p: int, T: int, head: int, taps: int, first: int, bulk: bool
     return ops
 
 
+def _long_spec_plan(p: int, T: int, head: int, taps: int, first: int, max_len: int):
+    """What a draft of ``T`` <= head tokens at position ``p`` must add to its columns because the blocks inside it have
+    not been run, pure -> (M or None, [(n, lo, tap0, tap1), ...]); the only place the draft's schedule lives.
+
+    M = (p // head + 1) * head is the one multiple of ``head`` that can lie inside (p, p + T).  If it does not, or if
+    M >= max_len (nothing is due there), the answer is (None, []): every column is ``acc`` + the head taps.  Otherwise the
+    list holds the entries of ``_long_stream_blocks(M, ...)`` without their out0, and a column t >= M needs
+
+        late(t) = sum over (n, lo, tap0, tap1) and the samples s = lo ... t - n with t - s < tap1 of  w[t - s] * hist[s]
+
+    -- at most t - M + 1 <= T - 1 pairs per level, every s below p (t - n < p because t - p < head <= n): old samples.
+    ``fc_long_spec`` derives the same M and levels from (t0, head, kernel, max_len); ``accept`` runs the blocks."""
+    M = (int(p) // head + 1) * head
+    if M >= p + T or M >= max_len:
+        return None, []
+    return M, [(n, lo, tap0, tap1) for n, lo, tap0, tap1, _ in _long_stream_blocks(M, head, taps, first)]
+
+
 def _long_stream_args(kernel, bias, groups, batch, max_len, head):
     """Argument checks of ``FFTLongConvStream`` (ValueError for shapes, counts and devices, TypeError for dtypes; before any
     device call) -> (cin, cout, taps, head)."""
@@ -1431,9 +1449,27 @@ class FFTLongConvStream:
                         (B, Cout, T): the columns T steps would have returned, through the schedule of ``_long_push_plan``
                         (windows of ``fc_long_push``, the step's blocks, and one bulk convolution per aligned run of the
                         chunk; FFTCONV_LONG_PUSH_BULK=0: no bulks).  May be mixed freely with ``step``.
+    ``speculate(x, pregate=None, postgate=None)``   shapes as ``push``, 1 <= T <= head -> y (B, Cout, T): the columns
+                        ``push`` would return for T DRAFT tokens, in ONE launch (``fc_long_spec``) that leaves ``position``,
+                        ``acc`` and ``hist[..., :position]`` alone.  The blocks that would fall due inside the draft (at the
+                        one multiple M of ``head`` it can pass; ``_long_spec_plan``) are not run: the kernel adds what they
+                        would have put on the columns t >= M as a direct sum over old samples of ``hist`` and the whole
+                        filter (the flipped float32 copy the prefill uses; no further copy is kept).  z is stored into
+                        ``hist[..., p:p + T]``: columns at or past the position are never read, so rejected ones are
+                        dead data that the next call overwrites.  Columns t < M have the bits ``push`` gives them; columns
+                        t >= M hold to the same error bound but sum the late pairs in another order than the blocks do.
+    ``accept(count)``   commits the first ``count`` (0 ... T, an int; one count for the whole batch) tokens of the pending
+                        draft: moves the position and runs the blocks due at M if p < M <= p + count.  No kernel of the
+                        step, the push or the draft is launched.  Afterwards ``acc``, ``hist[..., :position]`` and every
+                        later output have the bits they would have had after ``push`` of those ``count`` tokens alone:
+                        nothing depends on what was speculated.  ``RuntimeError`` without a pending draft.
+                        ``step``, ``push``, ``prefill``, ``reset`` and another ``speculate`` drop a pending draft silently,
+                        as ``accept(0)`` does.
     ``reset()``         back to position 0.
-    Stepping or pushing past ``max_len`` raises ``RuntimeError``; wrong shapes and devices ``ValueError``, wrong dtypes ``TypeError``,
-    before any device call."""
+    Stepping, pushing or speculating past ``max_len`` raises ``RuntimeError``; wrong shapes and devices ``ValueError``, wrong
+    dtypes ``TypeError``, before any device call."""
+
+    _draft = None      # (position, tokens) of the draft ``speculate`` left pending, until ``accept`` or any other call drops it
 
     def __init__(self, kernel: Tensor, bias: Optional[Tensor] = None, groups: int = 1, *, batch: int, max_len: int,
                  head: Optional[int] = None):
@@ -1493,6 +1529,7 @@ class FFTLongConvStream:
         self.hist.zero_()
         self.acc.zero_()
         self._position = self._first = 0
+        self._draft = None
 
     @torch.no_grad()
     def prefill(self, x: Tensor) -> Tensor:
@@ -1507,6 +1544,7 @@ class FFTLongConvStream:
             raise ValueError(f"`x` is on {x.device} but the stream is on {self.device}")
         if self._position:
             raise RuntimeError(f"prefill is allowed at position 0 only; the stream is at {self._position} (reset() first)")
+        self._draft = None
         length = int(x.shape[2])
         rows = x.detach().float().contiguous()
         full = _fft_long_conv_impl(rows, self._flipped, None, self.taps - 1, self.groups, False, None)
@@ -1526,6 +1564,7 @@ class FFTLongConvStream:
         t = self._position
         if t >= self.max_len:
             raise RuntimeError(f"the stream is at position {t} = max_len: no further step (reset() starts a new row)")
+        self._draft = None
         x_t, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x_t, pregate, postgate))
         ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
         if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
@@ -1548,6 +1587,7 @@ class FFTLongConvStream:
         if p + count > self.max_len:
             raise RuntimeError(f"a push of T = {count} tokens at position {p} passes max_len = {self.max_len} "
                                f"(reset() starts a new row)")
+        self._draft = None
         x, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x, pregate, postgate))
         ops = _long_push_plan(p, count, self.head, self.taps, self._first, _long_push_bulk_enabled())
         if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
@@ -1557,6 +1597,59 @@ class FFTLongConvStream:
                 y = self._run_push(ops, x, pregate, postgate, p, count)
         self._position = p + count
         return y
+
+    @torch.no_grad()
+    def speculate(self, x: Tensor, pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
+        """Verify T <= head draft tokens at the current position: the T columns ``push`` would return, in ONE library
+        call (``fc_long_spec``) that does not touch ``acc``.  The position does not move and ``hist`` below it is not
+        written; z = pregate * x is stored into ``hist[..., p:p + T]``, columns no kernel and no block reads until the
+        position passes them.  The draft (p, T) stays pending until ``accept``; see the class docstring."""
+        count = _long_push_args(x, pregate, postgate, self.batch, self.in_channels, self.out_channels, self.dtype, self.device)
+        p = self._position
+        if count > self.head:
+            raise ValueError(f"a draft of T = {count} tokens exceeds head = {self.head}: speculate verifies at most `head` "
+                             f"tokens at once (push appends any number)")
+        if p + count > self.max_len:
+            raise RuntimeError(f"a draft of T = {count} tokens at position p = {p} passes max_len = {self.max_len} "
+                               f"(reset() starts a new row)")
+        x, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x, pregate, postgate))
+        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
+            y = self._launch_spec(x, pregate, postgate, p, count)
+        else:
+            with torch.cuda.device(self.device):
+                y = self._launch_spec(x, pregate, postgate, p, count)
+        self._draft = (p, count)
+        return y
+
+    def _launch_spec(self, x, pregate, postgate, p: int, count: int) -> Tensor:
+        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+        y = torch.empty((self.batch, self.out_channels, count), dtype=self.dtype, device=self.device)
+        _native.long_spec(self._desc, x.data_ptr(), ptr(pregate), ptr(postgate), self._head_taps.data_ptr(),
+                          self._flipped.data_ptr(), ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(),
+                          p, count, self._first, torch.cuda.current_stream(self.device).cuda_stream)
+        return y
+
+    @torch.no_grad()
+    def accept(self, count: int) -> None:
+        """Commit the first ``count`` tokens of the pending draft (0 ... T; one count for the whole batch): the position
+        moves to p + count and, if a multiple M of ``head`` with p < M <= p + count lies below ``max_len``, the blocks due
+        at M run from ``hist`` as a step runs them.  No step, push or draft kernel is launched.  ``accept(0)`` only
+        clears the draft.  After it the state has the bits a ``push`` of those ``count`` tokens would have left."""
+        if self._draft is None:
+            raise RuntimeError("accept() without a pending draft: speculate() first (step, push, prefill, reset and another "
+                               "speculate drop a draft)")
+        p, T = self._draft
+        if isinstance(count, bool) or not isinstance(count, int):
+            raise TypeError(f"count must be an int, got {type(count).__name__}")
+        if not 0 <= count <= T:
+            raise ValueError(f"count must lie in [0, T = {T}], got {count}")
+        self._draft = None
+        self._position = p + count
+        M = (p // self.head + 1) * self.head      # (as ``_long_spec_plan``: the one multiple of head a draft can pass)
+        if M <= p + count and M < self.max_len:
+            with torch.cuda.device(self.device):
+                for n, lo, _, _, _ in _long_stream_blocks(M, self.head, self.taps, self._first):
+                    self._run_block(M, n, lo)
 
     def _run_push(self, ops, x, pregate, postgate, p: int, count: int) -> Tensor:
         y = torch.empty((self.batch, self.out_channels, count), dtype=self.dtype, device=self.device)

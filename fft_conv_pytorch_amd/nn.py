@@ -293,7 +293,9 @@ class FFTLongConv1d(_SpectrumCache, nn.Conv1d):
 
     def stream(self, batch: int, max_len: int, head=None):
         """A ``FFTLongConvStream`` on this module's weight and bias as they are now (a snapshot), for decoding one token at
-        a time: its outputs are the columns of this module's forward on the whole row.  Only for a module with
+        a time: its outputs are the columns of this module's forward on the whole row.  Besides ``step``, ``push`` and
+        ``prefill`` the stream verifies up to ``head`` draft tokens without committing them (``speculate``) and then
+        commits the accepted ones (``accept``).  Only for a module with
         ``causal=True``, stride 1, dilation 1, padding_mode 'zeros' and ``channels_last=False`` (else ``ValueError``)."""
         if not (self.causal and int(self.stride[0]) == 1 and int(self.dilation[0]) == 1 and self.padding_mode == "zeros"
                 and not self.channels_last):

@@ -560,7 +560,7 @@ int fc_long_forward_gated(const fc_long_plan* plan, const void* x, int x_dtype, 
                           const float* bias, void* y, const void* gate, void* y2, const void* gate2, int y_dtype,
                           int y2_dtype, void* workspace, void* hip_stream);
 
-/* ---- Token-by-token decoding of a causal long filter (ABI 7 extension: one new struct and two new entry points; every
+/* ---- Token-by-token decoding of a causal long filter (ABI 7 extension: one new struct and three new entry points; every
  * struct and call above keeps its layout, signature and meaning, and every kernel that existed its arguments).
  * A causal convolution y[t] = bias + sum_k kernel[k] * z[t - k] whose input arrives one sample at a time can be cut into
  * power-of-two blocks of history against segments of the taps; the caller runs those blocks with the calls above as they
@@ -617,6 +617,34 @@ int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pre
 int fc_long_push(const fc_long_step_desc* desc, const void* x, const void* pregate, const void* postgate,
                  const float* head_taps, const float* bias, float* hist, const float* acc, void* y,
                  int64_t t0, int64_t count, int64_t first, void* hip_stream);
+
+/* Up to `head` DRAFT tokens verified in ONE launch that leaves the accumulator alone: the columns t = t0 ... t0 + count - 1
+ * that fc_long_push would return if the caller had first run the blocks that fall due inside the chunk -- which the
+ * caller has NOT done, so that tokens the verifier rejects leave no trace in acc.  (A new entry point; ABI 7 as before.)
+ * With M = (t0 / head + 1) * head, the only multiple of head that can lie inside (t0, t0 + count):
+ *   z[b][c][t]  = pregate[b][c][j] * x[b][c][j]            stored to hist[b][c][t], as the push stores it
+ *   y[b][o][j]  = postgate[b][o][j] * (acc[b][o][t] + bias[o]
+ *                 + sum over c and the taps k < head with t - k >= first of head_taps[o][c][k] * z[b][c][t - k]
+ *                 + late[b][o][t])
+ *   late[b][o][t] = 0 for t < M, and whenever M >= t0 + count or M >= max_len; otherwise the sum over c, over the levels
+ *                 n = head, 2 head, 4 head, ... < kernel that divide M, and over the samples s = M - n ... t - n with
+ *                 s >= first and t - s < min(2n, kernel), of filter[o][c][t - s] * hist[b][c][s]
+ * -- what the blocks due at M would have added to acc[b][o][t].  Every such s lies below t0: an old sample of hist.
+ * filter_flipped (Cout, Cin/groups, kernel) is the whole float32 filter with tap k of (o, c) at index kernel - 1 - k; the
+ * other arguments are those of fc_long_push, and count <= head.  The columns [t0, t0 + count) of hist are the only place
+ * of hist that is written (a caller that rejects draft tokens simply does not advance: columns at or past the position
+ * are never read), acc is only read, y is written in full and no other byte.
+ * Bits: the head sum is the push kernel's chain and is added as there, so a column t < M has the bits fc_long_push gives
+ * it.  late is ONE chain of float32 fused multiply-adds of its own -- c ascending, then n ascending, then s ascending,
+ * pairs outside the conditions skipped -- added after the head sum; no atomics: the same call on the same state returns
+ * the same bits.  A column t >= M need not have the bits of a push that ran the blocks (their sums are formed otherwise).
+ *   One workgroup per (batch item, group, tile of 64 columns); stateless like the step.
+ *   FC_ERR_INVALID with text: a null tensor (filter_flipped included), the descriptor errors of fc_long_step, count < 1,
+ *   count > head, t0 < 0, t0 + count > max_len, first outside [0, t0].  FC_ERR_UNSUPPORTED with text: as for the push.
+ *   Either launches nothing. */
+int fc_long_spec(const fc_long_step_desc* desc, const void* x, const void* pregate, const void* postgate,
+                 const float* head_taps, const float* filter_flipped, const float* bias, float* hist, const float* acc,
+                 void* y, int64_t t0, int64_t count, int64_t first, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 // host_step.cpp -- fc_long_step, fc_long_push and fc_long_spec (include/fftconv_amd.h "Token-by-token decoding"):
 // descriptor checks and the one launch of long_step_kernel (long_step.hpp), long_push_kernel (long_push.hpp) or
-// long_spec_kernel (long_spec.hpp).  Stateless: no plan, no allocation, nothing but the launch on the caller's stream.
+// long_spec_kernel (long_spec.hpp).  The push and the draft are one chunk to the host as to the kernels (LongChunk): one
+// set of checks and one argument fill; the draft adds its count limit, M and the levels.  Stateless: no plan, no
+// allocation, nothing but the launch on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +40,18 @@ static int step_desc_limits(const fc_long_step_desc& d) {
   return FC_OK;
 }
 
+// the pointers and the shape that the three argument structs name alike
+template <class Args>
+static void fill_state(Args& a, const fc_long_step_desc& d, const void* x, const void* pregate, const void* postgate,
+                       const float* head_taps, const float* bias, float* hist, const float* acc, void* y) {
+  a.x = x; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
+  a.hist = hist; a.acc = acc; a.y = y;
+  a.max_len = d.max_len;
+  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
+  a.ulog = __builtin_ctzll((unsigned long long)d.head);
+  a.io = d.dtype;
+}
+
 extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, const void* pregate, const void* postgate,
                             const float* head_taps, const float* bias, float* hist, const float* acc, void* y_t, int64_t t,
                             int64_t first, void* hip_stream) {
@@ -49,17 +63,41 @@ extern "C" int fc_long_step(const fc_long_step_desc* desc, const void* x_t, cons
   if (first < 0 || first > t)
     return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t = %lld]", (long long)first, (long long)t);
   if (int st = step_desc_limits(d)) return st;
-  const int64_t cog = d.out_channels / d.groups;
   LongStepArgs a;
-  a.x = x_t; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
-  a.hist = hist; a.acc = acc; a.y = y_t;
-  a.t = t; a.max_len = d.max_len;
+  fill_state(a, d, x_t, pregate, postgate, head_taps, bias, hist, acc, y_t);
+  a.t = t;
   a.reach = (int)std::min<int64_t>(d.head - 1, t - first);
-  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
-  a.ulog = __builtin_ctzll((unsigned long long)d.head);
-  a.io = d.dtype;
-  const int waves = (int)std::min<int64_t>(cog, kLongStepWaves);
+  const int waves = (int)std::min<int64_t>(d.out_channels / d.groups, kLongStepWaves);
   FC_HIP(long_step_launch(a, d.batch * d.groups, waves, static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+// A chunk of `count` columns from t0 on, for the push and the draft alike: the refusals of the call's position, then
+// what the kernels address ...
+static int chunk_checks(const fc_long_step_desc& d, int64_t t0, int64_t count, int64_t first) {
+  if (count < 1) return fail(FC_ERR_INVALID, "count (%lld) must be positive", (long long)count);
+  if (t0 < 0 || t0 > d.max_len - count)
+    return fail(FC_ERR_INVALID, "the columns [%lld, %lld + %lld) lie outside the stream's max_len = %lld", (long long)t0,
+                (long long)t0, (long long)count, (long long)d.max_len);
+  if (first < 0 || first > t0)
+    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t0 = %lld]", (long long)first, (long long)t0);
+  return step_desc_limits(d);
+}
+
+struct ChunkLaunch { long long grid; int waves; size_t lds; };      // workgroups, waves of each, bytes of dynamic LDS
+
+// ... and last (the draft's own limit comes before it) the workgroups of the launch; then what fill_state leaves open
+static int fill_chunk(LongPushArgs& a, ChunkLaunch& l, const fc_long_step_desc& d, int64_t t0, int64_t count, int64_t first) {
+  const int64_t tiles = (count + 63) / 64;      // (count <= max_len < 2^29)
+  if (d.batch * d.groups > 0x7fffffffLL / tiles)
+    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups x %lld tiles of 64 columns exceed the 2^31 workgroups of "
+                "one launch", (long long)d.batch, (long long)d.groups, (long long)tiles);
+  a.t0 = t0; a.count = count; a.first = first;
+  a.tiles = (int)tiles;
+  const int64_t window = (64 + d.head - 1) * 4;      // bytes of one channel's staged samples: at most 4348
+  a.cblock = (int)std::min<int64_t>(d.in_channels / d.groups, kLongPushLds / window);
+  l = {d.batch * d.groups * tiles, (int)std::min<int64_t>(d.out_channels / d.groups, kLongPushWaves),
+       (size_t)(a.cblock * window)};
   return FC_OK;
 }
 
@@ -69,31 +107,12 @@ extern "C" int fc_long_push(const fc_long_step_desc* desc, const void* x, const 
   if (!desc || !x || !head_taps || !hist || !acc || !y) return fail(FC_ERR_INVALID, "null argument");
   const fc_long_step_desc& d = *desc;
   if (int st = step_desc_counts(d)) return st;
-  if (count < 1) return fail(FC_ERR_INVALID, "count (%lld) must be positive", (long long)count);
-  if (t0 < 0 || t0 > d.max_len - count)
-    return fail(FC_ERR_INVALID, "the columns [%lld, %lld + %lld) lie outside the stream's max_len = %lld", (long long)t0,
-                (long long)t0, (long long)count, (long long)d.max_len);
-  if (first < 0 || first > t0)
-    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t0 = %lld]", (long long)first, (long long)t0);
-  if (int st = step_desc_limits(d)) return st;
-  const int64_t cig = d.in_channels / d.groups, cog = d.out_channels / d.groups;
-  const int64_t tiles = (count + 63) / 64;      // (count <= max_len < 2^29)
-  if (d.batch * d.groups > 0x7fffffffLL / tiles)
-    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups x %lld tiles of 64 columns exceed the 2^31 workgroups of "
-                "one launch", (long long)d.batch, (long long)d.groups, (long long)tiles);
+  if (int st = chunk_checks(d, t0, count, first)) return st;
   LongPushArgs a;
-  a.x = x; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
-  a.hist = hist; a.acc = acc; a.y = y;
-  a.t0 = t0; a.count = count; a.first = first; a.max_len = d.max_len;
-  a.tiles = (int)tiles;
-  const int64_t window = (64 + d.head - 1) * 4;      // bytes of one channel's staged samples: at most 4348
-  a.cblock = (int)std::min<int64_t>(cig, kLongPushLds / window);
-  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
-  a.ulog = __builtin_ctzll((unsigned long long)d.head);
-  a.io = d.dtype;
-  const int waves = (int)std::min<int64_t>(cog, kLongPushWaves);
-  FC_HIP(long_push_launch(a, d.batch * d.groups * tiles, waves, (size_t)(a.cblock * window),
-                          static_cast<hipStream_t>(hip_stream)));
+  ChunkLaunch l;
+  if (int st = fill_chunk(a, l, d, t0, count, first)) return st;
+  fill_state(a, d, x, pregate, postgate, head_taps, bias, hist, acc, y);
+  FC_HIP(long_push_launch(a, l.grid, l.waves, l.lds, static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }
 
@@ -103,30 +122,14 @@ extern "C" int fc_long_spec(const fc_long_step_desc* desc, const void* x, const 
   if (!desc || !x || !head_taps || !filter_flipped || !hist || !acc || !y) return fail(FC_ERR_INVALID, "null argument");
   const fc_long_step_desc& d = *desc;
   if (int st = step_desc_counts(d)) return st;
-  if (count < 1) return fail(FC_ERR_INVALID, "count (%lld) must be positive", (long long)count);
-  if (t0 < 0 || t0 > d.max_len - count)
-    return fail(FC_ERR_INVALID, "the columns [%lld, %lld + %lld) lie outside the stream's max_len = %lld", (long long)t0,
-                (long long)t0, (long long)count, (long long)d.max_len);
-  if (first < 0 || first > t0)
-    return fail(FC_ERR_INVALID, "first (%lld) must lie in [0, t0 = %lld]", (long long)first, (long long)t0);
-  if (int st = step_desc_limits(d)) return st;
+  if (int st = chunk_checks(d, t0, count, first)) return st;
   if (count > d.head)
     return fail(FC_ERR_INVALID, "count (%lld) exceeds head = %lld: a draft is verified against the head taps and the blocks "
                 "due at one multiple of head", (long long)count, (long long)d.head);
-  const int64_t cig = d.in_channels / d.groups, cog = d.out_channels / d.groups;
-  const int64_t tiles = (count + 63) / 64;      // (count <= head <= 1024: at most 16)
-  if (d.batch * d.groups > 0x7fffffffLL / tiles)
-    return fail(FC_ERR_UNSUPPORTED, "%lld batch items x %lld groups x %lld tiles of 64 columns exceed the 2^31 workgroups of "
-                "one launch", (long long)d.batch, (long long)d.groups, (long long)tiles);
   LongSpecArgs s;
-  LongPushArgs& a = s.p;
-  a.x = x; a.pregate = pregate; a.postgate = postgate; a.taps = head_taps; a.bias = bias;
-  a.hist = hist; a.acc = acc; a.y = y;
-  a.t0 = t0; a.count = count; a.first = first; a.max_len = d.max_len;
-  a.tiles = (int)tiles;
-  a.Cin = (int)d.in_channels; a.Cout = (int)d.out_channels; a.groups = (int)d.groups;
-  a.ulog = __builtin_ctzll((unsigned long long)d.head);
-  a.io = d.dtype;
+  ChunkLaunch l;
+  if (int st = fill_chunk(s.p, l, d, t0, count, first)) return st;
+  fill_state(s.p, d, x, pregate, postgate, head_taps, bias, hist, acc, y);
   // the one multiple of head that can lie inside (t0, t0 + count); its blocks are due only if it does and below max_len
   const int64_t m = (t0 / d.head + 1) * d.head;
   s.flipped = filter_flipped; s.K = d.kernel; s.M = t0 + count; s.levels = 0;      // (M = the end: no column at or past it)
@@ -134,10 +137,6 @@ extern "C" int fc_long_spec(const fc_long_step_desc* desc, const void* x, const 
     s.M = m;
     for (int64_t n = d.head; n < d.kernel && m % n == 0; n *= 2) ++s.levels;      // (n <= m < 2^29: at most 26 levels)
   }
-  const int64_t window = (64 + d.head - 1) * 4;      // bytes of one channel's staged samples, as the push stages them
-  a.cblock = (int)std::min<int64_t>(cig, kLongPushLds / window);
-  const int waves = (int)std::min<int64_t>(cog, kLongPushWaves);
-  FC_HIP(long_spec_launch(s, d.batch * d.groups * tiles, waves, (size_t)(a.cblock * window),
-                          static_cast<hipStream_t>(hip_stream)));
+  FC_HIP(long_spec_launch(s, l.grid, l.waves, l.lds, static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

@@ -37,28 +37,46 @@ struct LongPushArgs {
 constexpr int kLongPushWaves = 4;
 constexpr int kLongPushLds = 32 * 1024;
 
+// One workgroup's tile of 64 chunk columns: the index prologue, the staging with the hist stores, the head chain and the
+// epilogue described above, for long_push_kernel and for long_spec_kernel (long_spec.hpp).  A draft column without a late
+// sum has the bits a push gives it because both kernels run THIS code; every member is inlined.
 template <int IO>
-__global__ __launch_bounds__(64 * kLongPushWaves) void long_push_kernel(const LongPushArgs a) {
+struct LongChunk {
   using T = typename Io<IO>::T;
-  extern __shared__ float lds_push[];
-  const Io<IO> io(a.io);
-  const int tile = blockIdx.x % a.tiles;
-  const int bg = blockIdx.x / a.tiles;
-  const int g = bg % a.groups, b = bg / a.groups;
-  const int Cig = a.Cin / a.groups, Cog = a.Cout / a.groups;
-  const int tid = threadIdx.x, nthreads = blockDim.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthreads >> 6;
-  const int U = 1 << a.ulog, W = 64 + U - 1;
-  const long long j0 = (long long)tile * 64;             // first chunk column of the tile
-  const long long base = a.t0 + j0 - (U - 1);            // row position of staged sample 0 (may be negative)
-  const size_t xrow = (size_t)b * a.Cin + (size_t)g * Cig, yrow = (size_t)b * a.Cout + (size_t)g * Cog;
-  const T* x = static_cast<const T*>(a.x) + xrow * (size_t)a.count;
-  const T* pre = a.pregate ? static_cast<const T*>(a.pregate) + xrow * (size_t)a.count : nullptr;
-  float* hist = a.hist + xrow * (size_t)a.max_len;
-  const long long j = j0 + lane;                         // this lane's column of the chunk
-  const bool live = j < a.count;
-  const int nblocks = (Cig + a.cblock - 1) / a.cblock;
-  for (int o0 = 0; o0 < Cog; o0 += nwaves) {
+  const LongPushArgs& a;
+  const Io<IO> io;
+  int g, Cig, Cog, tid, nthreads, lane, wave, nwaves, U, W, nblocks;
+  long long j0, base, j;
+  size_t yrow;
+  const T *x, *pre;
+  float* hist;            // row 0 of the group's input channels
+  bool live;
+
+  __device__ __forceinline__ explicit LongChunk(const LongPushArgs& args) : a(args), io(args.io) {
+    const int tile = blockIdx.x % a.tiles;
+    const int bg = blockIdx.x / a.tiles;
+    g = bg % a.groups;
+    const int b = bg / a.groups;
+    Cig = a.Cin / a.groups, Cog = a.Cout / a.groups;
+    tid = threadIdx.x, nthreads = blockDim.x;
+    lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = nthreads >> 6;
+    U = 1 << a.ulog, W = 64 + U - 1;
+    j0 = (long long)tile * 64;                           // first chunk column of the tile
+    base = a.t0 + j0 - (U - 1);                          // row position of staged sample 0 (may be negative)
+    const size_t xrow = (size_t)b * a.Cin + (size_t)g * Cig;
+    yrow = (size_t)b * a.Cout + (size_t)g * Cog;
+    x = static_cast<const T*>(a.x) + xrow * (size_t)a.count;
+    pre = a.pregate ? static_cast<const T*>(a.pregate) + xrow * (size_t)a.count : nullptr;
+    hist = a.hist + xrow * (size_t)a.max_len;
+    j = j0 + lane;                                       // this lane's column of the chunk
+    live = j < a.count;
+    nblocks = (Cig + a.cblock - 1) / a.cblock;
+  }
+
+  // The head chain of output channel o0 + wave of the group (0 for a wave past Cog); every wave of the workgroup calls it
+  // for the same o0, ascending from 0: the round o0 == 0 stores the tile's hist columns.
+  __device__ __forceinline__ float head(int o0) const {
+    extern __shared__ float lds_chunk[];
     const int o = o0 + wave;                             // wave-uniform
     float s = 0.f;
     for (int c0 = 0; c0 < Cig; c0 += a.cblock) {
@@ -80,7 +98,7 @@ __global__ __launch_bounds__(64 * kLongPushWaves) void long_push_kernel(const Lo
                 if (o0 == 0 && i >= U - 1) hist[ch * (size_t)a.max_len + (size_t)pos] = z;      // the tile's own column
               }
             }
-            lds_push[c * W + i] = z;
+            lds_chunk[c * W + i] = z;
           }
         }
         __syncthreads();
@@ -88,22 +106,34 @@ __global__ __launch_bounds__(64 * kLongPushWaves) void long_push_kernel(const Lo
       if (o < Cog) {
         const float* w = a.taps + (((size_t)g * Cog + o) * (size_t)Cig + (size_t)c0) * (size_t)U;
         for (int c = 0; c < nc; ++c) {
-          const float* zc = lds_push + c * W + lane + (U - 1);
+          const float* zc = lds_chunk + c * W + lane + (U - 1);
           const float* wc = w + (size_t)c * U;
 #pragma unroll 8
           for (int k = 0; k < U; ++k) s = __builtin_fmaf(wc[k], zc[-k], s);
         }
       }
     }
+    return s;
+  }
+
+  // y of output channel o at this lane's column: r = acc; r += bias; r += head; [r += late;] r *= postgate, rounded once
+  __device__ __forceinline__ void store(int o, float head, bool has_late = false, float late = 0.f) const {
     if (o < Cog && live) {
       float r = a.acc[(yrow + o) * (size_t)a.max_len + (size_t)(a.t0 + j)];
       if (a.bias) r += a.bias[g * Cog + o];
-      r += s;
+      r += head;
+      if (has_late) r += late;
       const size_t at = (yrow + o) * (size_t)a.count + (size_t)j;
       if (a.postgate) r *= io.in(static_cast<const T*>(a.postgate)[at]);
       static_cast<T*>(a.y)[at] = io.out(r);
     }
   }
+};
+
+template <int IO>
+__global__ __launch_bounds__(64 * kLongPushWaves) void long_push_kernel(const LongPushArgs a) {
+  const LongChunk<IO> t(a);
+  for (int o0 = 0; o0 < t.Cog; o0 += t.nwaves) t.store(o0 + t.wave, t.head(o0));
 }
 
 // the float32 or the 16-bit build by the fc_dtype code of a.io; grid = B * groups * tiles workgroups of `waves` waves

@@ -1324,11 +1324,16 @@ def _long_push_plan(p: int, T: int, head: int, taps: int, first: int, bulk: bool
     return ops
 
 
+def _long_spec_multiple(p: int, head: int) -> int:
+    """M = (p // head + 1) * head: the one multiple of ``head`` that a draft of at most ``head`` tokens at ``p`` can pass."""
+    return (int(p) // head + 1) * head
+
+
 def _long_spec_plan(p: int, T: int, head: int, taps: int, first: int, max_len: int):
     """What a draft of ``T`` <= head tokens at position ``p`` must add to its columns because the blocks inside it have
     not been run, pure -> (M or None, [(n, lo, tap0, tap1), ...]); the only place the draft's schedule lives.
 
-    M = (p // head + 1) * head is the one multiple of ``head`` that can lie inside (p, p + T).  If it does not, or if
+    M = ``_long_spec_multiple(p, head)`` is the one multiple of ``head`` that can lie inside (p, p + T).  If it does not, or if
     M >= max_len (nothing is due there), the answer is (None, []): every column is ``acc`` + the head taps.  Otherwise the
     list holds the entries of ``_long_stream_blocks(M, ...)`` without their out0, and a column t >= M needs
 
@@ -1336,7 +1341,7 @@ def _long_spec_plan(p: int, T: int, head: int, taps: int, first: int, max_len: i
 
     -- at most t - M + 1 <= T - 1 pairs per level, every s below p (t - n < p because t - p < head <= n): old samples.
     ``fc_long_spec`` derives the same M and levels from (t0, head, kernel, max_len); ``accept`` runs the blocks."""
-    M = (int(p) // head + 1) * head
+    M = _long_spec_multiple(p, head)
     if M >= p + T or M >= max_len:
         return None, []
     return M, [(n, lo, tap0, tap1) for n, lo, tap0, tap1, _ in _long_stream_blocks(M, head, taps, first)]
@@ -1381,20 +1386,25 @@ def _long_stream_args(kernel, bias, groups, batch, max_len, head):
     return cig * groups, cout, taps, head
 
 
-def _long_step_args(x_t, pregate, postgate, batch: int, cin: int, cout: int, dtype, device):
-    """Argument checks of ``FFTLongConvStream.step`` (before any device call), as ``_long_gates`` checks gates: a wrong
-    shape or device raises ValueError, a wrong dtype TypeError."""
-    for name, t, shape in (("x_t", x_t, (batch, cin)), ("pregate", pregate, (batch, cin)), ("postgate", postgate, (batch, cout))):
-        if t is None and name != "x_t":
+def _long_stream_tensors(xname: str, x, pregate, postgate, xshape: tuple, yshape: tuple, dtype, device):
+    """The checks that a step and a chunk share, on the samples ``x`` (called ``xname``) and the optional gates."""
+    for name, t, shape in ((xname, x, xshape), ("pregate", pregate, xshape), ("postgate", postgate, yshape)):
+        if t is None and name != xname:
             continue
         if not isinstance(t, Tensor):
-            raise TypeError(f"`{name}` must be a tensor{'' if name == 'x_t' else ' or None'}, got {type(t).__name__}")
+            raise TypeError(f"`{name}` must be a tensor{'' if name == xname else ' or None'}, got {type(t).__name__}")
         if tuple(t.shape) != shape:
             raise ValueError(f"`{name}` must have shape {shape}, got {tuple(t.shape)}")
         if t.dtype != dtype:
             raise TypeError(f"`{name}` has dtype {t.dtype} but the stream was made for {dtype}")
         if t.device != device:
             raise ValueError(f"`{name}` is on {t.device} but the stream is on {device}")
+
+
+def _long_step_args(x_t, pregate, postgate, batch: int, cin: int, cout: int, dtype, device):
+    """Argument checks of ``FFTLongConvStream.step`` (before any device call), as ``_long_gates`` checks gates: a wrong
+    shape or device raises ValueError, a wrong dtype TypeError."""
+    _long_stream_tensors("x_t", x_t, pregate, postgate, (batch, cin), (batch, cout), dtype, device)
 
 
 def _long_push_args(x, pregate, postgate, batch: int, cin: int, cout: int, dtype, device) -> int:
@@ -1404,19 +1414,13 @@ def _long_push_args(x, pregate, postgate, batch: int, cin: int, cout: int, dtype
     if x.ndim != 3 or tuple(x.shape[:2]) != (batch, cin) or x.shape[2] < 1:
         raise ValueError(f"`x` must have shape ({batch}, {cin}, T >= 1), got {tuple(x.shape)}")
     count = int(x.shape[2])
-    for name, t, shape in (("x", x, (batch, cin, count)), ("pregate", pregate, (batch, cin, count)),
-                           ("postgate", postgate, (batch, cout, count))):
-        if t is None and name != "x":
-            continue
-        if not isinstance(t, Tensor):
-            raise TypeError(f"`{name}` must be a tensor or None, got {type(t).__name__}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"`{name}` must have shape {shape}, got {tuple(t.shape)}")
-        if t.dtype != dtype:
-            raise TypeError(f"`{name}` has dtype {t.dtype} but the stream was made for {dtype}")
-        if t.device != device:
-            raise ValueError(f"`{name}` is on {t.device} but the stream is on {device}")
+    _long_stream_tensors("x", x, pregate, postgate, (batch, cin, count), (batch, cout, count), dtype, device)
     return count
+
+
+def _ptr(t: Optional[Tensor]) -> Optional[int]:
+    """The address of an optional tensor (None: a null pointer)."""
+    return None if t is None else t.data_ptr()
 
 
 class FFTLongConvStream:
@@ -1558,6 +1562,21 @@ class FFTLongConvStream:
         self._position = self._first = length
         return y.to(self.dtype).contiguous()
 
+    def _on_device(self, run, *args):
+        """``run(*args)`` with the stream's device current."""
+        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
+            return run(*args)
+        with torch.cuda.device(self.device):
+            return run(*args)
+
+    def _run_due(self, i: int, above: int = 0):
+        """Run the blocks that fall due once ``i`` samples are known, the levels past ``above`` only (a push's bulk has
+        covered those up to it).  Nothing is due at ``max_len``."""
+        if i < self.max_len:
+            for n, lo, _, _, _ in _long_stream_blocks(i, self.head, self.taps, self._first):
+                if n > above:
+                    self._run_block(i, n, lo)
+
     @torch.no_grad()
     def step(self, x_t: Tensor, pregate: Optional[Tensor] = None, postgate: Optional[Tensor] = None) -> Tensor:
         _long_step_args(x_t, pregate, postgate, self.batch, self.in_channels, self.out_channels, self.dtype, self.device)
@@ -1566,16 +1585,9 @@ class FFTLongConvStream:
             raise RuntimeError(f"the stream is at position {t} = max_len: no further step (reset() starts a new row)")
         self._draft = None
         x_t, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x_t, pregate, postgate))
-        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
-        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
-            y = self._launch_step(x_t, pregate, postgate, t, ptr)
-        else:
-            with torch.cuda.device(self.device):
-                y = self._launch_step(x_t, pregate, postgate, t, ptr)
-        self._position = i = t + 1
-        if i % self.head == 0 and i < self.max_len:
-            for n, lo, _, _, _ in _long_stream_blocks(i, self.head, self.taps, self._first):
-                self._run_block(i, n, lo)
+        y = self._on_device(self._launch_step, x_t, pregate, postgate, t)
+        self._position = t + 1
+        self._run_due(t + 1)
         return y
 
     @torch.no_grad()
@@ -1590,11 +1602,7 @@ class FFTLongConvStream:
         self._draft = None
         x, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x, pregate, postgate))
         ops = _long_push_plan(p, count, self.head, self.taps, self._first, _long_push_bulk_enabled())
-        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
-            y = self._run_push(ops, x, pregate, postgate, p, count)
-        else:
-            with torch.cuda.device(self.device):
-                y = self._run_push(ops, x, pregate, postgate, p, count)
+        y = self._on_device(self._run_push, ops, x, pregate, postgate, p, count)
         self._position = p + count
         return y
 
@@ -1613,19 +1621,14 @@ class FFTLongConvStream:
             raise RuntimeError(f"a draft of T = {count} tokens at position p = {p} passes max_len = {self.max_len} "
                                f"(reset() starts a new row)")
         x, pregate, postgate = (None if v is None else v.detach().contiguous() for v in (x, pregate, postgate))
-        if torch.cuda.current_device() == _device_index(self.device):      # the common case: no device switch to pay for
-            y = self._launch_spec(x, pregate, postgate, p, count)
-        else:
-            with torch.cuda.device(self.device):
-                y = self._launch_spec(x, pregate, postgate, p, count)
+        y = self._on_device(self._launch_spec, x, pregate, postgate, p, count)
         self._draft = (p, count)
         return y
 
     def _launch_spec(self, x, pregate, postgate, p: int, count: int) -> Tensor:
-        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
         y = torch.empty((self.batch, self.out_channels, count), dtype=self.dtype, device=self.device)
-        _native.long_spec(self._desc, x.data_ptr(), ptr(pregate), ptr(postgate), self._head_taps.data_ptr(),
-                          self._flipped.data_ptr(), ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(),
+        _native.long_spec(self._desc, x.data_ptr(), _ptr(pregate), _ptr(postgate), self._head_taps.data_ptr(),
+                          self._flipped.data_ptr(), _ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(),
                           p, count, self._first, torch.cuda.current_stream(self.device).cuda_stream)
         return y
 
@@ -1645,21 +1648,21 @@ class FFTLongConvStream:
             raise ValueError(f"count must lie in [0, T = {T}], got {count}")
         self._draft = None
         self._position = p + count
-        M = (p // self.head + 1) * self.head      # (as ``_long_spec_plan``: the one multiple of head a draft can pass)
-        if M <= p + count and M < self.max_len:
-            with torch.cuda.device(self.device):
-                for n, lo, _, _, _ in _long_stream_blocks(M, self.head, self.taps, self._first):
-                    self._run_block(M, n, lo)
+        M = _long_spec_multiple(p, self.head)
+        if M <= p + count:
+            self._on_device(self._run_due, M)
 
     def _run_push(self, ops, x, pregate, postgate, p: int, count: int) -> Tensor:
         y = torch.empty((self.batch, self.out_channels, count), dtype=self.dtype, device=self.device)
+        above = 0      # the level of the bulk that the next window follows: the blocks due behind it are the levels above
         for op in ops:
-            if op[0] == "window":
-                self._push_window(x, pregate, postgate, y, p, op[1], op[2])
-            elif op[0] == "bulk":
+            if op[0] == "bulk":
                 self._run_bulk(x, pregate, p, op[1], op[2])
-            elif op[1] < self.max_len:       # (as a step: nothing is due at max_len)
-                self._run_block(op[1], op[2], op[3])
+                above = op[2]
+            elif op[0] == "window":
+                self._push_window(x, pregate, postgate, y, p, op[1], op[2])
+                self._run_due(op[1] + op[2], above)      # the plan's "block" ops behind this window, as a step runs them
+                above = 0
         return y
 
     def _push_window(self, x, pregate, postgate, y, p: int, t: int, m: int):
@@ -1667,10 +1670,9 @@ class FFTLongConvStream:
         tensors of row length m: a window that is not the whole chunk runs on contiguous copies of its columns."""
         whole = m == int(x.shape[2])
         cut = lambda v: v if v is None or whole else v[:, :, t - p:t - p + m].contiguous()      # noqa: E731
-        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
         xs, pre, post = cut(x), cut(pregate), cut(postgate)
         out = y if whole else torch.empty((self.batch, self.out_channels, m), dtype=self.dtype, device=self.device)
-        _native.long_push(self._desc, xs.data_ptr(), ptr(pre), ptr(post), self._head_taps.data_ptr(), ptr(self._bias),
+        _native.long_push(self._desc, xs.data_ptr(), _ptr(pre), _ptr(post), self._head_taps.data_ptr(), _ptr(self._bias),
                           self.hist.data_ptr(), self.acc.data_ptr(), out.data_ptr(), t, m, self._first,
                           torch.cuda.current_stream(self.device).cuda_stream)
         if not whole:
@@ -1698,10 +1700,10 @@ class FFTLongConvStream:
         """Bytes of the spectra that pushes have made so far (``_bulk_levels``; none until a push runs a bulk)."""
         return sum(level[3].buf.numel() * level[3].buf.element_size() for level in self._bulk_levels.values())
 
-    def _launch_step(self, x_t, pregate, postgate, t, ptr) -> Tensor:
+    def _launch_step(self, x_t, pregate, postgate, t) -> Tensor:
         y = torch.empty((self.batch, self.out_channels), dtype=self.dtype, device=self.device)
-        _native.long_step(self._desc, x_t.data_ptr(), ptr(pregate), ptr(postgate), self._head_taps.data_ptr(),
-                          ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(), t, self._first,
+        _native.long_step(self._desc, x_t.data_ptr(), _ptr(pregate), _ptr(postgate), self._head_taps.data_ptr(),
+                          _ptr(self._bias), self.hist.data_ptr(), self.acc.data_ptr(), y.data_ptr(), t, self._first,
                           torch.cuda.current_stream(self.device).cuda_stream)
         return y
 

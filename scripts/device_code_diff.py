@@ -2,7 +2,7 @@
 """Compare the device code of two source trees, kernel by kernel.  No GPU needed.
 
 For every object of the native library that holds kernels (the 7 tile objects, the 7 long-filter objects,
-fft_f64, nd_f64, direct_f64) the device side of both trees is compiled to assembly text with the flags of
+fft_f64, nd_f64, direct_f64, long_f64, long_step) the device side of both trees is compiled to assembly text with the flags of
 csrc/Makefile (`hipcc ... --cuda-device-only -S`).  The kernels of the two sides are put in one-to-one
 correspondence by demangled name -- conv1d_pers_kernel by (P, S, CIB, NB, NT) and the set of features its parameter
 list switches on, in either spelling: the seven positional parameters or the pers:: feature mask -- and each pair is
@@ -49,7 +49,7 @@ def objects():
     for t in LONG_TILES:
         p, s = t.split("_")
         objs.append(("long_" + t, "long_inst.hip", ["-DFC_P=" + p, "-DFC_S=" + s]))
-    for n in ("fft_f64", "nd_f64", "direct_f64"):
+    for n in ("fft_f64", "nd_f64", "direct_f64", "long_f64", "long_step"):
         objs.append((n, n + ".hip", []))
     return objs
 

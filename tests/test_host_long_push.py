@@ -141,6 +141,26 @@ def test_pinned_plans():
     assert plan(0, 300, 16, 40, 0)[:2] == [("bulk", 0, 64, 16, 40), ("window", 0, 64)]
 
 
+@pytest.mark.parametrize("bulk", [True, False], ids=["bulk", "windows-only"])
+@pytest.mark.parametrize("L,K,U,L0", SCHEDULES, ids=IDS)
+def test_a_push_runs_the_ops_of_its_plan_in_their_order(L, K, U, L0, bulk):
+    """``_run_push`` with its three workers replaced by recorders: what runs is the plan, op for op -- every "block" op
+    too, though the push takes those from the blocks due behind a window -- except the blocks at ``max_len``."""
+    ran = []
+    s = object.__new__(FFTLongConvStream)
+    s.batch, s.out_channels, s.dtype, s.device = 1, 1, torch.float32, torch.device("meta")
+    s.taps, s.head, s.max_len, s._first = K, U, L, L0
+    s._push_window = lambda x, pre, post, y, p, t, m: ran.append(("window", t, m))
+    s._run_bulk = lambda x, pre, p, i, n: ran.append(("bulk", i, n))
+    s._run_block = lambda i, n, lo: ran.append(("block", i, n, lo))
+    for seed in range(CUTS):
+        for p, T in cuts(L, U, L0, seed):
+            ops = F_._long_push_plan(p, T, U, K, L0, bulk)
+            del ran[:]
+            s._run_push(ops, None, None, None, p, T)
+            assert ran == [op[:4 if op[0] == "block" else 3] for op in ops if op[0] != "block" or op[1] < L], (seed, p, T)
+
+
 def test_the_switch_is_read_per_call(monkeypatch):
     monkeypatch.delenv("FFTCONV_LONG_PUSH_BULK", raising=False)
     assert F_._long_push_bulk_enabled()

@@ -152,6 +152,8 @@ def _signatures() -> dict:
         "fc_debug_grid": (ll, (vp,)),
         "fc_wgrad_nd_plan_create": (i32, (desc, out)),
         "fc_wgrad_nd": (i32, (vp, vp, vp, vp, vp, vp, vp)),
+        "fc_wgrad_direct_geometry": (i32, (desc, i32, i64x8)),
+        "fc_wgrad_direct": (i32, (desc, vp, vp, vp, vp, vp)),
         "fc_debug_route": (i32, (vp, ptr(ctypes.c_int32 * 16))),
         "fc_long_geometry": (i32, (ldesc, i64x8)),
         "fc_long_plan_create": (i32, (ldesc, out)),
@@ -324,6 +326,25 @@ class WgradPlan(_Handle):
 
     def run(self, x_ptr: int, dy_ptr: int, dw_ptr: int, spectrum_ptr: int, workspace_ptr: Optional[int], stream: int):
         self._check(self._lib.fc_wgrad_nd(self._h, x_ptr, dy_ptr, dw_ptr, spectrum_ptr, workspace_ptr, stream))
+
+
+WGRAD_DIRECT_INFO_WORDS = ("tile0", "tile1", "tile2", "out_block", "in_block", "slices", "lds_bytes", "workspace_bytes")
+
+
+def wgrad_direct_geometry(desc: FcDesc, compute_units: int) -> dict:
+    """``fc_wgrad_direct_geometry`` as a dict of WGRAD_DIRECT_INFO_WORDS (no device is touched; FFTCONV_WGRAD_DIRECT_SLICES is
+    read by the call).  A shape the direct weight gradient does not cover raises NotImplementedError with the reason."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    _check(lib, lib.fc_wgrad_direct_geometry(ctypes.byref(desc), compute_units, ctypes.byref(info)))
+    return dict(zip(WGRAD_DIRECT_INFO_WORDS, (int(v) for v in info)))
+
+
+def wgrad_direct(desc: FcDesc, x_ptr: int, dy_ptr: int, dw_ptr: int, workspace_ptr: int, stream: int):
+    """``fc_wgrad_direct`` on the current device: x and dY of the descriptor's dtype -> float32 dW, ``workspace_bytes`` of the
+    geometry for this device's CU count behind ``workspace_ptr``."""
+    lib = load_library()
+    _check(lib, lib.fc_wgrad_direct(ctypes.byref(desc), x_ptr, dy_ptr, dw_ptr, workspace_ptr, stream))
 
 
 def read_route(lib, handle) -> dict:

@@ -30,6 +30,7 @@ conjugation flag exists in the C ABI), db is dY summed.  ``fc_wgrad_nd`` takes n
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -240,19 +241,13 @@ def _grad_weight_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilati
     return total[:n_w].view(wshape), (total[n_w:] if with_db else None)
 
 
-def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
-    """2-D / 3-D dW by ``fc_wgrad_nd``: the role-swapped convolution run by the library on the tensors as they are
-    (x (B, Cin, *S) and dY (B, Cout, *Lout) are read, dW (Cout, Cin/g, *k) is written, in these layouts) -- no transposed
-    copies, no crop, no reduction on the torch side.  None when not covered (1-D, float64, a shape the plan refuses).
-    16-bit x and dY are read as they are; dW is float32."""
+def _wgrad_nd_plan(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
+    """The ``fc_wgrad_nd`` plan of a 2-D / 3-D layer on x's device (created once per shape), False where the library
+    refuses the shape, None for 1-D and for dtypes the launch does not take."""
     n = x.ndim - 2
     if n < 2 or x.dtype not in _WGRAD_IO:
         return None
     from . import _native
-    if grad.device != x.device:
-        raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
-    if grad.dtype != x.dtype:
-        raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
     key = ("dwn", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device, x.dtype)
     plan = _BWD_PLANS.get(key)
     if plan is None:
@@ -266,6 +261,21 @@ def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dil
         if len(_BWD_PLANS) > 256:
             _BWD_PLANS.clear()
         _BWD_PLANS[key] = plan
+    return plan
+
+
+def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
+    """2-D / 3-D dW by ``fc_wgrad_nd``: the role-swapped convolution run by the library on the tensors as they are
+    (x (B, Cin, *S) and dY (B, Cout, *Lout) are read, dW (Cout, Cin/g, *k) is written, in these layouts) -- no transposed
+    copies, no crop, no reduction on the torch side.  None when not covered (1-D, float64, a shape the plan refuses).
+    16-bit x and dY are read as they are; dW is float32."""
+    if x.ndim - 2 < 2 or x.dtype not in _WGRAD_IO:
+        return None
+    if grad.device != x.device:
+        raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
+    if grad.dtype != x.dtype:
+        raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
+    plan = _wgrad_nd_plan(x, wshape, stride, padding, dilation, groups, padding_mode)
     if plan is False:
         return None
     x = x.contiguous()
@@ -279,16 +289,95 @@ def _grad_weight_nd_native(x: Tensor, grad: Tensor, wshape, stride, padding, dil
     return dw
 
 
+def _wgrad_direct_on() -> bool:
+    """FFTCONV_WGRAD_DIRECT (read per call): "1" tries the direct small-kernel weight gradient first for 2-D / 3-D real
+    tensors; unset or anything else never does."""
+    return os.environ.get("FFTCONV_WGRAD_DIRECT", "0") == "1"
+
+
+def _wgrad_direct_geometry(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
+    """(descriptor, geometry words) of ``fc_wgrad_direct`` for the layer on x's device, None where the library refuses it
+    (1-D, float64, more than 128 taps, ...).  Arithmetic only: ``fc_wgrad_direct_geometry`` touches no device; the CU
+    count is the device's, 256 for a tensor that is not on a GPU."""
+    n = x.ndim - 2
+    if n < 2 or x.dtype not in _WGRAD_IO:
+        return None
+    from . import _native
+    knob = os.environ.get("FFTCONV_WGRAD_DIRECT_SLICES")
+    key = ("dwd", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device, x.dtype, knob)
+    hit = _BWD_PLANS.get(key)
+    if hit is None:
+        desc = _native.conv_desc(n, x.shape[0], x.shape[1], wshape[0], groups, tuple(x.shape[2:]), tuple(wshape[2:]), stride,
+                                 padding, dilation, F_._native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
+        cus = torch.cuda.get_device_properties(x.device).multi_processor_count if x.is_cuda else 256
+        try:
+            hit = (desc, _native.wgrad_direct_geometry(desc, cus))
+        except NotImplementedError:
+            hit = False
+        if len(_BWD_PLANS) > 256:
+            _BWD_PLANS.clear()
+        _BWD_PLANS[key] = hit
+    return hit or None
+
+
+def _grad_weight_direct(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
+    """2-D / 3-D dW by ``fc_wgrad_direct`` (FFTCONV_WGRAD_DIRECT=1): the time-domain sum on the matrix pipe, x and dY read
+    where they lie, x through the padding mode.  float32 dW; None where the library does not cover the layer."""
+    hit = _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode)
+    if hit is None:
+        return None
+    from . import _native
+    if grad.device != x.device:
+        raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
+    if grad.dtype != x.dtype:
+        raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
+    desc, geom = hit
+    x = x.contiguous()
+    grad = grad.contiguous()
+    with torch.cuda.device(x.device):
+        dw = torch.empty(tuple(wshape), device=x.device, dtype=torch.float32)
+        ws = torch.empty(geom["workspace_bytes"], device=x.device, dtype=torch.uint8)
+        _native.wgrad_direct(desc, x.data_ptr(), grad.data_ptr(), dw.data_ptr(), ws.data_ptr(),
+                             torch.cuda.current_stream(x.device).cuda_stream)
+    return dw
+
+
+def dw_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> str:
+    """The route ``_grad_weight_db`` takes for the dW of this layer, by the tests it makes (launches nothing; a first call
+    may create the ``fc_wgrad_nd`` plan that the gradient itself would create): ``"direct"`` (FFTCONV_WGRAD_DIRECT=1 and a
+    layer ``fc_wgrad_direct`` covers), ``"wgrad1d"``, ``"wgrad_nd"`` or ``"plans"`` (forward plans with batch and channels
+    exchanged).  The arguments are those of ``_grad_weight_db``: tuples per axis, x the saved signal."""
+    if x.is_complex():
+        return "plans"
+    if x.ndim == 3:
+        if x.dtype not in _WGRAD_IO:
+            return "plans"
+        from . import _native
+        desc = _native.conv_desc(1, x.shape[0], x.shape[1], wshape[0], groups, (x.shape[2],), (wshape[2],), stride, padding,
+                                 dilation, F_._native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
+        with torch.cuda.device(x.device):
+            return "wgrad1d" if _native.wgrad1d_slices(desc) else "plans"
+    if _wgrad_direct_on() and _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode):
+        return "direct"
+    if _wgrad_nd_plan(x, wshape, stride, padding, dilation, groups, padding_mode):
+        return "wgrad_nd"
+    return "plans"
+
+
 def _grad_weight_db(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode,
                     want_db: bool = False, conj: str = ""):
-    """(dW, db or None) in float32 by the first route that covers the shape: fc_wgrad1d (db riding it where offered),
-    fc_wgrad_nd, forward plans.  16-bit x and dY that no 16-bit launch takes (a library without 16-bit weight gradients)
+    """(dW, db or None) in float32 by the first route that covers the shape (``dw_route`` names it): fc_wgrad1d (db riding
+    it where offered), under FFTCONV_WGRAD_DIRECT=1 fc_wgrad_direct, fc_wgrad_nd, forward plans.  16-bit x and dY that no 16-bit launch takes (a library without 16-bit weight gradients)
     are widened for this gradient, and the float32 routes decide -- the bits of the cast path either way."""
     if x.is_complex():      # (no complex weight-gradient launch: the role-swapped forward plan)
         return _grad_weight_plans(x, grad, wshape, stride, padding, dilation, groups, padding_mode, conj), None
     native = _grad_weight_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode, want_db)
     if native is not None:
         return native
+    if _wgrad_direct_on():
+        direct = _grad_weight_direct(x, grad, wshape, stride, padding, dilation, groups, padding_mode)
+        if direct is not None:
+            return direct, None
     nd = _grad_weight_nd_native(x, grad, wshape, stride, padding, dilation, groups, padding_mode)
     if nd is not None:
         return nd, None

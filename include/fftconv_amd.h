@@ -182,6 +182,29 @@ int fc_wgrad_nd_plan_create(const fc_desc* conv_desc, fc_plan** out_plan);
 int fc_wgrad_nd(const fc_plan* plan, const float* x, const float* dy, float* dw, void* spectrum, void* workspace,
                 void* hip_stream);
 
+/* Direct weight gradient of a 2-D / 3-D convolution with a small kernel (ABI 7 extension: two new entry points; fc_desc
+ * keeps its size and every call above its signature and meaning).  The sum above, taken in the time domain: a GEMM of
+ * (Cout/groups) x (Cin/groups * taps) with the reduction over batch * prod(out) on the matrix pipe, x and dY read where
+ * they lie, x through the layer's padding mode (all four).  For kernels of a few taps this replaces the 2x longer
+ * transforms per axis of fc_wgrad_nd.  conv_desc is the descriptor OF THE CONVOLUTION.
+ *   Covered: ndim 2 or 3; FC_F32, FC_F16 or FC_BF16 x and dY (both of the descriptor's dtype; dW float32); at most 128
+ *   taps in all; any batch, channels, groups, stride, dilation, padding and padding mode.  FC_ERR_UNSUPPORTED with text:
+ *   ndim 1, FC_F64, FC_C64, a transposed descriptor, more taps, a halo (the x samples one output position reaches
+ *   through every tap, for one input channel) that does not fit 160 KiB of LDS, an axis whose padded extent reaches 2^31, a
+ *   tensor of 2^40 samples, 2^31 units or workgroups.  The caller then takes fc_wgrad_nd or the forward plans.
+ * fc_wgrad_direct_geometry is pure arithmetic: no device is touched.  compute_units sizes the split of the reduction
+ * (a launch runs where fc_wgrad_direct is called: pass that device's CU count).  info words: output tile per axis in
+ * tensor order (3 words, 0 past ndim), output channels per workgroup (<= 16), input channels per workgroup, slices,
+ * bytes of LDS per workgroup, bytes of workspace = slices * Cout * Cin/groups * taps * 4.  A slice is a contiguous range
+ * of (batch item, output tile) units; FFTCONV_WGRAD_DIRECT_SLICES=n (read at this call) forces the slice count, clipped
+ * to the unit count.
+ * fc_wgrad_direct plans for the CURRENT device under the knob as it is then, and launches twice on hip_stream: the
+ * workgroups write every element of their (slices, Cout, Cin/groups, taps) partial sums into `workspace` (nothing is
+ * cleared, nothing uninitialised is read), and a second launch adds the slices in a fixed order into dw (Cout, Cin/groups,
+ * *k), every element written.  No atomics: equal calls give equal bits.  Asynchronous; allocates nothing. */
+int fc_wgrad_direct_geometry(const fc_desc* conv_desc, int compute_units, int64_t info[8]);
+int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const void* dy, float* dw, void* workspace, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

@@ -154,6 +154,7 @@ def _signatures() -> dict:
         "fc_wgrad_nd": (i32, (vp, vp, vp, vp, vp, vp, vp)),
         "fc_wgrad_direct_geometry": (i32, (desc, i32, i64x8)),
         "fc_wgrad_direct": (i32, (desc, vp, vp, vp, vp, vp)),
+        "fc_wgrad_direct_body": (i32, (desc, i32, ptr(i32))),
         "fc_debug_route": (i32, (vp, ptr(ctypes.c_int32 * 16))),
         "fc_long_geometry": (i32, (ldesc, i64x8)),
         "fc_long_plan_create": (i32, (ldesc, out)),
@@ -338,6 +339,18 @@ def wgrad_direct_geometry(desc: FcDesc, compute_units: int) -> dict:
     info = (ctypes.c_int64 * 8)()
     _check(lib, lib.fc_wgrad_direct_geometry(ctypes.byref(desc), compute_units, ctypes.byref(info)))
     return dict(zip(WGRAD_DIRECT_INFO_WORDS, (int(v) for v in info)))
+
+
+WGRAD_DIRECT_BODIES = ("mfma", "valu")
+
+
+def wgrad_direct_body(desc: FcDesc, compute_units: int) -> str:
+    """``fc_wgrad_direct_body``: the kernel body ``fc_wgrad_direct`` takes for the layer, ``"mfma"`` or ``"valu"`` (the
+    depthwise body), under FFTCONV_WGRAD_DIRECT_BODY as it is at the call.  Refusals as ``wgrad_direct_geometry``."""
+    lib = load_library()
+    body = ctypes.c_int(-1)
+    _check(lib, lib.fc_wgrad_direct_body(ctypes.byref(desc), compute_units, ctypes.byref(body)))
+    return WGRAD_DIRECT_BODIES[body.value]
 
 
 def wgrad_direct(desc: FcDesc, x_ptr: int, dy_ptr: int, dw_ptr: int, workspace_ptr: int, stream: int):

@@ -296,14 +296,14 @@ def _wgrad_direct_on() -> bool:
 
 
 def _wgrad_direct_geometry(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
-    """(descriptor, geometry words) of ``fc_wgrad_direct`` for the layer on x's device, None where the library refuses it
-    (1-D, float64, more than 128 taps, ...).  Arithmetic only: ``fc_wgrad_direct_geometry`` touches no device; the CU
-    count is the device's, 256 for a tensor that is not on a GPU."""
+    """(descriptor, geometry words, kernel body) of ``fc_wgrad_direct`` for the layer on x's device, None where the
+    library refuses it (1-D, float64, more than 128 taps, ...).  Arithmetic only: ``fc_wgrad_direct_geometry`` and
+    ``fc_wgrad_direct_body`` touch no device; the CU count is the device's, 256 for a tensor that is not on a GPU."""
     n = x.ndim - 2
     if n < 2 or x.dtype not in _WGRAD_IO:
         return None
     from . import _native
-    knob = os.environ.get("FFTCONV_WGRAD_DIRECT_SLICES")
+    knob = (os.environ.get("FFTCONV_WGRAD_DIRECT_SLICES"), os.environ.get("FFTCONV_WGRAD_DIRECT_BODY"))
     key = ("dwd", tuple(x.shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, x.device, x.dtype, knob)
     hit = _BWD_PLANS.get(key)
     if hit is None:
@@ -311,7 +311,7 @@ def _wgrad_direct_geometry(x: Tensor, wshape, stride, padding, dilation, groups,
                                  padding, dilation, F_._native.PAD_MODES[padding_mode], _WGRAD_IO[x.dtype])
         cus = torch.cuda.get_device_properties(x.device).multi_processor_count if x.is_cuda else 256
         try:
-            hit = (desc, _native.wgrad_direct_geometry(desc, cus))
+            hit = (desc, _native.wgrad_direct_geometry(desc, cus), _native.wgrad_direct_body(desc, cus))
         except NotImplementedError:
             hit = False
         if len(_BWD_PLANS) > 256:
@@ -321,8 +321,8 @@ def _wgrad_direct_geometry(x: Tensor, wshape, stride, padding, dilation, groups,
 
 
 def _grad_weight_direct(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
-    """2-D / 3-D dW by ``fc_wgrad_direct`` (FFTCONV_WGRAD_DIRECT=1): the time-domain sum on the matrix pipe, x and dY read
-    where they lie, x through the padding mode.  float32 dW; None where the library does not cover the layer."""
+    """2-D / 3-D dW by ``fc_wgrad_direct`` (FFTCONV_WGRAD_DIRECT=1): the time-domain sum on the matrix pipe (a depthwise
+    layer: on the vector ALU, ``dw_direct_body``), x and dY read where they lie, x through the padding mode.  float32 dW; None where the library does not cover the layer."""
     hit = _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode)
     if hit is None:
         return None
@@ -331,7 +331,7 @@ def _grad_weight_direct(x: Tensor, grad: Tensor, wshape, stride, padding, dilati
         raise ValueError(f"gradient is on {grad.device} but the signal is on {x.device}")
     if grad.dtype != x.dtype:
         raise TypeError(f"gradient is {grad.dtype} but the signal is {x.dtype}")
-    desc, geom = hit
+    desc, geom, _ = hit
     x = x.contiguous()
     grad = grad.contiguous()
     with torch.cuda.device(x.device):
@@ -362,6 +362,15 @@ def dw_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode)
     if _wgrad_nd_plan(x, wshape, stride, padding, dilation, groups, padding_mode):
         return "wgrad_nd"
     return "plans"
+
+
+def dw_direct_body(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Optional[str]:
+    """The kernel body of ``fc_wgrad_direct`` for a layer whose ``dw_route`` is ``"direct"``: ``"mfma"``, or ``"valu"``,
+    the depthwise body (one input channel per group; FFTCONV_WGRAD_DIRECT_BODY=mfma / valu overrides the planner's
+    rule).  None for every other route.  Launches nothing."""
+    if dw_route(x, wshape, stride, padding, dilation, groups, padding_mode) != "direct":
+        return None
+    return _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode)[2]
 
 
 def _grad_weight_db(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode,

@@ -1,14 +1,16 @@
-// host_wgrad.cpp -- fc_wgrad_direct_geometry and fc_wgrad_direct (include/fftconv_amd.h "Direct weight gradient"): the
-// planner of wgrad_direct_kernel (wgrad_direct.hpp) and its two launches.  The planner is pure arithmetic on the
-// descriptor, the CU count and FFTCONV_WGRAD_DIRECT_SLICES; the launch call plans again for the current device (the last
-// answer is remembered per thread), allocates nothing and synchronises nothing.
+// host_wgrad.cpp -- fc_wgrad_direct_geometry, fc_wgrad_direct_body and fc_wgrad_direct (include/fftconv_amd.h "Direct
+// weight gradient"): the planner of wgrad_direct_kernel (wgrad_direct.hpp) and of wgrad_direct_dw_kernel
+// (wgrad_direct_dw.hpp), and their two launches.  The planner is pure arithmetic on the descriptor, the CU count,
+// FFTCONV_WGRAD_DIRECT_SLICES and FFTCONV_WGRAD_DIRECT_BODY; the launch call plans again for the current device (the
+// last answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include "fc_plan.h"
-#include "wgrad_direct.hpp"
+#include "wgrad_direct_dw.hpp"
 
 using namespace fc;
 
@@ -18,6 +20,13 @@ constexpr int64_t kLdsShared = 64 * 1024;       // up to here two workgroups sha
 constexpr int64_t kLdsBudget = 160 * 1024;
 constexpr int kMaxTaps = 128;
 constexpr int kMaxCols = kWgdWaves * kWgdMaxCT * 16;      // columns (input channel, tap) of one workgroup
+enum Body { BODY_MFMA = 0, BODY_VALU = 1 };
+// The largest channel multiplier Cout/g of a layer with Cin/g == 1 that the automatic rule gives to the depthwise
+// body: the largest of 1, 2, 4, 8, 16 at which it was faster than the MFMA body by more than three spreads on
+// B8 C256 56^2 k7 bfloat16 (profiles/wgrad_direct_dw.jsonl).
+constexpr int kDwMaxMultiplier = 8;
+constexpr int kDwGroupsPerCu = 4;               // workgroups the slices aim at per CU, while LDS allows
+constexpr int64_t kDwLdsShared = kLdsBudget / kDwGroupsPerCu;
 
 struct Geom {
   int ax0;                   // first axis of the descriptor in the kernel's (z, y, x): 1 for a 2-D layer
@@ -26,6 +35,9 @@ struct Geom {
   int Cig, Cog, taps, cib, nib, nob, ct;
   int P, P4, slices;
   int64_t units, lds, ws;
+  int body;                  // Body; the depthwise body besides:
+  int kxb, nb, nbx, nblk;    // taps per block, blocks of the busiest wave, blocks per kernel row and in all
+  int runs, runs64;          // runs of kDwR positions per tile, rounded up to whole waves
 };
 
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -33,6 +45,78 @@ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int lds_bytes(int p4, int cib, int64_t hv, int64_t* out) {
   *out = 4 * ((int64_t)p4 * (1 + kWgdDyPitch) + cib * hv);
   return *out <= kLdsBudget;
+}
+
+// FFTCONV_WGRAD_DIRECT_BODY: 1 "mfma", 2 "valu", 0 unset or anything else (the automatic rule)
+int body_knob() {
+  const char* env = getenv("FFTCONV_WGRAD_DIRECT_BODY");
+  return !env ? 0 : !std::strcmp(env, "mfma") ? 1 : !std::strcmp(env, "valu") ? 2 : 0;
+}
+
+int64_t forced_slices() {
+  const char* env = getenv("FFTCONV_WGRAD_DIRECT_SLICES");
+  return env ? std::max<long long>(atoll(env), 0) : 0;
+}
+
+// Tile and slices of the depthwise body for a validated layer with Cin/g == 1.  Tiles are powers of two clipped to
+// the output, the last axis in whole runs; the one with the smallest cycle estimate of the launch wins among those whose
+// LDS (one dY tile with its run words, one halo) lets kDwGroupsPerCu workgroups share a CU, else among those that fit.
+// Per unit the estimate counts the FMAs of the busiest wave (4 cycles each), its LDS reads, half a cycle per staged
+// sample and a fixed cost for the exposed latency of the loads.
+int plan_dw(const fc_desc& c, int cus, Geom& g) {
+  const bool unit = g.stride[2] == 1 && g.dil[2] == 1;      // else the general build, a tap per block
+  g.kxb = !unit || g.k[2] == 1 ? 1 : g.k[2] == 2 ? 2 : g.k[2] <= 4 ? 4 : 8;
+  g.nbx = (int)cdiv(g.k[2], g.kxb); g.nblk = g.k[0] * g.k[1] * g.nbx; g.nb = (int)cdiv(g.nblk, kWgdWaves);
+  if (!wgrad_direct_dw_blocks(g.kxb, g.nb)) return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: no depthwise build of %d x %d", g.kxb, g.nb);
+  g.cib = 1; g.nib = 1; g.nob = g.Cog; g.ct = 0; g.P4 = 0;
+  double best = -1.0;
+  bool best_shared = false;
+  for (int tz = 1; tz <= 8; tz *= 2)
+    for (int ty = 1; ty <= 16; ty *= 2)
+      for (int tx = kDwR; tx <= 64; tx *= 2) {
+        const int t[3] = {std::min(tz, g.O[0]), std::min(ty, g.O[1]), std::min(tx, g.O[2])};
+        if ((tz > 1 && tz / 2 >= g.O[0]) || (ty > 1 && ty / 2 >= g.O[1]) || (tx > kDwR && tx / 2 >= g.O[2]))
+          continue;      // (the same clipped tile as a smaller candidate)
+        const int txr = (t[2] + kDwR - 1) / kDwR * kDwR, runs = t[0] * t[1] * (txr / kDwR);
+        if (runs * kDwR > kWgdMaxPos) continue;
+        const int runs64 = (runs + 63) & ~63;
+        int64_t halo[3], ntiles = 1;
+        for (int a = 0; a < 3; ++a) {
+          halo[a] = (int64_t)(t[a] - 1) * g.stride[a] + (int64_t)(g.k[a] - 1) * g.dil[a] + 1;
+          ntiles *= cdiv(g.O[a], t[a]);
+        }
+        // the row pitch: the window of the last run through the last tap block, dead tail included, in whole reads
+        halo[2] = unit ? (txr - kDwR) + (g.nbx - 1) * g.kxb + (g.kxb == 1 ? kDwR : 4 * dw_window4(g.kxb))
+                       : (int64_t)(txr - 1) * g.stride[2] + (int64_t)(g.k[2] - 1) * g.dil[2] + 1;
+        halo[2] = (halo[2] + 3) & ~(int64_t)3;
+        if (halo[0] > kLdsBudget || halo[1] > kLdsBudget || halo[2] > kLdsBudget || halo[0] * halo[1] > kLdsBudget) continue;
+        const int64_t hv = halo[0] * halo[1] * halo[2], lds = 4 * ((int64_t)runs64 * (1 + kDwR) + hv);
+        if (lds > kLdsBudget) continue;
+        const bool shared = lds <= kDwLdsShared;
+        if (best_shared && !shared) continue;
+        const double per_run = g.nb * (4.0 * g.kxb * kDwR + (g.kxb == 1 ? 8.0 * kDwR : 8.0 * dw_window4(g.kxb))) + 24.0;
+        const double cost = (double)ntiles * (runs64 / 64 * per_run + 3000.0 + 0.5 * ((double)hv + kDwR * runs64));
+        if (best < 0 || (shared && !best_shared) || cost < best) {
+          best = cost; best_shared = shared;
+          g.runs = runs; g.runs64 = runs64; g.P = runs * kDwR; g.lds = lds;
+          for (int a = 0; a < 3; ++a) { g.tile[a] = t[a]; g.ntile[a] = (int)cdiv(g.O[a], t[a]); g.halo[a] = (int)halo[a]; }
+        }
+      }
+  if (best < 0)
+    return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: the x samples that one run of output positions reaches through every tap "
+                "do not fit %lld bytes of LDS", (long long)kLdsBudget);
+  g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
+  if (g.units >= ((int64_t)1 << 31))
+    return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+  // channels x slices fill the device kDwGroupsPerCu workgroups deep
+  int64_t slices = std::max<int64_t>(1, ((int64_t)kDwGroupsPerCu * cus + c.out_channels / 2) / c.out_channels);
+  if (const int64_t forced = forced_slices()) slices = forced;
+  slices = std::min<int64_t>(slices, g.units);
+  if (c.out_channels * slices > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: %lld workgroups exceed the 2^31 of one launch", (long long)(c.out_channels * slices));
+  g.slices = (int)slices;
+  g.ws = slices * c.out_channels * g.taps * 4;
+  return FC_OK;
 }
 
 // Validates the descriptor and chooses input-channel block, tile and slices.  The tile and the channel block minimise a
@@ -85,6 +169,9 @@ int plan(const fc_desc& c, int cus, Geom& g) {
   g.Cig = (int)(c.in_channels / c.groups); g.Cog = (int)(c.out_channels / c.groups);
   if (c.in_channels >= (1 << 30) || c.out_channels >= (1 << 30)) return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: fewer than 2^30 channels");
   g.nob = (int)cdiv(g.Cog, kWgdRows);
+  const int knob = body_knob();
+  g.body = g.Cig == 1 && knob != 1 && (knob == 2 || g.Cog <= kDwMaxMultiplier) ? BODY_VALU : BODY_MFMA;
+  if (g.body == BODY_VALU) return plan_dw(c, cus, g);
 
   // candidates: the largest channel blocks of the first 8 even splits of the group, tiles of powers of two clipped to the output
   double best = -1.0;
@@ -136,10 +223,7 @@ int plan(const fc_desc& c, int cus, Geom& g) {
   if (g.units >= ((int64_t)1 << 31))
     return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
   int64_t slices = std::max<int64_t>(1, ((g.lds <= kLdsShared ? 2 : 1) * (int64_t)cus + blocks / 2) / blocks);
-  if (const char* env = getenv("FFTCONV_WGRAD_DIRECT_SLICES")) {
-    const long long forced = atoll(env);
-    if (forced >= 1) slices = forced;
-  }
+  if (const int64_t forced = forced_slices()) slices = forced;
   slices = std::min<int64_t>(slices, g.units);
   if (blocks * slices > 0x7fffffffLL)
     return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: %lld workgroups exceed the 2^31 of one launch", (long long)(blocks * slices));
@@ -155,7 +239,15 @@ extern "C" int fc_wgrad_direct_geometry(const fc_desc* conv_desc, int compute_un
   Geom g;
   if (int st = plan(*conv_desc, compute_units, g)) return st;
   for (int i = 0; i < 3; ++i) info[i] = i < conv_desc->ndim ? g.tile[g.ax0 + i] : 0;
-  info[3] = std::min(g.Cog, kWgdRows); info[4] = g.cib; info[5] = g.slices; info[6] = g.lds; info[7] = g.ws;
+  info[3] = g.body == BODY_VALU ? 1 : std::min(g.Cog, kWgdRows); info[4] = g.cib; info[5] = g.slices; info[6] = g.lds; info[7] = g.ws;
+  return FC_OK;
+}
+
+extern "C" int fc_wgrad_direct_body(const fc_desc* conv_desc, int compute_units, int* body) {
+  if (!conv_desc || !body) return fail(FC_ERR_INVALID, "null argument");
+  Geom g;
+  if (int st = plan(*conv_desc, compute_units, g)) return st;
+  *body = g.body;
   return FC_OK;
 }
 
@@ -166,14 +258,14 @@ extern "C" int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const vo
   int cus = 0;
   if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
   // the plan of the last call of this thread, while descriptor, CU count and the knob are what they were
-  struct Last { fc_desc d; int cus; long long knob; Geom g; bool set; };
+  struct Last { fc_desc d; int cus; long long knob; int body; Geom g; bool set; };
   static thread_local Last last = {};
-  const char* env = getenv("FFTCONV_WGRAD_DIRECT_SLICES");
-  const long long knob = env ? atoll(env) : 0;
-  if (!last.set || std::memcmp(&last.d, conv_desc, sizeof(fc_desc)) || last.cus != cus || last.knob != knob) {
+  const long long knob = forced_slices();
+  const int body = body_knob();
+  if (!last.set || std::memcmp(&last.d, conv_desc, sizeof(fc_desc)) || last.cus != cus || last.knob != knob || last.body != body) {
     last.set = false;
     if (int st = plan(*conv_desc, cus, last.g)) return st;
-    last.d = *conv_desc; last.cus = cus; last.knob = knob; last.set = true;
+    last.d = *conv_desc; last.cus = cus; last.knob = knob; last.body = body; last.set = true;
   }
   const Geom& g = last.g;
   const fc_desc& c = *conv_desc;
@@ -192,7 +284,13 @@ extern "C" int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const vo
   a.slices = g.slices; a.units = (int)g.units; a.P = g.P; a.P4 = g.P4;
   a.io = c.dtype;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  FC_HIP(wgrad_direct_launch(a, g.ct, c.groups * g.nob * g.nib * g.slices, (size_t)g.lds, st));
+  if (g.body == BODY_VALU) {
+    a.fd_rx = make_fastdiv(g.runs / (g.tile[0] * g.tile[1]));
+    a.runs = g.runs; a.runs64 = g.runs64; a.nbx = g.nbx; a.nblk = g.nblk;
+    FC_HIP(wgrad_direct_dw_launch(a, g.kxb, g.nb, c.out_channels * g.slices, (size_t)g.lds, st));
+  } else {
+    FC_HIP(wgrad_direct_launch(a, g.ct, c.groups * g.nob * g.nib * g.slices, (size_t)g.lds, st));
+  }
   FC_HIP(wgrad_direct_sum_launch(a.partial, dw, (long long)c.out_channels * g.Cig * g.taps, g.slices, st));
   return FC_OK;
 }

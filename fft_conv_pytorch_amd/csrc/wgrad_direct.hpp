@@ -55,9 +55,40 @@ struct WgradDirectArgs {
   int slices, units;    // units = B * ntile[0] * ntile[1] * ntile[2]
   int P, P4;            // positions of a tile, rounded up to the 4 of an MFMA step
   int io;               // fc_dtype code of x and dY
+  // the depthwise body (wgrad_direct_dw.hpp); there halo[2] is the padded pitch of a halo row
+  FastDiv fd_rx;        // runs of 4 output columns per tile row
+  int runs, runs64;     // runs of a tile, rounded up to whole waves
+  int nbx, nblk;        // tap blocks per kernel row, tap blocks in all
 };
 
 typedef float wgd_v4f __attribute__((ext_vector_type(4)));
+
+// unit u -> its batch item and the first output position of its tile
+__device__ __forceinline__ void wgd_unit_origin(const WgradDirectArgs& a, int u, int& b, int& o0z, int& o0y, int& o0x) {
+  const int tiles = a.ntile[0] * a.ntile[1] * a.ntile[2];
+  b = u / tiles;
+  int t = u - b * tiles;
+  const int tix = t % a.ntile[2]; t /= a.ntile[2];
+  o0x = tix * a.tile[2]; o0y = (t % a.ntile[1]) * a.tile[1]; o0z = (t / a.ntile[1]) * a.tile[0];
+}
+
+// The x halo of nci input channels (xsrc: the first, Svol samples apart) of the tile at (o0z, o0y, o0x) into
+// xl[ci][HV], through the padding mode: a zero where axis_src says -1.  Each global sample is read once.
+template <class IoT, class T>
+__device__ __forceinline__ void wgd_stage_halo(const WgradDirectArgs& a, const IoT& io, const T* xsrc, float* xl, int nci,
+                                               int HV, size_t Svol, int o0z, int o0y, int o0x, int tid) {
+  for (int e = tid; e < HV; e += kWgdThreads) {
+    unsigned q, hz;
+    const int hx = (int)fdivmod((unsigned)e, a.fd_hx, &q);
+    const int hy = (int)fdivmod(q, a.fd_hy, &hz);
+    const int sz = axis_src(a.map[0], o0z * a.stride[0] + (int)hz);
+    const int sy = axis_src(a.map[1], o0y * a.stride[1] + hy);
+    const int sx = axis_src(a.map[2], o0x * a.stride[2] + hx);
+    const bool live = (sz | sy | sx) >= 0;
+    const size_t off = ((size_t)max(sz, 0) * a.S[1] + max(sy, 0)) * a.S[2] + max(sx, 0);
+    for (int ci = 0; ci < nci; ++ci) xl[ci * HV + e] = live ? io.in(xsrc[ci * Svol + off]) : 0.f;
+  }
+}
 
 template <int IO, int CT>
 __global__ __launch_bounds__(kWgdThreads) void wgrad_direct_kernel(const WgradDirectArgs a) {
@@ -101,12 +132,9 @@ __global__ __launch_bounds__(kWgdThreads) void wgrad_direct_kernel(const WgradDi
   for (int c = 0; c < CT; ++c) acc2[c] = wgd_v4f{0.f, 0.f, 0.f, 0.f};
 
   const int u0 = (int)((long long)slice * a.units / a.slices), u1 = (int)((long long)(slice + 1) * a.units / a.slices);
-  const int tiles = a.ntile[0] * a.ntile[1] * a.ntile[2];
   for (int u = u0; u < u1; ++u) {
-    const int b = u / tiles;
-    int t = u - b * tiles;
-    const int tix = t % a.ntile[2]; t /= a.ntile[2];
-    const int o0x = tix * a.tile[2], o0y = (t % a.ntile[1]) * a.tile[1], o0z = (t / a.ntile[1]) * a.tile[0];
+    int b, o0z, o0y, o0x;
+    wgd_unit_origin(a, u, b, o0z, o0y, o0x);
     __syncthreads();      // the MFMA loop of the unit before has read its last sample
 
     // dY tile and the halo offsets of its positions
@@ -122,18 +150,7 @@ __global__ __launch_bounds__(kWgdThreads) void wgrad_direct_kernel(const WgradDi
       for (int i = 0; i < kWgdRows; ++i) dyl[p * kWgdDyPitch + i] = (live && i < nco) ? io.in(dsrc[i * Ovol + off]) : 0.f;
     }
     // x halo of the block's input channels, through the padding mode
-    const T* xsrc = xg + ((size_t)b * a.Cin + g * a.Cig + ci0) * Svol;
-    for (int e = tid; e < HV; e += kWgdThreads) {
-      unsigned q, hz;
-      const int hx = (int)fdivmod((unsigned)e, a.fd_hx, &q);
-      const int hy = (int)fdivmod(q, a.fd_hy, &hz);
-      const int sz = axis_src(a.map[0], o0z * a.stride[0] + (int)hz);
-      const int sy = axis_src(a.map[1], o0y * a.stride[1] + hy);
-      const int sx = axis_src(a.map[2], o0x * a.stride[2] + hx);
-      const bool live = (sz | sy | sx) >= 0;
-      const size_t off = ((size_t)max(sz, 0) * a.S[1] + max(sy, 0)) * a.S[2] + max(sx, 0);
-      for (int ci = 0; ci < nci; ++ci) xl[ci * HV + e] = live ? io.in(xsrc[ci * Svol + off]) : 0.f;
-    }
+    wgd_stage_halo(a, io, xg + ((size_t)b * a.Cin + g * a.Cig + ci0) * Svol, xl, nci, HV, Svol, o0z, o0y, o0x, tid);
     __syncthreads();
 
     wgd_v4f acc1[CT];

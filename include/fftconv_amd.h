@@ -201,8 +201,16 @@ int fc_wgrad_nd(const fc_plan* plan, const float* x, const float* dy, float* dw,
  * fc_wgrad_direct plans for the CURRENT device under the knob as it is then, and launches twice on hip_stream: the
  * workgroups write every element of their (slices, Cout, Cin/groups, taps) partial sums into `workspace` (nothing is
  * cleared, nothing uninitialised is read), and a second launch adds the slices in a fixed order into dw (Cout, Cin/groups,
- * *k), every element written.  No atomics: equal calls give equal bits.  Asynchronous; allocates nothing. */
+ * *k), every element written.  No atomics: equal calls give equal bits.  Asynchronous; allocates nothing.
+ * Two kernel bodies write the partial sums; fc_wgrad_direct_body names the one the planner takes for the layer: 0, the
+ * MFMA body above, or 1, the depthwise body, which runs a layer with Cin/groups == 1 on the vector ALU, one output
+ * channel and one slice per workgroup (info words 3 and 4 are then 1).  Unset, the planner takes the depthwise body
+ * for Cin/groups == 1 and a channel multiplier Cout/groups of at most 8.  FFTCONV_WGRAD_DIRECT_BODY (read where the
+ * slices knob is) overrides that: "mfma" takes the MFMA body everywhere, "valu" the depthwise body wherever
+ * Cin/groups == 1; a layer with more input channels per group runs the MFMA body under either.  Both bodies sum in
+ * float32 but in different orders, so the last bits of dW may differ between them.  Pure arithmetic, no device. */
 int fc_wgrad_direct_geometry(const fc_desc* conv_desc, int compute_units, int64_t info[8]);
+int fc_wgrad_direct_body(const fc_desc* conv_desc, int compute_units, int* body);
 int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const void* dy, float* dw, void* workspace, void* hip_stream);
 
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan

@@ -18,8 +18,16 @@ a shape are replayed in turn between HIP events, ``--iters`` replays in each of 
 are the median over all replays (60 by default), per call, the medians of the single rounds and their spread (largest
 minus smallest round median).  One JSON line per shape is appended to --out.
 
+``--depthwise`` times the depthwise rows of DESIGN.md 4.5c instead (layers with one input channel per group, and the
+sweep of the channel multiplier that the planner's rule was set by): the weight gradient alone, with two more columns
+
+  a_mfma       FFTCONV_WGRAD_DIRECT=1 FFTCONV_WGRAD_DIRECT_BODY=mfma: the MFMA body, which must reproduce c_parent,
+  a_valu       FFTCONV_WGRAD_DIRECT=1 FFTCONV_WGRAD_DIRECT_BODY=valu: the depthwise body at any channel multiplier,
+
+and per row the kernel body that a_direct ran (``a_body``).
+
     python scripts/wgrad_direct_bench.py [--iters 20] [--rounds 3] [--out profiles/wgrad_direct.jsonl] [--only SUBSTRING]
-                                         [--baseline [--root PARENT_CHECKOUT]]"""
+                                         [--depthwise] [--baseline [--root PARENT_CHECKOUT]]"""
 import argparse
 import importlib
 import json
@@ -41,9 +49,19 @@ SHAPES = [
     ("2-D depthwise B8 C256 56^2 k7 bf16", 8, 256, 256, 256, (56, 56), 7, 1, BF16),
     ("2-D B16 8->16 256^2 k3 stride 2", 16, 8, 16, 1, (256, 256), 3, 2, F32),
 ]
+# --depthwise: Cin/groups == 1; the last four rows are the first with a channel multiplier Cout/groups of 2, 4, 8, 16
+DW_SHAPES = [
+    ("2-D depthwise B8 C256 56^2 k7 bf16", 8, 256, 256, 256, (56, 56), 7, 1, BF16),
+    ("2-D depthwise B8 C256 56^2 k7 f32", 8, 256, 256, 256, (56, 56), 7, 1, F32),
+    ("2-D depthwise B8 C512 28^2 k3 bf16", 8, 512, 512, 512, (28, 28), 3, 1, BF16),
+    ("2-D depthwise B8 C96 112^2 k7 bf16", 8, 96, 96, 96, (112, 112), 7, 1, BF16),
+    ("2-D depthwise B8 C256 56^2 k5 stride 2 bf16", 8, 256, 256, 256, (56, 56), 5, 2, BF16),
+    ("3-D depthwise B4 C64 32^3 k3 bf16", 4, 64, 64, 64, (32, 32, 32), 3, 1, BF16),
+] + [(f"2-D B8 C256 x{m} 56^2 k7 bf16", 8, 256, 256 * m, 256, (56, 56), 7, 1, BF16) for m in (2, 4, 8, 16)]
 ROTATE_BYTES = 600 << 20
 HBM_BYTES_PER_US = 8e6      # 8 TB/s
 KNOB = "FFTCONV_WGRAD_DIRECT"
+BODY_KNOB = "FFTCONV_WGRAD_DIRECT_BODY"
 
 
 def capture(step):
@@ -71,7 +89,7 @@ def timed(g):
     return e0.elapsed_time(e1) * 1e3
 
 
-def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline):
+def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline, depthwise=False):
     torch.manual_seed(0)
     nd = len(size)
     auto = importlib.import_module(fca.__name__ + ".autograd")
@@ -91,10 +109,11 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
 
     def knob(value, fn):
         def step():
-            if value is None:
-                os.environ.pop(KNOB, None)
-            else:
-                os.environ[KNOB] = value
+            for name, v in ((KNOB, value and value[0]), (BODY_KNOB, value and value[1:] or None)):
+                if v is None:
+                    os.environ.pop(name, None)
+                else:
+                    os.environ[name] = v
             return fn()
         return step
 
@@ -107,10 +126,14 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
         with torch.no_grad():
             return auto._grad_weight(x, gy, wshape, *conf)
 
+    # (a variant's value: the switch, then the body knob)
     variants = {"c_parent": None} if baseline else {"a_direct": "1", "b_unset": None}
+    if depthwise:
+        variants = {"c_parent": "1"} if baseline else {**variants, "a_mfma": "1mfma", "a_valu": "1valu"}
     steps = {}
     for key, value in variants.items():
-        steps[key + "_step"] = knob(value, train_step)
+        if not depthwise:
+            steps[key + "_step"] = knob(value, train_step)
         steps[key + "_dw"] = knob(value, lambda: [dw_of(x, gy) for x, gy in zip(xs, gys)])
         one = knob(value, lambda: dw_of(xs[0], gys[0]))
         one()
@@ -122,6 +145,8 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
         row[key + "_dw_peak_bytes"] = torch.cuda.max_memory_allocated() - before
         if hasattr(auto, "dw_route"):
             row[key + "_route"] = knob(value, lambda: auto.dw_route(xs[0], wshape, *conf))()
+    if depthwise and hasattr(auto, "dw_direct_body"):
+        row["a_body"] = knob("1", lambda: auto.dw_direct_body(xs[0], wshape, *conf))()
     if not baseline:
         da, db = steps["a_direct_dw"]()[0].float(), steps["b_unset_dw"]()[0].float()
         row["a_vs_b_dW_max_rel"] = float((da - db).abs().max() / db.abs().max())
@@ -155,6 +180,7 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
     if row.get("a_direct_route") == "direct" and row.get("a_direct_dw_us"):
         row["a_roofline_fraction"] = round(row["roofline_us"] / row["a_direct_dw_us"], 3)
     os.environ.pop(KNOB, None)
+    os.environ.pop(BODY_KNOB, None)
     return row
 
 
@@ -162,20 +188,22 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join("profiles", "wgrad_direct.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/wgrad_direct.jsonl, with --depthwise profiles/wgrad_direct_dw.jsonl")
+    ap.add_argument("--depthwise", action="store_true", help="the depthwise rows and the multiplier sweep, dW alone")
     ap.add_argument("--only", default=None)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose fft_conv_pytorch_amd package is timed (default: this tree)")
     ap.add_argument("--tag", default=None, help="free text recorded with every row")
     a = ap.parse_args()
+    a.out = a.out or os.path.join("profiles", "wgrad_direct_dw.jsonl" if a.depthwise else "wgrad_direct.jsonl")
     sys.path.insert(0, os.path.abspath(a.root))
     import fft_conv_pytorch_amd as fca
     assert os.path.abspath(fca.__file__).startswith(os.path.abspath(a.root)), fca.__file__
-    for name, B, ci, co, g, size, k, s, dtype in SHAPES:
+    for name, B, ci, co, g, size, k, s, dtype in (DW_SHAPES if a.depthwise else SHAPES):
         if a.only and a.only not in name:
             continue
-        res = run_shape(fca, name, B, ci, co, g, size, k, s, dtype, a.iters, a.rounds, a.baseline)
+        res = run_shape(fca, name, B, ci, co, g, size, k, s, dtype, a.iters, a.rounds, a.baseline, a.depthwise)
         if a.tag:
             res["tag"] = a.tag
         line = json.dumps(res)

@@ -89,6 +89,9 @@ def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilat
     (``F_._forward_native``); ``channels_last``: dX lies that way (the layout of the signal) -- written so by the
     transposed plan's last pass where the padding is zeros, one torch copy behind ``_pad_adjoint`` otherwise."""
     lay = (channels_last, native)
+    direct = _grad_input_direct(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode, *lay)
+    if direct is not None:
+        return direct
     if grad.dtype in F_._LOW_PRECISION:
         if padding_mode == "constant":
             try:
@@ -99,6 +102,33 @@ def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilat
         return _grad_input_plan(grad.float(), weight.float(), in_spatial, stride, padding, dilation, groups,
                                 padding_mode, *lay).to(grad.dtype)
     return _grad_input_plan(grad, weight, in_spatial, stride, padding, dilation, groups, padding_mode, *lay)
+
+
+def _grad_input_direct(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode,
+                       channels_last: bool = False, native: bool = False) -> Optional[Tensor]:
+    """dX of a stride-1 layer with zero padding by ``fc_conv_direct`` (FFTCONV_DIRECT=1): the stride-1 transposed
+    convolution of dY, the weight (Cout, Cin/g, *k) read where it lies with the channel roles exchanged and the taps
+    flipped.  None where the call keeps the transposed FFT plan (``dx_route`` "plan")."""
+    if padding_mode != "constant" or any(s != 1 for s in stride):
+        return None
+    hit = F_._direct_hit(True, grad, weight, None, stride, padding, 0, dilation, groups, "constant", channels_last, native)
+    if hit is None or hit[2][2:] != tuple(in_spatial):
+        return None
+    return F_._direct_run(hit, grad, weight, None)
+
+
+def dx_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> str:
+    """The route ``_grad_input`` takes for the dX of this layer on a contiguous dY of x's dtype (launches nothing, creates
+    no plan): ``"direct"`` (FFTCONV_DIRECT=1, stride 1, zero padding and a layer ``fc_conv_direct`` covers in its
+    transposed form) or ``"plan"`` (the transposed FFT plan).  The arguments are those of ``dw_route``."""
+    if not F_._direct_on() or padding_mode != "constant" or any(s != 1 for s in stride) or x.ndim not in (4, 5):
+        return "plan"
+    if x.dtype in F_._LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
+        return "plan"
+    out = tuple(int(S) + 2 * p - d * (int(k) - 1) for S, p, d, k in zip(x.shape[2:], padding, dilation, wshape[2:]))
+    hit = F_._direct_geometry((int(x.shape[0]), int(wshape[0])) + out, x.dtype, x.device, tuple(wshape), tuple(stride),
+                              tuple(padding), tuple(dilation), groups, "constant", True)
+    return "direct" if hit else "plan"
 
 
 def _grad_input_plan(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode,
@@ -429,12 +459,15 @@ class FFTConvFunction(torch.autograd.Function):
     def forward(ctx, signal: Tensor, kernel: Tensor, bias: Optional[Tensor], stride: Tuple[int, ...],
                 padding: Tuple[int, ...], dilation: Tuple[int, ...], groups: int, padding_mode: str, spectrum,
                 channels_last: bool = False):
-        plan = F_._plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
-        if spectrum is None or spectrum.plan is not plan:
-            spectrum = F_.transform_kernel(plan, kernel)
         ctx.save_for_backward(signal, kernel)
         ctx.conf = (stride, padding, dilation, groups, padding_mode, bias is not None)
         ctx.channels_last = bool(channels_last)
+        direct = F_._direct_hit(False, signal, kernel, bias, stride, padding, 0, dilation, groups, padding_mode, channels_last)
+        if direct is not None:      # FFTCONV_DIRECT=1 and a covered layer: no plan, no spectrum
+            return F_._direct_run(direct, signal, kernel, bias)
+        plan = F_._plan_for(signal, kernel, bias, stride, padding, dilation, groups, padding_mode)
+        if spectrum is None or spectrum.plan is not plan:
+            spectrum = F_.transform_kernel(plan, kernel)
         return F_._forward_lay(signal, spectrum, bias, channels_last)
 
     @staticmethod
@@ -478,13 +511,17 @@ class FFTConvTransposeFunction(torch.autograd.Function):
     def forward(ctx, signal: Tensor, kernel: Tensor, bias: Optional[Tensor], stride: Tuple[int, ...],
                 padding: Tuple[int, ...], output_padding: Tuple[int, ...], dilation: Tuple[int, ...], groups: int,
                 spectrum, channels_last: bool = False):
+        ctx.save_for_backward(signal, kernel)
+        ctx.conf = (stride, padding, dilation, groups, bias is not None)
+        ctx.channels_last = bool(channels_last)
+        direct = F_._direct_hit(True, signal, kernel, bias, stride, padding, output_padding, dilation, groups, "constant",
+                                channels_last)
+        if direct is not None:      # FFTCONV_DIRECT=1 and a stride-1 layer the library covers: no plan, no spectrum
+            return F_._direct_run(direct, signal, kernel, bias)
         plan = F_._plan_for(signal, kernel, bias, stride, padding, dilation, groups, "constant",
                             transposed=True, output_padding=output_padding)
         if spectrum is None or spectrum.plan is not plan:
             spectrum = F_.transform_kernel(plan, kernel)
-        ctx.save_for_backward(signal, kernel)
-        ctx.conf = (stride, padding, dilation, groups, bias is not None)
-        ctx.channels_last = bool(channels_last)
         return F_._forward_lay(signal, spectrum, bias, channels_last)
 
     @staticmethod

@@ -1,0 +1,197 @@
+// host_direct.cpp -- fc_conv_direct_geometry and fc_conv_direct (include/fftconv_amd.h "Direct forward"): the planner of
+// conv_direct_kernel (conv_direct.hpp) and its launch.  The planner is pure arithmetic on the descriptor and the CU
+// count; the launch call plans again for the current device (the last answer is remembered per thread), allocates
+// nothing and synchronises nothing.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "conv_direct.hpp"
+#include "fc_plan.h"
+
+using namespace fc;
+
+namespace {
+
+constexpr int64_t kLdsShared = 64 * 1024;       // up to here two workgroups share a CU
+constexpr int64_t kLdsBudget = 160 * 1024;
+constexpr int kMaxTaps = 128;
+constexpr int kDepthwiseMaxMultiplier = 8;      // Cin/g == 1 and Cout/g up to here: of the layer's weight: refused
+
+struct Geom {
+  int ax0;                   // first axis of the descriptor in the kernel's (z, y, x): 1 for a 2-D layer
+  int O[3], S[3], k[3], stride[3], dil[3], pad[3];
+  int tile[3], ntile[3], halo[3];
+  int Cig, Cog, taps, cib, nib, nob, npt, steps, P;
+  int64_t units, lds;
+};
+
+int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Validates the descriptor and chooses input-channel block and tile.  Both minimise a cycle estimate of the whole
+// launch: per workgroup and input-channel block the MFMAs of a wave (steps x NPT instructions x 32 cycles), a fixed
+// cost for the exposed latency of its loads, and half a cycle per staged sample; among the candidates of which two
+// workgroups share a CU (64 KiB of LDS, fewer than 16 position tiles per wave), else among those that fit the 160 KiB budget.  (The constants are those of the weight gradient's planner,
+// host_wgrad.cpp; DESIGN 4.5d says what the benchmark showed of them.)
+int plan(const fc_desc& c, int cus, Geom& g) {
+  if (c.ndim == 1) return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct covers 2-D and 3-D convolutions (no 1-D)");
+  if (c.ndim < 1 || c.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", c.ndim);
+  if (c.dtype == FC_F64 || c.dtype == FC_C64)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct takes float32, float16 or bfloat16 tensors (no %s)",
+                c.dtype == FC_F64 ? "float64" : "complex64");
+  if (c.dtype != FC_F32 && c.dtype != FC_F16 && c.dtype != FC_BF16) return fail(FC_ERR_INVALID, "unknown dtype %d", c.dtype);
+  if (c.batch < 1 || c.in_channels < 1 || c.out_channels < 1 || c.groups < 1 || c.in_channels % c.groups || c.out_channels % c.groups)
+    return fail(FC_ERR_INVALID, "batch, channels and groups must be positive and the channels divisible by groups");
+  if (c.padding_mode < 0 || c.padding_mode > 3) return fail(FC_ERR_INVALID, "unknown padding_mode %d", c.padding_mode);
+  if (c.transposed && c.padding_mode != FC_PAD_CONSTANT) return fail(FC_ERR_INVALID, "a transposed convolution pads with zeros");
+  if (cus < 1) return fail(FC_ERR_INVALID, "compute_units must be positive (got %d)", cus);
+  g.ax0 = 3 - c.ndim;
+  for (int a = 0; a < 3; ++a) { g.O[a] = g.S[a] = g.k[a] = g.stride[a] = g.dil[a] = 1; g.pad[a] = 0; }
+  int64_t taps = 1, xs = c.batch * c.in_channels, ys = c.batch * c.out_channels;
+  for (int i = 0; i < c.ndim; ++i) {
+    const int a = g.ax0 + i;
+    if (c.spatial[i] < 1 || c.kernel[i] < 1 || c.stride[i] < 1 || c.dilation[i] < 1 || c.padding[i] < 0)
+      return fail(FC_ERR_INVALID, "axis %d: spatial/kernel/stride/dilation must be >= 1 and padding >= 0", i);
+    if (c.kernel[i] > kMaxTaps || c.dilation[i] >= (1 << 20) || c.stride[i] >= (1 << 20))
+      return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct covers kernels of at most %d taps in all", i, kMaxTaps);
+    int64_t pad = c.padding[i];
+    if (c.transposed) {
+      // the stride-1 transposed convolution is the forward one with the taps flipped and a padding of d * (k - 1) - p
+      if (c.stride[i] != 1)
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct runs a transposed convolution at stride 1 only (got stride %lld)", i,
+                    (long long)c.stride[i]);
+      if (c.output_padding[i] != 0)
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct runs a transposed convolution without output padding", i);
+      pad = (c.kernel[i] - 1) * c.dilation[i] - c.padding[i];
+      if (pad < 0)
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: the padding %lld of a transposed convolution exceeds d * (k - 1) = %lld: a crop, "
+                    "which fc_conv_direct does not run", i, (long long)c.padding[i], (long long)((c.kernel[i] - 1) * c.dilation[i]));
+    }
+    if (c.spatial[i] + 2 * pad >= ((int64_t)1 << 31))
+      return fail(FC_ERR_UNSUPPORTED, "axis %d: padded extent %lld exceeds 32-bit positions (must be < 2^31 samples)", i,
+                  (long long)(c.spatial[i] + 2 * pad));
+    const int64_t kd = (c.kernel[i] - 1) * c.dilation[i] + 1, span = c.spatial[i] + 2 * pad - kd;
+    if (span < 0) return fail(FC_ERR_INVALID, "axis %d: dilated kernel extent %lld is larger than the padded input", i, (long long)kd);
+    if (c.padding_mode == FC_PAD_REFLECT && pad >= c.spatial[i])
+      return fail(FC_ERR_INVALID, "axis %d: reflect padding (%lld) must be smaller than the input size (%lld)", i, (long long)pad,
+                  (long long)c.spatial[i]);
+    if (c.padding_mode == FC_PAD_CIRCULAR && pad > c.spatial[i])
+      return fail(FC_ERR_INVALID, "axis %d: circular padding (%lld) must not exceed the input size (%lld)", i, (long long)pad,
+                  (long long)c.spatial[i]);
+    g.S[a] = (int)c.spatial[i]; g.O[a] = (int)(span / c.stride[i] + 1); g.k[a] = (int)c.kernel[i];
+    g.stride[a] = (int)c.stride[i]; g.dil[a] = (int)c.dilation[i]; g.pad[a] = (int)pad;
+    taps *= c.kernel[i];
+    xs *= c.spatial[i]; ys *= g.O[a];
+    if (xs >= ((int64_t)1 << 40) || ys >= ((int64_t)1 << 40))
+      return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct indexes x and y in 64 bits but takes fewer than 2^40 samples each");
+  }
+  if (taps > kMaxTaps)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct covers kernels of at most %d taps in all (got %lld): a block of %d columns "
+                "holds whole input channels", kMaxTaps, (long long)taps, kCdMaxCols);
+  g.taps = (int)taps;
+  g.Cig = (int)(c.in_channels / c.groups); g.Cog = (int)(c.out_channels / c.groups);
+  if (c.in_channels >= (1 << 30) || c.out_channels >= (1 << 30)) return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct: fewer than 2^30 channels");
+  g.nob = (int)cdiv(g.Cog, kCdRows);
+
+  // candidates: the largest channel blocks of the first 8 even splits of the group, tiles of powers of two clipped to the output
+  double best = -1.0;
+  bool best_shared = false;
+  const int cibmax = std::min<int>(g.Cig, kCdMaxCols / g.taps);
+  int last_cib = 0, tried = 0;
+  for (int n = (int)cdiv(g.Cig, cibmax); n <= g.Cig && tried < 8; ++n) {
+    const int cib = (int)cdiv(g.Cig, n);
+    if (cib == last_cib) continue;
+    last_cib = cib; ++tried;
+    const int nib = (int)cdiv(g.Cig, cib), steps = (int)cdiv(cib * g.taps, 4);
+    for (int tz = 1; tz <= 8; tz *= 2)
+      for (int ty = 1; ty <= 16; ty *= 2)
+        for (int tx = 1; tx <= 64; tx *= 2) {
+          const int t[3] = {std::min(tz, g.O[0]), std::min(ty, g.O[1]), std::min(tx, g.O[2])};
+          if ((tz > 1 && t[0] < tz && tz / 2 >= g.O[0]) || (ty > 1 && t[1] < ty && ty / 2 >= g.O[1]) ||
+              (tx > 1 && t[2] < tx && tx / 2 >= g.O[2]))
+            continue;      // (the same clipped tile as a smaller candidate)
+          const int P = t[0] * t[1] * t[2];
+          if (P > kCdMaxPos) continue;
+          int npt = 1;
+          while (kCdWaves * npt * 16 < P) npt *= 2;
+          int64_t hv = 1, ntiles = 1;
+          for (int a = 0; a < 3; ++a) {
+            hv *= (int64_t)(t[a] - 1) * g.stride[a] + (int64_t)(g.k[a] - 1) * g.dil[a] + 1;
+            ntiles *= cdiv(g.O[a], t[a]);
+            if (hv > kLdsBudget) break;
+          }
+          if (hv > kLdsBudget) continue;
+          const int64_t lds = 4 * ((int64_t)steps * (kCdWPitch + 4) + cib * hv);
+          if (lds > kLdsBudget) continue;
+          const bool shared = lds <= kLdsShared && npt < kCdMaxPT;      // (the build of 16 tiles per wave: 312 VGPRs, one workgroup per CU)
+          if (best_shared && !shared) continue;
+          const double cost = (double)nib * (double)ntiles * (32.0 * steps * npt + 3000.0 + 0.5 * (cib * (double)hv + 64.0 * steps));
+          if (best < 0 || (shared && !best_shared) || cost < best) {
+            best = cost; best_shared = shared;
+            g.cib = cib; g.nib = nib; g.npt = npt; g.steps = steps; g.P = P; g.lds = lds;
+            for (int a = 0; a < 3; ++a) {
+              g.tile[a] = t[a]; g.ntile[a] = (int)cdiv(g.O[a], t[a]);
+              g.halo[a] = (t[a] - 1) * g.stride[a] + (g.k[a] - 1) * g.dil[a] + 1;
+            }
+          }
+        }
+  }
+  if (best < 0)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct: the x samples that one output position reaches through every tap do not "
+                "fit %lld bytes of LDS", (long long)kLdsBudget);
+  // (the layer whose weight this is: a transposed descriptor carries the weight of the layer it is the input gradient of)
+  if ((c.transposed ? g.Cog : g.Cig) == 1 && (c.transposed ? g.Cig : g.Cog) <= kDepthwiseMaxMultiplier)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct does not run depthwise layers (a weight with one input channel per group and "
+                "%d output channels per group: one live reduction column in four, at most 8 live rows in 16), forward or "
+                "transposed; they keep the FFT plan", c.transposed ? g.Cig : g.Cog);
+  g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
+  if (g.units >= ((int64_t)1 << 31))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+  if (g.units * c.groups * g.nob > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct: %lld workgroups exceed the 2^31 of one launch", (long long)(g.units * c.groups * g.nob));
+  return FC_OK;
+}
+
+}  // namespace
+
+extern "C" int fc_conv_direct_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
+  if (!desc || !info) return fail(FC_ERR_INVALID, "null argument");
+  Geom g;
+  if (int st = plan(*desc, compute_units, g)) return st;
+  for (int i = 0; i < 3; ++i) info[i] = i < desc->ndim ? g.tile[g.ax0 + i] : 0;
+  info[3] = std::min(g.Cog, kCdRows); info[4] = g.cib; info[5] = g.nob; info[6] = g.nib; info[7] = g.lds;
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream) {
+  if (!desc || !x || !weight || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward: a stale sticky error of an earlier call is not this call's)
+  int cus = 0;
+  if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
+  // the plan of the last call of this thread, while descriptor and CU count are what they were
+  struct Last { fc_desc d; int cus; Geom g; bool set; };
+  static thread_local Last last = {};
+  if (!last.set || std::memcmp(&last.d, desc, sizeof(fc_desc)) || last.cus != cus) {
+    last.set = false;
+    if (int st = plan(*desc, cus, last.g)) return st;
+    last.d = *desc; last.cus = cus; last.set = true;
+  }
+  const Geom& g = last.g;
+  const fc_desc& c = *desc;
+  ConvDirectArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.w = weight; a.bias = bias; a.y = y;
+  for (int i = 0; i < 3; ++i) {
+    a.map[i] = AxisMap{g.S[i], g.pad[i], c.padding_mode, 1};
+    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.stride[i] = g.stride[i]; a.dil[i] = g.dil[i];
+    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
+  }
+  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
+  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
+  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
+  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
+  a.io = c.dtype; a.transposed = c.transposed ? 1 : 0;
+  FC_HIP(conv_direct_launch(a, g.npt, g.units * c.groups * g.nob, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}

@@ -73,9 +73,10 @@ __device__ __forceinline__ void wgd_unit_origin(const WgradDirectArgs& a, int u,
 }
 
 // The x halo of nci input channels (xsrc: the first, Svol samples apart) of the tile at (o0z, o0y, o0x) into
-// xl[ci][HV], through the padding mode: a zero where axis_src says -1.  Each global sample is read once.
-template <class IoT, class T>
-__device__ __forceinline__ void wgd_stage_halo(const WgradDirectArgs& a, const IoT& io, const T* xsrc, float* xl, int nci,
+// xl[ci][HV], through the padding mode: a zero where axis_src says -1.  Each global sample is read once.  Args: the
+// argument struct of a kernel of 256 threads with map, stride, S, fd_hx and fd_hy (conv_direct.hpp stages its halo here too).
+template <class Args, class IoT, class T>
+__device__ __forceinline__ void wgd_stage_halo(const Args& a, const IoT& io, const T* xsrc, float* xl, int nci,
                                                int HV, size_t Svol, int o0z, int o0y, int o0x, int tid) {
   for (int e = tid; e < HV; e += kWgdThreads) {
     unsigned q, hz;

@@ -18,7 +18,7 @@ from torch import Tensor
 from . import _native
 from .utils import to_ntuple
 
-__all__ = ["fft_conv", "fft_long_conv", "fft_long_conv_gated", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum", "FFTLongConvStream"]
+__all__ = ["fft_conv", "conv_route", "fft_long_conv", "fft_long_conv_gated", "fft_long_conv_transpose", "fft_conv_transpose", "complex_matmul", "to_ntuple", "transform_kernel", "KernelSpectrum", "FFTLongConvStream"]
 
 
 _DTYPE_CODES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.complex64: 4}      # enum fc_dtype
@@ -376,6 +376,127 @@ def _needs_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
+# ---- the direct small-kernel route (FFTCONV_DIRECT=1; ``fc_conv_direct``, csrc/conv_direct.hpp)
+_DIRECT_IO = {torch.float32: 0, torch.float16: 2, torch.bfloat16: 3}      # fc_dtype code of x, weight, bias and y
+# (shapes, hyper-parameters, device, dtype, CU count) -> (descriptor, geometry words, shape of y), False where refused
+_DIRECT_GEOMETRY: "collections.OrderedDict[tuple, object]" = collections.OrderedDict()
+_DEVICE_CUS: dict = {}
+
+
+def _direct_on() -> bool:
+    """FFTCONV_DIRECT (read per call): "1" takes y and dX of 2-D / 3-D real layers of a few taps from the time-domain
+    kernel where the library covers the layer; unset or anything else never does.  Opt-in: the bits of y and dX change."""
+    return os.environ.get("FFTCONV_DIRECT", "0") == "1"
+
+
+def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, groups, padding_mode, transposed=False,
+                     output_padding=None):
+    """(descriptor, geometry words, shape of y) of ``fc_conv_direct`` for a signal of ``shape`` on ``device``, None where the
+    library refuses the layer (1-D, float64, complex64, more than 128 taps, depthwise, a strided transposed layer, ...) or
+    the arguments do not describe a layer.  Arithmetic only: ``fc_conv_direct_geometry`` touches no device; the CU count is
+    the device's, 256 for a device that is not a GPU.  ``stride`` ... ``output_padding``: tuples per axis."""
+    n = len(shape) - 2
+    if n not in (2, 3) or len(wshape) != n + 2 or dtype not in _DIRECT_IO or padding_mode not in _native.PAD_MODES:
+        return None
+    if not isinstance(groups, int) or groups < 1 or shape[1] % groups:
+        return None
+    output_padding = (0,) * n if output_padding is None else output_padding
+    cin = int(shape[1])
+    if transposed:
+        cout = int(wshape[1]) * groups
+        if int(wshape[0]) != cin:
+            return None
+    else:
+        cout = int(wshape[0])
+        if cout % groups or int(wshape[1]) * groups != cin:
+            return None
+    device = torch.device(device)
+    cus = _DEVICE_CUS.get(device)
+    if cus is None:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
+        _DEVICE_CUS[device] = cus
+    key = (tuple(shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, bool(transposed), output_padding,
+           device, dtype, cus)
+    hit = _DIRECT_GEOMETRY.get(key)
+    if hit is None:
+        hit = False
+        try:
+            desc = _native.conv_desc(n, int(shape[0]), cin, cout, groups, tuple(int(v) for v in shape[2:]),
+                                     tuple(int(v) for v in wshape[2:]), stride, padding, dilation,
+                                     _native.PAD_MODES[padding_mode], _DIRECT_IO[dtype], transposed=transposed,
+                                     output_padding=output_padding)
+            geom = _native.conv_direct_geometry(desc, cus)
+            if transposed:      # (stride 1, no output padding: the library refuses the rest)
+                out = tuple(int(S) - 2 * p + d * (int(k) - 1) for S, p, d, k in zip(shape[2:], padding, dilation, wshape[2:]))
+            else:
+                out = tuple((int(S) + 2 * p - d * (int(k) - 1) - 1) // s + 1
+                            for S, p, d, k, s in zip(shape[2:], padding, dilation, wshape[2:], stride))
+            hit = (desc, geom, (int(shape[0]), cout) + out)
+        except (NotImplementedError, ValueError, TypeError):
+            pass      # (refused, or not a layer: the FFT route takes the call and says what is wrong with it)
+        _DIRECT_GEOMETRY[key] = hit
+        while len(_DIRECT_GEOMETRY) > 256:
+            _DIRECT_GEOMETRY.popitem(last=False)
+    return hit or None
+
+
+def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
+                channels_last: bool = False, native: bool = False):
+    """``_direct_geometry`` of a call that takes the direct route: FFTCONV_DIRECT=1, contiguous real 4-D / 5-D signal,
+    kernel and bias of its dtype on its device (16-bit tensors: not under FFTCONV_HALF_IO=0), no channels-last operand
+    or result, a layer the library covers.  None keeps the call on the route it has without the switch."""
+    if not _direct_on() or channels_last or native or isinstance(padding, str):
+        return None
+    if not all(isinstance(t, Tensor) for t in (signal, kernel)) or signal.ndim not in (4, 5) or kernel.ndim != signal.ndim:
+        return None
+    if signal.dtype not in _DIRECT_IO or kernel.dtype != signal.dtype or (bias is not None and bias.dtype != signal.dtype):
+        return None
+    if signal.dtype in _LOW_PRECISION and not _half_native(signal, kernel, bias):
+        return None
+    if not signal.is_cuda or kernel.device != signal.device or (bias is not None and bias.device != signal.device):
+        return None
+    if not signal.is_contiguous():
+        return None
+    n = signal.ndim - 2
+    try:
+        conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
+    except (TypeError, ValueError):
+        return None
+    hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel.shape), conf[0], conf[1], conf[2],
+                           groups, padding_mode, transposed, conf[3])
+    if hit is not None and bias is not None and tuple(bias.shape) != (hit[2][1],):
+        return None
+    return hit
+
+
+def _direct_run(hit, signal: Tensor, kernel: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """One ``fc_conv_direct`` launch of a ``_direct_hit``: the weight is read where it lies, no plan, no spectrum."""
+    desc, _, shape = hit
+    signal, kernel = signal.detach(), kernel.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    with torch.cuda.device(signal.device):
+        out = torch.empty(shape, dtype=signal.dtype, device=signal.device)
+        _native.conv_direct(desc, signal.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(),
+                            out.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
+    return out
+
+
+def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, groups=1, padding_mode="constant", *,
+               channels_last: bool = False, transposed: bool = False, output_padding=0) -> str:
+    """The route the forward of ``fft_conv`` (``transposed``: of ``fft_conv_transpose``) takes for this signal and a
+    kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers) or
+    ``"fft"``.  Arithmetic only: launches nothing, creates no plan."""
+    if not _direct_on() or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
+        return "fft"
+    if signal.dtype in _LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
+        return "fft"
+    n = signal.ndim - 2
+    conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
+    hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0], conf[1], conf[2],
+                           groups, "constant" if padding_mode == "zeros" else padding_mode, transposed, conf[3])
+    return "direct" if hit else "fft"
+
+
 def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
                spectrum, plan, channels_last: bool = False, native: bool = False):
     """The body of ``_fft_conv_impl`` and ``_fft_conv_transpose_impl`` (``native``: see ``_forward_native``)."""
@@ -397,7 +518,13 @@ def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_p
     # float16 / bfloat16: the kernels read x and write y in the tensors' dtype (float32 arithmetic, the bits of the cast
     # path below) -- unless the library refuses the route (it reads y back between launches): then the cast path
     native16 = _half_native(signal, kernel, bias)
-    if native16 and plan is None:
+    # FFTCONV_DIRECT=1 and a covered layer: y from the time-domain kernel (no plan, no spectrum; a call that needs gradients
+    # takes it inside the autograd function below)
+    direct = _direct_hit(transposed, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
+                         channels_last, native)
+    if direct is not None and not _needs_grad(signal, kernel, bias):
+        return _direct_run(direct, signal, kernel, bias)
+    if native16 and plan is None and direct is None:
         try:
             plan = _plan_for(signal, kernel, bias, *conf)
         except NotImplementedError:

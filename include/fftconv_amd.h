@@ -213,6 +213,30 @@ int fc_wgrad_direct_geometry(const fc_desc* conv_desc, int compute_units, int64_
 int fc_wgrad_direct_body(const fc_desc* conv_desc, int compute_units, int* body);
 int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const void* dy, float* dw, void* workspace, void* hip_stream);
 
+/* Direct forward of a 2-D / 3-D convolution with a small kernel (ABI 7 extension: two new entry points; fc_desc keeps its
+ * size and every call above its signature and meaning).  No plan, no kernel spectrum, no workspace:
+ *   y[b][(g,o)][t] = bias[(g,o)] + sum_i sum_k W[(g,o)][i][k] * Xpad[b][(g,i)][t*stride + k*dilation - pad]
+ * taken in the time domain, a GEMM of (Cout/groups) x (Cin/groups * taps) with B * prod(out) columns on the matrix pipe,
+ * float32 accumulation, x read where it lies through the layer's padding mode (all four).  x, weight, bias and y all have
+ * the descriptor's dtype (16-bit tensors: widened exactly as loaded, y rounded once as stored); bias may be NULL.  Every
+ * sample of y is written exactly once and nothing else is; equal calls give equal bits.
+ *   Covered: ndim 2 or 3; FC_F32, FC_F16 or FC_BF16; at most 128 taps in all; any batch, channels, groups, stride, dilation,
+ *   padding and padding mode of a forward descriptor.  A descriptor with transposed = 1 is covered at stride 1 on every
+ *   axis, output_padding 0 and padding <= dilation * (kernel - 1) on every axis: the weight (Cin, Cout/groups, *k) is read
+ *   where it lies, channel roles exchanged and taps flipped, under a padding of dilation * (kernel - 1) - padding.  This is
+ *   the input gradient of every stride-1 layer with zero padding.
+ *   FC_ERR_UNSUPPORTED with text: ndim 1, FC_F64, FC_C64, more taps, any other transposed descriptor, a layer whose weight
+ *   has one input channel per group and at most 8 output channels per group (depthwise: it keeps its FFT plan; a
+ *   transposed descriptor carries the (Cout, Cin/groups, *k) weight of the layer it is the input gradient of), a halo (the x
+ *   samples one output position reaches through every tap, for one input channel) that does not fit 160 KiB of LDS, an
+ *   axis whose padded extent reaches 2^31, a tensor of 2^40 samples, 2^31 units or workgroups.
+ * fc_conv_direct_geometry is pure arithmetic: no device is touched.  info words: output tile per axis in tensor order
+ * (3 words, 0 past ndim), output channels per workgroup (<= 16), input channels per block (times the taps <= 512), blocks
+ * of output channels per group, blocks of input channels per group, bytes of LDS per workgroup.
+ * fc_conv_direct plans for the CURRENT device and launches once on hip_stream.  Asynchronous; allocates nothing. */
+int fc_conv_direct_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
+int fc_conv_direct(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

@@ -2,8 +2,10 @@
 """Compare the device code of two source trees, kernel by kernel.  No GPU needed.
 
 For every object of the native library that holds kernels (the 7 tile objects, the 7 long-filter objects,
-fft_f64, nd_f64, direct_f64, long_f64, long_step) the device side of both trees is compiled to assembly text with the flags of
-csrc/Makefile (`hipcc ... --cuda-device-only -S`).  The kernels of the two sides are put in one-to-one
+fft_f64, nd_f64, direct_f64, long_f64, long_step, wgrad_direct, conv_direct) the device side of both trees is
+compiled to assembly text with the flags of csrc/Makefile (`hipcc ... --cuda-device-only -S`).  An object whose
+source file one tree does not have counts as having no kernels there: its kernels are listed as only in the other
+tree.  The kernels of the two sides are put in one-to-one
 correspondence by demangled name -- conv1d_pers_kernel by (P, S, CIB, NB, NT) and the set of features its parameter
 list switches on, in either spelling: the seven positional parameters or the pers:: feature mask -- and each pair is
 compared in
@@ -51,6 +53,9 @@ def objects():
         objs.append(("long_" + t, "long_inst.hip", ["-DFC_P=" + p, "-DFC_S=" + s]))
     for n in ("fft_f64", "nd_f64", "direct_f64", "long_f64", "long_step"):
         objs.append((n, n + ".hip", []))
+    # (the direct weight gradient and the direct forward, with the flags of their rules in csrc/Makefile)
+    for n in ("wgrad_direct", "conv_direct"):
+        objs.append((n, n + ".hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     return objs
 
 
@@ -65,6 +70,8 @@ def tools():
 
 
 def compile_device(hipcc, tree, src, defs, out, reuse):
+    if not os.path.exists(os.path.join(tree, CSRC, src)):
+        return None      # (an object this tree does not have)
     if reuse and os.path.exists(out):
         return out
     cmd = [hipcc] + CXXFLAGS + defs + ["--cuda-device-only", "-S", src, "-o", out]
@@ -96,7 +103,9 @@ def pers_key(name):
 
 
 def parse(path, filt):
-    """-> {key: (instruction lines, {field: value})}"""
+    """-> {key: (instruction lines, {field: value})}; path None (no such object in the tree): no kernels"""
+    if path is None:
+        return {}
     text = open(path).read()
     lines = text.split("\n")
     # metadata: the entries of amdhsa.kernels, kernel-level keys at an indent of 4 (the first behind "  - ")

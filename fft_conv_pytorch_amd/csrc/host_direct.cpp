@@ -1,13 +1,15 @@
 // host_direct.cpp -- fc_conv_direct_geometry and fc_conv_direct (include/fftconv_amd.h "Direct forward"): the planner of
-// conv_direct_kernel (conv_direct.hpp) and its launch.  The planner is pure arithmetic on the descriptor and the CU
-// count; the launch call plans again for the current device (the last answer is remembered per thread), allocates
-// nothing and synchronises nothing.
+// conv_direct_kernel (conv_direct.hpp) and its launch; fc_conv_direct_dw_geometry and fc_conv_direct_dw ("Direct
+// depthwise forward"): those of conv_direct_dw_kernel (conv_direct_dw.hpp), behind the same validation.  The planners
+// are pure arithmetic on the descriptor and the CU count; a launch call plans again for the current device (the last
+// answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 
 #include "conv_direct.hpp"
+#include "conv_direct_dw.hpp"
 #include "fc_plan.h"
 
 using namespace fc;
@@ -25,20 +27,21 @@ struct Geom {
   int tile[3], ntile[3], halo[3];
   int Cig, Cog, taps, cib, nib, nob, npt, steps, P;
   int64_t units, lds;
+  // the depthwise kernel (plan_dw); there halo[2] is the padded pitch of a halo row
+  int m, slots, nr;          // channel multiplier, multiplier slots and runs per thread of the build
+  int kxb, nbx, kxp, wp, wl; // taps per block, blocks per kernel row, floats per staged tap row / channel / group
+  int runs;                  // runs of kDwR positions per tile
 };
 
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Validates the descriptor and chooses input-channel block and tile.  Both minimise a cycle estimate of the whole
-// launch: per workgroup and input-channel block the MFMAs of a wave (steps x NPT instructions x 32 cycles), a fixed
-// cost for the exposed latency of its loads, and half a cycle per staged sample; among the candidates of which two
-// workgroups share a CU (64 KiB of LDS, fewer than 16 position tiles per wave), else among those that fit the 160 KiB budget.  (The constants are those of the weight gradient's planner,
-// host_wgrad.cpp; DESIGN 4.5d says what the benchmark showed of them.)
-int plan(const fc_desc& c, int cus, Geom& g) {
-  if (c.ndim == 1) return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct covers 2-D and 3-D convolutions (no 1-D)");
+// The descriptor of a layer either direct forward covers, into g: extents, taps and channels per group.  `who` names the
+// entry point in the refusals, `why_taps` ends the one of a kernel past 128 taps.
+int validate(const fc_desc& c, int cus, const char* who, const char* why_taps, Geom& g) {
+  if (c.ndim == 1) return fail(FC_ERR_UNSUPPORTED, "%s covers 2-D and 3-D convolutions (no 1-D)", who);
   if (c.ndim < 1 || c.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", c.ndim);
   if (c.dtype == FC_F64 || c.dtype == FC_C64)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct takes float32, float16 or bfloat16 tensors (no %s)",
+    return fail(FC_ERR_UNSUPPORTED, "%s takes float32, float16 or bfloat16 tensors (no %s)", who,
                 c.dtype == FC_F64 ? "float64" : "complex64");
   if (c.dtype != FC_F32 && c.dtype != FC_F16 && c.dtype != FC_BF16) return fail(FC_ERR_INVALID, "unknown dtype %d", c.dtype);
   if (c.batch < 1 || c.in_channels < 1 || c.out_channels < 1 || c.groups < 1 || c.in_channels % c.groups || c.out_channels % c.groups)
@@ -54,19 +57,19 @@ int plan(const fc_desc& c, int cus, Geom& g) {
     if (c.spatial[i] < 1 || c.kernel[i] < 1 || c.stride[i] < 1 || c.dilation[i] < 1 || c.padding[i] < 0)
       return fail(FC_ERR_INVALID, "axis %d: spatial/kernel/stride/dilation must be >= 1 and padding >= 0", i);
     if (c.kernel[i] > kMaxTaps || c.dilation[i] >= (1 << 20) || c.stride[i] >= (1 << 20))
-      return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct covers kernels of at most %d taps in all", i, kMaxTaps);
+      return fail(FC_ERR_UNSUPPORTED, "axis %d: %s covers kernels of at most %d taps in all", i, who, kMaxTaps);
     int64_t pad = c.padding[i];
     if (c.transposed) {
       // the stride-1 transposed convolution is the forward one with the taps flipped and a padding of d * (k - 1) - p
       if (c.stride[i] != 1)
-        return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct runs a transposed convolution at stride 1 only (got stride %lld)", i,
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: %s runs a transposed convolution at stride 1 only (got stride %lld)", i, who,
                     (long long)c.stride[i]);
       if (c.output_padding[i] != 0)
-        return fail(FC_ERR_UNSUPPORTED, "axis %d: fc_conv_direct runs a transposed convolution without output padding", i);
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: %s runs a transposed convolution without output padding", i, who);
       pad = (c.kernel[i] - 1) * c.dilation[i] - c.padding[i];
       if (pad < 0)
         return fail(FC_ERR_UNSUPPORTED, "axis %d: the padding %lld of a transposed convolution exceeds d * (k - 1) = %lld: a crop, "
-                    "which fc_conv_direct does not run", i, (long long)c.padding[i], (long long)((c.kernel[i] - 1) * c.dilation[i]));
+                    "which %s does not run", i, (long long)c.padding[i], (long long)((c.kernel[i] - 1) * c.dilation[i]), who);
     }
     if (c.spatial[i] + 2 * pad >= ((int64_t)1 << 31))
       return fail(FC_ERR_UNSUPPORTED, "axis %d: padded extent %lld exceeds 32-bit positions (must be < 2^31 samples)", i,
@@ -84,14 +87,24 @@ int plan(const fc_desc& c, int cus, Geom& g) {
     taps *= c.kernel[i];
     xs *= c.spatial[i]; ys *= g.O[a];
     if (xs >= ((int64_t)1 << 40) || ys >= ((int64_t)1 << 40))
-      return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct indexes x and y in 64 bits but takes fewer than 2^40 samples each");
+      return fail(FC_ERR_UNSUPPORTED, "%s indexes x and y in 64 bits but takes fewer than 2^40 samples each", who);
   }
   if (taps > kMaxTaps)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct covers kernels of at most %d taps in all (got %lld): a block of %d columns "
-                "holds whole input channels", kMaxTaps, (long long)taps, kCdMaxCols);
+    return fail(FC_ERR_UNSUPPORTED, "%s covers kernels of at most %d taps in all (got %lld): %s", who, kMaxTaps, (long long)taps, why_taps);
   g.taps = (int)taps;
   g.Cig = (int)(c.in_channels / c.groups); g.Cog = (int)(c.out_channels / c.groups);
-  if (c.in_channels >= (1 << 30) || c.out_channels >= (1 << 30)) return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct: fewer than 2^30 channels");
+  if (c.in_channels >= (1 << 30) || c.out_channels >= (1 << 30)) return fail(FC_ERR_UNSUPPORTED, "%s: fewer than 2^30 channels", who);
+  return FC_OK;
+}
+
+// Validates the descriptor and chooses input-channel block and tile.  Both minimise a cycle estimate of the whole
+// launch: per workgroup and input-channel block the MFMAs of a wave (steps x NPT instructions x 32 cycles), a fixed
+// cost for the exposed latency of its loads, and half a cycle per staged sample; among the candidates of which two
+// workgroups share a CU (64 KiB of LDS, fewer than 16 position tiles per wave), else among those that fit the 160 KiB budget.  (The constants are those of the weight gradient's planner,
+// host_wgrad.cpp; DESIGN 4.5d says what the benchmark showed of them.)
+int plan(const fc_desc& c, int cus, Geom& g) {
+  static_assert(kCdMaxCols == 512, "the text below");
+  if (int st = validate(c, cus, "fc_conv_direct", "a block of 512 columns holds whole input channels", g)) return st;
   g.nob = (int)cdiv(g.Cog, kCdRows);
 
   // candidates: the largest channel blocks of the first 8 even splits of the group, tiles of powers of two clipped to the output
@@ -153,6 +166,75 @@ int plan(const fc_desc& c, int cus, Geom& g) {
   return FC_OK;
 }
 
+// The depthwise planner: the layer's weight must have one input channel per group and a multiplier of at most 8, the
+// set plan() refuses.  Tiles are powers of two clipped to the output, at most 256 * NR runs of 4 outputs (NR: runs per
+// thread of the build, 8 / multiplier slots).  The one with the smallest cycle estimate of the launch wins among those
+// whose LDS lets two workgroups share a CU, else among those that fit: rounds of workgroups over 2 x CUs, times per
+// workgroup the FMAs of a thread (4 cycles each), its 16-byte LDS reads (8 cycles each; the weights once per block, the
+// window once per run), half a cycle per staged sample and a fixed cost for the exposed latency of the loads.
+int plan_dw(const fc_desc& c, int cus, Geom& g) {
+  if (int st = validate(c, cus, "fc_conv_direct_dw", "the sums of one output sample are one chain", g)) return st;
+  const int wci = c.transposed ? g.Cog : g.Cig;      // (of the layer whose weight this is, as plan() reads it)
+  g.m = c.transposed ? g.Cig : g.Cog;
+  if (wci != 1)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_dw runs depthwise layers only: this weight has %d input channels per group, "
+                "not one (fc_conv_direct covers it)", wci);
+  if (g.m > kDepthwiseMaxMultiplier)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_dw runs channel multipliers of at most %d (got %d output channels per group; "
+                "fc_conv_direct covers it)", kDepthwiseMaxMultiplier, g.m);
+  g.slots = conv_direct_dw_slots(g.m, c.transposed);
+  g.nr = kCdwAcc / g.slots;
+  const bool unit = g.stride[2] == 1 && g.dil[2] == 1;      // else the general build, a tap per block
+  g.kxb = !unit ? 1 : g.k[2] <= 4 ? 4 : 8;
+  g.nbx = (int)cdiv(g.k[2], g.kxb); g.kxp = g.nbx * g.kxb; g.wp = g.k[0] * g.k[1] * g.kxp;
+  g.wl = (std::max(g.slots, g.m) * g.wp + 3) & ~3;      // (a slot past m: staged zeros)
+  const int nh = c.transposed ? g.m : 1, mlive = g.slots;      // staged halos; channels a block of taps feeds
+  const int64_t groups = c.batch * c.groups;
+  double best = -1.0;
+  bool best_shared = false;
+  for (int tz = 1; tz <= 8; tz *= 2)
+    for (int ty = 1; ty <= 64; ty *= 2)
+      for (int tx = kDwR; tx <= 128; tx *= 2) {
+        const int t[3] = {std::min(tz, g.O[0]), std::min(ty, g.O[1]), std::min(tx, g.O[2])};
+        if ((tz > 1 && tz / 2 >= g.O[0]) || (ty > 1 && ty / 2 >= g.O[1]) || (tx > kDwR && tx / 2 >= g.O[2]))
+          continue;      // (the same clipped tile as a smaller candidate)
+        const int txr = (t[2] + kDwR - 1) / kDwR * kDwR, runs = t[0] * t[1] * (txr / kDwR);
+        if (runs > kCdwThreads * g.nr) continue;
+        int64_t halo[3], ntiles = 1;
+        for (int a = 0; a < 3; ++a) {
+          halo[a] = (int64_t)(t[a] - 1) * g.stride[a] + (int64_t)(g.k[a] - 1) * g.dil[a] + 1;
+          ntiles *= cdiv(g.O[a], t[a]);
+        }
+        // the row pitch: the window of the last run through the last tap block, dead tail included, in whole reads
+        halo[2] = unit ? (txr - kDwR) + (g.nbx - 1) * g.kxb + 4 * dw_window4(g.kxb)
+                       : (int64_t)(txr - 1) * g.stride[2] + (int64_t)(g.k[2] - 1) * g.dil[2] + 1;
+        halo[2] = (halo[2] + 3) & ~(int64_t)3;
+        if (halo[0] > kLdsBudget || halo[1] > kLdsBudget || halo[2] > kLdsBudget || halo[0] * halo[1] > kLdsBudget) continue;
+        const int64_t hv = halo[0] * halo[1] * halo[2], lds = 4 * (g.wl + nh * hv);
+        if (lds > kLdsBudget) continue;
+        const bool shared = lds <= kLdsShared;
+        if (best_shared && !shared) continue;
+        const double rounds = (double)cdiv(runs, kCdwThreads), blocks = (double)nh * g.k[0] * g.k[1] * g.nbx;
+        const double reads = unit ? dw_window4(g.kxb) : kDwR;
+        const double work = blocks * (rounds * (4.0 * kDwR * g.kxb * mlive + 8.0 * reads) + 8.0 * mlive * std::max(1, g.kxb / 4));
+        const double cost = (double)cdiv(groups * ntiles, 2 * (int64_t)cus) * (work + 3000.0 + 0.5 * (nh * (double)hv + g.wl));
+        if (best < 0 || (shared && !best_shared) || cost < best) {
+          best = cost; best_shared = shared;
+          g.runs = runs; g.lds = lds;
+          for (int a = 0; a < 3; ++a) { g.tile[a] = t[a]; g.ntile[a] = (int)cdiv(g.O[a], t[a]); g.halo[a] = (int)halo[a]; }
+        }
+      }
+  if (best < 0)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_dw: the samples that one run of output positions reaches through every tap "
+                "(of %d channels) do not fit %lld bytes of LDS", nh, (long long)kLdsBudget);
+  g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
+  if (g.units >= ((int64_t)1 << 31))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_dw: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+  if (g.units * c.groups > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_dw: %lld workgroups exceed the 2^31 of one launch", (long long)(g.units * c.groups));
+  return FC_OK;
+}
+
 }  // namespace
 
 extern "C" int fc_conv_direct_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
@@ -193,5 +275,48 @@ extern "C" int fc_conv_direct(const fc_desc* desc, const void* x, const void* we
   a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
   a.io = c.dtype; a.transposed = c.transposed ? 1 : 0;
   FC_HIP(conv_direct_launch(a, g.npt, g.units * c.groups * g.nob, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_dw_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
+  if (!desc || !info) return fail(FC_ERR_INVALID, "null argument");
+  Geom g;
+  if (int st = plan_dw(*desc, compute_units, g)) return st;
+  for (int i = 0; i < 3; ++i) info[i] = i < desc->ndim ? g.tile[g.ax0 + i] : 0;
+  info[3] = g.kxb; info[4] = g.slots; info[5] = g.units * desc->groups; info[6] = g.lds; info[7] = g.nr;
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_dw(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream) {
+  if (!desc || !x || !weight || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward: a stale sticky error of an earlier call is not this call's)
+  int cus = 0;
+  if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
+  // the plan of the last call of this thread, while descriptor and CU count are what they were
+  struct Last { fc_desc d; int cus; Geom g; bool set; };
+  static thread_local Last last = {};
+  if (!last.set || std::memcmp(&last.d, desc, sizeof(fc_desc)) || last.cus != cus) {
+    last.set = false;
+    if (int st = plan_dw(*desc, cus, last.g)) return st;
+    last.d = *desc; last.cus = cus; last.set = true;
+  }
+  const Geom& g = last.g;
+  const fc_desc& c = *desc;
+  ConvDirectDwArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.w = weight; a.bias = bias; a.y = y;
+  for (int i = 0; i < 3; ++i) {
+    a.map[i] = AxisMap{g.S[i], g.pad[i], c.padding_mode, 1};
+    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.stride[i] = g.stride[i]; a.dil[i] = g.dil[i];
+    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
+  }
+  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
+  a.fd_rx = make_fastdiv((g.tile[2] + kDwR - 1) / kDwR); a.fd_ty = make_fastdiv(g.tile[1]);
+  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.G = (int)c.groups; a.m = g.m; a.taps = g.taps;
+  a.runs = g.runs; a.nbx = g.nbx; a.kxp = g.kxp; a.wp = g.wp; a.wl = g.wl;
+  // a live run goes out as one access where every run of y starts on a multiple of 4 samples of a 16-byte aligned tensor
+  a.vec = reinterpret_cast<uintptr_t>(y) % 16 == 0 && g.O[2] % kDwR == 0 && (g.tile[2] % kDwR == 0 || g.ntile[2] == 1);
+  a.io = c.dtype;
+  FC_HIP(conv_direct_dw_launch(a, g.kxb, c.transposed ? 1 : 0, g.units * c.groups, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

@@ -389,9 +389,17 @@ def _direct_on() -> bool:
     return os.environ.get("FFTCONV_DIRECT", "0") == "1"
 
 
+def _direct_dw_on() -> bool:
+    """FFTCONV_DIRECT_DW (read per call, independent of FFTCONV_DIRECT): "1" takes y and dX of depthwise 2-D / 3-D layers
+    of a few taps (one input channel per group, multiplier up to 8: what ``fc_conv_direct`` refuses as depthwise) from
+    ``fc_conv_direct_dw`` (csrc/conv_direct_dw.hpp).  Opt-in: the bits of y and dX change."""
+    return os.environ.get("FFTCONV_DIRECT_DW", "0") == "1"
+
+
 def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, groups, padding_mode, transposed=False,
-                     output_padding=None):
-    """(descriptor, geometry words, shape of y) of ``fc_conv_direct`` for a signal of ``shape`` on ``device``, None where the
+                     output_padding=None, dw=False):
+    """(descriptor, geometry words, shape of y, launch) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``) for a signal
+    of ``shape`` on ``device``, None where the
     library refuses the layer (1-D, float64, complex64, more than 128 taps, depthwise, a strided transposed layer, ...) or
     the arguments do not describe a layer.  Arithmetic only: ``fc_conv_direct_geometry`` touches no device; the CU count is
     the device's, 256 for a device that is not a GPU.  ``stride`` ... ``output_padding``: tuples per axis."""
@@ -416,7 +424,7 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
         cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
         _DEVICE_CUS[device] = cus
     key = (tuple(shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, bool(transposed), output_padding,
-           device, dtype, cus)
+           device, dtype, cus, bool(dw))
     hit = _DIRECT_GEOMETRY.get(key)
     if hit is None:
         hit = False
@@ -425,13 +433,13 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
                                      tuple(int(v) for v in wshape[2:]), stride, padding, dilation,
                                      _native.PAD_MODES[padding_mode], _DIRECT_IO[dtype], transposed=transposed,
                                      output_padding=output_padding)
-            geom = _native.conv_direct_geometry(desc, cus)
+            geom = (_native.conv_direct_dw_geometry if dw else _native.conv_direct_geometry)(desc, cus)
             if transposed:      # (stride 1, no output padding: the library refuses the rest)
                 out = tuple(int(S) - 2 * p + d * (int(k) - 1) for S, p, d, k in zip(shape[2:], padding, dilation, wshape[2:]))
             else:
                 out = tuple((int(S) + 2 * p - d * (int(k) - 1) - 1) // s + 1
                             for S, p, d, k, s in zip(shape[2:], padding, dilation, wshape[2:], stride))
-            hit = (desc, geom, (int(shape[0]), cout) + out)
+            hit = (desc, geom, (int(shape[0]), cout) + out, _native.conv_direct_dw if dw else _native.conv_direct)
         except (NotImplementedError, ValueError, TypeError):
             pass      # (refused, or not a layer: the FFT route takes the call and says what is wrong with it)
         _DIRECT_GEOMETRY[key] = hit
@@ -442,10 +450,12 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
 
 def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
                 channels_last: bool = False, native: bool = False):
-    """``_direct_geometry`` of a call that takes the direct route: FFTCONV_DIRECT=1, contiguous real 4-D / 5-D signal,
+    """``_direct_geometry`` of a call that takes a direct route: FFTCONV_DIRECT=1 and a layer ``fc_conv_direct`` covers, or
+    FFTCONV_DIRECT_DW=1 and a layer ``fc_conv_direct_dw`` covers (no layer is both); contiguous real 4-D / 5-D signal,
     kernel and bias of its dtype on its device (16-bit tensors: not under FFTCONV_HALF_IO=0), no channels-last operand
-    or result, a layer the library covers.  None keeps the call on the route it has without the switch."""
-    if not _direct_on() or channels_last or native or isinstance(padding, str):
+    or result.  None keeps the call on the route it has without the switches."""
+    on = (_direct_on(), _direct_dw_on())
+    if not any(on) or channels_last or native or isinstance(padding, str):
         return None
     if not all(isinstance(t, Tensor) for t in (signal, kernel)) or signal.ndim not in (4, 5) or kernel.ndim != signal.ndim:
         return None
@@ -462,39 +472,48 @@ def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_
         conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
     except (TypeError, ValueError):
         return None
-    hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel.shape), conf[0], conf[1], conf[2],
-                           groups, padding_mode, transposed, conf[3])
+    hit = None
+    for dw in (False, True):
+        if on[dw] and hit is None:
+            hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel.shape), conf[0], conf[1],
+                                   conf[2], groups, padding_mode, transposed, conf[3], dw)
     if hit is not None and bias is not None and tuple(bias.shape) != (hit[2][1],):
         return None
     return hit
 
 
 def _direct_run(hit, signal: Tensor, kernel: Tensor, bias: Optional[Tensor]) -> Tensor:
-    """One ``fc_conv_direct`` launch of a ``_direct_hit``: the weight is read where it lies, no plan, no spectrum."""
-    desc, _, shape = hit
+    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
+    no spectrum."""
+    desc, _, shape, launch = hit
     signal, kernel = signal.detach(), kernel.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     with torch.cuda.device(signal.device):
         out = torch.empty(shape, dtype=signal.dtype, device=signal.device)
-        _native.conv_direct(desc, signal.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(),
-                            out.data_ptr(), torch.cuda.current_stream(signal.device).cuda_stream)
+        launch(desc, signal.data_ptr(), kernel.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(),
+               torch.cuda.current_stream(signal.device).cuda_stream)
     return out
 
 
 def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, groups=1, padding_mode="constant", *,
                channels_last: bool = False, transposed: bool = False, output_padding=0) -> str:
     """The route the forward of ``fft_conv`` (``transposed``: of ``fft_conv_transpose``) takes for this signal and a
-    kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers) or
-    ``"fft"``.  Arithmetic only: launches nothing, creates no plan."""
-    if not _direct_on() or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
+    kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers),
+    ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and a call ``fc_conv_direct_dw`` covers) or ``"fft"``.  Arithmetic only: launches
+    nothing, creates no plan."""
+    on = (_direct_on(), _direct_dw_on())
+    if not any(on) or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
         return "fft"
     if signal.dtype in _LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
         return "fft"
     n = signal.ndim - 2
     conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
-    hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0], conf[1], conf[2],
-                           groups, "constant" if padding_mode == "zeros" else padding_mode, transposed, conf[3])
-    return "direct" if hit else "fft"
+    for dw, name in ((False, "direct"), (True, "direct-dw")):
+        if on[dw] and _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0], conf[1],
+                                       conf[2], groups, "constant" if padding_mode == "zeros" else padding_mode, transposed,
+                                       conf[3], dw):
+            return name
+    return "fft"
 
 
 def _conv_impl(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,

@@ -105,7 +105,8 @@ class _FFTConvForward(_SpectrumCache, nn.Module):
         cl = self.channels_last
         if F_._direct_hit(False, signal, self.weight, self.bias, self.stride, self.padding, 0, self.dilation, self.groups,
                           padding_mode, cl) is not None:
-            # FFTCONV_DIRECT=1 and a covered layer: the time-domain kernel reads the weight itself (no plan, no spectrum)
+            # FFTCONV_DIRECT=1 / FFTCONV_DIRECT_DW=1 and a covered layer: the time-domain kernel reads the weight itself (no plan,
+            # no spectrum)
             return F_._fft_conv_impl(signal, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                      self.groups, padding_mode, None, channels_last=cl)
         if isinstance(self.padding, str) or (signal.dtype not in (torch.float32, torch.float64, torch.complex64)
@@ -157,7 +158,7 @@ class _FFTConvTransposeForward(_SpectrumCache, nn.Module):
                                                    channels_last=cl)
         if F_._direct_hit(True, signal, self.weight, self.bias, self.stride, self.padding, self.output_padding, self.dilation,
                           self.groups, "constant", cl) is not None:
-            return cast()      # FFTCONV_DIRECT=1 and a covered layer: the functional runs the time-domain kernel
+            return cast()      # FFTCONV_DIRECT=1 / FFTCONV_DIRECT_DW=1 and a covered layer: the functional runs the time-domain kernel
         if signal.dtype in F_._LOW_PRECISION and not F_._half_native(signal, self.weight, self.bias):
             return cast()      # half-precision call the kernels do not read and write natively: the functional casts
         try:

@@ -237,6 +237,22 @@ int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const void* dy, flo
 int fc_conv_direct_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
 int fc_conv_direct(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
 
+/* Direct depthwise forward (ABI 7 extension: two new entry points): the sum of fc_conv_direct for the layers it refuses as
+ * depthwise -- a weight (G * m, 1, *k) with one input channel per group and a channel multiplier m = Cout/groups of 1 .. 8
+ * -- on the vector ALU in float32, one chain per output sample (transposed: one per channel of the group, the m of them
+ * added in order).  Operands, dtypes, the stride-1 transposed form (the input gradient of a stride-1 zero-padded
+ * depthwise layer, whose descriptor has Cin = G * m and Cout = G) and the guarantees are those of fc_conv_direct.
+ *   FC_ERR_UNSUPPORTED with text: a weight with more than one input channel per group or m > 8 (fc_conv_direct covers
+ *   both, so every layer either call covers has exactly one of the two), and every refusal of fc_conv_direct but the
+ *   depthwise one; the halo that must fit 160 KiB of LDS is that of one channel forward and of the m channels transposed.
+ * fc_conv_direct_dw_geometry is pure arithmetic: no device is touched.  info words: output tile per axis in tensor order
+ * (3 words, 0 past ndim), taps per block along the last kernel axis (1: the general build, taken exactly when stride or
+ * dilation of the last axis is not 1; else 4 or 8), multiplier slots of the build (1, 2, 4 or 8, >= m; transposed: 1),
+ * workgroups, bytes of LDS per workgroup, runs of 4 outputs per thread of the build.
+ * fc_conv_direct_dw plans for the CURRENT device and launches once on hip_stream.  Asynchronous; allocates nothing. */
+int fc_conv_direct_dw_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
+int fc_conv_direct_dw(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""The direct small-kernel forward and input gradient: ``fc_conv_direct_dw`` on depthwise layers (the
+default) or, with ``--dense``, ``fc_conv_direct`` on the shape list of DESIGN.md 4.5d.  Per shape, 'same' padding, no bias:
+
+  fwd    the no-grad forward of an ``FFTConv2d`` / ``FFTConv3d`` module of its own in ``eval()`` (a training step drops
+         the kernel spectrum that a module caches, and a captured no-grad forward would go on reading it),
+  dx     ``autograd._grad_input`` on dY (the call the backward function makes),
+  step   forward + dX + dW of a second module under FFTCONV_WGRAD_DIRECT=1,
+
+each as  a_set  the route's switch (FFTCONV_DIRECT_DW, ``--dense``: FFTCONV_DIRECT) set to 1,  b_unset  unset on the same
+tree,  d_torch  ``torch.nn.functional.conv2d/3d`` and its autograd.  ``--baseline --root PARENT_CHECKOUT`` times the
+b_unset calls on the package of another checkout (the parent commit: c_parent) in a process of its own.  The row also
+gives the read-once byte roofline of forward and dX, (bytes of x + bytes of y) / 8 TB/s, and the fraction a_set reaches.
+
+The method is that of scripts/wgrad_direct_bench.py (its ``capture`` and ``timed``): every call is captured into a HIP
+graph over rotating buffers that move 600 MiB through a replay, the graphs of a shape are replayed in turn, ``--iters``
+replays in each of ``--rounds`` alternating rounds; reported are the median over all replays per call, the medians of the
+rounds and their spread.  One JSON line per shape is appended to --out.
+
+    python scripts/conv_direct_bench.py [--dense] [--iters 20] [--rounds 3] [--out FILE] [--only SUBSTRING]
+                                        [--baseline [--root PARENT_CHECKOUT]]"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from wgrad_direct_bench import DEV, DW_SHAPES, F32, HBM_BYTES_PER_US, ROTATE_BYTES, capture, timed  # noqa: E402
+
+# (name, batch, cin, cout, groups, spatial, kernel, stride, dtype); padding is kernel // 2 on every axis
+DW = [s for s in DW_SHAPES if "x16" not in s[0]]      # (multiplier 16 is fc_conv_direct's)
+DENSE = [
+    ("3-D B8 8->8 64^3 k3", 8, 8, 8, 1, (64, 64, 64), 3, 1, F32),
+    ("3-D B2 8->8 128^3 k5", 2, 8, 8, 1, (128, 128, 128), 5, 1, F32),
+    ("2-D B16 8->8 512^2 k3", 16, 8, 8, 1, (512, 512), 3, 1, F32),
+    ("2-D dense B4 64->64 128^2 k3", 4, 64, 64, 1, (128, 128), 3, 1, F32),
+    ("2-D B16 8->16 256^2 k3 stride 2", 16, 8, 16, 1, (256, 256), 3, 2, F32),
+    ("2-D B16 8->8 512^2 k31 (refused)", 16, 8, 8, 1, (512, 512), 31, 1, F32),
+    ("2-D B1 16->16 16x8192 k3", 1, 16, 16, 1, (16, 8192), 3, 1, F32),
+]
+
+
+def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline):
+    torch.manual_seed(0)
+    nd = len(size)
+    auto = importlib.import_module(fca.__name__ + ".autograd")
+    fun = importlib.import_module(fca.__name__ + ".functional")
+    tconv = torch.nn.functional.conv2d if nd == 2 else torch.nn.functional.conv3d
+    es = torch.empty(0, dtype=dtype).element_size()
+    out = tuple((n + 2 * (k // 2) - k) // s + 1 for n in size)
+    io_bytes = B * (ci * torch.Size(size).numel() + co * torch.Size(out).numel()) * es
+    nbuf = max(2, min(8, -(-ROTATE_BYTES // io_bytes)))
+    xs = [torch.randn((B, ci) + size, device=DEV).to(dtype) for _ in range(nbuf)]
+    gys = [torch.randn((B, co) + out, device=DEV).to(dtype) for _ in range(nbuf)]
+    make = lambda: (fca.FFTConv2d if nd == 2 else fca.FFTConv3d)(ci, co, k, stride=s, padding=k // 2, groups=g,  # noqa: E731
+                                                                bias=False).to(DEV).to(dtype)
+    infer, train = make().eval(), make()
+    w = train.weight.detach()
+    conf = ((s,) * nd, (k // 2,) * nd, (1,) * nd, g, "constant")
+    xg = [x.detach().requires_grad_() for x in xs]
+    row = {"shape": name, "dtype": str(dtype).replace("torch.", ""), "B": B, "cin": ci, "cout": co, "groups": g, "size": list(size),
+           "k": k, "stride": s, "buffers": nbuf, "device": torch.cuda.get_device_name(0), "iters": iters, "rounds": rounds,
+           "knob": knob, "mode": "baseline" if baseline else "direct", "roofline_us": round(io_bytes / HBM_BYTES_PER_US, 1)}
+
+    def under(value, fn):
+        def step():
+            for var, v in ((knob, value), ("FFTCONV_WGRAD_DIRECT", "1")):
+                os.environ.pop(var, None) if v is None else os.environ.__setitem__(var, v)
+            return fn()
+        return step
+
+    def fwd():
+        with torch.no_grad():
+            return [infer(x) for x in xs]
+
+    def dx():
+        with torch.no_grad():
+            return [auto._grad_input(gy, w, size, *conf) for gy in gys]
+
+    def torch_step():
+        return [torch.autograd.grad(tconv(x, train.weight, None, s, k // 2, 1, g), (x, train.weight), gy) for x, gy in zip(xg, gys)]
+
+    steps = {}
+    for key, value in ({"c_parent": None} if baseline else {"a_set": "1", "b_unset": None}).items():
+        steps[key + "_fwd"] = under(value, fwd)
+        steps[key + "_dx"] = under(value, dx)
+        steps[key + "_step"] = under(value, lambda: [torch.autograd.grad(train(x), (x, train.weight), gy) for x, gy in zip(xg, gys)])
+        if hasattr(fun, "conv_route"):
+            row[key + "_routes"] = under(value, lambda: [fun.conv_route(xs[0], tuple(w.shape), *conf[:4]),
+                                                         auto.dx_route(xs[0], tuple(w.shape), *conf)])()
+    if not baseline:
+        tdx = torch.nn.grad.conv2d_input if nd == 2 else torch.nn.grad.conv3d_input
+        steps["d_torch_fwd"] = lambda: [tconv(x, w, None, s, k // 2, 1, g) for x in xs]
+        steps["d_torch_dx"] = lambda: [tdx(x.shape, w, gy, s, k // 2, 1, g) for x, gy in zip(xs, gys)]
+        steps["d_torch_step"] = torch_step
+    graphs = {}
+    for key, fn in steps.items():
+        try:
+            graphs[key] = capture(fn)
+        except Exception as exc:       # (a step that cannot run or be captured is reported, the others are still timed)
+            row[key + "_us"] = None
+            row[key + "_note"] = f"not captured: {str(exc)[:160]}"
+            torch.cuda.synchronize()
+    per_round, samples = {key: [] for key in graphs}, {key: [] for key in graphs}
+    for _ in range(rounds):
+        this = {key: [] for key in graphs}
+        for _ in range(iters):
+            for key, gr in graphs.items():          # in turn
+                this[key].append(timed(gr) / nbuf)
+        for key, vals in this.items():
+            per_round[key].append(round(statistics.median(vals), 1))
+            samples[key] += vals
+    for key, vals in samples.items():
+        row[key + "_us"] = round(statistics.median(vals), 1)
+        row[key + "_rounds_us"] = per_round[key]
+        row[key + "_spread_us"] = round(max(per_round[key]) - min(per_round[key]), 1)
+    for what in ("fwd", "dx", "step"):
+        if row.get(f"a_set_{what}_us") and row.get(f"b_unset_{what}_us"):
+            row[f"b_over_a_{what}"] = round(row[f"b_unset_{what}_us"] / row[f"a_set_{what}_us"], 2)
+            if what != "step":
+                row[f"a_roofline_fraction_{what}"] = round(row["roofline_us"] / row[f"a_set_{what}_us"], 3)
+    os.environ.pop(knob, None)
+    os.environ.pop("FFTCONV_WGRAD_DIRECT", None)
+    return row
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--dense", action="store_true", help="fc_conv_direct under FFTCONV_DIRECT on the shapes of DESIGN 4.5d")
+    ap.add_argument("--out", default=None, help="default: profiles/conv_direct_dw.jsonl, with --dense profiles/conv_direct.jsonl")
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    help="the checkout whose fft_conv_pytorch_amd package is timed (default: this tree)")
+    a = ap.parse_args()
+    a.out = a.out or os.path.join("profiles", "conv_direct.jsonl" if a.dense else "conv_direct_dw.jsonl")
+    sys.path.insert(0, os.path.abspath(a.root))
+    import fft_conv_pytorch_amd as fca
+    assert os.path.abspath(fca.__file__).startswith(os.path.abspath(a.root)), fca.__file__
+    for shape in (DENSE if a.dense else DW):
+        if a.only and a.only not in shape[0]:
+            continue
+        res = run_shape(fca, "FFTCONV_DIRECT" if a.dense else "FFTCONV_DIRECT_DW", *shape, a.iters, a.rounds, a.baseline)
+        line = json.dumps(res)
+        print(line, flush=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+        torch.cuda.empty_cache()

@@ -106,7 +106,8 @@ def _grad_input(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilat
 
 def _grad_input_direct(grad: Tensor, weight: Tensor, in_spatial, stride, padding, dilation, groups, padding_mode,
                        channels_last: bool = False, native: bool = False) -> Optional[Tensor]:
-    """dX of a stride-1 layer with zero padding by ``fc_conv_direct`` (FFTCONV_DIRECT=1) or, a depthwise layer, by
+    """dX of a stride-1 layer with zero padding by ``fc_conv_direct`` (FFTCONV_DIRECT=1; 16-bit tensors under
+    FFTCONV_DIRECT_BODY=h16: by ``fc_conv_direct_h16``) or, a depthwise layer, by
     ``fc_conv_direct_dw`` (FFTCONV_DIRECT_DW=1): the stride-1 transposed
     convolution of dY, the weight (Cout, Cin/g, *k) read where it lies with the channel roles exchanged and the taps
     flipped.  None where the call keeps the transposed FFT plan (``dx_route`` "plan")."""
@@ -121,7 +122,8 @@ def _grad_input_direct(grad: Tensor, weight: Tensor, in_spatial, stride, padding
 def dx_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> str:
     """The route ``_grad_input`` takes for the dX of this layer on a contiguous dY of x's dtype (launches nothing, creates
     no plan): ``"direct"`` (FFTCONV_DIRECT=1, stride 1, zero padding and a layer ``fc_conv_direct`` covers in its
-    transposed form), ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and the same of ``fc_conv_direct_dw``) or ``"plan"`` (the
+    transposed form), ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a layer
+    ``fc_conv_direct_h16`` covers), ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and the same of ``fc_conv_direct_dw``) or ``"plan"`` (the
     transposed FFT plan).  The arguments are those of ``dw_route``."""
     on = (F_._direct_on(), F_._direct_dw_on())
     if not any(on) or padding_mode != "constant" or any(s != 1 for s in stride) or x.ndim not in (4, 5):
@@ -129,10 +131,11 @@ def dx_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode)
     if x.dtype in F_._LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
         return "plan"
     out = tuple(int(S) + 2 * p - d * (int(k) - 1) for S, p, d, k in zip(x.shape[2:], padding, dilation, wshape[2:]))
-    for dw, name in ((False, "direct"), (True, "direct-dw")):
-        if on[dw] and F_._direct_geometry((int(x.shape[0]), int(wshape[0])) + out, x.dtype, x.device, tuple(wshape),
-                                          tuple(stride), tuple(padding), tuple(dilation), groups, "constant", True, None, dw):
-            return name
+    for dw in (False, True):
+        hit = on[dw] and F_._direct_geometry((int(x.shape[0]), int(wshape[0])) + out, x.dtype, x.device, tuple(wshape),
+                                             tuple(stride), tuple(padding), tuple(dilation), groups, "constant", True, None, dw)
+        if hit:
+            return hit[4]
     return "plan"
 
 

@@ -1,6 +1,8 @@
 // host_direct.cpp -- fc_conv_direct_geometry and fc_conv_direct (include/fftconv_amd.h "Direct forward"): the planner of
 // conv_direct_kernel (conv_direct.hpp) and its launch; fc_conv_direct_dw_geometry and fc_conv_direct_dw ("Direct
-// depthwise forward"): those of conv_direct_dw_kernel (conv_direct_dw.hpp), behind the same validation.  The planners
+// depthwise forward"): those of conv_direct_dw_kernel (conv_direct_dw.hpp), and fc_conv_direct_h16_geometry and
+// fc_conv_direct_h16 ("Direct forward on the 16-bit matrix instructions"): those of conv_direct_h16_kernel
+// (conv_direct_h16.hpp), behind the same validation.  The planners
 // are pure arithmetic on the descriptor and the CU count; a launch call plans again for the current device (the last
 // answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 
 #include "conv_direct.hpp"
 #include "conv_direct_dw.hpp"
+#include "conv_direct_h16.hpp"
 #include "fc_plan.h"
 
 using namespace fc;
@@ -166,6 +169,76 @@ int plan(const fc_desc& c, int cus, Geom& g) {
   return FC_OK;
 }
 
+// The planner of conv_direct_h16_kernel: plan() with input-channel blocks of whole cells of 8 channels, at most
+// kH16MaxCols = 1024 (channel, tap) pairs each (the 16-bit halo is half the size, the first-level chain kH16MaxSteps = 32
+// steps of 32 products), the same candidates, the same preference for two workgroups per CU and the same refusals,
+// float32 tensors besides.  The cycle estimate keeps plan()'s shape and constants, 32 cycles per MFMA among them (the
+// instruction itself is shorter, but its B operand is a KiB of LDS per wave): none of them is measured for this kernel.
+int plan_h16(const fc_desc& c, int cus, Geom& g) {
+  static_assert(kH16MaxCols == 1024 && kH16Cell == 8, "the text below");
+  if (c.dtype == FC_F32 || c.dtype == FC_F64 || c.dtype == FC_C64)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_h16 takes float16 or bfloat16 tensors (no %s)",
+                c.dtype == FC_F32 ? "float32: fc_conv_direct covers it" : c.dtype == FC_F64 ? "float64" : "complex64");
+  if (int st = validate(c, cus, "fc_conv_direct_h16", "a block of 1024 columns holds whole cells of 8 input channels", g)) return st;
+  g.nob = (int)cdiv(g.Cog, kCdRows);
+
+  // candidates: the largest cell blocks of the first 8 even splits of the group's cells, tiles as plan()
+  double best = -1.0;
+  bool best_shared = false;
+  const int cells = (int)cdiv(g.Cig, kH16Cell), cellmax = std::min<int>(cells, kH16MaxCols / kH16Cell / g.taps);
+  int last_cb = 0, tried = 0;
+  for (int n = (int)cdiv(cells, cellmax); n <= cells && tried < 8; ++n) {
+    const int cb = (int)cdiv(cells, n);
+    if (cb == last_cb) continue;
+    last_cb = cb; ++tried;
+    const int cib = cb * kH16Cell, nib = (int)cdiv(g.Cig, cib), steps = (int)cdiv(cb * g.taps, 4);
+    for (int tz = 1; tz <= 8; tz *= 2)
+      for (int ty = 1; ty <= 16; ty *= 2)
+        for (int tx = 1; tx <= 64; tx *= 2) {
+          const int t[3] = {std::min(tz, g.O[0]), std::min(ty, g.O[1]), std::min(tx, g.O[2])};
+          if ((tz > 1 && t[0] < tz && tz / 2 >= g.O[0]) || (ty > 1 && t[1] < ty && ty / 2 >= g.O[1]) ||
+              (tx > 1 && t[2] < tx && tx / 2 >= g.O[2]))
+            continue;      // (the same clipped tile as a smaller candidate)
+          const int P = t[0] * t[1] * t[2];
+          if (P > kCdMaxPos) continue;
+          int npt = 1;
+          while (kCdWaves * npt * 16 < P) npt *= 2;
+          int64_t hv = 1, ntiles = 1;
+          for (int a = 0; a < 3; ++a) {
+            hv *= (int64_t)(t[a] - 1) * g.stride[a] + (int64_t)(g.k[a] - 1) * g.dil[a] + 1;
+            ntiles *= cdiv(g.O[a], t[a]);
+            if (hv > kLdsBudget) break;
+          }
+          if (hv > kLdsBudget) continue;
+          const int64_t lds = 16 * ((int64_t)steps * (kH16WPitch + 1) + cb * hv);      // wl, cbl (4 ints a step), xl
+          if (lds > kLdsBudget) continue;
+          const bool shared = lds <= kLdsShared && npt < kCdMaxPT;      // (the build of 16 tiles per wave: 316 VGPRs, one workgroup per CU)
+          if (best_shared && !shared) continue;
+          const double cost = (double)nib * (double)ntiles * (32.0 * steps * npt + 3000.0 + 0.5 * (cb * (double)hv + 64.0 * steps));
+          if (best < 0 || (shared && !best_shared) || cost < best) {
+            best = cost; best_shared = shared;
+            g.cib = cib; g.nib = nib; g.npt = npt; g.steps = steps; g.P = P; g.lds = lds;
+            for (int a = 0; a < 3; ++a) {
+              g.tile[a] = t[a]; g.ntile[a] = (int)cdiv(g.O[a], t[a]);
+              g.halo[a] = (t[a] - 1) * g.stride[a] + (g.k[a] - 1) * g.dil[a] + 1;
+            }
+          }
+        }
+  }
+  if (best < 0)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_h16: the x samples that one output position reaches through every tap (of a "
+                "cell of 8 channels) do not fit %lld bytes of LDS", (long long)kLdsBudget);
+  if ((c.transposed ? g.Cog : g.Cig) == 1 && (c.transposed ? g.Cig : g.Cog) <= kDepthwiseMaxMultiplier)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_h16 does not run depthwise layers (a weight with one input channel per group "
+                "and %d output channels per group), forward or transposed, as fc_conv_direct", c.transposed ? g.Cig : g.Cog);
+  g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
+  if (g.units >= ((int64_t)1 << 31))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_h16: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+  if (g.units * c.groups * g.nob > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_h16: %lld workgroups exceed the 2^31 of one launch", (long long)(g.units * c.groups * g.nob));
+  return FC_OK;
+}
+
 // The depthwise planner: the layer's weight must have one input channel per group and a multiplier of at most 8, the
 // set plan() refuses.  Tiles are powers of two clipped to the output, at most 256 * NR runs of 4 outputs (NR: runs per
 // thread of the build, 8 / multiplier slots).  The one with the smallest cycle estimate of the launch wins among those
@@ -235,6 +308,24 @@ int plan_dw(const fc_desc& c, int cus, Geom& g) {
   return FC_OK;
 }
 
+// The kernel arguments of a plan()- or plan_h16()-planned launch (conv_direct_kernel and conv_direct_h16_kernel share the struct)
+ConvDirectArgs direct_args(const fc_desc& c, const Geom& g, const void* x, const void* weight, const void* bias, void* y) {
+  ConvDirectArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.w = weight; a.bias = bias; a.y = y;
+  for (int i = 0; i < 3; ++i) {
+    a.map[i] = AxisMap{g.S[i], g.pad[i], c.padding_mode, 1};
+    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.stride[i] = g.stride[i]; a.dil[i] = g.dil[i];
+    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
+  }
+  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
+  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
+  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
+  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
+  a.io = c.dtype; a.transposed = c.transposed ? 1 : 0;
+  return a;
+}
+
 }  // namespace
 
 extern "C" int fc_conv_direct_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
@@ -259,22 +350,9 @@ extern "C" int fc_conv_direct(const fc_desc* desc, const void* x, const void* we
     if (int st = plan(*desc, cus, last.g)) return st;
     last.d = *desc; last.cus = cus; last.set = true;
   }
-  const Geom& g = last.g;
-  const fc_desc& c = *desc;
-  ConvDirectArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x = x; a.w = weight; a.bias = bias; a.y = y;
-  for (int i = 0; i < 3; ++i) {
-    a.map[i] = AxisMap{g.S[i], g.pad[i], c.padding_mode, 1};
-    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.stride[i] = g.stride[i]; a.dil[i] = g.dil[i];
-    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
-  }
-  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
-  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
-  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
-  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
-  a.io = c.dtype; a.transposed = c.transposed ? 1 : 0;
-  FC_HIP(conv_direct_launch(a, g.npt, g.units * c.groups * g.nob, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
+  const ConvDirectArgs a = direct_args(*desc, last.g, x, weight, bias, y);
+  FC_HIP(conv_direct_launch(a, last.g.npt, last.g.units * desc->groups * last.g.nob, (size_t)last.g.lds,
+                            static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }
 
@@ -318,5 +396,33 @@ extern "C" int fc_conv_direct_dw(const fc_desc* desc, const void* x, const void*
   a.vec = reinterpret_cast<uintptr_t>(y) % 16 == 0 && g.O[2] % kDwR == 0 && (g.tile[2] % kDwR == 0 || g.ntile[2] == 1);
   a.io = c.dtype;
   FC_HIP(conv_direct_dw_launch(a, g.kxb, c.transposed ? 1 : 0, g.units * c.groups, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_h16_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
+  if (!desc || !info) return fail(FC_ERR_INVALID, "null argument");
+  Geom g;
+  if (int st = plan_h16(*desc, compute_units, g)) return st;
+  for (int i = 0; i < 3; ++i) info[i] = i < desc->ndim ? g.tile[g.ax0 + i] : 0;
+  info[3] = std::min(g.Cog, kCdRows); info[4] = std::min(g.cib, g.Cig); info[5] = g.nob; info[6] = g.nib; info[7] = g.lds;
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_h16(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream) {
+  if (!desc || !x || !weight || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward: a stale sticky error of an earlier call is not this call's)
+  int cus = 0;
+  if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
+  // the plan of the last call of this thread, while descriptor and CU count are what they were
+  struct Last { fc_desc d; int cus; Geom g; bool set; };
+  static thread_local Last last = {};
+  if (!last.set || std::memcmp(&last.d, desc, sizeof(fc_desc)) || last.cus != cus) {
+    last.set = false;
+    if (int st = plan_h16(*desc, cus, last.g)) return st;
+    last.d = *desc; last.cus = cus; last.set = true;
+  }
+  const ConvDirectArgs a = direct_args(*desc, last.g, x, weight, bias, y);
+  FC_HIP(conv_direct_h16_launch(a, last.g.npt, last.g.units * desc->groups * last.g.nob, (size_t)last.g.lds,
+                                static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

@@ -378,7 +378,8 @@ def _needs_grad(*tensors) -> bool:
 
 # ---- the direct small-kernel route (FFTCONV_DIRECT=1; ``fc_conv_direct``, csrc/conv_direct.hpp)
 _DIRECT_IO = {torch.float32: 0, torch.float16: 2, torch.bfloat16: 3}      # fc_dtype code of x, weight, bias and y
-# (shapes, hyper-parameters, device, dtype, CU count) -> (descriptor, geometry words, shape of y), False where refused
+# (shapes, hyper-parameters, device, dtype, CU count, depthwise, body) -> (descriptor, geometry words, shape of y, launch,
+# route name), False where refused
 _DIRECT_GEOMETRY: "collections.OrderedDict[tuple, object]" = collections.OrderedDict()
 _DEVICE_CUS: dict = {}
 
@@ -396,9 +397,18 @@ def _direct_dw_on() -> bool:
     return os.environ.get("FFTCONV_DIRECT_DW", "0") == "1"
 
 
+def _direct_body() -> str:
+    """FFTCONV_DIRECT_BODY (read per call): "h16" takes the float16 / bfloat16 calls of FFTCONV_DIRECT=1 that
+    ``fc_conv_direct_h16`` covers from the 16-bit matrix instructions (csrc/conv_direct_h16.hpp; route
+    "direct-h16"); unset, "f32" or anything else leaves every call the call it is without the variable.  Opt-in: the
+    float32 sums run in another order, so the last bit of a 16-bit y or dX may change."""
+    return "h16" if os.environ.get("FFTCONV_DIRECT_BODY", "f32") == "h16" else "f32"
+
+
 def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, groups, padding_mode, transposed=False,
                      output_padding=None, dw=False):
-    """(descriptor, geometry words, shape of y, launch) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``) for a signal
+    """(descriptor, geometry words, shape of y, launch, route name) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``;
+    16-bit tensors under FFTCONV_DIRECT_BODY=h16: of ``fc_conv_direct_h16`` where it covers the layer) for a signal
     of ``shape`` on ``device``, None where the
     library refuses the layer (1-D, float64, complex64, more than 128 taps, depthwise, a strided transposed layer, ...) or
     the arguments do not describe a layer.  Arithmetic only: ``fc_conv_direct_geometry`` touches no device; the CU count is
@@ -423,8 +433,9 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
     if cus is None:
         cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
         _DEVICE_CUS[device] = cus
+    body = _direct_body() if not dw and dtype in _LOW_PRECISION else "f32"
     key = (tuple(shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, bool(transposed), output_padding,
-           device, dtype, cus, bool(dw))
+           device, dtype, cus, bool(dw), body)
     hit = _DIRECT_GEOMETRY.get(key)
     if hit is None:
         hit = False
@@ -433,13 +444,22 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
                                      tuple(int(v) for v in wshape[2:]), stride, padding, dilation,
                                      _native.PAD_MODES[padding_mode], _DIRECT_IO[dtype], transposed=transposed,
                                      output_padding=output_padding)
-            geom = (_native.conv_direct_dw_geometry if dw else _native.conv_direct_geometry)(desc, cus)
+            name, launch = ("direct-dw", _native.conv_direct_dw) if dw else ("direct", _native.conv_direct)
+            geom = None
+            if body == "h16":
+                try:
+                    geom = _native.conv_direct_h16_geometry(desc, cus)
+                    name, launch = "direct-h16", _native.conv_direct_h16
+                except NotImplementedError:
+                    pass      # (the float32 body takes what it covers, as without the variable)
+            if geom is None:
+                geom = (_native.conv_direct_dw_geometry if dw else _native.conv_direct_geometry)(desc, cus)
             if transposed:      # (stride 1, no output padding: the library refuses the rest)
                 out = tuple(int(S) - 2 * p + d * (int(k) - 1) for S, p, d, k in zip(shape[2:], padding, dilation, wshape[2:]))
             else:
                 out = tuple((int(S) + 2 * p - d * (int(k) - 1) - 1) // s + 1
                             for S, p, d, k, s in zip(shape[2:], padding, dilation, wshape[2:], stride))
-            hit = (desc, geom, (int(shape[0]), cout) + out, _native.conv_direct_dw if dw else _native.conv_direct)
+            hit = (desc, geom, (int(shape[0]), cout) + out, launch, name)
         except (NotImplementedError, ValueError, TypeError):
             pass      # (refused, or not a layer: the FFT route takes the call and says what is wrong with it)
         _DIRECT_GEOMETRY[key] = hit
@@ -483,9 +503,9 @@ def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_
 
 
 def _direct_run(hit, signal: Tensor, kernel: Tensor, bias: Optional[Tensor]) -> Tensor:
-    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
+    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` / ``fc_conv_direct_h16`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
     no spectrum."""
-    desc, _, shape, launch = hit
+    desc, _, shape, launch, _ = hit
     signal, kernel = signal.detach(), kernel.detach().contiguous()
     bias = None if bias is None else bias.detach().contiguous()
     with torch.cuda.device(signal.device):
@@ -499,6 +519,7 @@ def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, gr
                channels_last: bool = False, transposed: bool = False, output_padding=0) -> str:
     """The route the forward of ``fft_conv`` (``transposed``: of ``fft_conv_transpose``) takes for this signal and a
     kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers),
+    ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a call ``fc_conv_direct_h16`` covers),
     ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and a call ``fc_conv_direct_dw`` covers) or ``"fft"``.  Arithmetic only: launches
     nothing, creates no plan."""
     on = (_direct_on(), _direct_dw_on())
@@ -508,11 +529,12 @@ def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, gr
         return "fft"
     n = signal.ndim - 2
     conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
-    for dw, name in ((False, "direct"), (True, "direct-dw")):
-        if on[dw] and _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0], conf[1],
-                                       conf[2], groups, "constant" if padding_mode == "zeros" else padding_mode, transposed,
-                                       conf[3], dw):
-            return name
+    for dw in (False, True):
+        hit = on[dw] and _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0],
+                                          conf[1], conf[2], groups, "constant" if padding_mode == "zeros" else padding_mode,
+                                          transposed, conf[3], dw)
+        if hit:
+            return hit[4]
     return "fft"
 
 

@@ -253,6 +253,22 @@ int fc_conv_direct(const fc_desc* desc, const void* x, const void* weight, const
 int fc_conv_direct_dw_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
 int fc_conv_direct_dw(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
 
+/* Direct forward on the 16-bit matrix instructions (ABI 7 extension: two new entry points): the sum of fc_conv_direct for
+ * FC_F16 / FC_BF16 tensors on v_mfma_f32_16x16x32_f16 / _bf16.  Nothing is widened: the products of two 16-bit values are
+ * exact in the float32 accumulator, so y is the float32 sum of fc_conv_direct's products in another order, rounded once.
+ * Operands, the stride-1 transposed form and the guarantees (every sample of y written exactly once, nothing else
+ * written, equal calls give equal bits) are those of fc_conv_direct.  A workgroup reduces blocks of whole cells of 8
+ * input channels, at most 1024 (channel, tap) pairs per block: a first-level chain of 32 MFMA steps of 32 products.
+ *   FC_ERR_UNSUPPORTED with text: FC_F32 (fc_conv_direct covers it) and every refusal of fc_conv_direct, depthwise
+ *   layers included; the halo that must fit 160 KiB of LDS is that of one cell of 8 channels in 16 bits.
+ * fc_conv_direct_h16_geometry is pure arithmetic: no device is touched.  info words as fc_conv_direct_geometry's: output
+ * tile per axis (3 words, 0 past ndim), output channels per workgroup (<= 16), input channels per block (a multiple of 8,
+ * or Cin/groups where one block holds the group; times the taps <= 1024), blocks of output channels per group, blocks
+ * of input channels per group, bytes of LDS per workgroup.
+ * fc_conv_direct_h16 plans for the CURRENT device and launches once on hip_stream.  Asynchronous; allocates nothing. */
+int fc_conv_direct_h16_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
+int fc_conv_direct_h16(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

@@ -9,7 +9,9 @@ default) or, with ``--dense``, ``fc_conv_direct`` on the shape list of DESIGN.md
 
 each as  a_set  the route's switch (FFTCONV_DIRECT_DW, ``--dense``: FFTCONV_DIRECT) set to 1,  b_unset  unset on the same
 tree,  d_torch  ``torch.nn.functional.conv2d/3d`` and its autograd.  ``--baseline --root PARENT_CHECKOUT`` times the
-b_unset calls on the package of another checkout (the parent commit: c_parent) in a process of its own.  The row also
+b_unset calls on the package of another checkout (the parent commit: c_parent) in a process of its own.  ``--h16`` times ``fc_conv_direct_h16`` on the first five dense shapes in bfloat16 and the
+64 -> 64 shape in float16 too, fwd and dx only:  a_set  FFTCONV_DIRECT=1 FFTCONV_DIRECT_BODY=h16,  a1_f32body  FFTCONV_DIRECT=1
+alone (the float32 MFMA body on the same tensors),  b_unset  and  d_torch.  The row also
 gives the read-once byte roofline of forward and dX, (bytes of x + bytes of y) / 8 TB/s, and the fraction a_set reaches.
 
 The method is that of scripts/wgrad_direct_bench.py (its ``capture`` and ``timed``): every call is captured into a HIP
@@ -17,7 +19,7 @@ graph over rotating buffers that move 600 MiB through a replay, the graphs of a 
 replays in each of ``--rounds`` alternating rounds; reported are the median over all replays per call, the medians of the
 rounds and their spread.  One JSON line per shape is appended to --out.
 
-    python scripts/conv_direct_bench.py [--dense] [--iters 20] [--rounds 3] [--out FILE] [--only SUBSTRING]
+    python scripts/conv_direct_bench.py [--dense | --h16] [--iters 20] [--rounds 3] [--out FILE] [--only SUBSTRING]
                                         [--baseline [--root PARENT_CHECKOUT]]"""
 import argparse
 import importlib
@@ -42,9 +44,11 @@ DENSE = [
     ("2-D B16 8->8 512^2 k31 (refused)", 16, 8, 8, 1, (512, 512), 31, 1, F32),
     ("2-D B1 16->16 16x8192 k3", 1, 16, 16, 1, (16, 8192), 3, 1, F32),
 ]
+H16 = [s[:-1] + (torch.bfloat16,) for s in DENSE[:5]] + [DENSE[3][:-1] + (torch.float16,)]
+KNOBS = ("FFTCONV_DIRECT", "FFTCONV_DIRECT_DW", "FFTCONV_DIRECT_BODY", "FFTCONV_WGRAD_DIRECT")
 
 
-def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline):
+def run_shape(fca, variants, whats, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline):
     torch.manual_seed(0)
     nd = len(size)
     auto = importlib.import_module(fca.__name__ + ".autograd")
@@ -64,11 +68,12 @@ def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, b
     xg = [x.detach().requires_grad_() for x in xs]
     row = {"shape": name, "dtype": str(dtype).replace("torch.", ""), "B": B, "cin": ci, "cout": co, "groups": g, "size": list(size),
            "k": k, "stride": s, "buffers": nbuf, "device": torch.cuda.get_device_name(0), "iters": iters, "rounds": rounds,
-           "knob": knob, "mode": "baseline" if baseline else "direct", "roofline_us": round(io_bytes / HBM_BYTES_PER_US, 1)}
+           "knob": variants, "mode": "baseline" if baseline else "direct", "roofline_us": round(io_bytes / HBM_BYTES_PER_US, 1)}
 
-    def under(value, fn):
+    def under(env, fn):
         def step():
-            for var, v in ((knob, value), ("FFTCONV_WGRAD_DIRECT", "1")):
+            for var in KNOBS:
+                v = {"FFTCONV_WGRAD_DIRECT": "1", **env}.get(var)
                 os.environ.pop(var, None) if v is None else os.environ.__setitem__(var, v)
             return fn()
         return step
@@ -85,7 +90,7 @@ def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, b
         return [torch.autograd.grad(tconv(x, train.weight, None, s, k // 2, 1, g), (x, train.weight), gy) for x, gy in zip(xg, gys)]
 
     steps = {}
-    for key, value in ({"c_parent": None} if baseline else {"a_set": "1", "b_unset": None}).items():
+    for key, value in variants.items():
         steps[key + "_fwd"] = under(value, fwd)
         steps[key + "_dx"] = under(value, dx)
         steps[key + "_step"] = under(value, lambda: [torch.autograd.grad(train(x), (x, train.weight), gy) for x, gy in zip(xg, gys)])
@@ -97,6 +102,7 @@ def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, b
         steps["d_torch_fwd"] = lambda: [tconv(x, w, None, s, k // 2, 1, g) for x in xs]
         steps["d_torch_dx"] = lambda: [tdx(x.shape, w, gy, s, k // 2, 1, g) for x, gy in zip(xs, gys)]
         steps["d_torch_step"] = torch_step
+    steps = {key: fn for key, fn in steps.items() if key.rsplit("_", 1)[1] in whats}
     graphs = {}
     for key, fn in steps.items():
         try:
@@ -119,12 +125,14 @@ def run_shape(fca, knob, name, B, ci, co, g, size, k, s, dtype, iters, rounds, b
         row[key + "_rounds_us"] = per_round[key]
         row[key + "_spread_us"] = round(max(per_round[key]) - min(per_round[key]), 1)
     for what in ("fwd", "dx", "step"):
+        if row.get(f"a_set_{what}_us") and row.get(f"a1_f32body_{what}_us"):
+            row[f"a1_over_a_{what}"] = round(row[f"a1_f32body_{what}_us"] / row[f"a_set_{what}_us"], 2)
         if row.get(f"a_set_{what}_us") and row.get(f"b_unset_{what}_us"):
             row[f"b_over_a_{what}"] = round(row[f"b_unset_{what}_us"] / row[f"a_set_{what}_us"], 2)
             if what != "step":
                 row[f"a_roofline_fraction_{what}"] = round(row["roofline_us"] / row[f"a_set_{what}_us"], 3)
-    os.environ.pop(knob, None)
-    os.environ.pop("FFTCONV_WGRAD_DIRECT", None)
+    for var in KNOBS:
+        os.environ.pop(var, None)
     return row
 
 
@@ -133,20 +141,25 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--dense", action="store_true", help="fc_conv_direct under FFTCONV_DIRECT on the shapes of DESIGN 4.5d")
-    ap.add_argument("--out", default=None, help="default: profiles/conv_direct_dw.jsonl, with --dense profiles/conv_direct.jsonl")
+    ap.add_argument("--h16", action="store_true", help="fc_conv_direct_h16 against fc_conv_direct on 16-bit tensors (DESIGN 4.5f)")
+    ap.add_argument("--out", default=None, help="default: profiles/conv_direct_dw.jsonl, --dense: conv_direct.jsonl, --h16: conv_direct_h16.jsonl")
     ap.add_argument("--only", default=None)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose fft_conv_pytorch_amd package is timed (default: this tree)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join("profiles", "conv_direct.jsonl" if a.dense else "conv_direct_dw.jsonl")
+    a.out = a.out or os.path.join("profiles", "conv_direct_h16.jsonl" if a.h16 else "conv_direct.jsonl" if a.dense else "conv_direct_dw.jsonl")
+    knob = "FFTCONV_DIRECT_DW" if not (a.dense or a.h16) else "FFTCONV_DIRECT"
+    variants = {"c_parent": {}} if a.baseline else {"a_set": {knob: "1"}, "b_unset": {}}
+    if a.h16:
+        variants = {"a_set": {knob: "1", "FFTCONV_DIRECT_BODY": "h16"}, "a1_f32body": {knob: "1"}, "b_unset": {}}
     sys.path.insert(0, os.path.abspath(a.root))
     import fft_conv_pytorch_amd as fca
     assert os.path.abspath(fca.__file__).startswith(os.path.abspath(a.root)), fca.__file__
-    for shape in (DENSE if a.dense else DW):
+    for shape in (H16 if a.h16 else DENSE if a.dense else DW):
         if a.only and a.only not in shape[0]:
             continue
-        res = run_shape(fca, "FFTCONV_DIRECT" if a.dense else "FFTCONV_DIRECT_DW", *shape, a.iters, a.rounds, a.baseline)
+        res = run_shape(fca, variants, ("fwd", "dx") if a.h16 else ("fwd", "dx", "step"), *shape, a.iters, a.rounds, a.baseline)
         line = json.dumps(res)
         print(line, flush=True)
         with open(a.out, "a") as f:

@@ -66,13 +66,21 @@ constexpr unsigned segments = 16;    // a segment of the taps of a long kernel: 
 // (a pending store's registers are reused), i.e. a wait for every output store of the first item.
 constexpr unsigned stamps = 32;
 constexpr unsigned half_io = 64;     // x and y are 16-bit (Io<IO_H16>: float16 or bfloat16 by the launch's `io` code)
+// lower_rows (the four-slot dense builds on a P*P tile, segments apart): a tile keeps its first V = T - K_d + 1 outputs, and in the last
+// inverse pass lane o holds the outputs o + P k, k = 0 .. P-1.  Where V <= lower_rows_max_v(P) no row past k = P/2 is
+// ever stored, so the last radix-2 stage of that pass computes the sums of its butterflies alone (plus the one
+// difference that is row P/2: fft_regs<.., LOWER>) and the store code ends at row P/2.  The rows that are stored hold
+// the bits of the full transform.  A plan property (long kernels: K_d >= T/2 - P + 1), hence a build, not a branch.
+constexpr unsigned lower_rows = 128;
+constexpr int lower_rows_max_v(int P) { return (P / 2 + 1) * P; }
 // the combinations that exist: pairs and quads are phase builds on a P*P tile with 8-channel blocks, quads fill
 // a workgroup of four slots and exclude pairs
 constexpr bool valid(unsigned build, int S, int CIB, int NB) {
   const bool packable = (build & phases) && !(build & (depthwise | segments)) && S == 1 && CIB == 8;
   if ((build & pairs) && !packable) return false;
   if ((build & quads) && !(packable && !(build & pairs) && NB == 4)) return false;
-  return build < 2 * half_io;
+  if ((build & lower_rows) && !(!(build & (phases | depthwise | segments)) && S == 1 && NB == 4)) return false;
+  return build < 2 * lower_rows;
 }
 }  // namespace pers
 
@@ -105,6 +113,10 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   // acts on both parts alike, so the mix contracts the packed spectra as they are, Y[o][f] = sum_c H[o][c][f] Z[c][f],
   // without separating the two real spectra first and re-packing them afterwards as the channel pairs need it.
   constexpr bool BPAIR = !(BUILD & (pers::phases | pers::depthwise)) && NB >= 2;
+  // rows k = 0 .. KROWS - 1 of the last pass may be stored (pers::lower_rows: the host takes the build where V allows it)
+  constexpr bool LOWROWS = (BUILD & pers::lower_rows) != 0;
+  constexpr int KROWS = LOWROWS ? P / 2 + 1 : P;
+  static_assert(!LOWROWS || BPAIR, "lower_rows is a batch-pair build");
   constexpr int RING = 2;                   // spectrum register sets of the mix
   using G = Geo<P, S>;
   constexpr int T = G::T;
@@ -737,7 +749,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
       stampi(it, 9);
       // ---------------------------------------------- inverse pass B' + store
       passB_load<G>(v, zseq, tseq);
-      const int j = passB_compute<G, +1>(v, tseq, twB);
+      const int j = passB_compute<G, +1, LOWROWS>(v, tseq, twB);
       if (more) {
         // (requested a whole inverse transform ago: no stall; but behind the stores the next item would have to wait
         // for every one of them to be acknowledged before it may touch its samples)
@@ -782,16 +794,18 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
           const BufRsrc yrB = make_rsrc(io_ptr<IO>(a.y) + ((size_t)bB * a.Cout + crow) * a.Lout, hasB ? ybytes : 0u);
           const unsigned voA = (unsigned)((size_t)pr * a.Lout + (size_t)(t0 + nbase)) * ES;
           const unsigned voB = (unsigned)((size_t)pr * a.Lout + (size_t)(t0B + nbase)) * ES;
-          static_for<0, P / 8>([&](auto bc) {
+          // (lower_rows: the blocks end at row P/2, whose block has no unguarded form)
+          static_for<0, (KROWS + 7) / 8>([&](auto bc) {
             constexpr int k0 = 8 * decltype(bc)::value;
-            if (kb >= k0 + 8) {
+            constexpr int kend = k0 + 8 < KROWS ? k0 + 8 : KROWS;
+            if (kend == k0 + 8 && kb >= k0 + 8) {
               static_for<k0, k0 + 8>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 io.store(scaled(v[k].x), yrA, voA, P * k * ES);
                 io.store(scaled(v[k].y), yrB, voB, P * k * ES);
               });
             } else if (ka >= k0) {
-              static_for<k0, k0 + 8>([&](auto kc) {
+              static_for<k0, kend>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 if (k <= ka) {
                   io.store(scaled(v[k].x), yrA, voA | ((nbase + P * k < limit) ? 0u : 0x80000000u), P * k * ES);

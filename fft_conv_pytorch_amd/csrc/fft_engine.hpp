@@ -198,13 +198,28 @@ __device__ __forceinline__ void bfly(f2& a, f2& b, int q) {
   }
 }
 
+// the sum output of the same butterfly alone: a = a + w*b, b is left as it is (q != 0)
+template <int DIR>
+__device__ __forceinline__ void bfly_sum(f2& a, const f2& b, int q) {
+  if (q == 16) {
+    a = (DIR > 0) ? add_pi(a, b) : add_mi(a, b);
+  } else {
+    const float c = cos64(q), s = (DIR > 0) ? sin64(q) : -sin64(q);
+    a = pkfma(mk2(c, c), b, pkfma(mk2(-s, s), b.yx, a));
+  }
+}
+
 // P-point FFT on registers, natural order in, natural order out.  `hook(stage)` runs after every radix-2 stage
 // (stage = 0 .. log2(P)-1 as an integral_constant): the batch-sharing kernel issues a few of the next work item's
 // global loads there, so their issue cost spreads over the butterflies instead of blocking the wave in one burst.
 struct NoHook {
   template <class T> __device__ __forceinline__ void operator()(T) const {}
 };
-template <int P, int DIR, class H = NoHook>
+//
+// LOWER: only the outputs v[0 .. P/2] are produced; v[P/2 + 1 .. P-1] keep their inputs.  The last radix-2 stage then
+// computes the sum t = a + w*b of every butterfly and the difference 2a - t of the first one alone (w = 1: v[P/2]), the
+// same products in the same order as the full transform: for a last inverse pass whose rows past P/2 are never stored.
+template <int P, int DIR, bool LOWER = false, class H = NoHook>
 __device__ __forceinline__ void fft_regs(f2 (&v)[P], H&& hook = H{}) {
 #if FC_DIAG == 8
   if constexpr (P == 32) {          // timing experiment: the 32-point register transforms do nothing
@@ -222,12 +237,15 @@ __device__ __forceinline__ void fft_regs(f2 (&v)[P], H&& hook = H{}) {
 #pragma unroll
     for (int blk = 0; blk < P; blk += len) {
 #pragma unroll
-      for (int j = 0; j < len / 2; ++j) bfly<DIR>(t[blk + j], t[blk + j + len / 2], j * (64 / len));
+      for (int j = 0; j < len / 2; ++j) {
+        if (LOWER && len == P && j > 0) bfly_sum<DIR>(t[j], t[j + len / 2], j * (64 / len));
+        else bfly<DIR>(t[blk + j], t[blk + j + len / 2], j * (64 / len));
+      }
     }
     hook(sc);
   });
 #pragma unroll
-  for (int i = 0; i < P; ++i) v[i] = t[i];
+  for (int i = 0; i < (LOWER ? P / 2 + 1 : P); ++i) v[i] = t[i];
 }
 
 // ---- buffer (SRSRC) loads: one VGPR byte offset + SGPR/constant offset per load ----
@@ -578,8 +596,10 @@ __device__ __forceinline__ void nat_load(f2 (&v)[G::P], const f2* __restrict__ l
 // k of this lane is X[k1 + P*(k + P*j)]   (k1 = tseq >> log2(S)).
 //   twB[r*P + k] = exp(-2*pi*i*r*k/N2) (forward sign): used by the S = 4 split, whose per-lane
 //   twiddles differ between the three non-trivial lanes of a quad (S = 2 uses compile-time roots)
-template <class G, int DIR, class H = NoHook>
+//   LOWER (S = 1 only): fft_regs<.., LOWER> -- the lane's elements k = 0 .. P/2 alone
+template <class G, int DIR, bool LOWER = false, class H = NoHook>
 __device__ __forceinline__ int passB_compute(f2 (&v)[G::P], int tseq, BufRsrc twB, H&& hook = H{}) {
+  static_assert(!LOWER || G::S == 1, "the lane split needs every element");
   if constexpr (G::S == 4) {
     const int r4 = tseq & 3;
     f2 w[G::P];
@@ -590,7 +610,7 @@ __device__ __forceinline__ int passB_compute(f2 (&v)[G::P], int tseq, BufRsrc tw
 #pragma unroll
     for (int k = 1; k < G::P; ++k) v[k] = (DIR > 0) ? cmulc(v[k], w[k]) : cmul(v[k], w[k]);
   } else {
-    fft_regs<G::P, DIR>(v, hook);
+    fft_regs<G::P, DIR, LOWER>(v, hook);
   }
   if constexpr (G::S == 1) {
     return 0;

@@ -199,13 +199,18 @@ constexpr size_t pers_lds_bytes(int nb) { return pers::lds_with_table<FC_P, FC_S
 //   * depthwise phases are neither packed nor profiled;
 //   * phases are packed in quads (ph2 == 2; four slots, not profiled: a profiled quad plan runs the pairs) or in pairs
 //     (ph2 != 0), both on the P*P tiles only;
-//   * the profiling build exists for the plain, the phase and the paired-phase kernel.
+//   * the profiling build exists for the plain, the phase and the paired-phase kernel;
+//   * the four-slot dense builds on the P*P tile (plain, profiling, 16-bit) end their last pass at row P/2
+//     (pers::lower_rows) where the plan keeps no output past it: V <= (P/2 + 1) P, i.e. K_d >= 481 on the 1024-point tile
+//     (a segment is 1025 samples long and never runs on that tile).
 constexpr unsigned kNoBuild = ~0u;
 unsigned pers_build(const Conv1dArgs& c, int nb) {
   const bool h16 = io_is_h16(c.io), ph = c.ph > 1, dg = c.diag != 0;
   if (c.io != 0 && (!h16 || c.segmented || c.stamps)) return kNoBuild;
   const unsigned io = h16 ? pers::half_io : 0u;
   if (c.segmented) return pers::segments | (dg ? pers::depthwise : 0u);
+  if (!ph && !dg && FC_S == 1 && nb == 4 && c.V <= pers::lower_rows_max_v(FC_P))
+    return io | pers::lower_rows | (c.stamps ? pers::stamps : 0u);
   if (ph && dg) return io | pers::phases | pers::depthwise;
   const unsigned st = c.stamps ? pers::stamps : 0u;
   if (ph && FC_S == 1 && c.ph2 == 2 && nb == 4 && !st) return io | pers::phases | pers::quads;
@@ -241,7 +246,8 @@ hipError_t launch_pers(const Conv1dPersArgs& a, int grid, hipStream_t st) {
                              phases | pairs, phases | pairs | stamps, phases | quads,
                              half_io, half_io | depthwise,
                              half_io | phases, half_io | phases | depthwise,
-                             half_io | phases | pairs, half_io | phases | quads>(pers_build(a.c, NB), a, grid, st);
+                             half_io | phases | pairs, half_io | phases | quads,
+                             lower_rows, lower_rows | stamps, lower_rows | half_io>(pers_build(a.c, NB), a, grid, st);
   }
 }
 

@@ -73,14 +73,19 @@ constexpr unsigned half_io = 64;     // x and y are 16-bit (Io<IO_H16>: float16 
 // the bits of the full transform.  A plan property (long kernels: K_d >= T/2 - P + 1), hence a build, not a branch.
 constexpr unsigned lower_rows = 128;
 constexpr int lower_rows_max_v(int P) { return (P / 2 + 1) * P; }
+// early_fetch (the four-slot dense builds on a P*P tile, where reg_twiddles holds): a workgroup's first item requests the
+// second item's samples in FRONT of the barrier that ends its mix, not behind it.  The requests read x, write registers and
+// touch no LDS, so they do not depend on the barrier, and at that point the mix's registers are dead: a wave that finishes
+// its bins early issues them while it would wait for the others.
+constexpr unsigned early_fetch = 256;
 // the combinations that exist: pairs and quads are phase builds on a P*P tile with 8-channel blocks, quads fill
 // a workgroup of four slots and exclude pairs
 constexpr bool valid(unsigned build, int S, int CIB, int NB) {
   const bool packable = (build & phases) && !(build & (depthwise | segments)) && S == 1 && CIB == 8;
   if ((build & pairs) && !packable) return false;
   if ((build & quads) && !(packable && !(build & pairs) && NB == 4)) return false;
-  if ((build & lower_rows) && !(!(build & (phases | depthwise | segments)) && S == 1 && NB == 4)) return false;
-  return build < 2 * lower_rows;
+  if ((build & (lower_rows | early_fetch)) && !(!(build & (phases | depthwise | segments)) && S == 1 && NB == 4)) return false;
+  return build < 2 * early_fetch;
 }
 }  // namespace pers
 
@@ -117,6 +122,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   constexpr bool LOWROWS = (BUILD & pers::lower_rows) != 0;
   constexpr int KROWS = LOWROWS ? P / 2 + 1 : P;
   static_assert(!LOWROWS || BPAIR, "lower_rows is a batch-pair build");
+  constexpr bool EARLY = (BUILD & pers::early_fetch) != 0;   // the second item's samples are requested in front of the mix's last barrier
   constexpr int RING = 2;                   // spectrum register sets of the mix
   using G = Geo<P, S>;
   constexpr int T = G::T;
@@ -151,6 +157,7 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
   constexpr bool REGTW = pers::reg_twiddles<P, S>(BUILD, NB);   // pass-A twiddles in registers, no table in LDS
   f2* twl = lds;
   f2* zbuf = lds + (REGTW ? 0 : TWN);       // [NSEQ][LSEQ], sequence (slot, pair) at slot * NPI + pair
+  static_assert(!EARLY || (REGTW && BPAIR), "early_fetch is a build of the four-slot dense kernel");
   f2* zseq = PH4 ? zbuf + (nb * 8 + pr) * G::LSEQ : zbuf + (nb * NPI + pr) * G::LSEQ;
 
   const PadMap pm = make_padmap(a.pad_mode, a.L);
@@ -728,16 +735,24 @@ __global__ __launch_bounds__(NT, 2) void conv1d_pers_kernel(const Conv1dPersArgs
     }
     }   // dense / depthwise mix
     stampi(it, 6);
+    // gfx9 counts loads and stores in ONE vmcnt: a value first used after later memory instructions went out through
+    // branches gets a full s_waitcnt vmcnt(0).  The bias is therefore declared arrived in front of the fetch (only this
+    // item's spectrum loads are older, all consumed), and the next item's samples right before this item's output stores.
+    // The next item's samples travel from HBM while this item's inverse passes run: requested in front of the mix's last
+    // barrier (early_fetch; stamp 14 splits the requests from the wait at the barrier) or behind it.
+    if constexpr (EARLY) {
+      asm volatile("" : "+v"(bias0), "+v"(bias1));
+      if (more) fetch(wnext, vnext);
+      stampi(it, 14);
+    }
 #if FC_DIAG != 5
     __syncthreads();
 #endif
     stampi(it, 7);
-    // gfx9 counts loads and stores in ONE vmcnt: a value first used after later memory instructions went out through
-    // branches gets a full s_waitcnt vmcnt(0).  The bias is therefore declared arrived here (only this item's spectrum
-    // loads are older, all consumed), and the next item's samples right before this item's output stores.
-    asm volatile("" : "+v"(bias0), "+v"(bias1));
-    // the next item's samples travel from HBM while this item's inverse passes run
-    if (more) fetch(wnext, vnext);
+    if constexpr (!EARLY) {
+      asm volatile("" : "+v"(bias0), "+v"(bias1));
+      if (more) fetch(wnext, vnext);
+    }
     // ------------------------------------------------ inverse pass A'
     if (act_in) {
       nat_load<G>(v, zseq, tseq);

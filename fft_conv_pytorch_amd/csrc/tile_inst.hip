@@ -203,8 +203,13 @@ constexpr size_t pers_lds_bytes(int nb) { return pers::lds_with_table<FC_P, FC_S
 //   * the four-slot dense builds on the P*P tile (plain, profiling, 16-bit) end their last pass at row P/2
 //     (pers::lower_rows) where the plan keeps no output past it: V <= (P/2 + 1) P, i.e. K_d >= 481 on the 1024-point tile
 //     (a segment is 1025 samples long and never runs on that tile).
+// On top of that choice every four-slot dense build on the P*P tile (plain, profiling, 16-bit, with or without the lower
+// rows) requests its second item's samples in front of the mix's last barrier (pers::early_fetch).
 constexpr unsigned kNoBuild = ~0u;
-unsigned pers_build(const Conv1dArgs& c, int nb) {
+constexpr unsigned pers_fetch(unsigned build, int nb) {
+  return (!(build & (pers::phases | pers::depthwise | pers::segments)) && FC_S == 1 && nb == 4) ? pers::early_fetch : 0u;
+}
+static unsigned pers_base_build(const Conv1dArgs& c, int nb) {
   const bool h16 = io_is_h16(c.io), ph = c.ph > 1, dg = c.diag != 0;
   if (c.io != 0 && (!h16 || c.segmented || c.stamps)) return kNoBuild;
   const unsigned io = h16 ? pers::half_io : 0u;
@@ -219,14 +224,18 @@ unsigned pers_build(const Conv1dArgs& c, int nb) {
   if (dg) return io | pers::depthwise;
   return io | st;
 }
+unsigned pers_build(const Conv1dArgs& c, int nb) {
+  const unsigned base = pers_base_build(c, nb);
+  return base == kNoBuild ? kNoBuild : base | pers_fetch(base, nb);
+}
 
-// launches the one of BUILDS that is `build`
+// launches the one of BUILDS, each with the fetch feature it takes at NB slots, that is `build`
 template <int NB, unsigned... BUILDS>
 hipError_t launch_pers_among(unsigned build, const Conv1dPersArgs& a, int grid, hipStream_t st) {
   constexpr int NT = NB * 4 * GG::TS;
   hipError_t e = hipErrorInvalidValue;
   auto launch = [&](auto b) {
-    constexpr unsigned B = decltype(b)::value;
+    constexpr unsigned B = decltype(b)::value | pers_fetch(decltype(b)::value, NB);
     if constexpr (pers::valid(B, FC_S, 8, NB))      // (pairs: only on the P*P tiles; quads: only with four slots)
       if (build == B) e = launch_kernel<conv1d_pers_kernel<FC_P, FC_S, 8, NB, NT, B>>(grid, NT, pers::lds_bytes<FC_P, FC_S>(B, NB), st, a);
   };

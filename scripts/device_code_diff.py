@@ -40,7 +40,7 @@ FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_siz
 # conv1d_pers_kernel's build: the positional parameters behind <P, S, CIB, NB, NT, of the old list (None: not a feature),
 # and the bits of the mask that replaced them (pers:: in conv1d_pers.hpp)
 OLD_PERS = ("phases", None, "depthwise", "segments", "pairs", "stamps", "quads", "half_io")
-NEW_PERS = ("phases", "pairs", "quads", "depthwise", "segments", "stamps", "half_io")
+NEW_PERS = ("phases", "pairs", "quads", "depthwise", "segments", "stamps", "half_io", "lower_rows", "early_fetch")
 
 
 def objects():

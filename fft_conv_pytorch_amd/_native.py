@@ -347,12 +347,12 @@ def wgrad_direct_geometry(desc: FcDesc, compute_units: int) -> dict:
     return dict(zip(WGRAD_DIRECT_INFO_WORDS, (int(v) for v in info)))
 
 
-WGRAD_DIRECT_BODIES = ("mfma", "valu")
+WGRAD_DIRECT_BODIES = ("mfma", "valu", "h16")
 
 
 def wgrad_direct_body(desc: FcDesc, compute_units: int) -> str:
-    """``fc_wgrad_direct_body``: the kernel body ``fc_wgrad_direct`` takes for the layer, ``"mfma"`` or ``"valu"`` (the
-    depthwise body), under FFTCONV_WGRAD_DIRECT_BODY as it is at the call.  Refusals as ``wgrad_direct_geometry``."""
+    """``fc_wgrad_direct_body``: the kernel body ``fc_wgrad_direct`` takes for the layer, ``"mfma"``, ``"valu"`` (the
+    depthwise body) or ``"h16"`` (float16 / bfloat16 layers on the 16-bit MFMAs), under FFTCONV_WGRAD_DIRECT_BODY as it is at the call.  Refusals as ``wgrad_direct_geometry``."""
     lib = load_library()
     body = ctypes.c_int(-1)
     _check(lib, lib.fc_wgrad_direct_body(ctypes.byref(desc), compute_units, ctypes.byref(body)))

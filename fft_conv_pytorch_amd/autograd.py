@@ -360,7 +360,7 @@ def _wgrad_direct_geometry(x: Tensor, wshape, stride, padding, dilation, groups,
 
 def _grad_weight_direct(x: Tensor, grad: Tensor, wshape, stride, padding, dilation, groups, padding_mode):
     """2-D / 3-D dW by ``fc_wgrad_direct`` (FFTCONV_WGRAD_DIRECT=1): the time-domain sum on the matrix pipe (a depthwise
-    layer: on the vector ALU, ``dw_direct_body``), x and dY read where they lie, x through the padding mode.  float32 dW; None where the library does not cover the layer."""
+    layer: on the vector ALU; a 16-bit layer under FFTCONV_WGRAD_DIRECT_BODY=h16: on the 16-bit MFMAs, ``dw_direct_body``), x and dY read where they lie, x through the padding mode.  float32 dW; None where the library does not cover the layer."""
     hit = _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode)
     if hit is None:
         return None
@@ -403,9 +403,10 @@ def dw_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode)
 
 
 def dw_direct_body(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> Optional[str]:
-    """The kernel body of ``fc_wgrad_direct`` for a layer whose ``dw_route`` is ``"direct"``: ``"mfma"``, or ``"valu"``,
+    """The kernel body of ``fc_wgrad_direct`` for a layer whose ``dw_route`` is ``"direct"``: ``"mfma"``, ``"valu"``,
     the depthwise body (one input channel per group; FFTCONV_WGRAD_DIRECT_BODY=mfma / valu overrides the planner's
-    rule).  None for every other route.  Launches nothing."""
+    rule), or ``"h16"``, the 16-bit MFMA body (FFTCONV_WGRAD_DIRECT_BODY=h16: float16 / bfloat16 layers that the rule
+    gives to ``"mfma"``).  None for every other route.  Launches nothing."""
     if dw_route(x, wshape, stride, padding, dilation, groups, padding_mode) != "direct":
         return None
     return _wgrad_direct_geometry(x, wshape, stride, padding, dilation, groups, padding_mode)[2]

@@ -1,6 +1,6 @@
 // host_wgrad.cpp -- fc_wgrad_direct_geometry, fc_wgrad_direct_body and fc_wgrad_direct (include/fftconv_amd.h "Direct
-// weight gradient"): the planner of wgrad_direct_kernel (wgrad_direct.hpp) and of wgrad_direct_dw_kernel
-// (wgrad_direct_dw.hpp), and their two launches.  The planner is pure arithmetic on the descriptor, the CU count,
+// weight gradient"): the planner of wgrad_direct_kernel (wgrad_direct.hpp), of wgrad_direct_dw_kernel
+// (wgrad_direct_dw.hpp) and of wgrad_direct_h16_kernel (wgrad_direct_h16.hpp), and their two launches.  The planner is pure arithmetic on the descriptor, the CU count,
 // FFTCONV_WGRAD_DIRECT_SLICES and FFTCONV_WGRAD_DIRECT_BODY; the launch call plans again for the current device (the
 // last answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "fc_plan.h"
 #include "wgrad_direct_dw.hpp"
+#include "wgrad_direct_h16.hpp"
 
 using namespace fc;
 
@@ -20,7 +21,7 @@ constexpr int64_t kLdsShared = 64 * 1024;       // up to here two workgroups sha
 constexpr int64_t kLdsBudget = 160 * 1024;
 constexpr int kMaxTaps = 128;
 constexpr int kMaxCols = kWgdWaves * kWgdMaxCT * 16;      // columns (input channel, tap) of one workgroup
-enum Body { BODY_MFMA = 0, BODY_VALU = 1 };
+enum Body { BODY_MFMA = 0, BODY_VALU = 1, BODY_H16 = 2 };
 // The largest channel multiplier Cout/g of a layer with Cin/g == 1 that the automatic rule gives to the depthwise
 // body: the largest of 1, 2, 4, 8, 16 at which it was faster than the MFMA body by more than three spreads on
 // B8 C256 56^2 k7 bfloat16 (profiles/wgrad_direct_dw.jsonl).
@@ -38,6 +39,9 @@ struct Geom {
   int body;                  // Body; the depthwise body besides:
   int kxb, nb, nbx, nblk;    // taps per block, blocks of the busiest wave, blocks per kernel row and in all
   int runs, runs64;          // runs of kDwR positions per tile, rounded up to whole waves
+  // the 16-bit MFMA body: slots per phase of a halo row, runs per tile row, rows of a tile and rounded up to 4, samples
+  // per channel of the dY tile, LDS byte offsets
+  int SP, RX, rows, rows4, dyp, off_dy, off_x0, off_x1;
 };
 
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -47,10 +51,11 @@ int lds_bytes(int p4, int cib, int64_t hv, int64_t* out) {
   return *out <= kLdsBudget;
 }
 
-// FFTCONV_WGRAD_DIRECT_BODY: 1 "mfma", 2 "valu", 0 unset or anything else (the automatic rule)
+// FFTCONV_WGRAD_DIRECT_BODY: 1 "mfma", 2 "valu", 3 "h16" (the automatic rule, and the 16-bit MFMA body where that gives a
+// float16 / bfloat16 layer to the MFMA body), 0 unset or anything else (the automatic rule)
 int body_knob() {
   const char* env = getenv("FFTCONV_WGRAD_DIRECT_BODY");
-  return !env ? 0 : !std::strcmp(env, "mfma") ? 1 : !std::strcmp(env, "valu") ? 2 : 0;
+  return !env ? 0 : !std::strcmp(env, "mfma") ? 1 : !std::strcmp(env, "valu") ? 2 : !std::strcmp(env, "h16") ? 3 : 0;
 }
 
 int64_t forced_slices() {
@@ -117,6 +122,76 @@ int plan_dw(const fc_desc& c, int cus, Geom& g) {
   g.slices = (int)slices;
   g.ws = slices * c.out_channels * g.taps * 4;
   return FC_OK;
+}
+
+// Input-channel block, tile and slices of the 16-bit MFMA body (wgrad_direct_h16.hpp) for a validated float16 /
+// bfloat16 layer that plan() gave to the MFMA body; false where no tile fits, and the layer keeps that body.  A tile is
+// tz x ty rows (rounded up to 4: the rows of one MFMA step) of RX whole runs of 8 positions, at most kWghMaxRuns runs.
+// LDS is counted in 16-bit samples: the dY tile of 16 channels with a pitch of 8 (runs + 1), and the halo twice (x0 and
+// the copy one sample to the left), its rows stride[2] phases of SP slots, SP the tile row and the farthest tap's slot
+// shift rounded up to 8.  The cycle estimate has the form and the constants of plan()'s (32 cycles per MFMA, 3000 of
+// exposed latency per unit, half a cycle per staged sample); they were measured for wgrad_direct_kernel, not for this
+// kernel.  Among the candidates that fit 64 KiB, else among those that fit the 160 KiB budget.
+bool plan_h16(const fc_desc& c, int cus, Geom& g) {
+  double best = -1.0;
+  bool best_shared = false;
+  Geom b = g;
+  const int cibmax = std::min<int>(g.Cig, kMaxCols / g.taps);
+  int last_cib = 0, tried = 0;
+  for (int n = (int)cdiv(g.Cig, cibmax); n <= g.Cig && tried < 8; ++n) {
+    const int cib = (int)cdiv(g.Cig, n);
+    if (cib == last_cib) continue;
+    last_cib = cib; ++tried;
+    const int nib = (int)cdiv(g.Cig, cib);
+    int ct = 1;
+    while (kWgdWaves * ct * 16 < cib * g.taps) ct *= 2;
+    for (int tz = 1; tz <= 8; tz *= 2)
+      for (int ty = 1; ty <= 16; ty *= 2)
+        for (int rx = 1; rx <= kWghMaxRX; rx *= 2) {
+          const int txr = rx * kWghRun;
+          const int t[3] = {std::min(tz, g.O[0]), std::min(ty, g.O[1]), std::min(txr, g.O[2])};
+          if ((tz > 1 && tz / 2 >= g.O[0]) || (ty > 1 && ty / 2 >= g.O[1]) || (rx > 1 && txr / 2 >= g.O[2]))
+            continue;      // (the same clipped tile as a smaller candidate)
+          const int rows = t[0] * t[1], rows4 = (rows + 3) & ~3, runs = rows4 * rx;
+          if (runs > kWghMaxRuns) continue;
+          const int64_t sp = ((int64_t)txr + (int64_t)(g.k[2] - 1) * g.dil[2] / g.stride[2] + 7) & ~(int64_t)7;
+          int64_t halo[3], ntiles = 1;
+          for (int a = 0; a < 3; ++a) {
+            halo[a] = (int64_t)(t[a] - 1) * g.stride[a] + (int64_t)(g.k[a] - 1) * g.dil[a] + 1;
+            ntiles *= cdiv(g.O[a], t[a]);
+          }
+          halo[2] = sp * g.stride[2];
+          if (halo[0] > kLdsBudget || halo[1] > kLdsBudget || halo[2] > kLdsBudget || halo[0] * halo[1] > kLdsBudget) continue;
+          const int64_t hv = halo[0] * halo[1] * halo[2], dyp = (int64_t)kWghRun * (runs + 1);
+          if (hv > kLdsBudget) continue;
+          const int64_t off_dy = kWghHeadBytes + 4 * rows4, off_x0 = off_dy + 2 * kWgdRows * dyp;
+          const int64_t off_x1 = off_x0 + 2 * cib * hv + 16, lds = off_x1 + 2 * cib * hv + 16;
+          if (lds > kLdsBudget) continue;
+          const bool shared = lds <= kLdsShared;
+          if (best_shared && !shared) continue;
+          const double cost = (double)nib * (double)ntiles * (32.0 * (runs / 4) * ct + 3000.0 + 0.5 * (cib * (double)hv + 16.0 * kWghRun * runs));
+          if (best < 0 || (shared && !best_shared) || cost < best) {
+            best = cost; best_shared = shared;
+            b.cib = cib; b.nib = nib; b.ct = ct; b.P = rows * txr; b.P4 = runs * kWghRun; b.lds = lds;
+            b.SP = (int)sp; b.RX = rx; b.rows = rows; b.rows4 = rows4; b.dyp = (int)dyp;
+            b.off_dy = (int)off_dy; b.off_x0 = (int)off_x0; b.off_x1 = (int)off_x1;
+            for (int a = 0; a < 3; ++a) { b.tile[a] = t[a]; b.ntile[a] = (int)cdiv(g.O[a], t[a]); b.halo[a] = (int)halo[a]; }
+          }
+        }
+  }
+  if (best < 0) return false;
+  b.units = c.batch * b.ntile[0] * b.ntile[1] * b.ntile[2];
+  const int64_t blocks = c.groups * b.nob * b.nib;
+  if (b.units >= ((int64_t)1 << 31)) return false;
+  int64_t slices = std::max<int64_t>(1, ((b.lds <= kLdsShared ? 2 : 1) * (int64_t)cus + blocks / 2) / blocks);
+  if (const int64_t forced = forced_slices()) slices = forced;
+  slices = std::min<int64_t>(slices, b.units);
+  if (blocks * slices > 0x7fffffffLL) return false;
+  b.slices = (int)slices;
+  b.ws = slices * c.out_channels * b.Cig * b.taps * 4;
+  b.body = BODY_H16;
+  g = b;
+  return true;
 }
 
 // Validates the descriptor and chooses input-channel block, tile and slices.  The tile and the channel block minimise a
@@ -229,6 +304,7 @@ int plan(const fc_desc& c, int cus, Geom& g) {
     return fail(FC_ERR_UNSUPPORTED, "fc_wgrad_direct: %lld workgroups exceed the 2^31 of one launch", (long long)(blocks * slices));
   g.slices = (int)slices;
   g.ws = slices * c.out_channels * g.Cig * g.taps * 4;
+  if (knob == 3 && (c.dtype == FC_F16 || c.dtype == FC_BF16)) plan_h16(c, cus, g);
   return FC_OK;
 }
 
@@ -284,7 +360,24 @@ extern "C" int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const vo
   a.slices = g.slices; a.units = (int)g.units; a.P = g.P; a.P4 = g.P4;
   a.io = c.dtype;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (g.body == BODY_VALU) {
+  if (g.body == BODY_H16) {
+    WgradH16Args h;
+    std::memset(&h, 0, sizeof h);
+    h.x = x; h.dy = dy; h.partial = a.partial;
+    for (int i = 0; i < 3; ++i) {
+      h.map[i] = a.map[i];
+      h.S[i] = g.S[i]; h.O[i] = g.O[i]; h.k[i] = g.k[i]; h.stride[i] = g.stride[i]; h.dil[i] = g.dil[i];
+      h.tile[i] = g.tile[i]; h.ntile[i] = g.ntile[i]; h.halo[i] = g.halo[i];
+    }
+    h.SP = g.SP; h.RX = g.RX; h.rows = g.rows; h.rows4 = g.rows4; h.dyp = g.dyp;
+    h.fd_ty = make_fastdiv(g.tile[1]); h.fd_rx = make_fastdiv(g.RX); h.fd_runs = make_fastdiv(g.rows4 * g.RX);
+    h.fd_sp2 = make_fastdiv(g.SP / 2); h.fd_s = make_fastdiv(g.stride[2]);
+    h.fd_hy = make_fastdiv(g.halo[1]); h.fd_hz = make_fastdiv(g.halo[0]);
+    h.Cin = a.Cin; h.Cout = a.Cout; h.Cig = g.Cig; h.Cog = g.Cog; h.taps = g.taps;
+    h.cib = g.cib; h.nib = g.nib; h.nob = g.nob; h.slices = g.slices; h.units = (int)g.units;
+    h.off_dy = g.off_dy; h.off_x0 = g.off_x0; h.off_x1 = g.off_x1; h.io = c.dtype;
+    FC_HIP(wgrad_direct_h16_launch(h, g.ct, c.groups * g.nob * g.nib * g.slices, (size_t)g.lds, st));
+  } else if (g.body == BODY_VALU) {
     a.fd_rx = make_fastdiv(g.runs / (g.tile[0] * g.tile[1]));
     a.runs = g.runs; a.runs64 = g.runs64; a.nbx = g.nbx; a.nblk = g.nblk;
     FC_HIP(wgrad_direct_dw_launch(a, g.kxb, g.nb, c.out_channels * g.slices, (size_t)g.lds, st));

@@ -208,7 +208,12 @@ int fc_wgrad_nd(const fc_plan* plan, const float* x, const float* dy, float* dw,
  * for Cin/groups == 1 and a channel multiplier Cout/groups of at most 8.  FFTCONV_WGRAD_DIRECT_BODY (read where the
  * slices knob is) overrides that: "mfma" takes the MFMA body everywhere, "valu" the depthwise body wherever
  * Cin/groups == 1; a layer with more input channels per group runs the MFMA body under either.  Both bodies sum in
- * float32 but in different orders, so the last bits of dW may differ between them.  Pure arithmetic, no device. */
+ * float32 but in different orders, so the last bits of dW may differ between them.  A third body, 2, runs float16 /
+ * bfloat16 x and dY on the 16-bit MFMAs with nothing widened (products of two 16-bit values are exact in the float32
+ * accumulator): under FFTCONV_WGRAD_DIRECT_BODY "h16" a 16-bit layer that the rule above gives to the MFMA body takes it;
+ * float32 layers and the layers the rule gives to the depthwise body keep their body and their bits.  The info words
+ * are then that body's (LDS in 16-bit samples, the last-axis tile in whole runs of 8 positions clipped to the output).
+ * Pure arithmetic, no device. */
 int fc_wgrad_direct_geometry(const fc_desc* conv_desc, int compute_units, int64_t info[8]);
 int fc_wgrad_direct_body(const fc_desc* conv_desc, int compute_units, int* body);
 int fc_wgrad_direct(const fc_desc* conv_desc, const void* x, const void* dy, float* dw, void* workspace, void* hip_stream);

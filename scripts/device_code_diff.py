@@ -2,7 +2,8 @@
 """Compare the device code of two source trees, kernel by kernel.  No GPU needed.
 
 For every object of the native library that holds kernels (the 7 tile objects, the 7 long-filter objects,
-fft_f64, nd_f64, direct_f64, long_f64, long_step, wgrad_direct, conv_direct, conv_direct_dw, conv_direct_h16) the device side of both trees is
+fft_f64, nd_f64, direct_f64, long_f64, long_step, wgrad_direct, conv_direct, conv_direct_dw, conv_direct_h16,
+wgrad_direct_h16) the device side of both trees is
 compiled to assembly text with the flags of csrc/Makefile (`hipcc ... --cuda-device-only -S`).  An object whose
 source file one tree does not have counts as having no kernels there: its kernels are listed as only in the other
 tree.  The kernels of the two sides are put in one-to-one
@@ -53,8 +54,8 @@ def objects():
         objs.append(("long_" + t, "long_inst.hip", ["-DFC_P=" + p, "-DFC_S=" + s]))
     for n in ("fft_f64", "nd_f64", "direct_f64", "long_f64", "long_step"):
         objs.append((n, n + ".hip", []))
-    # (the direct weight gradient and the three direct forwards, with the flags of their rules in csrc/Makefile)
-    for n in ("wgrad_direct", "conv_direct", "conv_direct_dw", "conv_direct_h16"):
+    # (the two direct weight gradients and the three direct forwards, with the flags of their rules in csrc/Makefile)
+    for n in ("wgrad_direct", "conv_direct", "conv_direct_dw", "conv_direct_h16", "wgrad_direct_h16"):
         objs.append((n, n + ".hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     return objs
 

@@ -26,8 +26,14 @@ sweep of the channel multiplier that the planner's rule was set by): the weight 
 
 and per row the kernel body that a_direct ran (``a_body``).
 
+``--h16`` times the 16-bit MFMA body of DESIGN.md 4.5g on the bfloat16 forms of the dense shapes and one float16 shape,
+weight gradient and step (the step with FFTCONV_DIRECT=1 FFTCONV_DIRECT_BODY=h16 besides, in every column), with
+
+  a_h16        FFTCONV_WGRAD_DIRECT=1 FFTCONV_WGRAD_DIRECT_BODY=h16,
+  a_direct     FFTCONV_WGRAD_DIRECT=1 alone (the float32 MFMA body); c_parent (``--baseline``) is this setting on the parent.
+
     python scripts/wgrad_direct_bench.py [--iters 20] [--rounds 3] [--out profiles/wgrad_direct.jsonl] [--only SUBSTRING]
-                                         [--depthwise] [--baseline [--root PARENT_CHECKOUT]]"""
+                                         [--depthwise | --h16] [--baseline [--root PARENT_CHECKOUT]]"""
 import argparse
 import importlib
 import json
@@ -58,6 +64,10 @@ DW_SHAPES = [
     ("2-D depthwise B8 C256 56^2 k5 stride 2 bf16", 8, 256, 256, 256, (56, 56), 5, 2, BF16),
     ("3-D depthwise B4 C64 32^3 k3 bf16", 4, 64, 64, 64, (32, 32, 32), 3, 1, BF16),
 ] + [(f"2-D B8 C256 x{m} 56^2 k7 bf16", 8, 256, 256 * m, 256, (56, 56), 7, 1, BF16) for m in (2, 4, 8, 16)]
+F16 = torch.float16
+# --h16: the dense rows of SHAPES in bfloat16, and one in float16
+H16_SHAPES = [(f"{name} bf16", B, ci, co, g, size, k, s, BF16) for name, B, ci, co, g, size, k, s, _ in SHAPES
+              if g == 1 and k < 9] + [("3-D B8 8->8 64^3 k3 f16", 8, 8, 8, 1, (64, 64, 64), 3, 1, F16)]
 ROTATE_BYTES = 600 << 20
 HBM_BYTES_PER_US = 8e6      # 8 TB/s
 KNOB = "FFTCONV_WGRAD_DIRECT"
@@ -89,7 +99,7 @@ def timed(g):
     return e0.elapsed_time(e1) * 1e3
 
 
-def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline, depthwise=False):
+def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baseline, depthwise=False, h16=False):
     torch.manual_seed(0)
     nd = len(size)
     auto = importlib.import_module(fca.__name__ + ".autograd")
@@ -130,6 +140,8 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
     variants = {"c_parent": None} if baseline else {"a_direct": "1", "b_unset": None}
     if depthwise:
         variants = {"c_parent": "1"} if baseline else {**variants, "a_mfma": "1mfma", "a_valu": "1valu"}
+    if h16:
+        variants = {"c_parent": "1"} if baseline else {"a_h16": "1h16", **variants}
     steps = {}
     for key, value in variants.items():
         if not depthwise:
@@ -147,6 +159,11 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
             row[key + "_route"] = knob(value, lambda: auto.dw_route(xs[0], wshape, *conf))()
     if depthwise and hasattr(auto, "dw_direct_body"):
         row["a_body"] = knob("1", lambda: auto.dw_direct_body(xs[0], wshape, *conf))()
+    if h16 and not baseline:
+        row["a_h16_body"] = knob("1h16", lambda: auto.dw_direct_body(xs[0], wshape, *conf))()
+        dh, da = steps["a_h16_dw"]()[0].float(), steps["a_direct_dw"]()[0].float()
+        row["h16_vs_direct_dW_max_rel"] = float((dh - da).abs().max() / da.abs().max())
+        del dh, da
     if not baseline:
         da, db = steps["a_direct_dw"]()[0].float(), steps["b_unset_dw"]()[0].float()
         row["a_vs_b_dW_max_rel"] = float((da - db).abs().max() / db.abs().max())
@@ -177,6 +194,8 @@ def run_shape(fca, name, B, ci, co, g, size, k, s, dtype, iters, rounds, baselin
     for what in ("step", "dw"):
         if row.get(f"a_direct_{what}_us") and row.get(f"b_unset_{what}_us"):
             row[f"b_over_a_{what}"] = round(row[f"b_unset_{what}_us"] / row[f"a_direct_{what}_us"], 2)
+        if row.get(f"a_h16_{what}_us") and row.get(f"a_direct_{what}_us"):
+            row[f"direct_over_h16_{what}"] = round(row[f"a_direct_{what}_us"] / row[f"a_h16_{what}_us"], 2)
     if row.get("a_direct_route") == "direct" and row.get("a_direct_dw_us"):
         row["a_roofline_fraction"] = round(row["roofline_us"] / row["a_direct_dw_us"], 3)
     os.environ.pop(KNOB, None)
@@ -190,20 +209,23 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None, help="default: profiles/wgrad_direct.jsonl, with --depthwise profiles/wgrad_direct_dw.jsonl")
     ap.add_argument("--depthwise", action="store_true", help="the depthwise rows and the multiplier sweep, dW alone")
+    ap.add_argument("--h16", action="store_true", help="the 16-bit MFMA body on the 16-bit forms of the dense rows")
     ap.add_argument("--only", default=None)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose fft_conv_pytorch_amd package is timed (default: this tree)")
     ap.add_argument("--tag", default=None, help="free text recorded with every row")
     a = ap.parse_args()
-    a.out = a.out or os.path.join("profiles", "wgrad_direct_dw.jsonl" if a.depthwise else "wgrad_direct.jsonl")
+    a.out = a.out or os.path.join("profiles", "wgrad_direct_h16.jsonl" if a.h16 else "wgrad_direct_dw.jsonl" if a.depthwise else "wgrad_direct.jsonl")
+    if a.h16:      # (the forward and dX of every step on the 16-bit MFMAs too; the weight gradient alone reads neither)
+        os.environ.update(FFTCONV_DIRECT="1", FFTCONV_DIRECT_BODY="h16")
     sys.path.insert(0, os.path.abspath(a.root))
     import fft_conv_pytorch_amd as fca
     assert os.path.abspath(fca.__file__).startswith(os.path.abspath(a.root)), fca.__file__
-    for name, B, ci, co, g, size, k, s, dtype in (DW_SHAPES if a.depthwise else SHAPES):
+    for name, B, ci, co, g, size, k, s, dtype in (H16_SHAPES if a.h16 else DW_SHAPES if a.depthwise else SHAPES):
         if a.only and a.only not in name:
             continue
-        res = run_shape(fca, name, B, ci, co, g, size, k, s, dtype, a.iters, a.rounds, a.baseline, a.depthwise)
+        res = run_shape(fca, name, B, ci, co, g, size, k, s, dtype, a.iters, a.rounds, a.baseline, a.depthwise, a.h16)
         if a.tag:
             res["tag"] = a.tag
         line = json.dumps(res)

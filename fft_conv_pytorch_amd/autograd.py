@@ -110,30 +110,51 @@ def _grad_input_direct(grad: Tensor, weight: Tensor, in_spatial, stride, padding
     FFTCONV_DIRECT_BODY=h16: by ``fc_conv_direct_h16``) or, a depthwise layer, by
     ``fc_conv_direct_dw`` (FFTCONV_DIRECT_DW=1): the stride-1 transposed
     convolution of dY, the weight (Cout, Cin/g, *k) read where it lies with the channel roles exchanged and the taps
-    flipped.  None where the call keeps the transposed FFT plan (``dx_route`` "plan")."""
-    if padding_mode != "constant" or any(s != 1 for s in stride):
+    flipped.  dX of a strided layer with zero padding by ``fc_conv_direct_tr`` (FFTCONV_DIRECT_TR=1): the strided transposed
+    convolution of dY by output phases, under the output padding ``_grad_input_plan`` computes.  None where the call keeps
+    the transposed FFT plan (``dx_route`` "plan")."""
+    if padding_mode != "constant":
         return None
-    hit = F_._direct_hit(True, grad, weight, None, stride, padding, 0, dilation, groups, "constant", channels_last, native)
+    out_pad = _dx_output_padding(tuple(grad.shape[2:]), tuple(weight.shape[2:]), in_spatial, stride, padding, dilation)
+    if out_pad is None:
+        return None
+    hit = F_._direct_hit(True, grad, weight, None, stride, padding, out_pad, dilation, groups, "constant", channels_last, native)
     if hit is None or hit[2][2:] != tuple(in_spatial):
         return None
     return F_._direct_run(hit, grad, weight, None)
+
+
+def _dx_output_padding(out, ksize, in_spatial, stride, padding, dilation):
+    """The output padding under which the transposed convolution of a dY of extent ``out`` has the extent of x: input
+    extent minus base extent per axis, zeros at stride 1.  None where a strided layer has no direct dX: FFTCONV_DIRECT_TR
+    is not "1"."""
+    if all(s == 1 for s in stride):
+        return (0,) * len(stride)
+    if not F_._direct_tr_on():
+        return None
+    return tuple(S - ((o - 1) * s - 2 * p + d * (k - 1) + 1)
+                 for S, o, s, p, d, k in zip(in_spatial, out, stride, padding, dilation, ksize))
 
 
 def dx_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode) -> str:
     """The route ``_grad_input`` takes for the dX of this layer on a contiguous dY of x's dtype (launches nothing, creates
     no plan): ``"direct"`` (FFTCONV_DIRECT=1, stride 1, zero padding and a layer ``fc_conv_direct`` covers in its
     transposed form), ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a layer
-    ``fc_conv_direct_h16`` covers), ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and the same of ``fc_conv_direct_dw``) or ``"plan"`` (the
-    transposed FFT plan).  The arguments are those of ``dw_route``."""
-    on = (F_._direct_on(), F_._direct_dw_on())
-    if not any(on) or padding_mode != "constant" or any(s != 1 for s in stride) or x.ndim not in (4, 5):
+    ``fc_conv_direct_h16`` covers), ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and the same of ``fc_conv_direct_dw``),
+    ``"direct-tr"`` (FFTCONV_DIRECT_TR=1, a stride above 1, zero padding and a layer ``fc_conv_direct_tr`` covers) or
+    ``"plan"`` (the transposed FFT plan).  The arguments are those of ``dw_route``."""
+    if padding_mode != "constant" or x.ndim not in (4, 5):
         return "plan"
     if x.dtype in F_._LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
         return "plan"
-    out = tuple(int(S) + 2 * p - d * (int(k) - 1) for S, p, d, k in zip(x.shape[2:], padding, dilation, wshape[2:]))
-    for dw in (False, True):
-        hit = on[dw] and F_._direct_geometry((int(x.shape[0]), int(wshape[0])) + out, x.dtype, x.device, tuple(wshape),
-                                             tuple(stride), tuple(padding), tuple(dilation), groups, "constant", True, None, dw)
+    out = tuple((int(S) + 2 * p - d * (int(k) - 1) - 1) // s + 1
+                for S, p, d, k, s in zip(x.shape[2:], padding, dilation, wshape[2:], stride))
+    out_pad = _dx_output_padding(out, tuple(wshape[2:]), tuple(int(S) for S in x.shape[2:]), stride, padding, dilation)
+    if out_pad is None:
+        return "plan"
+    for kind in F_._direct_kinds(True, tuple(stride)):
+        hit = F_._direct_geometry((int(x.shape[0]), int(wshape[0])) + out, x.dtype, x.device, tuple(wshape),
+                                  tuple(stride), tuple(padding), tuple(dilation), groups, "constant", True, out_pad, kind)
         if hit:
             return hit[4]
     return "plan"

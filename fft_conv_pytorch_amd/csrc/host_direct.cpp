@@ -2,7 +2,8 @@
 // conv_direct_kernel (conv_direct.hpp) and its launch; fc_conv_direct_dw_geometry and fc_conv_direct_dw ("Direct
 // depthwise forward"): those of conv_direct_dw_kernel (conv_direct_dw.hpp), and fc_conv_direct_h16_geometry and
 // fc_conv_direct_h16 ("Direct forward on the 16-bit matrix instructions"): those of conv_direct_h16_kernel
-// (conv_direct_h16.hpp), behind the same validation.  The planners
+// (conv_direct_h16.hpp), behind the same validation; fc_conv_direct_tr_geometry and fc_conv_direct_tr ("Direct strided
+// transposed convolution"): those of conv_direct_tr_kernel (conv_direct_tr.hpp), validation extended.  The planners
 // are pure arithmetic on the descriptor and the CU count; a launch call plans again for the current device (the last
 // answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include "conv_direct.hpp"
 #include "conv_direct_dw.hpp"
 #include "conv_direct_h16.hpp"
+#include "conv_direct_tr.hpp"
 #include "fc_plan.h"
 
 using namespace fc;
@@ -39,8 +41,10 @@ struct Geom {
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The descriptor of a layer either direct forward covers, into g: extents, taps and channels per group.  `who` names the
-// entry point in the refusals, `why_taps` ends the one of a kernel past 128 taps.
-int validate(const fc_desc& c, int cus, const char* who, const char* why_taps, Geom& g) {
+// entry point in the refusals, `why_taps` ends the one of a kernel past 128 taps.  `by_phases` (plan_tr): a transposed
+// descriptor may have any stride up to 8, an output padding and any padding that leaves an output; g.pad is then the
+// descriptor's padding and g.O the extent of the transposed convolution.
+int validate(const fc_desc& c, int cus, const char* who, const char* why_taps, Geom& g, bool by_phases = false) {
   if (c.ndim == 1) return fail(FC_ERR_UNSUPPORTED, "%s covers 2-D and 3-D convolutions (no 1-D)", who);
   if (c.ndim < 1 || c.ndim > 3) return fail(FC_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", c.ndim);
   if (c.dtype == FC_F64 || c.dtype == FC_C64)
@@ -62,6 +66,26 @@ int validate(const fc_desc& c, int cus, const char* who, const char* why_taps, G
     if (c.kernel[i] > kMaxTaps || c.dilation[i] >= (1 << 20) || c.stride[i] >= (1 << 20))
       return fail(FC_ERR_UNSUPPORTED, "axis %d: %s covers kernels of at most %d taps in all", i, who, kMaxTaps);
     int64_t pad = c.padding[i];
+    if (c.transposed && by_phases) {
+      if (c.stride[i] > kCdtMaxStride)
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: %s covers a stride of at most %d (got %lld)", i, who, kCdtMaxStride,
+                    (long long)c.stride[i]);
+      if (c.output_padding[i] < 0 || c.output_padding[i] >= std::max(c.stride[i], c.dilation[i]))
+        return fail(FC_ERR_INVALID, "axis %d: output_padding must be >= 0 and smaller than stride or dilation", i);
+      if (c.spatial[i] >= (1 << 26) || pad >= ((int64_t)1 << 30))
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: extent %lld times the stride exceeds 32-bit positions", i, (long long)c.spatial[i]);
+      const int64_t out = (c.spatial[i] - 1) * c.stride[i] - 2 * pad + (c.kernel[i] - 1) * c.dilation[i] + c.output_padding[i] + 1;
+      if (out < 1) return fail(FC_ERR_INVALID, "axis %d: the padding %lld leaves no output sample", i, (long long)pad);
+      if (out >= ((int64_t)1 << 30))
+        return fail(FC_ERR_UNSUPPORTED, "axis %d: output extent %lld exceeds 32-bit positions", i, (long long)out);
+      g.S[a] = (int)c.spatial[i]; g.O[a] = (int)out; g.k[a] = (int)c.kernel[i];
+      g.stride[a] = (int)c.stride[i]; g.dil[a] = (int)c.dilation[i]; g.pad[a] = (int)pad;
+      taps *= c.kernel[i];
+      xs *= c.spatial[i]; ys *= out;
+      if (xs >= ((int64_t)1 << 40) || ys >= ((int64_t)1 << 40))
+        return fail(FC_ERR_UNSUPPORTED, "%s indexes x and y in 64 bits but takes fewer than 2^40 samples each", who);
+      continue;
+    }
     if (c.transposed) {
       // the stride-1 transposed convolution is the forward one with the taps flipped and a padding of d * (k - 1) - p
       if (c.stride[i] != 1)
@@ -308,6 +332,126 @@ int plan_dw(const fc_desc& c, int cus, Geom& g) {
   return FC_OK;
 }
 
+// What plan_tr adds to a Geom (tile, ntile and halo of which are in the space of base positions q)
+struct TrPlan {
+  Geom g;
+  int qlo[3], Q[3], M[3];
+  int phases, ppp, ph, npass;      // prod(stride); live phases and phase slots of a pass; passes
+  int k0[3][kCdtMaxStride], nk[3][kCdtMaxStride], m0[3][kCdtMaxStride], kstep[3], mstep[3];
+  unsigned short soff[kCdtMaxPhases + 1];
+};
+
+// MFMA steps of the phases of a block of cib input channels, each phase padded to whole steps: soff[f] is the first step
+// of phase f (the last axis fastest), the return value soff[phases]
+int tr_steps(const TrPlan& t, int cib, unsigned short* soff) {
+  const int* s = t.g.stride;
+  int total = 0, f = 0;
+  for (int rz = 0; rz < s[0]; ++rz)
+    for (int ry = 0; ry < s[1]; ++ry)
+      for (int rx = 0; rx < s[2]; ++rx, ++f) {
+        if (soff) soff[f] = (unsigned short)total;
+        total += (int)cdiv((int64_t)cib * t.nk[0][rz] * t.nk[1][ry] * t.nk[2][rx], 4);
+      }
+  if (soff) soff[f] = (unsigned short)total;
+  return total;
+}
+
+// The planner of conv_direct_tr_kernel: validate() in its by_phases form, the live taps of every phase, then plan()'s
+// search with three changes.  The tiles are tiles of base positions q (t + p = s q + r), their halo is tile + M; the
+// candidates carry the phase slots of a pass (2 .. 16, whole rows of last-axis phases) times the position tiles per wave
+// (<= 16 together); and the cycle estimate counts the MFMAs over the live steps of all phases and the staging once per
+// pass.  The constants are plan()'s, inherited: none of them is measured for this kernel.
+int plan_tr(const fc_desc& c, int cus, TrPlan& t) {
+  static_assert(kCdMaxCols == 512 && kCdtMaxStride == 8 && kCdtMaxPhases == 64, "the text below");
+  Geom& g = t.g;
+  if (int st = validate(c, cus, "fc_conv_direct_tr", "a block of 512 columns holds whole input channels", g, true)) return st;
+  if (!c.transposed || (g.stride[0] == 1 && g.stride[1] == 1 && g.stride[2] == 1))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr runs transposed convolutions with a stride above 1 on some axis (this one "
+                "is %s: fc_conv_direct covers it)", c.transposed ? "at stride 1" : "not transposed");
+  t.phases = g.stride[0] * g.stride[1] * g.stride[2];
+  if (t.phases > kCdtMaxPhases)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr covers at most %d phases (the product of the strides; got %d)", kCdtMaxPhases,
+                t.phases);
+  if (g.Cog == 1 && g.Cig <= kDepthwiseMaxMultiplier)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr does not run depthwise layers (a weight with one input channel per group and "
+                "%d output channels per group), as fc_conv_direct; they keep the FFT plan", g.Cig);
+  g.nob = (int)cdiv(g.Cog, kCdRows);
+  for (int a = 0; a < 3; ++a) {
+    const int s = g.stride[a], d = g.dil[a], k = g.k[a];
+    t.qlo[a] = g.pad[a] / s; t.Q[a] = (g.O[a] - 1 + g.pad[a]) / s - t.qlo[a] + 1;
+    t.M[a] = (int)((int64_t)(k - 1) * d / s);
+    int gcd = s, v = d % s;
+    while (v) { const int w = gcd % v; gcd = v; v = w; }
+    t.kstep[a] = s / gcd; t.mstep[a] = d / gcd;
+    for (int r = 0; r < kCdtMaxStride; ++r) {
+      t.k0[a][r] = t.nk[a][r] = t.m0[a][r] = 0;
+      if (r >= s) continue;
+      int k0 = 0;
+      while (k0 < t.kstep[a] && k0 < k && ((int64_t)k0 * d - r) % s) ++k0;
+      if (k0 >= t.kstep[a] || k0 >= k) continue;      // (gcd(d, s) does not divide r, or the kernel ends before the first)
+      t.k0[a][r] = k0; t.nk[a][r] = (k - 1 - k0) / t.kstep[a] + 1; t.m0[a][r] = (int)(((int64_t)k0 * d - r) / s);
+    }
+  }
+
+  double best = -1.0;
+  bool best_shared = false;
+  int cibmax = std::min<int>(g.Cig, kCdMaxCols / g.taps);
+  while (cibmax > 1 && 4 * tr_steps(t, cibmax, nullptr) > kCdMaxCols) --cibmax;      // (one channel: at most 128 + 3 * 64 columns)
+  const int sx = g.stride[2], rows = t.phases / sx;
+  int last_cib = 0, tried = 0;
+  for (int n = (int)cdiv(g.Cig, cibmax); n <= g.Cig && tried < 8; ++n) {
+    const int cib = (int)cdiv(g.Cig, n);
+    if (cib == last_cib) continue;
+    last_cib = cib; ++tried;
+    const int nib = (int)cdiv(g.Cig, cib), steps = tr_steps(t, cib, nullptr);
+    for (int ph = 2; ph <= 16; ph *= 2) {
+      if (ph < sx || (ph > 2 && ph / 2 >= sx && ph / 2 / sx >= rows)) continue;      // (no whole row; the slots of a smaller build)
+      const int ppp = std::min(ph / sx, rows) * sx, npass = (int)cdiv(t.phases, ppp);
+      for (int tz = 1; tz <= 8; tz *= 2)
+        for (int ty = 1; ty <= 16; ty *= 2)
+          for (int tx = 1; tx <= 64; tx *= 2) {
+            const int q[3] = {std::min(tz, t.Q[0]), std::min(ty, t.Q[1]), std::min(tx, t.Q[2])};
+            if ((tz > 1 && q[0] < tz && tz / 2 >= t.Q[0]) || (ty > 1 && q[1] < ty && ty / 2 >= t.Q[1]) ||
+                (tx > 1 && q[2] < tx && tx / 2 >= t.Q[2]))
+              continue;      // (the same clipped tile as a smaller candidate)
+            const int P = q[0] * q[1] * q[2];
+            int npt = 1;
+            while (kCdWaves * npt * 16 < P) npt *= 2;
+            if (ph * npt > kCdMaxPT) continue;
+            int64_t hv = 1, ntiles = 1;
+            for (int a = 0; a < 3; ++a) {
+              hv *= (int64_t)q[a] + t.M[a];
+              ntiles *= cdiv(t.Q[a], q[a]);
+              if (hv > kLdsBudget) break;
+            }
+            if (hv > kLdsBudget) continue;
+            const int64_t lds = 4 * ((int64_t)steps * (kCdWPitch + 8) + cib * hv);      // wl, cbl and cwl, xl
+            if (lds > kLdsBudget) continue;
+            const bool shared = lds <= kLdsShared && ph * npt < kCdMaxPT;
+            if (best_shared && !shared) continue;
+            const double staged = nib > 1 ? (double)npass * cib * (double)hv : cib * (double)hv;
+            const double cost = (double)nib * (double)ntiles * (32.0 * steps * npt + 3000.0 * npass + 0.5 * (staged + 64.0 * steps));
+            if (best < 0 || (shared && !best_shared) || cost < best) {
+              best = cost; best_shared = shared;
+              g.cib = cib; g.nib = nib; g.npt = npt; g.steps = steps; g.P = P; g.lds = lds;
+              t.ph = ph; t.ppp = ppp; t.npass = npass;
+              for (int a = 0; a < 3; ++a) { g.tile[a] = q[a]; g.ntile[a] = (int)cdiv(t.Q[a], q[a]); g.halo[a] = q[a] + t.M[a]; }
+            }
+          }
+    }
+  }
+  if (best < 0)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: the x samples that one base position reaches through every tap do not fit "
+                "%lld bytes of LDS", (long long)kLdsBudget);
+  tr_steps(t, g.cib, t.soff);
+  g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
+  if (g.units >= ((int64_t)1 << 31))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+  if (g.units * c.groups * g.nob > 0x7fffffffLL)
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: %lld workgroups exceed the 2^31 of one launch", (long long)(g.units * c.groups * g.nob));
+  return FC_OK;
+}
+
 // The kernel arguments of a plan()- or plan_h16()-planned launch (conv_direct_kernel and conv_direct_h16_kernel share the struct)
 ConvDirectArgs direct_args(const fc_desc& c, const Geom& g, const void* x, const void* weight, const void* bias, void* y) {
   ConvDirectArgs a;
@@ -424,5 +568,51 @@ extern "C" int fc_conv_direct_h16(const fc_desc* desc, const void* x, const void
   const ConvDirectArgs a = direct_args(*desc, last.g, x, weight, bias, y);
   FC_HIP(conv_direct_h16_launch(a, last.g.npt, last.g.units * desc->groups * last.g.nob, (size_t)last.g.lds,
                                 static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_tr_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
+  if (!desc || !info) return fail(FC_ERR_INVALID, "null argument");
+  TrPlan t;
+  if (int st = plan_tr(*desc, compute_units, t)) return st;
+  for (int i = 0; i < 3; ++i) info[i] = i < desc->ndim ? t.g.tile[t.g.ax0 + i] : 0;
+  info[3] = t.phases; info[4] = t.ppp; info[5] = t.g.cib; info[6] = t.g.nib; info[7] = t.g.lds;
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_tr(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream) {
+  if (!desc || !x || !weight || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward: a stale sticky error of an earlier call is not this call's)
+  int cus = 0;
+  if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
+  // the plan of the last call of this thread, while descriptor and CU count are what they were
+  struct Last { fc_desc d; int cus; TrPlan t; bool set; };
+  static thread_local Last last = {};
+  if (!last.set || std::memcmp(&last.d, desc, sizeof(fc_desc)) || last.cus != cus) {
+    last.set = false;
+    if (int st = plan_tr(*desc, cus, last.t)) return st;
+    last.d = *desc; last.cus = cus; last.set = true;
+  }
+  const TrPlan& t = last.t;
+  const Geom& g = t.g;
+  const fc_desc& c = *desc;
+  ConvDirectTrArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.w = weight; a.bias = bias; a.y = y;
+  for (int i = 0; i < 3; ++i) {
+    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.up[i] = g.stride[i]; a.pad[i] = g.pad[i];
+    a.qlo[i] = t.qlo[i]; a.Q[i] = t.Q[i]; a.M[i] = t.M[i];
+    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
+    a.kstep[i] = t.kstep[i]; a.mstep[i] = t.mstep[i];
+  }
+  std::memcpy(a.k0, t.k0, sizeof a.k0); std::memcpy(a.nk, t.nk, sizeof a.nk); std::memcpy(a.m0, t.m0, sizeof a.m0);
+  std::memcpy(a.soff, t.soff, sizeof a.soff);
+  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
+  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
+  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
+  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
+  a.phases = t.phases; a.ppp = t.ppp; a.npass = t.npass;
+  a.io = c.dtype;
+  FC_HIP(conv_direct_tr_launch(a, t.ph, g.npt, g.units * c.groups * g.nob, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

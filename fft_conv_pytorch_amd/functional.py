@@ -405,9 +405,31 @@ def _direct_body() -> str:
     return "h16" if os.environ.get("FFTCONV_DIRECT_BODY", "f32") == "h16" else "f32"
 
 
+def _direct_tr_on() -> bool:
+    """FFTCONV_DIRECT_TR (read per call, independent of the other direct switches): "1" takes transposed 2-D / 3-D calls
+    with a stride above 1 -- ``fft_conv_transpose`` at stride >= 2 and the dX of strided zero-padded layers -- from
+    ``fc_conv_direct_tr`` (csrc/conv_direct_tr.hpp; route "direct-tr") where it covers them.  Opt-in: the
+    bits of y and dX change."""
+    return os.environ.get("FFTCONV_DIRECT_TR", "0") == "1"
+
+
+def _direct_kinds(transposed: bool, stride) -> tuple:
+    """The direct planners a call may ask, in order: "tr" (FFTCONV_DIRECT_TR=1, a transposed call with a stride above 1),
+    "" (FFTCONV_DIRECT=1) and "dw" (FFTCONV_DIRECT_DW=1).  No layer is covered by two of them."""
+    kinds = []
+    if transposed and _direct_tr_on() and any(s > 1 for s in stride):
+        kinds.append("tr")
+    if _direct_on():
+        kinds.append("")
+    if _direct_dw_on():
+        kinds.append("dw")
+    return tuple(kinds)
+
+
 def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, groups, padding_mode, transposed=False,
                      output_padding=None, dw=False):
-    """(descriptor, geometry words, shape of y, launch, route name) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``;
+    """(descriptor, geometry words, shape of y, launch, route name) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``,
+    or ``dw == "tr"``: of ``fc_conv_direct_tr``;
     16-bit tensors under FFTCONV_DIRECT_BODY=h16: of ``fc_conv_direct_h16`` where it covers the layer) for a signal
     of ``shape`` on ``device``, None where the
     library refuses the layer (1-D, float64, complex64, more than 128 taps, depthwise, a strided transposed layer, ...) or
@@ -435,7 +457,7 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
         _DEVICE_CUS[device] = cus
     body = _direct_body() if not dw and dtype in _LOW_PRECISION else "f32"
     key = (tuple(shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, bool(transposed), output_padding,
-           device, dtype, cus, bool(dw), body)
+           device, dtype, cus, dw if dw == "tr" else bool(dw), body)
     hit = _DIRECT_GEOMETRY.get(key)
     if hit is None:
         hit = False
@@ -452,10 +474,14 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
                     name, launch = "direct-h16", _native.conv_direct_h16
                 except NotImplementedError:
                     pass      # (the float32 body takes what it covers, as without the variable)
-            if geom is None:
+            if dw == "tr":
+                geom = _native.conv_direct_tr_geometry(desc, cus)
+                name, launch = "direct-tr", _native.conv_direct_tr
+            elif geom is None:
                 geom = (_native.conv_direct_dw_geometry if dw else _native.conv_direct_geometry)(desc, cus)
-            if transposed:      # (stride 1, no output padding: the library refuses the rest)
-                out = tuple(int(S) - 2 * p + d * (int(k) - 1) for S, p, d, k in zip(shape[2:], padding, dilation, wshape[2:]))
+            if transposed:      # (the other kernels: stride 1, no output padding; the library refuses the rest)
+                out = tuple((int(S) - 1) * s - 2 * p + d * (int(k) - 1) + o + 1
+                            for S, s, p, d, k, o in zip(shape[2:], stride, padding, dilation, wshape[2:], output_padding))
             else:
                 out = tuple((int(S) + 2 * p - d * (int(k) - 1) - 1) // s + 1
                             for S, p, d, k, s in zip(shape[2:], padding, dilation, wshape[2:], stride))
@@ -471,11 +497,11 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
 def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_padding, dilation, groups, padding_mode,
                 channels_last: bool = False, native: bool = False):
     """``_direct_geometry`` of a call that takes a direct route: FFTCONV_DIRECT=1 and a layer ``fc_conv_direct`` covers, or
-    FFTCONV_DIRECT_DW=1 and a layer ``fc_conv_direct_dw`` covers (no layer is both); contiguous real 4-D / 5-D signal,
+    FFTCONV_DIRECT_DW=1 and a layer ``fc_conv_direct_dw`` covers, or FFTCONV_DIRECT_TR=1 and a strided transposed layer
+    ``fc_conv_direct_tr`` covers (no layer is two of them); contiguous real 4-D / 5-D signal,
     kernel and bias of its dtype on its device (16-bit tensors: not under FFTCONV_HALF_IO=0), no channels-last operand
     or result.  None keeps the call on the route it has without the switches."""
-    on = (_direct_on(), _direct_dw_on())
-    if not any(on) or channels_last or native or isinstance(padding, str):
+    if not (_direct_on() or _direct_dw_on() or _direct_tr_on()) or channels_last or native or isinstance(padding, str):
         return None
     if not all(isinstance(t, Tensor) for t in (signal, kernel)) or signal.ndim not in (4, 5) or kernel.ndim != signal.ndim:
         return None
@@ -493,17 +519,17 @@ def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_
     except (TypeError, ValueError):
         return None
     hit = None
-    for dw in (False, True):
-        if on[dw] and hit is None:
+    for kind in _direct_kinds(transposed, conf[0]):
+        if hit is None:
             hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel.shape), conf[0], conf[1],
-                                   conf[2], groups, padding_mode, transposed, conf[3], dw)
+                                   conf[2], groups, padding_mode, transposed, conf[3], kind)
     if hit is not None and bias is not None and tuple(bias.shape) != (hit[2][1],):
         return None
     return hit
 
 
 def _direct_run(hit, signal: Tensor, kernel: Tensor, bias: Optional[Tensor]) -> Tensor:
-    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` / ``fc_conv_direct_h16`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
+    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` / ``fc_conv_direct_h16`` / ``fc_conv_direct_tr`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
     no spectrum."""
     desc, _, shape, launch, _ = hit
     signal, kernel = signal.detach(), kernel.detach().contiguous()
@@ -520,19 +546,18 @@ def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, gr
     """The route the forward of ``fft_conv`` (``transposed``: of ``fft_conv_transpose``) takes for this signal and a
     kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers),
     ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a call ``fc_conv_direct_h16`` covers),
-    ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and a call ``fc_conv_direct_dw`` covers) or ``"fft"``.  Arithmetic only: launches
-    nothing, creates no plan."""
-    on = (_direct_on(), _direct_dw_on())
-    if not any(on) or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
+    ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and a call ``fc_conv_direct_dw`` covers), ``"direct-tr"`` (FFTCONV_DIRECT_TR=1 and a
+    strided transposed call ``fc_conv_direct_tr`` covers) or ``"fft"``.  Arithmetic only: launches nothing, creates no plan."""
+    if not (_direct_on() or _direct_dw_on() or _direct_tr_on()) or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
         return "fft"
     if signal.dtype in _LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":
         return "fft"
     n = signal.ndim - 2
     conf = tuple(tuple(int(v) for v in to_ntuple(t, n=n)) for t in (stride, padding, dilation, output_padding))
-    for dw in (False, True):
-        hit = on[dw] and _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0],
-                                          conf[1], conf[2], groups, "constant" if padding_mode == "zeros" else padding_mode,
-                                          transposed, conf[3], dw)
+    for kind in _direct_kinds(transposed, conf[0]):
+        hit = _direct_geometry(tuple(signal.shape), signal.dtype, signal.device, tuple(kernel_shape), conf[0],
+                               conf[1], conf[2], groups, "constant" if padding_mode == "zeros" else padding_mode,
+                               transposed, conf[3], kind)
         if hit:
             return hit[4]
     return "fft"

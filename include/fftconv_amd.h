@@ -274,6 +274,29 @@ int fc_conv_direct_dw(const fc_desc* desc, const void* x, const void* weight, co
 int fc_conv_direct_h16_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
 int fc_conv_direct_h16(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
 
+/* Direct strided transposed convolution (ABI 7 extension: two new entry points; fc_desc keeps its size and every call above
+ * its signature and meaning): the transposed descriptors fc_conv_direct refuses for their stride or output padding,
+ *   y[b][(g,o)][t] = bias[(g,o)] + sum_i sum_k W[(g,i)][o][k] * x[b][(g,i)][(t + padding - k*dilation) / stride]
+ * over the taps whose division is exact and whose index lies in x, taken in the time domain by output phases: per axis
+ * t + padding = stride * q + r, and phase r multiplies only the taps with k * dilation = r (mod stride), so no zero of the
+ * spread signal is multiplied.  On the matrix pipe in float32, no plan, no spectrum, no workspace; the weight
+ * (Cin, Cout/groups, *k) is read where it lies.  This is fft_conv_transpose at stride >= 2 and the input gradient of every
+ * strided layer with zero padding.  Operands, dtypes and the guarantees (every sample of y written exactly once, phases
+ * without a tap included; nothing else written; equal calls give equal bits) are those of fc_conv_direct.
+ *   Covered: transposed = 1, ndim 2 or 3, a stride above 1 on at least one axis, every stride <= 8 and their product
+ *   <= 64; FC_F32, FC_F16 or FC_BF16; at most 128 taps; any dilation, groups, output_padding < max(stride, dilation) and any
+ *   padding that leaves an output sample on every axis.
+ *   FC_ERR_UNSUPPORTED with text: a descriptor that is not transposed or has stride 1 on every axis (fc_conv_direct covers
+ *   it), ndim 1, FC_F64, FC_C64, more taps, a stride above 8, more than 64 phases, a depthwise weight by the rule of
+ *   fc_conv_direct, a halo that does not fit 160 KiB of LDS, a tensor of 2^40 samples, 2^31 units or workgroups.
+ * fc_conv_direct_tr_geometry is pure arithmetic: no device is touched.  info words: tile of base positions q per axis in
+ * tensor order (3 words, 0 past ndim), phases (the product of the strides), phases of one pass over the input channels
+ * (whole rows of last-axis phases), input channels per block (times the taps <= 512), blocks of input channels per group,
+ * bytes of LDS per workgroup.
+ * fc_conv_direct_tr plans for the CURRENT device and launches once on hip_stream.  Asynchronous; allocates nothing. */
+int fc_conv_direct_tr_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
+int fc_conv_direct_tr(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

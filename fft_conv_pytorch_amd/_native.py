@@ -163,6 +163,8 @@ def _signatures() -> dict:
         "fc_conv_direct_h16": (i32, (desc, vp, vp, vp, vp, vp)),
         "fc_conv_direct_tr_geometry": (i32, (desc, i32, i64x8)),
         "fc_conv_direct_tr": (i32, (desc, vp, vp, vp, vp, vp)),
+        "fc_conv_direct_tr_h16_geometry": (i32, (desc, i32, i64x8)),
+        "fc_conv_direct_tr_h16": (i32, (desc, vp, vp, vp, vp, vp)),
         "fc_debug_route": (i32, (vp, ptr(ctypes.c_int32 * 16))),
         "fc_long_geometry": (i32, (ldesc, i64x8)),
         "fc_long_plan_create": (i32, (ldesc, out)),
@@ -419,6 +421,22 @@ def conv_direct_tr(desc: FcDesc, x_ptr: int, weight_ptr: int, bias_ptr: Optional
     """``fc_conv_direct_tr`` on the current device: x, weight, bias (or None) and y, all of the descriptor's dtype."""
     lib = load_library()
     _check(lib, lib.fc_conv_direct_tr(ctypes.byref(desc), x_ptr, weight_ptr, bias_ptr, y_ptr, stream))
+
+
+def conv_direct_tr_h16_geometry(desc: FcDesc, compute_units: int) -> dict:
+    """``fc_conv_direct_tr_h16_geometry`` as a dict of CONV_DIRECT_TR_INFO_WORDS (no device is touched).  A descriptor the
+    strided transposed kernel on the 16-bit matrix instructions does not cover (float32 among them) raises
+    NotImplementedError with the library's reason."""
+    lib = load_library()
+    info = (ctypes.c_int64 * 8)()
+    _check(lib, lib.fc_conv_direct_tr_h16_geometry(ctypes.byref(desc), compute_units, ctypes.byref(info)))
+    return dict(zip(CONV_DIRECT_TR_INFO_WORDS, (int(v) for v in info)))
+
+
+def conv_direct_tr_h16(desc: FcDesc, x_ptr: int, weight_ptr: int, bias_ptr: Optional[int], y_ptr: int, stream: int):
+    """``fc_conv_direct_tr_h16`` on the current device: x, weight, bias (or None) and y, all float16 or all bfloat16."""
+    lib = load_library()
+    _check(lib, lib.fc_conv_direct_tr_h16(ctypes.byref(desc), x_ptr, weight_ptr, bias_ptr, y_ptr, stream))
 
 
 CONV_DIRECT_DW_INFO_WORDS = ("tile0", "tile1", "tile2", "taps_per_block", "slots", "workgroups", "lds_bytes", "runs_per_thread")

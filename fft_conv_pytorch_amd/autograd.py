@@ -110,7 +110,8 @@ def _grad_input_direct(grad: Tensor, weight: Tensor, in_spatial, stride, padding
     FFTCONV_DIRECT_BODY=h16: by ``fc_conv_direct_h16``) or, a depthwise layer, by
     ``fc_conv_direct_dw`` (FFTCONV_DIRECT_DW=1): the stride-1 transposed
     convolution of dY, the weight (Cout, Cin/g, *k) read where it lies with the channel roles exchanged and the taps
-    flipped.  dX of a strided layer with zero padding by ``fc_conv_direct_tr`` (FFTCONV_DIRECT_TR=1): the strided transposed
+    flipped.  dX of a strided layer with zero padding by ``fc_conv_direct_tr`` (FFTCONV_DIRECT_TR=1; 16-bit tensors under
+    FFTCONV_DIRECT_BODY=h16: by ``fc_conv_direct_tr_h16``): the strided transposed
     convolution of dY by output phases, under the output padding ``_grad_input_plan`` computes.  None where the call keeps
     the transposed FFT plan (``dx_route`` "plan")."""
     if padding_mode != "constant":
@@ -141,7 +142,8 @@ def dx_route(x: Tensor, wshape, stride, padding, dilation, groups, padding_mode)
     no plan): ``"direct"`` (FFTCONV_DIRECT=1, stride 1, zero padding and a layer ``fc_conv_direct`` covers in its
     transposed form), ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a layer
     ``fc_conv_direct_h16`` covers), ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and the same of ``fc_conv_direct_dw``),
-    ``"direct-tr"`` (FFTCONV_DIRECT_TR=1, a stride above 1, zero padding and a layer ``fc_conv_direct_tr`` covers) or
+    ``"direct-tr"`` (FFTCONV_DIRECT_TR=1, a stride above 1, zero padding and a layer ``fc_conv_direct_tr`` covers),
+    ``"direct-tr-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a layer ``fc_conv_direct_tr_h16`` covers) or
     ``"plan"`` (the transposed FFT plan).  The arguments are those of ``dw_route``."""
     if padding_mode != "constant" or x.ndim not in (4, 5):
         return "plan"

@@ -3,7 +3,9 @@
 // depthwise forward"): those of conv_direct_dw_kernel (conv_direct_dw.hpp), and fc_conv_direct_h16_geometry and
 // fc_conv_direct_h16 ("Direct forward on the 16-bit matrix instructions"): those of conv_direct_h16_kernel
 // (conv_direct_h16.hpp), behind the same validation; fc_conv_direct_tr_geometry and fc_conv_direct_tr ("Direct strided
-// transposed convolution"): those of conv_direct_tr_kernel (conv_direct_tr.hpp), validation extended.  The planners
+// transposed convolution"): those of conv_direct_tr_kernel (conv_direct_tr.hpp), validation extended, and
+// fc_conv_direct_tr_h16_geometry and fc_conv_direct_tr_h16 ("... on the 16-bit matrix instructions"): those of
+// conv_direct_tr_h16_kernel (conv_direct_tr_h16.hpp).  The planners
 // are pure arithmetic on the descriptor and the CU count; a launch call plans again for the current device (the last
 // answer is remembered per thread), allocates nothing and synchronises nothing.
 #include <hip/hip_runtime.h>
@@ -15,6 +17,7 @@
 #include "conv_direct_dw.hpp"
 #include "conv_direct_h16.hpp"
 #include "conv_direct_tr.hpp"
+#include "conv_direct_tr_h16.hpp"
 #include "fc_plan.h"
 
 using namespace fc;
@@ -341,16 +344,17 @@ struct TrPlan {
   unsigned short soff[kCdtMaxPhases + 1];
 };
 
-// MFMA steps of the phases of a block of cib input channels, each phase padded to whole steps: soff[f] is the first step
-// of phase f (the last axis fastest), the return value soff[phases]
-int tr_steps(const TrPlan& t, int cib, unsigned short* soff) {
+// MFMA steps of the phases of a block of nc input channels (plan_tr_h16: nc cells of 8 channels; a column is then (cell,
+// tap) and a step 32 products), each phase padded to whole steps: soff[f] is the first step of phase f (the last axis
+// fastest), the return value soff[phases]
+int tr_steps(const TrPlan& t, int nc, unsigned short* soff) {
   const int* s = t.g.stride;
   int total = 0, f = 0;
   for (int rz = 0; rz < s[0]; ++rz)
     for (int ry = 0; ry < s[1]; ++ry)
       for (int rx = 0; rx < s[2]; ++rx, ++f) {
         if (soff) soff[f] = (unsigned short)total;
-        total += (int)cdiv((int64_t)cib * t.nk[0][rz] * t.nk[1][ry] * t.nk[2][rx], 4);
+        total += (int)cdiv((int64_t)nc * t.nk[0][rz] * t.nk[1][ry] * t.nk[2][rx], 4);
       }
   if (soff) soff[f] = (unsigned short)total;
   return total;
@@ -361,20 +365,33 @@ int tr_steps(const TrPlan& t, int cib, unsigned short* soff) {
 // candidates carry the phase slots of a pass (2 .. 16, whole rows of last-axis phases) times the position tiles per wave
 // (<= 16 together); and the cycle estimate counts the MFMAs over the live steps of all phases and the staging once per
 // pass.  The constants are plan()'s, inherited: none of them is measured for this kernel.
-int plan_tr(const fc_desc& c, int cus, TrPlan& t) {
+//
+// `h16`: the planner of conv_direct_tr_h16_kernel (plan_tr_h16).  The input-channel blocks are whole cells of 8 channels
+// and a column is (cell, tap); the steps of a whole block are capped at kTrH16MaxSteps = 64, those of a pass being what
+// a thread carries to the next block (a block of one cell may have more, up to (128 + 3 * 64) / 4 = 80, but a pass of at
+// most 16 phases of it no more than (128 + 3 * 16) / 4 = 44); the LDS is plan_h16's, 16-byte cells at kH16WPitch, with
+// cwl.  Same candidates, same refusals, float32 tensors besides.  The cycle estimate is unchanged, 32 cycles per MFMA
+// among its constants, as plan_h16 keeps plan()'s: none of them is measured for this kernel either.
+int plan_tr(const fc_desc& c, int cus, TrPlan& t, bool h16 = false) {
   static_assert(kCdMaxCols == 512 && kCdtMaxStride == 8 && kCdtMaxPhases == 64, "the text below");
+  static_assert(kTrH16MaxSteps == 64 && kH16Cell == 8, "the text above and below");
   Geom& g = t.g;
-  if (int st = validate(c, cus, "fc_conv_direct_tr", "a block of 512 columns holds whole input channels", g, true)) return st;
+  const char* who = h16 ? "fc_conv_direct_tr_h16" : "fc_conv_direct_tr";
+  if (h16 && (c.dtype == FC_F32 || c.dtype == FC_F64 || c.dtype == FC_C64))
+    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr_h16 takes float16 or bfloat16 tensors (no %s)",
+                c.dtype == FC_F32 ? "float32: fc_conv_direct_tr covers it" : c.dtype == FC_F64 ? "float64" : "complex64");
+  if (int st = validate(c, cus, who, h16 ? "a block of 256 columns holds whole cells of 8 input channels"
+                                         : "a block of 512 columns holds whole input channels", g, true)) return st;
   if (!c.transposed || (g.stride[0] == 1 && g.stride[1] == 1 && g.stride[2] == 1))
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr runs transposed convolutions with a stride above 1 on some axis (this one "
-                "is %s: fc_conv_direct covers it)", c.transposed ? "at stride 1" : "not transposed");
+    return fail(FC_ERR_UNSUPPORTED, "%s runs transposed convolutions with a stride above 1 on some axis (this one "
+                "is %s: fc_conv_direct covers it)", who, c.transposed ? "at stride 1" : "not transposed");
   t.phases = g.stride[0] * g.stride[1] * g.stride[2];
   if (t.phases > kCdtMaxPhases)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr covers at most %d phases (the product of the strides; got %d)", kCdtMaxPhases,
+    return fail(FC_ERR_UNSUPPORTED, "%s covers at most %d phases (the product of the strides; got %d)", who, kCdtMaxPhases,
                 t.phases);
   if (g.Cog == 1 && g.Cig <= kDepthwiseMaxMultiplier)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr does not run depthwise layers (a weight with one input channel per group and "
-                "%d output channels per group), as fc_conv_direct; they keep the FFT plan", g.Cig);
+    return fail(FC_ERR_UNSUPPORTED, "%s does not run depthwise layers (a weight with one input channel per group and "
+                "%d output channels per group), as fc_conv_direct; they keep the FFT plan", who, g.Cig);
   g.nob = (int)cdiv(g.Cog, kCdRows);
   for (int a = 0; a < 3; ++a) {
     const int s = g.stride[a], d = g.dil[a], k = g.k[a];
@@ -395,15 +412,17 @@ int plan_tr(const fc_desc& c, int cus, TrPlan& t) {
 
   double best = -1.0;
   bool best_shared = false;
-  int cibmax = std::min<int>(g.Cig, kCdMaxCols / g.taps);
-  while (cibmax > 1 && 4 * tr_steps(t, cibmax, nullptr) > kCdMaxCols) --cibmax;      // (one channel: at most 128 + 3 * 64 columns)
+  // in units of a column's channels: one, or a cell of 8 (a ragged last cell counts whole)
+  const int unit = h16 ? kH16Cell : 1, ncu = (int)cdiv(g.Cig, unit), maxsteps = h16 ? kTrH16MaxSteps : kCdMaxCols / 4;
+  int cumax = std::min<int>(ncu, std::max(1, 4 * maxsteps / g.taps));
+  while (cumax > 1 && tr_steps(t, cumax, nullptr) > maxsteps) --cumax;      // (one channel: at most 128 + 3 * 64 columns)
   const int sx = g.stride[2], rows = t.phases / sx;
-  int last_cib = 0, tried = 0;
-  for (int n = (int)cdiv(g.Cig, cibmax); n <= g.Cig && tried < 8; ++n) {
-    const int cib = (int)cdiv(g.Cig, n);
-    if (cib == last_cib) continue;
-    last_cib = cib; ++tried;
-    const int nib = (int)cdiv(g.Cig, cib), steps = tr_steps(t, cib, nullptr);
+  int last_cu = 0, tried = 0;
+  for (int n = (int)cdiv(ncu, cumax); n <= ncu && tried < 8; ++n) {
+    const int cu = (int)cdiv(ncu, n);
+    if (cu == last_cu) continue;
+    last_cu = cu; ++tried;
+    const int cib = cu * unit, nib = (int)cdiv(g.Cig, cib), steps = tr_steps(t, cu, nullptr);
     for (int ph = 2; ph <= 16; ph *= 2) {
       if (ph < sx || (ph > 2 && ph / 2 >= sx && ph / 2 / sx >= rows)) continue;      // (no whole row; the slots of a smaller build)
       const int ppp = std::min(ph / sx, rows) * sx, npass = (int)cdiv(t.phases, ppp);
@@ -425,11 +444,12 @@ int plan_tr(const fc_desc& c, int cus, TrPlan& t) {
               if (hv > kLdsBudget) break;
             }
             if (hv > kLdsBudget) continue;
-            const int64_t lds = 4 * ((int64_t)steps * (kCdWPitch + 8) + cib * hv);      // wl, cbl and cwl, xl
+            const int64_t lds = h16 ? 16 * ((int64_t)steps * (kH16WPitch + 2) + cu * hv)      // wl, cbl and cwl (4 ints a step each), xl
+                                    : 4 * ((int64_t)steps * (kCdWPitch + 8) + cib * hv);
             if (lds > kLdsBudget) continue;
             const bool shared = lds <= kLdsShared && ph * npt < kCdMaxPT;
             if (best_shared && !shared) continue;
-            const double staged = nib > 1 ? (double)npass * cib * (double)hv : cib * (double)hv;
+            const double staged = nib > 1 ? (double)npass * cib * (double)hv : cib * (double)hv;      // (h16: a load per channel too)
             const double cost = (double)nib * (double)ntiles * (32.0 * steps * npt + 3000.0 * npass + 0.5 * (staged + 64.0 * steps));
             if (best < 0 || (shared && !best_shared) || cost < best) {
               best = cost; best_shared = shared;
@@ -441,16 +461,18 @@ int plan_tr(const fc_desc& c, int cus, TrPlan& t) {
     }
   }
   if (best < 0)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: the x samples that one base position reaches through every tap do not fit "
-                "%lld bytes of LDS", (long long)kLdsBudget);
-  tr_steps(t, g.cib, t.soff);
+    return fail(FC_ERR_UNSUPPORTED, "%s: the x samples that one base position reaches through every tap%s do not fit "
+                "%lld bytes of LDS", who, h16 ? " (of a cell of 8 channels)" : "", (long long)kLdsBudget);
+  tr_steps(t, g.cib / unit, t.soff);
   g.units = c.batch * g.ntile[0] * g.ntile[1] * g.ntile[2];
   if (g.units >= ((int64_t)1 << 31))
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: %lld (batch item, tile) units exceed 2^31", (long long)g.units);
+    return fail(FC_ERR_UNSUPPORTED, "%s: %lld (batch item, tile) units exceed 2^31", who, (long long)g.units);
   if (g.units * c.groups * g.nob > 0x7fffffffLL)
-    return fail(FC_ERR_UNSUPPORTED, "fc_conv_direct_tr: %lld workgroups exceed the 2^31 of one launch", (long long)(g.units * c.groups * g.nob));
+    return fail(FC_ERR_UNSUPPORTED, "%s: %lld workgroups exceed the 2^31 of one launch", who, (long long)(g.units * c.groups * g.nob));
   return FC_OK;
 }
+
+int plan_tr_h16(const fc_desc& c, int cus, TrPlan& t) { return plan_tr(c, cus, t, true); }
 
 // The kernel arguments of a plan()- or plan_h16()-planned launch (conv_direct_kernel and conv_direct_h16_kernel share the struct)
 ConvDirectArgs direct_args(const fc_desc& c, const Geom& g, const void* x, const void* weight, const void* bias, void* y) {
@@ -467,6 +489,29 @@ ConvDirectArgs direct_args(const fc_desc& c, const Geom& g, const void* x, const
   a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
   a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
   a.io = c.dtype; a.transposed = c.transposed ? 1 : 0;
+  return a;
+}
+
+// The kernel arguments of a plan_tr()- or plan_tr_h16()-planned launch (the two kernels share the struct)
+ConvDirectTrArgs tr_args(const fc_desc& c, const TrPlan& t, const void* x, const void* weight, const void* bias, void* y) {
+  const Geom& g = t.g;
+  ConvDirectTrArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.w = weight; a.bias = bias; a.y = y;
+  for (int i = 0; i < 3; ++i) {
+    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.up[i] = g.stride[i]; a.pad[i] = g.pad[i];
+    a.qlo[i] = t.qlo[i]; a.Q[i] = t.Q[i]; a.M[i] = t.M[i];
+    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
+    a.kstep[i] = t.kstep[i]; a.mstep[i] = t.mstep[i];
+  }
+  std::memcpy(a.k0, t.k0, sizeof a.k0); std::memcpy(a.nk, t.nk, sizeof a.nk); std::memcpy(a.m0, t.m0, sizeof a.m0);
+  std::memcpy(a.soff, t.soff, sizeof a.soff);
+  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
+  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
+  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
+  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
+  a.phases = t.phases; a.ppp = t.ppp; a.npass = t.npass;
+  a.io = c.dtype;
   return a;
 }
 
@@ -593,26 +638,36 @@ extern "C" int fc_conv_direct_tr(const fc_desc* desc, const void* x, const void*
     if (int st = plan_tr(*desc, cus, last.t)) return st;
     last.d = *desc; last.cus = cus; last.set = true;
   }
-  const TrPlan& t = last.t;
-  const Geom& g = t.g;
-  const fc_desc& c = *desc;
-  ConvDirectTrArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x = x; a.w = weight; a.bias = bias; a.y = y;
-  for (int i = 0; i < 3; ++i) {
-    a.S[i] = g.S[i]; a.O[i] = g.O[i]; a.k[i] = g.k[i]; a.up[i] = g.stride[i]; a.pad[i] = g.pad[i];
-    a.qlo[i] = t.qlo[i]; a.Q[i] = t.Q[i]; a.M[i] = t.M[i];
-    a.tile[i] = g.tile[i]; a.ntile[i] = g.ntile[i]; a.halo[i] = g.halo[i];
-    a.kstep[i] = t.kstep[i]; a.mstep[i] = t.mstep[i];
+  const ConvDirectTrArgs a = tr_args(*desc, last.t, x, weight, bias, y);
+  FC_HIP(conv_direct_tr_launch(a, last.t.ph, last.t.g.npt, last.t.g.units * desc->groups * last.t.g.nob, (size_t)last.t.g.lds,
+                               static_cast<hipStream_t>(hip_stream)));
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_tr_h16_geometry(const fc_desc* desc, int compute_units, int64_t info[8]) {
+  if (!desc || !info) return fail(FC_ERR_INVALID, "null argument");
+  TrPlan t;
+  if (int st = plan_tr_h16(*desc, compute_units, t)) return st;
+  for (int i = 0; i < 3; ++i) info[i] = i < desc->ndim ? t.g.tile[t.g.ax0 + i] : 0;
+  info[3] = t.phases; info[4] = t.ppp; info[5] = t.g.cib; info[6] = t.g.nib; info[7] = t.g.lds;
+  return FC_OK;
+}
+
+extern "C" int fc_conv_direct_tr_h16(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream) {
+  if (!desc || !x || !weight || !y) return fail(FC_ERR_INVALID, "null argument");
+  (void)hipGetLastError();   // (as fc_forward: a stale sticky error of an earlier call is not this call's)
+  int cus = 0;
+  if (!current_device_cus(&cus) || cus < 1) return fail(FC_ERR_HIP, "the CU count of the current device is not available");
+  // the plan of the last call of this thread, while descriptor and CU count are what they were
+  struct Last { fc_desc d; int cus; TrPlan t; bool set; };
+  static thread_local Last last = {};
+  if (!last.set || std::memcmp(&last.d, desc, sizeof(fc_desc)) || last.cus != cus) {
+    last.set = false;
+    if (int st = plan_tr_h16(*desc, cus, last.t)) return st;
+    last.d = *desc; last.cus = cus; last.set = true;
   }
-  std::memcpy(a.k0, t.k0, sizeof a.k0); std::memcpy(a.nk, t.nk, sizeof a.nk); std::memcpy(a.m0, t.m0, sizeof a.m0);
-  std::memcpy(a.soff, t.soff, sizeof a.soff);
-  a.fd_tx = make_fastdiv(g.tile[2]); a.fd_ty = make_fastdiv(g.tile[1]);
-  a.fd_hx = make_fastdiv(g.halo[2]); a.fd_hy = make_fastdiv(g.halo[1]);
-  a.Cin = (int)c.in_channels; a.Cout = (int)c.out_channels; a.Cig = g.Cig; a.Cog = g.Cog; a.G = (int)c.groups; a.taps = g.taps;
-  a.cib = g.cib; a.nib = g.nib; a.nob = g.nob; a.P = g.P; a.steps = g.steps;
-  a.phases = t.phases; a.ppp = t.ppp; a.npass = t.npass;
-  a.io = c.dtype;
-  FC_HIP(conv_direct_tr_launch(a, t.ph, g.npt, g.units * c.groups * g.nob, (size_t)g.lds, static_cast<hipStream_t>(hip_stream)));
+  const ConvDirectTrArgs a = tr_args(*desc, last.t, x, weight, bias, y);
+  FC_HIP(conv_direct_tr_h16_launch(a, last.t.ph, last.t.g.npt, last.t.g.units * desc->groups * last.t.g.nob, (size_t)last.t.g.lds,
+                                   static_cast<hipStream_t>(hip_stream)));
   return FC_OK;
 }

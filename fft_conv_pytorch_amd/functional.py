@@ -400,7 +400,9 @@ def _direct_dw_on() -> bool:
 def _direct_body() -> str:
     """FFTCONV_DIRECT_BODY (read per call): "h16" takes the float16 / bfloat16 calls of FFTCONV_DIRECT=1 that
     ``fc_conv_direct_h16`` covers from the 16-bit matrix instructions (csrc/conv_direct_h16.hpp; route
-    "direct-h16"); unset, "f32" or anything else leaves every call the call it is without the variable.  Opt-in: the
+    "direct-h16"), and the float16 / bfloat16 calls of FFTCONV_DIRECT_TR=1 that ``fc_conv_direct_tr_h16`` covers likewise
+    (csrc/conv_direct_tr_h16.hpp; route "direct-tr-h16"); unset, "f32" or anything else leaves every call
+    the call it is without the variable.  Opt-in: the
     float32 sums run in another order, so the last bit of a 16-bit y or dX may change."""
     return "h16" if os.environ.get("FFTCONV_DIRECT_BODY", "f32") == "h16" else "f32"
 
@@ -408,7 +410,8 @@ def _direct_body() -> str:
 def _direct_tr_on() -> bool:
     """FFTCONV_DIRECT_TR (read per call, independent of the other direct switches): "1" takes transposed 2-D / 3-D calls
     with a stride above 1 -- ``fft_conv_transpose`` at stride >= 2 and the dX of strided zero-padded layers -- from
-    ``fc_conv_direct_tr`` (csrc/conv_direct_tr.hpp; route "direct-tr") where it covers them.  Opt-in: the
+    ``fc_conv_direct_tr`` (csrc/conv_direct_tr.hpp; route "direct-tr") where it covers them; 16-bit tensors
+    under FFTCONV_DIRECT_BODY=h16 from ``fc_conv_direct_tr_h16`` (route "direct-tr-h16").  Opt-in: the
     bits of y and dX change."""
     return os.environ.get("FFTCONV_DIRECT_TR", "0") == "1"
 
@@ -430,7 +433,8 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
                      output_padding=None, dw=False):
     """(descriptor, geometry words, shape of y, launch, route name) of ``fc_conv_direct`` (``dw``: of ``fc_conv_direct_dw``,
     or ``dw == "tr"``: of ``fc_conv_direct_tr``;
-    16-bit tensors under FFTCONV_DIRECT_BODY=h16: of ``fc_conv_direct_h16`` where it covers the layer) for a signal
+    16-bit tensors under FFTCONV_DIRECT_BODY=h16: of ``fc_conv_direct_h16``, or ``dw == "tr"``: of
+    ``fc_conv_direct_tr_h16``, where it covers the layer) for a signal
     of ``shape`` on ``device``, None where the
     library refuses the layer (1-D, float64, complex64, more than 128 taps, depthwise, a strided transposed layer, ...) or
     the arguments do not describe a layer.  Arithmetic only: ``fc_conv_direct_geometry`` touches no device; the CU count is
@@ -455,7 +459,7 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
     if cus is None:
         cus = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
         _DEVICE_CUS[device] = cus
-    body = _direct_body() if not dw and dtype in _LOW_PRECISION else "f32"
+    body = _direct_body() if (not dw or dw == "tr") and dtype in _LOW_PRECISION else "f32"
     key = (tuple(shape), tuple(wshape), stride, padding, dilation, groups, padding_mode, bool(transposed), output_padding,
            device, dtype, cus, dw if dw == "tr" else bool(dw), body)
     hit = _DIRECT_GEOMETRY.get(key)
@@ -470,11 +474,15 @@ def _direct_geometry(shape, dtype, device, wshape, stride, padding, dilation, gr
             geom = None
             if body == "h16":
                 try:
-                    geom = _native.conv_direct_h16_geometry(desc, cus)
-                    name, launch = "direct-h16", _native.conv_direct_h16
+                    if dw == "tr":
+                        geom = _native.conv_direct_tr_h16_geometry(desc, cus)
+                        name, launch = "direct-tr-h16", _native.conv_direct_tr_h16
+                    else:
+                        geom = _native.conv_direct_h16_geometry(desc, cus)
+                        name, launch = "direct-h16", _native.conv_direct_h16
                 except NotImplementedError:
                     pass      # (the float32 body takes what it covers, as without the variable)
-            if dw == "tr":
+            if geom is None and dw == "tr":
                 geom = _native.conv_direct_tr_geometry(desc, cus)
                 name, launch = "direct-tr", _native.conv_direct_tr
             elif geom is None:
@@ -529,7 +537,7 @@ def _direct_hit(transposed: bool, signal, kernel, bias, stride, padding, output_
 
 
 def _direct_run(hit, signal: Tensor, kernel: Tensor, bias: Optional[Tensor]) -> Tensor:
-    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` / ``fc_conv_direct_h16`` / ``fc_conv_direct_tr`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
+    """One ``fc_conv_direct`` / ``fc_conv_direct_dw`` / ``fc_conv_direct_h16`` / ``fc_conv_direct_tr`` / ``fc_conv_direct_tr_h16`` launch of a ``_direct_hit``: the weight is read where it lies, no plan,
     no spectrum."""
     desc, _, shape, launch, _ = hit
     signal, kernel = signal.detach(), kernel.detach().contiguous()
@@ -547,7 +555,8 @@ def conv_route(signal: Tensor, kernel_shape, stride=1, padding=0, dilation=1, gr
     kernel of ``kernel_shape`` of its dtype: ``"direct"`` (FFTCONV_DIRECT=1 and a call ``fc_conv_direct`` covers),
     ``"direct-h16"`` (the same under FFTCONV_DIRECT_BODY=h16, 16-bit tensors and a call ``fc_conv_direct_h16`` covers),
     ``"direct-dw"`` (FFTCONV_DIRECT_DW=1 and a call ``fc_conv_direct_dw`` covers), ``"direct-tr"`` (FFTCONV_DIRECT_TR=1 and a
-    strided transposed call ``fc_conv_direct_tr`` covers) or ``"fft"``.  Arithmetic only: launches nothing, creates no plan."""
+    strided transposed call ``fc_conv_direct_tr`` covers), ``"direct-tr-h16"`` (the same under FFTCONV_DIRECT_BODY=h16,
+    16-bit tensors and a call ``fc_conv_direct_tr_h16`` covers) or ``"fft"``.  Arithmetic only: launches nothing, creates no plan."""
     if not (_direct_on() or _direct_dw_on() or _direct_tr_on()) or channels_last or isinstance(padding, str) or signal.ndim not in (4, 5) or not signal.is_contiguous():
         return "fft"
     if signal.dtype in _LOW_PRECISION and os.environ.get("FFTCONV_HALF_IO", "1") == "0":

@@ -297,6 +297,21 @@ int fc_conv_direct_h16(const fc_desc* desc, const void* x, const void* weight, c
 int fc_conv_direct_tr_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
 int fc_conv_direct_tr(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
 
+/* Direct strided transposed convolution on the 16-bit matrix instructions (ABI 7 extension: two new entry points): the sum
+ * of fc_conv_direct_tr for FC_F16 / FC_BF16 tensors on v_mfma_f32_16x16x32_f16 / _bf16, by the same output phases.  Nothing
+ * is widened: the products of two 16-bit values are exact in the float32 accumulator, so y is the float32 sum of
+ * fc_conv_direct_tr's products in another order, rounded once.  Operands and the guarantees (every sample of y written
+ * exactly once, phases without a tap included; nothing else written; equal calls give equal bits) are those of
+ * fc_conv_direct_tr.  A workgroup reduces blocks of whole cells of 8 input channels; the columns (cell, live tap) of a
+ * block, each phase padded to 4, make at most 64 MFMA steps of 32 products (a block of one cell: what it has).
+ *   FC_ERR_UNSUPPORTED with text: FC_F32 (fc_conv_direct_tr covers it) and every refusal of fc_conv_direct_tr; the halo
+ *   that must fit 160 KiB of LDS is that of one cell of 8 channels in 16 bits.
+ * fc_conv_direct_tr_h16_geometry is pure arithmetic: no device is touched.  info words as fc_conv_direct_tr_geometry's;
+ * the input channels per block are a multiple of 8 (the last cell of a group may be ragged).
+ * fc_conv_direct_tr_h16 plans for the CURRENT device and launches once on hip_stream.  Asynchronous; allocates nothing. */
+int fc_conv_direct_tr_h16_geometry(const fc_desc* desc, int compute_units, int64_t info[8]);
+int fc_conv_direct_tr_h16(const fc_desc* desc, const void* x, const void* weight, const void* bias, void* y, void* hip_stream);
+
 /* Profiling variant of fc_forward (not part of the drop-in surface; the plan stays immutable; a float32 2-D / 3-D plan
  * that runs its kernel in segments of taps has no stamped forward: FC_ERR_UNSUPPORTED when stamps is not NULL):
  * `stamps` is a device buffer of 16 * fc_debug_grid(plan) uint64 in which lane 0 of the waves of the

@@ -17,12 +17,16 @@ gives the read-once byte roofline of forward and dX, (bytes of x + bytes of y) /
 ``--tr`` times ``fc_conv_direct_tr`` (FFTCONV_DIRECT_TR): the dX of the strided dense shape in float32 and
 bfloat16 and the forward of ``fft_conv_transpose`` on four up-convolutions, ``d_torch`` being ``conv_transpose2d/3d``.
 
+``--tr-h16`` times ``fc_conv_direct_tr_h16`` on the five shapes of ``--tr`` in bfloat16 and the k4 s2 p1
+up-convolution in float16 too:  a_set  FFTCONV_DIRECT_TR=1 FFTCONV_DIRECT_BODY=h16,  a1_f32body  FFTCONV_DIRECT_TR=1 alone
+(``fc_conv_direct_tr`` on the same tensors),  b_unset  and  d_torch.
+
 The method is that of scripts/wgrad_direct_bench.py (its ``capture`` and ``timed``): every call is captured into a HIP
 graph over rotating buffers that move 600 MiB through a replay, the graphs of a shape are replayed in turn, ``--iters``
 replays in each of ``--rounds`` alternating rounds; reported are the median over all replays per call, the medians of the
 rounds and their spread.  One JSON line per shape is appended to --out.
 
-    python scripts/conv_direct_bench.py [--dense | --h16 | --tr] [--iters 20] [--rounds 3] [--out FILE] [--only SUBSTRING]
+    python scripts/conv_direct_bench.py [--dense | --h16 | --tr | --tr-h16] [--iters 20] [--rounds 3] [--out FILE] [--only SUBSTRING]
                                         [--baseline [--root PARENT_CHECKOUT]]"""
 import argparse
 import importlib
@@ -59,10 +63,12 @@ TR = [
     ("convT 2-D B8 32->16 128^2 k3 s2 p1 op1", "fwd", 8, 32, 16, (128, 128), 3, 2, 1, 1, F32),
     ("convT 3-D B2 32->16 32^3 k2 s2", "fwd", 2, 32, 16, (32, 32, 32), 2, 2, 0, 0, F32),
 ]
+TR_H16 = [s[:-1] + (torch.bfloat16,) for s in TR[1:]] + [TR[2][:-1] + (torch.float16,)]
 
 
-def run_tr_shape(fca, name, what, B, ci, co, size, k, s, p, op, dtype, iters, rounds):
-    """One row of --tr: a_set (FFTCONV_DIRECT_TR=1), b_unset and d_torch of one call, timed as run_shape times its calls."""
+def run_tr_shape(fca, name, what, B, ci, co, size, k, s, p, op, dtype, iters, rounds, h16=False):
+    """One row of --tr: a_set (FFTCONV_DIRECT_TR=1), b_unset and d_torch of one call, timed as run_shape times its calls.
+    ``h16`` (--tr-h16): a_set has FFTCONV_DIRECT_BODY=h16 too, a1_f32body is FFTCONV_DIRECT_TR=1 alone."""
     torch.manual_seed(0)
     nd = len(size)
     auto = importlib.import_module(fca.__name__ + ".autograd")
@@ -91,13 +97,12 @@ def run_tr_shape(fca, name, what, B, ci, co, size, k, s, p, op, dtype, iters, ro
                 return [auto._grad_input(t, w, size, *conf) for t in srcs]
             return [fun.fft_conv_transpose(t, w, None, stride=s, padding=p, output_padding=op) for t in srcs]
 
-    def under(value):
+    def under(env, fn=ours):
         def step():
             for var in KNOBS:
                 os.environ.pop(var, None)
-            if value:
-                os.environ["FFTCONV_DIRECT_TR"] = value
-            return ours()
+            os.environ.update(env)
+            return fn()
         return step
 
     def route():
@@ -105,13 +110,14 @@ def run_tr_shape(fca, name, what, B, ci, co, size, k, s, p, op, dtype, iters, ro
             return auto.dx_route(torch.empty(dst, device=DEV, dtype=dtype), wshape, *conf)
         return fun.conv_route(srcs[0], wshape, s, p, transposed=True, output_padding=op)
 
-    steps = {"a_set": under("1"), "b_unset": under(None),
+    a_env = {"FFTCONV_DIRECT_TR": "1", "FFTCONV_DIRECT_BODY": "h16"} if h16 else {"FFTCONV_DIRECT_TR": "1"}
+    steps = {"a_set": under(a_env), **({"a1_f32body": under({"FFTCONV_DIRECT_TR": "1"})} if h16 else {}), "b_unset": under({}),
              "d_torch": (lambda: [tdx(dst, w, t, s, p, 1, 1) for t in srcs]) if what == "dx" else
                         (lambda: [tconvt(t, w, None, s, p, op) for t in srcs])}
-    os.environ["FFTCONV_DIRECT_TR"] = "1"
-    row["a_set_route"] = route()
-    os.environ.pop("FFTCONV_DIRECT_TR")
-    row["b_unset_route"] = route()
+    row["a_set_route"] = under(a_env, route)()
+    if h16:
+        row["a1_f32body_route"] = under({"FFTCONV_DIRECT_TR": "1"}, route)()
+    row["b_unset_route"] = under({}, route)()
     graphs = {}
     for key, fn in steps.items():
         try:
@@ -136,6 +142,8 @@ def run_tr_shape(fca, name, what, B, ci, co, size, k, s, p, op, dtype, iters, ro
     if row.get("a_set_us") and row.get("b_unset_us"):
         row["b_over_a"] = round(row["b_unset_us"] / row["a_set_us"], 2)
         row["a_roofline_fraction"] = round(row["roofline_us"] / row["a_set_us"], 3)
+    if row.get("a_set_us") and row.get("a1_f32body_us"):
+        row["a1_over_a"] = round(row["a1_f32body_us"] / row["a_set_us"], 2)
     for var in KNOBS:
         os.environ.pop(var, None)
     return row
@@ -236,14 +244,15 @@ if __name__ == "__main__":
     ap.add_argument("--dense", action="store_true", help="fc_conv_direct under FFTCONV_DIRECT on the shapes of DESIGN 4.5d")
     ap.add_argument("--h16", action="store_true", help="fc_conv_direct_h16 against fc_conv_direct on 16-bit tensors (DESIGN 4.5f)")
     ap.add_argument("--tr", action="store_true", help="fc_conv_direct_tr under FFTCONV_DIRECT_TR on strided transposed calls (DESIGN 4.5h)")
+    ap.add_argument("--tr-h16", action="store_true", help="fc_conv_direct_tr_h16 against fc_conv_direct_tr on 16-bit tensors (DESIGN 4.5i)")
     ap.add_argument("--out", default=None, help="default: profiles/conv_direct_dw.jsonl, --dense: conv_direct.jsonl, --h16: conv_direct_h16.jsonl, "
-                    "--tr: conv_direct_tr.jsonl")
+                    "--tr: conv_direct_tr.jsonl, --tr-h16: conv_direct_tr_h16.jsonl")
     ap.add_argument("--only", default=None)
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose fft_conv_pytorch_amd package is timed (default: this tree)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join("profiles", "conv_direct_tr.jsonl" if a.tr else "conv_direct_h16.jsonl" if a.h16 else "conv_direct.jsonl" if a.dense else "conv_direct_dw.jsonl")
+    a.out = a.out or os.path.join("profiles", "conv_direct_tr_h16.jsonl" if a.tr_h16 else "conv_direct_tr.jsonl" if a.tr else "conv_direct_h16.jsonl" if a.h16 else "conv_direct.jsonl" if a.dense else "conv_direct_dw.jsonl")
     knob = "FFTCONV_DIRECT_DW" if not (a.dense or a.h16) else "FFTCONV_DIRECT"
     variants = {"c_parent": {}} if a.baseline else {"a_set": {knob: "1"}, "b_unset": {}}
     if a.h16:
@@ -251,10 +260,10 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.abspath(a.root))
     import fft_conv_pytorch_amd as fca
     assert os.path.abspath(fca.__file__).startswith(os.path.abspath(a.root)), fca.__file__
-    for shape in (TR if a.tr else H16 if a.h16 else DENSE if a.dense else DW):
+    for shape in (TR_H16 if a.tr_h16 else TR if a.tr else H16 if a.h16 else DENSE if a.dense else DW):
         if a.only and a.only not in shape[0]:
             continue
-        res = run_tr_shape(fca, *shape, a.iters, a.rounds) if a.tr else run_shape(fca, variants, ("fwd", "dx") if a.h16 else ("fwd", "dx", "step"), *shape, a.iters, a.rounds, a.baseline)
+        res = run_tr_shape(fca, *shape, a.iters, a.rounds, a.tr_h16) if a.tr or a.tr_h16 else run_shape(fca, variants, ("fwd", "dx") if a.h16 else ("fwd", "dx", "step"), *shape, a.iters, a.rounds, a.baseline)
         line = json.dumps(res)
         print(line, flush=True)
         with open(a.out, "a") as f:

@@ -3,7 +3,7 @@
 
 For every object of the native library that holds kernels (the 7 tile objects, the 7 long-filter objects,
 fft_f64, nd_f64, direct_f64, long_f64, long_step, wgrad_direct, conv_direct, conv_direct_dw, conv_direct_h16,
-wgrad_direct_h16, conv_direct_tr) the device side of both trees is
+wgrad_direct_h16, conv_direct_tr, conv_direct_tr_h16) the device side of both trees is
 compiled to assembly text with the flags of csrc/Makefile (`hipcc ... --cuda-device-only -S`).  An object whose
 source file one tree does not have counts as having no kernels there: its kernels are listed as only in the other
 tree.  The kernels of the two sides are put in one-to-one
@@ -54,8 +54,9 @@ def objects():
         objs.append(("long_" + t, "long_inst.hip", ["-DFC_P=" + p, "-DFC_S=" + s]))
     for n in ("fft_f64", "nd_f64", "direct_f64", "long_f64", "long_step"):
         objs.append((n, n + ".hip", []))
-    # (the two direct weight gradients and the four direct forwards, with the flags of their rules in csrc/Makefile)
-    for n in ("wgrad_direct", "conv_direct", "conv_direct_dw", "conv_direct_h16", "wgrad_direct_h16", "conv_direct_tr"):
+    # (the two direct weight gradients and the five direct forwards, with the flags of their rules in csrc/Makefile)
+    for n in ("wgrad_direct", "conv_direct", "conv_direct_dw", "conv_direct_h16", "wgrad_direct_h16", "conv_direct_tr",
+              "conv_direct_tr_h16"):
         objs.append((n, n + ".hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     return objs
 
